@@ -13,12 +13,15 @@ step     N=1: all kernels of the field, its transfer WRITING the field's dose bo
          field, in field order, into its own slab of the dose volume (plan.BevExchange). The plan's volume is left sharded by
          slabs across the GPUs; it is bit-identical to the sequential one-GPU accumulation of the N fields.
 
-One JSON line on rank 0; `roofline` describes the dominant kernel (kernel superposition) from the kernels' own dispatch
-timestamps taken by the engine on the launch stream during the timed steps; `cpu_baseline` is the CPU oracle timed on this host.
-Also reported: `ms_plan_latency` (ONE plan, nothing to pipeline against) and, at N=1, `ms_plan_end_to_end` (the reference's
-"total global execution time": CT + LUT upload, dose up, all kernels, dose down, from page-locked host buffers).
+One JSON line on rank 0. A plain run sets up, warms up, times the K steps and prints the headline: `value`, `ms_per_step`, the
+per-stage device times of the timed steps (`stage_ms`) and the workload (`config`). With --dump-outputs DIR it first writes what
+the last timed step computed (dump_outputs). Everything else runs with --full only: `roofline` describes the dominant kernel
+(kernel superposition) from the kernels' own dispatch timestamps taken by the engine on the launch stream during the timed steps;
+`cpu_baseline` is the CPU oracle timed on this host. Also reported: `ms_plan_latency` (ONE plan, nothing to pipeline against),
+the secondary multi-stream leg, the self-checks, the parity against the CPU oracle and, at N=1, `ms_plan_end_to_end` (the
+reference's "total global execution time": CT + LUT upload, dose up, all kernels, dose down, from page-locked host buffers).
 
-Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--size 512] [--no-cpu]
+Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--size 512] [--dump-outputs DIR] [--full [--no-cpu] [--no-secondary]]
        N>1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
             or plain `python bench.py --gpus N ...`, which starts exactly that launcher as a child process and relays its output
 """
@@ -62,6 +65,32 @@ def algorithmic_bytes(info, dims, ct_footprint):
     return out
 
 
+DUMP_SAMPLE = 1 << 22        # voxels drawn (with repeats, which are dropped) for dose_sample.npy
+DUMP_SEED = 2024
+
+
+def dump_outputs(out_dir, vol, dist=None, backend="nccl", rank=0):
+    """Write the dose volume of the last timed step as float32 .npy files in out_dir (~20 MB at 512^3): `dose_sample`, the voxels at
+    a fixed seeded set of flat indices (ascending; the same set for the same --size), and the three central planes `dose_mid_z`,
+    `dose_mid_y`, `dose_mid_x` (the volume is indexed [z][y][x]). N>1: each rank's volume is zero outside its slab, so a sum over the
+    ranks (x + 0 = x exactly) assembles the plan's volume; rank 0 writes."""
+    import torch
+    n = vol.shape[0]
+    idx = np.unique(np.random.default_rng(DUMP_SEED).integers(0, vol.numel(), size=DUMP_SAMPLE, dtype=np.int64))
+    parts = {"dose_sample": vol.reshape(-1)[torch.from_numpy(idx).to(vol.device)], "dose_mid_z": vol[n // 2], "dose_mid_y": vol[:, n // 2],
+             "dose_mid_x": vol[:, :, n // 2]}
+    for k, t in parts.items():
+        t = t.clone(memory_format=torch.contiguous_format)       # a copy: the planes are views of the volume, the reduce works in place
+        if dist is not None:
+            t = t if backend == "nccl" else t.cpu()
+            dist.reduce(t, dst=0, op=dist.ReduceOp.SUM)
+        parts[k] = t
+    if rank == 0:
+        os.makedirs(out_dir, exist_ok=True)
+        for k, t in parts.items():
+            np.save(os.path.join(out_dir, k + ".npy"), t.cpu().numpy().astype(np.float32, copy=False))
+
+
 def cpu_model():
     try:
         for ln in open("/proc/cpuinfo"):
@@ -78,14 +107,21 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--size", type=int, default=512, help="CT edge in voxels (512 = C3/C4, 768 = C5)")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline / parity / end-to-end legs")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also everything else the benchmark measures and checks: single-plan latency, the secondary "
+                         "multi-stream leg, the self-checks, roofline and algorithmic bytes, CPU baseline, parity against the CPU oracle, "
+                         "end-to-end call (a plain run does only what the headline needs)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (a seeded sample and the central planes of the dose volume) as "
+                         "float32 .npy files into DIR")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: skip the cpu_baseline / parity / end-to-end legs")
     ap.add_argument("--cpu-threads", type=int, default=0)
     ap.add_argument("--streams", type=int, default=1,
                     help="N=1 only, not the default: launch consecutive plans round-robin on this many HIP streams, so the kernels of "
                          "independent plans overlap (throughput of a multi-field plan on one GPU; per-kernel durations in stage_ms / "
                          "roofline then include the sharing of the GPU)")
     ap.add_argument("--no-secondary", action="store_true",
-                    help="skip the secondary leg (throughput_streams: the same steps once more with consecutive plans on 4 HIP streams). "
+                    help="--full: skip the secondary leg (throughput_streams: the same steps once more with consecutive plans on 4 HIP streams). "
                          "profiles/collect.sh passes this: the leg's overlapped kernels would enter the per-kernel averages of a "
                          "`rocprofv3 --stats -- python bench.py` beside the timed single-stream loop, whose kernel durations are what `roofline` reports")
     ap.add_argument("--secondary", action="store_true", help=argparse.SUPPRESS)      # (accepted for older command lines: the default now)
@@ -286,28 +322,31 @@ def main():
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         elapsed = float(tmax.item())
     ms_per_step = 1000.0 * elapsed / args.steps
+    if args.dump_outputs:               # the last timed plan's volume (launch(): plan i writes doses[i % len(doses)])
+        dump_outputs(args.dump_outputs, doses[(step_no[0] - 1) % len(doses)], dist, args.backend, rank)
 
     # ---- latency of ONE plan: nothing to pipeline against (launch, finish, drained stream), mean of 5 ----
-    lat = []
-    for _ in range(5):
-        barrier()
-        l0 = time.perf_counter()
-        launch()
-        retire()
-        torch.cuda.synchronize()
-        lat.append(time.perf_counter() - l0)
-    ms_latency = 1000.0 * sum(lat) / len(lat)
-    if xchg:
-        tl = torch.tensor([ms_latency], dtype=torch.float64, device=dev)
-        dist.all_reduce(tl, op=dist.ReduceOp.MAX)
-        ms_latency = float(tl.item())
+    if args.full:
+        lat = []
+        for _ in range(5):
+            barrier()
+            l0 = time.perf_counter()
+            launch()
+            retire()
+            torch.cuda.synchronize()
+            lat.append(time.perf_counter() - l0)
+        ms_latency = 1000.0 * sum(lat) / len(lat)
+        if xchg:
+            tl = torch.tensor([ms_latency], dtype=torch.float64, device=dev)
+            dist.all_reduce(tl, op=dist.ReduceOp.MAX)
+            ms_latency = float(tl.item())
 
     # ---- secondary figure (N=1): throughput with consecutive plans on 4 HIP streams — independent plans (a plan's fields, or a queue
     #      of patients) overlap: the latency-bound launches of one (scan, plans, the tails of fill / superposition / transfer) run beside
     #      the issue-bound kernels of another. NOT the headline: `value`, stage_ms and the roofline come from the single-stream loop
     #      above, where a kernel's duration is that of the kernel alone and a step is one plan's latency chain. ----
     multi = None
-    if not xchg and n_streams == 1 and not args.no_secondary:
+    if args.full and not xchg and n_streams == 1 and not args.no_secondary:
         ns = max(2, args.secondary_streams)
         ss = [torch.cuda.Stream(device=dev) for _ in range(ns)]
         fl = [eng.create_field(beam, scn.dims) for _ in range(ns)]
@@ -341,77 +380,101 @@ def main():
             f.destroy()
         del vols
 
-    # ---- self-checks (untimed) ----
-    # (a) a volume restored by the dirty-box clears of launch() is bit-identical to the same plan computed into a fully zeroed volume
-    launch()
-    i_chk, f_chk = in_flight[0]
-    retire()
-    last = doses[i_chk % len(doses)]
-    ref = torch.zeros_like(last)
-    if ex is None:
-        fld2 = flds[(i_chk + 1) % len(flds)]
-        fld2.compute(ref.data_ptr())
-        fld2.finish()
-    else:
-        ex.complete(f_chk, i_chk % 2, ref.data_ptr())      # same gathered slabs, same field order, fresh volume
-        f_chk.finish()
-    torch.cuda.synchronize()
-    clear_ok = torch.tensor([1 if torch.equal(last, ref) else 0], dtype=torch.int64, device=dev)
-    if xchg:
-        dist.all_reduce(clear_ok, op=dist.ReduceOp.MIN)
-    clear_check = bool(int(clear_ok.item()))
-    # (b) N>1: the slabs of all ranks together hold the sum of all fields (each rank also transfers its own field unclipped)
-    reduce_check = None
-    if xchg:
-        slab_sum = last.sum(dtype=torch.float64).reshape(1)
-        ref.zero_()
-        f_chk.transfer(ref.data_ptr())
-        f_chk.finish()
-        torch.cuda.synchronize()
-        field_sum = ref.sum(dtype=torch.float64).reshape(1)
-        dist.all_reduce(slab_sum, op=dist.ReduceOp.SUM)
-        dist.all_reduce(field_sum, op=dist.ReduceOp.SUM)
-        reduce_check = abs(float(slab_sum.item()) - float(field_sum.item())) / max(float(field_sum.item()), 1e-300)
-    # (c) N>1: the plan's volume ASSEMBLED on rank 0 — every rank's volume is zero outside its slab, so a sum over the ranks
-    #     (x + 0 = x exactly) is the gather of the slabs — against the reference's sequential beam loop on one GPU
-    #     (kernel_wrapper.cu:601, `+=` at :92): all fields accumulated into one zeroed volume in field order. Bit for bit.
-    assembled_check = None
-    if xchg:
-        if args.backend == "nccl":
-            dist.reduce(last, dst=0, op=dist.ReduceOp.SUM)
-            assembled = last
+    # ---- self-checks (untimed, --full) ----
+    clear_check = reduce_check = assembled_check = None
+    if args.full:
+        # (a) a volume restored by the dirty-box clears of launch() is bit-identical to the same plan computed into a fully zeroed volume
+        launch()
+        i_chk, f_chk = in_flight[0]
+        retire()
+        last = doses[i_chk % len(doses)]
+        ref = torch.zeros_like(last)
+        if ex is None:
+            fld2 = flds[(i_chk + 1) % len(flds)]
+            fld2.compute(ref.data_ptr())
+            fld2.finish()
         else:
-            host_part = last.cpu()
-            dist.reduce(host_part, dst=0, op=dist.ReduceOp.SUM)
-            assembled = host_part.to(dev) if rank == 0 else None
-        if rank == 0:
+            ex.complete(f_chk, i_chk % 2, ref.data_ptr())      # same gathered slabs, same field order, fresh volume
+            f_chk.finish()
+        torch.cuda.synchronize()
+        clear_ok = torch.tensor([1 if torch.equal(last, ref) else 0], dtype=torch.int64, device=dev)
+        if xchg:
+            dist.all_reduce(clear_ok, op=dist.ReduceOp.MIN)
+        clear_check = bool(int(clear_ok.item()))
+        # (b) N>1: the slabs of all ranks together hold the sum of all fields (each rank also transfers its own field unclipped)
+        if xchg:
+            slab_sum = last.sum(dtype=torch.float64).reshape(1)
             ref.zero_()
-            for r in range(world):
-                fr = flds[0] if r == rank else eng.create_field(scn.beams[r], scn.dims)
-                fr.compute(ref.data_ptr())
-                fr.finish()
-                if r != rank:
-                    fr.destroy()
+            f_chk.transfer(ref.data_ptr())
+            f_chk.finish()
             torch.cuda.synchronize()
-            assembled_check = bool(torch.equal(assembled, ref))
+            field_sum = ref.sum(dtype=torch.float64).reshape(1)
+            dist.all_reduce(slab_sum, op=dist.ReduceOp.SUM)
+            dist.all_reduce(field_sum, op=dist.ReduceOp.SUM)
+            reduce_check = abs(float(slab_sum.item()) - float(field_sum.item())) / max(float(field_sum.item()), 1e-300)
+        # (c) N>1: the plan's volume ASSEMBLED on rank 0 — every rank's volume is zero outside its slab, so a sum over the ranks
+        #     (x + 0 = x exactly) is the gather of the slabs — against the reference's sequential beam loop on one GPU
+        #     (kernel_wrapper.cu:601, `+=` at :92): all fields accumulated into one zeroed volume in field order. Bit for bit.
+        if xchg:
+            if args.backend == "nccl":
+                dist.reduce(last, dst=0, op=dist.ReduceOp.SUM)
+                assembled = last
+            else:
+                host_part = last.cpu()
+                dist.reduce(host_part, dst=0, op=dist.ReduceOp.SUM)
+                assembled = host_part.to(dev) if rank == 0 else None
+            if rank == 0:
+                ref.zero_()
+                for r in range(world):
+                    fr = flds[0] if r == rank else eng.create_field(scn.beams[r], scn.dims)
+                    fr.compute(ref.data_ptr())
+                    fr.finish()
+                    if r != rank:
+                        fr.destroy()
+                torch.cuda.synchronize()
+                assembled_check = bool(torch.equal(assembled, ref))
+            last.zero_()
+        del ref
+    if ex is not None:
         # the headers of the messages this rank received carry the senders' device-side error flags: none may be set
         # (attached here: a rank whose slab came out empty — a late rank gets none — has transferred nothing and attached nothing)
-        ex.attach_all(i_chk % 2)
+        ex.attach_all((step_no[0] - 1) % 2)         # the last plan launched: the last timed step's, or --full's self-check plan
         for f_r in ex.remote.values():
             f_r.finish()
-        last.zero_()
-    del ref
 
     if rank == 0:
         info["_steps"] = beam.tracerSteps
         stage_ms = {k: buckets[k] / args.steps for k in buckets if k.endswith("_ms")}
         ct_fp = None
         oracle = None
-        if not args.no_cpu and not xchg:
+        if args.full and not args.no_cpu and not xchg:
             from oracle import oracle
             ncpu = args.cpu_threads or min(16, os.cpu_count() or 1)
             oracle.set_threads(ncpu)
             ct_fp = oracle.ct_footprint(scn, beam)
+        result = {
+            "metric": "Mvoxels/s dose deposited (%d^3 CT, 1 field per GPU), inputs resident in HBM" % n,
+            "value": round(world * n_vox / elapsed * args.steps / 1e6, 3),
+            "unit": "Mvoxels/s",
+            "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": round(ms_per_step, 4),
+            "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+            "dtype": "f32", "data": "synthetic",
+            "config": {"workload": "%s: %d^3 synthetic heterogeneous CT (HU->density/SP LUTs), %d field(s) one per GPU, "
+                                   "10x10 spots x 20 layers = 2000 spots, 512 tracer steps, 1 mm rays"
+                                   % ("C5" if n == 768 else ("C3" if world == 1 else "C4" if world == 4 else "C3 fields at %d angles" % world) if n == 512 else "size %d" % n, n, world),
+                       "plans_in_flight_on_streams": n_streams, "ray_grid": info["ray_dims"], "live_steps": info["live_steps"], "max_radius": info["max_radius"],
+                       "bbox_voxels": int(np.prod([info["bbox_max"][i] - info["bbox_min"][i] + 1 for i in range(3)])),
+                       "ct_footprint_voxels": ct_fp,
+                       "exchange": ("none" if not xchg else
+                                    "one RCCL all-gather of the packed BEV slabs per plan (%d x %.1f MB), overlapped with the next plan's kernels; every "
+                                    "rank writes its slab of the dose volume (axis %d, ranges %s) with all fields, in field order, in one fused launch: the volume stays "
+                                    "sharded by slabs, no dose data crosses xGMI; slabs cut for even step times from the ranks' measured field times %s us and "
+                                    "transfer rates %s ps per 1000 voxels" % (world, ex.cap / 1e6, ex.axis, ex.ranges, ex.heads_us, ex.rates_ps_kvox))},
+            "ms_plan": round(ms_per_step, 4),
+            "stage_ms": {k: round(v, 4) for k, v in stage_ms.items()},
+        }
+    if rank == 0 and args.full:
         alg = algorithmic_bytes(info, scn.dims, ct_fp)
         ks_ms = stage_ms["superp_kernel_ms"]
         ks_gbs = alg["superposition"] / (ks_ms * 1e-3) / 1e9 if ks_ms > 0 else 0.0
@@ -440,35 +503,15 @@ def main():
             roof["mfma_peak_tflops"] = F32_MATRIX_PEAK_TF
             if valu_per_launch and pmc.get("simd_cycles_per_launch"):
                 roof["issue_cycle_frac"] = round((4.0 * valu_per_launch + 32.0 * mfma_per_launch) / pmc["simd_cycles_per_launch"], 3)
-        result = {
-            "metric": "Mvoxels/s dose deposited (%d^3 CT, 1 field per GPU), inputs resident in HBM" % n,
-            "value": round(world * n_vox / elapsed * args.steps / 1e6, 3),
-            "unit": "Mvoxels/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": round(ms_per_step, 4),
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": "f32", "data": "synthetic",
-            "config": {"workload": "%s: %d^3 synthetic heterogeneous CT (HU->density/SP LUTs), %d field(s) one per GPU, "
-                                   "10x10 spots x 20 layers = 2000 spots, 512 tracer steps, 1 mm rays"
-                                   % ("C5" if n == 768 else ("C3" if world == 1 else "C4" if world == 4 else "C3 fields at %d angles" % world) if n == 512 else "size %d" % n, n, world),
-                       "plans_in_flight_on_streams": n_streams, "ray_grid": info["ray_dims"], "live_steps": info["live_steps"], "max_radius": info["max_radius"],
-                       "bbox_voxels": int(np.prod([info["bbox_max"][i] - info["bbox_min"][i] + 1 for i in range(3)])),
-                       "ct_footprint_voxels": ct_fp,
-                       "exchange": ("none" if not xchg else
-                                    "one RCCL all-gather of the packed BEV slabs per plan (%d x %.1f MB), overlapped with the next plan's kernels; every "
-                                    "rank writes its slab of the dose volume (axis %d, ranges %s) with all fields, in field order, in one fused launch: the volume stays "
-                                    "sharded by slabs, no dose data crosses xGMI; slabs cut for even step times from the ranks' measured field times %s us and "
-                                    "transfer rates %s ps per 1000 voxels" % (world, ex.cap / 1e6, ex.axis, ex.ranges, ex.heads_us, ex.rates_ps_kvox))},
-            "ms_plan": round(ms_per_step, 4),
+        result.update({
             "ms_plan_latency": round(ms_latency, 4),
             "throughput_streams": multi,
             "reduce_check_rel_err": reduce_check, "clear_check": clear_check, "assembled_check": assembled_check,
-            "stage_ms": {k: round(v, 4) for k, v in stage_ms.items()},
             "algorithmic_bytes": alg,
             "path_gbs": round(alg["total"] / (stage_ms["total_ms"] * 1e-3) / 1e9, 2),
             "path_frac_of_hbm_peak": round(alg["total"] / (stage_ms["total_ms"] * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
             "roofline": roof,
-        }
+        })
         if multi is not None:       # the pipelined leg against the same algorithmic bytes (wall time of its steps, not a stage sum)
             multi["path_frac_of_hbm_peak"] = round(alg["total"] / (multi["ms_per_step"] * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)
             multi["what"] = ("the same %d plans once more, consecutive plans round-robin on %d HIP streams (one field object and one dose volume "
@@ -587,6 +630,7 @@ def main():
             result["ms_plan_end_to_end"] = e2e
             # the metric on the REFERENCE'S timed span (uploads + kernels + download); `value` above is the resident-data rate
             result["value_reference_span_mvoxels_s"] = round(n_vox / (e2e["second_call"]["ms"] * 1e-3) / 1e6, 1)
+    if rank == 0:
         print(json.dumps(result))
     for f in flds:
         f.destroy()

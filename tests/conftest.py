@@ -8,7 +8,6 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 GOLDEN = os.path.join(ROOT, "tests", "golden")
-REF_LUTS = "/root/reference/LUTs/"
 
 
 def pytest_configure(config):

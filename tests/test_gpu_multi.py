@@ -390,7 +390,7 @@ def test_in_process_plan_over_rccl_transport(orc, engine, synth, monkeypatch):
 
 
 def test_bench_exchange_path_under_rccl_with_one_rank():
-    """bench.py --exchange-selftest: the N>1 code path (nccl process group, all-gathers, packed message, fused slab transfer,
+    """bench.py --exchange-selftest --full: the N>1 code path (nccl process group, all-gathers, packed message, fused slab transfer,
     pipelining on two volumes) with a world of one rank — what can be run of it on a one-GPU box. The volume it leaves equals the
     plain transfer of the field bit for bit (reduce_check 0) and the reuse of a dirty volume is clean (clear_check)."""
     import json
@@ -400,7 +400,7 @@ def test_bench_exchange_path_under_rccl_with_one_rank():
     from conftest import ROOT
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT="29541")
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--exchange-selftest", "--size", "128", "--steps", "4", "--warmup", "2",
-                        "--no-cpu"], capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
+                        "--full", "--no-cpu"], capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
     assert p.returncode == 0, p.stderr[-2000:]
     line = [l for l in p.stdout.splitlines() if l.startswith("{")][-1]
     r = json.loads(line)
@@ -412,7 +412,7 @@ def test_bench_exchange_path_under_rccl_with_one_rank():
 def test_bench_launches_its_own_ranks_two_processes_one_gpu(cut):
     """(Second case: the slab cut is told that rank 1's field is hopelessly late, so its slab holds nothing that any field's dose box reaches (or is empty) — it
     transfers nothing and attaches nothing; the eight-field plan has such a rank — and the run must still produce its line, checks included.)
-    `python bench.py --gpus 2` with no launcher in front: bench.py starts torch.distributed.run as a child process before it
+    `python bench.py --gpus 2 --full` with no launcher in front: bench.py starts torch.distributed.run as a child process before it
     touches the GPU and relays rank 0's line. Two ranks share this box's one GPU over gloo (the RCCL world needs one GPU per rank):
     the N>1 path with two real ranks — two slabs gathered, each rank writing its slab with both fields. The slabs together hold the
     sum of the fields (reduce_check), a reused volume is clean (clear_check), and the volume assembled on rank 0 equals the
@@ -424,7 +424,7 @@ def test_bench_launches_its_own_ranks_two_processes_one_gpu(cut):
     from conftest import ROOT
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--size", "128", "--steps", "4",
-                        "--warmup", "2", "--no-cpu"] + ([] if cut == "measured" else ["--debug-head-us", "600,90000"]),
+                        "--warmup", "2", "--full", "--no-cpu"] + ([] if cut == "measured" else ["--debug-head-us", "600,90000"]),
                        capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
@@ -468,14 +468,14 @@ def test_deferred_ct_uploads_only_what_the_rays_cross(engine, synth, angles):
 
 
 def test_bench_line_keeps_the_contract():
-    """bench.py (small CT, few steps): ONE JSON line with every key of the driver's contract, the roofline and cpu_baseline objects, the
-    self-checks true and the parity leg green."""
+    """bench.py --full (small CT, few steps): ONE JSON line with every key of the driver's contract, the roofline and cpu_baseline objects,
+    the self-checks true and the parity leg green."""
     import json
     import os
     import subprocess
     import sys
     from conftest import ROOT
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--size", "128", "--steps", "3", "--warmup", "1"],
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--size", "128", "--steps", "3", "--warmup", "1", "--full"],
                        capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
@@ -494,3 +494,42 @@ def test_bench_line_keeps_the_contract():
     assert r["cpu_baseline"]["kind"] in ("port", "reference") and r["cpu_baseline"]["value"] > 0
     assert r["clear_check"] is True and r["parity"]["gamma_1pct_1mm_pass"] == 1.0 and r["parity"]["max_rel_diff_above_10pct"] < 1e-4
     assert r["ms_plan_end_to_end"]["matches_resident_path"] is True
+
+
+def test_plain_bench_line_and_dumped_outputs(engine, synth, tmp_path):
+    """A plain bench.py run (no --full) prints the headline keys only, times exactly --steps steps, and with --dump-outputs writes what
+    its last timed step computed: the seeded voxel sample and the three central planes of the dose volume, float32, equal bit for bit
+    to the same field computed into a zeroed volume."""
+    import json
+    import os
+    import subprocess
+    import sys
+    import bench
+    from conftest import ROOT
+    out = tmp_path / "dump"
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--size", "128", "--steps", "5", "--warmup", "2", "--dump-outputs", str(out)],
+                       capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert p.returncode == 0, p.stderr[-2000:]
+    lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    r = json.loads(lines[0])
+    assert r["steps"] == 5 and r["warmup"] == 2 and r["n_gpus"] == 1 and r["unit"] == "Mvoxels/s" and r["dtype"] == "f32"
+    assert r["higher_is_better"] is True and r["ms_per_step"] > 0 and "128^3" in r["metric"]
+    assert abs(r["value"] - 128 ** 3 / (r["ms_per_step"] * 1e-3) / 1e6) <= 1e-2 * r["value"]
+    for k in ("roofline", "cpu_baseline", "throughput_streams", "ms_plan_latency", "clear_check", "parity"):
+        assert k not in r, k
+    got = {k: np.load(str(out / (k + ".npy"))) for k in ("dose_sample", "dose_mid_z", "dose_mid_y", "dose_mid_x")}
+    assert all(a.dtype == np.float32 for a in got.values())
+    ct, _ = scenarios.hetero_phantom(128)
+    scn = scenarios.hetero_ct(synth, n=128, angles=[0.0], ct=ct)
+    want = np.zeros_like(scn.ct)
+    with engine.Engine(0) as eng:
+        eng.set_luts(synth)
+        eng.set_ct(scn.ct)
+        eng.compute(scn.beams, want)
+    idx = np.unique(np.random.default_rng(bench.DUMP_SEED).integers(0, want.size, size=bench.DUMP_SAMPLE, dtype=np.int64))
+    assert want.max() > 0 and got["dose_sample"].max() > 0
+    np.testing.assert_array_equal(got["dose_sample"], want.reshape(-1)[idx])
+    np.testing.assert_array_equal(got["dose_mid_z"], want[64])
+    np.testing.assert_array_equal(got["dose_mid_y"], want[:, 64])
+    np.testing.assert_array_equal(got["dose_mid_x"], want[:, :, 64])

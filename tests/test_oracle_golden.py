@@ -1,14 +1,16 @@
 """The oracle against the golden vectors produced by the REFERENCE's own host code (oracle/make_golden.py):
 G1 LUT parser (energy_reader.cpp), G2 search/interpolation (vector_find.h, vector_interpolate.h),
-G7 erf-difference convolution weights (cpu_convolution_1d.cpp). Bit-exact comparisons."""
+G7 erf-difference convolution weights (cpu_convolution_1d.cpp). Bit-exact comparisons. The reference's real LUT directory is
+read from its xz-compressed copy in tests/golden/lut_real/."""
 import ctypes as C
 import hashlib
+import lzma
 import os
 
 import numpy as np
 import pytest
 
-from conftest import GOLDEN, REF_LUTS
+from conftest import GOLDEN
 from raytracedicom_amd import abi, luts
 
 fp = abi.c_float_p
@@ -16,6 +18,17 @@ fp = abi.c_float_p
 
 def P(a):
     return a.ctypes.data_as(fp)
+
+
+@pytest.fixture(scope="module")
+def real_luts(tmp_path_factory):
+    """The reference's LUT directory, unpacked from tests/golden/lut_real/*.xz (path ends with '/', as the parsers expect)."""
+    src = os.path.join(GOLDEN, "lut_real")
+    d = tmp_path_factory.mktemp("lut_real")
+    for name in os.listdir(src):
+        with lzma.open(os.path.join(src, name)) as fi:
+            (d / name[:-len(".xz")]).write_bytes(fi.read())
+    return str(d) + "/"
 
 
 def _oracle_parse(orc, directory, water):
@@ -58,13 +71,12 @@ def test_g1_small_lut_dir(orc, water, parser):
         assert (g["small_arr6"] != g["small_water_arr6"]).sum() == 1
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_LUTS), reason="reference LUT files only exist in the build container")
 @pytest.mark.parametrize("water", [False, True])
 @pytest.mark.parametrize("parser", ["oracle", "python"])
-def test_g1_real_lut_dir(orc, water, parser):
+def test_g1_real_lut_dir(orc, real_luts, water, parser):
     g = np.load(os.path.join(GOLDEN, "golden_g1_lut_parse.npz"))
     tag = "real_water" if water else "real"
-    arrs, scal, scales = _oracle_parse(orc, REF_LUTS, water) if parser == "oracle" else _python_parse(REF_LUTS, water)
+    arrs, scal, scales = _oracle_parse(orc, real_luts, water) if parser == "oracle" else _python_parse(real_luts, water)
     assert list(scal) == list(g[tag + "_scal"]) == [1024, 147, 3072, 3072, 3072]
     np.testing.assert_array_equal(np.array(scales, dtype=np.float32), g[tag + "_scales"])
     for i, a in enumerate(arrs):
@@ -154,15 +166,13 @@ def test_g1n_nuclear_tables_small_dir(orc, variant, parser):
 
 
 @pytest.mark.parametrize("variant", [1, 2, 3])
-def test_g1n_nuclear_tables_of_the_reference(orc, variant):
-    """The reference's real nuclear tables (read where they lie; skipped where /root/reference is absent): sizes, checksums, ends."""
-    if not os.path.isdir(REF_LUTS):
-        pytest.skip("reference LUTs not present")
+def test_g1n_nuclear_tables_of_the_reference(orc, real_luts, variant):
+    """The reference's real nuclear tables (tests/golden/lut_real): sizes, checksums, ends."""
     g = np.load(os.path.join(GOLDEN, "golden_g1n_nuclear_lut.npz"))
-    es = luts.read_lut_dir(REF_LUTS, False, nuclear_corr=variant)
+    es = luts.read_lut_dir(real_luts, False, nuclear_corr=variant)
     L = orc.lib()
     s = abi.RtdLuts()
-    assert L.orc_read_luts_nuc(REF_LUTS.encode(), 0, variant, C.byref(s)) == 0
+    assert L.orc_read_luts_nuc(real_luts.encode(), 0, variant, C.byref(s)) == 0
     n = s.n_energies * s.n_energy_samples
     for nm, py, oc in (("weight", es.nucWeightMatrix.reshape(-1), np.ctypeslib.as_array(s.nuc_weight_matrix, (n,)).copy()),
                        ("sqsigma", es.nucSqSigmaMatrix.reshape(-1), np.ctypeslib.as_array(s.nuc_sq_sigma_matrix, (n,)).copy())):
