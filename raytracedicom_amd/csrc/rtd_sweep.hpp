@@ -45,7 +45,7 @@ constexpr int kSwOut = kSwPatch + 2 * kSwMaxR;       // 96: edge of the output t
 constexpr int kSwOutRows = kSwPatchRows + 2 * kSwMaxR;   // rows of the output tile
 constexpr int kSwNCB = kSwOut / 16;                  // 6 column blocks
 constexpr int kSwGuard = kSwMaxR + 1;                // table entry 17 is always zero: the lookups clamp to it
-constexpr int kSwTS = 19;                            // floats per source table (entries 0 .. 17 + pad; odd: the build's stores are conflict-free)
+constexpr int kSwTP = 68;                            // table pitch: the tables of a wave are [entry 0 .. 17][source 0 .. 63 + pad] (below)
 constexpr int kSwPitch = 100;                        // row pitch of the tile in LDS: 4 rows = 400 floats = 16 banks on — the four row groups
                                                      // of a flush (rows 4 kq + r, columns li) fall into 64 different banks
 constexpr int kSwSlot = kSwOutRows * kSwOut;             // floats of a partial tile
@@ -59,9 +59,13 @@ constexpr int kSwNDelta = 12;                        // pair offsets delta = -28
 // the lanes' distances are delta + (li - kq), li - kq in [-3, 15]
 __host__ __device__ constexpr int swNeed(int delta) { return delta > 3 ? delta - 3 : (delta < -15 ? -delta - 15 : 0); }
 
-// dynamic LDS (floats): the output tile [96][kSwPitch], then the weight tables [wave][64][kSwTS]
+// dynamic LDS (floats): the output tile [96][kSwPitch], then the weight tables [wave][entry 0 .. 17][kSwTP], entry-major: an A read
+// (entry li, source 4 q + kq) falls into bank 4 li + 4 q + kq — the 64 lanes of a quad into 64 different banks; the B reads (entry
+// min(|delta + li - kq|, 17), same sources) repeat addresses (broadcasts); the build's store of one entry by the 64 lanes is 64
+// consecutive words, at the immediate offset entry * 272 bytes. (Source-major with 19 floats per source, the A and B reads were
+// mostly 2-way conflicts: four kq groups spread over 76 words.)
 constexpr int kSwLdsTab = kSwOutRows * kSwPitch;
-constexpr int kSwWaveLds = 64 * kSwTS;                    // a wave's tables
+constexpr int kSwWaveLds = (kSwGuard + 1) * kSwTP;       // a wave's tables
 constexpr int kSwLdsWords = kSwLdsTab + kSwWaves * kSwWaveLds;
 
 // erf(t), t >= 0, for the tables of sources sharper than sigma = 1.4 pixels: the two branches of rtd_erf_det (include/rtd_detmath.h:
@@ -148,6 +152,68 @@ __device__ inline void swBuild(float* __restrict__ m, float rs, float w, int rho
     for (int i = rhoRow + 1; i <= prevRho; ++i) m[i] = 0.0f;         // what the previous row-layer left beyond this one's reach
 }
 
+// K7s's build (swBuild is K7b's: source-major tables, radii to 32). The same values, bit for bit, into the entry-major tables:
+// m = the lane's source column, entry i at m[i * kSwTP].
+// The series of every lane, entries 0 .. rhoRow, unmasked: swBuildSeries's expressions in its order, unrolled (i^2 are literals, the
+// stores have immediate offsets, one scalar compare per entry is all that is left of the loop).
+__device__ inline void swSeriesT(float* __restrict__ m, float r, float w, int rhoRow, bool dead) {
+    const float h2 = r * r, h4 = h2 * h2;
+    const float k1 = h2 * (1.0f / 24.0f), k2 = h4 * (1.0f / 1920.0f), k3 = h4 * h2 * (1.0f / 322560.0f);
+    const float c0 = 1.0f - 2.0f * k1 + 12.0f * k2 - 120.0f * k3;
+    const float c1 = (4.0f * k1 - 48.0f * k2 + 720.0f * k3) * h2;
+    const float c2 = (16.0f * k2 - 480.0f * k3) * h4;
+    const float c3 = 64.0f * k3 * (h4 * h2);
+    float q = __builtin_amdgcn_exp2f(-1.4426950409f * h2), gq = 0.5641895835f * r * w;
+    const float cq = q * q;
+    m[0] = dead ? 0.0f : c0 * gq;
+    gq *= q; q *= cq;
+#pragma unroll
+    for (int i = 1; i <= kSwMaxR; i += 2) {
+        if (i > rhoRow) return;
+        const float w0 = (float)(i * i), w1 = (float)((i + 1) * (i + 1));
+        const float s0 = __builtin_fmaf(__builtin_fmaf(__builtin_fmaf(c3, w0, c2), w0, c1), w0, c0);
+        const float s1 = __builtin_fmaf(__builtin_fmaf(__builtin_fmaf(c3, w1, c2), w1, c1), w1, c0);
+        const float g1 = gq * q, q1 = q * cq;
+        const float ea = gq * s0, eb = g1 * s1;
+        gq = g1 * q1; q = q1 * cq;
+        m[i * kSwTP] = ea;
+        if (i + 1 > rhoRow) return;
+        m[(i + 1) * kSwTP] = eb;
+    }
+}
+// One (source row, layer) of K7s. Entries 0 .. rhoRow of every lane are stored unmasked first, then the lanes that end earlier zero
+// their tails (their own batch radius below the wave's, or an erf table: see below) — the values swBuild stores, without a compare and
+// select per entry in the usual wave. A dead lane (rhoS < 0) has w = sqrt(0) = +0, and the series at r = 1/4 is positive: its entries
+// are already +0.
+__device__ inline void swBuildT(float* __restrict__ m, float rs, float w, int rhoS, int rhoRow, int prevRho) {
+    const bool dead = rhoS < 0;
+    const bool series = dead || rs <= 0.75f;                         // (swBuild's choice)
+    if (__any(series)) swSeriesT(m, dead ? 0.25f : rs, w, rhoRow, dead);   // (an erf lane's series values are overwritten below)
+    int last = dead ? rhoRow : rhoS;                                 // the lane's last entry that may be nonzero
+    if (!__all(series)) {
+        // erf lanes (1/sigma > 0.75): erf differences. From entry 6 on both arguments r (i -+ 0.5) are >= 0.75 * 5.5 = 4.125, where
+        // swErf is clamped to one value (fminf(t, 4), and t >= 0.875: the second branch; NaN and inf take it too): such an entry is
+        // 0.5 * (+0) * w = +0 exactly, and is left to the tail below instead of being evaluated.
+        const float r = series ? 1.0f : rs;
+        float erfNew = swErf(r * 0.5f), erfOld = -erfNew;
+#pragma unroll
+        for (int i = 0; i <= 5; ++i) {
+            if (i > rhoRow) break;
+            const float e = 0.5f * (erfNew - erfOld) * w;
+            if (!series) m[i * kSwTP] = e;
+            if (i == 5) break;
+            erfOld = erfNew;
+            erfNew = swErf(r * ((float)i + 1.5f));
+        }
+        if (!series) last = min(last, 5);
+    }
+    if (__any(last < rhoRow)) {                                      // entries last + 1 .. rhoRow of the short lanes -> 0
+        for (int i = waveMinI(last) + 1; i <= rhoRow; ++i)
+            if (i > last) m[i * kSwTP] = 0.0f;
+    }
+    for (int i = rhoRow + 1; i <= prevRho; ++i) m[i * kSwTP] = 0.0f;  // what the previous row-layer left beyond this one's reach
+}
+
 // The pairs that come into reach at radius NEED (0, 1, 5, 9, 13): T += A(quad) * B(quad, column block). A row-layer of radius rho runs
 // the levels NEED <= rho one after the other, each in runs of up to eight quads: a run's A and B operands are requested from LDS in
 // one burst, then its MFMAs follow (sched_barrier between them) — an MFMA never waits for a read issued just in front of it; with
@@ -162,9 +228,9 @@ struct SwLevel {
 // has two offsets (delta = -15 - NEED and 3 + NEED: -16 / 4, -20 / 8, -24 / 12, -28 / 16), computed when the level runs (3 vector
 // instructions each).
 struct SwIdx {
-    int base, lk;                                                    // the lane's source of quad 0; li - kq
+    int base, lk;                                                    // the lane's source of quad 0 (entry 0); li - kq
     int d0[4];                                                       // delta = -12, -8, -4, 0
-    __device__ inline int at(int delta) const { return base + min(abs(delta + lk), kSwGuard); }
+    __device__ inline int at(int delta) const { return base + min(abs(delta + lk), kSwGuard) * kSwTP; }
 };
 // quads [Q0, Q1) of a level (a patch whose last columns lie outside the field's dose rectangle skips its last quads: their tables are zero)
 template <int NEED, int Q0, int Q1>
@@ -178,7 +244,7 @@ __device__ inline void swLevelLoadQ(float (&b)[SwLevel<NEED>::kN], const float* 
             const int delta = 16 * (t - 1) - 4 * q;                  // a constant once unrolled
             if (swNeed(delta) == NEED) {
                 const int idx = NEED == 0 ? ix.d0[(delta + 12) >> 2] : (delta < 0 ? lo : hi);
-                if (q >= Q0 && q < Q1) b[n] = lds[idx + q * 4 * kSwTS];
+                if (q >= Q0 && q < Q1) b[n] = lds[idx + q * 4];
                 ++n;
             }
         }
@@ -204,7 +270,7 @@ __device__ inline void swLevelRunQ(f32x4 (&acc)[kSwNCB], const float* __restrict
         bool any = false;
 #pragma unroll
         for (int t = 0; t < kSwNCB; ++t) any = any || swNeed(16 * (t - 1) - 4 * q) == NEED;
-        if (any) a[q] = lds[idxA + q * 4 * kSwTS];
+        if (any) a[q] = lds[idxA + q * 4];
     }
     swLevelLoadQ<NEED, Q0, Q1>(b, lds, ix);
     __builtin_amdgcn_sched_barrier(0);
@@ -356,8 +422,8 @@ __global__ __launch_bounds__(64 * kSwWaves, 4) void k_superpose_sweep(const floa
     if (dbg) dbgT1 = (long long)__builtin_amdgcn_s_memtime();
     // ---- per-lane operand addresses (float indices into the dynamic LDS), fixed for the whole block ----
     const int li = lane & 15, kq = lane >> 4;                        // MFMA 16x16x4: A[i = li][k = kq], B[k = kq][j = li], D[i = 4 kq + r][j = li]
-    const int tabBase = kSwLdsTab + wv * kSwWaveLds + kq * kSwTS;    // the lane's source of quad 0
-    const int idxA = tabBase + li;                                   // row |dy| = li of T
+    const int tabBase = kSwLdsTab + wv * kSwWaveLds + kq;            // the lane's source of quad 0, entry 0
+    const int idxA = tabBase + li * kSwTP;                           // row |dy| = li of T
     SwIdx idxB;                                                      // table entry min(|output column - source column|, guard) per pair offset
     idxB.base = tabBase; idxB.lk = li - kq;
 #pragma unroll
@@ -409,7 +475,7 @@ __global__ __launch_bounds__(64 * kSwWaves, 4) void k_superpose_sweep(const floa
             if (rhoS < 0) dose = 0.0f;
             if (!__any(rhoS >= 0)) continue;                         // the row carries no dose in this layer: exact zeros
             const int rhoRow = waveMaxI(rhoS);
-            swBuild(tab + lane * kSwTS, rs, __builtin_amdgcn_sqrtf(dose), rhoS, rhoRow, prevRho);
+            swBuildT(tab + lane, rs, __builtin_amdgcn_sqrtf(dose), rhoS, rhoRow, prevRho);
             prevRho = rhoRow;
             rhoFlush = max(rhoFlush, rhoRow);
             swLevelRun<0>(acc, sw, idxA, idxB, qTail);
@@ -432,7 +498,7 @@ __global__ __launch_bounds__(64 * kSwWaves, 4) void k_superpose_sweep(const floa
                     float v = 0.0f;
                     for (int dx = -kSwMaxR; dx <= kSwMaxR; ++dx) {
                         const int sI = c - kSwMaxR - dx;             // source index in the row
-                        if (c < kSwOut && sI >= 0 && sI < kSwPatch) v += tab[sI * kSwTS + kSwMaxR] * tab[sI * kSwTS + abs(dx)];
+                        if (c < kSwOut && sI >= 0 && sI < kSwPatch) v += tab[kSwMaxR * kSwTP + sI] * tab[abs(dx) * kSwTP + sI];
                     }
                     t16[hf] += v;
                 }
