@@ -296,6 +296,37 @@ int rtd_field_fetch(rtd_handle h, rtd_field f, const char* name, void* host_out,
                     size_t* bytes_needed);
 
 /*
+ * ---- Spot-weight gradients (the transposed dose path) ----
+ *
+ * For a field whose last rtd_field_compute or rtd_field_compute_bev ran at spot weights w ([L][ny][nx]) and a voxel-weight volume
+ * g on the dose grid ([dims[2]][dims[1]][dims[0]] float):
+ *
+ *     grad[l][sy][sx] = sum_v g[v] * dD[v] / dw[l][sy][sx]
+ *
+ * D is the dose this field adds to the volume. The set of live rays is frozen at w: a ray is dead when its weight is below
+ * ray_weight_cutoff or when it leaves the patient before its layer's first step (afterLast < pFirst, k_fill); dead rays contribute
+ * 0. On that live set D is linear for w >= 0, so the result is exact: for every delta >= 0 that keeps the live set,
+ * <D(w + delta) - D(w), g> = <delta, grad>. Rays of weight 0 are live under ray_weight_cutoff = 0, and their gradient includes the
+ * voxels their dose would reach. Optimisers should set ray_weight_cutoff = 0: with the default cut-off of 1 a spot whose rays all
+ * sit below it gets a gradient of 0.
+ *
+ * rtd_field_spot_gradient  dev_voxel_weights, dev_spot_grad: device memory of this handle's device. WRITES (does not accumulate)
+ *                          [L][ny][nx] into dev_spot_grad. Waits for the field's plan (host sync, as rtd_field_wait_plan), then runs
+ *                          asynchronously on the handle's stream. Bitwise reproducible; changes neither the field's BEV dose nor
+ *                          anything a later transfer reads. The workspace (grad_bev, grad_ray_weights) is allocated by the first call
+ *                          and reused. RTD_ERR_NOT_READY before any compute of the field; RTD_ERR_INVALID_ARG for a remote field,
+ *                          nuclear_corr or a null pointer; RTD_ERR_RADIUS_OVERFLOW when the forward found one (as rtd_field_finish).
+ * rtd_spot_gradient        the host-memory, reference-shaped form: every beam is computed up to its BEV dose and its gradient taken;
+ *                          spot_grad_out receives the per-beam [L][ny][nx] blocks concatenated in beam order.
+ * rtd_field_fetch names of the last gradient call: "grad_bev" [S][H+64][W+64] float (<g, D> = <grad_bev, bev>) and
+ * "grad_ray_weights" [L][H][W] float (<grad_bev, bev> = <grad_ray_weights, ray_weights>).
+ * Not available: nuclear_corr, remote fields, the multi-GPU rtd_plan_* path.
+ */
+int rtd_field_spot_gradient(rtd_handle h, rtd_field f, const float* dev_voxel_weights, float* dev_spot_grad);
+int rtd_spot_gradient(rtd_handle h, const rtd_beam* beams, int n_beams, const float* voxel_weights, const uint32_t dose_dims[3],
+                      float* spot_grad_out);
+
+/*
  * ---- Multi-GPU plans behind the boundary (SURVEY.md 8(b) "Threading": one handle and one host thread per device) ----
  *
  * rtd_plan is the reference-shaped call on several GPUs of one process: the 4-beam cudaWrapperProtons of the C++ shim uses

@@ -26,6 +26,7 @@
 #include "rtd_sweep.hpp"
 #include "rtd_sweep_big.hpp"
 #include "rtd_uniform.hpp"
+#include "rtd_adjoint.hpp"
 
 using namespace rtd;
 
@@ -149,6 +150,10 @@ struct rtd_field_impl {
     float* dSwSlotsBig = nullptr; int* dSwCountBig = nullptr;
     int radiusHint = -1;          // largest batch radius the last finished compute found (-1 unknown), under hintEpoch like uniformHint
     bool sweepEnabled = true;     // RTD_NO_SWEEP: every field through k_superpose_mfma
+    // spot-weight gradient (rtd_field_spot_gradient, rtd_adjoint.hpp): allocated by the first call, reused after it
+    float *dGradBev = nullptr, *dGradRw = nullptr, *dAdjPart = nullptr, *dAdjInterm = nullptr;
+    float4* dAdjWalk = nullptr;   // [chunk][L][H][W] the dose walk's state in front of every chunk of k_adj_superpose
+    bool gradDone = false;        // a gradient has been launched: grad_bev / grad_ray_weights hold the last one's intermediates
 };
 
 #define RTD_HIP(h, call)                                                                         \
@@ -496,7 +501,8 @@ int rtd_field_destroy(rtd_handle hh, rtd_field ff) {
     void* ptrs[] = { f->dSpotWeights, f->dConvInterm, f->dRayWeights, f->dDensity, f->dWepl, f->dRrl, f->dIdd, f->dRSigma, f->dBev, f->dBevPart, f->dNodeCount, f->dSwSlots, f->dSwCount, f->dSwSlotsBig, f->dSwCountBig,
                      f->dFirstInside, f->dFirstOutside, f->dFirstPassive, f->dWeplMin, f->dBlockWeplMin, f->dSegPos, f->dKsArgs, f->dTileRad,
                      f->dLayers, f->dState, f->dStepTab, f->dActive, f->dSigMin, f->dSigMax, f->dFillDbg, f->dSweepDbg, f->dSweepBigDbg, f->dScanDbg, f->dUniDbg,
-                     f->dNucSpotIdx, f->dNucRayWeights, f->dNucIdd, f->dNucRs, f->dNucBev, f->dNucEffT, f->dStateNuc };
+                     f->dNucSpotIdx, f->dNucRayWeights, f->dNucIdd, f->dNucRs, f->dNucBev, f->dNucEffT, f->dStateNuc,
+                     f->dGradBev, f->dGradRw, f->dAdjPart, f->dAdjInterm, f->dAdjWalk };
     for (void* p : ptrs) if (p) (void)hipFree(p);
     if (f->hState) (void)hipHostFree(f->hState);
     for (auto& e : f->ev) if (e) (void)hipEventDestroy(e);
@@ -514,6 +520,10 @@ int rtd_field_release(rtd_handle hh, rtd_field ff) {
     (void)hipSetDevice(h->device);
     (void)hipStreamSynchronize(h->stream);      // its kernels have drained: the next owner uploads with plain copies
     f->computed = false; f->transferred = false;
+    for (float** p : {&f->dGradBev, &f->dGradRw, &f->dAdjPart, &f->dAdjInterm}) { if (*p) (void)hipFree(*p); *p = nullptr; }   // (not part of the shape's workspace)
+    if (f->dAdjWalk) (void)hipFree(f->dAdjWalk);
+    f->dAdjWalk = nullptr;
+    f->gradDone = false;
     h->fieldCache.push_back(f);
     return RTD_OK;
 }
@@ -1301,6 +1311,99 @@ int rtd_field_finish(rtd_handle hh, rtd_field ff, rtd_timing* timing, rtd_field_
     return RTD_OK;
 }
 
+// Spot-weight gradient of <dose, g> (include/rtd.h; kernels in rtd_adjoint.hpp): transfer^T, fill^T + superposition^T, the chunks'
+// reduce, convolution^T (y then x). Asynchronous on the handle's stream after the forward's plan is known on the host (its
+// device-side error flag is reported here, as rtd_field_finish reports it).
+int rtd_field_spot_gradient(rtd_handle hh, rtd_field ff, const float* dev_voxel_weights, float* dev_spot_grad) {
+    auto* h = reinterpret_cast<rtd_handle_impl*>(hh);
+    auto* f = reinterpret_cast<rtd_field_impl*>(ff);
+    if (!h || !f) return RTD_ERR_INVALID_ARG;
+    if (!dev_voxel_weights || !dev_spot_grad) return fail(h, RTD_ERR_INVALID_ARG, "rtd_field_spot_gradient: null device pointer");
+    if (f->remote) return fail(h, RTD_ERR_INVALID_ARG, "rtd_field_spot_gradient: a remote field has no workspace");
+    if (f->fc.nuclearCorr) return fail(h, RTD_ERR_INVALID_ARG, "rtd_field_spot_gradient: not available with nuclear_corr");
+    if (!f->computed) return fail(h, RTD_ERR_NOT_READY, "rtd_field_spot_gradient: field not computed");
+    RTD_HIP(h, hipSetDevice(h->device));
+    RTD_HIP(h, hipEventSynchronize(f->selfPlanned ? f->ev[5] : f->ev[4]));   // the plan's state record, mirrored into pinned host memory
+    if (f->hState->errorFlags & kErrRadiusOverflow)
+        return fail(h, RTD_ERR_RADIUS_OVERFLOW, "Found larger than allowed kernel superposition radius");
+    const FieldConst& fc = f->fc;
+    const size_t P = (size_t)fc.bevW * fc.bevH, nRw = f->R * (size_t)fc.L;
+    const int nChunks = (fc.S + kAdjChunk - 1) / kAdjChunk;
+    if (!f->dGradBev) {
+        int st = devAlloc(h, &f->dGradBev, P * fc.S);
+        if (st == RTD_OK) st = devAlloc(h, &f->dGradRw, nRw);
+        if (st == RTD_OK) st = devAlloc(h, &f->dAdjPart, nRw * nChunks);
+        if (st == RTD_OK) st = devAlloc(h, &f->dAdjInterm, (size_t)fc.L * fc.spotNy * fc.W);
+        if (st == RTD_OK) st = devAlloc(h, &f->dAdjWalk, nRw * nChunks);
+        if (st != RTD_OK) {
+            for (float** p : {&f->dGradBev, &f->dGradRw, &f->dAdjPart, &f->dAdjInterm}) { if (*p) (void)hipFree(*p); *p = nullptr; }
+            if (f->dAdjWalk) (void)hipFree(f->dAdjWalk);
+            f->dAdjWalk = nullptr;
+            return st;
+        }
+    }
+    hipStream_t s = h->stream;
+    const FieldState* st = f->dState;
+    const size_t nCells = P * fc.S;
+    k_adj_transfer<<<dim3((unsigned)((nCells + 255) / 256)), dim3(256), 0, s>>>(f->dGradBev, dev_voxel_weights, (int)f->doseDims[0],
+                                                                              (int)f->doseDims[1], (int)f->doseDims[2], st, fc, f->rayIdxToDoseIdx);
+    k_adj_walk<<<dim3((unsigned)((f->R + 255) / 256), (unsigned)fc.L), dim3(256), 0, s>>>((const float*)f->dDensity, (const float*)f->dWepl,
+                                                                                      (const float*)f->dRayWeights, (const int*)f->dFirstInside,
+                                                                                      (const int*)f->dFirstOutside, (const LayerPlan*)f->dLayers, st,
+                                                                                      h->lut, fc, (const float*)f->dStepTab, f->dAdjWalk);
+    k_adj_superpose<<<dim3((unsigned)nChunks, (unsigned)(fc.tilesX * fc.tilesY), (unsigned)fc.L), dim3(kSuperpTileX, kSuperpTileY),
+                      (size_t)kAdjLdsWords * sizeof(float), s>>>((const float*)f->dGradBev, (const float*)f->dDensity, (const float*)f->dWepl,
+                                                                 (const float*)f->dRSigma, (const float*)f->dRayWeights, (const int*)f->dFirstInside,
+                                                                 (const int*)f->dFirstOutside, (const unsigned char*)f->dTileRad,
+                                                                 (const LayerPlan*)f->dLayers, st, h->lut, fc, (const float*)f->dStepTab,
+                                                                 (const float4*)f->dAdjWalk, f->dAdjPart);
+    k_adj_reduce<<<dim3((unsigned)((nRw + 255) / 256)), dim3(256), 0, s>>>((const float*)f->dAdjPart, f->dGradRw, nRw, nChunks);
+    k_adj_conv_y<<<dim3((unsigned)((fc.spotNy * fc.W + 255) / 256), (unsigned)fc.L), dim3(256), 0, s>>>((const float*)f->dGradRw, f->dAdjInterm,
+                                                                                                       (const LayerPlan*)f->dLayers, st, fc);
+    k_adj_conv_x<<<dim3((unsigned)((fc.spotNy * fc.spotNx + 255) / 256), (unsigned)fc.L), dim3(256), 0, s>>>((const float*)f->dAdjInterm, dev_spot_grad,
+                                                                                                            (const LayerPlan*)f->dLayers, st, fc);
+    RTD_HIP(h, hipGetLastError());
+    f->gradDone = true;
+    return RTD_OK;
+}
+
+// The host-memory form: every beam up to its BEV dose, then its gradient; the per-beam [L][ny][nx] blocks in beam order.
+int rtd_spot_gradient(rtd_handle hh, const rtd_beam* beams, int n_beams, const float* voxel_weights, const uint32_t dose_dims[3],
+                      float* spot_grad_out) {
+    auto* h = reinterpret_cast<rtd_handle_impl*>(hh);
+    if (!h || !beams || n_beams < 0 || !voxel_weights || !dose_dims || !spot_grad_out) return RTD_ERR_INVALID_ARG;
+    if (!h->dCt || !h->haveLuts) return fail(h, RTD_ERR_NOT_READY, "rtd_spot_gradient: set LUTs and CT first");
+    RTD_HIP(h, hipSetDevice(h->device));
+    const size_t n = (size_t)dose_dims[0] * dose_dims[1] * dose_dims[2];
+    size_t nGrad = 0;
+    for (int i = 0; i < n_beams; ++i) nGrad = std::max(nGrad, (size_t)beams[i].n_layers * beams[i].spot_ny * beams[i].spot_nx);
+    float *dG = nullptr, *dOut = nullptr;
+    RTD_HIP(h, hipMalloc((void**)&dG, n * sizeof(float)));
+    hipError_t e = hipMalloc((void**)&dOut, std::max<size_t>(nGrad, 1) * sizeof(float));
+    if (e == hipSuccess) e = hipMemcpyAsync(dG, voxel_weights, n * sizeof(float), hipMemcpyHostToDevice, h->stream);
+    int st = RTD_OK;
+    if (e != hipSuccess) { h->error = std::string("HIP error: ") + hipGetErrorString(e); st = RTD_ERR_HIP; }
+    size_t off = 0;
+    for (int i = 0; i < n_beams && st == RTD_OK; ++i) {
+        rtd_field f = nullptr;
+        st = rtd_field_create(hh, &beams[i], dose_dims, &f);
+        if (st == RTD_OK) st = rtd_field_compute_bev(hh, f);
+        if (st == RTD_OK) st = rtd_field_spot_gradient(hh, f, dG, dOut);
+        const size_t m = (size_t)beams[i].n_layers * beams[i].spot_ny * beams[i].spot_nx;
+        if (st == RTD_OK) {
+            e = hipMemcpyAsync(spot_grad_out + off, dOut, m * sizeof(float), hipMemcpyDeviceToHost, h->stream);
+            if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+            if (e != hipSuccess) { h->error = std::string("HIP error: ") + hipGetErrorString(e); st = RTD_ERR_HIP; }
+        }
+        off += m;
+        if (f) { const std::string keep = h->error; rtd_field_release(hh, f); h->error = keep; }
+    }
+    (void)hipStreamSynchronize(h->stream);
+    (void)hipFree(dG);
+    (void)hipFree(dOut);
+    return st;
+}
+
 int rtd_field_fetch(rtd_handle hh, rtd_field ff, const char* name, void* host_out, size_t bytes, size_t* bytes_needed) {
     auto* h = reinterpret_cast<rtd_handle_impl*>(hh);
     auto* f = reinterpret_cast<rtd_field_impl*>(ff);
@@ -1322,6 +1425,8 @@ int rtd_field_fetch(rtd_handle hh, rtd_field ff, const char* name, void* host_ou
     else if (nm == "first_passive") { src = f->dFirstPassive; n = 4 * R * L; }
     else if (nm == "tile_radius") { src = f->dTileRad; n = L * S * tiles; }
     else if (nm == "bev") { src = f->dBev; n = 4 * (size_t)fc.bevW * fc.bevH * S; }
+    else if (nm == "grad_bev" && f->gradDone) { src = f->dGradBev; n = 4 * (size_t)fc.bevW * fc.bevH * S; }
+    else if (nm == "grad_ray_weights" && f->gradDone) { src = f->dGradRw; n = 4 * R * L; }
     else if (nm == "fill_debug" && f->dFillDbg) { src = f->dFillDbg; n = f->fillDbgN * sizeof(long long); }
     else if (nm == "uniform_debug" && f->dUniDbg) { src = f->dUniDbg; n = f->uniDbgN * sizeof(long long); }
     else if (nm == "sweep_debug" && f->dSweepDbg) { src = f->dSweepDbg; n = f->sweepDbgN * sizeof(long long); }

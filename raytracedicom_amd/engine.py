@@ -76,6 +76,8 @@ def lib():
         L.rtd_field_attach_bev.argtypes = [vp, vp, vp]
         L.rtd_field_clear_dose_box.argtypes = [vp, vp, vp, i3, i3]
         L.rtd_field_release.argtypes = [vp, vp]
+        L.rtd_field_spot_gradient.argtypes = [vp, vp, vp, vp]
+        L.rtd_spot_gradient.argtypes = [vp, C.POINTER(abi.RtdBeam), C.c_int, abi.c_float_p, u3, abi.c_float_p]
         L.rtd_host_register.argtypes = [vp, C.c_size_t]
         L.rtd_host_unregister.argtypes = [vp]
         L.rtd_plan_create.argtypes = [C.POINTER(C.c_int), C.c_int, vpp]
@@ -164,6 +166,12 @@ class Field:
         """Launch all kernels of the field; asynchronous. dev_dose: device pointer (int) of the dose volume."""
         self.eng._check(lib().rtd_field_compute(self.eng._h, self._h, C.c_void_p(int(dev_dose))))
         self.computed = True
+
+    def spot_gradient(self, dev_g, dev_out):
+        """rtd_field_spot_gradient: the gradient of <dose, g> with respect to the spot weights of the last compute, written to
+        dev_out ([L][ny][nx] float32, device pointer); dev_g: the voxel-weight volume (device pointer, dose-grid shape).
+        Asynchronous after the field's plan is known; the live rays are those of the last compute."""
+        self.eng._check(lib().rtd_field_spot_gradient(self.eng._h, self._h, C.c_void_p(int(dev_g)), C.c_void_p(int(dev_out))))
 
     def clear_dose(self, dev_dose):
         """Zero the voxels of dev_dose that the last compute() of this field could have changed; asynchronous."""
@@ -256,6 +264,22 @@ class Engine:
         tm = (abi.RtdTiming * max(1, len(beams)))()
         self._check(lib().rtd_compute(self._h, ba, len(beams), abi.fptr(dose), abi.uint3((dose.shape[2], dose.shape[1], dose.shape[0])), tm))
         return [tm[i].as_dict() for i in range(len(beams))]
+
+    def spot_gradient(self, beams, voxel_weights):
+        """rtd_spot_gradient: for every beam the gradient of <its dose, voxel_weights> with respect to its spot weights, at the
+        beam's own weights; voxel_weights: host array [Z][Y][X] float32. Returns one [L][ny][nx] float32 array per beam."""
+        from .scenarios import beams_abi
+        g = abi.f32(voxel_weights)
+        ba = beams_abi(beams)
+        sizes = [int(np.prod(np.asarray(b.spotWeights).shape)) for b in beams]
+        out = np.zeros(max(1, sum(sizes)), dtype=np.float32)
+        self._check(lib().rtd_spot_gradient(self._h, ba, len(beams), abi.fptr(g), abi.uint3((g.shape[2], g.shape[1], g.shape[0])),
+                                            abi.fptr(out)))
+        res, off = [], 0
+        for b, n in zip(beams, sizes):
+            res.append(out[off:off + n].reshape(np.asarray(b.spotWeights).shape).copy())
+            off += n
+        return res
 
     def create_field(self, beam, dose_dims, remote=False):
         return Field(self, beam, dose_dims, remote=remote)
