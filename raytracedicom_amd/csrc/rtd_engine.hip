@@ -17,6 +17,8 @@
 #include <cstring>
 #include <fstream>
 #include <limits>
+#include <map>
+#include <optional>
 #include <string>
 #include <vector>
 
@@ -50,12 +52,7 @@ struct rtd_handle_impl {
     std::string error;
     rtd_options opt{};
     int numCUs = 256;             // compute units of the device (grid size of the grid-stride kernels)
-    bool scanLdsSet = false;      // dynamic-LDS cap of k_trace_scan raised (once per handle)
-    size_t traceTLds = 0;         // dynamic-LDS cap set for k_trace_sample_t so far
-    bool uni4LdsSet = false;      // ... for k_superpose_uniform4
-    bool sweepLdsSet = false;     // ... for k_superpose_sweep
-    size_t traceDLds = 0;         // ... for k_trace_sample_d
-    bool sweepBigLdsSet = false;  // ... for k_superpose_sweep_big
+    std::map<const void*, size_t> ldsCaps;   // dynamic-LDS cap set so far, per kernel (raiseLdsCap)
     unsigned inputEpoch = 0;      // bumped whenever CT, LUTs or options change (fields re-test what they learned about their input)
     // LUTs
     bool haveLuts = false;
@@ -76,19 +73,29 @@ struct rtd_handle_impl {
     void clearCtBoxes() { for (auto& b : ctBoxes) if (b.done) (void)hipEventDestroy(b.done); ctBoxes.clear(); }
 };
 
-// what the device allocations of a field depend on: a released workspace is reused by a field with the same signature
-// (W and H separately, not only R = W * H: the padded BEV cube is (W + 64) x (H + 64) x S and the superposition's hand-off slots and
-//  node counters scale with ceil(bevW / 64) * ceil(bevH / 32) — a 64 x 32 and a 32 x 64 ray grid need different sizes)
-struct AllocSig {
-    size_t W = 0, H = 0, S = 0, L = 0, nSpot = 0, nInterm = 0, G = 0, Gs = 0, tileRadWords = 0;
-    bool operator==(const AllocSig& o) const {
-        return W == o.W && H == o.H && S == o.S && L == o.L && nSpot == o.nSpot && nInterm == o.nInterm && G == o.G && Gs == o.Gs &&
-               tileRadWords == o.tileRadWords;
-    }
+// The engine's RTD_* switches (diagnostics, and the second implementations the tests compare with): read once, when a field is
+// created. RTD_NO_UNIFORM_PATH, RTD_UNIFORM_V2, RTD_NO_SWEEP, RTD_SEPARATE_PLAN, RTD_SEPARATE_KS_PLAN, RTD_*_DEBUG (per-block clock
+// stamps), and the overrides RTD_TRACE_MODE, RTD_TRACE_DIAG_B, RTD_KS_GROUPS, RTD_SW_GROUPS.
+struct Switches {
+    bool noUniformPath = false, uniformV2 = false, noSweep = false, separatePlan = false, separateKsPlan = false;
+    bool scanDebug = false, fillDebug = false, uniformDebug = false, sweepDebug = false;
+    std::optional<int> traceMode, traceDiagB, ksGroups, swGroups;
 };
 
+Switches readSwitches() {
+    auto on = [](const char* name) { return std::getenv(name) != nullptr; };
+    auto num = [](const char* name) { const char* v = std::getenv(name); return v ? std::optional<int>(std::atoi(v)) : std::nullopt; };
+    return Switches{on("RTD_NO_UNIFORM_PATH"), on("RTD_UNIFORM_V2"), on("RTD_NO_SWEEP"), on("RTD_SEPARATE_PLAN"), on("RTD_SEPARATE_KS_PLAN"),
+                    on("RTD_SCAN_DEBUG"), on("RTD_FILL_DEBUG"), on("RTD_UNIFORM_DEBUG"), on("RTD_SWEEP_DEBUG"),
+                    num("RTD_TRACE_MODE"), num("RTD_TRACE_DIAG_B"), num("RTD_KS_GROUPS"), num("RTD_SW_GROUPS")};
+}
+
+// Classes of a field's device buffers: the workspace that a field of the same shape takes over (rtd_field_release), the NUCLEAR_CORR
+// halo, the spot-weight gradient's (allocated by its first call), the RTD_*_DEBUG clock stamps.
+enum BufClass : unsigned { kShape = 1, kNuclear = 2, kGradient = 4, kDiag = 8, kAllBufs = 15 };
+
 struct rtd_field_impl {
-    AllocSig sig;
+    Switches sw;
     FieldConst fc{};
     TracerParams tracer{};
     FillGeom fillGeom{};
@@ -99,7 +106,7 @@ struct rtd_field_impl {
     int transferMode = 0;           // transfer kernel: lanes of the BEV gathers along dose x (0), y (1) or z (2)
     uint32_t doseDims[3] = {0, 0, 0};
     size_t R = 0;
-    // device workspace
+    // device workspace (forEachBuffer lists every buffer with its size)
     float *dSpotWeights = nullptr, *dConvInterm = nullptr, *dRayWeights = nullptr;
     float *dDensity = nullptr, *dWepl = nullptr, *dRrl = nullptr, *dIdd = nullptr, *dRSigma = nullptr, *dBev = nullptr, *dBevPart = nullptr;
     int* dNodeCount = nullptr;   // [output tile][step][32] arrival counters of the superposition's reduction tree (all zero between launches)
@@ -126,16 +133,16 @@ struct rtd_field_impl {
     FromFan nucIdxToDoseIdx{};
     TransferParams transfer0Nuc{};
     int transferModeNuc = 0;
-    long long* dFillDbg = nullptr; size_t fillDbgN = 0;   // RTD_FILL_DEBUG: per-block clock stamps of k_fill (diagnostics)
-    long long* dUniDbg = nullptr; size_t uniDbgN = 0;     // RTD_UNIFORM_DEBUG: per-block clock stamps of k_superpose_uniform4 (diagnostics)
-    long long* dSweepDbg = nullptr; size_t sweepDbgN = 0; // RTD_SWEEP_DEBUG: per-block clock stamps of k_superpose_sweep (diagnostics)
-    long long* dSweepBigDbg = nullptr; size_t sweepBigDbgN = 0; // ... and of k_superpose_sweep_big
-    long long* dScanDbg = nullptr; size_t scanDbgN = 0;         // RTD_SCAN_DEBUG: ... of k_trace_scan
+    long long* dFillDbg = nullptr;       // RTD_FILL_DEBUG: per-block clock stamps of k_fill (diagnostics)
+    long long* dUniDbg = nullptr;        // RTD_UNIFORM_DEBUG: ... of k_superpose_uniform4
+    long long* dSweepDbg = nullptr;      // RTD_SWEEP_DEBUG: ... of k_superpose_sweep
+    long long* dSweepBigDbg = nullptr;   // ... and of k_superpose_sweep_big
+    long long* dScanDbg = nullptr;       // RTD_SCAN_DEBUG: ... of k_trace_scan
     FieldState* dState = nullptr;
     FieldState* hState = nullptr;      // pinned host mirror of *dState (written by k_ks_plan), and its device-side address
     FieldState* dHostState = nullptr;
     std::vector<LayerPlan> hLayers;
-    hipEvent_t ev[9] = {};       // 0..6 stage ends, 7 / 8 stop / start of k_superpose_mfma
+    hipEvent_t ev[8] = {};       // 0..6 stage ends, 7 start of the superposition (its first launch)
     bool selfPlanned = false;    // the last compute had no k_ks_plan launch: block 0 of k_superpose_sweep's launch was the plan (ev[4] not recorded)
     bool computed = false;       // the BEV dose and the state record of the last rtd_field_compute[_bev] exist (or a slab is attached)
     bool transferred = false;    // a transfer has been launched since (ev[6] is recorded)
@@ -154,6 +161,52 @@ struct rtd_field_impl {
     float *dGradBev = nullptr, *dGradRw = nullptr, *dAdjPart = nullptr, *dAdjInterm = nullptr;
     float4* dAdjWalk = nullptr;   // [chunk][L][H][W] the dose walk's state in front of every chunk of k_adj_superpose
     bool gradDone = false;        // a gradient has been launched: grad_bev / grad_ray_weights hold the last one's intermediates
+    std::vector<size_t> released; // released: the element counts of its shape buffers (a new field takes it over if its own are the same)
+
+    bool uniform4() const { return fc.W <= 16 * (kU2XB - 4) && fc.W % 4 == 0 && !sw.uniformV2; }   // k_superpose_uniform4, else _uniform2
+
+    // Every device buffer of the field, once: visit(pointer, element count, class, cleared when allocated, rtd_field_fetch name or
+    // nullptr). A count of 0: the field has no such buffer. Allocation, takeover, release, destruction and fetch go through here.
+    template <typename V> void forEachBuffer(V&& visit) {
+        const size_t S = fc.S, L = fc.L, P = (size_t)fc.bevW * fc.bevH, tiles = (size_t)fc.tilesX * fc.tilesY;
+        const size_t mfma = sweepEnabled ? 0 : 1, sweep = 1 - mfma, nuc = fc.nuclearCorr ? 1 : 0, patches = S * swPX * swPY;
+        const size_t nOutTiles = (size_t)((fc.bevW + kKsTileX - 1) / kKsTileX) * ((fc.bevH + kKsTileY - 1) / kKsTileY);
+        const size_t nucR = (size_t)fc.nucW * fc.nucH, nucBev = (size_t)(fc.nucW + 2 * kMaxSuperpR) * (fc.nucH + 2 * kMaxSuperpR);
+        const size_t nucTiles = (size_t)(fc.nucW / kSuperpTileX) * (fc.nucH / kSuperpTileY);
+        const size_t nChunks = (S + kAdjChunk - 1) / kAdjChunk, nPartsU4 = ((fc.bevH + 15) / 16 + kU4RB - 1) / kU4RB;
+        visit(dSpotWeights, (size_t)fc.spotNx * fc.spotNy * L, kShape, false, nullptr);
+        visit(dConvInterm, (size_t)fc.W * fc.spotNy * L, kShape, false, nullptr);
+        visit(dRayWeights, R * L, kShape, false, "ray_weights");
+        visit(dDensity, R * S, kShape, false, "density"); visit(dWepl, R * S, kShape, false, "wepl"); visit(dRrl, R * S, kShape, false, nullptr);
+        visit(dIdd, R * S * L, kShape, false, "idd"); visit(dRSigma, R * S * L, kShape, false, "rsigma");
+        // (the transfer reads the slices [entry, passive) only, and the superposition's reduce writes every pixel of those: slices
+        //  outside hold stale values that nothing samples; a fresh buffer is cleared once so that a fetch of "bev" reads zeros there)
+        visit(dBev, P * S, kShape, true, "bev");
+        visit(dBevPart, mfma * nOutTiles * kKsTileX * kKsTileY * S * ksGroups, kShape, false, nullptr);
+        visit(dNodeCount, mfma * nOutTiles * S * 32, kShape, true, nullptr);
+        visit(dSwSlots, sweep * patches * swGroups * kSwSlot, kShape, false, nullptr); visit(dSwCount, sweep * S, kShape, true, nullptr);
+        visit(dSwSlotsBig, sweep * patches * bgGroups * kBgSlot, kShape, false, nullptr); visit(dSwCountBig, sweep * S, kShape, true, nullptr);
+        visit(dFirstInside, R, kShape, false, "first_inside"); visit(dFirstOutside, R, kShape, false, "first_outside");
+        visit(dFirstPassive, R * L, kShape, false, "first_passive");
+        visit(dWeplMin, S, kShape, false, "wepl_min"); visit(dBlockWeplMin, (R / 64) * S, kShape, false, nullptr);
+        visit(dSegPos, (S / kTraceSeg + 1) * 3 * R, kShape, false, nullptr);
+        visit(dKsArgs, (size_t)1, kShape, false, nullptr);
+        visit(dTileRad, tileRadWords * 4, kShape, false, "tile_radius");
+        visit(dLayers, L, kShape, false, nullptr); visit(dState, (size_t)1, kShape, false, nullptr); visit(dStepTab, 2 * S, kShape, false, nullptr);
+        visit(dActive, 4 * L * S, kShape, false, nullptr); visit(dSigMin, L * S, kShape, false, nullptr); visit(dSigMax, L * S, kShape, false, nullptr);
+        visit(dNucSpotIdx, nuc * R, kNuclear, false, nullptr); visit(dNucRayWeights, nucR * L, kNuclear, false, nullptr);
+        visit(dNucIdd, nucR * L, kNuclear, false, nullptr); visit(dNucRs, nucR * L, kNuclear, false, nullptr);
+        visit(dNucBev, nuc * nucBev, kNuclear, false, nullptr); visit(dNucEffT, nucTiles * L, kNuclear, false, nullptr);
+        visit(dStateNuc, nuc, kNuclear, false, nullptr);
+        visit(dGradBev, P * S, kGradient, false, "grad_bev"); visit(dGradRw, R * L, kGradient, false, "grad_ray_weights");
+        visit(dAdjPart, R * L * nChunks, kGradient, false, nullptr); visit(dAdjWalk, R * L * nChunks, kGradient, false, nullptr);
+        visit(dAdjInterm, L * fc.spotNy * fc.W, kGradient, false, nullptr);
+        visit(dScanDbg, sw.scanDebug ? 8 * (R / 64) : 0, kDiag, true, "scan_debug");
+        visit(dFillDbg, sw.fillDebug ? 4 * 2 * tiles * L : 0, kDiag, false, "fill_debug");
+        visit(dUniDbg, sw.uniformDebug && uniformEligible && uniform4() ? 16 * S * nPartsU4 : 0, kDiag, true, "uniform_debug");
+        visit(dSweepDbg, sw.sweepDebug ? sweep * (8 + 4 * 16) * (patches * swGroups + 1) : 0, kDiag, true, "sweep_debug");
+        visit(dSweepBigDbg, sw.sweepDebug ? sweep * 48 * patches * bgGroups : 0, kDiag, true, "sweep_big_debug");
+    }
 };
 
 #define RTD_HIP(h, call)                                                                         \
@@ -180,9 +233,49 @@ IdxTransform toIdx(const rtd_idx_transform& t) {
     return r;
 }
 
-template <typename T>
-int devAlloc(rtd_handle_impl* h, T** p, size_t n) {
-    RTD_HIP(h, hipMalloc((void**)p, n * sizeof(T)));
+// Allocates the field's buffers of the given classes (clearing those marked so); after a failure the caller frees them.
+int allocBuffers(rtd_handle_impl* h, rtd_field_impl* f, unsigned classes) {
+    hipError_t e = hipSuccess;
+    f->forEachBuffer([&](auto*& p, size_t n, BufClass c, bool clear, const char*) {
+        if (e != hipSuccess || !(classes & c) || n == 0) return;
+        e = hipMalloc((void**)&p, n * sizeof *p);
+        if (e == hipSuccess && clear) e = hipMemset(p, 0, n * sizeof *p);
+    });
+    RTD_HIP(h, e);
+    return RTD_OK;
+}
+
+void freeBuffers(rtd_field_impl* f, unsigned classes) {
+    f->forEachBuffer([&](auto*& p, size_t, BufClass c, bool, const char*) { if ((classes & c) && p) { (void)hipFree(p); p = nullptr; } });
+}
+
+std::vector<size_t> shapeCounts(rtd_field_impl* f) {
+    std::vector<size_t> n;
+    f->forEachBuffer([&](auto*&, size_t count, BufClass c, bool, const char*) { if (c == kShape) n.push_back(count); });
+    return n;
+}
+
+// Raises a kernel's dynamic-LDS cap to `bytes` unless this handle has set it at least that high already.
+template <typename K>
+hipError_t raiseLdsCap(rtd_handle_impl* h, K kernel, size_t bytes) {
+    const void* k = reinterpret_cast<const void*>(kernel);
+    size_t& cap = h->ldsCaps[k];
+    if (bytes <= cap) return hipSuccess;
+    const hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+    if (e == hipSuccess) cap = bytes;
+    return e;
+}
+
+// What a finished plan tells the host (its state record, mirrored into pinned host memory). The hints belong to the inputs the
+// compute was LAUNCHED under: CT, LUTs or options may have changed since.
+int takeFindings(rtd_handle_impl* h, rtd_field_impl* f, const FieldState& st) {
+    if (f->triedUniform) { f->uniformHint = st.uniformField ? 1 : 0; f->hintEpoch = f->launchEpoch; }
+    else if (f->hintEpoch != f->launchEpoch) { f->uniformHint = -1; f->hintEpoch = f->launchEpoch; }
+    f->radiusHint = (st.errorFlags || st.empty) ? -1 : st.maxRadius;   // (valid under hintEpoch, like the uniform hint)
+    // A compute that skipped the general kernel (hint: uniform) on a field the device then found heterogeneous has written no BEV
+    // dose: only possible when the caller changed a bound device volume in place (rtd_set_ct_device) without telling the handle.
+    if (f->launchedKnownUniform && !st.uniformField && !st.errorFlags && !st.empty)
+        return fail(h, RTD_ERR_NOT_READY, "the field was launched as a uniform-sigma field but is not one: its inputs were modified in place; call rtd_set_ct* again and recompute");
     return RTD_OK;
 }
 
@@ -498,12 +591,7 @@ int rtd_field_destroy(rtd_handle hh, rtd_field ff) {
     if (!h || !f) return RTD_ERR_INVALID_ARG;
     (void)hipSetDevice(h->device);
     (void)hipStreamSynchronize(h->stream);
-    void* ptrs[] = { f->dSpotWeights, f->dConvInterm, f->dRayWeights, f->dDensity, f->dWepl, f->dRrl, f->dIdd, f->dRSigma, f->dBev, f->dBevPart, f->dNodeCount, f->dSwSlots, f->dSwCount, f->dSwSlotsBig, f->dSwCountBig,
-                     f->dFirstInside, f->dFirstOutside, f->dFirstPassive, f->dWeplMin, f->dBlockWeplMin, f->dSegPos, f->dKsArgs, f->dTileRad,
-                     f->dLayers, f->dState, f->dStepTab, f->dActive, f->dSigMin, f->dSigMax, f->dFillDbg, f->dSweepDbg, f->dSweepBigDbg, f->dScanDbg, f->dUniDbg,
-                     f->dNucSpotIdx, f->dNucRayWeights, f->dNucIdd, f->dNucRs, f->dNucBev, f->dNucEffT, f->dStateNuc,
-                     f->dGradBev, f->dGradRw, f->dAdjPart, f->dAdjInterm, f->dAdjWalk };
-    for (void* p : ptrs) if (p) (void)hipFree(p);
+    freeBuffers(f, kAllBufs);
     if (f->hState) (void)hipHostFree(f->hState);
     for (auto& e : f->ev) if (e) (void)hipEventDestroy(e);
     delete f;
@@ -520,10 +608,9 @@ int rtd_field_release(rtd_handle hh, rtd_field ff) {
     (void)hipSetDevice(h->device);
     (void)hipStreamSynchronize(h->stream);      // its kernels have drained: the next owner uploads with plain copies
     f->computed = false; f->transferred = false;
-    for (float** p : {&f->dGradBev, &f->dGradRw, &f->dAdjPart, &f->dAdjInterm}) { if (*p) (void)hipFree(*p); *p = nullptr; }   // (not part of the shape's workspace)
-    if (f->dAdjWalk) (void)hipFree(f->dAdjWalk);
-    f->dAdjWalk = nullptr;
+    freeBuffers(f, kGradient | kDiag);          // (not part of the shape's workspace)
     f->gradDone = false;
+    f->released = shapeCounts(f);
     h->fieldCache.push_back(f);
     return RTD_OK;
 }
@@ -564,6 +651,7 @@ static int createField(rtd_handle hh, const rtd_beam* b, const uint32_t dose_dim
 
     auto* f = new rtd_field_impl();
     f->remote = remote;
+    f->sw = readSwitches();
     FieldConst& fc = f->fc;
     fc.W = W; fc.H = H; fc.L = L; fc.S = S; fc.bevW = W + 2 * kMaxSuperpR; fc.bevH = H + 2 * kMaxSuperpR;
     fc.tilesX = tilesX; fc.tilesY = tilesY;
@@ -577,7 +665,7 @@ static int createField(rtd_handle hh, const rtd_beam* b, const uint32_t dose_dim
     fc.ksSigmaCutoff = opt.ks_sigma_cutoff; fc.rayWeightCutoff = opt.ray_weight_cutoff;
     fc.doseToWater = opt.dose_to_water; fc.nozzle = opt.nozzle;
     fc.nuclearCorr = remote ? 0 : opt.nuclear_corr;
-    f->uniformEligible = !remote && !fc.nuclearCorr && fc.bevH <= kUniMaxBevH && L <= 256 && std::getenv("RTD_NO_UNIFORM_PATH") == nullptr;
+    f->uniformEligible = !remote && !fc.nuclearCorr && fc.bevH <= kUniMaxBevH && L <= 256 && !f->sw.noUniformPath;
     fc.nucW = fc.nuclearCorr ? roundTo((int)b->spot_nx, kSuperpTileX) : 0;                                     // :667
     fc.nucH = fc.nuclearCorr ? roundTo((int)b->spot_ny, kSuperpTileY) : 0;
     fc.spotDist = sitg.delta.x / b->ray_spacing[0];                                                            // spotDistInRays, :922
@@ -615,8 +703,8 @@ static int createField(rtd_handle hh, const rtd_beam* b, const uint32_t dose_dim
             const float costDiag = (W % kTdRays == 0) ? 79.0f + 11.0f * bestD : 1e30f;
             f->traceMode = costAcross <= costAlong && costAcross <= costDiag ? 0 : (costAlong <= costDiag ? 1 : 2);
         }
-        if (const char* v = std::getenv("RTD_TRACE_MODE")) f->traceMode = std::atoi(v);   // diagnostics: force the plain (0) / along-beam (1) / diagonal (2) sampling kernel
-        if (const char* v = std::getenv("RTD_TRACE_DIAG_B")) f->traceDiagB = std::atoi(v);
+        if (f->sw.traceMode) f->traceMode = *f->sw.traceMode;   // diagnostics: force the plain (0) / along-beam (1) / diagonal (2) sampling kernel
+        if (f->sw.traceDiagB) f->traceDiagB = *f->sw.traceDiagB;
         if (f->traceMode == 2 && (f->traceDiagB == 0 || W % kTdRays != 0)) f->traceMode = 0;
     }
     f->fillGeom = makeFillGeom(h->rrlScale, rayIdxToImIdx);                                                    // :925
@@ -657,58 +745,42 @@ static int createField(rtd_handle hh, const rtd_beam* b, const uint32_t dose_dim
         for (int i = 0; i < kMaxSuperpR + 2; ++i) p.effRad[i] = i;
     }
 
-    if (const char* v = std::getenv("RTD_KS_GROUPS")) f->ksGroups = std::max(1, std::min(kKsMaxGroups, std::atoi(v)));
+    if (f->sw.ksGroups) f->ksGroups = std::max(1, std::min(kKsMaxGroups, *f->sw.ksGroups));
     f->ksGroups = std::min(f->ksGroups, L);
     {   // keep the partial BEV buffers below ~4 GiB for large ray grids (G only trades parallelism for memory)
         const size_t sliceBytes = (size_t)fc.bevW * fc.bevH * (size_t)S * sizeof(float);
         const size_t cap = (size_t)4 << 30;
         f->ksGroups = (int)std::max<size_t>(1, std::min<size_t>((size_t)f->ksGroups, cap / std::max<size_t>(sliceBytes, 1)));
     }
-    // workspace (the reference's per-beam cudaMallocs, :685-734, :804-808): taken over from a released field of the same shape
-    // when there is one (rtd_field_release), so a plan of similar beams allocates once
-    const size_t R = f->R, P = (size_t)fc.bevW * fc.bevH;
-    const size_t nSpot = (size_t)b->spot_nx * b->spot_ny * L;
-    f->tileRadWords = ((size_t)L * S * tilesX * tilesY + 3) / 4;      // filled as 32-bit words by k_reset
-    f->sig.W = (size_t)W; f->sig.H = (size_t)H; f->sig.S = (size_t)S; f->sig.L = (size_t)L; f->sig.nSpot = nSpot; f->sig.nInterm = (size_t)W * b->spot_ny * L;
-    f->sig.G = (size_t)f->ksGroups; f->sig.tileRadWords = f->tileRadWords;
     // sweep: 4 layer groups unless told otherwise; at most 64 layers per group; partial tiles below ~2 GiB
-    f->sweepEnabled = std::getenv("RTD_NO_SWEEP") == nullptr;
-    if (const char* v = std::getenv("RTD_SW_GROUPS")) f->swGroups = std::atoi(v);
+    f->sweepEnabled = !f->sw.noSweep;
+    if (f->sw.swGroups) f->swGroups = *f->sw.swGroups;
     f->swGroups = std::max(std::max(1, (L + kSwMaxLay - 1) / kSwMaxLay), std::min(std::min(f->swGroups, kSwMaxGroups), L));
     f->swPX = (W + kSwPatch - 1) / kSwPatch; f->swPY = (H + kSwPatchRows - 1) / kSwPatchRows;
     while (f->swGroups > std::max(1, (L + kSwMaxLay - 1) / kSwMaxLay) &&
            (size_t)S * f->swPX * f->swPY * f->swGroups * kSwSlot * sizeof(float) > ((size_t)2 << 30)) --f->swGroups;
-    f->sig.Gs = (size_t)f->swGroups;
     f->bgGroups = std::max(1, std::min(kBgMaxGroups, L));
     while (f->bgGroups > std::max(1, (L + kSwMaxLay - 1) / kSwMaxLay) &&       // (a group holds at most kSwMaxLay layers: L <= 256 needs up to 4)
            (size_t)S * f->swPX * f->swPY * f->bgGroups * kBgSlot * sizeof(float) > ((size_t)1 << 30)) --f->bgGroups;
-    if (f->sweepEnabled) f->sig.G = 0;      // (the partial BEV buffers of k_superpose_mfma exist only without the sweep)
+    const size_t R = f->R, nSpot = (size_t)b->spot_nx * b->spot_ny * L;
+    f->tileRadWords = ((size_t)L * S * tilesX * tilesY + 3) / 4;      // filled as 32-bit words by k_reset
+    // workspace (the reference's per-beam cudaMallocs, :685-734, :804-808): taken over from a released field whose shape buffers have
+    // the same sizes when there is one (rtd_field_release), so a plan of similar beams allocates once
+    const std::vector<size_t> counts = shapeCounts(f);
     rtd_field_impl* husk = nullptr;
     for (size_t i = 0; i < h->fieldCache.size(); ++i)
-        if (h->fieldCache[i]->sig == f->sig) { husk = h->fieldCache[i]; h->fieldCache.erase(h->fieldCache.begin() + (long)i); break; }
+        if (h->fieldCache[i]->released == counts) { husk = h->fieldCache[i]; h->fieldCache.erase(h->fieldCache.begin() + (long)i); break; }
     if (husk) {
-        f->dSpotWeights = husk->dSpotWeights; f->dConvInterm = husk->dConvInterm; f->dRayWeights = husk->dRayWeights;
-        f->dDensity = husk->dDensity; f->dWepl = husk->dWepl; f->dRrl = husk->dRrl; f->dIdd = husk->dIdd; f->dRSigma = husk->dRSigma;
-        f->dBev = husk->dBev; f->dBevPart = husk->dBevPart; f->dNodeCount = husk->dNodeCount; f->dSwSlots = husk->dSwSlots; f->dSwCount = husk->dSwCount; f->dSwSlotsBig = husk->dSwSlotsBig; f->dSwCountBig = husk->dSwCountBig; f->dFirstInside = husk->dFirstInside; f->dFirstOutside = husk->dFirstOutside;
-        f->dFirstPassive = husk->dFirstPassive; f->dWeplMin = husk->dWeplMin; f->dBlockWeplMin = husk->dBlockWeplMin; f->dSegPos = husk->dSegPos; f->dKsArgs = husk->dKsArgs; f->dTileRad = husk->dTileRad; f->dLayers = husk->dLayers;
-        f->dState = husk->dState; f->dStepTab = husk->dStepTab; f->dActive = husk->dActive; f->dSigMin = husk->dSigMin; f->dSigMax = husk->dSigMax; f->hState = husk->hState; f->dHostState = husk->dHostState;
-        for (int i = 0; i < 9; ++i) f->ev[i] = husk->ev[i];
+        std::vector<void*> ws;
+        husk->forEachBuffer([&](auto*& p, size_t, BufClass c, bool, const char*) { if (c == kShape) { ws.push_back(p); p = nullptr; } });
+        size_t i = 0;
+        f->forEachBuffer([&](auto*& p, size_t, BufClass c, bool, const char*) { if (c == kShape) p = static_cast<std::decay_t<decltype(p)>>(ws[i++]); });
+        f->hState = husk->hState; f->dHostState = husk->dHostState;
+        std::copy(std::begin(husk->ev), std::end(husk->ev), f->ev);
         delete husk;
     }
     const bool fresh = husk == nullptr;
-    int st = RTD_OK;
-    auto A = [&](auto** p, size_t n) { if (st == RTD_OK && fresh) st = devAlloc(h, p, n); };
-    A(&f->dSpotWeights, nSpot); A(&f->dConvInterm, (size_t)W * b->spot_ny * L); A(&f->dRayWeights, R * L);
-    A(&f->dDensity, R * S); A(&f->dWepl, R * S); A(&f->dRrl, R * S); A(&f->dIdd, R * S * L); A(&f->dRSigma, R * S * L); A(&f->dBev, P * S);
-    const size_t nOutTiles = (size_t)((fc.bevW + kKsTileX - 1) / kKsTileX) * ((fc.bevH + kKsTileY - 1) / kKsTileY);
-    if (!f->sweepEnabled) { A(&f->dBevPart, nOutTiles * kKsTileX * kKsTileY * S * f->ksGroups); A(&f->dNodeCount, nOutTiles * S * 32); }
-    else {
-        A(&f->dSwSlots, (size_t)S * f->swPX * f->swPY * f->swGroups * kSwSlot); A(&f->dSwCount, (size_t)S);
-        A(&f->dSwSlotsBig, (size_t)S * f->swPX * f->swPY * f->bgGroups * kBgSlot); A(&f->dSwCountBig, (size_t)S);
-    }
-    A(&f->dFirstInside, R); A(&f->dFirstOutside, R); A(&f->dFirstPassive, R * L); A(&f->dWeplMin, (size_t)S); A(&f->dBlockWeplMin, (R / 64) * (size_t)S); A(&f->dSegPos, ((size_t)S / kTraceSeg + 1) * 3 * R); A(&f->dKsArgs, (size_t)1);
-    A(&f->dTileRad, f->tileRadWords * 4); A(&f->dLayers, (size_t)L); A(&f->dState, (size_t)1); A(&f->dStepTab, (size_t)2 * S); A(&f->dActive, (size_t)4 * L * S); A(&f->dSigMin, (size_t)L * S); A(&f->dSigMax, (size_t)L * S);
-    if (st != RTD_OK) { rtd_field_destroy(hh, reinterpret_cast<rtd_field>(f)); return st; }
+    { const int st = allocBuffers(h, f, (fresh ? kShape : 0u) | kNuclear | kDiag); if (st != RTD_OK) { rtd_field_destroy(hh, reinterpret_cast<rtd_field>(f)); return st; } }
     hipError_t e = hipMemcpy(f->dSpotWeights, b->spot_weights, nSpot * sizeof(float), hipMemcpyHostToDevice);   // :851
     if (e == hipSuccess) e = hipMemcpy(f->dLayers, f->hLayers.data(), (size_t)L * sizeof(LayerPlan), hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemset(f->dState, 0, sizeof(FieldState));
@@ -736,9 +808,8 @@ static int createField(rtd_handle hh, const rtd_beam* b, const uint32_t dose_dim
         if (e == hipSuccess) e = hipMemcpy(f->dStepTab, tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice);
     }
     if (fc.nuclearCorr && e == hipSuccess) {
-        // NUCLEAR_CORR set-up (kernel_wrapper.cu:736-751, 858-892): spot index of every ray, padded spot weights, halo buffers
-        const size_t nucR = (size_t)fc.nucW * fc.nucH, bevN = (size_t)(fc.nucW + 2 * kMaxSuperpR) * (fc.nucH + 2 * kMaxSuperpR);
-        const size_t nTn = (size_t)(fc.nucW / kSuperpTileX) * (fc.nucH / kSuperpTileY);
+        // NUCLEAR_CORR set-up (kernel_wrapper.cu:736-751, 858-892): spot index of every ray, padded spot weights
+        const size_t nucR = (size_t)fc.nucW * fc.nucH;
         std::vector<int> spotIdx(R, -1);
         for (unsigned int sy = 0; sy < b->spot_ny; ++sy) {
             const float gy = (float)sy * sitg.delta.y + sitg.offset.y;
@@ -752,11 +823,6 @@ static int createField(rtd_handle hh, const rtd_beam* b, const uint32_t dose_dim
         std::vector<float> padded(nucR * (size_t)L, 0.0f);               // extendAndPadd, :51-66
         for (int z = 0; z < L; ++z) for (unsigned int y = 0; y < b->spot_ny; ++y) for (unsigned int x = 0; x < b->spot_nx; ++x)
             padded[(size_t)z * nucR + (size_t)y * fc.nucW + x] = b->spot_weights[((size_t)z * b->spot_ny + y) * b->spot_nx + x];
-        int stn = RTD_OK;
-        auto An = [&](auto** p, size_t n) { if (stn == RTD_OK) stn = devAlloc(h, p, n); };
-        An(&f->dNucSpotIdx, R); An(&f->dNucRayWeights, nucR * L); An(&f->dNucIdd, nucR * L); An(&f->dNucRs, nucR * L);
-        An(&f->dNucBev, bevN); An(&f->dNucEffT, nTn * L); An(&f->dStateNuc, (size_t)1);
-        if (stn != RTD_OK) { rtd_field_destroy(hh, reinterpret_cast<rtd_field>(f)); return stn; }
         e = hipMemcpy(f->dNucSpotIdx, spotIdx.data(), R * sizeof(int), hipMemcpyHostToDevice);
         if (e == hipSuccess) e = hipMemcpy(f->dNucRayWeights, padded.data(), padded.size() * sizeof(float), hipMemcpyHostToDevice);
         if (e == hipSuccess) e = hipMemset(f->dStateNuc, 0, sizeof(FieldState));
@@ -769,13 +835,6 @@ static int createField(rtd_handle hh, const rtd_beam* b, const uint32_t dose_dim
     }
     if (fresh) for (auto& ev : f->ev) if (e == hipSuccess) e = hipEventCreate(&ev);
     if (e != hipSuccess) { h->error = std::string("HIP error (field set-up): ") + hipGetErrorString(e); rtd_field_destroy(hh, reinterpret_cast<rtd_field>(f)); return RTD_ERR_HIP; }
-    // (the transfer reads the slices [entry, passive) only, and the superposition's reduce writes every pixel of those: slices
-    //  outside hold stale values that nothing samples; a fresh buffer is cleared once so that a fetch of "bev" reads zeros there)
-    if (fresh) e = hipMemset(f->dBev, 0, P * (size_t)S * sizeof(float));
-    if (fresh && e == hipSuccess && f->dNodeCount) e = hipMemset(f->dNodeCount, 0, nOutTiles * (size_t)S * 32 * sizeof(int));
-    if (fresh && e == hipSuccess && f->dSwCount) e = hipMemset(f->dSwCount, 0, (size_t)S * sizeof(int));
-    if (fresh && e == hipSuccess && f->dSwCountBig) e = hipMemset(f->dSwCountBig, 0, (size_t)S * sizeof(int));
-    if (e != hipSuccess) { h->error = std::string("HIP error (clearing the BEV buffer / node counters): ") + hipGetErrorString(e); rtd_field_destroy(hh, reinterpret_cast<rtd_field>(f)); return RTD_ERR_HIP; }
     *out = reinterpret_cast<rtd_field>(f);
     return RTD_OK;
 }
@@ -863,20 +922,14 @@ int rtd_field_compute_bev(rtd_handle hh, rtd_field ff) {
     const size_t tLds = lutLds + (size_t)3 * kTrRays * kTrPitch * sizeof(float);
     const size_t dLds = lutLds + (size_t)3 * kTdSteps * kTdPitch * sizeof(float);
     if (f->traceMode == 2 && dLds <= 150 * 1024) {
-        if (h->traceDLds < dLds) {
-            RTD_HIP(h, hipFuncSetAttribute(reinterpret_cast<const void*>(k_trace_sample_d), hipFuncAttributeMaxDynamicSharedMemorySize, (int)dLds));
-            h->traceDLds = dLds;
-        }
+        RTD_HIP(h, raiseLdsCap(h, k_trace_sample_d, dLds));
         launchK(k_trace_sample_d, dim3((unsigned)(fc.W / kTdRays), (unsigned)fc.H, (unsigned)((fc.S + kTdSteps - 1) / kTdSteps)), dim3(kTdThreads), dLds, s, f->ev[0], nullptr,
                 (const float*)h->dCt, (int)h->ctDims[0], (int)h->ctDims[1], (int)h->ctDims[2], h->lut, f->tracer, fc.W, fc.H, f->dDensity, f->dWepl, f->dIdd,
                 f->dRrl, h->rrlScale, f->dState, (const float*)f->dSegPos, f->traceDiagB);
     } else if (f->traceMode == 1 && tLds <= 144 * 1024) {
         // the beam runs along the CT x axis: lanes on consecutive steps of one ray (see k_trace_sample_t); 16 rays per block
         // measured best (4 .. 12 rays: 0.107 - 0.133 ms for the stage, 16: 0.100 ms)
-        if (h->traceTLds < tLds) {
-            RTD_HIP(h, hipFuncSetAttribute(reinterpret_cast<const void*>(k_trace_sample_t), hipFuncAttributeMaxDynamicSharedMemorySize, (int)tLds));
-            h->traceTLds = tLds;
-        }
+        RTD_HIP(h, raiseLdsCap(h, k_trace_sample_t, tLds));
         launchK(k_trace_sample_t, dim3((unsigned)((f->R + kTrRays - 1) / kTrRays)), dim3(64, kTrRays), tLds, s, f->ev[0], nullptr,
                 (const float*)h->dCt, (int)h->ctDims[0], (int)h->ctDims[1], (int)h->ctDims[2], h->lut, f->tracer, fc.W, fc.H, f->dDensity, f->dWepl, f->dIdd,
                 f->dRrl, h->rrlScale, f->dState);
@@ -886,21 +939,13 @@ int rtd_field_compute_bev(rtd_handle hh, rtd_field ff) {
                 f->dRrl, h->rrlScale, f->dState, (const float*)f->dSegPos);
     }
     constexpr size_t scanLds = 2 * 2 * kScanChunk * 64 * sizeof(float);   // two buffers of 64 KiB: above the 64 KiB default cap of dynamic LDS
-    if (!h->scanLdsSet) {
-        RTD_HIP(h, hipFuncSetAttribute(reinterpret_cast<const void*>(k_trace_scan), hipFuncAttributeMaxDynamicSharedMemorySize, (int)scanLds));
-        h->scanLdsSet = true;
-    }
-    if (!f->dScanDbg && std::getenv("RTD_SCAN_DEBUG")) {
-        f->scanDbgN = (size_t)8 * (f->R / 64);
-        RTD_HIP(h, hipMalloc((void**)&f->dScanDbg, f->scanDbgN * sizeof(long long)));
-        RTD_HIP(h, hipMemset(f->dScanDbg, 0, f->scanDbgN * sizeof(long long)));
-    }
+    RTD_HIP(h, raiseLdsCap(h, k_trace_scan, scanLds));
     const ResetJob resetJob{f->dLayers, fc.L, reinterpret_cast<unsigned int*>(f->dTileRad), f->tileRadWords, f->dActive, (size_t)4 * fc.L * fc.S,
                             f->dNucIdd, f->dNucRs, fc.nuclearCorr ? (size_t)fc.nucW * fc.nucH * fc.L : (size_t)0,
                             f->dSigMin, f->dSigMax, (size_t)fc.L * fc.S, f->dScanDbg};
     launchK(k_trace_scan, dim3((unsigned)(f->R / 64)), dim3(64, kScanWaves), scanLds, s, nullptr, ev(1), (const float*)f->dIdd, f->dWepl, fc.W, fc.H,
             (unsigned)fc.S, f->dFirstInside, f->dFirstOutside, f->dState, f->dBlockWeplMin, resetJob);
-    if (fc.spotNy <= kPlanConvMaxRows && std::getenv("RTD_SEPARATE_PLAN") == nullptr) {
+    if (fc.spotNy <= kPlanConvMaxRows && !f->sw.separatePlan) {
         // the plan and the spot -> ray convolution in one launch (k_plan_conv): neither reads what the other writes
         launchK(k_plan_conv, dim3(fc.W / 32, (fc.H / 8 + 3) / 4, fc.L + 1), dim3(1024), (size_t)4 * fc.spotNy * 32 * sizeof(float), s, nullptr, ev(2),
                 (const float*)f->dSpotWeights, f->dRayWeights, f->dLayers, f->dState, (const float*)f->dBlockWeplMin, (int)(f->R / 64), f->dWeplMin, fc);
@@ -921,10 +966,6 @@ int rtd_field_compute_bev(rtd_handle hh, rtd_field ff) {
         const dim3 fillGrid(2 * rayGrid.x * rayGrid.y * fc.L);          // (layer, tile, role) items: sigma walk and dose walk of every tile; placement is decided in the kernel
         const dim3 fillBlk = blk;
         const NucFill nucFill{f->dNucSpotIdx, f->dNucRayWeights, f->dNucIdd, f->dNucRs};
-        if (!f->dFillDbg && std::getenv("RTD_FILL_DEBUG")) {
-            f->fillDbgN = (size_t)4 * fillGrid.x;
-            RTD_HIP(h, hipMalloc((void**)&f->dFillDbg, f->fillDbgN * sizeof(long long)));
-        }
         auto launchFill = [&](auto kern, size_t lds) {
             launchK(kern, fillGrid, fillBlk, lds, s, nullptr, ev(3), (const float*)f->dDensity, (const float*)f->dWepl, (const float*)f->dRrl, f->dIdd,
                     f->dRSigma, (const float*)f->dRayWeights, (const int*)f->dFirstInside, (const int*)f->dFirstOutside,
@@ -946,7 +987,7 @@ int rtd_field_compute_bev(rtd_handle hh, rtd_field ff) {
                             tryUniform ? 1 : 0, f->sweepEnabled ? kSwMaxR : -1, f->bgGroups};
     // Once the host knows that the field is not a uniform-sigma one (and without the halo), the sweep's launch plans for itself
     // (k_superpose_sweep<true>: its block 0 is the plan): one launch and its gap less on the critical path.
-    const bool selfPlan = f->sweepEnabled && !tryUniform && !fc.nuclearCorr && std::getenv("RTD_SEPARATE_KS_PLAN") == nullptr;
+    const bool selfPlan = f->sweepEnabled && !tryUniform && !fc.nuclearCorr && !f->sw.separateKsPlan;
     f->selfPlanned = selfPlan;
     // (a field that may be a uniform-sigma one has its 2 x L x S sigma extremes compared by this one block: 1024 threads make that
     //  three memory round trips instead of ten)
@@ -956,26 +997,16 @@ int rtd_field_compute_bev(rtd_handle hh, rtd_field ff) {
         k_nuc_superpose<<<(nPix + 255) / 256, 256, 0, s>>>((const float*)f->dNucIdd, (const float*)f->dNucRs, (const int*)f->dNucEffT,
                                                            (const FieldState*)f->dStateNuc, fc, f->dNucBev);
     }
-    hipEvent_t ksStart = ev(8);
+    hipEvent_t ksStart = ev(7);
     if (tryUniform) {
         // A field with one sigma per slice (water) is superposed as a separable convolution; whether this field is one is known
         // on the device only (FieldState::uniformField): the launch returns at once otherwise, k_superpose_mfma below when it is.
         // A small persistent grid, so that the empty launch of a heterogeneous field costs next to nothing.
         const int nYB = (fc.bevH + 15) / 16;
-        const bool u4 = fc.W <= 16 * (kU2XB - 4) && fc.W % 4 == 0 && std::getenv("RTD_UNIFORM_V2") == nullptr;
-        if (u4) {
+        if (f->uniform4()) {
             // (rtd_uniform.hpp: a block per four row blocks of a slice, the rows within their reach staged layer by layer)
             const int nPartsU4 = (nYB + kU4RB - 1) / kU4RB;
-            if (!h->uni4LdsSet) {
-                RTD_HIP(h, hipFuncSetAttribute(reinterpret_cast<const void*>(k_superpose_uniform4), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                               (int)((kU4Rows + kU4Slack) * (16 * (kU2XB - 4) + 16) * sizeof(float))));
-                h->uni4LdsSet = true;
-            }
-            if (!f->dUniDbg && std::getenv("RTD_UNIFORM_DEBUG")) {
-                f->uniDbgN = (size_t)16 * fc.S * nPartsU4;
-                RTD_HIP(h, hipMalloc((void**)&f->dUniDbg, f->uniDbgN * sizeof(long long)));
-                RTD_HIP(h, hipMemset(f->dUniDbg, 0, f->uniDbgN * sizeof(long long)));
-            }
+            RTD_HIP(h, raiseLdsCap(h, k_superpose_uniform4, (kU4Rows + kU4Slack) * (16 * (kU2XB - 4) + 16) * sizeof(float)));   // (the widest grid's)
             launchK(k_superpose_uniform4, dim3((unsigned)(fc.S * nPartsU4)), dim3(64 * kU4Waves), (size_t)(kU4Rows + kU4Slack) * (fc.W + 16) * sizeof(float), s, ksStart,
                     knownUniform ? f->ev[5] : nullptr, (const float*)f->dIdd, (const LayerPlan*)f->dLayers, (const FieldState*)f->dState, fc,
                     (const unsigned int*)f->dSigMin, (const float*)f->dStepTab, f->dBev, f->dUniDbg);
@@ -999,17 +1030,9 @@ int rtd_field_compute_bev(rtd_handle hh, rtd_field ff) {
     if (runSweep) {
         constexpr size_t swLds = (size_t)kSwLdsWords * sizeof(float);
         static_assert(sizeof(KsPlanLds) <= swLds, "the plan block's LDS is the front of the sweep's");
-        if (!h->sweepLdsSet) {
-            RTD_HIP(h, hipFuncSetAttribute(reinterpret_cast<const void*>(k_superpose_sweep<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)swLds));
-            RTD_HIP(h, hipFuncSetAttribute(reinterpret_cast<const void*>(k_superpose_sweep<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)swLds));
-            h->sweepLdsSet = true;
-        }
+        RTD_HIP(h, raiseLdsCap(h, k_superpose_sweep<false>, swLds));
+        RTD_HIP(h, raiseLdsCap(h, k_superpose_sweep<true>, swLds));
         const unsigned nSwBlocks = (unsigned)(fc.S * f->swPX * f->swPY * f->swGroups) + (selfPlan ? 1u : 0u);
-        if (!f->dSweepDbg && std::getenv("RTD_SWEEP_DEBUG")) {
-            f->sweepDbgN = (size_t)(8 + 4 * 16) * (fc.S * f->swPX * f->swPY * f->swGroups + 1);
-            RTD_HIP(h, hipMalloc((void**)&f->dSweepDbg, f->sweepDbgN * sizeof(long long)));
-            RTD_HIP(h, hipMemset(f->dSweepDbg, 0, f->sweepDbgN * sizeof(long long)));
-        }
         auto launchSweep = [&](auto kern) {
             launchK(kern, dim3(nSwBlocks), dim3(64 * kSwWaves), swLds, s, ksStart, runBig ? nullptr : f->ev[5],
                     (const float*)f->dIdd, (const float*)f->dRSigma, (const unsigned char*)f->dTileRad, (const LayerPlan*)f->dLayers, (const FieldState*)f->dState, fc,
@@ -1020,15 +1043,7 @@ int rtd_field_compute_bev(rtd_handle hh, rtd_field ff) {
     }
     if (runBig) {
         constexpr size_t bgLds = (size_t)kBgLdsWords * sizeof(float);
-        if (!h->sweepBigLdsSet) {
-            RTD_HIP(h, hipFuncSetAttribute(reinterpret_cast<const void*>(k_superpose_sweep_big), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bgLds));
-            h->sweepBigLdsSet = true;
-        }
-        if (!f->dSweepBigDbg && std::getenv("RTD_SWEEP_DEBUG")) {
-            f->sweepBigDbgN = (size_t)48 * fc.S * f->swPX * f->swPY * f->bgGroups;
-            RTD_HIP(h, hipMalloc((void**)&f->dSweepBigDbg, f->sweepBigDbgN * sizeof(long long)));
-            RTD_HIP(h, hipMemset(f->dSweepBigDbg, 0, f->sweepBigDbgN * sizeof(long long)));
-        }
+        RTD_HIP(h, raiseLdsCap(h, k_superpose_sweep_big, bgLds));
         launchK(k_superpose_sweep_big, dim3((unsigned)(fc.S * f->swPX * f->swPY * f->bgGroups)), dim3(64 * kSwWaves), bgLds, s, nullptr, f->ev[5],
                 (const float*)f->dIdd, (const float*)f->dRSigma, (const unsigned char*)f->dTileRad, (const LayerPlan*)f->dLayers, (const FieldState*)f->dState, fc,
                 f->bgGroups, f->swPX, f->swPY, (const int*)f->dActive, f->dSwSlotsBig, f->dSwCountBig, f->dBev, f->dSweepBigDbg);
@@ -1205,12 +1220,7 @@ int rtd_field_wait_plan(rtd_handle hh, rtd_field ff, rtd_field_info* info, size_
     RTD_HIP(h, hipSetDevice(h->device));
     RTD_HIP(h, hipEventSynchronize(f->selfPlanned ? f->ev[5] : f->ev[4]));   // (a launch that planned for itself: its plan is complete when the superposition is)
     const FieldState st = *f->hState;                                // mirrored by the plan into pinned host memory
-    // (the finding belongs to the inputs the compute was LAUNCHED under: CT, LUTs or options may have changed since)
-    if (f->triedUniform) { f->uniformHint = st.uniformField ? 1 : 0; f->hintEpoch = f->launchEpoch; }
-    else if (f->hintEpoch != f->launchEpoch) { f->uniformHint = -1; f->hintEpoch = f->launchEpoch; }
-    f->radiusHint = (st.errorFlags || st.empty) ? -1 : st.maxRadius;   // (valid under hintEpoch, like the uniform hint)
-    if (f->launchedKnownUniform && !st.uniformField && !st.errorFlags && !st.empty)
-        return fail(h, RTD_ERR_NOT_READY, "the field was launched as a uniform-sigma field but is not one: its inputs were modified in place; call rtd_set_ct* again and recompute");
+    { const int r = takeFindings(h, f, st); if (r != RTD_OK) return r; }
     if (info) fillInfo(f, st, info);
     if (packed_bytes) {
         const int nz = std::max(st.firstCalculatedPassive - st.beamFirstInside, 0);
@@ -1279,13 +1289,7 @@ int rtd_field_finish(rtd_handle hh, rtd_field ff, rtd_timing* timing, rtd_field_
     const int last = f->transferred ? 6 : 5;                         // BEV only: the superposition's reduce is the last kernel
     RTD_HIP(h, hipEventSynchronize(f->ev[last]));
     const FieldState st = *f->hState;                                // mirrored by k_ks_plan into pinned host memory
-    if (f->triedUniform) { f->uniformHint = st.uniformField ? 1 : 0; f->hintEpoch = f->launchEpoch; }
-    else if (f->hintEpoch != f->launchEpoch) { f->uniformHint = -1; f->hintEpoch = f->launchEpoch; }
-    f->radiusHint = (st.errorFlags || st.empty) ? -1 : st.maxRadius;   // (valid under hintEpoch, like the uniform hint)
-    // A compute that skipped the general kernel (hint: uniform) on a field the device then found heterogeneous has written no BEV
-    // dose: only possible when the caller changed a bound device volume in place (rtd_set_ct_device) without telling the handle.
-    if (f->launchedKnownUniform && !st.uniformField && !st.errorFlags && !st.empty)
-        return fail(h, RTD_ERR_NOT_READY, "the field was launched as a uniform-sigma field but is not one: its inputs were modified in place; call rtd_set_ct* again and recompute");
+    { const int r = takeFindings(h, f, st); if (r != RTD_OK) return r; }
     if (timing) {
         std::memset(timing, 0, sizeof *timing);
         RTD_HIP(h, hipEventElapsedTime(&timing->total_ms, f->ev[0], f->ev[last]));
@@ -1293,10 +1297,10 @@ int rtd_field_finish(rtd_handle hh, rtd_field ff, rtd_timing* timing, rtd_field_
             RTD_HIP(h, hipEventElapsedTime(&timing->raytracing_ms, f->ev[0], f->ev[1]));
             RTD_HIP(h, hipEventElapsedTime(&timing->prepare_energy_loop_ms, f->ev[1], f->ev[2]));
             RTD_HIP(h, hipEventElapsedTime(&timing->fill_idd_sigma_ms, f->ev[2], f->ev[3]));
-            hipEvent_t planEnd = f->selfPlanned ? f->ev[8] : f->ev[4];   // (self-planned: the plan is inside the superposition launch)
+            hipEvent_t planEnd = f->selfPlanned ? f->ev[7] : f->ev[4];   // (self-planned: the plan is inside the superposition launch)
             RTD_HIP(h, hipEventElapsedTime(&timing->prepare_superp_ms, f->ev[3], planEnd));
             RTD_HIP(h, hipEventElapsedTime(&timing->superp_ms, planEnd, f->ev[5]));
-            RTD_HIP(h, hipEventElapsedTime(&timing->superp_kernel_ms, f->ev[8], f->ev[5]));
+            RTD_HIP(h, hipEventElapsedTime(&timing->superp_kernel_ms, f->ev[7], f->ev[5]));
             if (f->transferred) RTD_HIP(h, hipEventElapsedTime(&timing->transforming_ms, f->ev[5], f->ev[6]));
         }
         timing->superp_launches = 1;   // k_superpose_mfma, all layers and radii (the reference: up to 33 launches per layer)
@@ -1330,17 +1334,8 @@ int rtd_field_spot_gradient(rtd_handle hh, rtd_field ff, const float* dev_voxel_
     const size_t P = (size_t)fc.bevW * fc.bevH, nRw = f->R * (size_t)fc.L;
     const int nChunks = (fc.S + kAdjChunk - 1) / kAdjChunk;
     if (!f->dGradBev) {
-        int st = devAlloc(h, &f->dGradBev, P * fc.S);
-        if (st == RTD_OK) st = devAlloc(h, &f->dGradRw, nRw);
-        if (st == RTD_OK) st = devAlloc(h, &f->dAdjPart, nRw * nChunks);
-        if (st == RTD_OK) st = devAlloc(h, &f->dAdjInterm, (size_t)fc.L * fc.spotNy * fc.W);
-        if (st == RTD_OK) st = devAlloc(h, &f->dAdjWalk, nRw * nChunks);
-        if (st != RTD_OK) {
-            for (float** p : {&f->dGradBev, &f->dGradRw, &f->dAdjPart, &f->dAdjInterm}) { if (*p) (void)hipFree(*p); *p = nullptr; }
-            if (f->dAdjWalk) (void)hipFree(f->dAdjWalk);
-            f->dAdjWalk = nullptr;
-            return st;
-        }
+        const int st = allocBuffers(h, f, kGradient);
+        if (st != RTD_OK) { freeBuffers(f, kGradient); return st; }
     }
     hipStream_t s = h->stream;
     const FieldState* st = f->dState;
@@ -1409,30 +1404,19 @@ int rtd_field_fetch(rtd_handle hh, rtd_field ff, const char* name, void* host_ou
     auto* f = reinterpret_cast<rtd_field_impl*>(ff);
     if (!h || !f || !name) return RTD_ERR_INVALID_ARG;
     const FieldConst& fc = f->fc;
-    const size_t R = f->R, S = fc.S, L = fc.L, tiles = (size_t)fc.tilesX * fc.tilesY;
+    const size_t S = fc.S, L = fc.L, tiles = (size_t)fc.tilesX * fc.tilesY;
     const void* src = nullptr; size_t n = 0;
     std::string nm(name);
     std::vector<char> staging;
     RTD_HIP(h, hipStreamSynchronize(h->stream));
-    if (nm == "density") { src = f->dDensity; n = 4 * R * S; }
-    else if (nm == "wepl") { src = f->dWepl; n = 4 * R * S; }
-    else if (nm == "first_inside") { src = f->dFirstInside; n = 4 * R; }
-    else if (nm == "first_outside") { src = f->dFirstOutside; n = 4 * R; }
-    else if (nm == "wepl_min") { src = f->dWeplMin; n = 4 * S; }
-    else if (nm == "ray_weights") { src = f->dRayWeights; n = 4 * R * L; }
-    else if (nm == "idd") { src = f->dIdd; n = 4 * R * S * L; }
-    else if (nm == "rsigma") { src = f->dRSigma; n = 4 * R * S * L; }
-    else if (nm == "first_passive") { src = f->dFirstPassive; n = 4 * R * L; }
-    else if (nm == "tile_radius") { src = f->dTileRad; n = L * S * tiles; }
-    else if (nm == "bev") { src = f->dBev; n = 4 * (size_t)fc.bevW * fc.bevH * S; }
-    else if (nm == "grad_bev" && f->gradDone) { src = f->dGradBev; n = 4 * (size_t)fc.bevW * fc.bevH * S; }
-    else if (nm == "grad_ray_weights" && f->gradDone) { src = f->dGradRw; n = 4 * R * L; }
-    else if (nm == "fill_debug" && f->dFillDbg) { src = f->dFillDbg; n = f->fillDbgN * sizeof(long long); }
-    else if (nm == "uniform_debug" && f->dUniDbg) { src = f->dUniDbg; n = f->uniDbgN * sizeof(long long); }
-    else if (nm == "sweep_debug" && f->dSweepDbg) { src = f->dSweepDbg; n = f->sweepDbgN * sizeof(long long); }
-    else if (nm == "sweep_big_debug" && f->dSweepBigDbg) { src = f->dSweepBigDbg; n = f->sweepBigDbgN * sizeof(long long); }
-    else if (nm == "scan_debug" && f->dScanDbg) { src = f->dScanDbg; n = f->scanDbgN * sizeof(long long); }
-    else if (nm == "eff_radius" || nm == "layer_plan") {
+    bool found = false;   // (grad_* only after a gradient, *_debug only when allocated)
+    f->forEachBuffer([&](auto*& p, size_t count, BufClass c, bool, const char* fetchName) {
+        if (found || !fetchName || nm != fetchName || (c == kGradient && !f->gradDone) || (c == kDiag && !p)) return;
+        found = true; src = p; n = count * sizeof *p;
+    });
+    if (found) {
+        if (nm == "tile_radius") n = L * S * tiles;   // (the allocation is rounded up to whole 32-bit words)
+    } else if (nm == "eff_radius" || nm == "layer_plan") {
         std::vector<LayerPlan> lp(L);
         RTD_HIP(h, hipMemcpy(lp.data(), f->dLayers, L * sizeof(LayerPlan), hipMemcpyDeviceToHost));
         if (nm == "eff_radius") {

@@ -299,12 +299,44 @@ def test_released_workspace_is_taken_over(engine, synth):
         np.testing.assert_array_equal(out, want)
         eng.device_free(d)
 
+    # A workspace whose field has run a spot gradient: the field of the same shape that takes it over computes a dose and a gradient,
+    # and everything it can fetch equals, bit for bit, what the released field fetched when it was freshly created.
+    beam = scn.beams[0]
+    names = ("density", "wepl", "first_inside", "first_outside", "wepl_min", "ray_weights", "idd", "rsigma", "first_passive",
+             "tile_radius", "bev", "eff_radius", "layer_plan", "grad_bev", "grad_ray_weights")
+    n_grad = np.asarray(beam.spotWeights).size
+    with engine.Engine(0) as eng:
+        eng.set_luts(scn.luts)
+        eng.set_ct(scn.ct)
+        d, d_g, d_out = eng.device_alloc(4 * n), eng.device_alloc(4 * n), eng.device_alloc(4 * n_grad)
+        eng.to_device(d_g, np.random.default_rng(7).random(scn.ct.shape, dtype=np.float32))
 
-def test_released_workspace_is_not_taken_over_by_a_transposed_ray_grid(engine, synth):
-    """Two beams with the same number of rays, steps, layers and spots but transposed ray grids (64 x 32 against 32 x 64) need
-    different workspaces: the padded BEV cube is (W + 64) x (H + 64) x S and the superposition's hand-off slots / node counters
-    scale with ceil(bevW / 64) * ceil(bevH / 32) (6 against 8 output tiles here). A released workspace must only go to a field of
-    the same W AND H; the result of the second beam equals a fresh engine's bit for bit."""
+        def run():
+            f = eng.create_field(beam, scn.dims)
+            eng.device_zero(d, 4 * n)
+            f.compute(d)
+            f.finish()
+            f.spot_gradient(d_g, d_out)
+            dose, grad = np.empty_like(scn.ct), np.empty(n_grad, dtype=np.float32)
+            eng.to_host(dose, d)
+            eng.to_host(grad, d_out)
+            return f, [dose, grad] + [f.fetch(k).copy() for k in names]
+        fresh, want = run()
+        fresh.release()
+        taker, got = run()
+        taker.destroy()
+        for k, w, g in zip(("dose", "spot_gradient") + names, want, got):
+            assert w.dtype == g.dtype and np.array_equal(w.view(np.uint8), g.view(np.uint8)), k
+        for p in (d, d_g, d_out):
+            eng.device_free(p)
+
+
+def test_released_workspace_is_not_taken_over_by_a_transposed_ray_grid(engine, synth, monkeypatch):
+    """Two beams with the same number of rays, steps, layers and spots but transposed ray grids (64 x 32 against 32 x 64). A released
+    workspace goes to a new field only if every buffer has the size the new field needs. The padded BEV cube, (W + 64) x (H + 64) x S,
+    and the sweep's buffers have the same sizes here; under RTD_NO_SWEEP the node counters of k_superpose_mfma scale with
+    ceil(bevW / 64) * ceil(bevH / 32) (6 against 8 output tiles), so the second field allocates its own workspace there. Either
+    way the result of the second beam equals a fresh engine's bit for bit."""
     ct, _ = scenarios.hetero_phantom(64)
 
     def beam_of(spots, pitch):
@@ -313,26 +345,31 @@ def test_released_workspace_is_not_taken_over_by_a_transposed_ray_grid(engine, s
     a, b = beam_of((4, 1), 9.0), beam_of((2, 2), (1.0, 27.0))
     scn = scenarios.hetero_ct(synth, n=64, spots=2, pitch=4.0, n_layers=2, angles=[0.0], steps=160, ct=ct)
     n = scn.n_voxels
-    want = _sequential(engine, scenarios.Scenario("b", synth, ct, scn.spacing, [b]))
-    with engine.Engine(0) as eng:
-        eng.set_luts(synth)
-        eng.set_ct(ct)
-        d = eng.device_alloc(4 * n)
-        fa = eng.create_field(a, scn.dims)
-        eng.device_zero(d, 4 * n)
-        fa.compute(d)
-        _, ia = fa.finish()
-        fa.release()
-        fb = eng.create_field(b, scn.dims)
-        eng.device_zero(d, 4 * n)
-        fb.compute(d)
-        _, ib = fb.finish()
-        assert ia["ray_dims"][:2] == [64, 32] and ib["ray_dims"][:2] == [32, 64], (ia["ray_dims"], ib["ray_dims"])
-        out = np.empty_like(ct)
-        eng.to_host(out, d)
-        np.testing.assert_array_equal(out, want)
-        fb.release()
-        eng.device_free(d)
+    for no_sweep in (None, "1"):
+        if no_sweep is None:
+            monkeypatch.delenv("RTD_NO_SWEEP", raising=False)
+        else:
+            monkeypatch.setenv("RTD_NO_SWEEP", no_sweep)
+        want = _sequential(engine, scenarios.Scenario("b", synth, ct, scn.spacing, [b]))
+        with engine.Engine(0) as eng:
+            eng.set_luts(synth)
+            eng.set_ct(ct)
+            d = eng.device_alloc(4 * n)
+            fa = eng.create_field(a, scn.dims)
+            eng.device_zero(d, 4 * n)
+            fa.compute(d)
+            _, ia = fa.finish()
+            fa.release()
+            fb = eng.create_field(b, scn.dims)
+            eng.device_zero(d, 4 * n)
+            fb.compute(d)
+            _, ib = fb.finish()
+            assert ia["ray_dims"][:2] == [64, 32] and ib["ray_dims"][:2] == [32, 64], (ia["ray_dims"], ib["ray_dims"])
+            out = np.empty_like(ct)
+            eng.to_host(out, d)
+            np.testing.assert_array_equal(out, want)
+            fb.release()
+            eng.device_free(d)
 
 
 def test_uniform_hint_belongs_to_the_inputs_of_the_launch(orc, engine, synth):
