@@ -327,6 +327,36 @@ int rtd_spot_gradient(rtd_handle h, const rtd_beam* beams, int n_beams, const fl
                       float* spot_grad_out);
 
 /*
+ * ---- Dose-influence matrix (Dij): per-spot sparse dose columns of a field ----
+ *
+ * Dij belongs to a local field, on that field's dose grid, under the options the field was created with. Column j is spot
+ * j = (l * ny + sy) * nx + sx, in the [L][ny][nx] order of spot_weights and of rtd_field_spot_gradient; row v is the linear voxel
+ * index of the dose grid (x fastest), as int32. Column j is the dose the field adds to the volume when spot j has weight 1 and every
+ * other spot weight 0. So Dij w = D(w) (rtd_field_compute) and Dij^T g = rtd_field_spot_gradient(g).
+ *
+ * options.ray_weight_cutoff must be 0 (else RTD_ERR_INVALID_ARG): only then is the forward linear in the spot weights with a live set
+ * that does not depend on them. rel_threshold in [0, 1): entry v of column j is kept iff value != 0 and value >= rel_threshold *
+ * max(column j); with 0 every non-zero is kept. Spots with no dose get empty columns.
+ *
+ * rtd_field_dose_influence       computes Dij and keeps it on the device as CSC: col_ptr int64[n_spots + 1], row_idx int32[nnz]
+ *                                (strictly ascending within a column), values float32[nnz]; returns nnz. No prior compute is needed.
+ *                                Bitwise reproducible: the same field, inputs and threshold give the same arrays. No side effects: on
+ *                                return, the field's BEV dose, its state record and everything a later rtd_field_transfer*,
+ *                                rtd_field_clear_dose* or rtd_field_spot_gradient reads are those of a compute at the field's own
+ *                                weights (the call ends with one). Synchronous. The CSC lives with the field: the next call replaces it,
+ *                                release or destroy frees it. RTD_ERR_INVALID_ARG for nuclear_corr, a remote field, a null pointer or a
+ *                                threshold outside [0, 1); RTD_ERR_RADIUS_OVERFLOW as rtd_field_finish. Not on the rtd_plan_* path.
+ * rtd_field_dose_influence_copy  copies the last result; the three pointers may be host or device memory.
+ * rtd_field_set_spot_weights     new spot weights [L][ny][nx] (device memory), copied on the handle's stream. What the field learned
+ *                                from its last compute is forgotten; the next rtd_field_compute gives, bit for bit, what a fresh
+ *                                rtd_field_create with these weights gives. Not for remote fields.
+ * rtd_field_fetch name of the last Dij call: "dij_batch" [L][ny][nx] int32, the batch each spot was computed in (-1: empty column).
+ */
+int rtd_field_dose_influence(rtd_handle h, rtd_field f, float rel_threshold, size_t* nnz);
+int rtd_field_dose_influence_copy(rtd_handle h, rtd_field f, int64_t* col_ptr, int32_t* row_idx, float* values);
+int rtd_field_set_spot_weights(rtd_handle h, rtd_field f, const float* dev_spot_weights);
+
+/*
  * ---- Multi-GPU plans behind the boundary (SURVEY.md 8(b) "Threading": one handle and one host thread per device) ----
  *
  * rtd_plan is the reference-shaped call on several GPUs of one process: the 4-beam cudaWrapperProtons of the C++ shim uses

@@ -29,6 +29,7 @@
 #include "rtd_sweep_big.hpp"
 #include "rtd_uniform.hpp"
 #include "rtd_adjoint.hpp"
+#include "rtd_dij.hpp"
 
 using namespace rtd;
 
@@ -91,8 +92,9 @@ Switches readSwitches() {
 }
 
 // Classes of a field's device buffers: the workspace that a field of the same shape takes over (rtd_field_release), the NUCLEAR_CORR
-// halo, the spot-weight gradient's (allocated by its first call), the RTD_*_DEBUG clock stamps.
-enum BufClass : unsigned { kShape = 1, kNuclear = 2, kGradient = 4, kDiag = 8, kAllBufs = 15 };
+// halo, the spot-weight gradient's (allocated by its first call), the RTD_*_DEBUG clock stamps, the dose-influence matrix's workspace
+// and its result (rtd_field_dose_influence: allocated by its first call, the result replaced by every call).
+enum BufClass : unsigned { kShape = 1, kNuclear = 2, kGradient = 4, kDiag = 8, kDij = 16, kDijOut = 32, kAllBufs = 63 };
 
 struct rtd_field_impl {
     Switches sw;
@@ -161,6 +163,16 @@ struct rtd_field_impl {
     float *dGradBev = nullptr, *dGradRw = nullptr, *dAdjPart = nullptr, *dAdjInterm = nullptr;
     float4* dAdjWalk = nullptr;   // [chunk][L][H][W] the dose walk's state in front of every chunk of k_adj_superpose
     bool gradDone = false;        // a gradient has been launched: grad_bev / grad_ray_weights hold the last one's intermediates
+    // dose-influence matrix (rtd_field_dose_influence, rtd_dij.hpp): workspace allocated by the first call; the batch-major staging
+    // (dijCap entries) grows geometrically; the CSC result (dijNnz entries) is replaced by every call
+    float *dDijSave = nullptr, *dDijDose = nullptr, *dDijValsB = nullptr, *dDijVals = nullptr;
+    unsigned short* dDijOwner = nullptr;
+    int *dDijFoot = nullptr, *dDijList = nullptr, *dDijBoxes = nullptr, *dDijCnt = nullptr, *dDijMisc = nullptr, *dDijRowsB = nullptr, *dDijRows = nullptr;
+    unsigned int* dDijColMax = nullptr;
+    long long *dDijColLen = nullptr, *dDijColSrc = nullptr, *dDijColPtr = nullptr;
+    size_t dijCap = 0, dijNnz = 0;
+    bool dijDone = false;          // the CSC buffers hold the last call's result
+    std::vector<int> dijBatchOf;   // per spot: its batch in the last call (-1: empty column); rtd_field_fetch "dij_batch"
     std::vector<size_t> released; // released: the element counts of its shape buffers (a new field takes it over if its own are the same)
 
     bool uniform4() const { return fc.W <= 16 * (kU2XB - 4) && fc.W % 4 == 0 && !sw.uniformV2; }   // k_superpose_uniform4, else _uniform2
@@ -201,6 +213,15 @@ struct rtd_field_impl {
         visit(dGradBev, P * S, kGradient, false, "grad_bev"); visit(dGradRw, R * L, kGradient, false, "grad_ray_weights");
         visit(dAdjPart, R * L * nChunks, kGradient, false, nullptr); visit(dAdjWalk, R * L * nChunks, kGradient, false, nullptr);
         visit(dAdjInterm, L * fc.spotNy * fc.W, kGradient, false, nullptr);
+        const size_t nSpot = (size_t)fc.spotNx * fc.spotNy * L, dijSpots = std::min(nSpot, (size_t)kDijMaxSpots);
+        visit(dDijSave, nSpot, kDij, false, nullptr); visit(dDijDose, (size_t)doseDims[0] * doseDims[1] * doseDims[2], kDij, false, nullptr);
+        visit(dDijOwner, P, kDij, false, nullptr); visit(dDijFoot, 2 * L * (size_t)(fc.spotNx + fc.spotNy), kDij, false, nullptr);
+        visit(dDijList, nSpot, kDij, false, nullptr); visit(dDijBoxes, 4 * nSpot, kDij, false, nullptr);
+        visit(dDijCnt, (size_t)kDijBlocks * dijSpots, kDij, false, nullptr); visit(dDijColMax, dijSpots, kDij, false, nullptr);
+        visit(dDijMisc, (size_t)4, kDij, true, nullptr); visit(dDijColLen, nSpot, kDij, false, nullptr); visit(dDijColSrc, nSpot, kDij, false, nullptr);
+        visit(dDijRowsB, dijCap, kDij, false, nullptr); visit(dDijValsB, dijCap, kDij, false, nullptr);
+        visit(dDijColPtr, nSpot + 1, kDijOut, false, nullptr); visit(dDijRows, std::max<size_t>(dijNnz, 1), kDijOut, false, nullptr);
+        visit(dDijVals, std::max<size_t>(dijNnz, 1), kDijOut, false, nullptr);
         visit(dScanDbg, sw.scanDebug ? 8 * (R / 64) : 0, kDiag, true, "scan_debug");
         visit(dFillDbg, sw.fillDebug ? 4 * 2 * tiles * L : 0, kDiag, false, "fill_debug");
         visit(dUniDbg, sw.uniformDebug && uniformEligible && uniform4() ? 16 * S * nPartsU4 : 0, kDiag, true, "uniform_debug");
@@ -608,8 +629,9 @@ int rtd_field_release(rtd_handle hh, rtd_field ff) {
     (void)hipSetDevice(h->device);
     (void)hipStreamSynchronize(h->stream);      // its kernels have drained: the next owner uploads with plain copies
     f->computed = false; f->transferred = false;
-    freeBuffers(f, kGradient | kDiag);          // (not part of the shape's workspace)
+    freeBuffers(f, kGradient | kDiag | kDij | kDijOut);   // (not part of the shape's workspace)
     f->gradDone = false;
+    f->dijDone = false; f->dijCap = 0; f->dijNnz = 0; f->dijBatchOf.clear();
     f->released = shapeCounts(f);
     h->fieldCache.push_back(f);
     return RTD_OK;
@@ -1399,6 +1421,237 @@ int rtd_spot_gradient(rtd_handle hh, const rtd_beam* beams, int n_beams, const f
     return st;
 }
 
+// New spot weights for a field, on the handle's stream (device -> device). What the field learned from its last compute (uniform-sigma
+// and radius hints) is forgotten: with a ray-weight cut-off above 0 the live set moves with the weights.
+int rtd_field_set_spot_weights(rtd_handle hh, rtd_field ff, const float* dev_spot_weights) {
+    auto* h = reinterpret_cast<rtd_handle_impl*>(hh);
+    auto* f = reinterpret_cast<rtd_field_impl*>(ff);
+    if (!h || !f) return RTD_ERR_INVALID_ARG;
+    if (!dev_spot_weights) return fail(h, RTD_ERR_INVALID_ARG, "rtd_field_set_spot_weights: null device pointer");
+    if (f->remote) return fail(h, RTD_ERR_INVALID_ARG, "rtd_field_set_spot_weights: a remote field has no workspace");
+    RTD_HIP(h, hipSetDevice(h->device));
+    const FieldConst& fc = f->fc;
+    const size_t nx = fc.spotNx, ny = fc.spotNy;
+    RTD_HIP(h, hipMemcpyAsync(f->dSpotWeights, dev_spot_weights, nx * ny * fc.L * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
+    if (fc.nuclearCorr)      // the halo's padded copy of the weights (extendAndPadd at creation; the padding stays zero)
+        for (int l = 0; l < fc.L; ++l)
+            RTD_HIP(h, hipMemcpy2DAsync(f->dNucRayWeights + (size_t)l * fc.nucW * fc.nucH, (size_t)fc.nucW * sizeof(float),
+                                        dev_spot_weights + (size_t)l * nx * ny, nx * sizeof(float), nx * sizeof(float), ny,
+                                        hipMemcpyDeviceToDevice, h->stream));
+    f->uniformHint = -1; f->radiusHint = -1;
+    return RTD_OK;
+}
+
+// Dose-influence matrix of a field (include/rtd.h; kernels in rtd_dij.hpp). One forward at the field's own
+// weights gives the largest batch radius Rmax and the entry plane; the exact spot -> ray footprints come back from the device; the
+// spots are coloured greedily, in spot order, into batches whose footprints grown by Rmax + 2 rays are disjoint; every batch is one
+// forward at unit weights on its spots, transferred into a scratch volume and split by owner into per-spot columns. A last forward at
+// the field's own weights restores every buffer a later transfer, clear or gradient reads.
+int rtd_field_dose_influence(rtd_handle hh, rtd_field ff, float rel_threshold, size_t* nnz) {
+    auto* h = reinterpret_cast<rtd_handle_impl*>(hh);
+    auto* f = reinterpret_cast<rtd_field_impl*>(ff);
+    if (!h || !f) return RTD_ERR_INVALID_ARG;
+    if (!nnz) return fail(h, RTD_ERR_INVALID_ARG, "rtd_field_dose_influence: null nnz pointer");
+    if (!(rel_threshold >= 0.0f && rel_threshold < 1.0f)) return fail(h, RTD_ERR_INVALID_ARG, "rtd_field_dose_influence: rel_threshold must lie in [0, 1)");
+    if (f->remote) return fail(h, RTD_ERR_INVALID_ARG, "rtd_field_dose_influence: a remote field has no workspace");
+    if (f->fc.nuclearCorr) return fail(h, RTD_ERR_INVALID_ARG, "rtd_field_dose_influence: not available with nuclear_corr");
+    if (f->fc.rayWeightCutoff != 0.0f)
+        return fail(h, RTD_ERR_INVALID_ARG, "rtd_field_dose_influence: needs options.ray_weight_cutoff = 0 when the field is created (only then is the dose linear in the spot weights)");
+    if (!h->dCt || !h->haveLuts) return fail(h, RTD_ERR_NOT_READY, "rtd_field_dose_influence: set LUTs and CT first");
+    const FieldConst& fc = f->fc;
+    const size_t nVox = (size_t)f->doseDims[0] * f->doseDims[1] * f->doseDims[2];
+    if (nVox > (size_t)0x7fffffff) return fail(h, RTD_ERR_INVALID_ARG, "rtd_field_dose_influence: more than 2^31 - 1 dose voxels (int32 row indices)");
+    RTD_HIP(h, hipSetDevice(h->device));
+    hipStream_t s = h->stream;
+    const size_t nSpot = (size_t)fc.spotNx * fc.spotNy * fc.L;
+    f->dijDone = false;
+    if (!f->dDijSave) {
+        f->dijCap = (size_t)1 << 20;
+        const int st = allocBuffers(h, f, kDij);
+        if (st != RTD_OK) { freeBuffers(f, kDij); f->dijCap = 0; return st; }
+    }
+    // 1. the forward at the field's own weights: Rmax, the entry plane, the field's findings
+    { const int st = rtd_field_compute_bev(hh, ff); if (st != RTD_OK) return st; }
+    RTD_HIP(h, hipStreamSynchronize(s));
+    const FieldState own = *f->hState;
+    { const int st = takeFindings(h, f, own); if (st != RTD_OK) return st; }
+    if (own.errorFlags & kErrRadiusOverflow) return fail(h, RTD_ERR_RADIUS_OVERFLOW, "Found larger than allowed kernel superposition radius");
+    const int rMax = own.maxRadius;
+    const int saveUniform = f->uniformHint, saveRadius = f->radiusHint;
+    const unsigned saveEpoch = f->hintEpoch;
+    // 2. footprints, exactly as the convolution's loops visit the spots
+    std::vector<int> footX(2 * nSpot / fc.spotNy), footY(2 * nSpot / fc.spotNx);
+    {
+        const int nT = fc.L * (fc.spotNx + fc.spotNy);
+        k_dij_footprint<<<(nT + 255) / 256, 256, 0, s>>>((const LayerPlan*)f->dLayers, (const FieldState*)f->dState, fc, f->dDijFoot,
+                                                       f->dDijFoot + footX.size());
+        RTD_HIP(h, hipGetLastError());
+        RTD_HIP(h, hipMemcpyAsync(footX.data(), f->dDijFoot, footX.size() * sizeof(int), hipMemcpyDeviceToHost, s));
+        RTD_HIP(h, hipMemcpyAsync(footY.data(), f->dDijFoot + footX.size(), footY.size() * sizeof(int), hipMemcpyDeviceToHost, s));
+        RTD_HIP(h, hipStreamSynchronize(s));
+    }
+    // 3. batches: first fit in spot order over occupancy bitmaps of the padded BEV grid
+    const int bevW = fc.bevW, bevH = fc.bevH, words = (bevW + 63) / 64, grow = rMax + 2;
+    std::vector<std::array<int, 4>> box(nSpot);
+    std::vector<std::vector<uint64_t>> occ;
+    std::vector<std::vector<int>> members;
+    f->dijBatchOf.assign(nSpot, -1);
+    auto meets = [&](const std::vector<uint64_t>& bm, const std::array<int, 4>& b) {
+        for (int y = b[1]; y <= b[3]; ++y)
+            for (int w = b[0] / 64; w <= b[2] / 64; ++w) {
+                const int lo = std::max(b[0], 64 * w) - 64 * w, hi = std::min(b[2], 64 * w + 63) - 64 * w;
+                const uint64_t m = (hi == 63 ? ~0ull : ((1ull << (hi + 1)) - 1)) & ~((1ull << lo) - 1);
+                if (bm[(size_t)y * words + w] & m) return true;
+            }
+        return false;
+    };
+    for (size_t j = 0; j < nSpot; ++j) {
+        const size_t l = j / ((size_t)fc.spotNx * fc.spotNy), sy = (j / fc.spotNx) % fc.spotNy, sx = j % fc.spotNx;
+        const int* fx = &footX[2 * (l * fc.spotNx + sx)];
+        const int* fy = &footY[2 * (l * fc.spotNy + sy)];
+        if (fx[1] < fx[0] || fy[1] < fy[0]) continue;                // no ray sees the spot: an empty column
+        std::array<int, 4>& b = box[j];
+        b = {std::max(fx[0] + kMaxSuperpR - grow, 0), std::max(fy[0] + kMaxSuperpR - grow, 0),
+             std::min(fx[1] + kMaxSuperpR + grow, bevW - 1), std::min(fy[1] + kMaxSuperpR + grow, bevH - 1)};
+        size_t k = 0;
+        while (k < occ.size() && (members[k].size() >= (size_t)kDijMaxSpots || meets(occ[k], b))) ++k;
+        if (k == occ.size()) { occ.emplace_back((size_t)bevH * words, 0ull); members.emplace_back(); }
+        for (int y = b[1]; y <= b[3]; ++y) for (int x = b[0]; x <= b[2]; ++x) occ[k][(size_t)y * words + x / 64] |= 1ull << (x % 64);
+        members[k].push_back((int)j);
+        f->dijBatchOf[j] = (int)k;
+    }
+    occ.clear();
+    std::vector<int> list, boxes;
+    std::vector<size_t> first(members.size() + 1, 0);
+    for (size_t k = 0; k < members.size(); ++k) {
+        first[k] = list.size();
+        for (int j : members[k]) { list.push_back(j); boxes.insert(boxes.end(), box[(size_t)j].begin(), box[(size_t)j].end()); }
+    }
+    first[members.size()] = list.size();
+    std::vector<long long> colLen(nSpot, 0);
+    long long total = 0;
+    int dijErr = 0;
+    int st = RTD_OK;
+    auto hipFail = [&](hipError_t e) { h->error = std::string("HIP error (dose influence): ") + hipGetErrorString(e); st = RTD_ERR_HIP; };
+    hipError_t e = hipSuccess;
+    if (!list.empty()) {
+        e = hipMemcpyAsync(f->dDijList, list.data(), list.size() * sizeof(int), hipMemcpyHostToDevice, s);
+        if (e == hipSuccess) e = hipMemcpyAsync(f->dDijBoxes, boxes.data(), boxes.size() * sizeof(int), hipMemcpyHostToDevice, s);
+        if (e == hipSuccess) e = hipMemcpyAsync(f->dDijSave, f->dSpotWeights, nSpot * sizeof(float), hipMemcpyDeviceToDevice, s);
+        if (e == hipSuccess) e = hipMemsetAsync(f->dDijDose, 0, nVox * sizeof(float), s);
+        if (e == hipSuccess) e = hipMemsetAsync(f->dDijMisc, 0, 4 * sizeof(int), s);
+        if (e == hipSuccess) e = hipMemsetAsync(f->dDijColLen, 0, nSpot * sizeof(long long), s);
+        if (e == hipSuccess) e = hipMemsetAsync(f->dDijColSrc, 0, nSpot * sizeof(long long), s);
+        if (e == hipSuccess) e = hipStreamSynchronize(s);             // (the host vectors above are pageable)
+        if (e != hipSuccess) hipFail(e);
+        // the batches run without the field's hints: each one is planned (uniform-sigma detection, second sweep launch) on its own
+        f->uniformHint = -1; f->radiusHint = -1;
+    }
+    // 4. per batch: unit weights, owner map, forward + transfer into the scratch volume, split, clear of its dose box
+    for (size_t k = 0; k < members.size() && st == RTD_OK; ++k) {
+        const int n = (int)(first[k + 1] - first[k]);
+        const int* dList = f->dDijList + first[k];
+        e = hipMemsetAsync(f->dSpotWeights, 0, nSpot * sizeof(float), s);
+        if (e == hipSuccess) e = hipMemsetAsync(f->dDijOwner, 0xFF, (size_t)bevW * bevH * sizeof(unsigned short), s);
+        if (e != hipSuccess) { hipFail(e); break; }
+        k_dij_weights<<<(n + 255) / 256, 256, 0, s>>>(f->dSpotWeights, dList, n);
+        k_dij_owner<<<n, 256, 0, s>>>(f->dDijOwner, bevW, f->dDijBoxes + 4 * first[k]);
+        if ((e = hipGetLastError()) != hipSuccess) { hipFail(e); break; }
+        f->uniformHint = -1; f->radiusHint = -1;
+        st = rtd_field_compute_bev(hh, ff);
+        if (st == RTD_OK) st = transferImpl(hh, ff, f->dDijDose, nullptr, nullptr, false);
+        if (st != RTD_OK) break;
+        k_dij_check<<<1, 64, 0, s>>>((const FieldState*)f->dState, rMax, f->dDijMisc + 1);
+        const size_t lds = (size_t)n * sizeof(unsigned int);
+        auto split = [&](auto kern) {
+            kern<<<kDijBlocks, 64, lds, s>>>((const float*)f->dDijDose, (int)f->doseDims[0], (int)f->doseDims[1], (const FieldState*)f->dState,
+                                            (const unsigned short*)f->dDijOwner, bevW, bevH, n, rel_threshold, f->dDijColMax, f->dDijCnt,
+                                            f->dDijRowsB + total, f->dDijValsB + total, f->dDijMisc + 1);
+        };
+        if (rel_threshold > 0.0f) {
+            if ((e = hipMemsetAsync(f->dDijColMax, 0, (size_t)n * sizeof(unsigned int), s)) != hipSuccess) { hipFail(e); break; }
+            split(k_dij_split<0>);
+        }
+        split(k_dij_split<1>);
+        k_dij_scan<<<1, 1024, 0, s>>>(f->dDijCnt, kDijBlocks, n, dList, total, f->dDijColLen, f->dDijColSrc, f->dDijMisc);
+        int count = 0;
+        e = hipGetLastError();
+        if (e == hipSuccess) e = hipMemcpyAsync(&count, f->dDijMisc, sizeof(int), hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess) e = hipStreamSynchronize(s);
+        if (e != hipSuccess) { hipFail(e); break; }
+        if ((size_t)(total + count) > f->dijCap) {                   // grow the batch-major staging geometrically (the stream is idle)
+            size_t cap = f->dijCap;
+            while (cap < (size_t)(total + count)) cap *= 2;
+            int* r = nullptr; float* v = nullptr;
+            e = hipMalloc((void**)&r, cap * sizeof(int));
+            if (e == hipSuccess) e = hipMalloc((void**)&v, cap * sizeof(float));
+            if (e == hipSuccess) e = hipMemcpy(r, f->dDijRowsB, (size_t)total * sizeof(int), hipMemcpyDeviceToDevice);
+            if (e == hipSuccess) e = hipMemcpy(v, f->dDijValsB, (size_t)total * sizeof(float), hipMemcpyDeviceToDevice);
+            if (e != hipSuccess) { if (r) (void)hipFree(r); if (v) (void)hipFree(v); hipFail(e); break; }
+            (void)hipFree(f->dDijRowsB); (void)hipFree(f->dDijValsB);
+            f->dDijRowsB = r; f->dDijValsB = v; f->dijCap = cap;
+        }
+        split(k_dij_split<2>);
+        if ((e = hipGetLastError()) != hipSuccess) { hipFail(e); break; }
+        total += count;
+        st = rtd_field_clear_dose(hh, ff, f->dDijDose);
+    }
+    // 5. restore: the field's own weights and hints, one forward at them (deterministic: the same bits as before the call)
+    if (!list.empty()) {
+        (void)hipStreamSynchronize(s);
+        if (st == RTD_OK) {
+            e = hipMemcpyAsync(&dijErr, f->dDijMisc + 1, sizeof(int), hipMemcpyDeviceToHost, s);
+            if (e == hipSuccess) e = hipMemcpyAsync(colLen.data(), f->dDijColLen, nSpot * sizeof(long long), hipMemcpyDeviceToHost, s);
+            if (e == hipSuccess) e = hipStreamSynchronize(s);
+            if (e != hipSuccess) hipFail(e);
+        }
+        const std::string keep = h->error;
+        const hipError_t re = hipMemcpyAsync(f->dSpotWeights, f->dDijSave, nSpot * sizeof(float), hipMemcpyDeviceToDevice, s);
+        f->uniformHint = saveUniform; f->radiusHint = saveRadius; f->hintEpoch = saveEpoch;
+        int rst = re == hipSuccess ? rtd_field_compute_bev(hh, ff) : RTD_ERR_HIP;
+        if (rst == RTD_OK && hipStreamSynchronize(s) != hipSuccess) rst = RTD_ERR_HIP;
+        if (st == RTD_OK && rst != RTD_OK) { st = rst; if (h->error == keep) h->error = "HIP error (dose influence): restoring the field's forward failed"; }
+        else h->error = keep;
+    }
+    if (st != RTD_OK) return st;
+    if (dijErr & kDijErrOverflow) return fail(h, RTD_ERR_RADIUS_OVERFLOW, "Found larger than allowed kernel superposition radius");
+    if (dijErr) return fail(h, RTD_ERR_HIP, "rtd_field_dose_influence: internal error: a batch's dose reached beyond the field's superposition radius");
+    // 6. CSC: column pointers on the host, the batch-major columns gathered into column order on the device
+    std::vector<long long> colPtr(nSpot + 1, 0);
+    for (size_t j = 0; j < nSpot; ++j) colPtr[j + 1] = colPtr[j] + colLen[j];
+    freeBuffers(f, kDijOut);
+    f->dijNnz = (size_t)colPtr[nSpot];
+    { const int ast = allocBuffers(h, f, kDijOut); if (ast != RTD_OK) { freeBuffers(f, kDijOut); f->dijNnz = 0; return ast; } }
+    RTD_HIP(h, hipMemcpyAsync(f->dDijColPtr, colPtr.data(), colPtr.size() * sizeof(long long), hipMemcpyHostToDevice, s));
+    if (f->dijNnz)
+        k_dij_gather<<<(unsigned)nSpot, 256, 0, s>>>((const long long*)f->dDijColPtr, (const long long*)f->dDijColSrc, (const int*)f->dDijRowsB,
+                                                     (const float*)f->dDijValsB, f->dDijRows, f->dDijVals);
+    RTD_HIP(h, hipGetLastError());
+    RTD_HIP(h, hipStreamSynchronize(s));
+    f->dijDone = true;
+    *nnz = f->dijNnz;
+    return RTD_OK;
+}
+
+// Copies the last rtd_field_dose_influence result (host or device memory: hipMemcpyDefault).
+int rtd_field_dose_influence_copy(rtd_handle hh, rtd_field ff, int64_t* col_ptr, int32_t* row_idx, float* values) {
+    auto* h = reinterpret_cast<rtd_handle_impl*>(hh);
+    auto* f = reinterpret_cast<rtd_field_impl*>(ff);
+    if (!h || !f) return RTD_ERR_INVALID_ARG;
+    if (!f->dijDone) return fail(h, RTD_ERR_NOT_READY, "rtd_field_dose_influence_copy: no dose-influence matrix (call rtd_field_dose_influence first)");
+    if (!col_ptr || (f->dijNnz && (!row_idx || !values))) return fail(h, RTD_ERR_INVALID_ARG, "rtd_field_dose_influence_copy: null pointer");
+    RTD_HIP(h, hipSetDevice(h->device));
+    const size_t nSpot = (size_t)f->fc.spotNx * f->fc.spotNy * f->fc.L;
+    hipStream_t s = h->stream;
+    RTD_HIP(h, hipMemcpyAsync(col_ptr, f->dDijColPtr, (nSpot + 1) * sizeof(int64_t), hipMemcpyDefault, s));
+    if (f->dijNnz) {
+        RTD_HIP(h, hipMemcpyAsync(row_idx, f->dDijRows, f->dijNnz * sizeof(int32_t), hipMemcpyDefault, s));
+        RTD_HIP(h, hipMemcpyAsync(values, f->dDijVals, f->dijNnz * sizeof(float), hipMemcpyDefault, s));
+    }
+    RTD_HIP(h, hipStreamSynchronize(s));
+    return RTD_OK;
+}
+
 int rtd_field_fetch(rtd_handle hh, rtd_field ff, const char* name, void* host_out, size_t bytes, size_t* bytes_needed) {
     auto* h = reinterpret_cast<rtd_handle_impl*>(hh);
     auto* f = reinterpret_cast<rtd_field_impl*>(ff);
@@ -1416,6 +1669,10 @@ int rtd_field_fetch(rtd_handle hh, rtd_field ff, const char* name, void* host_ou
     });
     if (found) {
         if (nm == "tile_radius") n = L * S * tiles;   // (the allocation is rounded up to whole 32-bit words)
+    } else if (nm == "dij_batch") {
+        if (!f->dijDone) return fail(h, RTD_ERR_NOT_READY, "rtd_field_fetch: no dose-influence matrix");
+        n = f->dijBatchOf.size() * sizeof(int); staging.resize(std::max<size_t>(n, 1));
+        std::memcpy(staging.data(), f->dijBatchOf.data(), n);
     } else if (nm == "eff_radius" || nm == "layer_plan") {
         std::vector<LayerPlan> lp(L);
         RTD_HIP(h, hipMemcpy(lp.data(), f->dLayers, L * sizeof(LayerPlan), hipMemcpyDeviceToHost));

@@ -20,7 +20,8 @@ LIB_PATH = os.path.join(_HERE, "librtd_hip.so")
 _LIB = None
 
 _FETCH_DTYPES = {"first_inside": np.int32, "first_outside": np.int32, "first_passive": np.int32,
-                 "eff_radius": np.int32, "tile_radius": np.uint8, "fill_debug": np.int64, "sweep_debug": np.int64, "uniform_debug": np.int64, "sweep_big_debug": np.int64, "scan_debug": np.int64}
+                 "eff_radius": np.int32, "tile_radius": np.uint8, "fill_debug": np.int64, "sweep_debug": np.int64, "uniform_debug": np.int64, "sweep_big_debug": np.int64, "scan_debug": np.int64,
+                 "dij_batch": np.int32}
 
 
 class RtdError(RuntimeError):
@@ -78,6 +79,9 @@ def lib():
         L.rtd_field_release.argtypes = [vp, vp]
         L.rtd_field_spot_gradient.argtypes = [vp, vp, vp, vp]
         L.rtd_spot_gradient.argtypes = [vp, C.POINTER(abi.RtdBeam), C.c_int, abi.c_float_p, u3, abi.c_float_p]
+        L.rtd_field_dose_influence.argtypes = [vp, vp, C.c_float, C.POINTER(C.c_size_t)]
+        L.rtd_field_dose_influence_copy.argtypes = [vp, vp, vp, vp, vp]
+        L.rtd_field_set_spot_weights.argtypes = [vp, vp, vp]
         L.rtd_host_register.argtypes = [vp, C.c_size_t]
         L.rtd_host_unregister.argtypes = [vp]
         L.rtd_plan_create.argtypes = [C.POINTER(C.c_int), C.c_int, vpp]
@@ -105,6 +109,49 @@ def lib():
     return _LIB
 
 
+class DoseInfluence:
+    """A field's dose-influence matrix in CSC form: column j (spot j of the [L][ny][nx] map) holds the dose of that spot at unit
+    weight; rows are linear voxel indices of the dose grid (x fastest). shape = (n_voxels, n_spots). matvec / rmatvec in float64.
+    scipy users: scipy.sparse.csc_matrix((d.data, d.indices, d.indptr), shape=d.shape)."""
+
+    def __init__(self, indptr, indices, data, dose_dims, spot_shape):
+        self.indptr = indptr
+        self.indices = indices
+        self.data = data
+        self.dose_dims = tuple(int(v) for v in dose_dims)
+        self.spot_shape = tuple(int(v) for v in spot_shape)
+        self.shape = (int(np.prod(self.dose_dims)), int(indptr.size - 1))
+
+    @property
+    def nnz(self):
+        return int(self.indptr[-1])
+
+    def column(self, j):
+        """(rows, values) of column j."""
+        a, b = int(self.indptr[j]), int(self.indptr[j + 1])
+        return self.indices[a:b], self.data[a:b]
+
+    def _col_of_entry(self):
+        return np.repeat(np.arange(self.shape[1], dtype=np.int64), np.diff(self.indptr))
+
+    def matvec(self, w):
+        """Dij w: the dose volume (float64, flat, n_voxels) of spot weights w ([L][ny][nx] or flat)."""
+        w = np.asarray(w, dtype=np.float64).reshape(-1)
+        assert w.size == self.shape[1]
+        out = np.zeros(self.shape[0], dtype=np.float64)
+        np.add.at(out, self.indices, self.data.astype(np.float64) * w[self._col_of_entry()])
+        return out
+
+    def rmatvec(self, g):
+        """Dij^T g: per-spot sums (float64, flat, n_spots) of a voxel-weight volume g (dose-grid shape or flat)."""
+        g = np.asarray(g, dtype=np.float64).reshape(-1)
+        assert g.size == self.shape[0]
+        prod = self.data.astype(np.float64) * g[self.indices]
+        out = np.zeros(self.shape[1], dtype=np.float64)
+        np.add.at(out, self._col_of_entry(), prod)
+        return out
+
+
 class Field:
     """One beam prepared on the device (rtd_field_*)."""
 
@@ -113,6 +160,7 @@ class Field:
         self._beam = beam            # keeps the numpy arrays alive
         self._h = C.c_void_p()
         ba = beam.as_abi()
+        self._dims = tuple(int(d) for d in dose_dims)
         create = lib().rtd_field_create_remote if remote else lib().rtd_field_create
         eng._check(create(eng._h, C.byref(ba), abi.uint3(dose_dims), C.byref(self._h)))
         self.remote = remote
@@ -172,6 +220,26 @@ class Field:
         dev_out ([L][ny][nx] float32, device pointer); dev_g: the voxel-weight volume (device pointer, dose-grid shape).
         Asynchronous after the field's plan is known; the live rays are those of the last compute."""
         self.eng._check(lib().rtd_field_spot_gradient(self.eng._h, self._h, C.c_void_p(int(dev_g)), C.c_void_p(int(dev_out))))
+
+    def dose_influence(self, rel_threshold=0.0):
+        """rtd_field_dose_influence: the field's dose-influence matrix (n_voxels x n_spots, CSC) as a DoseInfluence. Needs
+        ray_weight_cutoff = 0; the field's own state is that of a compute at its own weights afterwards."""
+        e = lib()
+        nnz = C.c_size_t(0)
+        self.eng._check(e.rtd_field_dose_influence(self.eng._h, self._h, C.c_float(rel_threshold), C.byref(nnz)))
+        shape = np.asarray(self._beam.spotWeights).shape
+        n_spots = int(np.prod(shape))
+        indptr = np.empty(n_spots + 1, dtype=np.int64)
+        indices = np.empty(max(nnz.value, 1), dtype=np.int32)
+        data = np.empty(max(nnz.value, 1), dtype=np.float32)
+        self.eng._check(e.rtd_field_dose_influence_copy(self.eng._h, self._h, indptr.ctypes.data_as(C.c_void_p),
+                                                        indices.ctypes.data_as(C.c_void_p), data.ctypes.data_as(C.c_void_p)))
+        self.computed = True
+        return DoseInfluence(indptr, indices[:nnz.value], data[:nnz.value], self._dims, shape)
+
+    def set_spot_weights(self, dev_spot_weights):
+        """rtd_field_set_spot_weights: new [L][ny][nx] float32 weights from device memory (stream-ordered)."""
+        self.eng._check(lib().rtd_field_set_spot_weights(self.eng._h, self._h, C.c_void_p(int(dev_spot_weights))))
 
     def clear_dose(self, dev_dose):
         """Zero the voxels of dev_dose that the last compute() of this field could have changed; asynchronous."""
@@ -280,6 +348,18 @@ class Engine:
             res.append(out[off:off + n].reshape(np.asarray(b.spotWeights).shape).copy())
             off += n
         return res
+
+    def dose_influence(self, beams, dose_dims, rel_threshold=0.0):
+        """The dose-influence matrix of every beam on the dose grid dose_dims (x, y, z): one DoseInfluence per beam, as
+        spot_gradient returns one array per beam. Needs ray_weight_cutoff = 0."""
+        out = []
+        for b in beams:
+            f = self.create_field(b, dose_dims)
+            try:
+                out.append(f.dose_influence(rel_threshold))
+            finally:
+                f.release()
+        return out
 
     def create_field(self, beam, dose_dims, remote=False):
         return Field(self, beam, dose_dims, remote=remote)
