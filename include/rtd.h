@@ -357,6 +357,50 @@ int rtd_field_dose_influence_copy(rtd_handle h, rtd_field f, int64_t* col_ptr, i
 int rtd_field_set_spot_weights(rtd_handle h, rtd_field f, const float* dev_spot_weights);
 
 /*
+ * ---- Products with the resident Dij: Dij w and Dij^T g on the device ----
+ *
+ * All four calls act on the matrix of the field's LAST rtd_field_dose_influence call, at the threshold it was made with, where it
+ * lies (no copy to the host): RTD_ERR_NOT_READY before any such call; RTD_ERR_INVALID_ARG for a null pointer or a remote field. The
+ * matrix does not depend on the spot weights: rtd_field_set_spot_weights leaves it, and what prepare built, valid. A new
+ * rtd_field_dose_influence call replaces both. Device pointers are memory of this handle's device; w and the result of apply_t are
+ * float32 [L][ny][nx] as spot_weights, g and the dose volume float32 on the field's dose grid. Not on the rtd_plan_* path.
+ *
+ * rtd_field_dose_influence_prepare  builds, once per matrix, what the products need: a row-major companion of the matrix over the
+ *                                   voxels of the field's dose box (the box rtd_field_clear_dose clears; grown to the bounding box of
+ *                                   the matrix's rows should spots of weight 0 reach beyond it), every row's entries in ascending column
+ *                                   order, and the chunk tables of the columns. Allocates, and keeps until the matrix is replaced or
+ *                                   the field released or destroyed: 8 bytes per entry (int32 column + float32 value: the matrix's
+ *                                   footprint once more), 8 bytes per box voxel + 8 (int64 row pointers), 4 bytes per spot + 4, and 8
+ *                                   bytes per column chunk of 2048 entries; 4 bytes per box voxel more while it runs. Synchronous and
+ *                                   deterministic. A second call is a no-op.
+ * rtd_field_dose_influence_apply    s[v] = sum_j Dij[v][j] * w[j]. init == 0: dev_dose[v] += s[v] for the voxels that have entries,
+ *                                   no other voxel is touched (the counterpart of rtd_field_transfer: the fields of a plan are applied
+ *                                   one after the other into one volume). init != 0: every voxel of the box above is WRITTEN with s[v]
+ *                                   or 0 and nothing outside it is touched (the counterpart of rtd_field_transfer_init).
+ * rtd_field_dose_influence_apply_t  WRITES dev_spot_grad[j] = sum_v Dij[v][j] * g[v], as rtd_field_spot_gradient does; empty columns
+ *                                   give +0.
+ * rtd_field_dose_influence_device   the device pointers of the CSC arrays (col_ptr int64[n_spots + 1], row_idx int32[nnz], values
+ *                                   float32[nnz]) and nnz, for callers with a GPU solver of their own. No copy: the arrays are owned by
+ *                                   the field and valid until its next rtd_field_dose_influence, release or destroy.
+ *
+ * Determinism: every output element is a float32 sum of separately rounded float32 products, in an order fixed by the matrix alone.
+ * apply: the entries of row v in ascending column order are dealt to 16 lanes (entry i to lane i mod 16), each lane adds its entries
+ * in order, and the 16 lane sums are added in a butterfly (distances 8, 4, 2, 1). apply_t: column j is cut into chunks of 2048
+ * consecutive entries; within a chunk entry i goes to lane i mod 64, each lane adds in order, the 64 lane sums are added in a butterfly
+ * (32, ..., 1); the chunk sums of a column are added the same way (chunk c to lane c mod 64). No float atomics: the same inputs give
+ * the same bits across calls, handles and processes.
+ *
+ * Stream behaviour: after prepare, apply and apply_t only launch kernels on the handle's stream (no allocation, no host
+ * synchronisation, no copy), so they can be captured into a graph like rtd_field_compute. An apply or apply_t without a prior prepare
+ * runs it first, and is synchronous that once. With an all-empty matrix nothing is launched where nothing is to be written.
+ */
+int rtd_field_dose_influence_prepare(rtd_handle h, rtd_field f);
+int rtd_field_dose_influence_apply(rtd_handle h, rtd_field f, const float* dev_spot_weights, float* dev_dose, int init);
+int rtd_field_dose_influence_apply_t(rtd_handle h, rtd_field f, const float* dev_voxel_weights, float* dev_spot_grad);
+int rtd_field_dose_influence_device(rtd_handle h, rtd_field f, const int64_t** col_ptr, const int32_t** row_idx, const float** values,
+                                    size_t* nnz);
+
+/*
  * ---- Multi-GPU plans behind the boundary (SURVEY.md 8(b) "Threading": one handle and one host thread per device) ----
  *
  * rtd_plan is the reference-shaped call on several GPUs of one process: the 4-beam cudaWrapperProtons of the C++ shim uses

@@ -30,6 +30,7 @@
 #include "rtd_uniform.hpp"
 #include "rtd_adjoint.hpp"
 #include "rtd_dij.hpp"
+#include "rtd_dij_apply.hpp"
 
 using namespace rtd;
 
@@ -93,7 +94,8 @@ Switches readSwitches() {
 
 // Classes of a field's device buffers: the workspace that a field of the same shape takes over (rtd_field_release), the NUCLEAR_CORR
 // halo, the spot-weight gradient's (allocated by its first call), the RTD_*_DEBUG clock stamps, the dose-influence matrix's workspace
-// and its result (rtd_field_dose_influence: allocated by its first call, the result replaced by every call).
+// and its result (rtd_field_dose_influence: allocated by its first call, the result replaced by every call; the result's class also
+// holds what rtd_field_dose_influence_prepare builds from it, so that the two are freed together).
 enum BufClass : unsigned { kShape = 1, kNuclear = 2, kGradient = 4, kDiag = 8, kDij = 16, kDijOut = 32, kAllBufs = 63 };
 
 struct rtd_field_impl {
@@ -173,6 +175,14 @@ struct rtd_field_impl {
     size_t dijCap = 0, dijNnz = 0;
     bool dijDone = false;          // the CSC buffers hold the last call's result
     std::vector<int> dijBatchOf;   // per spot: its batch in the last call (-1: empty column); rtd_field_fetch "dij_batch"
+    // products with the matrix (rtd_field_dose_influence_prepare / _apply / _apply_t, rtd_dij_apply.hpp): the row-major companion over the
+    // voxels of dijBox (row pointers, columns ascending within a row, values) and the column chunks of the transposed product
+    long long* dDijRowPtr = nullptr; int* dDijCCols = nullptr; float* dDijCVals = nullptr;
+    int *dDijChunkFirst = nullptr, *dDijChunkCol = nullptr; float* dDijPartial = nullptr;
+    bool dijPrepared = false;      // the buffers above exist and belong to the CSC result
+    int dijOwnBox[6] = {0, 0, 0, -1, -1, -1};   // the field's dose box (min, max) when the matrix was computed
+    DijBox dijBox{};               // ... united with the bounding box of the matrix's rows: the voxels that have a row
+    size_t dijRowsN = 0, dijChunks = 0;
     std::vector<size_t> released; // released: the element counts of its shape buffers (a new field takes it over if its own are the same)
 
     bool uniform4() const { return fc.W <= 16 * (kU2XB - 4) && fc.W % 4 == 0 && !sw.uniformV2; }   // k_superpose_uniform4, else _uniform2
@@ -222,6 +232,11 @@ struct rtd_field_impl {
         visit(dDijRowsB, dijCap, kDij, false, nullptr); visit(dDijValsB, dijCap, kDij, false, nullptr);
         visit(dDijColPtr, nSpot + 1, kDijOut, false, nullptr); visit(dDijRows, std::max<size_t>(dijNnz, 1), kDijOut, false, nullptr);
         visit(dDijVals, std::max<size_t>(dijNnz, 1), kDijOut, false, nullptr);
+        const size_t ap = dijPrepared ? 1 : 0;   // (only after rtd_field_dose_influence_prepare)
+        visit(dDijRowPtr, ap * (dijRowsN + 1), kDijOut, false, nullptr); visit(dDijCCols, ap * std::max<size_t>(dijNnz, 1), kDijOut, false, nullptr);
+        visit(dDijCVals, ap * std::max<size_t>(dijNnz, 1), kDijOut, false, nullptr); visit(dDijChunkFirst, ap * (nSpot + 1), kDijOut, false, nullptr);
+        visit(dDijChunkCol, ap * std::max<size_t>(dijChunks, 1), kDijOut, false, nullptr);
+        visit(dDijPartial, ap * std::max<size_t>(dijChunks, 1), kDijOut, false, nullptr);
         visit(dScanDbg, sw.scanDebug ? 8 * (R / 64) : 0, kDiag, true, "scan_debug");
         visit(dFillDbg, sw.fillDebug ? 4 * 2 * tiles * L : 0, kDiag, false, "fill_debug");
         visit(dUniDbg, sw.uniformDebug && uniformEligible && uniform4() ? 16 * S * nPartsU4 : 0, kDiag, true, "uniform_debug");
@@ -631,7 +646,7 @@ int rtd_field_release(rtd_handle hh, rtd_field ff) {
     f->computed = false; f->transferred = false;
     freeBuffers(f, kGradient | kDiag | kDij | kDijOut);   // (not part of the shape's workspace)
     f->gradDone = false;
-    f->dijDone = false; f->dijCap = 0; f->dijNnz = 0; f->dijBatchOf.clear();
+    f->dijDone = false; f->dijPrepared = false; f->dijCap = 0; f->dijNnz = 0; f->dijBatchOf.clear();
     f->released = shapeCounts(f);
     h->fieldCache.push_back(f);
     return RTD_OK;
@@ -1619,7 +1634,9 @@ int rtd_field_dose_influence(rtd_handle hh, rtd_field ff, float rel_threshold, s
     // 6. CSC: column pointers on the host, the batch-major columns gathered into column order on the device
     std::vector<long long> colPtr(nSpot + 1, 0);
     for (size_t j = 0; j < nSpot; ++j) colPtr[j + 1] = colPtr[j] + colLen[j];
-    freeBuffers(f, kDijOut);
+    freeBuffers(f, kDijOut);                                          // (with it what rtd_field_dose_influence_prepare built)
+    f->dijPrepared = false;
+    { const FieldState& fin = *f->hState; for (int i = 0; i < 3; ++i) { f->dijOwnBox[i] = fin.tboxMin[i]; f->dijOwnBox[3 + i] = fin.tboxMax[i]; } }
     f->dijNnz = (size_t)colPtr[nSpot];
     { const int ast = allocBuffers(h, f, kDijOut); if (ast != RTD_OK) { freeBuffers(f, kDijOut); f->dijNnz = 0; return ast; } }
     RTD_HIP(h, hipMemcpyAsync(f->dDijColPtr, colPtr.data(), colPtr.size() * sizeof(long long), hipMemcpyHostToDevice, s));
@@ -1649,6 +1666,156 @@ int rtd_field_dose_influence_copy(rtd_handle hh, rtd_field ff, int64_t* col_ptr,
         RTD_HIP(h, hipMemcpyAsync(values, f->dDijVals, f->dijNnz * sizeof(float), hipMemcpyDefault, s));
     }
     RTD_HIP(h, hipStreamSynchronize(s));
+    return RTD_OK;
+}
+
+// The device pointers of the last rtd_field_dose_influence result (no copy; owned by the field).
+int rtd_field_dose_influence_device(rtd_handle hh, rtd_field ff, const int64_t** col_ptr, const int32_t** row_idx, const float** values, size_t* nnz) {
+    auto* h = reinterpret_cast<rtd_handle_impl*>(hh);
+    auto* f = reinterpret_cast<rtd_field_impl*>(ff);
+    if (!h || !f) return RTD_ERR_INVALID_ARG;
+    if (!col_ptr || !row_idx || !values || !nnz) return fail(h, RTD_ERR_INVALID_ARG, "rtd_field_dose_influence_device: null pointer");
+    if (f->remote) return fail(h, RTD_ERR_INVALID_ARG, "rtd_field_dose_influence_device: a remote field has no workspace");
+    if (!f->dijDone) return fail(h, RTD_ERR_NOT_READY, "rtd_field_dose_influence_device: no dose-influence matrix (call rtd_field_dose_influence first)");
+    *col_ptr = reinterpret_cast<const int64_t*>(f->dDijColPtr); *row_idx = f->dDijRows; *values = f->dDijVals; *nnz = f->dijNnz;
+    return RTD_OK;
+}
+
+// Builds what the products with the last rtd_field_dose_influence result need (include/rtd.h; kernels in
+// rtd_dij_apply.hpp): the row-major companion over the field's dose box and the chunk tables of the columns. Synchronous. The
+// batch-major staging of rtd_field_dose_influence (dead since its gather into CSC, and at least nnz entries long) is the scratch of
+// the placement: the companion costs no memory beyond its own.
+int rtd_field_dose_influence_prepare(rtd_handle hh, rtd_field ff) {
+    auto* h = reinterpret_cast<rtd_handle_impl*>(hh);
+    auto* f = reinterpret_cast<rtd_field_impl*>(ff);
+    if (!h || !f) return RTD_ERR_INVALID_ARG;
+    if (f->remote) return fail(h, RTD_ERR_INVALID_ARG, "rtd_field_dose_influence_prepare: a remote field has no workspace");
+    if (!f->dijDone) return fail(h, RTD_ERR_NOT_READY, "rtd_field_dose_influence_prepare: no dose-influence matrix (call rtd_field_dose_influence first)");
+    if (f->dijPrepared) return RTD_OK;
+    RTD_HIP(h, hipSetDevice(h->device));
+    hipStream_t s = h->stream;
+    const size_t nSpot = (size_t)f->fc.spotNx * f->fc.spotNy * f->fc.L;
+    const long long nnz = (long long)f->dijNnz;
+    const int nx = (int)f->doseDims[0], ny = (int)f->doseDims[1];
+    if (nnz && (f->dijCap < f->dijNnz || !f->dDijRowsB || !f->dDijValsB))
+        return fail(h, RTD_ERR_HIP, "rtd_field_dose_influence_prepare: internal error: the staging buffers are smaller than the matrix");
+    // column pointers -> the chunks of the transposed product
+    std::vector<long long> colPtr(nSpot + 1);
+    RTD_HIP(h, hipMemcpyAsync(colPtr.data(), f->dDijColPtr, colPtr.size() * sizeof(long long), hipMemcpyDeviceToHost, s));
+    RTD_HIP(h, hipStreamSynchronize(s));
+    std::vector<int> chunkFirst(nSpot + 1, 0), chunkCol;
+    for (size_t j = 0; j < nSpot; ++j) {
+        const long long n = (colPtr[j + 1] - colPtr[j] + kDijApChunk - 1) / kDijApChunk;
+        if ((long long)chunkCol.size() + n > 0x7fffffffLL) return fail(h, RTD_ERR_INVALID_ARG, "rtd_field_dose_influence_prepare: more than 2^31 - 1 column chunks");
+        chunkCol.insert(chunkCol.end(), (size_t)n, (int)j);
+        chunkFirst[j + 1] = (int)chunkCol.size();
+    }
+    // the voxels that get a row: the field's dose box, grown (if need be) to hold every row of the matrix
+    int lo[3], hi[3];
+    for (int i = 0; i < 3; ++i) { lo[i] = f->dijOwnBox[i]; hi[i] = f->dijOwnBox[3 + i]; }
+    if (hi[0] < lo[0] || hi[1] < lo[1] || hi[2] < lo[2]) for (int i = 0; i < 3; ++i) { lo[i] = 0x7fffffff; hi[i] = -1; }
+    int *dTmp = nullptr; long long* dBlockSum = nullptr;
+    hipError_t e = hipSuccess;
+    auto done = [&](int st) { (void)hipStreamSynchronize(s); if (dTmp) (void)hipFree(dTmp); if (dBlockSum) (void)hipFree(dBlockSum); return st; };
+    auto hipFailed = [&]() { h->error = std::string("HIP error (dose influence prepare): ") + hipGetErrorString(e); return done(RTD_ERR_HIP); };
+    const unsigned streamGrid = (unsigned)std::min<long long>((nnz + 255) / 256, (long long)h->numCUs * 32);
+    if (nnz) {
+        int mm[6] = {0x7fffffff, 0x7fffffff, 0x7fffffff, -1, -1, -1};
+        e = hipMalloc((void**)&dTmp, sizeof mm);
+        if (e == hipSuccess) e = hipMemcpyAsync(dTmp, mm, sizeof mm, hipMemcpyHostToDevice, s);
+        if (e == hipSuccess) e = hipStreamSynchronize(s);
+        if (e != hipSuccess) return hipFailed();
+        k_dijap_bounds<<<streamGrid, 256, 0, s>>>((const int*)f->dDijRows, nnz, nx, ny, dTmp);
+        e = hipGetLastError();
+        if (e == hipSuccess) e = hipMemcpyAsync(mm, dTmp, sizeof mm, hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess) e = hipStreamSynchronize(s);
+        if (e != hipSuccess) return hipFailed();
+        (void)hipFree(dTmp); dTmp = nullptr;
+        for (int i = 0; i < 3; ++i) { lo[i] = std::min(lo[i], mm[i]); hi[i] = std::max(hi[i], mm[3 + i]); }
+    }
+    DijBox box{0, 0, 0, 0, 0, 0};
+    if (hi[0] >= lo[0]) box = DijBox{lo[0], lo[1], lo[2], hi[0] - lo[0] + 1, hi[1] - lo[1] + 1, hi[2] - lo[2] + 1};
+    const long long nRows = (long long)box.bw * box.bh * box.bd;
+    f->dijBox = box; f->dijRowsN = (size_t)nRows; f->dijChunks = chunkCol.size();
+    f->dijPrepared = true;                                            // (the buffer table lists the companion from here on)
+    f->forEachBuffer([&](auto*& p, size_t n, BufClass c, bool, const char*) {
+        if (e == hipSuccess && c == kDijOut && n && !p) e = hipMalloc((void**)&p, n * sizeof *p);
+    });
+    auto undo = [&]() {   // the CSC stays; the companion goes
+        f->dijPrepared = false;
+        for (void** p : {(void**)&f->dDijRowPtr, (void**)&f->dDijCCols, (void**)&f->dDijCVals, (void**)&f->dDijChunkFirst, (void**)&f->dDijChunkCol,
+                         (void**)&f->dDijPartial})
+            if (*p) { (void)hipFree(*p); *p = nullptr; }
+    };
+    if (e == hipSuccess) e = hipMemcpyAsync(f->dDijChunkFirst, chunkFirst.data(), chunkFirst.size() * sizeof(int), hipMemcpyHostToDevice, s);
+    if (e == hipSuccess && !chunkCol.empty()) e = hipMemcpyAsync(f->dDijChunkCol, chunkCol.data(), chunkCol.size() * sizeof(int), hipMemcpyHostToDevice, s);
+    if (e == hipSuccess && !nnz) e = hipMemsetAsync(f->dDijRowPtr, 0, (size_t)(nRows + 1) * sizeof(long long), s);
+    if (e == hipSuccess && nnz) {
+        const int nBlocks = (int)((nRows + kDijApScanItems - 1) / kDijApScanItems);
+        e = hipMalloc((void**)&dTmp, (size_t)nRows * sizeof(int));
+        if (e == hipSuccess) e = hipMalloc((void**)&dBlockSum, (size_t)nBlocks * sizeof(long long));
+        if (e == hipSuccess) e = hipMemsetAsync(dTmp, 0, (size_t)nRows * sizeof(int), s);
+        if (e == hipSuccess) {
+            k_dijap_count<<<streamGrid, 256, 0, s>>>((const int*)f->dDijRows, nnz, nx, ny, box, dTmp);
+            k_dijap_scan_sums<<<(unsigned)nBlocks, 256, 0, s>>>((const int*)dTmp, nRows, dBlockSum);
+            k_dijap_scan_blocks<<<1, 256, 0, s>>>(dBlockSum, nBlocks);
+            k_dijap_scan_write<<<(unsigned)nBlocks, 256, 0, s>>>((const int*)dTmp, nRows, (const long long*)dBlockSum, f->dDijRowPtr);
+            e = hipGetLastError();
+        }
+        if (e == hipSuccess) e = hipMemsetAsync(dTmp, 0, (size_t)nRows * sizeof(int), s);
+        if (e == hipSuccess) {
+            k_dijap_fill<<<(unsigned)nSpot, 256, 0, s>>>((const long long*)f->dDijColPtr, (const int*)f->dDijRows, (const float*)f->dDijVals, nx, ny, box,
+                                                         (const long long*)f->dDijRowPtr, dTmp, f->dDijRowsB, f->dDijValsB);
+            const unsigned g = (unsigned)std::min<long long>((nRows + 3) / 4, (long long)h->numCUs * 64);
+            k_dijap_sort<<<g, 256, 0, s>>>((const long long*)f->dDijRowPtr, nRows, (const int*)f->dDijRowsB, (const float*)f->dDijValsB, f->dDijCCols,
+                                           f->dDijCVals);
+            e = hipGetLastError();
+        }
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(s);                 // (the host vectors above are pageable; the scratch is freed below)
+    if (e != hipSuccess) { (void)hipStreamSynchronize(s); undo(); return hipFailed(); }
+    return done(RTD_OK);
+}
+
+// Dij w on the handle's stream: launches only once prepared (the first call prepares, and is synchronous that once).
+int rtd_field_dose_influence_apply(rtd_handle hh, rtd_field ff, const float* dev_spot_weights, float* dev_dose, int init) {
+    auto* h = reinterpret_cast<rtd_handle_impl*>(hh);
+    auto* f = reinterpret_cast<rtd_field_impl*>(ff);
+    if (!h || !f) return RTD_ERR_INVALID_ARG;
+    if (!dev_spot_weights || !dev_dose) return fail(h, RTD_ERR_INVALID_ARG, "rtd_field_dose_influence_apply: null device pointer");
+    if (f->remote) return fail(h, RTD_ERR_INVALID_ARG, "rtd_field_dose_influence_apply: a remote field has no workspace");
+    if (!f->dijDone) return fail(h, RTD_ERR_NOT_READY, "rtd_field_dose_influence_apply: no dose-influence matrix (call rtd_field_dose_influence first)");
+    if (!f->dijPrepared) { const int st = rtd_field_dose_influence_prepare(hh, ff); if (st != RTD_OK) return st; }
+    RTD_HIP(h, hipSetDevice(h->device));
+    const long long nRows = (long long)f->dijRowsN;
+    if (nRows == 0 || (!init && f->dijNnz == 0)) return RTD_OK;       // nothing to write: no launch
+    const unsigned g = (unsigned)((nRows * kDijApGroup + 255) / 256);
+    auto launch = [&](auto kern) {
+        kern<<<g, 256, 0, h->stream>>>((const long long*)f->dDijRowPtr, (const int*)f->dDijCCols, (const float*)f->dDijCVals, dev_spot_weights, dev_dose,
+                                       (int)f->doseDims[0], (int)f->doseDims[1], f->dijBox, nRows);
+    };
+    if (init) launch(k_dijap_apply<true>); else launch(k_dijap_apply<false>);
+    RTD_HIP(h, hipGetLastError());
+    return RTD_OK;
+}
+
+// Dij^T g on the handle's stream (the chunk sums, then their sums per column).
+int rtd_field_dose_influence_apply_t(rtd_handle hh, rtd_field ff, const float* dev_voxel_weights, float* dev_spot_grad) {
+    auto* h = reinterpret_cast<rtd_handle_impl*>(hh);
+    auto* f = reinterpret_cast<rtd_field_impl*>(ff);
+    if (!h || !f) return RTD_ERR_INVALID_ARG;
+    if (!dev_voxel_weights || !dev_spot_grad) return fail(h, RTD_ERR_INVALID_ARG, "rtd_field_dose_influence_apply_t: null device pointer");
+    if (f->remote) return fail(h, RTD_ERR_INVALID_ARG, "rtd_field_dose_influence_apply_t: a remote field has no workspace");
+    if (!f->dijDone) return fail(h, RTD_ERR_NOT_READY, "rtd_field_dose_influence_apply_t: no dose-influence matrix (call rtd_field_dose_influence first)");
+    if (!f->dijPrepared) { const int st = rtd_field_dose_influence_prepare(hh, ff); if (st != RTD_OK) return st; }
+    RTD_HIP(h, hipSetDevice(h->device));
+    const int nSpot = f->fc.spotNx * f->fc.spotNy * f->fc.L, nChunks = (int)f->dijChunks;
+    if (nChunks)
+        k_dijap_apply_t<<<(unsigned)((nChunks + 3) / 4), 256, 0, h->stream>>>((const long long*)f->dDijColPtr, (const int*)f->dDijRows, (const float*)f->dDijVals,
+                                                                            (const int*)f->dDijChunkCol, (const int*)f->dDijChunkFirst, dev_voxel_weights,
+                                                                            f->dDijPartial, nChunks);
+    k_dijap_reduce_t<<<(unsigned)((nSpot + 3) / 4), 256, 0, h->stream>>>((const int*)f->dDijChunkFirst, (const float*)f->dDijPartial, dev_spot_grad, nSpot);
+    RTD_HIP(h, hipGetLastError());
     return RTD_OK;
 }
 

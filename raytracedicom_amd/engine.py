@@ -82,6 +82,10 @@ def lib():
         L.rtd_field_dose_influence.argtypes = [vp, vp, C.c_float, C.POINTER(C.c_size_t)]
         L.rtd_field_dose_influence_copy.argtypes = [vp, vp, vp, vp, vp]
         L.rtd_field_set_spot_weights.argtypes = [vp, vp, vp]
+        L.rtd_field_dose_influence_prepare.argtypes = [vp, vp]
+        L.rtd_field_dose_influence_apply.argtypes = [vp, vp, vp, vp, C.c_int]
+        L.rtd_field_dose_influence_apply_t.argtypes = [vp, vp, vp, vp]
+        L.rtd_field_dose_influence_device.argtypes = [vp, vp, vpp, vpp, vpp, C.POINTER(C.c_size_t)]
         L.rtd_host_register.argtypes = [vp, C.c_size_t]
         L.rtd_host_unregister.argtypes = [vp]
         L.rtd_plan_create.argtypes = [C.POINTER(C.c_int), C.c_int, vpp]
@@ -236,6 +240,28 @@ class Field:
                                                         indices.ctypes.data_as(C.c_void_p), data.ctypes.data_as(C.c_void_p)))
         self.computed = True
         return DoseInfluence(indptr, indices[:nnz.value], data[:nnz.value], self._dims, shape)
+
+    def dose_influence_prepare(self):
+        """rtd_field_dose_influence_prepare: builds, once per matrix, what dose_influence_apply / _apply_t need (synchronous)."""
+        self.eng._check(lib().rtd_field_dose_influence_prepare(self.eng._h, self._h))
+
+    def dose_influence_apply(self, dev_w, dev_dose, init=False):
+        """rtd_field_dose_influence_apply: Dij w with the resident matrix of the last dose_influence(); dev_w [L][ny][nx] float32,
+        dev_dose the dose volume (device pointers). init=False adds to the voxels that have entries; init=True writes the field's
+        dose box (sum or 0). Asynchronous once prepared."""
+        self.eng._check(lib().rtd_field_dose_influence_apply(self.eng._h, self._h, C.c_void_p(int(dev_w)), C.c_void_p(int(dev_dose)), int(bool(init))))
+
+    def dose_influence_apply_t(self, dev_g, dev_out):
+        """rtd_field_dose_influence_apply_t: Dij^T g written to dev_out ([L][ny][nx] float32); dev_g: the voxel-weight volume (device
+        pointers). Asynchronous once prepared."""
+        self.eng._check(lib().rtd_field_dose_influence_apply_t(self.eng._h, self._h, C.c_void_p(int(dev_g)), C.c_void_p(int(dev_out))))
+
+    def dose_influence_device(self):
+        """rtd_field_dose_influence_device: (col_ptr, row_idx, values, nnz) — the device pointers of the resident CSC arrays as ints
+        (owned by the field, valid until its next dose_influence(), release or destroy) and the entry count."""
+        cp, ri, va, n = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_size_t(0)
+        self.eng._check(lib().rtd_field_dose_influence_device(self.eng._h, self._h, C.byref(cp), C.byref(ri), C.byref(va), C.byref(n)))
+        return int(cp.value or 0), int(ri.value or 0), int(va.value or 0), int(n.value)
 
     def set_spot_weights(self, dev_spot_weights):
         """rtd_field_set_spot_weights: new [L][ny][nx] float32 weights from device memory (stream-ordered)."""
