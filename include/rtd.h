@@ -401,6 +401,126 @@ int rtd_field_dose_influence_device(rtd_handle h, rtd_field f, const int64_t** c
                                     size_t* nnz);
 
 /*
+ * ---- Dose objectives and the resident spot-weight optimiser ----
+ *
+ * rtd_objective: structures (ROIs: sets of voxels of one dose grid) and penalty terms on them; from a dose volume on the device to
+ * the objective value, the value of every term and the voxel gradient g = df/dd, without leaving the device. The gradient is what
+ * rtd_field_dose_influence_apply_t takes. A term's value is weight / N_roi * sum_{v in roi} phi(d[v]) with phi by kind:
+ *     RTD_OBJ_SQ_DEVIATION (d - level)^2, RTD_OBJ_SQ_OVERDOSE max(d - level, 0)^2, RTD_OBJ_SQ_UNDERDOSE min(d - level, 0)^2,
+ *     RTD_OBJ_MEAN d (level ignored);
+ * the objective is the sum of its terms. ROIs may overlap. At most RTD_OBJ_MAX_TERMS terms.
+ *
+ * rtd_objective_create    an empty objective on the dose grid dose_dims.
+ * rtd_objective_add_roi   voxels: host memory, n >= 1 linear voxel indices (x fastest), strictly ascending, copied; *roi_id receives
+ *                         the ROI's number (0, 1, ... in the order added).
+ * rtd_objective_add_term  kind, roi (a number add_roi returned), weight > 0, dose_level (finite).
+ * rtd_objective_eval      dev_dose: float32 volume on the grid; dev_values: float64[1 + terms], [0] the objective, [1 + t] term t;
+ *                         dev_voxel_grad: float32 volume on the grid, WRITTEN at every voxel of the union of the ROIs (0 where a
+ *                         voxel's ROIs carry no term) and touched NOWHERE else: the caller zeroes that volume once. The first eval after
+ *                         an add_roi / add_term builds the device tables (the union of the ROIs ascending and, per union voxel, its
+ *                         terms in term order) and is synchronous that once; every other eval is two launches on the handle's stream:
+ *                         no allocation, no copy, no host synchronisation; it can be captured into a graph.
+ * rtd_objective_destroy   frees it (before rtd_destroy of its handle; not while an optimiser uses it).
+ * RTD_ERR_INVALID_ARG: a null pointer, a zero dimension or more than 2^31 - 1 voxels, an empty ROI, indices not strictly ascending or
+ * out of range, an unknown kind or ROI, a weight that is not positive and finite, a level that is not finite, a 65th term, eval of an
+ * objective without terms. After a refusal the objective is what it was.
+ *
+ * Arithmetic of eval (fixed, so that it can be restated): d[v] is widened to float64. With x = d[v] - level (float64), clamped as the
+ * kind says (x < 0 ? 0 : x for OVERDOSE, x > 0 ? 0 : x for UNDERDOSE; a NaN stays a NaN), c_t = 2.0 * weight_t / N_t and
+ * wn_t = weight_t / N_t computed once on the host in float64: g[v] = float32(sum over the voxel's terms, in term order, starting from
+ * 0.0, of c_t * x, or of wn_t for a MEAN term), every product and sum in float64 without contraction, rounded once. Values: one
+ * thread per union voxel, blocks of 256; the phi of term t are added over each wave of 64 by a butterfly (lane distances 32, ..., 1),
+ * the four wave sums of a block as (w0 + w1) + (w2 + w3); a second launch adds the block sums of a term (block b to lane b mod 64,
+ * each lane in ascending order, butterfly), multiplies by wn_t, and adds the terms in term order. float64 throughout, no atomics: the
+ * same inputs give the same bits across calls, handles and processes.
+ *
+ * rtd_optimizer: spectral projected gradient descent (Barzilai-Borwein steps, projection on w >= 0) on an objective of the dose of
+ * 1 .. RTD_OPT_MAX_FIELDS local fields of one handle on one dose grid, each with a matrix from rtd_field_dose_influence
+ * (RTD_ERR_NOT_READY without; create runs rtd_field_dose_influence_prepare where it has not run). Everything the iteration touches
+ * lives on the device and belongs to the optimiser: one dose volume and one g volume (zeroed at creation), w, w_prev, grad, grad_prev,
+ * w_best (float32, the fields' [L][ny][nx] maps concatenated in list order), a float64 history and a record of scalars. The fields,
+ * their matrices and the objective must outlive it unchanged.
+ *
+ * One iteration k, every step a launch on the handle's stream, no decision taken on the host:
+ *   1. dose = sum_f Dij_f w_f: bit for bit a zeroed volume followed by rtd_field_dose_influence_apply(init = 0) of the fields in list
+ *      order (field 0 writes its box with init = 1 after the boxes of the other fields have been cleared: the same bits);
+ *   2. rtd_objective_eval -> f_k, g; history[k] = f_k while k < history_capacity;
+ *   3. grad_f = Dij_f^T g (rtd_field_dose_influence_apply_t) per field;
+ *   4. if f_k < f_best (+inf at the start): w_best = w, f_best = f_k, best_iteration = k;
+ *   5. the step length alpha (float64). Without a Barzilai-Borwein pair (the first iteration, and the one after a guard, 7.):
+ *      m = max_j |P(w - grad)_j - w_j| with P the clamp at 0, evaluated in float64 without cancellation as w_j - grad_j < 0 ? |w_j| :
+      |grad_j| (a gradient can be 1e-15 of a weight); alpha = m > 0 ? 1 / m : 0 (a stationary start: alpha = 0).
+ *      Else s = w - w_prev, y = grad - grad_prev (float64 differences of the float32 values), alpha = <s, s> / <s, y> if <s, y> > 0,
+ *      else step_max; clamped to [step_min, step_max]. The dot products in float64 by a fixed tree: chunks of 2048 entries, one wave
+ *      each, lane t adds the entries t, t + 64, ... in order, butterfly (32, ..., 1); the chunk sums are added the same way;
+ *   6. w_prev = w, grad_prev = grad, w = P(w - float32(alpha) * grad) in float32 (P(x) = x > 0 ? x : +0), the product rounded before the subtraction;
+ *   7. guard: if f_k is not finite, 4.-6. do not happen; w = w_best, the pair is forgotten, the next iteration takes the first rule.
+ *
+ * rtd_optimizer_create       options may be NULL (rtd_default_optimizer_options: step_min 1e-30, step_max 1e30, history_capacity
+ *                            4096). w and w_best start as each field's own spot weights. Synchronous.
+ * rtd_optimizer_set_weights  dev_w: [L][ny][nx] float32 of field field_index, copied on the stream into w. Before the first run it
+ *                            sets w_best too (the start weights); later it keeps w_best, f_best and the Barzilai-Borwein pair.
+ * rtd_optimizer_run          launches n_iterations iterations; asynchronous, launches only (no allocation, copy or synchronisation: a
+ *                            run can be captured into a graph). A later run continues where the last stopped. n_iterations = 0: no-op.
+ * rtd_optimizer_result       waits for the stream; report and the first min(capacity, report.history_len) history entries to host
+ *                            memory (history may be NULL with capacity 0). RTD_ERR_INVALID_ARG (report still filled) when an iterate
+ *                            was not finite before any finite one had been seen: the start itself is unusable.
+ * rtd_optimizer_weights      asynchronous copy of field field_index's part of w (best == 0) or w_best (best != 0) to dev_w_out.
+ * rtd_optimizer_dose         the optimiser's own volume. After a run it holds the dose of the iterate that ENTERED the last iteration
+ *                            (the one f_last belongs to), not of the updated w.
+ * RTD_ERR_INVALID_ARG: a null pointer, 0 or more than 16 fields, a remote field, fields of different dose grids, an objective on
+ * other dims or without terms, a field index out of range, step_min > step_max or not positive. After a refusal every object stays
+ * usable. Not available: nuclear_corr, remote fields, the rtd_plan_* path (as the matrix itself).
+ */
+enum { RTD_OBJ_SQ_DEVIATION = 0, RTD_OBJ_SQ_OVERDOSE = 1, RTD_OBJ_SQ_UNDERDOSE = 2, RTD_OBJ_MEAN = 3 };
+#define RTD_OBJ_MAX_TERMS 64
+#define RTD_OPT_MAX_FIELDS 16
+
+typedef struct rtd_objective_term {
+    int32_t kind;          /* RTD_OBJ_* */
+    int32_t roi;           /* as returned by rtd_objective_add_roi */
+    double weight;         /* > 0 */
+    double dose_level;     /* in the unit of the dose volume; ignored by RTD_OBJ_MEAN */
+} rtd_objective_term;
+
+typedef struct rtd_optimizer_options {
+    double step_min;            /* bounds of the Barzilai-Borwein step: they only keep it finite */
+    double step_max;
+    uint32_t history_capacity;  /* objective values kept on the device (later iterations are not recorded) */
+    int32_t reserved[3];
+} rtd_optimizer_options;
+
+typedef struct rtd_optimizer_report {
+    double f_last;              /* objective of the iterate that entered the last iteration */
+    double f_best;              /* smallest finite objective seen (+inf before any) */
+    double step;                /* alpha of the last iteration (unchanged by a guarded one) */
+    int64_t best_iteration;     /* iteration (0-based, counted over all runs) whose iterate is w_best; -1 before any */
+    uint32_t iterations;        /* iterations run so far */
+    uint32_t history_len;       /* min(iterations, history_capacity) */
+    int32_t guarded;            /* iterations that took the guard */
+    int32_t reserved[3];
+} rtd_optimizer_report;
+
+typedef struct rtd_objective_s* rtd_objective;
+typedef struct rtd_optimizer_s* rtd_optimizer;
+
+int rtd_objective_create(rtd_handle h, const uint32_t dose_dims[3], rtd_objective* out);
+int rtd_objective_add_roi(rtd_handle h, rtd_objective obj, const int32_t* voxels, size_t n, int32_t* roi_id);
+int rtd_objective_add_term(rtd_handle h, rtd_objective obj, const rtd_objective_term* t);
+int rtd_objective_eval(rtd_handle h, rtd_objective obj, const float* dev_dose, double* dev_values, float* dev_voxel_grad);
+int rtd_objective_destroy(rtd_handle h, rtd_objective obj);
+
+void rtd_default_optimizer_options(rtd_optimizer_options* out);
+int rtd_optimizer_create(rtd_handle h, const rtd_field* fields, uint32_t n_fields, rtd_objective obj, const rtd_optimizer_options* o,
+                         rtd_optimizer* out);
+int rtd_optimizer_set_weights(rtd_handle h, rtd_optimizer opt, uint32_t field_index, const float* dev_w);
+int rtd_optimizer_run(rtd_handle h, rtd_optimizer opt, uint32_t n_iterations);
+int rtd_optimizer_result(rtd_handle h, rtd_optimizer opt, rtd_optimizer_report* r, double* history, uint32_t capacity);
+int rtd_optimizer_weights(rtd_handle h, rtd_optimizer opt, uint32_t field_index, float* dev_w_out, int best);
+int rtd_optimizer_dose(rtd_handle h, rtd_optimizer opt, const float** dev_dose);
+int rtd_optimizer_destroy(rtd_handle h, rtd_optimizer opt);
+
+/*
  * ---- Multi-GPU plans behind the boundary (SURVEY.md 8(b) "Threading": one handle and one host thread per device) ----
  *
  * rtd_plan is the reference-shaped call on several GPUs of one process: the 4-beam cudaWrapperProtons of the C++ shim uses

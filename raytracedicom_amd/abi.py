@@ -18,6 +18,9 @@ RTD_ERR_NOT_READY = -4
 RTD_ERR_IO = -5
 RTD_ERR_NO_DEVICE = -6
 RTD_NUC_OFF, RTD_NUC_SOUKUP, RTD_NUC_FLUKA, RTD_NUC_GAUSS_FIT = 0, 1, 2, 3
+RTD_OBJ_SQ_DEVIATION, RTD_OBJ_SQ_OVERDOSE, RTD_OBJ_SQ_UNDERDOSE, RTD_OBJ_MEAN = 0, 1, 2, 3
+RTD_OBJ_MAX_TERMS = 64
+RTD_OPT_MAX_FIELDS = 16
 
 c_float_p = C.POINTER(C.c_float)
 
@@ -107,6 +110,31 @@ class RtdPlanTiming(C.Structure):
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
+
+
+class RtdObjectiveTerm(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("roi", C.c_int32), ("weight", C.c_double), ("dose_level", C.c_double)]
+
+
+class RtdOptimizerOptions(C.Structure):
+    _fields_ = [("step_min", C.c_double), ("step_max", C.c_double), ("history_capacity", C.c_uint32), ("reserved", C.c_int32 * 3)]
+
+
+class RtdOptimizerReport(C.Structure):
+    _fields_ = [("f_last", C.c_double), ("f_best", C.c_double), ("step", C.c_double), ("best_iteration", C.c_int64),
+                ("iterations", C.c_uint32), ("history_len", C.c_uint32), ("guarded", C.c_int32), ("reserved", C.c_int32 * 3)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
+
+
+def default_optimizer_options():
+    """rtd_default_optimizer_options: the step bounds only keep the Barzilai-Borwein step finite."""
+    o = RtdOptimizerOptions()
+    o.step_min = 1e-30
+    o.step_max = 1e30
+    o.history_capacity = 4096
+    return o
 
 
 def default_options():

@@ -10,6 +10,7 @@
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
 
+#include <algorithm>
 #include <array>
 #include <cmath>
 #include <cstdio>
@@ -31,6 +32,7 @@
 #include "rtd_adjoint.hpp"
 #include "rtd_dij.hpp"
 #include "rtd_dij_apply.hpp"
+#include "rtd_optimize.hpp"
 
 using namespace rtd;
 
@@ -1816,6 +1818,356 @@ int rtd_field_dose_influence_apply_t(rtd_handle hh, rtd_field ff, const float* d
                                                                             f->dDijPartial, nChunks);
     k_dijap_reduce_t<<<(unsigned)((nSpot + 3) / 4), 256, 0, h->stream>>>((const int*)f->dDijChunkFirst, (const float*)f->dDijPartial, dev_spot_grad, nSpot);
     RTD_HIP(h, hipGetLastError());
+    return RTD_OK;
+}
+
+// ---- Dose objectives and the resident optimiser (include/rtd.h; kernels in rtd_optimize.hpp) ----
+// Plain owned allocations: neither object is a field, so neither goes through a field's buffer table.
+
+namespace {
+
+struct rtd_objective_impl {
+    uint32_t dims[3] = {0, 0, 0};
+    size_t nVox = 0;
+    std::vector<std::vector<int32_t>> rois;
+    std::vector<rtd_objective_term> terms;
+    bool built = false;           // the device tables belong to rois / terms as they are
+    int nU = 0, nBlocks = 0;      // union voxels; blocks of k_obj_eval
+    int* dUv = nullptr; int* dTPtr = nullptr; unsigned char* dTIdx = nullptr; ObjTerm* dTerms = nullptr; double* dPartial = nullptr;
+    void freeTables() {
+        for (void** p : {(void**)&dUv, (void**)&dTPtr, (void**)&dTIdx, (void**)&dTerms, (void**)&dPartial}) if (*p) { (void)hipFree(*p); *p = nullptr; }
+        built = false;
+    }
+};
+
+struct rtd_optimizer_impl {
+    std::vector<rtd_field_impl*> fields;
+    std::vector<int> offset;      // offset[f] .. offset[f + 1]: field f's part of the concatenated vectors
+    rtd_objective_impl* obj = nullptr;
+    rtd_optimizer_options opt{};
+    int n = 0, nCh = 0;
+    size_t nVox = 0;
+    uint32_t launched = 0;        // iterations launched so far (a count of launches, not a finding of the device)
+    float *dDose = nullptr, *dG = nullptr, *dVec = nullptr;   // dVec: w | w_prev | grad | grad_prev | w_best, n each
+    double *dHistory = nullptr, *dValues = nullptr, *dPart = nullptr;
+    OptState* dState = nullptr;
+    float* w() const { return dVec; }
+    float* wPrev() const { return dVec + n; }
+    float* grad() const { return dVec + 2 * (size_t)n; }
+    float* gradPrev() const { return dVec + 3 * (size_t)n; }
+    float* wBest() const { return dVec + 4 * (size_t)n; }
+    void freeAll() {
+        for (void** p : {(void**)&dDose, (void**)&dG, (void**)&dVec, (void**)&dHistory, (void**)&dValues, (void**)&dPart, (void**)&dState})
+            if (*p) { (void)hipFree(*p); *p = nullptr; }
+    }
+};
+
+// The union of the ROIs ascending and, per union voxel, its terms in term order (CSR); set-up work, on the host. Synchronous.
+int buildObjective(rtd_handle_impl* h, rtd_objective_impl* o) {
+    RTD_HIP(h, hipSetDevice(h->device));
+    RTD_HIP(h, hipStreamSynchronize(h->stream));                      // (an eval in flight may still read the old tables)
+    o->freeTables();
+    std::vector<uint64_t> keys;                                       // voxel << 8 | (term + 1); 0 in the low byte: the voxel alone
+    size_t total = 0;
+    for (const auto& r : o->rois) total += r.size();
+    for (const auto& t : o->terms) total += o->rois[(size_t)t.roi].size();
+    keys.reserve(total);
+    for (const auto& r : o->rois) for (int32_t v : r) keys.push_back((uint64_t)(uint32_t)v << 8);
+    for (size_t t = 0; t < o->terms.size(); ++t) for (int32_t v : o->rois[(size_t)o->terms[t].roi]) keys.push_back((uint64_t)(uint32_t)v << 8 | (t + 1));
+    std::sort(keys.begin(), keys.end());
+    std::vector<int> uv, tPtr;
+    std::vector<unsigned char> tIdx;
+    for (size_t k = 0; k < keys.size(); ++k) {
+        const int v = (int)(keys[k] >> 8), t = (int)(keys[k] & 0xff);
+        if (uv.empty() || uv.back() != v) { uv.push_back(v); tPtr.push_back((int)tIdx.size()); }
+        if (t) tIdx.push_back((unsigned char)(t - 1));
+    }
+    tPtr.push_back((int)tIdx.size());
+    std::vector<ObjTerm> terms(o->terms.size());
+    for (size_t t = 0; t < terms.size(); ++t) {
+        const double N = (double)o->rois[(size_t)o->terms[t].roi].size(), wt = o->terms[t].weight;
+        terms[t] = ObjTerm{o->terms[t].dose_level, 2.0 * wt / N, wt / N, o->terms[t].kind, 0};
+    }
+    o->nU = (int)uv.size();
+    o->nBlocks = (o->nU + 255) / 256;
+    hipError_t e = hipMalloc((void**)&o->dUv, std::max<size_t>(uv.size(), 1) * sizeof(int));
+    if (e == hipSuccess) e = hipMalloc((void**)&o->dTPtr, tPtr.size() * sizeof(int));
+    if (e == hipSuccess) e = hipMalloc((void**)&o->dTIdx, std::max<size_t>(tIdx.size(), 1));
+    if (e == hipSuccess) e = hipMalloc((void**)&o->dTerms, std::max<size_t>(terms.size(), 1) * sizeof(ObjTerm));
+    if (e == hipSuccess) e = hipMalloc((void**)&o->dPartial, std::max<size_t>((size_t)o->nBlocks * terms.size(), 1) * sizeof(double));
+    if (e == hipSuccess && !uv.empty()) e = hipMemcpy(o->dUv, uv.data(), uv.size() * sizeof(int), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(o->dTPtr, tPtr.data(), tPtr.size() * sizeof(int), hipMemcpyHostToDevice);
+    if (e == hipSuccess && !tIdx.empty()) e = hipMemcpy(o->dTIdx, tIdx.data(), tIdx.size(), hipMemcpyHostToDevice);
+    if (e == hipSuccess && !terms.empty()) e = hipMemcpy(o->dTerms, terms.data(), terms.size() * sizeof(ObjTerm), hipMemcpyHostToDevice);
+    if (e != hipSuccess) { o->freeTables(); RTD_HIP(h, e); }
+    o->built = true;
+    return RTD_OK;
+}
+
+// eval without the argument checks of the entry point: two launches once the tables exist.
+int evalObjective(rtd_handle_impl* h, rtd_objective_impl* o, const float* dDose, double* dValues, float* dGrad) {
+    if (!o->built) { const int st = buildObjective(h, o); if (st != RTD_OK) return st; }
+    const int nTerms = (int)o->terms.size();
+    if (o->nBlocks)
+        k_obj_eval<<<(unsigned)o->nBlocks, 256, 0, h->stream>>>((const int*)o->dUv, (const int*)o->dTPtr, (const unsigned char*)o->dTIdx, (const ObjTerm*)o->dTerms,
+                                                                nTerms, o->nU, dDose, dGrad, o->dPartial, o->nBlocks);
+    k_obj_reduce<<<1, 256, 0, h->stream>>>((const double*)o->dPartial, o->nBlocks, (const ObjTerm*)o->dTerms, nTerms, dValues);
+    RTD_HIP(h, hipGetLastError());
+    return RTD_OK;
+}
+
+// The two products of an iteration. A matrix-free route (rtd_field_compute + rtd_field_spot_gradient) would replace these two.
+// dose = sum_f Dij_f w_f, bit for bit "zero the volume, apply(init = 0) per field in list order": the row boxes of the fields 1..
+// are cleared, field 0 then WRITES its whole box (init = 1: s or +0, and 0 + s = s since a sum is never -0), the others accumulate.
+int optForward(rtd_handle hh, rtd_handle_impl* h, rtd_optimizer_impl* p) {
+    for (size_t i = 1; i < p->fields.size(); ++i) {
+        const rtd_field_impl* f = p->fields[i];
+        const long long nRows = (long long)f->dijRowsN;
+        if (nRows) k_opt_clear_box<<<(unsigned)((nRows + 255) / 256), 256, 0, h->stream>>>(p->dDose, (int)f->doseDims[0], (int)f->doseDims[1], f->dijBox, nRows);
+    }
+    for (size_t i = 0; i < p->fields.size(); ++i) {
+        const int st = rtd_field_dose_influence_apply(hh, reinterpret_cast<rtd_field>(p->fields[i]), p->w() + p->offset[i], p->dDose, i == 0 ? 1 : 0);
+        if (st != RTD_OK) return st;
+    }
+    return RTD_OK;
+}
+int optAdjoint(rtd_handle hh, rtd_optimizer_impl* p) {
+    for (size_t i = 0; i < p->fields.size(); ++i) {
+        const int st = rtd_field_dose_influence_apply_t(hh, reinterpret_cast<rtd_field>(p->fields[i]), p->dG, p->grad() + p->offset[i]);
+        if (st != RTD_OK) return st;
+    }
+    return RTD_OK;
+}
+
+}  // namespace
+
+int rtd_objective_create(rtd_handle hh, const uint32_t dose_dims[3], rtd_objective* out) {
+    auto* h = reinterpret_cast<rtd_handle_impl*>(hh);
+    if (!h) return RTD_ERR_INVALID_ARG;
+    if (!dose_dims || !out) return fail(h, RTD_ERR_INVALID_ARG, "rtd_objective_create: null pointer");
+    *out = nullptr;
+    const size_t nVox = (size_t)dose_dims[0] * dose_dims[1] * dose_dims[2];
+    if (!nVox || nVox > (size_t)0x7fffffff) return fail(h, RTD_ERR_INVALID_ARG, "rtd_objective_create: a zero dimension or more than 2^31 - 1 voxels");
+    auto* o = new rtd_objective_impl();
+    for (int i = 0; i < 3; ++i) o->dims[i] = dose_dims[i];
+    o->nVox = nVox;
+    *out = reinterpret_cast<rtd_objective>(o);
+    return RTD_OK;
+}
+
+int rtd_objective_add_roi(rtd_handle hh, rtd_objective oo, const int32_t* voxels, size_t n, int32_t* roi_id) {
+    auto* h = reinterpret_cast<rtd_handle_impl*>(hh);
+    auto* o = reinterpret_cast<rtd_objective_impl*>(oo);
+    if (!h) return RTD_ERR_INVALID_ARG;
+    if (!o || !voxels || !roi_id) return fail(h, RTD_ERR_INVALID_ARG, "rtd_objective_add_roi: null pointer");
+    if (!n) return fail(h, RTD_ERR_INVALID_ARG, "rtd_objective_add_roi: an ROI needs at least one voxel");
+    for (size_t i = 0; i < n; ++i)
+        if (voxels[i] < 0 || (size_t)voxels[i] >= o->nVox || (i && voxels[i] <= voxels[i - 1]))
+            return fail(h, RTD_ERR_INVALID_ARG, "rtd_objective_add_roi: voxel indices must be strictly ascending and inside the dose grid");
+    o->rois.emplace_back(voxels, voxels + n);
+    o->built = false;
+    *roi_id = (int32_t)o->rois.size() - 1;
+    return RTD_OK;
+}
+
+int rtd_objective_add_term(rtd_handle hh, rtd_objective oo, const rtd_objective_term* t) {
+    auto* h = reinterpret_cast<rtd_handle_impl*>(hh);
+    auto* o = reinterpret_cast<rtd_objective_impl*>(oo);
+    if (!h) return RTD_ERR_INVALID_ARG;
+    if (!o || !t) return fail(h, RTD_ERR_INVALID_ARG, "rtd_objective_add_term: null pointer");
+    if (t->kind < RTD_OBJ_SQ_DEVIATION || t->kind > RTD_OBJ_MEAN) return fail(h, RTD_ERR_INVALID_ARG, "rtd_objective_add_term: unknown kind");
+    if (t->roi < 0 || (size_t)t->roi >= o->rois.size()) return fail(h, RTD_ERR_INVALID_ARG, "rtd_objective_add_term: unknown ROI");
+    if (!(t->weight > 0.0) || !std::isfinite(t->weight)) return fail(h, RTD_ERR_INVALID_ARG, "rtd_objective_add_term: the weight must be positive and finite");
+    if (!std::isfinite(t->dose_level)) return fail(h, RTD_ERR_INVALID_ARG, "rtd_objective_add_term: the dose level must be finite");
+    if (o->terms.size() >= (size_t)kObjMaxTerms) return fail(h, RTD_ERR_INVALID_ARG, "rtd_objective_add_term: more than RTD_OBJ_MAX_TERMS terms");
+    o->terms.push_back(*t);
+    o->built = false;
+    return RTD_OK;
+}
+
+int rtd_objective_eval(rtd_handle hh, rtd_objective oo, const float* dev_dose, double* dev_values, float* dev_voxel_grad) {
+    auto* h = reinterpret_cast<rtd_handle_impl*>(hh);
+    auto* o = reinterpret_cast<rtd_objective_impl*>(oo);
+    if (!h) return RTD_ERR_INVALID_ARG;
+    if (!o || !dev_dose || !dev_values || !dev_voxel_grad) return fail(h, RTD_ERR_INVALID_ARG, "rtd_objective_eval: null pointer");
+    if (o->terms.empty()) return fail(h, RTD_ERR_INVALID_ARG, "rtd_objective_eval: the objective has no terms");
+    RTD_HIP(h, hipSetDevice(h->device));
+    return evalObjective(h, o, dev_dose, dev_values, dev_voxel_grad);
+}
+
+int rtd_objective_destroy(rtd_handle hh, rtd_objective oo) {
+    auto* h = reinterpret_cast<rtd_handle_impl*>(hh);
+    auto* o = reinterpret_cast<rtd_objective_impl*>(oo);
+    if (!h || !o) return RTD_ERR_INVALID_ARG;
+    (void)hipSetDevice(h->device);
+    (void)hipStreamSynchronize(h->stream);
+    o->freeTables();
+    delete o;
+    return RTD_OK;
+}
+
+void rtd_default_optimizer_options(rtd_optimizer_options* o) {
+    std::memset(o, 0, sizeof *o);
+    o->step_min = 1e-30; o->step_max = 1e30; o->history_capacity = 4096;
+}
+
+int rtd_optimizer_create(rtd_handle hh, const rtd_field* fields, uint32_t n_fields, rtd_objective oo, const rtd_optimizer_options* opt,
+                         rtd_optimizer* out) {
+    auto* h = reinterpret_cast<rtd_handle_impl*>(hh);
+    auto* o = reinterpret_cast<rtd_objective_impl*>(oo);
+    if (!h) return RTD_ERR_INVALID_ARG;
+    if (!fields || !o || !out) return fail(h, RTD_ERR_INVALID_ARG, "rtd_optimizer_create: null pointer");
+    *out = nullptr;
+    if (n_fields < 1 || n_fields > RTD_OPT_MAX_FIELDS) return fail(h, RTD_ERR_INVALID_ARG, "rtd_optimizer_create: 1 to 16 fields");
+    rtd_optimizer_options op;
+    rtd_default_optimizer_options(&op);
+    if (opt) op = *opt;
+    if (!(op.step_min > 0.0) || !(op.step_max >= op.step_min) || !std::isfinite(op.step_max))
+        return fail(h, RTD_ERR_INVALID_ARG, "rtd_optimizer_create: needs 0 < step_min <= step_max < inf");
+    for (uint32_t i = 0; i < n_fields; ++i) {
+        auto* f = reinterpret_cast<rtd_field_impl*>(fields[i]);
+        if (!f) return fail(h, RTD_ERR_INVALID_ARG, "rtd_optimizer_create: null field");
+        if (f->remote) return fail(h, RTD_ERR_INVALID_ARG, "rtd_optimizer_create: a remote field has no matrix");
+        for (int a = 0; a < 3; ++a)
+            if (f->doseDims[a] != o->dims[a]) return fail(h, RTD_ERR_INVALID_ARG, "rtd_optimizer_create: the fields and the objective must share one dose grid");
+    }
+    if (o->terms.empty()) return fail(h, RTD_ERR_INVALID_ARG, "rtd_optimizer_create: the objective has no terms");
+    for (uint32_t i = 0; i < n_fields; ++i)
+        if (!reinterpret_cast<rtd_field_impl*>(fields[i])->dijDone)
+            return fail(h, RTD_ERR_NOT_READY, "rtd_optimizer_create: a field has no dose-influence matrix (call rtd_field_dose_influence first)");
+    RTD_HIP(h, hipSetDevice(h->device));
+    for (uint32_t i = 0; i < n_fields; ++i) { const int st = rtd_field_dose_influence_prepare(hh, fields[i]); if (st != RTD_OK) return st; }
+    if (!o->built) { const int st = buildObjective(h, o); if (st != RTD_OK) return st; }
+    auto* p = new rtd_optimizer_impl();
+    p->obj = o; p->opt = op; p->nVox = o->nVox;
+    p->offset.push_back(0);
+    long long total = 0;
+    for (uint32_t i = 0; i < n_fields; ++i) {
+        auto* f = reinterpret_cast<rtd_field_impl*>(fields[i]);
+        p->fields.push_back(f);
+        total += (long long)f->fc.spotNx * f->fc.spotNy * f->fc.L;
+        if (total > 0x7fffffffLL) { delete p; return fail(h, RTD_ERR_INVALID_ARG, "rtd_optimizer_create: more than 2^31 - 1 spots"); }
+        p->offset.push_back((int)total);
+    }
+    p->n = (int)total;
+    p->nCh = (p->n + kOptChunk - 1) / kOptChunk;
+    const size_t n = (size_t)p->n, cap = std::max<size_t>(op.history_capacity, 1);
+    hipStream_t s = h->stream;
+    hipError_t e = hipMalloc((void**)&p->dDose, p->nVox * sizeof(float));
+    if (e == hipSuccess) e = hipMalloc((void**)&p->dG, p->nVox * sizeof(float));
+    if (e == hipSuccess) e = hipMalloc((void**)&p->dVec, 5 * n * sizeof(float));
+    if (e == hipSuccess) e = hipMalloc((void**)&p->dHistory, cap * sizeof(double));
+    if (e == hipSuccess) e = hipMalloc((void**)&p->dValues, (1 + kObjMaxTerms) * sizeof(double));
+    if (e == hipSuccess) e = hipMalloc((void**)&p->dPart, 3 * (size_t)p->nCh * sizeof(double));
+    if (e == hipSuccess) e = hipMalloc((void**)&p->dState, sizeof(OptState));
+    if (e == hipSuccess) e = hipMemsetAsync(p->dDose, 0, p->nVox * sizeof(float), s);
+    if (e == hipSuccess) e = hipMemsetAsync(p->dG, 0, p->nVox * sizeof(float), s);
+    if (e == hipSuccess) e = hipMemsetAsync(p->dVec, 0, 5 * n * sizeof(float), s);
+    if (e == hipSuccess) e = hipMemsetAsync(p->dHistory, 0, cap * sizeof(double), s);
+    if (e == hipSuccess) e = hipMemsetAsync(p->dValues, 0, (1 + kObjMaxTerms) * sizeof(double), s);
+    OptState st0{};
+    st0.fBest = std::numeric_limits<double>::infinity(); st0.bestIter = -1;
+    if (e == hipSuccess) e = hipMemcpyAsync(p->dState, &st0, sizeof st0, hipMemcpyHostToDevice, s);
+    for (uint32_t i = 0; i < n_fields && e == hipSuccess; ++i) {
+        const size_t cnt = (size_t)(p->offset[i + 1] - p->offset[i]) * sizeof(float);
+        e = hipMemcpyAsync(p->w() + p->offset[i], p->fields[i]->dSpotWeights, cnt, hipMemcpyDeviceToDevice, s);
+        if (e == hipSuccess) e = hipMemcpyAsync(p->wBest() + p->offset[i], p->fields[i]->dSpotWeights, cnt, hipMemcpyDeviceToDevice, s);
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(s);                 // (st0 lives on this stack)
+    if (e != hipSuccess) { (void)hipStreamSynchronize(s); p->freeAll(); delete p; RTD_HIP(h, e); }
+    *out = reinterpret_cast<rtd_optimizer>(p);
+    return RTD_OK;
+}
+
+int rtd_optimizer_set_weights(rtd_handle hh, rtd_optimizer pp, uint32_t field_index, const float* dev_w) {
+    auto* h = reinterpret_cast<rtd_handle_impl*>(hh);
+    auto* p = reinterpret_cast<rtd_optimizer_impl*>(pp);
+    if (!h) return RTD_ERR_INVALID_ARG;
+    if (!p || !dev_w) return fail(h, RTD_ERR_INVALID_ARG, "rtd_optimizer_set_weights: null pointer");
+    if (field_index >= p->fields.size()) return fail(h, RTD_ERR_INVALID_ARG, "rtd_optimizer_set_weights: field index out of range");
+    RTD_HIP(h, hipSetDevice(h->device));
+    const size_t cnt = (size_t)(p->offset[field_index + 1] - p->offset[field_index]) * sizeof(float);
+    RTD_HIP(h, hipMemcpyAsync(p->w() + p->offset[field_index], dev_w, cnt, hipMemcpyDeviceToDevice, h->stream));
+    if (!p->launched) RTD_HIP(h, hipMemcpyAsync(p->wBest() + p->offset[field_index], dev_w, cnt, hipMemcpyDeviceToDevice, h->stream));
+    return RTD_OK;
+}
+
+int rtd_optimizer_run(rtd_handle hh, rtd_optimizer pp, uint32_t n_iterations) {
+    auto* h = reinterpret_cast<rtd_handle_impl*>(hh);
+    auto* p = reinterpret_cast<rtd_optimizer_impl*>(pp);
+    if (!h) return RTD_ERR_INVALID_ARG;
+    if (!p) return fail(h, RTD_ERR_INVALID_ARG, "rtd_optimizer_run: null pointer");
+    if (p->obj->terms.empty()) return fail(h, RTD_ERR_INVALID_ARG, "rtd_optimizer_run: the objective has no terms");
+    RTD_HIP(h, hipSetDevice(h->device));
+    hipStream_t s = h->stream;
+    for (uint32_t k = 0; k < n_iterations; ++k) {
+        int st = optForward(hh, h, p);                                                    // 1.
+        if (st == RTD_OK) st = evalObjective(h, p->obj, p->dDose, p->dValues, p->dG);     // 2.
+        if (st == RTD_OK) st = optAdjoint(hh, p);                                         // 3.
+        if (st != RTD_OK) return st;
+        k_opt_partials<<<(unsigned)((p->nCh + 3) / 4), 256, 0, s>>>((const float*)p->w(), (const float*)p->wPrev(), (const float*)p->grad(),
+                                                                   (const float*)p->gradPrev(), p->n, p->nCh, p->dPart);
+        k_opt_step<<<1, 64, 0, s>>>((const double*)p->dPart, p->nCh, (const double*)p->dValues, p->dState, p->dHistory, p->opt.history_capacity,
+                                    p->opt.step_min, p->opt.step_max);                    // 2. (history), 4., 5., 7.: the decisions
+        k_opt_update<<<(unsigned)((p->n + 255) / 256), 256, 0, s>>>((const OptState*)p->dState, p->w(), p->wPrev(), (const float*)p->grad(), p->gradPrev(),
+                                                                   p->wBest(), p->n);     // 4., 6., 7.: per entry
+        RTD_HIP(h, hipGetLastError());
+        ++p->launched;
+    }
+    return RTD_OK;
+}
+
+int rtd_optimizer_result(rtd_handle hh, rtd_optimizer pp, rtd_optimizer_report* r, double* history, uint32_t capacity) {
+    auto* h = reinterpret_cast<rtd_handle_impl*>(hh);
+    auto* p = reinterpret_cast<rtd_optimizer_impl*>(pp);
+    if (!h) return RTD_ERR_INVALID_ARG;
+    if (!p || !r || (capacity && !history)) return fail(h, RTD_ERR_INVALID_ARG, "rtd_optimizer_result: null pointer");
+    RTD_HIP(h, hipSetDevice(h->device));
+    OptState st{};
+    RTD_HIP(h, hipMemcpyAsync(&st, p->dState, sizeof st, hipMemcpyDeviceToHost, h->stream));
+    RTD_HIP(h, hipStreamSynchronize(h->stream));
+    std::memset(r, 0, sizeof *r);
+    r->f_last = st.fLast; r->f_best = st.fBest; r->step = st.alpha; r->best_iteration = st.bestIter;
+    r->iterations = (uint32_t)st.iter; r->history_len = (uint32_t)std::min<long long>(st.iter, (long long)p->opt.history_capacity);
+    r->guarded = st.guarded;
+    const uint32_t cnt = std::min(capacity, r->history_len);
+    if (cnt) {
+        RTD_HIP(h, hipMemcpyAsync(history, p->dHistory, cnt * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+        RTD_HIP(h, hipStreamSynchronize(h->stream));
+    }
+    if (st.startBad) return fail(h, RTD_ERR_INVALID_ARG, "rtd_optimizer_result: the objective of the start weights is not finite");
+    return RTD_OK;
+}
+
+int rtd_optimizer_weights(rtd_handle hh, rtd_optimizer pp, uint32_t field_index, float* dev_w_out, int best) {
+    auto* h = reinterpret_cast<rtd_handle_impl*>(hh);
+    auto* p = reinterpret_cast<rtd_optimizer_impl*>(pp);
+    if (!h) return RTD_ERR_INVALID_ARG;
+    if (!p || !dev_w_out) return fail(h, RTD_ERR_INVALID_ARG, "rtd_optimizer_weights: null pointer");
+    if (field_index >= p->fields.size()) return fail(h, RTD_ERR_INVALID_ARG, "rtd_optimizer_weights: field index out of range");
+    RTD_HIP(h, hipSetDevice(h->device));
+    const size_t cnt = (size_t)(p->offset[field_index + 1] - p->offset[field_index]) * sizeof(float);
+    RTD_HIP(h, hipMemcpyAsync(dev_w_out, (best ? p->wBest() : p->w()) + p->offset[field_index], cnt, hipMemcpyDeviceToDevice, h->stream));
+    return RTD_OK;
+}
+
+int rtd_optimizer_dose(rtd_handle hh, rtd_optimizer pp, const float** dev_dose) {
+    auto* h = reinterpret_cast<rtd_handle_impl*>(hh);
+    auto* p = reinterpret_cast<rtd_optimizer_impl*>(pp);
+    if (!h) return RTD_ERR_INVALID_ARG;
+    if (!p || !dev_dose) return fail(h, RTD_ERR_INVALID_ARG, "rtd_optimizer_dose: null pointer");
+    *dev_dose = p->dDose;
+    return RTD_OK;
+}
+
+int rtd_optimizer_destroy(rtd_handle hh, rtd_optimizer pp) {
+    auto* h = reinterpret_cast<rtd_handle_impl*>(hh);
+    auto* p = reinterpret_cast<rtd_optimizer_impl*>(pp);
+    if (!h || !p) return RTD_ERR_INVALID_ARG;
+    (void)hipSetDevice(h->device);
+    (void)hipStreamSynchronize(h->stream);
+    p->freeAll();
+    delete p;
     return RTD_OK;
 }
 

@@ -86,6 +86,20 @@ def lib():
         L.rtd_field_dose_influence_apply.argtypes = [vp, vp, vp, vp, C.c_int]
         L.rtd_field_dose_influence_apply_t.argtypes = [vp, vp, vp, vp]
         L.rtd_field_dose_influence_device.argtypes = [vp, vp, vpp, vpp, vpp, C.POINTER(C.c_size_t)]
+        L.rtd_objective_create.argtypes = [vp, u3, vpp]
+        L.rtd_objective_add_roi.argtypes = [vp, vp, i3, C.c_size_t, i3]
+        L.rtd_objective_add_term.argtypes = [vp, vp, C.POINTER(abi.RtdObjectiveTerm)]
+        L.rtd_objective_eval.argtypes = [vp, vp, vp, vp, vp]
+        L.rtd_objective_destroy.argtypes = [vp, vp]
+        L.rtd_default_optimizer_options.argtypes = [C.POINTER(abi.RtdOptimizerOptions)]
+        L.rtd_default_optimizer_options.restype = None
+        L.rtd_optimizer_create.argtypes = [vp, vpp, C.c_uint32, vp, C.POINTER(abi.RtdOptimizerOptions), vpp]
+        L.rtd_optimizer_set_weights.argtypes = [vp, vp, C.c_uint32, vp]
+        L.rtd_optimizer_run.argtypes = [vp, vp, C.c_uint32]
+        L.rtd_optimizer_result.argtypes = [vp, vp, C.POINTER(abi.RtdOptimizerReport), C.POINTER(C.c_double), C.c_uint32]
+        L.rtd_optimizer_weights.argtypes = [vp, vp, C.c_uint32, vp, C.c_int]
+        L.rtd_optimizer_dose.argtypes = [vp, vp, vpp]
+        L.rtd_optimizer_destroy.argtypes = [vp, vp]
         L.rtd_host_register.argtypes = [vp, C.c_size_t]
         L.rtd_host_unregister.argtypes = [vp]
         L.rtd_plan_create.argtypes = [C.POINTER(C.c_int), C.c_int, vpp]
@@ -301,6 +315,112 @@ class Field:
             pass
 
 
+class Objective:
+    """rtd_objective_*: ROIs and penalty terms on one dose grid; eval() gives the objective, its terms and the voxel gradient on the
+    device. Kinds: abi.RTD_OBJ_SQ_DEVIATION / _SQ_OVERDOSE / _SQ_UNDERDOSE / _MEAN."""
+
+    def __init__(self, eng, dose_dims):
+        self.eng = eng
+        self._h = C.c_void_p()
+        self.dims = tuple(int(d) for d in dose_dims)
+        self.n_terms = 0
+        eng._check(lib().rtd_objective_create(eng._h, abi.uint3(self.dims), C.byref(self._h)))
+
+    def add_roi(self, mask_or_indices):
+        """A boolean mask of the dose grid ([Z][Y][X] or flat) or linear voxel indices (strictly ascending) -> the ROI's id."""
+        a = np.asarray(mask_or_indices)
+        idx = np.flatnonzero(a) if a.dtype == np.bool_ else a.reshape(-1)
+        idx = np.ascontiguousarray(idx, dtype=np.int32)
+        rid = C.c_int32(-1)
+        self.eng._check(lib().rtd_objective_add_roi(self.eng._h, self._h, idx.ctypes.data_as(C.POINTER(C.c_int32)), idx.size, C.byref(rid)))
+        return int(rid.value)
+
+    def add_term(self, kind, roi, weight, level=0.0):
+        t = abi.RtdObjectiveTerm(int(kind), int(roi), float(weight), float(level))
+        self.eng._check(lib().rtd_objective_add_term(self.eng._h, self._h, C.byref(t)))
+        self.n_terms += 1
+
+    def eval(self, dev_dose, dev_g, dev_values=None):
+        """rtd_objective_eval: dev_dose, dev_g device pointers of float32 volumes (dev_g zeroed once by the caller: only the voxels
+        of the ROIs are written). With dev_values (device pointer, float64[1 + n_terms]) asynchronous, returns None; without,
+        returns the values as a float64 array ([0] the objective, [1 + t] term t)."""
+        own = dev_values is None
+        dv = self.eng.device_alloc(8 * (1 + abi.RTD_OBJ_MAX_TERMS)) if own else dev_values
+        try:
+            self.eng._check(lib().rtd_objective_eval(self.eng._h, self._h, C.c_void_p(int(dev_dose)), C.c_void_p(int(dv)), C.c_void_p(int(dev_g))))
+            if own:
+                out = np.empty(1 + self.n_terms, dtype=np.float64)
+                self.eng.to_host(out, dv)
+                return out
+        finally:
+            if own:
+                self.eng.device_free(dv)
+        return None
+
+    def destroy(self):
+        if self._h:
+            lib().rtd_objective_destroy(self.eng._h, self._h)
+            self._h = C.c_void_p()
+
+
+class Optimizer:
+    """rtd_optimizer_*: the resident spectral projected gradient iteration on an Objective of the dose of `fields` (each with a
+    dose_influence() matrix). Destroy it before its fields, its objective and its engine."""
+
+    def __init__(self, eng, fields, objective, options=None):
+        self.eng = eng
+        self.fields = list(fields)
+        self.objective = objective
+        self._h = C.c_void_p()
+        arr = (C.c_void_p * max(1, len(self.fields)))(*[f._h for f in self.fields])
+        eng._check(lib().rtd_optimizer_create(eng._h, arr, len(self.fields), objective._h, C.byref(options) if options is not None else None,
+                                              C.byref(self._h)))
+
+    def set_weights(self, field_index, dev_w):
+        self.eng._check(lib().rtd_optimizer_set_weights(self.eng._h, self._h, int(field_index), C.c_void_p(int(dev_w))))
+
+    def run(self, n_iterations):
+        """Launches n_iterations iterations on the engine's stream; asynchronous."""
+        self.eng._check(lib().rtd_optimizer_run(self.eng._h, self._h, int(n_iterations)))
+
+    def result(self, capacity=None):
+        """Waits; (report dict, history float64 array). A start whose objective is not finite raises RtdError (INVALID_ARG)."""
+        r = abi.RtdOptimizerReport()
+        self.eng._check(lib().rtd_optimizer_result(self.eng._h, self._h, C.byref(r), None, 0))
+        n = r.history_len if capacity is None else min(int(capacity), r.history_len)
+        hist = np.empty(n, dtype=np.float64)
+        if n:
+            self.eng._check(lib().rtd_optimizer_result(self.eng._h, self._h, C.byref(r), hist.ctypes.data_as(C.POINTER(C.c_double)), n))
+        return r.as_dict(), hist
+
+    def weights(self, field_index, dev_w_out=None, best=False):
+        """Field field_index's part of the current (or best) iterate: copied to dev_w_out (device pointer, asynchronous), or, without
+        one, returned as a float32 array of the field's [L][ny][nx] shape."""
+        if dev_w_out is not None:
+            self.eng._check(lib().rtd_optimizer_weights(self.eng._h, self._h, int(field_index), C.c_void_p(int(dev_w_out)), int(bool(best))))
+            return None
+        shape = np.asarray(self.fields[field_index]._beam.spotWeights).shape
+        out = np.empty(shape, dtype=np.float32)
+        d = self.eng.device_alloc(out.nbytes)
+        try:
+            self.eng._check(lib().rtd_optimizer_weights(self.eng._h, self._h, int(field_index), C.c_void_p(d), int(bool(best))))
+            self.eng.to_host(out, d)
+        finally:
+            self.eng.device_free(d)
+        return out
+
+    def dose(self):
+        """Device pointer of the optimiser's dose volume: the dose of the iterate that entered the last iteration."""
+        p = C.c_void_p()
+        self.eng._check(lib().rtd_optimizer_dose(self.eng._h, self._h, C.byref(p)))
+        return int(p.value or 0)
+
+    def destroy(self):
+        if self._h:
+            lib().rtd_optimizer_destroy(self.eng._h, self._h)
+            self._h = C.c_void_p()
+
+
 class Engine:
     """One rtd_handle: one GPU, one stream, resident CT and LUTs."""
 
@@ -389,6 +509,12 @@ class Engine:
 
     def create_field(self, beam, dose_dims, remote=False):
         return Field(self, beam, dose_dims, remote=remote)
+
+    def create_objective(self, dose_dims):
+        return Objective(self, dose_dims)
+
+    def create_optimizer(self, fields, objective, options=None):
+        return Optimizer(self, fields, objective, options)
 
     def transfer_fields_init(self, fields, dev_dose, box_min=None, box_max=None):
         """rtd_fields_transfer_init: every voxel of the inclusive dose-index box is written with 0 + fields[0] + fields[1] + ...
