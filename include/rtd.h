@@ -521,6 +521,75 @@ int rtd_optimizer_dose(rtd_handle h, rtd_optimizer opt, const float** dev_dose);
 int rtd_optimizer_destroy(rtd_handle h, rtd_optimizer opt);
 
 /*
+ * ---- Dose-volume histograms and DVH-point objectives ----
+ *
+ * Additive to the block above (RTD_ABI_VERSION stays 3): what a dose volume does to a structure in dose-volume terms, evaluated and
+ * penalised on the device.
+ *
+ * Dose at volume. For a ROI of N voxels and a volume fraction v in (0, 1], D_v is the k-th LARGEST float32 dose of the ROI with
+ * k = min(N, max(1, ceil(v * N))), the product in float64, computed once on the host. The order is that of the monotone key of a
+ * float (its bits, the sign bit flipped for non-negative values, all bits flipped for negative ones), compared as an unsigned number:
+ * D_v is a value that occurs in the ROI, ties cannot make it ambiguous, -0 sorts below +0 and NaNs sort by their bits (a NaN with the
+ * sign bit clear above +inf, one with it set below -inf). v = 1 gives the minimum of the ROI, any v <= 1 / N the maximum.
+ *
+ * rtd_objective_add_dvh_term     a term of kind RTD_OBJ_MAX_DVH or RTD_OBJ_MIN_DVH. It counts towards RTD_OBJ_MAX_TERMS and takes the
+ *                                next term number, mixed with the terms of rtd_objective_add_term in the order added. Its value is
+ *                                weight / N * sum x^2 and it adds c_t * x to g[v] at its place in the voxel's term order, with
+ *                                D = double(D_v of the dose being evaluated), d = double(dose[v]), level = dose_level and
+ *                                    RTD_OBJ_MAX_DVH  x = (d > level && d <= D) ? d - level : 0   ("at most a fraction v above level":
+ *                                                     satisfied, value 0, when D <= level),
+ *                                    RTD_OBJ_MIN_DVH  x = (d < level && d >= D) ? d - level : 0   ("at least a fraction v receives
+ *                                                     level": satisfied when D >= level);
+ *                                a NaN d gives x = d, so a dose that is not finite still gives an objective that is not finite and the
+ *                                optimiser's guard acts as before. D is held constant in the gradient (the usual treatment of
+ *                                dose-volume penalties). The sums are those of rtd_objective_eval; the four kinds above are unchanged.
+ * rtd_objective_dose_at_volume   queries: host memory, 1 <= n <= RTD_DVH_MAX_QUERIES of (roi, volume_fraction; reserved = 0);
+ *                                dev_out[q] = D_v of query q (float32, device). The ranks travel as kernel arguments: once the tables
+ *                                exist the call is four launches on the handle's stream (no allocation, copy or synchronisation) and
+ *                                can be captured into a graph.
+ * rtd_objective_dvh              the cumulative histogram of every ROI: dev_counts[roi * n_bins + b] (uint32, device) = the number of
+ *                                voxels of the ROI with double(d) >= edge(b), edge(b) = (b * dose_max) / n_bins evaluated in float64
+ *                                (product first). Exact. 1 <= n_bins <= 4096, dose_max finite and > 0. A NaN dose is in no bin. A
+ *                                clear of dev_counts and two launches on the handle's stream.
+ * rtd_objective_eval             of an objective with DVH terms: the selection (four launches, shared by all its DVH terms) in front
+ *                                of the two launches of before: still no allocation, copy or host synchronisation after the first
+ *                                eval, still capturable, so rtd_optimizer_run keeps its guarantees. An objective without DVH terms
+ *                                launches what it launched before.
+ * The first of these calls after an add_roi builds the ROI index lists on the device and is synchronous that once.
+ *
+ * Selection: a radix select on the keys (three passes over digits of 11, 11 and 10 bits, most significant first). Each pass counts the
+ * digit of the keys that carry the digits found so far, per block in LDS, merged into one histogram per selection; the digit that
+ * holds rank k is found by a descending scan of the bins. All counting is integer addition, which is associative: unlike a float
+ * atomic, the order in which blocks arrive cannot change the result. The same inputs give the same bits across calls, handles and
+ * processes.
+ *
+ * RTD_ERR_INVALID_ARG: a null pointer, a kind other than the two (and either of the two passed to rtd_objective_add_term), an unknown
+ * ROI, a weight that is not positive and finite, a level that is not finite, a fraction outside (0, 1], a 65th term, n = 0 or
+ * n > RTD_DVH_MAX_QUERIES, n_bins or dose_max out of range. After a refusal the objective is what it was.
+ */
+enum { RTD_OBJ_MAX_DVH = 4, RTD_OBJ_MIN_DVH = 5 };   /* accepted by rtd_objective_add_dvh_term only */
+#define RTD_DVH_MAX_QUERIES 64
+
+typedef struct rtd_objective_dvh_term {
+    int32_t kind;             /* RTD_OBJ_MAX_DVH or RTD_OBJ_MIN_DVH */
+    int32_t roi;
+    double weight;            /* > 0 */
+    double dose_level;
+    double volume_fraction;   /* in (0, 1] */
+} rtd_objective_dvh_term;
+
+typedef struct rtd_dvh_query {
+    int32_t roi;
+    int32_t reserved;
+    double volume_fraction;   /* in (0, 1] */
+} rtd_dvh_query;
+
+int rtd_objective_add_dvh_term(rtd_handle h, rtd_objective obj, const rtd_objective_dvh_term* t);
+int rtd_objective_dose_at_volume(rtd_handle h, rtd_objective obj, const float* dev_dose, const rtd_dvh_query* queries, uint32_t n,
+                                 float* dev_out);
+int rtd_objective_dvh(rtd_handle h, rtd_objective obj, const float* dev_dose, uint32_t n_bins, double dose_max, uint32_t* dev_counts);
+
+/*
  * ---- Multi-GPU plans behind the boundary (SURVEY.md 8(b) "Threading": one handle and one host thread per device) ----
  *
  * rtd_plan is the reference-shaped call on several GPUs of one process: the 4-beam cudaWrapperProtons of the C++ shim uses

@@ -21,6 +21,8 @@ RTD_NUC_OFF, RTD_NUC_SOUKUP, RTD_NUC_FLUKA, RTD_NUC_GAUSS_FIT = 0, 1, 2, 3
 RTD_OBJ_SQ_DEVIATION, RTD_OBJ_SQ_OVERDOSE, RTD_OBJ_SQ_UNDERDOSE, RTD_OBJ_MEAN = 0, 1, 2, 3
 RTD_OBJ_MAX_TERMS = 64
 RTD_OPT_MAX_FIELDS = 16
+RTD_OBJ_MAX_DVH, RTD_OBJ_MIN_DVH = 4, 5     # rtd_objective_add_dvh_term only
+RTD_DVH_MAX_QUERIES = 64
 
 c_float_p = C.POINTER(C.c_float)
 
@@ -114,6 +116,14 @@ class RtdPlanTiming(C.Structure):
 
 class RtdObjectiveTerm(C.Structure):
     _fields_ = [("kind", C.c_int32), ("roi", C.c_int32), ("weight", C.c_double), ("dose_level", C.c_double)]
+
+
+class RtdObjectiveDvhTerm(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("roi", C.c_int32), ("weight", C.c_double), ("dose_level", C.c_double), ("volume_fraction", C.c_double)]
+
+
+class RtdDvhQuery(C.Structure):
+    _fields_ = [("roi", C.c_int32), ("reserved", C.c_int32), ("volume_fraction", C.c_double)]
 
 
 class RtdOptimizerOptions(C.Structure):

@@ -33,6 +33,7 @@
 #include "rtd_dij.hpp"
 #include "rtd_dij_apply.hpp"
 #include "rtd_optimize.hpp"
+#include "rtd_dvh.hpp"
 
 using namespace rtd;
 
@@ -1830,7 +1831,8 @@ struct rtd_objective_impl {
     uint32_t dims[3] = {0, 0, 0};
     size_t nVox = 0;
     std::vector<std::vector<int32_t>> rois;
-    std::vector<rtd_objective_term> terms;
+    std::vector<rtd_objective_term> terms;   // kinds 4 and 5 (DVH terms) among them, in the order added
+    std::vector<double> vfrac;    // per term: the volume fraction of a DVH term, 0 for the others
     bool built = false;           // the device tables belong to rois / terms as they are
     int nU = 0, nBlocks = 0;      // union voxels; blocks of k_obj_eval
     int* dUv = nullptr; int* dTPtr = nullptr; unsigned char* dTIdx = nullptr; ObjTerm* dTerms = nullptr; double* dPartial = nullptr;
@@ -1838,6 +1840,18 @@ struct rtd_objective_impl {
         for (void** p : {(void**)&dUv, (void**)&dTPtr, (void**)&dTIdx, (void**)&dTerms, (void**)&dPartial}) if (*p) { (void)hipFree(*p); *p = nullptr; }
         built = false;
     }
+    // DVH (section 13): the ROI index lists concatenated on the device, the selection histograms and the thresholds eval reads. Built
+    // when a DVH term, a dose-at-volume query or a histogram first needs them; they depend on the ROIs alone.
+    bool dvhBuilt = false;
+    std::vector<int> roiOff;      // ROI r: dRoiIdx[roiOff[r] .. roiOff[r + 1])
+    int* dRoiIdx = nullptr; int* dRoiOff = nullptr; unsigned* dSelHist = nullptr; float* dThr = nullptr;
+    DvhSel evalSel{};             // the selections of eval: one per DVH term, in term order, slot = the term
+    int nEvalSel = 0;
+    void freeDvh() {
+        for (void** p : {(void**)&dRoiIdx, (void**)&dRoiOff, (void**)&dSelHist, (void**)&dThr}) if (*p) { (void)hipFree(*p); *p = nullptr; }
+        dvhBuilt = false;
+    }
+    bool hasDvhTerms() const { for (double v : vfrac) if (v > 0.0) return true; return false; }
 };
 
 struct rtd_optimizer_impl {
@@ -1861,6 +1875,39 @@ struct rtd_optimizer_impl {
             if (*p) { (void)hipFree(*p); *p = nullptr; }
     }
 };
+
+// k of "the k-th largest of n" for a volume fraction v in (0, 1]: min(n, max(1, ceil(v n))), the product in float64.
+int dvhRank(double v, int n) {
+    const double c = std::ceil(v * (double)n);
+    return c >= (double)n ? n : c <= 1.0 ? 1 : (int)c;
+}
+
+// The ROI index lists on the device, the cleared selection histograms and the threshold array. Synchronous.
+int buildDvh(rtd_handle_impl* h, rtd_objective_impl* o) {
+    if (o->dvhBuilt) return RTD_OK;
+    RTD_HIP(h, hipSetDevice(h->device));
+    RTD_HIP(h, hipStreamSynchronize(h->stream));
+    o->freeDvh();
+    o->roiOff.assign(1, 0);
+    std::vector<int> idx;
+    for (const auto& r : o->rois) {
+        if (idx.size() + r.size() > (size_t)0x7fffffff) return fail(h, RTD_ERR_INVALID_ARG, "rtd_objective: the ROIs together hold more than 2^31 - 1 voxels");
+        idx.insert(idx.end(), r.begin(), r.end());
+        o->roiOff.push_back((int)idx.size());
+    }
+    const size_t histBytes = (size_t)kDvhMaxSel * 3 * kDvhBins * sizeof(unsigned);
+    hipError_t e = hipMalloc((void**)&o->dRoiIdx, std::max<size_t>(idx.size(), 1) * sizeof(int));
+    if (e == hipSuccess) e = hipMalloc((void**)&o->dRoiOff, o->roiOff.size() * sizeof(int));
+    if (e == hipSuccess) e = hipMalloc((void**)&o->dSelHist, histBytes);
+    if (e == hipSuccess) e = hipMalloc((void**)&o->dThr, kObjMaxTerms * sizeof(float));
+    if (e == hipSuccess && !idx.empty()) e = hipMemcpy(o->dRoiIdx, idx.data(), idx.size() * sizeof(int), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(o->dRoiOff, o->roiOff.data(), o->roiOff.size() * sizeof(int), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemset(o->dSelHist, 0, histBytes);
+    if (e == hipSuccess) e = hipMemset(o->dThr, 0, kObjMaxTerms * sizeof(float));
+    if (e != hipSuccess) { o->freeDvh(); RTD_HIP(h, e); }
+    o->dvhBuilt = true;
+    return RTD_OK;
+}
 
 // The union of the ROIs ascending and, per union voxel, its terms in term order (CSR); set-up work, on the host. Synchronous.
 int buildObjective(rtd_handle_impl* h, rtd_objective_impl* o) {
@@ -1900,7 +1947,32 @@ int buildObjective(rtd_handle_impl* h, rtd_objective_impl* o) {
     if (e == hipSuccess && !tIdx.empty()) e = hipMemcpy(o->dTIdx, tIdx.data(), tIdx.size(), hipMemcpyHostToDevice);
     if (e == hipSuccess && !terms.empty()) e = hipMemcpy(o->dTerms, terms.data(), terms.size() * sizeof(ObjTerm), hipMemcpyHostToDevice);
     if (e != hipSuccess) { o->freeTables(); RTD_HIP(h, e); }
+    o->nEvalSel = 0;
+    for (size_t t = 0; t < o->terms.size(); ++t)
+        if (o->vfrac[t] > 0.0) {
+            const int i = o->nEvalSel++, n = (int)o->rois[(size_t)o->terms[t].roi].size();
+            o->evalSel.n[i] = n; o->evalSel.k[i] = dvhRank(o->vfrac[t], n); o->evalSel.slot[i] = (int)t;
+            o->evalSel.off[i] = o->terms[t].roi;                      // (the ROI for now: its offset once the lists exist, below)
+        }
+    if (o->nEvalSel) {
+        const int st = buildDvh(h, o);
+        if (st != RTD_OK) { o->freeTables(); return st; }
+        for (int i = 0; i < o->nEvalSel; ++i) o->evalSel.off[i] = o->roiOff[(size_t)o->evalSel.off[i]];
+    }
     o->built = true;
+    return RTD_OK;
+}
+
+// The selections of one call: three counting passes and the launch that turns the digits into floats. Launches only.
+int dvhSelect(rtd_handle_impl* h, rtd_objective_impl* o, const float* dDose, const DvhSel& sel, int nSel, float* dOut) {
+    int nMax = 0;
+    for (int i = 0; i < nSel; ++i) nMax = std::max(nMax, sel.n[i]);
+    const dim3 grid((unsigned)((nMax + kDvhChunk - 1) / kDvhChunk), (unsigned)nSel);
+    k_dvh_pass<0><<<grid, 256, 0, h->stream>>>((const int*)o->dRoiIdx, dDose, sel, o->dSelHist);
+    k_dvh_pass<1><<<grid, 256, 0, h->stream>>>((const int*)o->dRoiIdx, dDose, sel, o->dSelHist);
+    k_dvh_pass<2><<<grid, 256, 0, h->stream>>>((const int*)o->dRoiIdx, dDose, sel, o->dSelHist);
+    k_dvh_finish<<<(unsigned)nSel, 256, 0, h->stream>>>(sel, o->dSelHist, dOut);
+    RTD_HIP(h, hipGetLastError());
     return RTD_OK;
 }
 
@@ -1908,9 +1980,15 @@ int buildObjective(rtd_handle_impl* h, rtd_objective_impl* o) {
 int evalObjective(rtd_handle_impl* h, rtd_objective_impl* o, const float* dDose, double* dValues, float* dGrad) {
     if (!o->built) { const int st = buildObjective(h, o); if (st != RTD_OK) return st; }
     const int nTerms = (int)o->terms.size();
-    if (o->nBlocks)
-        k_obj_eval<<<(unsigned)o->nBlocks, 256, 0, h->stream>>>((const int*)o->dUv, (const int*)o->dTPtr, (const unsigned char*)o->dTIdx, (const ObjTerm*)o->dTerms,
-                                                                nTerms, o->nU, dDose, dGrad, o->dPartial, o->nBlocks);
+    if (o->nEvalSel) {                                                // DVH terms: their doses at volume of this dose first
+        const int st = dvhSelect(h, o, dDose, o->evalSel, o->nEvalSel, o->dThr);
+        if (st != RTD_OK) return st;
+        k_obj_eval<true><<<(unsigned)o->nBlocks, 256, 0, h->stream>>>((const int*)o->dUv, (const int*)o->dTPtr, (const unsigned char*)o->dTIdx,
+                                                                      (const ObjTerm*)o->dTerms, nTerms, o->nU, dDose, dGrad, o->dPartial, o->nBlocks,
+                                                                      (const float*)o->dThr);
+    } else if (o->nBlocks)
+        k_obj_eval<false><<<(unsigned)o->nBlocks, 256, 0, h->stream>>>((const int*)o->dUv, (const int*)o->dTPtr, (const unsigned char*)o->dTIdx,
+                                                                       (const ObjTerm*)o->dTerms, nTerms, o->nU, dDose, dGrad, o->dPartial, o->nBlocks, nullptr);
     k_obj_reduce<<<1, 256, 0, h->stream>>>((const double*)o->dPartial, o->nBlocks, (const ObjTerm*)o->dTerms, nTerms, dValues);
     RTD_HIP(h, hipGetLastError());
     return RTD_OK;
@@ -1966,6 +2044,7 @@ int rtd_objective_add_roi(rtd_handle hh, rtd_objective oo, const int32_t* voxels
             return fail(h, RTD_ERR_INVALID_ARG, "rtd_objective_add_roi: voxel indices must be strictly ascending and inside the dose grid");
     o->rois.emplace_back(voxels, voxels + n);
     o->built = false;
+    o->dvhBuilt = false;
     *roi_id = (int32_t)o->rois.size() - 1;
     return RTD_OK;
 }
@@ -1981,7 +2060,69 @@ int rtd_objective_add_term(rtd_handle hh, rtd_objective oo, const rtd_objective_
     if (!std::isfinite(t->dose_level)) return fail(h, RTD_ERR_INVALID_ARG, "rtd_objective_add_term: the dose level must be finite");
     if (o->terms.size() >= (size_t)kObjMaxTerms) return fail(h, RTD_ERR_INVALID_ARG, "rtd_objective_add_term: more than RTD_OBJ_MAX_TERMS terms");
     o->terms.push_back(*t);
+    o->vfrac.push_back(0.0);
     o->built = false;
+    return RTD_OK;
+}
+
+int rtd_objective_add_dvh_term(rtd_handle hh, rtd_objective oo, const rtd_objective_dvh_term* t) {
+    auto* h = reinterpret_cast<rtd_handle_impl*>(hh);
+    auto* o = reinterpret_cast<rtd_objective_impl*>(oo);
+    if (!h) return RTD_ERR_INVALID_ARG;
+    if (!o || !t) return fail(h, RTD_ERR_INVALID_ARG, "rtd_objective_add_dvh_term: null pointer");
+    if (t->kind != RTD_OBJ_MAX_DVH && t->kind != RTD_OBJ_MIN_DVH) return fail(h, RTD_ERR_INVALID_ARG, "rtd_objective_add_dvh_term: the kind must be RTD_OBJ_MAX_DVH or RTD_OBJ_MIN_DVH");
+    if (t->roi < 0 || (size_t)t->roi >= o->rois.size()) return fail(h, RTD_ERR_INVALID_ARG, "rtd_objective_add_dvh_term: unknown ROI");
+    if (!(t->weight > 0.0) || !std::isfinite(t->weight)) return fail(h, RTD_ERR_INVALID_ARG, "rtd_objective_add_dvh_term: the weight must be positive and finite");
+    if (!std::isfinite(t->dose_level)) return fail(h, RTD_ERR_INVALID_ARG, "rtd_objective_add_dvh_term: the dose level must be finite");
+    if (!(t->volume_fraction > 0.0 && t->volume_fraction <= 1.0)) return fail(h, RTD_ERR_INVALID_ARG, "rtd_objective_add_dvh_term: the volume fraction must lie in (0, 1]");
+    if (o->terms.size() >= (size_t)kObjMaxTerms) return fail(h, RTD_ERR_INVALID_ARG, "rtd_objective_add_dvh_term: more than RTD_OBJ_MAX_TERMS terms");
+    o->terms.push_back(rtd_objective_term{t->kind, t->roi, t->weight, t->dose_level});
+    o->vfrac.push_back(t->volume_fraction);
+    o->built = false;
+    return RTD_OK;
+}
+
+int rtd_objective_dose_at_volume(rtd_handle hh, rtd_objective oo, const float* dev_dose, const rtd_dvh_query* queries, uint32_t n, float* dev_out) {
+    auto* h = reinterpret_cast<rtd_handle_impl*>(hh);
+    auto* o = reinterpret_cast<rtd_objective_impl*>(oo);
+    if (!h) return RTD_ERR_INVALID_ARG;
+    if (!o || !dev_dose || !queries || !dev_out) return fail(h, RTD_ERR_INVALID_ARG, "rtd_objective_dose_at_volume: null pointer");
+    if (n < 1 || n > RTD_DVH_MAX_QUERIES) return fail(h, RTD_ERR_INVALID_ARG, "rtd_objective_dose_at_volume: 1 to RTD_DVH_MAX_QUERIES queries");
+    for (uint32_t q = 0; q < n; ++q) {
+        if (queries[q].roi < 0 || (size_t)queries[q].roi >= o->rois.size()) return fail(h, RTD_ERR_INVALID_ARG, "rtd_objective_dose_at_volume: unknown ROI");
+        if (!(queries[q].volume_fraction > 0.0 && queries[q].volume_fraction <= 1.0))
+            return fail(h, RTD_ERR_INVALID_ARG, "rtd_objective_dose_at_volume: the volume fraction must lie in (0, 1]");
+    }
+    RTD_HIP(h, hipSetDevice(h->device));
+    const int st = buildDvh(h, o);
+    if (st != RTD_OK) return st;
+    DvhSel sel{};
+    for (uint32_t q = 0; q < n; ++q) {
+        const size_t r = (size_t)queries[q].roi;
+        sel.off[q] = o->roiOff[r]; sel.n[q] = o->roiOff[r + 1] - o->roiOff[r]; sel.k[q] = dvhRank(queries[q].volume_fraction, sel.n[q]); sel.slot[q] = (int)q;
+    }
+    return dvhSelect(h, o, dev_dose, sel, (int)n, dev_out);
+}
+
+int rtd_objective_dvh(rtd_handle hh, rtd_objective oo, const float* dev_dose, uint32_t n_bins, double dose_max, uint32_t* dev_counts) {
+    auto* h = reinterpret_cast<rtd_handle_impl*>(hh);
+    auto* o = reinterpret_cast<rtd_objective_impl*>(oo);
+    if (!h) return RTD_ERR_INVALID_ARG;
+    if (!o || !dev_dose || !dev_counts) return fail(h, RTD_ERR_INVALID_ARG, "rtd_objective_dvh: null pointer");
+    if (n_bins < 1 || n_bins > (uint32_t)kDvhMaxHistBins) return fail(h, RTD_ERR_INVALID_ARG, "rtd_objective_dvh: 1 to 4096 bins");
+    if (!(dose_max > 0.0) || !std::isfinite(dose_max)) return fail(h, RTD_ERR_INVALID_ARG, "rtd_objective_dvh: dose_max must be positive and finite");
+    if (o->rois.empty()) return fail(h, RTD_ERR_INVALID_ARG, "rtd_objective_dvh: the objective has no ROIs");
+    RTD_HIP(h, hipSetDevice(h->device));
+    const int st = buildDvh(h, o);
+    if (st != RTD_OK) return st;
+    const size_t nRoi = o->rois.size();
+    int nMax = 0;
+    for (size_t r = 0; r < nRoi; ++r) nMax = std::max(nMax, o->roiOff[r + 1] - o->roiOff[r]);
+    RTD_HIP(h, hipMemsetAsync(dev_counts, 0, nRoi * n_bins * sizeof(uint32_t), h->stream));
+    k_dvh_hist<<<dim3((unsigned)((nMax + kDvhChunk - 1) / kDvhChunk), (unsigned)nRoi), 256, 0, h->stream>>>((const int*)o->dRoiIdx, (const int*)o->dRoiOff, dev_dose, (int)n_bins,
+                                                                                                           dose_max, dev_counts);
+    k_dvh_suffix<<<(unsigned)nRoi, 256, 0, h->stream>>>(dev_counts, (int)n_bins);
+    RTD_HIP(h, hipGetLastError());
     return RTD_OK;
 }
 
@@ -2002,6 +2143,7 @@ int rtd_objective_destroy(rtd_handle hh, rtd_objective oo) {
     (void)hipSetDevice(h->device);
     (void)hipStreamSynchronize(h->stream);
     o->freeTables();
+    o->freeDvh();
     delete o;
     return RTD_OK;
 }

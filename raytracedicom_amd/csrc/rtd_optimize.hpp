@@ -43,9 +43,12 @@ __device__ inline double optWaveMax(double v) {
 }
 
 // partial[t * nBlocks + block] = the block's sum of phi_t. Threads past the union and voxels outside a term add +0.0 (exact).
+// kDvh: the objective has DVH terms (RTD_OBJ_MAX_DVH / _MIN_DVH, rtd_dvh.hpp); thr[t] is then term t's dose at volume of this dose.
+// Without them the instantiation is the kernel as it was, and thr is not read.
+template <bool kDvh>
 __global__ __launch_bounds__(256) void k_obj_eval(const int* __restrict__ uv, const int* __restrict__ tPtr, const unsigned char* __restrict__ tIdx,
                                                   const ObjTerm* __restrict__ terms, int nTerms, int nU, const float* __restrict__ dose,
-                                                  float* __restrict__ g, double* __restrict__ partial, int nBlocks) {
+                                                  float* __restrict__ g, double* __restrict__ partial, int nBlocks, const float* __restrict__ thr) {
     __shared__ double sh[4][kObjMaxTerms];
     const int i = blockIdx.x * 256 + threadIdx.x, lane = threadIdx.x % 64, wave = threadIdx.x / 64;
     int v = 0, e = 0, end = 0;
@@ -60,7 +63,15 @@ __global__ __launch_bounds__(256) void k_obj_eval(const int* __restrict__ uv, co
             if (mine) {
                 const ObjTerm tm = terms[t];
                 if (tm.kind == RTD_OBJ_MEAN) { phi = d; gs += tm.wn; }
-                else {
+                else if (kDvh && tm.kind >= RTD_OBJ_MAX_DVH) {
+                    const double D = (double)thr[t];
+                    double x = d;                                     // (a NaN stays a NaN)
+                    if (d == d) {
+                        const bool in = tm.kind == RTD_OBJ_MAX_DVH ? (d > tm.level && d <= D) : (d < tm.level && d >= D);
+                        x = in ? d - tm.level : 0.0;
+                    }
+                    phi = x * x; gs += tm.c * x;
+                } else {
                     double x = d - tm.level;
                     if (tm.kind == RTD_OBJ_SQ_OVERDOSE) x = x < 0.0 ? 0.0 : x;
                     else if (tm.kind == RTD_OBJ_SQ_UNDERDOSE) x = x > 0.0 ? 0.0 : x;

@@ -91,6 +91,9 @@ def lib():
         L.rtd_objective_add_term.argtypes = [vp, vp, C.POINTER(abi.RtdObjectiveTerm)]
         L.rtd_objective_eval.argtypes = [vp, vp, vp, vp, vp]
         L.rtd_objective_destroy.argtypes = [vp, vp]
+        L.rtd_objective_add_dvh_term.argtypes = [vp, vp, C.POINTER(abi.RtdObjectiveDvhTerm)]
+        L.rtd_objective_dose_at_volume.argtypes = [vp, vp, vp, C.POINTER(abi.RtdDvhQuery), C.c_uint32, vp]
+        L.rtd_objective_dvh.argtypes = [vp, vp, vp, C.c_uint32, C.c_double, vp]
         L.rtd_default_optimizer_options.argtypes = [C.POINTER(abi.RtdOptimizerOptions)]
         L.rtd_default_optimizer_options.restype = None
         L.rtd_optimizer_create.argtypes = [vp, vpp, C.c_uint32, vp, C.POINTER(abi.RtdOptimizerOptions), vpp]
@@ -317,13 +320,15 @@ class Field:
 
 class Objective:
     """rtd_objective_*: ROIs and penalty terms on one dose grid; eval() gives the objective, its terms and the voxel gradient on the
-    device. Kinds: abi.RTD_OBJ_SQ_DEVIATION / _SQ_OVERDOSE / _SQ_UNDERDOSE / _MEAN."""
+    device. Kinds: abi.RTD_OBJ_SQ_DEVIATION / _SQ_OVERDOSE / _SQ_UNDERDOSE / _MEAN; through add_dvh_term abi.RTD_OBJ_MAX_DVH / _MIN_DVH.
+    dose_at_volume() and dvh() report on a dose volume in dose-volume terms."""
 
     def __init__(self, eng, dose_dims):
         self.eng = eng
         self._h = C.c_void_p()
         self.dims = tuple(int(d) for d in dose_dims)
         self.n_terms = 0
+        self.n_rois = 0
         eng._check(lib().rtd_objective_create(eng._h, abi.uint3(self.dims), C.byref(self._h)))
 
     def add_roi(self, mask_or_indices):
@@ -333,12 +338,56 @@ class Objective:
         idx = np.ascontiguousarray(idx, dtype=np.int32)
         rid = C.c_int32(-1)
         self.eng._check(lib().rtd_objective_add_roi(self.eng._h, self._h, idx.ctypes.data_as(C.POINTER(C.c_int32)), idx.size, C.byref(rid)))
+        self.n_rois += 1
         return int(rid.value)
 
     def add_term(self, kind, roi, weight, level=0.0):
         t = abi.RtdObjectiveTerm(int(kind), int(roi), float(weight), float(level))
         self.eng._check(lib().rtd_objective_add_term(self.eng._h, self._h, C.byref(t)))
         self.n_terms += 1
+
+    def add_dvh_term(self, kind, roi, weight, level, volume_fraction):
+        """A dose-volume term: RTD_OBJ_MAX_DVH (at most volume_fraction of the ROI above level) or RTD_OBJ_MIN_DVH (at least
+        volume_fraction of the ROI receives level). It takes the next term number, like add_term."""
+        t = abi.RtdObjectiveDvhTerm(int(kind), int(roi), float(weight), float(level), float(volume_fraction))
+        self.eng._check(lib().rtd_objective_add_dvh_term(self.eng._h, self._h, C.byref(t)))
+        self.n_terms += 1
+
+    def dose_at_volume(self, dev_dose, queries, dev_out=None):
+        """rtd_objective_dose_at_volume: queries = [(roi, volume_fraction), ...] (at most abi.RTD_DVH_MAX_QUERIES). With dev_out (device
+        pointer, float32[n]) asynchronous, returns None; without, returns the doses as a float32 array."""
+        qs = list(queries)
+        arr = (abi.RtdDvhQuery * max(1, len(qs)))(*[abi.RtdDvhQuery(int(r), 0, float(v)) for r, v in qs])
+        own = dev_out is None
+        do = self.eng.device_alloc(4 * abi.RTD_DVH_MAX_QUERIES) if own else dev_out
+        try:
+            self.eng._check(lib().rtd_objective_dose_at_volume(self.eng._h, self._h, C.c_void_p(int(dev_dose)), arr, len(qs), C.c_void_p(int(do))))
+            if own:
+                out = np.empty(len(qs), dtype=np.float32)
+                self.eng.to_host(out, do)
+                return out
+        finally:
+            if own:
+                self.eng.device_free(do)
+        return None
+
+    def dvh(self, dev_dose, n_bins, dose_max, dev_counts=None):
+        """rtd_objective_dvh: the cumulative dose-volume histogram of every ROI, counts[roi][b] = voxels of the ROI with
+        dose >= b * dose_max / n_bins. With dev_counts (device pointer, uint32[rois * n_bins]) asynchronous, returns None; without,
+        returns a uint32 array [rois, n_bins]."""
+        own = dev_counts is None
+        nbytes = 4 * max(1, self.n_rois) * max(1, int(n_bins))
+        dc = self.eng.device_alloc(nbytes) if own else dev_counts
+        try:
+            self.eng._check(lib().rtd_objective_dvh(self.eng._h, self._h, C.c_void_p(int(dev_dose)), int(n_bins), float(dose_max), C.c_void_p(int(dc))))
+            if own:
+                out = np.empty((self.n_rois, int(n_bins)), dtype=np.uint32)
+                self.eng.to_host(out, dc)
+                return out
+        finally:
+            if own:
+                self.eng.device_free(dc)
+        return None
 
     def eval(self, dev_dose, dev_g, dev_values=None):
         """rtd_objective_eval: dev_dose, dev_g device pointers of float32 volumes (dev_g zeroed once by the caller: only the voxels
