@@ -187,7 +187,11 @@ int rtd_set_ct(rtd_handle h, const float* hu_plus_1000, const uint32_t dims[3]);
  * been finished — and every field uploads, in front of its tracer, only the index box of the volume its rays can sample (a beam
  * of the 512^3 bench plan reads a tenth of the CT; the upload of all 537 MB was 9.4 of the 13 ms of a one-field call). */
 int rtd_set_ct_deferred(rtd_handle h, const float* hu_plus_1000, const uint32_t dims[3]);
-/* Same, for a CT already resident on this handle's device (not copied, not owned). */
+/* Same, for a CT already resident on this handle's device (not copied, not owned).
+ * A BOUND VOLUME IS ANNOUNCED AS CHANGED BY CALLING rtd_set_ct* AGAIN (rtd_set_ct_device with the same pointer, rtd_set_ct_deferred
+ * with the same host volume): the handle cannot see a volume rewritten in place, and a field keeps between computes what it
+ * derived from CT, LUTs and options (see rtd_field_compute below). Every rtd_set_ct*, rtd_set_luts, rtd_load_luts_dir and
+ * rtd_set_options call makes every field of the handle derive it again at its next compute. */
 int rtd_set_ct_device(rtd_handle h, const float* dev_hu_plus_1000, const uint32_t dims[3]);
 
 /*
@@ -211,6 +215,16 @@ int rtd_compute(rtd_handle h, const rtd_beam* beams, int n_beams, float* dose_in
  *                    rtd_field_compute could have changed (its device-side dose box). A plan loop that starts
  *                    every iteration from an all-zero volume (the reference uploads a zero dose image per call,
  *                    main.cu:192-206, kernel_wrapper.cu:542) restores it with this instead of clearing all of it.
+ *
+ * What a field keeps between computes: its ray trace (density, WEPL, radiation length, entry and exit steps) and the plan made
+ * from it (cut-off steps, entry plane and entry sigmas), which depend on CT, LUTs, options and the beam's geometry but not on the
+ * spot weights. Once a compute of the field has been FINISHED (rtd_field_finish, rtd_field_wait_plan, rtd_field_dose_influence)
+ * without a device-side error, a later rtd_field_compute / _compute_bev with no rtd_set_ct*, LUT or options call in between
+ * launches neither the tracer nor the plan (with a deferred CT it uploads nothing either); the result is bit for bit that of a full
+ * compute. rtd_field_set_spot_weights keeps the trace, so the re-weighting loop of an optimiser traces once; a CT rewritten in
+ * place must be announced (rtd_set_ct_device above). Not kept: across rtd_field_release; with nuclear_corr; for spot maps of more
+ * than 64 rows; by launches into a capturing stream (a graph holds the full sequence). rtd_timing of such a compute: raytracing_ms
+ * = 0, total_ms from its first launch. rtd_field_fetch "trace_reused" tells which kind the last launched compute was.
  */
 int rtd_field_create(rtd_handle h, const rtd_beam* beam, const uint32_t dose_dims[3], rtd_field* out);
 int rtd_field_compute(rtd_handle h, rtd_field f, float* dev_dose);
@@ -289,7 +303,8 @@ int rtd_set_stream(rtd_handle h, void* hip_stream);
  * "wepl_min" [S] float; "ray_weights" [L][H][W] float; "idd" "rsigma" [L][S][H][W] float;
  * "first_passive" [L][H][W] int32; "tile_radius" [L][S][tilesY][tilesX] uint8 (0xFF = not classified);
  * "eff_radius" [L][34] int32 (batch radius per tile radius); "bev" [S][H+64][W+64] float;
- * "layer_plan" [L][8] float (energyIdx, scaleFact, peakDepth, entrySigmaX, entrySigmaY, afterLast, 0, 0).
+ * "layer_plan" [L][8] float (energyIdx, scaleFact, peakDepth, entrySigmaX, entrySigmaY, afterLast, 0, 0);
+ * "trace_reused" int32[1]: 1 if the last launched compute reused the field's trace and plan (see rtd_field_compute).
  * Returns the number of bytes the buffer holds via *bytes_needed when host_out is NULL.
  */
 int rtd_field_fetch(rtd_handle h, rtd_field f, const char* name, void* host_out, size_t bytes,
@@ -348,7 +363,8 @@ int rtd_spot_gradient(rtd_handle h, const rtd_beam* beams, int n_beams, const fl
  *                                threshold outside [0, 1); RTD_ERR_RADIUS_OVERFLOW as rtd_field_finish. Not on the rtd_plan_* path.
  * rtd_field_dose_influence_copy  copies the last result; the three pointers may be host or device memory.
  * rtd_field_set_spot_weights     new spot weights [L][ny][nx] (device memory), copied on the handle's stream. What the field learned
- *                                from its last compute is forgotten; the next rtd_field_compute gives, bit for bit, what a fresh
+ *                                from its last compute about its weights (uniform-sigma and radius hints) is forgotten, its trace
+ *                                and plan, which do not depend on them, are kept; the next rtd_field_compute gives, bit for bit, what a fresh
  *                                rtd_field_create with these weights gives. Not for remote fields.
  * rtd_field_fetch name of the last Dij call: "dij_batch" [L][ny][nx] int32, the batch each spot was computed in (-1: empty column).
  */

@@ -79,10 +79,11 @@ struct rtd_handle_impl {
 };
 
 // The engine's RTD_* switches (diagnostics, and the second implementations the tests compare with): read once, when a field is
-// created. RTD_NO_UNIFORM_PATH, RTD_UNIFORM_V2, RTD_NO_SWEEP, RTD_SEPARATE_PLAN, RTD_SEPARATE_KS_PLAN, RTD_*_DEBUG (per-block clock
-// stamps), and the overrides RTD_TRACE_MODE, RTD_TRACE_DIAG_B, RTD_KS_GROUPS, RTD_SW_GROUPS.
+// created. RTD_NO_UNIFORM_PATH, RTD_UNIFORM_V2, RTD_NO_SWEEP, RTD_SEPARATE_PLAN, RTD_SEPARATE_KS_PLAN, RTD_NO_TRACE_REUSE (every compute
+// traces and plans the field again), RTD_*_DEBUG (per-block clock stamps), and the overrides RTD_TRACE_MODE, RTD_TRACE_DIAG_B,
+// RTD_KS_GROUPS, RTD_SW_GROUPS.
 struct Switches {
-    bool noUniformPath = false, uniformV2 = false, noSweep = false, separatePlan = false, separateKsPlan = false;
+    bool noUniformPath = false, uniformV2 = false, noSweep = false, separatePlan = false, separateKsPlan = false, noTraceReuse = false;
     bool scanDebug = false, fillDebug = false, uniformDebug = false, sweepDebug = false;
     std::optional<int> traceMode, traceDiagB, ksGroups, swGroups;
 };
@@ -91,6 +92,7 @@ Switches readSwitches() {
     auto on = [](const char* name) { return std::getenv(name) != nullptr; };
     auto num = [](const char* name) { const char* v = std::getenv(name); return v ? std::optional<int>(std::atoi(v)) : std::nullopt; };
     return Switches{on("RTD_NO_UNIFORM_PATH"), on("RTD_UNIFORM_V2"), on("RTD_NO_SWEEP"), on("RTD_SEPARATE_PLAN"), on("RTD_SEPARATE_KS_PLAN"),
+                    on("RTD_NO_TRACE_REUSE"),
                     on("RTD_SCAN_DEBUG"), on("RTD_FILL_DEBUG"), on("RTD_UNIFORM_DEBUG"), on("RTD_SWEEP_DEBUG"),
                     num("RTD_TRACE_MODE"), num("RTD_TRACE_DIAG_B"), num("RTD_KS_GROUPS"), num("RTD_SW_GROUPS")};
 }
@@ -133,6 +135,13 @@ struct rtd_field_impl {
     unsigned launchEpoch = 0;     // handle->inputEpoch when the compute in flight was launched (what its findings are valid for)
     bool launchedKnownUniform = false;   // the compute in flight skipped the general superposition kernel on the strength of the hint
     bool triedUniform = false;    // the compute in flight ran the detection
+    // The trace and the plan (density, WEPL, radiation length, entry / exit steps, WEPL minima, the plan's part of the state record and
+    // of the layer records) depend on CT, LUTs, options and geometry only, not on the spot weights: a compute under the inputs of a
+    // FINISHED compute that produced them launches neither the tracer nor the scan nor the plan (rtd_field_compute_bev).
+    bool traceLaunched = false;   // a compute that traces has been launched (not into a capturing stream) under traceEpoch
+    unsigned traceEpoch = 0;      // handle->inputEpoch of that launch
+    bool traceUsable = false;     // ... and a finished compute under that epoch has been seen without a device error (takeFindings)
+    bool launchedReuse = false;   // the compute in flight reused the trace: ev[1] is not recorded (rtd_field_fetch "trace_reused")
     // NUCLEAR_CORR (default off): the halo on the spot-resolution grid
     int* dNucSpotIdx = nullptr; float *dNucRayWeights = nullptr, *dNucIdd = nullptr, *dNucRs = nullptr, *dNucBev = nullptr;
     int* dNucEffT = nullptr;
@@ -311,6 +320,8 @@ int takeFindings(rtd_handle_impl* h, rtd_field_impl* f, const FieldState& st) {
     if (f->triedUniform) { f->uniformHint = st.uniformField ? 1 : 0; f->hintEpoch = f->launchEpoch; }
     else if (f->hintEpoch != f->launchEpoch) { f->uniformHint = -1; f->hintEpoch = f->launchEpoch; }
     f->radiusHint = (st.errorFlags || st.empty) ? -1 : st.maxRadius;   // (valid under hintEpoch, like the uniform hint)
+    // the field's trace and plan are complete and stand for the inputs of the launch (a later compute may run on another stream)
+    f->traceUsable = f->traceLaunched && f->launchEpoch == f->traceEpoch && !st.errorFlags && !f->remote;
     // A compute that skipped the general kernel (hint: uniform) on a field the device then found heterogeneous has written no BEV
     // dose: only possible when the caller changed a bound device volume in place (rtd_set_ct_device) without telling the handle.
     if (f->launchedKnownUniform && !st.uniformField && !st.errorFlags && !st.empty)
@@ -647,6 +658,7 @@ int rtd_field_release(rtd_handle hh, rtd_field ff) {
     (void)hipSetDevice(h->device);
     (void)hipStreamSynchronize(h->stream);      // its kernels have drained: the next owner uploads with plain copies
     f->computed = false; f->transferred = false;
+    f->traceLaunched = false; f->traceUsable = false;   // (the next owner of the workspace is a new field object anyway: nothing carries over)
     freeBuffers(f, kGradient | kDiag | kDij | kDijOut);   // (not part of the shape's workspace)
     f->gradDone = false;
     f->dijDone = false; f->dijPrepared = false; f->dijCap = 0; f->dijNnz = 0; f->dijBatchOf.clear();
@@ -939,7 +951,24 @@ int rtd_field_compute_bev(rtd_handle hh, rtd_field ff) {
     if (f->remote) return fail(h, RTD_ERR_INVALID_ARG, "rtd_field_compute_bev: a remote field has no workspace (attach a slab instead)");
     if (!h->dCt || !h->haveLuts) return fail(h, RTD_ERR_NOT_READY, "rtd_field_compute: set LUTs and CT first");
     RTD_HIP(h, hipSetDevice(h->device));   // one host thread may drive handles on several devices
-    { const int st = ensureCtBox(h, f); if (st != RTD_OK) return st; }
+    const FieldConst& fc = f->fc;
+    hipStream_t s = h->stream;
+    // The trace and the plan of a finished compute stand while CT, LUTs and options do (inputEpoch; a bound device CT rewritten in place
+    // is announced by rtd_set_ct* like any other change): the launches in front of the convolution are then left out. Not with the
+    // halo, not for spot maps beyond k_plan_conv's rows, not with RTD_SEPARATE_PLAN (the full sequence, deliberately: DESIGN.md section
+    // 4), and never into a capturing stream: a graph must not depend on what the field knew when it was captured.
+    bool reuse = f->traceUsable && f->traceEpoch == h->inputEpoch && !f->sw.noTraceReuse && !f->sw.separatePlan && !fc.nuclearCorr &&
+                 fc.spotNy <= kPlanConvMaxRows;
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    RTD_HIP(h, hipStreamIsCapturing(s, &cs));
+    const bool capturing = cs != hipStreamCaptureStatusNone;
+    if (capturing) reuse = false;
+    if (!reuse) {
+        const int st = ensureCtBox(h, f); if (st != RTD_OK) return st;
+        // (a captured launch runs when its graph does, not now: it leaves no record)
+        f->traceUsable = false; f->traceLaunched = !capturing; f->traceEpoch = h->inputEpoch;
+    }
+    f->launchedReuse = reuse;
     // the uniform-sigma detection and kernel are skipped for a field that was found heterogeneous under the same CT / LUTs / options
     const bool tryUniform = f->uniformEligible && !(f->uniformHint == 0 && f->hintEpoch == h->inputEpoch);
     f->triedUniform = tryUniform;
@@ -948,8 +977,6 @@ int rtd_field_compute_bev(rtd_handle hh, rtd_field ff) {
     // the same values): the general superposition kernel, all of whose ~10^5 blocks would only look at the flag and leave, is not launched
     const bool knownUniform = tryUniform && f->uniformHint == 1 && f->hintEpoch == h->inputEpoch;
     f->launchedKnownUniform = knownUniform;
-    const FieldConst& fc = f->fc;
-    hipStream_t s = h->stream;
     const bool timing = h->opt.fine_grained_timing != 0;
     const dim3 blk(kSuperpTileX, kSuperpTileY);
     const dim3 rayGrid(fc.W / kSuperpTileX, fc.H / kSuperpTileY);
@@ -961,6 +988,14 @@ int rtd_field_compute_bev(rtd_handle hh, rtd_field ff) {
     // dIdd doubles as the HU scratch of the tracer (it is written by k_fill only afterwards)
     const size_t tLds = lutLds + (size_t)3 * kTrRays * kTrPitch * sizeof(float);
     const size_t dLds = lutLds + (size_t)3 * kTdSteps * kTdPitch * sizeof(float);
+    const ResetJob resetJob{f->dLayers, fc.L, reinterpret_cast<unsigned int*>(f->dTileRad), f->tileRadWords, f->dActive, (size_t)4 * fc.L * fc.S,
+                            f->dNucIdd, f->dNucRs, fc.nuclearCorr ? (size_t)fc.nucW * fc.nucH * fc.L : (size_t)0,
+                            f->dSigMin, f->dSigMax, (size_t)fc.L * fc.S, f->dScanDbg};
+    if (reuse) {
+        // the spot -> ray convolution is the first launch; it carries the reset of what k_fill and the superposition's plan accumulate into
+        launchK(k_reset_conv, dim3(fc.W / 32, (fc.H / 8 + 3) / 4, fc.L), dim3(1024), (size_t)4 * fc.spotNy * 32 * sizeof(float), s, f->ev[0], ev(2),
+                (const float*)f->dSpotWeights, f->dRayWeights, (const LayerPlan*)f->dLayers, f->dState, resetJob, fc);
+    } else {
     if (f->traceMode == 2 && dLds <= 150 * 1024) {
         RTD_HIP(h, raiseLdsCap(h, k_trace_sample_d, dLds));
         launchK(k_trace_sample_d, dim3((unsigned)(fc.W / kTdRays), (unsigned)fc.H, (unsigned)((fc.S + kTdSteps - 1) / kTdSteps)), dim3(kTdThreads), dLds, s, f->ev[0], nullptr,
@@ -980,9 +1015,6 @@ int rtd_field_compute_bev(rtd_handle hh, rtd_field ff) {
     }
     constexpr size_t scanLds = 2 * 2 * kScanChunk * 64 * sizeof(float);   // two buffers of 64 KiB: above the 64 KiB default cap of dynamic LDS
     RTD_HIP(h, raiseLdsCap(h, k_trace_scan, scanLds));
-    const ResetJob resetJob{f->dLayers, fc.L, reinterpret_cast<unsigned int*>(f->dTileRad), f->tileRadWords, f->dActive, (size_t)4 * fc.L * fc.S,
-                            f->dNucIdd, f->dNucRs, fc.nuclearCorr ? (size_t)fc.nucW * fc.nucH * fc.L : (size_t)0,
-                            f->dSigMin, f->dSigMax, (size_t)fc.L * fc.S, f->dScanDbg};
     launchK(k_trace_scan, dim3((unsigned)(f->R / 64)), dim3(64, kScanWaves), scanLds, s, nullptr, ev(1), (const float*)f->dIdd, f->dWepl, fc.W, fc.H,
             (unsigned)fc.S, f->dFirstInside, f->dFirstOutside, f->dState, f->dBlockWeplMin, resetJob);
     if (fc.spotNy <= kPlanConvMaxRows && !f->sw.separatePlan) {
@@ -999,6 +1031,7 @@ int rtd_field_compute_bev(rtd_handle hh, rtd_field ff) {
         k_conv_x<<<dim3(fc.W / 32, (fc.spotNy + 7) / 8, fc.L), blk, 0, s>>>(f->dSpotWeights, f->dConvInterm, f->dLayers, f->dState, fc);
         launchK(k_conv_y, dim3(fc.W / 32, fc.H / 8, fc.L), blk, 0, s, nullptr, ev(2), (const float*)f->dConvInterm, f->dRayWeights,
                 (const LayerPlan*)f->dLayers, (const FieldState*)f->dState, fc);
+    }
     }
     }
     {
@@ -1334,8 +1367,9 @@ int rtd_field_finish(rtd_handle hh, rtd_field ff, rtd_timing* timing, rtd_field_
         std::memset(timing, 0, sizeof *timing);
         RTD_HIP(h, hipEventElapsedTime(&timing->total_ms, f->ev[0], f->ev[last]));
         if (h->opt.fine_grained_timing) {
-            RTD_HIP(h, hipEventElapsedTime(&timing->raytracing_ms, f->ev[0], f->ev[1]));
-            RTD_HIP(h, hipEventElapsedTime(&timing->prepare_energy_loop_ms, f->ev[1], f->ev[2]));
+            // (a compute that reused the trace: no tracer stage, the convolution's launch is the first)
+            if (!f->launchedReuse) RTD_HIP(h, hipEventElapsedTime(&timing->raytracing_ms, f->ev[0], f->ev[1]));
+            RTD_HIP(h, hipEventElapsedTime(&timing->prepare_energy_loop_ms, f->launchedReuse ? f->ev[0] : f->ev[1], f->ev[2]));
             RTD_HIP(h, hipEventElapsedTime(&timing->fill_idd_sigma_ms, f->ev[2], f->ev[3]));
             hipEvent_t planEnd = f->selfPlanned ? f->ev[7] : f->ev[4];   // (self-planned: the plan is inside the superposition launch)
             RTD_HIP(h, hipEventElapsedTime(&timing->prepare_superp_ms, f->ev[3], planEnd));
@@ -2334,6 +2368,10 @@ int rtd_field_fetch(rtd_handle hh, rtd_field ff, const char* name, void* host_ou
         if (!f->dijDone) return fail(h, RTD_ERR_NOT_READY, "rtd_field_fetch: no dose-influence matrix");
         n = f->dijBatchOf.size() * sizeof(int); staging.resize(std::max<size_t>(n, 1));
         std::memcpy(staging.data(), f->dijBatchOf.data(), n);
+    } else if (nm == "trace_reused") {
+        const int32_t v = f->computed && f->launchedReuse ? 1 : 0;   // the last launched compute left out the tracer, the scan and the plan
+        n = sizeof v; staging.resize(n);
+        std::memcpy(staging.data(), &v, n);
     } else if (nm == "eff_radius" || nm == "layer_plan") {
         std::vector<LayerPlan> lp(L);
         RTD_HIP(h, hipMemcpy(lp.data(), f->dLayers, L * sizeof(LayerPlan), hipMemcpyDeviceToHost));

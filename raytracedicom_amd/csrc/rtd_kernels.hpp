@@ -203,12 +203,20 @@ __device__ inline float sample3dBorder(const float* __restrict__ vol, int nx, in
 // its own: the scalars that the tracer's scan accumulates into are reset by the first thread of the sampling kernel (the
 // launch before the scan), the per-layer records and the two fills that the reference does with cudaMemset per layer
 // (kernel_wrapper.cu:824-827) by the waves of the scan kernel that have no serial chain to walk.
-__device__ inline void resetFieldScalars(FieldState* st) {
-    st->beamFirstInside = 0x7fffffff; st->beamFirstOutside = -0x7fffffff; st->firstGuaranteedPassive = 0;
+//
+// A compute that reuses the field's trace and plan (k_reset_conv) resets only what k_fill and the superposition's plan accumulate
+// into or derive: resetAccumulatedScalars and resetFieldArrays<true>. What the scan and k_plan wrote stays: beamFirstInside /
+// beamFirstOutside, firstGuaranteedPassive, entryZ, pxSpMultX / pxSpMultY, empty, fillItems; of a layer afterLast, entrySigmaX / Y.
+__device__ inline void resetAccumulatedScalars(FieldState* st) {
     st->firstCalculatedPassive = 0; st->errorFlags = 0; st->maxRadius = 0; st->liveSteps = 0;
-    st->empty = 0; st->nonUniform = 0; st->uniformField = 0;
+    st->nonUniform = 0; st->uniformField = 0;
     for (int i = 0; i < 4; ++i) st->actUnion[i] = 0x7fffffff;
     for (int i = 0; i < 3; ++i) { st->bboxMin[i] = 0; st->bboxMax[i] = 0; st->tboxMin[i] = 0; st->tboxMax[i] = -1; }
+}
+__device__ inline void resetFieldScalars(FieldState* st) {
+    st->beamFirstInside = 0x7fffffff; st->beamFirstOutside = -0x7fffffff; st->firstGuaranteedPassive = 0;
+    st->empty = 0;
+    resetAccumulatedScalars(st);
 }
 struct ResetJob {
     LayerPlan* layers; int L;
@@ -218,9 +226,11 @@ struct ResetJob {
     unsigned int* sigMin; unsigned int* sigMax; size_t nSig;   // per (layer, step): bits of the smallest / largest tile-uniform sigma^2
     long long* scanDbg;             // diagnostic build only (RTD_SCAN_DEBUG): clock stamps of k_trace_scan's blocks, 8 per block
 };
+template <bool kKeepPlan = false>
 __device__ inline void resetFieldArrays(const ResetJob& j, size_t t, size_t nT) {
     for (size_t l = t; l < (size_t)j.L; l += nT) {
-        j.layers[l].layerFirstPassive = 0; j.layers[l].afterLast = 0;
+        j.layers[l].layerFirstPassive = 0;
+        if (!kKeepPlan) j.layers[l].afterLast = 0;
         for (int i = 0; i < kMaxSuperpR + 2; ++i) { j.layers[l].hist[i] = 0; j.layers[l].effRad[i] = i; j.layers[l].classLo[i] = 0x7fffffff; j.layers[l].classHi[i] = -1; }
     }
     for (size_t i = t; i < j.nRadWords; i += nT) j.tileRadWords[i] = 0xFFFFFFFFu;    // every (layer, step, tile): "not classified"
@@ -864,6 +874,22 @@ __global__ __launch_bounds__(1024) void k_plan_conv(const float* __restrict__ in
         if (blockIdx.x == 0 && blockIdx.y == 0) planBody(st, layers, blockWeplMin, nScanBlocks, weplMinBits, fc, tid, (int)blockDim.x);
         return;
     }
+    const int v = tid >> 8, t = tid & 255;
+    convTile(in, out, layers, st, fc, (int)blockIdx.x, 4 * (int)blockIdx.y + v, (int)blockIdx.z, t & 31, t >> 5, sInterm + (size_t)v * fc.spotNy * 32);
+}
+
+// K3+K4 of a compute that reuses the field's trace and plan (rtd_engine.hip: the CT, the LUTs and the options stand since a finished
+// compute traced the field): no tracer, no scan, no plan in front of it, so this launch carries K0 — thread 0 of block 0 the
+// scalars, all threads a share of the arrays, ahead of their tile (plain stores: nothing waits for them before the tile's barrier).
+// The reset touches no word the convolution reads (st->beamFirstInside; of a layer the beam model's constants), and keeps what the
+// tracer, the scan and the plan wrote. Four 32 x 8 ray tiles of layer z per block, like k_plan_conv.
+__global__ __launch_bounds__(1024) void k_reset_conv(const float* __restrict__ in, float* __restrict__ out, const LayerPlan* layers, FieldState* st,
+                                                     ResetJob reset, FieldConst fc) {
+    extern __shared__ float sInterm[];                               // [4 tiles][spotNy][32]
+    const int tid = threadIdx.x;
+    const size_t block = ((size_t)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
+    if (block == 0 && tid == 0) resetAccumulatedScalars(st);
+    resetFieldArrays<true>(reset, block * 1024 + tid, (size_t)gridDim.x * gridDim.y * gridDim.z * 1024);
     const int v = tid >> 8, t = tid & 255;
     convTile(in, out, layers, st, fc, (int)blockIdx.x, 4 * (int)blockIdx.y + v, (int)blockIdx.z, t & 31, t >> 5, sInterm + (size_t)v * fc.spotNy * 32);
 }
