@@ -606,6 +606,76 @@ int rtd_objective_dose_at_volume(rtd_handle h, rtd_objective obj, const float* d
 int rtd_objective_dvh(rtd_handle h, rtd_objective obj, const float* dev_dose, uint32_t n_bins, double dose_max, uint32_t* dev_counts);
 
 /*
+ * ---- Robust spot-weight optimisation over error scenarios ----
+ *
+ * Additive to the two blocks above (RTD_ABI_VERSION stays 3). A scenario is one realisation of the plan under an error: the same
+ * spot maps on a displaced geometry (a set-up error) or under LUTs with a scaled stopping-power table (a range error). To the engine
+ * it is just another list of fields, each with its own matrix from rtd_field_dose_influence. A robust optimiser holds S scenarios of
+ * F fields and ONE weight vector (the F spot maps concatenated, shared by all scenarios), and minimises either the expected value or
+ * the worst case of the objective over the scenarios.
+ *
+ * rtd_optimizer_create_robust   fields: n_scenarios x n_fields handles, scenario-major; scenario 0 is by convention the nominal one.
+ *                               Field f of every scenario must have the spot-map shape (nx, ny, L) of field f of scenario 0. Start
+ *                               weights are those of scenario 0's fields. Returns an ordinary rtd_optimizer: rtd_optimizer_set_weights,
+ *                               _run, _result, _weights, _dose (scenario 0) and _destroy work on it unchanged. On top of what a plain
+ *                               optimiser owns it allocates a dose and a g volume per further scenario (2 S volumes in all), S
+ *                               per-scenario spot gradients and the record below. Synchronous. The environment variable
+ *                               RTD_ROBUST_NO_BATCH, read once here, makes the optimiser issue the single-matrix launches of the plain
+ *                               iteration scenario by scenario instead of the launches batched over the scenario axis: the same bits.
+ * rtd_optimizer_scenario_values waits for the stream; f_s, lambda_s (may be NULL) and the worst scenario s* (may be NULL; under
+ *                               EXPECTED the lowest index holding the maximum as well) of the iterate f_last belongs to; zeros before
+ *                               the first run. On a plain optimiser: one scenario, values[0] = f_last, lambda 1.0, worst 0.
+ * rtd_optimizer_scenario_dose   scenario s's own volume: after a run the dose of the iterate that entered the last iteration under
+ *                               scenario s. On a plain optimiser scenario 0 is rtd_optimizer_dose.
+ *
+ * One iteration k, every step a launch on the handle's stream, no decision taken on the host:
+ *   1. for every scenario s: dose_s = sum_f Dij_{s,f} w_f, into the scenario's own volume: bit for bit a zeroed volume followed by
+ *      rtd_field_dose_influence_apply(init = 0) of that scenario's fields in list order (step 1 above, per scenario);
+ *   2. for every scenario s: rtd_objective_eval(dose_s) -> f_s, its term values, g_s (own volume, zeroed once at creation). The
+ *      objective's scratch (DVH thresholds, partial sums) is shared: the evals run one after the other on the stream;
+ *   3. one launch decides. EXPECTED: lambda_s = p_s, F = sum_s p_s * f_s in float64, ascending s, starting from 0.0, every product
+ *      rounded before it is added. WORST_CASE: s* is the lowest index with f_s == max_s f_s, lambda_{s*} = 1.0, the others 0.0,
+ *      F = f_{s*}. If any f_s is not finite, s* is the lowest such index and F = f_{s*} in either mode (the guard, 7., then acts).
+ *      lambda, f_s and s* are kept in the optimiser's device record; history[k] = F_k while k < history_capacity;
+ *   4. for every scenario with lambda_s != 0: grad_s = Dij_{s,f}^T g_s per field, float32, as rtd_field_dose_influence_apply_t writes it;
+ *   5. grad[j] = float32(sum over the scenarios with lambda_s != 0, ascending s, of lambda_s * double(grad_s[j])): a float64 sum of
+ *      separately rounded products that STARTS FROM THE FIRST PRODUCT, not from 0.0, rounded once. With one scenario and lambda 1.0
+ *      the result is grad_0[j] to the bit, a -0 included;
+ *   6. steps 4.-7. of the iteration above, word for word, with f_k := F_k and grad := the combined gradient.
+ * With n_scenarios = 1, EXPECTED and p = 1.0 this is the plain iteration bit for bit.
+ *
+ * Launches: per field position one launch covers that position in all scenarios (the grid has a scenario dimension, the per-scenario
+ * operands travel as one kernel argument); the blocks of a scenario whose lambda_s, read from the device record, is 0 leave the
+ * transposed product at once, so under WORST_CASE only the worst scenario's transposed product does work. Per output element the
+ * lane assignment, the order of the additions and the butterflies are those of the single-matrix products. As rtd_optimizer_run of a
+ * plain optimiser: launches only, no allocation, copy or host synchronisation, capturable into a graph, no float atomics, every
+ * order of summation fixed by the inputs alone: the same bits across calls, handles and processes.
+ *
+ * RTD_ERR_INVALID_ARG: a null pointer, an unknown mode, 0 or more than RTD_ROBUST_MAX_SCENARIOS scenarios, 0 or more than 16 fields
+ * per scenario, a probability that is not positive and finite, a remote field, a field listed twice (a field's product workspace is
+ * its own, and the batched launches would share it), a spot-map shape that differs between scenarios, fields of different dose grids,
+ * an objective on other dims or without terms, a scenario index out of range. RTD_ERR_NOT_READY: a field without a matrix. After a
+ * refusal every object stays usable. Not available: nuclear_corr, remote fields, the rtd_plan_* path (as the matrix itself).
+ */
+enum { RTD_ROBUST_EXPECTED = 0, RTD_ROBUST_WORST_CASE = 1 };
+#define RTD_ROBUST_MAX_SCENARIOS 32
+
+typedef struct rtd_robust_options {
+    int32_t  mode;                /* RTD_ROBUST_*                                   */
+    uint32_t n_scenarios;         /* 1 .. RTD_ROBUST_MAX_SCENARIOS                  */
+    const double* probabilities;  /* [n_scenarios], each finite and > 0, used as given (not normalised);
+                                     NULL: 1.0 / n_scenarios each. Ignored by WORST_CASE. Copied. */
+    int32_t  reserved[4];
+} rtd_robust_options;
+
+int rtd_optimizer_create_robust(rtd_handle h, const rtd_field* fields /* [n_scenarios][n_fields], scenario-major */,
+                                uint32_t n_fields, const rtd_robust_options* robust, rtd_objective obj,
+                                const rtd_optimizer_options* o, rtd_optimizer* out);
+int rtd_optimizer_scenario_values(rtd_handle h, rtd_optimizer opt, double* values /* host [n_scenarios] */,
+                                  double* lambdas /* host [n_scenarios] or NULL */, int32_t* worst /* or NULL */);
+int rtd_optimizer_scenario_dose(rtd_handle h, rtd_optimizer opt, uint32_t scenario, const float** dev_dose);
+
+/*
  * ---- Multi-GPU plans behind the boundary (SURVEY.md 8(b) "Threading": one handle and one host thread per device) ----
  *
  * rtd_plan is the reference-shaped call on several GPUs of one process: the 4-beam cudaWrapperProtons of the C++ shim uses

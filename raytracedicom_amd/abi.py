@@ -23,6 +23,8 @@ RTD_OBJ_MAX_TERMS = 64
 RTD_OPT_MAX_FIELDS = 16
 RTD_OBJ_MAX_DVH, RTD_OBJ_MIN_DVH = 4, 5     # rtd_objective_add_dvh_term only
 RTD_DVH_MAX_QUERIES = 64
+RTD_ROBUST_EXPECTED, RTD_ROBUST_WORST_CASE = 0, 1
+RTD_ROBUST_MAX_SCENARIOS = 32
 
 c_float_p = C.POINTER(C.c_float)
 
@@ -136,6 +138,10 @@ class RtdOptimizerReport(C.Structure):
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
+
+
+class RtdRobustOptions(C.Structure):
+    _fields_ = [("mode", C.c_int32), ("n_scenarios", C.c_uint32), ("probabilities", C.POINTER(C.c_double)), ("reserved", C.c_int32 * 4)]
 
 
 def default_optimizer_options():

@@ -34,6 +34,7 @@
 #include "rtd_dij_apply.hpp"
 #include "rtd_optimize.hpp"
 #include "rtd_dvh.hpp"
+#include "rtd_robust.hpp"
 
 using namespace rtd;
 
@@ -1899,14 +1900,26 @@ struct rtd_optimizer_impl {
     float *dDose = nullptr, *dG = nullptr, *dVec = nullptr;   // dVec: w | w_prev | grad | grad_prev | w_best, n each
     double *dHistory = nullptr, *dValues = nullptr, *dPart = nullptr;
     OptState* dState = nullptr;
+    // Robust scenarios (section 14). A plain optimiser is nScen == 1, robust == false, and touches none of what follows.
+    bool robust = false, batch = true;
+    int nScen = 1, mode = 0;
+    std::vector<rtd_field_impl*> sfields;   // [nScen][fields.size()], scenario-major; row 0 is `fields`
+    std::vector<float*> doseS, gS;          // per scenario; [0] = dDose, dG
+    float* dGradS = nullptr;                // [nScen][n]: Dij_s^T g_s
+    double* dScenValues = nullptr;          // [nScen][1 + kObjMaxTerms]
+    RobustState* dRobust = nullptr;
+    rtd_field_impl* sf(int s, size_t i) const { return sfields[(size_t)s * fields.size() + i]; }
     float* w() const { return dVec; }
     float* wPrev() const { return dVec + n; }
     float* grad() const { return dVec + 2 * (size_t)n; }
     float* gradPrev() const { return dVec + 3 * (size_t)n; }
     float* wBest() const { return dVec + 4 * (size_t)n; }
     void freeAll() {
-        for (void** p : {(void**)&dDose, (void**)&dG, (void**)&dVec, (void**)&dHistory, (void**)&dValues, (void**)&dPart, (void**)&dState})
+        for (void** p : {(void**)&dDose, (void**)&dG, (void**)&dVec, (void**)&dHistory, (void**)&dValues, (void**)&dPart, (void**)&dState,
+                         (void**)&dGradS, (void**)&dScenValues, (void**)&dRobust})
             if (*p) { (void)hipFree(*p); *p = nullptr; }
+        for (size_t s = 1; s < doseS.size(); ++s) { if (doseS[s]) (void)hipFree(doseS[s]); if (s < gS.size() && gS[s]) (void)hipFree(gS[s]); }
+        doseS.clear(); gS.clear();
     }
 };
 
@@ -2051,6 +2064,86 @@ int optAdjoint(rtd_handle hh, rtd_optimizer_impl* p) {
     return RTD_OK;
 }
 
+// The same two products over the scenario axis (section 14; kernels in rtd_robust.hpp). Batched: per field position one launch covers
+// every scenario. Unbatched (RTD_ROBUST_NO_BATCH): the single-matrix launches, scenario by scenario. Either way scenario s's volume
+// gets what optForward gives a plain optimiser of that scenario's fields, and gradS[s] what optAdjoint gives it.
+int robustForward(rtd_handle hh, rtd_handle_impl* h, rtd_optimizer_impl* p) {
+    const size_t F = p->fields.size();
+    const int S = p->nScen, nx = (int)p->fields[0]->doseDims[0], ny = (int)p->fields[0]->doseDims[1];
+    if (!p->batch) {
+        for (int s = 0; s < S; ++s) {
+            for (size_t i = 1; i < F; ++i) {
+                const rtd_field_impl* f = p->sf(s, i);
+                const long long nRows = (long long)f->dijRowsN;
+                if (nRows) k_opt_clear_box<<<(unsigned)((nRows + 255) / 256), 256, 0, h->stream>>>(p->doseS[s], nx, ny, f->dijBox, nRows);
+            }
+            for (size_t i = 0; i < F; ++i) {
+                const int st = rtd_field_dose_influence_apply(hh, reinterpret_cast<rtd_field>(p->sf(s, i)), p->w() + p->offset[i], p->doseS[s], i == 0 ? 1 : 0);
+                if (st != RTD_OK) return st;
+            }
+        }
+        return RTD_OK;
+    }
+    for (size_t i = 1; i < F; ++i) {
+        RobustClear a{};
+        long long most = 0;
+        for (int s = 0; s < S; ++s) {
+            const rtd_field_impl* f = p->sf(s, i);
+            a.dose[s] = p->doseS[s]; a.nRows[s] = (long long)f->dijRowsN; a.box[s] = f->dijBox;
+            most = std::max(most, a.nRows[s]);
+        }
+        if (most) k_robust_clear_box<<<dim3((unsigned)((most + 255) / 256), (unsigned)S), 256, 0, h->stream>>>(a, nx, ny);
+    }
+    for (size_t i = 0; i < F; ++i) {
+        RobustFwd a{};
+        long long most = 0;
+        for (int s = 0; s < S; ++s) {
+            const rtd_field_impl* f = p->sf(s, i);
+            a.rowPtr[s] = (const long long*)f->dDijRowPtr; a.cCols[s] = f->dDijCCols; a.cVals[s] = f->dDijCVals; a.dose[s] = p->doseS[s];
+            a.nRows[s] = (i != 0 && f->dijNnz == 0) ? 0 : (long long)f->dijRowsN;   // (an empty matrix adds nothing: no work, as the single call)
+            a.box[s] = f->dijBox;
+            most = std::max(most, a.nRows[s]);
+        }
+        if (!most) continue;
+        const dim3 grid((unsigned)((most * kDijApGroup + 255) / 256), (unsigned)S);
+        if (i == 0) k_dijap_apply_batch<true><<<grid, 256, 0, h->stream>>>(a, (const float*)(p->w() + p->offset[i]), nx, ny);
+        else k_dijap_apply_batch<false><<<grid, 256, 0, h->stream>>>(a, (const float*)(p->w() + p->offset[i]), nx, ny);
+    }
+    RTD_HIP(h, hipGetLastError());
+    return RTD_OK;
+}
+int robustAdjoint(rtd_handle hh, rtd_handle_impl* h, rtd_optimizer_impl* p) {
+    const size_t F = p->fields.size();
+    const int S = p->nScen;
+    if (!p->batch) {   // no decision on the host: every scenario's product is taken, the combine uses those with lambda != 0
+        for (int s = 0; s < S; ++s)
+            for (size_t i = 0; i < F; ++i) {
+                const int st = rtd_field_dose_influence_apply_t(hh, reinterpret_cast<rtd_field>(p->sf(s, i)), p->gS[s], p->dGradS + (size_t)s * p->n + p->offset[i]);
+                if (st != RTD_OK) return st;
+            }
+        return RTD_OK;
+    }
+    for (size_t i = 0; i < F; ++i) {
+        RobustAdj a{};
+        RobustRed r{};
+        int most = 0;
+        for (int s = 0; s < S; ++s) {
+            const rtd_field_impl* f = p->sf(s, i);
+            a.colPtr[s] = (const long long*)f->dDijColPtr; a.rows[s] = (const int*)f->dDijRows; a.vals[s] = (const float*)f->dDijVals;
+            a.chunkCol[s] = (const int*)f->dDijChunkCol; a.chunkFirst[s] = (const int*)f->dDijChunkFirst; a.g[s] = p->gS[s];
+            a.partial[s] = f->dDijPartial; a.nChunks[s] = (int)f->dijChunks;
+            r.chunkFirst[s] = (const int*)f->dDijChunkFirst; r.partial[s] = (const float*)f->dDijPartial;
+            r.out[s] = p->dGradS + (size_t)s * p->n + p->offset[i];
+            most = std::max(most, a.nChunks[s]);
+        }
+        const int nSpot = p->offset[i + 1] - p->offset[i];
+        if (most) k_dijap_apply_t_batch<<<dim3((unsigned)((most + 3) / 4), (unsigned)S), 256, 0, h->stream>>>(a, (const RobustState*)p->dRobust);
+        k_dijap_reduce_t_batch<<<dim3((unsigned)((nSpot + 3) / 4), (unsigned)S), 256, 0, h->stream>>>(r, (const RobustState*)p->dRobust, nSpot);
+    }
+    RTD_HIP(h, hipGetLastError());
+    return RTD_OK;
+}
+
 }  // namespace
 
 int rtd_objective_create(rtd_handle hh, const uint32_t dose_dims[3], rtd_objective* out) {
@@ -2187,35 +2280,59 @@ void rtd_default_optimizer_options(rtd_optimizer_options* o) {
     o->step_min = 1e-30; o->step_max = 1e30; o->history_capacity = 4096;
 }
 
-int rtd_optimizer_create(rtd_handle hh, const rtd_field* fields, uint32_t n_fields, rtd_objective oo, const rtd_optimizer_options* opt,
-                         rtd_optimizer* out) {
+namespace {
+// rtd_optimizer_create (robust == nullptr: one scenario, nothing of section 14 allocated or launched) and rtd_optimizer_create_robust.
+int optCreate(rtd_handle hh, const rtd_field* fields, uint32_t n_fields, const rtd_robust_options* robust, rtd_objective oo,
+              const rtd_optimizer_options* opt, rtd_optimizer* out) {
     auto* h = reinterpret_cast<rtd_handle_impl*>(hh);
     auto* o = reinterpret_cast<rtd_objective_impl*>(oo);
     if (!h) return RTD_ERR_INVALID_ARG;
     if (!fields || !o || !out) return fail(h, RTD_ERR_INVALID_ARG, "rtd_optimizer_create: null pointer");
     *out = nullptr;
+    const uint32_t nScen = robust ? robust->n_scenarios : 1;
+    if (robust) {
+        if (robust->mode != RTD_ROBUST_EXPECTED && robust->mode != RTD_ROBUST_WORST_CASE) return fail(h, RTD_ERR_INVALID_ARG, "rtd_optimizer_create_robust: unknown mode");
+        if (nScen < 1 || nScen > RTD_ROBUST_MAX_SCENARIOS) return fail(h, RTD_ERR_INVALID_ARG, "rtd_optimizer_create_robust: 1 to 32 scenarios");
+        if (robust->probabilities)
+            for (uint32_t sc = 0; sc < nScen; ++sc)
+                if (!(robust->probabilities[sc] > 0.0) || !std::isfinite(robust->probabilities[sc]))
+                    return fail(h, RTD_ERR_INVALID_ARG, "rtd_optimizer_create_robust: a probability must be positive and finite");
+    }
     if (n_fields < 1 || n_fields > RTD_OPT_MAX_FIELDS) return fail(h, RTD_ERR_INVALID_ARG, "rtd_optimizer_create: 1 to 16 fields");
     rtd_optimizer_options op;
     rtd_default_optimizer_options(&op);
     if (opt) op = *opt;
     if (!(op.step_min > 0.0) || !(op.step_max >= op.step_min) || !std::isfinite(op.step_max))
         return fail(h, RTD_ERR_INVALID_ARG, "rtd_optimizer_create: needs 0 < step_min <= step_max < inf");
-    for (uint32_t i = 0; i < n_fields; ++i) {
+    const uint32_t nAll = nScen * n_fields;
+    for (uint32_t i = 0; i < nAll; ++i) {
         auto* f = reinterpret_cast<rtd_field_impl*>(fields[i]);
         if (!f) return fail(h, RTD_ERR_INVALID_ARG, "rtd_optimizer_create: null field");
         if (f->remote) return fail(h, RTD_ERR_INVALID_ARG, "rtd_optimizer_create: a remote field has no matrix");
         for (int a = 0; a < 3; ++a)
             if (f->doseDims[a] != o->dims[a]) return fail(h, RTD_ERR_INVALID_ARG, "rtd_optimizer_create: the fields and the objective must share one dose grid");
+        if (robust) {
+            const auto* f0 = reinterpret_cast<rtd_field_impl*>(fields[i % n_fields]);
+            if (f0 && (f->fc.spotNx != f0->fc.spotNx || f->fc.spotNy != f0->fc.spotNy || f->fc.L != f0->fc.L))
+                return fail(h, RTD_ERR_INVALID_ARG, "rtd_optimizer_create_robust: field f of every scenario must have the spot-map shape of field f of scenario 0");
+            for (uint32_t k = 0; k < i; ++k)
+                if (fields[k] == fields[i]) return fail(h, RTD_ERR_INVALID_ARG, "rtd_optimizer_create_robust: a field is listed twice");
+        }
     }
     if (o->terms.empty()) return fail(h, RTD_ERR_INVALID_ARG, "rtd_optimizer_create: the objective has no terms");
-    for (uint32_t i = 0; i < n_fields; ++i)
+    for (uint32_t i = 0; i < nAll; ++i)
         if (!reinterpret_cast<rtd_field_impl*>(fields[i])->dijDone)
             return fail(h, RTD_ERR_NOT_READY, "rtd_optimizer_create: a field has no dose-influence matrix (call rtd_field_dose_influence first)");
     RTD_HIP(h, hipSetDevice(h->device));
-    for (uint32_t i = 0; i < n_fields; ++i) { const int st = rtd_field_dose_influence_prepare(hh, fields[i]); if (st != RTD_OK) return st; }
+    for (uint32_t i = 0; i < nAll; ++i) { const int st = rtd_field_dose_influence_prepare(hh, fields[i]); if (st != RTD_OK) return st; }
     if (!o->built) { const int st = buildObjective(h, o); if (st != RTD_OK) return st; }
     auto* p = new rtd_optimizer_impl();
     p->obj = o; p->opt = op; p->nVox = o->nVox;
+    if (robust) {
+        p->robust = true; p->nScen = (int)nScen; p->mode = robust->mode;
+        p->batch = std::getenv("RTD_ROBUST_NO_BATCH") == nullptr;      // read once, here (the convention of the engine switches)
+        for (uint32_t i = 0; i < nAll; ++i) p->sfields.push_back(reinterpret_cast<rtd_field_impl*>(fields[i]));
+    }
     p->offset.push_back(0);
     long long total = 0;
     for (uint32_t i = 0; i < n_fields; ++i) {
@@ -2249,9 +2366,77 @@ int rtd_optimizer_create(rtd_handle hh, const rtd_field* fields, uint32_t n_fiel
         e = hipMemcpyAsync(p->w() + p->offset[i], p->fields[i]->dSpotWeights, cnt, hipMemcpyDeviceToDevice, s);
         if (e == hipSuccess) e = hipMemcpyAsync(p->wBest() + p->offset[i], p->fields[i]->dSpotWeights, cnt, hipMemcpyDeviceToDevice, s);
     }
-    if (e == hipSuccess) e = hipStreamSynchronize(s);                 // (st0 lives on this stack)
+    p->doseS.assign(1, p->dDose); p->gS.assign(1, p->dG);
+    RobustState rs0{};
+    if (robust) {
+        p->doseS.resize(nScen, nullptr); p->gS.resize(nScen, nullptr);
+        for (uint32_t sc = 1; sc < nScen && e == hipSuccess; ++sc) {
+            e = hipMalloc((void**)&p->doseS[sc], p->nVox * sizeof(float));
+            if (e == hipSuccess) e = hipMalloc((void**)&p->gS[sc], p->nVox * sizeof(float));
+            if (e == hipSuccess) e = hipMemsetAsync(p->doseS[sc], 0, p->nVox * sizeof(float), s);
+            if (e == hipSuccess) e = hipMemsetAsync(p->gS[sc], 0, p->nVox * sizeof(float), s);
+        }
+        const size_t gradBytes = std::max<size_t>((size_t)nScen * n, 1) * sizeof(float), valBytes = (size_t)nScen * (1 + kObjMaxTerms) * sizeof(double);
+        if (e == hipSuccess) e = hipMalloc((void**)&p->dGradS, gradBytes);
+        if (e == hipSuccess) e = hipMalloc((void**)&p->dScenValues, valBytes);
+        if (e == hipSuccess) e = hipMalloc((void**)&p->dRobust, sizeof(RobustState));
+        if (e == hipSuccess) e = hipMemsetAsync(p->dGradS, 0, gradBytes, s);
+        if (e == hipSuccess) e = hipMemsetAsync(p->dScenValues, 0, valBytes, s);
+        for (uint32_t sc = 0; sc < nScen; ++sc) rs0.prob[sc] = robust->probabilities ? robust->probabilities[sc] : 1.0 / (double)nScen;
+        if (e == hipSuccess) e = hipMemcpyAsync(p->dRobust, &rs0, sizeof rs0, hipMemcpyHostToDevice, s);
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(s);                 // (st0 and rs0 live on this stack)
     if (e != hipSuccess) { (void)hipStreamSynchronize(s); p->freeAll(); delete p; RTD_HIP(h, e); }
     *out = reinterpret_cast<rtd_optimizer>(p);
+    return RTD_OK;
+}
+}  // namespace
+
+int rtd_optimizer_create(rtd_handle hh, const rtd_field* fields, uint32_t n_fields, rtd_objective oo, const rtd_optimizer_options* opt,
+                         rtd_optimizer* out) {
+    return optCreate(hh, fields, n_fields, nullptr, oo, opt, out);
+}
+
+int rtd_optimizer_create_robust(rtd_handle hh, const rtd_field* fields, uint32_t n_fields, const rtd_robust_options* robust, rtd_objective oo,
+                                const rtd_optimizer_options* opt, rtd_optimizer* out) {
+    auto* h = reinterpret_cast<rtd_handle_impl*>(hh);
+    if (!h) return RTD_ERR_INVALID_ARG;
+    if (!robust) return fail(h, RTD_ERR_INVALID_ARG, "rtd_optimizer_create_robust: null pointer");
+    if (out) *out = nullptr;
+    return optCreate(hh, fields, n_fields, robust, oo, opt, out);
+}
+
+// f_s, lambda_s and the worst scenario of the iterate f_last belongs to. A plain optimiser is a set of one scenario.
+int rtd_optimizer_scenario_values(rtd_handle hh, rtd_optimizer pp, double* values, double* lambdas, int32_t* worst) {
+    auto* h = reinterpret_cast<rtd_handle_impl*>(hh);
+    auto* p = reinterpret_cast<rtd_optimizer_impl*>(pp);
+    if (!h) return RTD_ERR_INVALID_ARG;
+    if (!p || !values) return fail(h, RTD_ERR_INVALID_ARG, "rtd_optimizer_scenario_values: null pointer");
+    RTD_HIP(h, hipSetDevice(h->device));
+    if (!p->robust) {
+        OptState st{};
+        RTD_HIP(h, hipMemcpyAsync(&st, p->dState, sizeof st, hipMemcpyDeviceToHost, h->stream));
+        RTD_HIP(h, hipStreamSynchronize(h->stream));
+        values[0] = st.fLast;
+        if (lambdas) lambdas[0] = 1.0;
+        if (worst) *worst = 0;
+        return RTD_OK;
+    }
+    RobustState rs{};
+    RTD_HIP(h, hipMemcpyAsync(&rs, p->dRobust, sizeof rs, hipMemcpyDeviceToHost, h->stream));
+    RTD_HIP(h, hipStreamSynchronize(h->stream));
+    for (int sc = 0; sc < p->nScen; ++sc) { values[sc] = rs.f[sc]; if (lambdas) lambdas[sc] = rs.lambda[sc]; }
+    if (worst) *worst = rs.worst;
+    return RTD_OK;
+}
+
+int rtd_optimizer_scenario_dose(rtd_handle hh, rtd_optimizer pp, uint32_t scenario, const float** dev_dose) {
+    auto* h = reinterpret_cast<rtd_handle_impl*>(hh);
+    auto* p = reinterpret_cast<rtd_optimizer_impl*>(pp);
+    if (!h) return RTD_ERR_INVALID_ARG;
+    if (!p || !dev_dose) return fail(h, RTD_ERR_INVALID_ARG, "rtd_optimizer_scenario_dose: null pointer");
+    if (scenario >= (uint32_t)p->nScen) return fail(h, RTD_ERR_INVALID_ARG, "rtd_optimizer_scenario_dose: scenario index out of range");
+    *dev_dose = p->doseS[scenario];
     return RTD_OK;
 }
 
@@ -2277,9 +2462,22 @@ int rtd_optimizer_run(rtd_handle hh, rtd_optimizer pp, uint32_t n_iterations) {
     RTD_HIP(h, hipSetDevice(h->device));
     hipStream_t s = h->stream;
     for (uint32_t k = 0; k < n_iterations; ++k) {
-        int st = optForward(hh, h, p);                                                    // 1.
-        if (st == RTD_OK) st = evalObjective(h, p->obj, p->dDose, p->dValues, p->dG);     // 2.
-        if (st == RTD_OK) st = optAdjoint(hh, p);                                         // 3.
+        int st = RTD_OK;
+        if (!p->robust) {
+            st = optForward(hh, h, p);                                                    // 1.
+            if (st == RTD_OK) st = evalObjective(h, p->obj, p->dDose, p->dValues, p->dG); // 2.
+            if (st == RTD_OK) st = optAdjoint(hh, p);                                     // 3.
+        } else {                                                                          // section 14, steps 1.-5.
+            st = robustForward(hh, h, p);
+            for (int sc = 0; sc < p->nScen && st == RTD_OK; ++sc)
+                st = evalObjective(h, p->obj, p->doseS[sc], p->dScenValues + (size_t)sc * (1 + kObjMaxTerms), p->gS[sc]);
+            if (st == RTD_OK) {
+                k_robust_decide<<<1, 64, 0, s>>>((const double*)p->dScenValues, 1 + kObjMaxTerms, p->nScen, p->mode, p->dRobust, p->dValues);
+                st = robustAdjoint(hh, h, p);
+            }
+            if (st == RTD_OK)
+                k_robust_combine<<<(unsigned)((p->n + 255) / 256), 256, 0, s>>>((const float*)p->dGradS, (const RobustState*)p->dRobust, p->nScen, p->n, p->grad());
+        }
         if (st != RTD_OK) return st;
         k_opt_partials<<<(unsigned)((p->nCh + 3) / 4), 256, 0, s>>>((const float*)p->w(), (const float*)p->wPrev(), (const float*)p->grad(),
                                                                    (const float*)p->gradPrev(), p->n, p->nCh, p->dPart);

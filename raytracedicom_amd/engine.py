@@ -103,6 +103,9 @@ def lib():
         L.rtd_optimizer_weights.argtypes = [vp, vp, C.c_uint32, vp, C.c_int]
         L.rtd_optimizer_dose.argtypes = [vp, vp, vpp]
         L.rtd_optimizer_destroy.argtypes = [vp, vp]
+        L.rtd_optimizer_create_robust.argtypes = [vp, vpp, C.c_uint32, C.POINTER(abi.RtdRobustOptions), vp, C.POINTER(abi.RtdOptimizerOptions), vpp]
+        L.rtd_optimizer_scenario_values.argtypes = [vp, vp, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int32)]
+        L.rtd_optimizer_scenario_dose.argtypes = [vp, vp, C.c_uint32, vpp]
         L.rtd_host_register.argtypes = [vp, C.c_size_t]
         L.rtd_host_unregister.argtypes = [vp]
         L.rtd_plan_create.argtypes = [C.POINTER(C.c_int), C.c_int, vpp]
@@ -416,14 +419,35 @@ class Optimizer:
     """rtd_optimizer_*: the resident spectral projected gradient iteration on an Objective of the dose of `fields` (each with a
     dose_influence() matrix). Destroy it before its fields, its objective and its engine."""
 
-    def __init__(self, eng, fields, objective, options=None):
+    def __init__(self, eng, fields, objective, options=None, scenario_fields=None, mode=None, probabilities=None):
+        """scenario_fields (a list of per-scenario field lists, scenario 0 the nominal one) makes it a robust optimiser
+        (rtd_optimizer_create_robust) in mode abi.RTD_ROBUST_EXPECTED / _WORST_CASE; `fields` is then ignored."""
         self.eng = eng
-        self.fields = list(fields)
         self.objective = objective
         self._h = C.c_void_p()
-        arr = (C.c_void_p * max(1, len(self.fields)))(*[f._h for f in self.fields])
-        eng._check(lib().rtd_optimizer_create(eng._h, arr, len(self.fields), objective._h, C.byref(options) if options is not None else None,
-                                              C.byref(self._h)))
+        po = C.byref(options) if options is not None else None
+        if scenario_fields is None:
+            self.fields = list(fields)
+            self.scenario_fields = [self.fields]
+            arr = (C.c_void_p * max(1, len(self.fields)))(*[f._h for f in self.fields])
+            eng._check(lib().rtd_optimizer_create(eng._h, arr, len(self.fields), objective._h, po, C.byref(self._h)))
+            return
+        self.scenario_fields = [list(fs) for fs in scenario_fields]
+        self.fields = self.scenario_fields[0] if self.scenario_fields else []
+        n_fields = len(self.fields)
+        if any(len(fs) != n_fields for fs in self.scenario_fields):
+            raise ValueError("every scenario needs the same number of fields")
+        flat = [f._h for fs in self.scenario_fields for f in fs]
+        arr = (C.c_void_p * max(1, len(flat)))(*flat)
+        ro = abi.RtdRobustOptions()
+        ro.mode = int(abi.RTD_ROBUST_EXPECTED if mode is None else mode)
+        ro.n_scenarios = len(self.scenario_fields)
+        if probabilities is not None:
+            pr = np.ascontiguousarray(probabilities, dtype=np.float64).reshape(-1)
+            if pr.size != len(self.scenario_fields):
+                raise ValueError("one probability per scenario")
+            ro.probabilities = pr.ctypes.data_as(C.POINTER(C.c_double))
+        eng._check(lib().rtd_optimizer_create_robust(eng._h, arr, n_fields, C.byref(ro), objective._h, po, C.byref(self._h)))
 
     def set_weights(self, field_index, dev_w):
         self.eng._check(lib().rtd_optimizer_set_weights(self.eng._h, self._h, int(field_index), C.c_void_p(int(dev_w))))
@@ -462,6 +486,21 @@ class Optimizer:
         """Device pointer of the optimiser's dose volume: the dose of the iterate that entered the last iteration."""
         p = C.c_void_p()
         self.eng._check(lib().rtd_optimizer_dose(self.eng._h, self._h, C.byref(p)))
+        return int(p.value or 0)
+
+    def scenario_values(self):
+        """Waits; (values float64[S], lambdas float64[S], worst): every scenario's objective, its share of the combined gradient and
+        the worst scenario, of the iterate that entered the last iteration. A plain optimiser is a set of one scenario."""
+        n = len(self.scenario_fields)
+        vals, lams, worst = np.zeros(n, dtype=np.float64), np.zeros(n, dtype=np.float64), C.c_int32(0)
+        dp = C.POINTER(C.c_double)
+        self.eng._check(lib().rtd_optimizer_scenario_values(self.eng._h, self._h, vals.ctypes.data_as(dp), lams.ctypes.data_as(dp), C.byref(worst)))
+        return vals, lams, int(worst.value)
+
+    def scenario_dose(self, s):
+        """Device pointer of scenario s's dose volume (scenario 0: dose())."""
+        p = C.c_void_p()
+        self.eng._check(lib().rtd_optimizer_scenario_dose(self.eng._h, self._h, int(s), C.byref(p)))
         return int(p.value or 0)
 
     def destroy(self):
@@ -564,6 +603,11 @@ class Engine:
 
     def create_optimizer(self, fields, objective, options=None):
         return Optimizer(self, fields, objective, options)
+
+    def create_robust_optimizer(self, scenario_fields, objective, mode, probabilities=None, options=None):
+        """rtd_optimizer_create_robust: scenario_fields is a list of per-scenario field lists (scenario 0 the nominal one, every field
+        with a dose_influence() matrix); mode abi.RTD_ROBUST_EXPECTED or abi.RTD_ROBUST_WORST_CASE. See raytracedicom_amd.robust."""
+        return Optimizer(self, None, objective, options, scenario_fields=scenario_fields, mode=mode, probabilities=probabilities)
 
     def transfer_fields_init(self, fields, dev_dose, box_min=None, box_max=None):
         """rtd_fields_transfer_init: every voxel of the inclusive dose-index box is written with 0 + fields[0] + fields[1] + ...
