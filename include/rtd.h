@@ -676,6 +676,77 @@ int rtd_optimizer_scenario_values(rtd_handle h, rtd_optimizer opt, double* value
 int rtd_optimizer_scenario_dose(rtd_handle h, rtd_optimizer opt, uint32_t scenario, const float** dev_dose);
 
 /*
+ * ---- The voxel-wise worst case over error scenarios ----
+ *
+ * Additive to the three blocks above (RTD_ABI_VERSION stays 3; rtd_robust_options and rtd_optimizer_create_robust are untouched). The
+ * block above decides per SCENARIO. Here every voxel takes, across the scenarios, the dose that is worst for each term (the composite
+ * worst-case dose): over-dose penalties see the voxel's maximum, under-dose penalties its minimum, and the gradient of a voxel's
+ * penalty flows back through the scenario that supplied that extreme.
+ *
+ * Extremes of a voxel v over the doses d_s = dose_s[v], s = 0 .. S - 1, compared as float32: hi is the largest d_s and s_hi the lowest
+ * index that holds it, lo the smallest d_s and s_lo the lowest index that holds it (-0 == +0, so the lower index wins). If any d_s is a
+ * NaN, hi = lo = the NaN of the lowest such s and s_hi = s_lo = that s: a dose that is not finite still gives an objective that is not
+ * finite, and the optimiser's guard acts as before.
+ *
+ * rtd_objective_eval_voxelwise   the sibling of rtd_objective_eval on S volumes. dev_doses, dev_voxel_grads: HOST arrays of
+ *                                n_scenarios device pointers (float32 volumes on the grid; read during the call only, they travel
+ *                                as one kernel argument); dev_values: float64[1 + terms] as rtd_objective_eval; dev_active: one
+ *                                word on the device, bit s set iff scenario s received a gradient that is not zero. Per union
+ *                                voxel v and per term t of the voxel, in term order, the term sees the dose d of
+ *                                    RTD_OBJ_SQ_OVERDOSE, RTD_OBJ_MEAN   (hi, s_hi),
+ *                                    RTD_OBJ_SQ_UNDERDOSE                (lo, s_lo),
+ *                                    RTD_OBJ_SQ_DEVIATION                (hi, s_hi) when |hi - level| >= |lo - level| in float64,
+ *                                                                        else (lo, s_lo),
+ *                                and phi and the contribution c_t x (wn_t for MEAN) are those of rtd_objective_eval on that d.
+ *                                Gradient: the contributions at v are summed in float64, in term order, starting from 0.0, one sum
+ *                                per receiving scenario; when s_hi == s_lo every term adds to ONE sum (so that with one scenario the
+ *                                result is rtd_objective_eval to the bit). g_{s_hi}[v] and g_{s_lo}[v] get their sum rounded once to
+ *                                float32, every other scenario's g_s[v] gets +0.0f: all S volumes are WRITTEN at every voxel of the
+ *                                union of the ROIs, because the choice moves between calls, and touched nowhere else. Active word:
+ *                                bit s is set iff some value written to g_s compares != 0 (a NaN does); the call clears the word
+ *                                first, a wave sets its bits with one integer OR (order-free, as the DVH counts). Values: the sums
+ *                                of phi per term by the tree of rtd_objective_eval, unchanged. After the objective's tables exist
+ *                                the call is a clear of the word and two launches on the handle's stream: no allocation, no copy, no
+ *                                host synchronisation; it can be captured into a graph. The dose at volume of a composite needs the
+ *                                composite materialised first, so an objective with DVH terms is refused here (left for later);
+ *                                rtd_scenario_dose_extremes materialises it for reporting.
+ * rtd_scenario_dose_extremes     dev_min[v] = lo, dev_max[v] = hi (the rules above) for v < n_voxels; either output may be NULL.
+ *                                One launch on the handle's stream, capturable. What rtd_objective_dvh and
+ *                                rtd_objective_dose_at_volume are pointed at for worst-case DVH bands and a worst-case D95.
+ * rtd_optimizer_create_voxelwise ownership, checks and refusals of rtd_optimizer_create_robust (the field list, RTD_ERR_NOT_READY
+ *                                without a matrix, the same spot-map shapes and dose grid across scenarios, RTD_ROBUST_NO_BATCH);
+ *                                in addition an objective with DVH terms is refused. Returns an ordinary rtd_optimizer; it owns
+ *                                what a robust optimiser owns and the active word.
+ *
+ * One iteration k, every step a launch on the handle's stream, no decision taken on the host:
+ *   1. step 1 of the block above: dose_s = sum_f Dij_{s,f} w_f into the S volumes;
+ *   2. rtd_objective_eval_voxelwise on the S volumes -> F, the term values, g_s, the active word;
+ *   3. one thread of one launch: lambda_s = 1.0 where bit s is set and 0.0 elsewhere; f_s = F for every s (a composite has no
+ *      per-scenario split); s* = the lowest active s, or 0 if none is; history[k] = F while k < history_capacity;
+ *   4. step 4 of the block above: grad_s = Dij_{s,f}^T g_s for the scenarios with lambda_s != 0;
+ *   5. step 5 of the block above: grad[j] = float32(sum over the active scenarios, ascending s, of double(grad_s[j])), from the first
+ *      product, rounded once; +0 when no scenario is active;
+ *   6. steps 4.-7. of the plain iteration, word for word, with f_k := F_k and grad := the combined gradient.
+ * With n_scenarios = 1 this is the plain iteration bit for bit. rtd_optimizer_scenario_values returns the record of step 3;
+ * rtd_optimizer_scenario_dose, _dose, _weights, _result, _set_weights, _run and _destroy work as on a robust optimiser.
+ *
+ * RTD_ERR_INVALID_ARG: a null pointer (any entry of either array included), n_scenarios of 0 or above RTD_ROBUST_MAX_SCENARIOS, an
+ * objective without terms or with DVH terms, n_voxels == 0, both outputs NULL, and whatever rtd_optimizer_create_robust refuses.
+ * After a refusal every object is what it was.
+ */
+int rtd_objective_eval_voxelwise(rtd_handle h, rtd_objective obj,
+        const float* const* dev_doses  /* host array of n_scenarios device pointers */,
+        uint32_t n_scenarios           /* 1 .. RTD_ROBUST_MAX_SCENARIOS */,
+        double* dev_values             /* [1 + terms], as rtd_objective_eval */,
+        float* const* dev_voxel_grads  /* host array of n_scenarios device pointers */,
+        uint32_t* dev_active           /* one word: bit s set iff scenario s received a non-zero gradient */);
+int rtd_scenario_dose_extremes(rtd_handle h, const float* const* dev_doses, uint32_t n_scenarios,
+                               size_t n_voxels, float* dev_min /* or NULL */, float* dev_max /* or NULL */);
+int rtd_optimizer_create_voxelwise(rtd_handle h, const rtd_field* fields /* [n_scenarios][n_fields], scenario-major */,
+                                   uint32_t n_fields, uint32_t n_scenarios, rtd_objective obj,
+                                   const rtd_optimizer_options* o, rtd_optimizer* out);
+
+/*
  * ---- Multi-GPU plans behind the boundary (SURVEY.md 8(b) "Threading": one handle and one host thread per device) ----
  *
  * rtd_plan is the reference-shaped call on several GPUs of one process: the 4-beam cudaWrapperProtons of the C++ shim uses

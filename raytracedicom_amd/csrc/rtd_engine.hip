@@ -35,6 +35,7 @@
 #include "rtd_optimize.hpp"
 #include "rtd_dvh.hpp"
 #include "rtd_robust.hpp"
+#include "rtd_voxelwise.hpp"
 
 using namespace rtd;
 
@@ -1908,6 +1909,9 @@ struct rtd_optimizer_impl {
     float* dGradS = nullptr;                // [nScen][n]: Dij_s^T g_s
     double* dScenValues = nullptr;          // [nScen][1 + kObjMaxTerms]
     RobustState* dRobust = nullptr;
+    // The voxel-wise worst case (section 15): a robust optimiser whose steps 2 and 3 are one composite evaluation and its own decision.
+    bool voxelwise = false;
+    unsigned* dActive = nullptr;            // one word: the scenarios that received a non-zero voxel gradient
     rtd_field_impl* sf(int s, size_t i) const { return sfields[(size_t)s * fields.size() + i]; }
     float* w() const { return dVec; }
     float* wPrev() const { return dVec + n; }
@@ -1916,7 +1920,7 @@ struct rtd_optimizer_impl {
     float* wBest() const { return dVec + 4 * (size_t)n; }
     void freeAll() {
         for (void** p : {(void**)&dDose, (void**)&dG, (void**)&dVec, (void**)&dHistory, (void**)&dValues, (void**)&dPart, (void**)&dState,
-                         (void**)&dGradS, (void**)&dScenValues, (void**)&dRobust})
+                         (void**)&dGradS, (void**)&dScenValues, (void**)&dRobust, (void**)&dActive})
             if (*p) { (void)hipFree(*p); *p = nullptr; }
         for (size_t s = 1; s < doseS.size(); ++s) { if (doseS[s]) (void)hipFree(doseS[s]); if (s < gS.size() && gS[s]) (void)hipFree(gS[s]); }
         doseS.clear(); gS.clear();
@@ -2036,6 +2040,24 @@ int evalObjective(rtd_handle_impl* h, rtd_objective_impl* o, const float* dDose,
     } else if (o->nBlocks)
         k_obj_eval<false><<<(unsigned)o->nBlocks, 256, 0, h->stream>>>((const int*)o->dUv, (const int*)o->dTPtr, (const unsigned char*)o->dTIdx,
                                                                        (const ObjTerm*)o->dTerms, nTerms, o->nU, dDose, dGrad, o->dPartial, o->nBlocks, nullptr);
+    k_obj_reduce<<<1, 256, 0, h->stream>>>((const double*)o->dPartial, o->nBlocks, (const ObjTerm*)o->dTerms, nTerms, dValues);
+    RTD_HIP(h, hipGetLastError());
+    return RTD_OK;
+}
+
+// eval_voxelwise without the null-pointer checks of the entry point: a clear of the word and two launches once the tables exist.
+int evalVoxelwise(rtd_handle_impl* h, rtd_objective_impl* o, const float* const* dDoses, int nScen, double* dValues, float* const* dGrads, unsigned* dActive) {
+    if (o->hasDvhTerms()) return fail(h, RTD_ERR_INVALID_ARG, "rtd_objective_eval_voxelwise: an objective with DVH terms has no voxel-wise worst case");
+    if (!o->built) { const int st = buildObjective(h, o); if (st != RTD_OK) return st; }
+    VoxelwiseVols a{};
+    const int padded = (nScen + kVoxelwiseUnroll - 1) / kVoxelwiseUnroll * kVoxelwiseUnroll;
+    for (int s = 0; s < padded; ++s) a.dose[s] = dDoses[s < nScen ? s : 0];
+    for (int s = 0; s < nScen; ++s) a.g[s] = dGrads[s];
+    const int nTerms = (int)o->terms.size();
+    RTD_HIP(h, hipMemsetAsync(dActive, 0, sizeof(unsigned), h->stream));
+    if (o->nBlocks)
+        k_obj_eval_voxelwise<<<(unsigned)o->nBlocks, 256, 0, h->stream>>>(a, nScen, (const int*)o->dUv, (const int*)o->dTPtr, (const unsigned char*)o->dTIdx,
+                                                                          (const ObjTerm*)o->dTerms, nTerms, o->nU, o->dPartial, o->nBlocks, dActive);
     k_obj_reduce<<<1, 256, 0, h->stream>>>((const double*)o->dPartial, o->nBlocks, (const ObjTerm*)o->dTerms, nTerms, dValues);
     RTD_HIP(h, hipGetLastError());
     return RTD_OK;
@@ -2263,6 +2285,38 @@ int rtd_objective_eval(rtd_handle hh, rtd_objective oo, const float* dev_dose, d
     return evalObjective(h, o, dev_dose, dev_values, dev_voxel_grad);
 }
 
+int rtd_objective_eval_voxelwise(rtd_handle hh, rtd_objective oo, const float* const* dev_doses, uint32_t n_scenarios, double* dev_values,
+                                 float* const* dev_voxel_grads, uint32_t* dev_active) {
+    auto* h = reinterpret_cast<rtd_handle_impl*>(hh);
+    auto* o = reinterpret_cast<rtd_objective_impl*>(oo);
+    if (!h) return RTD_ERR_INVALID_ARG;
+    if (!o || !dev_doses || !dev_values || !dev_voxel_grads || !dev_active) return fail(h, RTD_ERR_INVALID_ARG, "rtd_objective_eval_voxelwise: null pointer");
+    if (n_scenarios < 1 || n_scenarios > RTD_ROBUST_MAX_SCENARIOS) return fail(h, RTD_ERR_INVALID_ARG, "rtd_objective_eval_voxelwise: 1 to 32 scenarios");
+    for (uint32_t s = 0; s < n_scenarios; ++s)
+        if (!dev_doses[s] || !dev_voxel_grads[s]) return fail(h, RTD_ERR_INVALID_ARG, "rtd_objective_eval_voxelwise: null pointer");
+    if (o->terms.empty()) return fail(h, RTD_ERR_INVALID_ARG, "rtd_objective_eval_voxelwise: the objective has no terms");
+    RTD_HIP(h, hipSetDevice(h->device));
+    return evalVoxelwise(h, o, dev_doses, (int)n_scenarios, dev_values, dev_voxel_grads, dev_active);
+}
+
+int rtd_scenario_dose_extremes(rtd_handle hh, const float* const* dev_doses, uint32_t n_scenarios, size_t n_voxels, float* dev_min, float* dev_max) {
+    auto* h = reinterpret_cast<rtd_handle_impl*>(hh);
+    if (!h) return RTD_ERR_INVALID_ARG;
+    if (!dev_doses || (!dev_min && !dev_max)) return fail(h, RTD_ERR_INVALID_ARG, "rtd_scenario_dose_extremes: null pointer");
+    if (n_scenarios < 1 || n_scenarios > RTD_ROBUST_MAX_SCENARIOS) return fail(h, RTD_ERR_INVALID_ARG, "rtd_scenario_dose_extremes: 1 to 32 scenarios");
+    for (uint32_t s = 0; s < n_scenarios; ++s)
+        if (!dev_doses[s]) return fail(h, RTD_ERR_INVALID_ARG, "rtd_scenario_dose_extremes: null pointer");
+    const size_t nBlocks = (n_voxels + 255) / 256;
+    if (!n_voxels || nBlocks > (size_t)0x7fffffff) return fail(h, RTD_ERR_INVALID_ARG, "rtd_scenario_dose_extremes: 1 to 2^31 - 1 blocks of 256 voxels");
+    RTD_HIP(h, hipSetDevice(h->device));
+    VoxelwiseDoses a{};
+    const uint32_t padded = (n_scenarios + kVoxelwiseUnroll - 1) / kVoxelwiseUnroll * kVoxelwiseUnroll;
+    for (uint32_t s = 0; s < padded; ++s) a.dose[s] = dev_doses[s < n_scenarios ? s : 0];
+    k_dose_extremes<<<(unsigned)nBlocks, 256, 0, h->stream>>>(a, (int)n_scenarios, n_voxels, dev_min, dev_max);
+    RTD_HIP(h, hipGetLastError());
+    return RTD_OK;
+}
+
 int rtd_objective_destroy(rtd_handle hh, rtd_objective oo) {
     auto* h = reinterpret_cast<rtd_handle_impl*>(hh);
     auto* o = reinterpret_cast<rtd_objective_impl*>(oo);
@@ -2281,9 +2335,10 @@ void rtd_default_optimizer_options(rtd_optimizer_options* o) {
 }
 
 namespace {
-// rtd_optimizer_create (robust == nullptr: one scenario, nothing of section 14 allocated or launched) and rtd_optimizer_create_robust.
+// rtd_optimizer_create (robust == nullptr: one scenario, nothing of section 14 allocated or launched), rtd_optimizer_create_robust and
+// rtd_optimizer_create_voxelwise (voxelwise: what a robust optimiser owns plus the word of active scenarios; robust->mode is not read).
 int optCreate(rtd_handle hh, const rtd_field* fields, uint32_t n_fields, const rtd_robust_options* robust, rtd_objective oo,
-              const rtd_optimizer_options* opt, rtd_optimizer* out) {
+              const rtd_optimizer_options* opt, rtd_optimizer* out, bool voxelwise = false) {
     auto* h = reinterpret_cast<rtd_handle_impl*>(hh);
     auto* o = reinterpret_cast<rtd_objective_impl*>(oo);
     if (!h) return RTD_ERR_INVALID_ARG;
@@ -2291,7 +2346,7 @@ int optCreate(rtd_handle hh, const rtd_field* fields, uint32_t n_fields, const r
     *out = nullptr;
     const uint32_t nScen = robust ? robust->n_scenarios : 1;
     if (robust) {
-        if (robust->mode != RTD_ROBUST_EXPECTED && robust->mode != RTD_ROBUST_WORST_CASE) return fail(h, RTD_ERR_INVALID_ARG, "rtd_optimizer_create_robust: unknown mode");
+        if (!voxelwise && robust->mode != RTD_ROBUST_EXPECTED && robust->mode != RTD_ROBUST_WORST_CASE) return fail(h, RTD_ERR_INVALID_ARG, "rtd_optimizer_create_robust: unknown mode");
         if (nScen < 1 || nScen > RTD_ROBUST_MAX_SCENARIOS) return fail(h, RTD_ERR_INVALID_ARG, "rtd_optimizer_create_robust: 1 to 32 scenarios");
         if (robust->probabilities)
             for (uint32_t sc = 0; sc < nScen; ++sc)
@@ -2320,6 +2375,7 @@ int optCreate(rtd_handle hh, const rtd_field* fields, uint32_t n_fields, const r
         }
     }
     if (o->terms.empty()) return fail(h, RTD_ERR_INVALID_ARG, "rtd_optimizer_create: the objective has no terms");
+    if (voxelwise && o->hasDvhTerms()) return fail(h, RTD_ERR_INVALID_ARG, "rtd_optimizer_create_voxelwise: an objective with DVH terms has no voxel-wise worst case");
     for (uint32_t i = 0; i < nAll; ++i)
         if (!reinterpret_cast<rtd_field_impl*>(fields[i])->dijDone)
             return fail(h, RTD_ERR_NOT_READY, "rtd_optimizer_create: a field has no dose-influence matrix (call rtd_field_dose_influence first)");
@@ -2329,7 +2385,7 @@ int optCreate(rtd_handle hh, const rtd_field* fields, uint32_t n_fields, const r
     auto* p = new rtd_optimizer_impl();
     p->obj = o; p->opt = op; p->nVox = o->nVox;
     if (robust) {
-        p->robust = true; p->nScen = (int)nScen; p->mode = robust->mode;
+        p->robust = true; p->nScen = (int)nScen; p->mode = robust->mode; p->voxelwise = voxelwise;
         p->batch = std::getenv("RTD_ROBUST_NO_BATCH") == nullptr;      // read once, here (the convention of the engine switches)
         for (uint32_t i = 0; i < nAll; ++i) p->sfields.push_back(reinterpret_cast<rtd_field_impl*>(fields[i]));
     }
@@ -2384,6 +2440,10 @@ int optCreate(rtd_handle hh, const rtd_field* fields, uint32_t n_fields, const r
         if (e == hipSuccess) e = hipMemsetAsync(p->dScenValues, 0, valBytes, s);
         for (uint32_t sc = 0; sc < nScen; ++sc) rs0.prob[sc] = robust->probabilities ? robust->probabilities[sc] : 1.0 / (double)nScen;
         if (e == hipSuccess) e = hipMemcpyAsync(p->dRobust, &rs0, sizeof rs0, hipMemcpyHostToDevice, s);
+        if (voxelwise) {
+            if (e == hipSuccess) e = hipMalloc((void**)&p->dActive, sizeof(unsigned));
+            if (e == hipSuccess) e = hipMemsetAsync(p->dActive, 0, sizeof(unsigned), s);
+        }
     }
     if (e == hipSuccess) e = hipStreamSynchronize(s);                 // (st0 and rs0 live on this stack)
     if (e != hipSuccess) { (void)hipStreamSynchronize(s); p->freeAll(); delete p; RTD_HIP(h, e); }
@@ -2404,6 +2464,16 @@ int rtd_optimizer_create_robust(rtd_handle hh, const rtd_field* fields, uint32_t
     if (!robust) return fail(h, RTD_ERR_INVALID_ARG, "rtd_optimizer_create_robust: null pointer");
     if (out) *out = nullptr;
     return optCreate(hh, fields, n_fields, robust, oo, opt, out);
+}
+
+int rtd_optimizer_create_voxelwise(rtd_handle hh, const rtd_field* fields, uint32_t n_fields, uint32_t n_scenarios, rtd_objective oo,
+                                   const rtd_optimizer_options* opt, rtd_optimizer* out) {
+    auto* h = reinterpret_cast<rtd_handle_impl*>(hh);
+    if (!h) return RTD_ERR_INVALID_ARG;
+    if (out) *out = nullptr;
+    rtd_robust_options ro{};
+    ro.mode = RTD_ROBUST_EXPECTED; ro.n_scenarios = n_scenarios;
+    return optCreate(hh, fields, n_fields, &ro, oo, opt, out, true);
 }
 
 // f_s, lambda_s and the worst scenario of the iterate f_last belongs to. A plain optimiser is a set of one scenario.
@@ -2467,6 +2537,15 @@ int rtd_optimizer_run(rtd_handle hh, rtd_optimizer pp, uint32_t n_iterations) {
             st = optForward(hh, h, p);                                                    // 1.
             if (st == RTD_OK) st = evalObjective(h, p->obj, p->dDose, p->dValues, p->dG); // 2.
             if (st == RTD_OK) st = optAdjoint(hh, p);                                     // 3.
+        } else if (p->voxelwise) {                                                        // section 15, steps 1.-5.
+            st = robustForward(hh, h, p);
+            if (st == RTD_OK) st = evalVoxelwise(h, p->obj, p->doseS.data(), p->nScen, p->dValues, p->gS.data(), p->dActive);
+            if (st == RTD_OK) {
+                k_voxelwise_decide<<<1, 64, 0, s>>>((const unsigned*)p->dActive, p->nScen, p->dRobust, p->dValues);
+                st = robustAdjoint(hh, h, p);
+            }
+            if (st == RTD_OK)
+                k_robust_combine<<<(unsigned)((p->n + 255) / 256), 256, 0, s>>>((const float*)p->dGradS, (const RobustState*)p->dRobust, p->nScen, p->n, p->grad());
         } else {                                                                          // section 14, steps 1.-5.
             st = robustForward(hh, h, p);
             for (int sc = 0; sc < p->nScen && st == RTD_OK; ++sc)

@@ -106,6 +106,9 @@ def lib():
         L.rtd_optimizer_create_robust.argtypes = [vp, vpp, C.c_uint32, C.POINTER(abi.RtdRobustOptions), vp, C.POINTER(abi.RtdOptimizerOptions), vpp]
         L.rtd_optimizer_scenario_values.argtypes = [vp, vp, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int32)]
         L.rtd_optimizer_scenario_dose.argtypes = [vp, vp, C.c_uint32, vpp]
+        L.rtd_objective_eval_voxelwise.argtypes = [vp, vp, vpp, C.c_uint32, vp, vpp, vp]
+        L.rtd_scenario_dose_extremes.argtypes = [vp, vpp, C.c_uint32, C.c_size_t, vp, vp]
+        L.rtd_optimizer_create_voxelwise.argtypes = [vp, vpp, C.c_uint32, C.c_uint32, vp, C.POINTER(abi.RtdOptimizerOptions), vpp]
         L.rtd_host_register.argtypes = [vp, C.c_size_t]
         L.rtd_host_unregister.argtypes = [vp]
         L.rtd_plan_create.argtypes = [C.POINTER(C.c_int), C.c_int, vpp]
@@ -409,6 +412,32 @@ class Objective:
                 self.eng.device_free(dv)
         return None
 
+    def eval_voxelwise(self, dose_ptrs, grad_ptrs, dev_values=None, dev_active=None):
+        """rtd_objective_eval_voxelwise: the composite (voxel-wise worst case) objective of the scenario volumes dose_ptrs (device
+        pointers of float32 volumes, at most abi.RTD_ROBUST_MAX_SCENARIOS), its voxel gradient scattered over the volumes grad_ptrs
+        (one per scenario, zeroed once by the caller: only the voxels of the ROIs are written). With dev_values (float64[1 + n_terms])
+        and dev_active (one uint32), both device pointers, asynchronous, returns None; without, returns (values float64 array,
+        active mask: bit s set iff scenario s received a gradient that is not zero)."""
+        doses, grads = [int(p) for p in dose_ptrs], [int(p) for p in grad_ptrs]
+        if len(doses) != len(grads):
+            raise ValueError("one gradient volume per scenario")
+        own = dev_values is None or dev_active is None
+        nv = 8 * (1 + abi.RTD_OBJ_MAX_TERMS)
+        buf = self.eng.device_alloc(nv + 8) if own else None
+        dv, da = (buf, buf + nv) if own else (dev_values, dev_active)
+        try:
+            self.eng._check(lib().rtd_objective_eval_voxelwise(self.eng._h, self._h, (C.c_void_p * max(1, len(doses)))(*doses), len(doses), C.c_void_p(int(dv)),
+                                                               (C.c_void_p * max(1, len(grads)))(*grads), C.c_void_p(int(da))))
+            if own:
+                out, active = np.empty(1 + self.n_terms, dtype=np.float64), np.zeros(1, dtype=np.uint32)
+                self.eng.to_host(out, dv)
+                self.eng.to_host(active, da)
+                return out, int(active[0])
+        finally:
+            if own:
+                self.eng.device_free(buf)
+        return None
+
     def destroy(self):
         if self._h:
             lib().rtd_objective_destroy(self.eng._h, self._h)
@@ -419,9 +448,10 @@ class Optimizer:
     """rtd_optimizer_*: the resident spectral projected gradient iteration on an Objective of the dose of `fields` (each with a
     dose_influence() matrix). Destroy it before its fields, its objective and its engine."""
 
-    def __init__(self, eng, fields, objective, options=None, scenario_fields=None, mode=None, probabilities=None):
+    def __init__(self, eng, fields, objective, options=None, scenario_fields=None, mode=None, probabilities=None, voxelwise=False):
         """scenario_fields (a list of per-scenario field lists, scenario 0 the nominal one) makes it a robust optimiser
-        (rtd_optimizer_create_robust) in mode abi.RTD_ROBUST_EXPECTED / _WORST_CASE; `fields` is then ignored."""
+        (rtd_optimizer_create_robust) in mode abi.RTD_ROBUST_EXPECTED / _WORST_CASE, or with voxelwise=True the voxel-wise worst case
+        (rtd_optimizer_create_voxelwise; mode and probabilities are then not used); `fields` is then ignored."""
         self.eng = eng
         self.objective = objective
         self._h = C.c_void_p()
@@ -439,6 +469,9 @@ class Optimizer:
             raise ValueError("every scenario needs the same number of fields")
         flat = [f._h for fs in self.scenario_fields for f in fs]
         arr = (C.c_void_p * max(1, len(flat)))(*flat)
+        if voxelwise:
+            eng._check(lib().rtd_optimizer_create_voxelwise(eng._h, arr, n_fields, len(self.scenario_fields), objective._h, po, C.byref(self._h)))
+            return
         ro = abi.RtdRobustOptions()
         ro.mode = int(abi.RTD_ROBUST_EXPECTED if mode is None else mode)
         ro.n_scenarios = len(self.scenario_fields)
@@ -608,6 +641,19 @@ class Engine:
         """rtd_optimizer_create_robust: scenario_fields is a list of per-scenario field lists (scenario 0 the nominal one, every field
         with a dose_influence() matrix); mode abi.RTD_ROBUST_EXPECTED or abi.RTD_ROBUST_WORST_CASE. See raytracedicom_amd.robust."""
         return Optimizer(self, None, objective, options, scenario_fields=scenario_fields, mode=mode, probabilities=probabilities)
+
+    def create_voxelwise_optimizer(self, scenario_fields, objective, options=None):
+        """rtd_optimizer_create_voxelwise: the voxel-wise worst case over the scenarios (every voxel takes, per term, the scenario
+        dose that is worst for it). scenario_fields as create_robust_optimizer; the objective must not have DVH terms."""
+        return Optimizer(self, None, objective, options, scenario_fields=scenario_fields, voxelwise=True)
+
+    def dose_extremes(self, dose_ptrs, n_voxels, d_min=None, d_max=None):
+        """rtd_scenario_dose_extremes: d_min[v] / d_max[v] (device pointers of float32[n_voxels], either may be None) = the smallest /
+        largest of the scenario volumes dose_ptrs at v; asynchronous. Point Objective.dvh and .dose_at_volume at them for worst-case
+        DVH bands."""
+        doses = [int(p) for p in dose_ptrs]
+        self._check(lib().rtd_scenario_dose_extremes(self._h, (C.c_void_p * max(1, len(doses)))(*doses), len(doses), int(n_voxels),
+                                                     C.c_void_p(int(d_min)) if d_min else None, C.c_void_p(int(d_max)) if d_max else None))
 
     def transfer_fields_init(self, fields, dev_dose, box_min=None, box_max=None):
         """rtd_fields_transfer_init: every voxel of the inclusive dose-index box is written with 0 + fields[0] + fields[1] + ...
