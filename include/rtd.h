@@ -747,6 +747,88 @@ int rtd_optimizer_create_voxelwise(rtd_handle h, const rtd_field* fields /* [n_s
                                    const rtd_optimizer_options* o, rtd_optimizer* out);
 
 /*
+ * ---- RT Structure Set contours -> ROI voxel lists ----
+ *
+ * Additive to the blocks above (RTD_ABI_VERSION stays 3). Everything above begins at rtd_objective_add_roi, which takes strictly
+ * ascending linear voxel indices of the dose grid; this block makes such a list from the closed planar contours of a structure
+ * (rtd_dicom::readStructureSet and rtd_dicom::flatten of include/rtd_dicom.hpp deliver them). The mask is decided by comparisons of
+ * float64 values and by integer counting only: the same inputs give the same bits across calls, handles and processes, and the rule can
+ * be restated in a few lines (tests/roi_reference.py does).
+ *
+ * Inputs. rtd_roi_grid: the dims of the dose grid, the affine that takes a point in mm to (fractional) voxel indices (i, j, k) of
+ * that grid (voxel centres at the integers), and the thickness in mm of the slab a contour plane stands for (the spacing of the
+ * contoured image's slices). rtd_contour_set: n_contours closed polygons; contour c owns the points offsets[c] .. offsets[c + 1] - 1 of
+ * `points` (xyz in mm, host memory); the last point closes to the first.
+ *
+ * Transform (host, float64, the float32 inputs widened, every product and sum rounded, nothing contracted), for a point (x, y, z):
+ *     u  = ((m[0] x + m[1] y) + m[2] z) + v[0]        v = ((m[3] x + m[4] y) + m[5] z) + v[1]        kc = ((m[6] x + m[7] y) + m[8] z) + v[2]
+ * Planarity: a contour's plane coordinate is the kc of its first point; the call is refused if any of its points differs from that
+ *     by more than 1e-3 (slices).
+ * Planes: the contours sorted stably by plane coordinate; a new plane starts when a contour's coordinate exceeds the coordinate of the
+ *     plane's FIRST contour by more than 1e-3. kc_p is the coordinate of plane p's first contour.
+ * Slice assignment: slab = double(plane_thickness_mm) * sqrt((m[6] m[6] + m[7] m[7]) + m[8] m[8]) (slices). Slice k takes the plane p
+ *     that minimises |k - kc_p|, a tie going to the lower kc_p, and only if |k - kc_p| <= slab / 2; otherwise the slice takes no plane.
+ * Inside test: even-odd over ALL edges a -> b of ALL contours of the slice's plane (nested contours are holes, overlapping contours
+ *     XOR: the RTSTRUCT convention). For row j and edge a -> b in (u, v):
+ *         no crossing when (av <= j) == (bv <= j); otherwise t = (j - av) / (bv - av), xc = au + t * (bu - au),
+ *     every operation rounded to float64, nothing contracted; voxel i of the row is flipped iff double(i) < xc. Voxel (i, j, k) is in the
+ *     ROI iff it was flipped an odd number of times. No other number enters: a vertex on a row, a horizontal edge on a row and a
+ *     crossing exactly on a voxel centre are decided by these comparisons alone.
+ *
+ * rtd_roi_rasterize   synchronous set-up call (allocations, copies and a wait). The result owns its device memory, like an objective:
+ *                     the packed mask of the covered slices and the voxel list. A structure that covers no voxel is a valid result
+ *                     (n_voxels == 0); rtd_objective_add_roi goes on refusing an empty list.
+ * rtd_roi_get_info    n_voxels; the inclusive bounding box of the voxels in (i, j, k) (all zero when n_voxels == 0); the number of
+ *                     planes; the number of slices that took a plane.
+ * rtd_roi_voxels      the list in host memory: linear indices (k ny + j) nx + i, strictly ascending. capacity (in entries) must be at
+ *                     least n_voxels. Synchronous.
+ * rtd_roi_device      the list on the device (owned by the ROI, valid until rtd_roi_destroy) and its length.
+ * rtd_roi_fill_mask   dev_mask: dims[0] dims[1] dims[2] bytes on the device, x fastest; EVERY byte is written, 1 inside and 0 outside.
+ *                     One launch on the handle's stream.
+ * rtd_roi_kernel_ms   the time of the kernels of rtd_roi_rasterize that made this ROI (hipEvents on the handle's stream), for reports.
+ *
+ * Kernels (rtd_roi.hpp): per covered slice and group of rows the crossings toggle bits of a per-row difference mask in LDS (integer
+ * atomicXor, order-free); a suffix XOR over the bits gives the row mask, stored packed; a popcount per row, an exclusive integer scan over
+ * the rows in (k, j) order and an emit of the set bits give the list ascending without a sort. Slices without a plane launch nothing.
+ * The only atomics are integer XOR / min / max; there are no float atomics.
+ *
+ * RTD_ERR_INVALID_ARG, after which every object stays usable: a null pointer, a zero dimension or more than 2^31 - 1 voxels,
+ * n_contours == 0, a contour with fewer than 3 points, offsets that are not ascending, more than 2^31 - 1 points, a coordinate or
+ * matrix entry that is not finite, plane_thickness_mm not positive and finite, a contour that is not planar in the grid's k, a capacity
+ * below n_voxels.
+ */
+typedef struct rtd_roi_grid {
+    uint32_t dims[3];
+    rtd_affine world_to_idx;      /* mm -> voxel index (i, j, k) of the dose grid */
+    float plane_thickness_mm;     /* > 0 */
+    int32_t reserved[3];
+} rtd_roi_grid;
+
+typedef struct rtd_contour_set {
+    const float* points;          /* host, xyz mm */
+    const uint32_t* offsets;      /* host, n_contours + 1, ascending */
+    uint32_t n_contours;
+    int32_t reserved[3];
+} rtd_contour_set;
+
+typedef struct rtd_roi_info {
+    uint64_t n_voxels;
+    uint32_t box_lo[3], box_hi[3];   /* inclusive, (i, j, k) */
+    uint32_t n_planes, n_slices_covered;
+    int32_t reserved[2];
+} rtd_roi_info;
+
+typedef struct rtd_roi_s* rtd_roi;
+
+int rtd_roi_rasterize(rtd_handle h, const rtd_roi_grid* grid, const rtd_contour_set* contours, rtd_roi* out);
+int rtd_roi_get_info(rtd_handle h, rtd_roi roi, rtd_roi_info* info);
+int rtd_roi_voxels(rtd_handle h, rtd_roi roi, int32_t* host_out, size_t capacity);
+int rtd_roi_device(rtd_handle h, rtd_roi roi, const int32_t** dev_voxels, size_t* n);
+int rtd_roi_fill_mask(rtd_handle h, rtd_roi roi, uint8_t* dev_mask);
+int rtd_roi_kernel_ms(rtd_handle h, rtd_roi roi, float* ms);
+int rtd_roi_destroy(rtd_handle h, rtd_roi roi);
+
+/*
  * ---- Multi-GPU plans behind the boundary (SURVEY.md 8(b) "Threading": one handle and one host thread per device) ----
  *
  * rtd_plan is the reference-shaped call on several GPUs of one process: the 4-beam cudaWrapperProtons of the C++ shim uses

@@ -1,5 +1,5 @@
-// rtd_dicom.hpp — minimal DICOM input for the dose engine: a CT series and an RT Ion Plan, without
-// ITK / GDCM / dicom-interface (none of which exist on the target image).
+// rtd_dicom.hpp — minimal DICOM input for the dose engine: a CT series, an RT Ion Plan and an RT Structure
+// Set, without ITK / GDCM / dicom-interface (none of which exist on the target image).
 //
 // What the reference gets from those libraries and what is rebuilt here:
 //   * itk_reader (src/dicom_reader.cpp:15-129): first series of a directory, slices stacked along the slice normal, pixels
@@ -71,6 +71,9 @@ inline bool knownSequence(uint32_t t) {
     switch (t) {
         case 0x300A03A2u: case 0x300A03A8u: case 0x300A00B0u: case 0x300A0070u: case 0x300C0004u: case 0x300A0010u:
         case 0x300A03A4u: case 0x300A03ACu: case 0x300A0314u: case 0x300A0360u: case 0x300A0342u: case 0x300A00B6u:
+        // RT Structure Set: StructureSetROI, ROIContour, Contour, ContourImage, RTROIObservations, ReferencedFrameOfReference and below
+        case 0x30060020u: case 0x30060039u: case 0x30060040u: case 0x30060016u: case 0x30060080u: case 0x30060010u: case 0x30060012u:
+        case 0x30060014u:
             return true;
         default: return false;
     }
@@ -343,6 +346,80 @@ inline PlanBeam readPlanBeam(const File& plan, const std::string& beamName) {
         return out;
     }
     throw std::runtime_error(plan.path + ": no beam named " + beamName);
+}
+
+// ---- RT Structure Set -> the closed planar contours of every ROI ----
+// StructureSetROISequence (3006,0020) names the ROIs (ROINumber (3006,0022), ROIName (3006,0026)); ROIContourSequence (3006,0039) holds,
+// per ReferencedROINumber (3006,0084), the ContourSequence (3006,0040) with ContourGeometricType (3006,0042), NumberOfContourPoints
+// (3006,0046) and ContourData (3006,0050: x\y\z triplets in mm, patient coordinates). Only CLOSED_PLANAR contours are kept; the
+// others (POINT, OPEN_PLANAR, ...) are counted in `skipped`.
+struct StructureContour { std::vector<float> points; };               // xyz, xyz, ...
+struct Structure {
+    int number = 0;
+    std::string name;
+    std::vector<StructureContour> contours;
+    unsigned int skipped = 0;
+};
+// What rtd_contour_set takes (include/rtd.h): the points of all contours, and where each contour starts.
+struct FlatContours {
+    std::vector<float> points;
+    std::vector<uint32_t> offsets;                                     // contours + 1
+    uint32_t nContours = 0;
+};
+
+inline std::vector<Structure> readStructureSet(const std::string& path) {
+    const File f = readFile(path);
+    const std::string modality = str(f.find(tag(0x0008, 0x0060)));
+    if (modality != "RTSTRUCT") throw std::runtime_error(path + ": Unknown modality " + modality);
+    const Element* rois = f.find(tag(0x3006, 0x0020));
+    if (!rois) throw std::runtime_error(path + ": no StructureSetROISequence (not an RT Structure Set)");
+    auto get = [](const Dataset& d, uint16_t g, uint16_t e) -> const Element* { auto it = d.find(tag(g, e)); return it == d.end() ? nullptr : &it->second; };
+    std::vector<Structure> out;
+    std::map<int, size_t> byNumber;
+    for (const Dataset& r : rois->items) {
+        const std::vector<double> num = numbers(get(r, 0x3006, 0x0022));
+        if (num.size() != 1) throw std::runtime_error(path + ": a structure set ROI without ROINumber");
+        Structure s;
+        s.number = (int)num[0];
+        s.name = str(get(r, 0x3006, 0x0026));
+        if (byNumber.count(s.number)) throw std::runtime_error(path + ": ROI number " + std::to_string(s.number) + " appears twice");
+        byNumber[s.number] = out.size();
+        out.push_back(std::move(s));
+    }
+    if (const Element* rcs = f.find(tag(0x3006, 0x0039))) {
+        for (const Dataset& rc : rcs->items) {
+            const std::vector<double> ref = numbers(get(rc, 0x3006, 0x0084));
+            if (ref.size() != 1) throw std::runtime_error(path + ": a ROIContour without ReferencedROINumber");
+            const auto it = byNumber.find((int)ref[0]);
+            if (it == byNumber.end()) throw std::runtime_error(path + ": a ROIContour references the unknown ROI number " + std::to_string((int)ref[0]));
+            Structure& s = out[it->second];
+            const Element* seq = get(rc, 0x3006, 0x0040);
+            if (!seq) continue;                                        // an ROI without contours
+            for (const Dataset& c : seq->items) {
+                if (str(get(c, 0x3006, 0x0042)) != "CLOSED_PLANAR") { ++s.skipped; continue; }
+                const std::vector<double> n = numbers(get(c, 0x3006, 0x0046)), data = numbers(get(c, 0x3006, 0x0050));
+                if (data.size() % 3 != 0) throw std::runtime_error(path + ": ContourData of ROI " + s.name + " is not a list of xyz triplets");
+                if (n.size() != 1 || n[0] < 0 || (size_t)n[0] != data.size() / 3)
+                    throw std::runtime_error(path + ": NumberOfContourPoints disagrees with ContourData in ROI " + s.name);
+                StructureContour sc;
+                sc.points.reserve(data.size());
+                for (double d : data) sc.points.push_back((float)d);
+                s.contours.push_back(std::move(sc));
+            }
+        }
+    }
+    return out;
+}
+
+inline FlatContours flatten(const Structure& s) {
+    FlatContours fc;
+    fc.offsets.push_back(0u);
+    for (const StructureContour& c : s.contours) {
+        fc.points.insert(fc.points.end(), c.points.begin(), c.points.end());
+        fc.offsets.push_back((uint32_t)(fc.points.size() / 3));
+    }
+    fc.nContours = (uint32_t)s.contours.size();
+    return fc;
 }
 
 // ---- geometry of a plan beam in the DICOM patient coordinate system ----

@@ -144,6 +144,23 @@ class RtdRobustOptions(C.Structure):
     _fields_ = [("mode", C.c_int32), ("n_scenarios", C.c_uint32), ("probabilities", C.POINTER(C.c_double)), ("reserved", C.c_int32 * 4)]
 
 
+class RtdRoiGrid(C.Structure):
+    _fields_ = [("dims", C.c_uint32 * 3), ("world_to_idx", RtdAffine), ("plane_thickness_mm", C.c_float), ("reserved", C.c_int32 * 3)]
+
+
+class RtdContourSet(C.Structure):
+    _fields_ = [("points", c_float_p), ("offsets", C.POINTER(C.c_uint32)), ("n_contours", C.c_uint32), ("reserved", C.c_int32 * 3)]
+
+
+class RtdRoiInfo(C.Structure):
+    _fields_ = [("n_voxels", C.c_uint64), ("box_lo", C.c_uint32 * 3), ("box_hi", C.c_uint32 * 3), ("n_planes", C.c_uint32),
+                ("n_slices_covered", C.c_uint32), ("reserved", C.c_int32 * 2)]
+
+    def as_dict(self):
+        return {"n_voxels": int(self.n_voxels), "box_lo": list(self.box_lo), "box_hi": list(self.box_hi), "n_planes": int(self.n_planes),
+                "n_slices_covered": int(self.n_slices_covered)}
+
+
 def default_optimizer_options():
     """rtd_default_optimizer_options: the step bounds only keep the Barzilai-Borwein step finite."""
     o = RtdOptimizerOptions()

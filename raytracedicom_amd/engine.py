@@ -109,6 +109,13 @@ def lib():
         L.rtd_objective_eval_voxelwise.argtypes = [vp, vp, vpp, C.c_uint32, vp, vpp, vp]
         L.rtd_scenario_dose_extremes.argtypes = [vp, vpp, C.c_uint32, C.c_size_t, vp, vp]
         L.rtd_optimizer_create_voxelwise.argtypes = [vp, vpp, C.c_uint32, C.c_uint32, vp, C.POINTER(abi.RtdOptimizerOptions), vpp]
+        L.rtd_roi_rasterize.argtypes = [vp, C.POINTER(abi.RtdRoiGrid), C.POINTER(abi.RtdContourSet), vpp]
+        L.rtd_roi_get_info.argtypes = [vp, vp, C.POINTER(abi.RtdRoiInfo)]
+        L.rtd_roi_voxels.argtypes = [vp, vp, i3, C.c_size_t]
+        L.rtd_roi_device.argtypes = [vp, vp, vpp, C.POINTER(C.c_size_t)]
+        L.rtd_roi_fill_mask.argtypes = [vp, vp, vp]
+        L.rtd_roi_kernel_ms.argtypes = [vp, vp, C.POINTER(C.c_float)]
+        L.rtd_roi_destroy.argtypes = [vp, vp]
         L.rtd_host_register.argtypes = [vp, C.c_size_t]
         L.rtd_host_unregister.argtypes = [vp]
         L.rtd_plan_create.argtypes = [C.POINTER(C.c_int), C.c_int, vpp]
@@ -444,6 +451,61 @@ class Objective:
             self._h = C.c_void_p()
 
 
+class Roi:
+    """rtd_roi_*: the voxels of the dose grid inside the closed planar contours of one structure (Engine.rasterize_roi). voxels() is what
+    Objective.add_roi takes."""
+
+    def __init__(self, eng, dims, world_to_idx, contours, plane_thickness_mm):
+        self.eng = eng
+        self._h = C.c_void_p()
+        self.dims = tuple(int(d) for d in dims)
+        g = abi.RtdRoiGrid()
+        for i in range(3):
+            g.dims[i] = self.dims[i]
+        g.world_to_idx = world_to_idx if isinstance(world_to_idx, abi.RtdAffine) else abi.make_affine(*world_to_idx)
+        g.plane_thickness_mm = float(plane_thickness_mm)
+        cs = [np.ascontiguousarray(c, dtype=np.float32).reshape(-1, 3) for c in contours]
+        pts = np.ascontiguousarray(np.concatenate(cs, axis=0)) if cs else np.zeros((1, 3), dtype=np.float32)
+        offs = np.zeros(len(cs) + 1, dtype=np.uint32)
+        offs[1:] = np.cumsum([len(c) for c in cs], dtype=np.int64)
+        s = abi.RtdContourSet()
+        s.points = abi.fptr(pts)
+        s.offsets = offs.ctypes.data_as(C.POINTER(C.c_uint32))
+        s.n_contours = len(cs)
+        eng._check(lib().rtd_roi_rasterize(eng._h, C.byref(g), C.byref(s), C.byref(self._h)))
+        i = abi.RtdRoiInfo()
+        eng._check(lib().rtd_roi_get_info(eng._h, self._h, C.byref(i)))
+        self.info = i.as_dict()
+
+    def voxels(self):
+        """The linear voxel indices ((k ny + j) nx + i, strictly ascending) as a numpy int32 array."""
+        out = np.empty(self.info["n_voxels"], dtype=np.int32)
+        self.eng._check(lib().rtd_roi_voxels(self.eng._h, self._h, out.ctypes.data_as(C.POINTER(C.c_int32)), out.size))
+        return out
+
+    def device(self):
+        """(device pointer of the int32 list, its length); owned by the ROI."""
+        p, n = C.c_void_p(), C.c_size_t(0)
+        self.eng._check(lib().rtd_roi_device(self.eng._h, self._h, C.byref(p), C.byref(n)))
+        return int(p.value or 0), int(n.value)
+
+    def fill_mask(self, t):
+        """Writes the whole uint8 volume t (a device pointer, or anything with data_ptr(): a torch.uint8 tensor of the grid's size)
+        with 1 inside and 0 outside; asynchronous on the engine's stream."""
+        ptr = t.data_ptr() if hasattr(t, "data_ptr") else int(t)
+        self.eng._check(lib().rtd_roi_fill_mask(self.eng._h, self._h, C.c_void_p(ptr)))
+
+    def kernel_ms(self):
+        ms = C.c_float(0.0)
+        self.eng._check(lib().rtd_roi_kernel_ms(self.eng._h, self._h, C.byref(ms)))
+        return float(ms.value)
+
+    def close(self):
+        if self._h:
+            lib().rtd_roi_destroy(self.eng._h, self._h)
+            self._h = C.c_void_p()
+
+
 class Optimizer:
     """rtd_optimizer_*: the resident spectral projected gradient iteration on an Objective of the dose of `fields` (each with a
     dose_influence() matrix). Destroy it before its fields, its objective and its engine."""
@@ -633,6 +695,12 @@ class Engine:
 
     def create_objective(self, dose_dims):
         return Objective(self, dose_dims)
+
+    def rasterize_roi(self, dims, world_to_idx, contours, plane_thickness_mm):
+        """rtd_roi_rasterize: dims (x, y, z) of the dose grid; world_to_idx an abi.RtdAffine or (m 3x3, v 3) taking mm to voxel indices;
+        contours a list of (n, 3) arrays of xyz mm (closed polygons, each planar in the grid's k); plane_thickness_mm the slice spacing
+        of the contoured image. Returns a Roi."""
+        return Roi(self, dims, world_to_idx, contours, plane_thickness_mm)
 
     def create_optimizer(self, fields, objective, options=None):
         return Optimizer(self, fields, objective, options)
