@@ -1,0 +1,302 @@
+// rtd_engine_impl.hpp — what the host files of the engine share: the handle, a field with its buffer table, the owner of every
+// other device buffer, and the helpers around them. Part of rtd_engine.hip's translation unit: included there once, after the system
+// and kernel headers (the buffer table is sized with the kernels' constants) and ahead of the rtd_*_host.hpp files.
+#pragma once
+
+using namespace rtd;
+
+namespace {
+
+struct rtd_field_impl;
+
+struct rtd_handle_impl {
+    std::vector<rtd_field_impl*> fieldCache;   // released field objects whose device workspace the next field of the same shape takes over
+    int device = 0;
+    hipStream_t ownStream = nullptr;
+    hipStream_t stream = nullptr;
+    std::string error;
+    rtd_options opt{};
+    int numCUs = 256;             // compute units of the device (grid size of the grid-stride kernels)
+    std::map<const void*, size_t> ldsCaps;   // dynamic-LDS cap set so far, per kernel (raiseLdsCap)
+    unsigned inputEpoch = 0;      // bumped whenever CT, LUTs or options change (fields re-test what they learned about their input)
+    // LUTs
+    bool haveLuts = false;
+    std::vector<float> energiesPerU, peakDepths, scaleFacts;
+    float densityScale = 0, spScale = 0, rrlScale = 0;
+    float* dLutBlock = nullptr;   // one allocation: cidd | density | sp | rrl (| nuclear weight | nuclear sigma^2)
+    size_t lutBlockFloats = 0;
+    LutView lut{};
+    // CT
+    const float* dCt = nullptr;
+    float* dCtOwned = nullptr;
+    size_t ctOwnedVoxels = 0;     // size of dCtOwned: a CT of the same size is uploaded in place (no free + malloc of the volume)
+    uint32_t ctDims[3] = {0, 0, 0};
+    const float* ctHost = nullptr;                 // rtd_set_ct_deferred: the caller's volume, uploaded box by box as fields need it
+    struct CtBox { std::array<int, 6> box; hipEvent_t done; hipStream_t stream; };
+    std::vector<CtBox> ctBoxes;                    // boxes of ctHost already on the device (x0, y0, z0, x1, y1, z1 inclusive), each with the
+                                                   // event of its upload and the stream it was issued on (a consumer on another stream waits for it)
+    void clearCtBoxes() { for (auto& b : ctBoxes) if (b.done) (void)hipEventDestroy(b.done); ctBoxes.clear(); }
+};
+
+// The engine's RTD_* switches (diagnostics, and the second implementations the tests compare with): read once, when a field is
+// created. RTD_NO_UNIFORM_PATH, RTD_UNIFORM_V2, RTD_NO_SWEEP, RTD_SEPARATE_PLAN, RTD_SEPARATE_KS_PLAN, RTD_NO_TRACE_REUSE (every compute
+// traces and plans the field again), RTD_*_DEBUG (per-block clock stamps), and the overrides RTD_TRACE_MODE, RTD_TRACE_DIAG_B,
+// RTD_KS_GROUPS, RTD_SW_GROUPS.
+struct Switches {
+    bool noUniformPath = false, uniformV2 = false, noSweep = false, separatePlan = false, separateKsPlan = false, noTraceReuse = false;
+    bool scanDebug = false, fillDebug = false, uniformDebug = false, sweepDebug = false;
+    std::optional<int> traceMode, traceDiagB, ksGroups, swGroups;
+};
+
+Switches readSwitches() {
+    auto on = [](const char* name) { return std::getenv(name) != nullptr; };
+    auto num = [](const char* name) { const char* v = std::getenv(name); return v ? std::optional<int>(std::atoi(v)) : std::nullopt; };
+    return Switches{on("RTD_NO_UNIFORM_PATH"), on("RTD_UNIFORM_V2"), on("RTD_NO_SWEEP"), on("RTD_SEPARATE_PLAN"), on("RTD_SEPARATE_KS_PLAN"),
+                    on("RTD_NO_TRACE_REUSE"),
+                    on("RTD_SCAN_DEBUG"), on("RTD_FILL_DEBUG"), on("RTD_UNIFORM_DEBUG"), on("RTD_SWEEP_DEBUG"),
+                    num("RTD_TRACE_MODE"), num("RTD_TRACE_DIAG_B"), num("RTD_KS_GROUPS"), num("RTD_SW_GROUPS")};
+}
+
+// Classes of a field's device buffers: the workspace that a field of the same shape takes over (rtd_field_release), the NUCLEAR_CORR
+// halo, the spot-weight gradient's (allocated by its first call), the RTD_*_DEBUG clock stamps, the dose-influence matrix's workspace
+// and its result (rtd_field_dose_influence: allocated by its first call, the result replaced by every call; the result's class also
+// holds what rtd_field_dose_influence_prepare builds from it, so that the two are freed together).
+enum BufClass : unsigned { kShape = 1, kNuclear = 2, kGradient = 4, kDiag = 8, kDij = 16, kDijOut = 32, kAllBufs = 63 };
+
+struct rtd_field_impl {
+    Switches sw;
+    FieldConst fc{};
+    TracerParams tracer{};
+    FillGeom fillGeom{};
+    FromFan rayIdxToDoseIdx{};
+    TransferParams transfer0{};
+    int traceMode = 0;              // tracer: 0 lanes across the rays, 1 along the beam (CT x runs along it), 2 along diagonals of (ray, step) (oblique beams)
+    int traceDiagB = 0;             // ... mode 2: steps per ray along a diagonal
+    int transferMode = 0;           // transfer kernel: lanes of the BEV gathers along dose x (0), y (1) or z (2)
+    uint32_t doseDims[3] = {0, 0, 0};
+    size_t R = 0;
+    // device workspace (forEachBuffer lists every buffer with its size)
+    float *dSpotWeights = nullptr, *dConvInterm = nullptr, *dRayWeights = nullptr;
+    float *dDensity = nullptr, *dWepl = nullptr, *dRrl = nullptr, *dIdd = nullptr, *dRSigma = nullptr, *dBev = nullptr, *dBevPart = nullptr;
+    int* dNodeCount = nullptr;   // [output tile][step][32] arrival counters of the superposition's reduction tree (all zero between launches)
+    int *dFirstInside = nullptr, *dFirstOutside = nullptr, *dFirstPassive = nullptr, *dWeplMin = nullptr;
+    float* dBlockWeplMin = nullptr;   // [R/64][S] per scan block and step: smallest WEPL of the block's 64 rays
+    KsPlanArgs* dKsArgs = nullptr;    // the plan's arguments for a launch that plans for itself (k_superpose_sweep<true>): written at each such launch
+    float* dSegPos = nullptr;         // [S / kTraceSeg + 1][3][R] sample positions at the segment boundaries of k_trace_sample (walked once, at creation)
+    unsigned char* dTileRad = nullptr;
+    size_t tileRadWords = 0;
+    LayerPlan* dLayers = nullptr;
+    float* dStepTab = nullptr;
+    int* dActive = nullptr;      // [L][S][4] minima of (x, y, -x, -y) over rays with dose > 0
+    unsigned int *dSigMin = nullptr, *dSigMax = nullptr;   // [L][S] bits of the smallest / largest tile-uniform sigma^2 (uniform-sigma detection)
+    bool uniformEligible = false; // the separable superposition may take the field (no nuclear halo, BEV height within its accumulators)
+    int uniformHint = -1;         // what the last finished compute found: 0 heterogeneous, 1 one sigma per slice, -1 unknown
+    unsigned hintEpoch = 0;       // ... under this handle->inputEpoch
+    unsigned launchEpoch = 0;     // handle->inputEpoch when the compute in flight was launched (what its findings are valid for)
+    bool launchedKnownUniform = false;   // the compute in flight skipped the general superposition kernel on the strength of the hint
+    bool triedUniform = false;    // the compute in flight ran the detection
+    // The trace and the plan (density, WEPL, radiation length, entry / exit steps, WEPL minima, the plan's part of the state record and
+    // of the layer records) depend on CT, LUTs, options and geometry only, not on the spot weights: a compute under the inputs of a
+    // FINISHED compute that produced them launches neither the tracer nor the scan nor the plan (rtd_field_compute_bev).
+    bool traceLaunched = false;   // a compute that traces has been launched (not into a capturing stream) under traceEpoch
+    unsigned traceEpoch = 0;      // handle->inputEpoch of that launch
+    bool traceUsable = false;     // ... and a finished compute under that epoch has been seen without a device error (takeFindings)
+    bool launchedReuse = false;   // the compute in flight reused the trace: ev[1] is not recorded (rtd_field_fetch "trace_reused")
+    // NUCLEAR_CORR (default off): the halo on the spot-resolution grid
+    int* dNucSpotIdx = nullptr; float *dNucRayWeights = nullptr, *dNucIdd = nullptr, *dNucRs = nullptr, *dNucBev = nullptr;
+    int* dNucEffT = nullptr;
+    FieldState* dStateNuc = nullptr;
+    FromFan nucIdxToDoseIdx{};
+    TransferParams transfer0Nuc{};
+    int transferModeNuc = 0;
+    long long* dFillDbg = nullptr;       // RTD_FILL_DEBUG: per-block clock stamps of k_fill (diagnostics)
+    long long* dUniDbg = nullptr;        // RTD_UNIFORM_DEBUG: ... of k_superpose_uniform4
+    long long* dSweepDbg = nullptr;      // RTD_SWEEP_DEBUG: ... of k_superpose_sweep
+    long long* dSweepBigDbg = nullptr;   // ... and of k_superpose_sweep_big
+    long long* dScanDbg = nullptr;       // RTD_SCAN_DEBUG: ... of k_trace_scan
+    FieldState* dState = nullptr;
+    FieldState* hState = nullptr;      // pinned host mirror of *dState (written by k_ks_plan), and its device-side address
+    FieldState* dHostState = nullptr;
+    std::vector<LayerPlan> hLayers;
+    hipEvent_t ev[8] = {};       // 0..6 stage ends, 7 start of the superposition (its first launch)
+    bool selfPlanned = false;    // the last compute had no k_ks_plan launch: block 0 of k_superpose_sweep's launch was the plan (ev[4] not recorded)
+    bool computed = false;       // the BEV dose and the state record of the last rtd_field_compute[_bev] exist (or a slab is attached)
+    bool transferred = false;    // a transfer has been launched since (ev[6] is recorded)
+    bool remote = false;         // geometry only: the BEV slab comes from another GPU (rtd_field_attach_bev)
+    const unsigned char* attached = nullptr;   // remote: the packed message [FieldState | slab]
+    int ksGroups = 14;   // layer groups of the superposition (partial BEV buffers); RTD_KS_GROUPS overrides
+    // k_superpose_sweep (rtd_sweep.hpp): layer groups, patches of the ray grid, partial tiles [step][patch][group][96 x 96], arrival counters [step]
+    int swGroups = 4, swPX = 1, swPY = 1;
+    float* dSwSlots = nullptr; int* dSwCount = nullptr;
+    // k_superpose_sweep_big (rtd_sweep_big.hpp), the sources of batch radius 17 .. 32: its own layer groups, partial tiles [step][patch][group][128 x 128], counters
+    int bgGroups = kBgMaxGroups;
+    float* dSwSlotsBig = nullptr; int* dSwCountBig = nullptr;
+    int radiusHint = -1;          // largest batch radius the last finished compute found (-1 unknown), under hintEpoch like uniformHint
+    bool sweepEnabled = true;     // RTD_NO_SWEEP: every field through k_superpose_mfma
+    // spot-weight gradient (rtd_field_spot_gradient, rtd_adjoint.hpp): allocated by the first call, reused after it
+    float *dGradBev = nullptr, *dGradRw = nullptr, *dAdjPart = nullptr, *dAdjInterm = nullptr;
+    float4* dAdjWalk = nullptr;   // [chunk][L][H][W] the dose walk's state in front of every chunk of k_adj_superpose
+    bool gradDone = false;        // a gradient has been launched: grad_bev / grad_ray_weights hold the last one's intermediates
+    // dose-influence matrix (rtd_field_dose_influence, rtd_dij.hpp): workspace allocated by the first call; the batch-major staging
+    // (dijCap entries) grows geometrically; the CSC result (dijNnz entries) is replaced by every call
+    float *dDijSave = nullptr, *dDijDose = nullptr, *dDijValsB = nullptr, *dDijVals = nullptr;
+    unsigned short* dDijOwner = nullptr;
+    int *dDijFoot = nullptr, *dDijList = nullptr, *dDijBoxes = nullptr, *dDijCnt = nullptr, *dDijMisc = nullptr, *dDijRowsB = nullptr, *dDijRows = nullptr;
+    unsigned int* dDijColMax = nullptr;
+    long long *dDijColLen = nullptr, *dDijColSrc = nullptr, *dDijColPtr = nullptr;
+    size_t dijCap = 0, dijNnz = 0;
+    bool dijDone = false;          // the CSC buffers hold the last call's result
+    std::vector<int> dijBatchOf;   // per spot: its batch in the last call (-1: empty column); rtd_field_fetch "dij_batch"
+    // products with the matrix (rtd_field_dose_influence_prepare / _apply / _apply_t, rtd_dij_apply.hpp): the row-major companion over the
+    // voxels of dijBox (row pointers, columns ascending within a row, values) and the column chunks of the transposed product
+    long long* dDijRowPtr = nullptr; int* dDijCCols = nullptr; float* dDijCVals = nullptr;
+    int *dDijChunkFirst = nullptr, *dDijChunkCol = nullptr; float* dDijPartial = nullptr;
+    bool dijPrepared = false;      // the buffers above exist and belong to the CSC result
+    int dijOwnBox[6] = {0, 0, 0, -1, -1, -1};   // the field's dose box (min, max) when the matrix was computed
+    DijBox dijBox{};               // ... united with the bounding box of the matrix's rows: the voxels that have a row
+    size_t dijRowsN = 0, dijChunks = 0;
+    std::vector<size_t> released; // released: the element counts of its shape buffers (a new field takes it over if its own are the same)
+
+    bool uniform4() const { return fc.W <= 16 * (kU2XB - 4) && fc.W % 4 == 0 && !sw.uniformV2; }   // k_superpose_uniform4, else _uniform2
+
+    // Every device buffer of the field, once: visit(pointer, element count, class, cleared when allocated, rtd_field_fetch name or
+    // nullptr). A count of 0: the field has no such buffer. Allocation, takeover, release, destruction and fetch go through here.
+    template <typename V> void forEachBuffer(V&& visit) {
+        const size_t S = fc.S, L = fc.L, P = (size_t)fc.bevW * fc.bevH, tiles = (size_t)fc.tilesX * fc.tilesY;
+        const size_t mfma = sweepEnabled ? 0 : 1, sweep = 1 - mfma, nuc = fc.nuclearCorr ? 1 : 0, patches = S * swPX * swPY;
+        const size_t nOutTiles = (size_t)((fc.bevW + kKsTileX - 1) / kKsTileX) * ((fc.bevH + kKsTileY - 1) / kKsTileY);
+        const size_t nucR = (size_t)fc.nucW * fc.nucH, nucBev = (size_t)(fc.nucW + 2 * kMaxSuperpR) * (fc.nucH + 2 * kMaxSuperpR);
+        const size_t nucTiles = (size_t)(fc.nucW / kSuperpTileX) * (fc.nucH / kSuperpTileY);
+        const size_t nChunks = (S + kAdjChunk - 1) / kAdjChunk, nPartsU4 = ((fc.bevH + 15) / 16 + kU4RB - 1) / kU4RB;
+        visit(dSpotWeights, (size_t)fc.spotNx * fc.spotNy * L, kShape, false, nullptr);
+        visit(dConvInterm, (size_t)fc.W * fc.spotNy * L, kShape, false, nullptr);
+        visit(dRayWeights, R * L, kShape, false, "ray_weights");
+        visit(dDensity, R * S, kShape, false, "density"); visit(dWepl, R * S, kShape, false, "wepl"); visit(dRrl, R * S, kShape, false, nullptr);
+        visit(dIdd, R * S * L, kShape, false, "idd"); visit(dRSigma, R * S * L, kShape, false, "rsigma");
+        // (the transfer reads the slices [entry, passive) only, and the superposition's reduce writes every pixel of those: slices
+        //  outside hold stale values that nothing samples; a fresh buffer is cleared once so that a fetch of "bev" reads zeros there)
+        visit(dBev, P * S, kShape, true, "bev");
+        visit(dBevPart, mfma * nOutTiles * kKsTileX * kKsTileY * S * ksGroups, kShape, false, nullptr);
+        visit(dNodeCount, mfma * nOutTiles * S * 32, kShape, true, nullptr);
+        visit(dSwSlots, sweep * patches * swGroups * kSwSlot, kShape, false, nullptr); visit(dSwCount, sweep * S, kShape, true, nullptr);
+        visit(dSwSlotsBig, sweep * patches * bgGroups * kBgSlot, kShape, false, nullptr); visit(dSwCountBig, sweep * S, kShape, true, nullptr);
+        visit(dFirstInside, R, kShape, false, "first_inside"); visit(dFirstOutside, R, kShape, false, "first_outside");
+        visit(dFirstPassive, R * L, kShape, false, "first_passive");
+        visit(dWeplMin, S, kShape, false, "wepl_min"); visit(dBlockWeplMin, (R / 64) * S, kShape, false, nullptr);
+        visit(dSegPos, (S / kTraceSeg + 1) * 3 * R, kShape, false, nullptr);
+        visit(dKsArgs, (size_t)1, kShape, false, nullptr);
+        visit(dTileRad, tileRadWords * 4, kShape, false, "tile_radius");
+        visit(dLayers, L, kShape, false, nullptr); visit(dState, (size_t)1, kShape, false, nullptr); visit(dStepTab, 2 * S, kShape, false, nullptr);
+        visit(dActive, 4 * L * S, kShape, false, nullptr); visit(dSigMin, L * S, kShape, false, nullptr); visit(dSigMax, L * S, kShape, false, nullptr);
+        visit(dNucSpotIdx, nuc * R, kNuclear, false, nullptr); visit(dNucRayWeights, nucR * L, kNuclear, false, nullptr);
+        visit(dNucIdd, nucR * L, kNuclear, false, nullptr); visit(dNucRs, nucR * L, kNuclear, false, nullptr);
+        visit(dNucBev, nuc * nucBev, kNuclear, false, nullptr); visit(dNucEffT, nucTiles * L, kNuclear, false, nullptr);
+        visit(dStateNuc, nuc, kNuclear, false, nullptr);
+        visit(dGradBev, P * S, kGradient, false, "grad_bev"); visit(dGradRw, R * L, kGradient, false, "grad_ray_weights");
+        visit(dAdjPart, R * L * nChunks, kGradient, false, nullptr); visit(dAdjWalk, R * L * nChunks, kGradient, false, nullptr);
+        visit(dAdjInterm, L * fc.spotNy * fc.W, kGradient, false, nullptr);
+        const size_t nSpot = (size_t)fc.spotNx * fc.spotNy * L, dijSpots = std::min(nSpot, (size_t)kDijMaxSpots);
+        visit(dDijSave, nSpot, kDij, false, nullptr); visit(dDijDose, (size_t)doseDims[0] * doseDims[1] * doseDims[2], kDij, false, nullptr);
+        visit(dDijOwner, P, kDij, false, nullptr); visit(dDijFoot, 2 * L * (size_t)(fc.spotNx + fc.spotNy), kDij, false, nullptr);
+        visit(dDijList, nSpot, kDij, false, nullptr); visit(dDijBoxes, 4 * nSpot, kDij, false, nullptr);
+        visit(dDijCnt, (size_t)kDijBlocks * dijSpots, kDij, false, nullptr); visit(dDijColMax, dijSpots, kDij, false, nullptr);
+        visit(dDijMisc, (size_t)4, kDij, true, nullptr); visit(dDijColLen, nSpot, kDij, false, nullptr); visit(dDijColSrc, nSpot, kDij, false, nullptr);
+        visit(dDijRowsB, dijCap, kDij, false, nullptr); visit(dDijValsB, dijCap, kDij, false, nullptr);
+        visit(dDijColPtr, nSpot + 1, kDijOut, false, nullptr); visit(dDijRows, std::max<size_t>(dijNnz, 1), kDijOut, false, nullptr);
+        visit(dDijVals, std::max<size_t>(dijNnz, 1), kDijOut, false, nullptr);
+        const size_t ap = dijPrepared ? 1 : 0;   // (only after rtd_field_dose_influence_prepare)
+        visit(dDijRowPtr, ap * (dijRowsN + 1), kDijOut, false, nullptr); visit(dDijCCols, ap * std::max<size_t>(dijNnz, 1), kDijOut, false, nullptr);
+        visit(dDijCVals, ap * std::max<size_t>(dijNnz, 1), kDijOut, false, nullptr); visit(dDijChunkFirst, ap * (nSpot + 1), kDijOut, false, nullptr);
+        visit(dDijChunkCol, ap * std::max<size_t>(dijChunks, 1), kDijOut, false, nullptr);
+        visit(dDijPartial, ap * std::max<size_t>(dijChunks, 1), kDijOut, false, nullptr);
+        visit(dScanDbg, sw.scanDebug ? 8 * (R / 64) : 0, kDiag, true, "scan_debug");
+        visit(dFillDbg, sw.fillDebug ? 4 * 2 * tiles * L : 0, kDiag, false, "fill_debug");
+        visit(dUniDbg, sw.uniformDebug && uniformEligible && uniform4() ? 16 * S * nPartsU4 : 0, kDiag, true, "uniform_debug");
+        visit(dSweepDbg, sw.sweepDebug ? sweep * (8 + 4 * 16) * (patches * swGroups + 1) : 0, kDiag, true, "sweep_debug");
+        visit(dSweepBigDbg, sw.sweepDebug ? sweep * 48 * patches * bgGroups : 0, kDiag, true, "sweep_big_debug");
+    }
+};
+
+#define RTD_HIP(h, call)                                                                         \
+    do {                                                                                         \
+        hipError_t e_ = (call);                                                                  \
+        if (e_ != hipSuccess) {                                                                  \
+            char buf_[512];                                                                      \
+            snprintf(buf_, sizeof buf_, "HIP error: %s %s %d", hipGetErrorString(e_), __FILE__, __LINE__); \
+            (h)->error = buf_;                                                                   \
+            return RTD_ERR_HIP;                                                                  \
+        }                                                                                        \
+    } while (0)
+
+int fail(rtd_handle_impl* h, int code, const std::string& msg) { h->error = msg; return code; }
+
+// Owner of one device allocation that is neither in a field's buffer table nor the handle's LUT / CT block. The destructor frees:
+// whoever deletes the object that holds one, or lets one go out of scope, has made the device current and drained the stream first.
+template <typename T>
+struct DevBuf {
+    T* p = nullptr;
+    DevBuf() = default;
+    DevBuf(DevBuf&& o) noexcept : p(o.p) { o.p = nullptr; }
+    DevBuf& operator=(DevBuf&& o) noexcept { std::swap(p, o.p); return *this; }   // (o frees what this held)
+    ~DevBuf() { reset(); }
+    hipError_t alloc(size_t n) { reset(); return hipMalloc((void**)&p, n * sizeof(T)); }   // n elements, replacing what it held
+    void reset() { if (p) { (void)hipFree(p); p = nullptr; } }
+    operator T*() const { return p; }
+};
+
+// Allocates the field's buffers of the given classes (clearing those marked so); after a failure the caller frees them.
+int allocBuffers(rtd_handle_impl* h, rtd_field_impl* f, unsigned classes) {
+    hipError_t e = hipSuccess;
+    f->forEachBuffer([&](auto*& p, size_t n, BufClass c, bool clear, const char*) {
+        if (e != hipSuccess || !(classes & c) || n == 0) return;
+        e = hipMalloc((void**)&p, n * sizeof *p);
+        if (e == hipSuccess && clear) e = hipMemset(p, 0, n * sizeof *p);
+    });
+    RTD_HIP(h, e);
+    return RTD_OK;
+}
+
+void freeBuffers(rtd_field_impl* f, unsigned classes) {
+    f->forEachBuffer([&](auto*& p, size_t, BufClass c, bool, const char*) { if ((classes & c) && p) { (void)hipFree(p); p = nullptr; } });
+}
+
+std::vector<size_t> shapeCounts(rtd_field_impl* f) {
+    std::vector<size_t> n;
+    f->forEachBuffer([&](auto*&, size_t count, BufClass c, bool, const char*) { if (c == kShape) n.push_back(count); });
+    return n;
+}
+
+// Raises a kernel's dynamic-LDS cap to `bytes` unless this handle has set it at least that high already.
+template <typename K>
+hipError_t raiseLdsCap(rtd_handle_impl* h, K kernel, size_t bytes) {
+    const void* k = reinterpret_cast<const void*>(kernel);
+    size_t& cap = h->ldsCaps[k];
+    if (bytes <= cap) return hipSuccess;
+    const hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+    if (e == hipSuccess) cap = bytes;
+    return e;
+}
+
+// What a finished plan tells the host (its state record, mirrored into pinned host memory). The hints belong to the inputs the
+// compute was LAUNCHED under: CT, LUTs or options may have changed since.
+int takeFindings(rtd_handle_impl* h, rtd_field_impl* f, const FieldState& st) {
+    if (f->triedUniform) { f->uniformHint = st.uniformField ? 1 : 0; f->hintEpoch = f->launchEpoch; }
+    else if (f->hintEpoch != f->launchEpoch) { f->uniformHint = -1; f->hintEpoch = f->launchEpoch; }
+    f->radiusHint = (st.errorFlags || st.empty) ? -1 : st.maxRadius;   // (valid under hintEpoch, like the uniform hint)
+    // the field's trace and plan are complete and stand for the inputs of the launch (a later compute may run on another stream)
+    f->traceUsable = f->traceLaunched && f->launchEpoch == f->traceEpoch && !st.errorFlags && !f->remote;
+    // A compute that skipped the general kernel (hint: uniform) on a field the device then found heterogeneous has written no BEV
+    // dose: only possible when the caller changed a bound device volume in place (rtd_set_ct_device) without telling the handle.
+    if (f->launchedKnownUniform && !st.uniformField && !st.errorFlags && !st.empty)
+        return fail(h, RTD_ERR_NOT_READY, "the field was launched as a uniform-sigma field but is not one: its inputs were modified in place; call rtd_set_ct* again and recompute");
+    return RTD_OK;
+}
+
+}  // namespace
+
+// Launch with optional start / stop events taken from the kernel's own dispatch timestamps (hipExtLaunchKernelGGL): no
+// event packets between kernels. (Measured alternative: plain launches bracketed by hipEventRecord, +25 us per field.)
+template <typename K, typename... Args>
+static void launchK(K kernel, dim3 grid, dim3 block, size_t lds, hipStream_t s, hipEvent_t startEv, hipEvent_t stopEv, Args... args) {
+    hipExtLaunchKernelGGL(kernel, grid, block, lds, s, startEv, stopEv, 0, args...);
+}

@@ -1,0 +1,422 @@
+// rtd_optimizer_host.hpp — host side of the resident spot-weight optimiser, plain, robust and voxel-wise worst case (include/rtd.h,
+// DESIGN.md sections 12, 14 and 15; kernels in rtd_optimize.hpp, rtd_robust.hpp and rtd_voxelwise.hpp). Part of rtd_engine.hip's
+// translation unit, included after rtd_dij_host.hpp and rtd_objective_host.hpp, whose products and evaluations an iteration launches.
+#pragma once
+
+namespace {
+
+struct rtd_optimizer_impl {
+    std::vector<rtd_field_impl*> fields;
+    std::vector<int> offset;      // offset[f] .. offset[f + 1]: field f's part of the concatenated vectors
+    rtd_objective_impl* obj = nullptr;
+    rtd_optimizer_options opt{};
+    int n = 0, nCh = 0;
+    size_t nVox = 0;
+    uint32_t launched = 0;        // iterations launched so far (a count of launches, not a finding of the device)
+    DevBuf<float> dDose, dG, dVec;   // dVec: w | w_prev | grad | grad_prev | w_best, n each
+    DevBuf<double> dHistory, dValues, dPart;
+    DevBuf<OptState> dState;
+    // Robust scenarios (section 14). A plain optimiser is nScen == 1, robust == false: its one scenario is `fields` on dDose and dG, and
+    // nothing else of what follows is allocated.
+    bool robust = false, batch = true;
+    int nScen = 1, mode = 0;
+    std::vector<rtd_field_impl*> sfields;   // [nScen][fields.size()], scenario-major; row 0 is `fields`
+    std::vector<float*> doseS, gS;          // per scenario, what the launches read; [0] = dDose, dG
+    std::vector<DevBuf<float>> doseOwn, gOwn;   // ... and the owners of [1 ..]
+    DevBuf<float> dGradS;                   // [nScen][n]: Dij_s^T g_s
+    DevBuf<double> dScenValues;             // [nScen][1 + kObjMaxTerms]
+    DevBuf<RobustState> dRobust;
+    // The voxel-wise worst case (section 15): a robust optimiser whose steps 2 and 3 are one composite evaluation and its own decision.
+    bool voxelwise = false;
+    DevBuf<unsigned> dActive;               // one word: the scenarios that received a non-zero voxel gradient
+    rtd_field_impl* sf(int s, size_t i) const { return sfields[(size_t)s * fields.size() + i]; }
+    float* w() const { return dVec; }
+    float* wPrev() const { return dVec + n; }
+    float* grad() const { return dVec + 2 * (size_t)n; }
+    float* gradPrev() const { return dVec + 3 * (size_t)n; }
+    float* wBest() const { return dVec + 4 * (size_t)n; }
+};
+
+// The two products of an iteration, for one scenario (a plain optimiser is scenario 0). A matrix-free route (rtd_field_compute +
+// rtd_field_spot_gradient) would replace these two.
+// dose = sum_f Dij_f w_f, bit for bit "zero the volume, apply(init = 0) per field in list order": the row boxes of the fields 1..
+// are cleared, field 0 then WRITES its whole box (init = 1: s or +0, and 0 + s = s since a sum is never -0), the others accumulate.
+int scenarioForward(rtd_handle hh, rtd_handle_impl* h, rtd_optimizer_impl* p, int s) {
+    for (size_t i = 1; i < p->fields.size(); ++i) {
+        const rtd_field_impl* f = p->sf(s, i);
+        const long long nRows = (long long)f->dijRowsN;
+        if (nRows) k_opt_clear_box<<<(unsigned)((nRows + 255) / 256), 256, 0, h->stream>>>(p->doseS[s], (int)f->doseDims[0], (int)f->doseDims[1], f->dijBox, nRows);
+    }
+    for (size_t i = 0; i < p->fields.size(); ++i) {
+        const int st = rtd_field_dose_influence_apply(hh, reinterpret_cast<rtd_field>(p->sf(s, i)), p->w() + p->offset[i], p->doseS[s], i == 0 ? 1 : 0);
+        if (st != RTD_OK) return st;
+    }
+    return RTD_OK;
+}
+int scenarioAdjoint(rtd_handle hh, rtd_optimizer_impl* p, int s, float* out) {   // out[offset[i] ..] = Dij_(s, i)^T g_s
+    for (size_t i = 0; i < p->fields.size(); ++i) {
+        const int st = rtd_field_dose_influence_apply_t(hh, reinterpret_cast<rtd_field>(p->sf(s, i)), p->gS[s], out + p->offset[i]);
+        if (st != RTD_OK) return st;
+    }
+    return RTD_OK;
+}
+
+// The same two products over the scenario axis (section 14; kernels in rtd_robust.hpp). Batched: per field position one launch covers
+// every scenario. Unbatched (RTD_ROBUST_NO_BATCH): the single-matrix launches, scenario by scenario. Either way scenario s's volume
+// gets what scenarioForward gives it, and gradS[s] what scenarioAdjoint gives it.
+int robustForward(rtd_handle hh, rtd_handle_impl* h, rtd_optimizer_impl* p) {
+    const size_t F = p->fields.size();
+    const int S = p->nScen, nx = (int)p->fields[0]->doseDims[0], ny = (int)p->fields[0]->doseDims[1];
+    if (!p->batch) {
+        for (int s = 0; s < S; ++s) { const int st = scenarioForward(hh, h, p, s); if (st != RTD_OK) return st; }
+        return RTD_OK;
+    }
+    for (size_t i = 1; i < F; ++i) {
+        RobustClear a{};
+        long long most = 0;
+        for (int s = 0; s < S; ++s) {
+            const rtd_field_impl* f = p->sf(s, i);
+            a.dose[s] = p->doseS[s]; a.nRows[s] = (long long)f->dijRowsN; a.box[s] = f->dijBox;
+            most = std::max(most, a.nRows[s]);
+        }
+        if (most) k_robust_clear_box<<<dim3((unsigned)((most + 255) / 256), (unsigned)S), 256, 0, h->stream>>>(a, nx, ny);
+    }
+    for (size_t i = 0; i < F; ++i) {
+        RobustFwd a{};
+        long long most = 0;
+        for (int s = 0; s < S; ++s) {
+            const rtd_field_impl* f = p->sf(s, i);
+            a.rowPtr[s] = (const long long*)f->dDijRowPtr; a.cCols[s] = f->dDijCCols; a.cVals[s] = f->dDijCVals; a.dose[s] = p->doseS[s];
+            a.nRows[s] = (i != 0 && f->dijNnz == 0) ? 0 : (long long)f->dijRowsN;   // (an empty matrix adds nothing: no work, as the single call)
+            a.box[s] = f->dijBox;
+            most = std::max(most, a.nRows[s]);
+        }
+        if (!most) continue;
+        const dim3 grid((unsigned)((most * kDijApGroup + 255) / 256), (unsigned)S);
+        if (i == 0) k_dijap_apply_batch<true><<<grid, 256, 0, h->stream>>>(a, (const float*)(p->w() + p->offset[i]), nx, ny);
+        else k_dijap_apply_batch<false><<<grid, 256, 0, h->stream>>>(a, (const float*)(p->w() + p->offset[i]), nx, ny);
+    }
+    RTD_HIP(h, hipGetLastError());
+    return RTD_OK;
+}
+int robustAdjoint(rtd_handle hh, rtd_handle_impl* h, rtd_optimizer_impl* p) {
+    const size_t F = p->fields.size();
+    const int S = p->nScen;
+    if (!p->batch) {   // no decision on the host: every scenario's product is taken, the combine uses those with lambda != 0
+        for (int s = 0; s < S; ++s) { const int st = scenarioAdjoint(hh, p, s, p->dGradS + (size_t)s * p->n); if (st != RTD_OK) return st; }
+        return RTD_OK;
+    }
+    for (size_t i = 0; i < F; ++i) {
+        RobustAdj a{};
+        RobustRed r{};
+        int most = 0;
+        for (int s = 0; s < S; ++s) {
+            const rtd_field_impl* f = p->sf(s, i);
+            a.colPtr[s] = (const long long*)f->dDijColPtr; a.rows[s] = (const int*)f->dDijRows; a.vals[s] = (const float*)f->dDijVals;
+            a.chunkCol[s] = (const int*)f->dDijChunkCol; a.chunkFirst[s] = (const int*)f->dDijChunkFirst; a.g[s] = p->gS[s];
+            a.partial[s] = f->dDijPartial; a.nChunks[s] = (int)f->dijChunks;
+            r.chunkFirst[s] = (const int*)f->dDijChunkFirst; r.partial[s] = (const float*)f->dDijPartial;
+            r.out[s] = p->dGradS + (size_t)s * p->n + p->offset[i];
+            most = std::max(most, a.nChunks[s]);
+        }
+        const int nSpot = p->offset[i + 1] - p->offset[i];
+        if (most) k_dijap_apply_t_batch<<<dim3((unsigned)((most + 3) / 4), (unsigned)S), 256, 0, h->stream>>>(a, (const RobustState*)p->dRobust);
+        k_dijap_reduce_t_batch<<<dim3((unsigned)((nSpot + 3) / 4), (unsigned)S), 256, 0, h->stream>>>(r, (const RobustState*)p->dRobust, nSpot);
+    }
+    RTD_HIP(h, hipGetLastError());
+    return RTD_OK;
+}
+
+// rtd_optimizer_create (robust == nullptr: one scenario, nothing of section 14 allocated or launched), rtd_optimizer_create_robust and
+// rtd_optimizer_create_voxelwise (voxelwise: what a robust optimiser owns plus the word of active scenarios; robust->mode is not read).
+int optCreate(rtd_handle hh, const rtd_field* fields, uint32_t n_fields, const rtd_robust_options* robust, rtd_objective oo,
+              const rtd_optimizer_options* opt, rtd_optimizer* out, bool voxelwise = false) {
+    auto* h = reinterpret_cast<rtd_handle_impl*>(hh);
+    auto* o = reinterpret_cast<rtd_objective_impl*>(oo);
+    if (!h) return RTD_ERR_INVALID_ARG;
+    if (!fields || !o || !out) return fail(h, RTD_ERR_INVALID_ARG, "rtd_optimizer_create: null pointer");
+    *out = nullptr;
+    const uint32_t nScen = robust ? robust->n_scenarios : 1;
+    if (robust) {
+        if (!voxelwise && robust->mode != RTD_ROBUST_EXPECTED && robust->mode != RTD_ROBUST_WORST_CASE) return fail(h, RTD_ERR_INVALID_ARG, "rtd_optimizer_create_robust: unknown mode");
+        if (nScen < 1 || nScen > RTD_ROBUST_MAX_SCENARIOS) return fail(h, RTD_ERR_INVALID_ARG, "rtd_optimizer_create_robust: 1 to 32 scenarios");
+        if (robust->probabilities)
+            for (uint32_t sc = 0; sc < nScen; ++sc)
+                if (!(robust->probabilities[sc] > 0.0) || !std::isfinite(robust->probabilities[sc]))
+                    return fail(h, RTD_ERR_INVALID_ARG, "rtd_optimizer_create_robust: a probability must be positive and finite");
+    }
+    if (n_fields < 1 || n_fields > RTD_OPT_MAX_FIELDS) return fail(h, RTD_ERR_INVALID_ARG, "rtd_optimizer_create: 1 to 16 fields");
+    rtd_optimizer_options op;
+    rtd_default_optimizer_options(&op);
+    if (opt) op = *opt;
+    if (!(op.step_min > 0.0) || !(op.step_max >= op.step_min) || !std::isfinite(op.step_max))
+        return fail(h, RTD_ERR_INVALID_ARG, "rtd_optimizer_create: needs 0 < step_min <= step_max < inf");
+    const uint32_t nAll = nScen * n_fields;
+    for (uint32_t i = 0; i < nAll; ++i) {
+        auto* f = reinterpret_cast<rtd_field_impl*>(fields[i]);
+        if (!f) return fail(h, RTD_ERR_INVALID_ARG, "rtd_optimizer_create: null field");
+        if (f->remote) return fail(h, RTD_ERR_INVALID_ARG, "rtd_optimizer_create: a remote field has no matrix");
+        for (int a = 0; a < 3; ++a)
+            if (f->doseDims[a] != o->dims[a]) return fail(h, RTD_ERR_INVALID_ARG, "rtd_optimizer_create: the fields and the objective must share one dose grid");
+        if (robust) {
+            const auto* f0 = reinterpret_cast<rtd_field_impl*>(fields[i % n_fields]);
+            if (f0 && (f->fc.spotNx != f0->fc.spotNx || f->fc.spotNy != f0->fc.spotNy || f->fc.L != f0->fc.L))
+                return fail(h, RTD_ERR_INVALID_ARG, "rtd_optimizer_create_robust: field f of every scenario must have the spot-map shape of field f of scenario 0");
+            for (uint32_t k = 0; k < i; ++k)
+                if (fields[k] == fields[i]) return fail(h, RTD_ERR_INVALID_ARG, "rtd_optimizer_create_robust: a field is listed twice");
+        }
+    }
+    if (o->terms.empty()) return fail(h, RTD_ERR_INVALID_ARG, "rtd_optimizer_create: the objective has no terms");
+    if (voxelwise && o->hasDvhTerms()) return fail(h, RTD_ERR_INVALID_ARG, "rtd_optimizer_create_voxelwise: an objective with DVH terms has no voxel-wise worst case");
+    for (uint32_t i = 0; i < nAll; ++i)
+        if (!reinterpret_cast<rtd_field_impl*>(fields[i])->dijDone)
+            return fail(h, RTD_ERR_NOT_READY, "rtd_optimizer_create: a field has no dose-influence matrix (call rtd_field_dose_influence first)");
+    RTD_HIP(h, hipSetDevice(h->device));
+    for (uint32_t i = 0; i < nAll; ++i) { const int st = rtd_field_dose_influence_prepare(hh, fields[i]); if (st != RTD_OK) return st; }
+    if (!o->built) { const int st = buildObjective(h, o); if (st != RTD_OK) return st; }
+    auto* p = new rtd_optimizer_impl();
+    p->obj = o; p->opt = op; p->nVox = o->nVox;
+    if (robust) {
+        p->robust = true; p->nScen = (int)nScen; p->mode = robust->mode; p->voxelwise = voxelwise;
+        p->batch = std::getenv("RTD_ROBUST_NO_BATCH") == nullptr;      // read once, here (the convention of the engine switches)
+    }
+    for (uint32_t i = 0; i < nAll; ++i) p->sfields.push_back(reinterpret_cast<rtd_field_impl*>(fields[i]));
+    p->offset.push_back(0);
+    long long total = 0;
+    for (uint32_t i = 0; i < n_fields; ++i) {
+        auto* f = reinterpret_cast<rtd_field_impl*>(fields[i]);
+        p->fields.push_back(f);
+        total += (long long)f->fc.spotNx * f->fc.spotNy * f->fc.L;
+        if (total > 0x7fffffffLL) { delete p; return fail(h, RTD_ERR_INVALID_ARG, "rtd_optimizer_create: more than 2^31 - 1 spots"); }
+        p->offset.push_back((int)total);
+    }
+    p->n = (int)total;
+    p->nCh = (p->n + kOptChunk - 1) / kOptChunk;
+    const size_t n = (size_t)p->n, cap = std::max<size_t>(op.history_capacity, 1);
+    hipStream_t s = h->stream;
+    hipError_t e = p->dDose.alloc(p->nVox);
+    if (e == hipSuccess) e = p->dG.alloc(p->nVox);
+    if (e == hipSuccess) e = p->dVec.alloc(5 * n);
+    if (e == hipSuccess) e = p->dHistory.alloc(cap);
+    if (e == hipSuccess) e = p->dValues.alloc(1 + kObjMaxTerms);
+    if (e == hipSuccess) e = p->dPart.alloc(3 * (size_t)p->nCh);
+    if (e == hipSuccess) e = p->dState.alloc(1);
+    if (e == hipSuccess) e = hipMemsetAsync(p->dDose, 0, p->nVox * sizeof(float), s);
+    if (e == hipSuccess) e = hipMemsetAsync(p->dG, 0, p->nVox * sizeof(float), s);
+    if (e == hipSuccess) e = hipMemsetAsync(p->dVec, 0, 5 * n * sizeof(float), s);
+    if (e == hipSuccess) e = hipMemsetAsync(p->dHistory, 0, cap * sizeof(double), s);
+    if (e == hipSuccess) e = hipMemsetAsync(p->dValues, 0, (1 + kObjMaxTerms) * sizeof(double), s);
+    OptState st0{};
+    st0.fBest = std::numeric_limits<double>::infinity(); st0.bestIter = -1;
+    if (e == hipSuccess) e = hipMemcpyAsync(p->dState, &st0, sizeof st0, hipMemcpyHostToDevice, s);
+    for (uint32_t i = 0; i < n_fields && e == hipSuccess; ++i) {
+        const size_t cnt = (size_t)(p->offset[i + 1] - p->offset[i]) * sizeof(float);
+        e = hipMemcpyAsync(p->w() + p->offset[i], p->fields[i]->dSpotWeights, cnt, hipMemcpyDeviceToDevice, s);
+        if (e == hipSuccess) e = hipMemcpyAsync(p->wBest() + p->offset[i], p->fields[i]->dSpotWeights, cnt, hipMemcpyDeviceToDevice, s);
+    }
+    p->doseS.assign(1, p->dDose.p); p->gS.assign(1, p->dG.p);
+    RobustState rs0{};
+    if (robust) {
+        p->doseS.resize(nScen, nullptr); p->gS.resize(nScen, nullptr);
+        p->doseOwn.resize(nScen - 1); p->gOwn.resize(nScen - 1);
+        for (uint32_t sc = 1; sc < nScen && e == hipSuccess; ++sc) {
+            e = p->doseOwn[sc - 1].alloc(p->nVox);
+            if (e == hipSuccess) e = p->gOwn[sc - 1].alloc(p->nVox);
+            p->doseS[sc] = p->doseOwn[sc - 1].p; p->gS[sc] = p->gOwn[sc - 1].p;
+            if (e == hipSuccess) e = hipMemsetAsync(p->doseS[sc], 0, p->nVox * sizeof(float), s);
+            if (e == hipSuccess) e = hipMemsetAsync(p->gS[sc], 0, p->nVox * sizeof(float), s);
+        }
+        const size_t nGrad = std::max<size_t>((size_t)nScen * n, 1), nVal = (size_t)nScen * (1 + kObjMaxTerms);
+        if (e == hipSuccess) e = p->dGradS.alloc(nGrad);
+        if (e == hipSuccess) e = p->dScenValues.alloc(nVal);
+        if (e == hipSuccess) e = p->dRobust.alloc(1);
+        if (e == hipSuccess) e = hipMemsetAsync(p->dGradS, 0, nGrad * sizeof(float), s);
+        if (e == hipSuccess) e = hipMemsetAsync(p->dScenValues, 0, nVal * sizeof(double), s);
+        for (uint32_t sc = 0; sc < nScen; ++sc) rs0.prob[sc] = robust->probabilities ? robust->probabilities[sc] : 1.0 / (double)nScen;
+        if (e == hipSuccess) e = hipMemcpyAsync(p->dRobust, &rs0, sizeof rs0, hipMemcpyHostToDevice, s);
+        if (voxelwise) {
+            if (e == hipSuccess) e = p->dActive.alloc(1);
+            if (e == hipSuccess) e = hipMemsetAsync(p->dActive, 0, sizeof(unsigned), s);
+        }
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(s);                 // (st0 and rs0 live on this stack)
+    if (e != hipSuccess) { (void)hipStreamSynchronize(s); delete p; RTD_HIP(h, e); }
+    *out = reinterpret_cast<rtd_optimizer>(p);
+    return RTD_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+void rtd_default_optimizer_options(rtd_optimizer_options* o) {
+    std::memset(o, 0, sizeof *o);
+    o->step_min = 1e-30; o->step_max = 1e30; o->history_capacity = 4096;
+}
+
+int rtd_optimizer_create(rtd_handle hh, const rtd_field* fields, uint32_t n_fields, rtd_objective oo, const rtd_optimizer_options* opt,
+                         rtd_optimizer* out) {
+    return optCreate(hh, fields, n_fields, nullptr, oo, opt, out);
+}
+
+int rtd_optimizer_create_robust(rtd_handle hh, const rtd_field* fields, uint32_t n_fields, const rtd_robust_options* robust, rtd_objective oo,
+                                const rtd_optimizer_options* opt, rtd_optimizer* out) {
+    auto* h = reinterpret_cast<rtd_handle_impl*>(hh);
+    if (!h) return RTD_ERR_INVALID_ARG;
+    if (!robust) return fail(h, RTD_ERR_INVALID_ARG, "rtd_optimizer_create_robust: null pointer");
+    if (out) *out = nullptr;
+    return optCreate(hh, fields, n_fields, robust, oo, opt, out);
+}
+
+int rtd_optimizer_create_voxelwise(rtd_handle hh, const rtd_field* fields, uint32_t n_fields, uint32_t n_scenarios, rtd_objective oo,
+                                   const rtd_optimizer_options* opt, rtd_optimizer* out) {
+    auto* h = reinterpret_cast<rtd_handle_impl*>(hh);
+    if (!h) return RTD_ERR_INVALID_ARG;
+    if (out) *out = nullptr;
+    rtd_robust_options ro{};
+    ro.mode = RTD_ROBUST_EXPECTED; ro.n_scenarios = n_scenarios;
+    return optCreate(hh, fields, n_fields, &ro, oo, opt, out, true);
+}
+
+// f_s, lambda_s and the worst scenario of the iterate f_last belongs to. A plain optimiser is a set of one scenario.
+int rtd_optimizer_scenario_values(rtd_handle hh, rtd_optimizer pp, double* values, double* lambdas, int32_t* worst) {
+    auto* h = reinterpret_cast<rtd_handle_impl*>(hh);
+    auto* p = reinterpret_cast<rtd_optimizer_impl*>(pp);
+    if (!h) return RTD_ERR_INVALID_ARG;
+    if (!p || !values) return fail(h, RTD_ERR_INVALID_ARG, "rtd_optimizer_scenario_values: null pointer");
+    RTD_HIP(h, hipSetDevice(h->device));
+    if (!p->robust) {
+        OptState st{};
+        RTD_HIP(h, hipMemcpyAsync(&st, p->dState, sizeof st, hipMemcpyDeviceToHost, h->stream));
+        RTD_HIP(h, hipStreamSynchronize(h->stream));
+        values[0] = st.fLast;
+        if (lambdas) lambdas[0] = 1.0;
+        if (worst) *worst = 0;
+        return RTD_OK;
+    }
+    RobustState rs{};
+    RTD_HIP(h, hipMemcpyAsync(&rs, p->dRobust, sizeof rs, hipMemcpyDeviceToHost, h->stream));
+    RTD_HIP(h, hipStreamSynchronize(h->stream));
+    for (int sc = 0; sc < p->nScen; ++sc) { values[sc] = rs.f[sc]; if (lambdas) lambdas[sc] = rs.lambda[sc]; }
+    if (worst) *worst = rs.worst;
+    return RTD_OK;
+}
+
+int rtd_optimizer_scenario_dose(rtd_handle hh, rtd_optimizer pp, uint32_t scenario, const float** dev_dose) {
+    auto* h = reinterpret_cast<rtd_handle_impl*>(hh);
+    auto* p = reinterpret_cast<rtd_optimizer_impl*>(pp);
+    if (!h) return RTD_ERR_INVALID_ARG;
+    if (!p || !dev_dose) return fail(h, RTD_ERR_INVALID_ARG, "rtd_optimizer_scenario_dose: null pointer");
+    if (scenario >= (uint32_t)p->nScen) return fail(h, RTD_ERR_INVALID_ARG, "rtd_optimizer_scenario_dose: scenario index out of range");
+    *dev_dose = p->doseS[scenario];
+    return RTD_OK;
+}
+
+int rtd_optimizer_set_weights(rtd_handle hh, rtd_optimizer pp, uint32_t field_index, const float* dev_w) {
+    auto* h = reinterpret_cast<rtd_handle_impl*>(hh);
+    auto* p = reinterpret_cast<rtd_optimizer_impl*>(pp);
+    if (!h) return RTD_ERR_INVALID_ARG;
+    if (!p || !dev_w) return fail(h, RTD_ERR_INVALID_ARG, "rtd_optimizer_set_weights: null pointer");
+    if (field_index >= p->fields.size()) return fail(h, RTD_ERR_INVALID_ARG, "rtd_optimizer_set_weights: field index out of range");
+    RTD_HIP(h, hipSetDevice(h->device));
+    const size_t cnt = (size_t)(p->offset[field_index + 1] - p->offset[field_index]) * sizeof(float);
+    RTD_HIP(h, hipMemcpyAsync(p->w() + p->offset[field_index], dev_w, cnt, hipMemcpyDeviceToDevice, h->stream));
+    if (!p->launched) RTD_HIP(h, hipMemcpyAsync(p->wBest() + p->offset[field_index], dev_w, cnt, hipMemcpyDeviceToDevice, h->stream));
+    return RTD_OK;
+}
+
+int rtd_optimizer_run(rtd_handle hh, rtd_optimizer pp, uint32_t n_iterations) {
+    auto* h = reinterpret_cast<rtd_handle_impl*>(hh);
+    auto* p = reinterpret_cast<rtd_optimizer_impl*>(pp);
+    if (!h) return RTD_ERR_INVALID_ARG;
+    if (!p) return fail(h, RTD_ERR_INVALID_ARG, "rtd_optimizer_run: null pointer");
+    if (p->obj->terms.empty()) return fail(h, RTD_ERR_INVALID_ARG, "rtd_optimizer_run: the objective has no terms");
+    RTD_HIP(h, hipSetDevice(h->device));
+    hipStream_t s = h->stream;
+    for (uint32_t k = 0; k < n_iterations; ++k) {
+        int st = RTD_OK;
+        if (!p->robust) {
+            st = scenarioForward(hh, h, p, 0);                                            // 1.
+            if (st == RTD_OK) st = evalObjective(h, p->obj, p->dDose, p->dValues, p->dG); // 2.
+            if (st == RTD_OK) st = scenarioAdjoint(hh, p, 0, p->grad());                  // 3.
+        } else {                              // sections 14 and 15, steps 1.-5.: they differ in the evaluation and in who decides on it
+            st = robustForward(hh, h, p);
+            if (p->voxelwise) {
+                if (st == RTD_OK) st = evalVoxelwise(h, p->obj, p->doseS.data(), p->nScen, p->dValues, p->gS.data(), p->dActive);
+                if (st == RTD_OK) k_voxelwise_decide<<<1, 64, 0, s>>>((const unsigned*)p->dActive, p->nScen, p->dRobust, p->dValues);
+            } else {
+                for (int sc = 0; sc < p->nScen && st == RTD_OK; ++sc)
+                    st = evalObjective(h, p->obj, p->doseS[sc], p->dScenValues + (size_t)sc * (1 + kObjMaxTerms), p->gS[sc]);
+                if (st == RTD_OK) k_robust_decide<<<1, 64, 0, s>>>((const double*)p->dScenValues, 1 + kObjMaxTerms, p->nScen, p->mode, p->dRobust, p->dValues);
+            }
+            if (st == RTD_OK) st = robustAdjoint(hh, h, p);
+            if (st == RTD_OK)
+                k_robust_combine<<<(unsigned)((p->n + 255) / 256), 256, 0, s>>>((const float*)p->dGradS, (const RobustState*)p->dRobust, p->nScen, p->n, p->grad());
+        }
+        if (st != RTD_OK) return st;
+        k_opt_partials<<<(unsigned)((p->nCh + 3) / 4), 256, 0, s>>>((const float*)p->w(), (const float*)p->wPrev(), (const float*)p->grad(),
+                                                                   (const float*)p->gradPrev(), p->n, p->nCh, p->dPart);
+        k_opt_step<<<1, 64, 0, s>>>((const double*)p->dPart, p->nCh, (const double*)p->dValues, p->dState, p->dHistory, p->opt.history_capacity,
+                                    p->opt.step_min, p->opt.step_max);                    // 2. (history), 4., 5., 7.: the decisions
+        k_opt_update<<<(unsigned)((p->n + 255) / 256), 256, 0, s>>>((const OptState*)p->dState, p->w(), p->wPrev(), (const float*)p->grad(), p->gradPrev(),
+                                                                   p->wBest(), p->n);     // 4., 6., 7.: per entry
+        RTD_HIP(h, hipGetLastError());
+        ++p->launched;
+    }
+    return RTD_OK;
+}
+
+int rtd_optimizer_result(rtd_handle hh, rtd_optimizer pp, rtd_optimizer_report* r, double* history, uint32_t capacity) {
+    auto* h = reinterpret_cast<rtd_handle_impl*>(hh);
+    auto* p = reinterpret_cast<rtd_optimizer_impl*>(pp);
+    if (!h) return RTD_ERR_INVALID_ARG;
+    if (!p || !r || (capacity && !history)) return fail(h, RTD_ERR_INVALID_ARG, "rtd_optimizer_result: null pointer");
+    RTD_HIP(h, hipSetDevice(h->device));
+    OptState st{};
+    RTD_HIP(h, hipMemcpyAsync(&st, p->dState, sizeof st, hipMemcpyDeviceToHost, h->stream));
+    RTD_HIP(h, hipStreamSynchronize(h->stream));
+    std::memset(r, 0, sizeof *r);
+    r->f_last = st.fLast; r->f_best = st.fBest; r->step = st.alpha; r->best_iteration = st.bestIter;
+    r->iterations = (uint32_t)st.iter; r->history_len = (uint32_t)std::min<long long>(st.iter, (long long)p->opt.history_capacity);
+    r->guarded = st.guarded;
+    const uint32_t cnt = std::min(capacity, r->history_len);
+    if (cnt) {
+        RTD_HIP(h, hipMemcpyAsync(history, p->dHistory, cnt * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+        RTD_HIP(h, hipStreamSynchronize(h->stream));
+    }
+    if (st.startBad) return fail(h, RTD_ERR_INVALID_ARG, "rtd_optimizer_result: the objective of the start weights is not finite");
+    return RTD_OK;
+}
+
+int rtd_optimizer_weights(rtd_handle hh, rtd_optimizer pp, uint32_t field_index, float* dev_w_out, int best) {
+    auto* h = reinterpret_cast<rtd_handle_impl*>(hh);
+    auto* p = reinterpret_cast<rtd_optimizer_impl*>(pp);
+    if (!h) return RTD_ERR_INVALID_ARG;
+    if (!p || !dev_w_out) return fail(h, RTD_ERR_INVALID_ARG, "rtd_optimizer_weights: null pointer");
+    if (field_index >= p->fields.size()) return fail(h, RTD_ERR_INVALID_ARG, "rtd_optimizer_weights: field index out of range");
+    RTD_HIP(h, hipSetDevice(h->device));
+    const size_t cnt = (size_t)(p->offset[field_index + 1] - p->offset[field_index]) * sizeof(float);
+    RTD_HIP(h, hipMemcpyAsync(dev_w_out, (best ? p->wBest() : p->w()) + p->offset[field_index], cnt, hipMemcpyDeviceToDevice, h->stream));
+    return RTD_OK;
+}
+
+int rtd_optimizer_dose(rtd_handle hh, rtd_optimizer pp, const float** dev_dose) {
+    auto* h = reinterpret_cast<rtd_handle_impl*>(hh);
+    auto* p = reinterpret_cast<rtd_optimizer_impl*>(pp);
+    if (!h) return RTD_ERR_INVALID_ARG;
+    if (!p || !dev_dose) return fail(h, RTD_ERR_INVALID_ARG, "rtd_optimizer_dose: null pointer");
+    *dev_dose = p->dDose;
+    return RTD_OK;
+}
+
+int rtd_optimizer_destroy(rtd_handle hh, rtd_optimizer pp) {
+    auto* h = reinterpret_cast<rtd_handle_impl*>(hh);
+    auto* p = reinterpret_cast<rtd_optimizer_impl*>(pp);
+    if (!h || !p) return RTD_ERR_INVALID_ARG;
+    (void)hipSetDevice(h->device);
+    (void)hipStreamSynchronize(h->stream);
+    delete p;
+    return RTD_OK;
+}
+
+}  // extern "C"
