@@ -17,7 +17,9 @@
 // dose would reach. The extents used here are the transfer's coverage box (bbox, from the live steps only), the slices
 // [beamFirstInside, firstCalculatedPassive), the tile radius classes and batch radii (liveness and sigma only) and every ray.
 #pragma once
-#include "rtd_kernels.hpp"
+#include "rtd_field_state.hpp"
+#include "rtd_plan_conv.hpp"
+#include "rtd_ks_plan.hpp"
 #include "rtd_sweep.hpp"
 
 namespace rtd {

@@ -181,4 +181,10 @@ __global__ __launch_bounds__(256) void k_dijap_reduce_t(const int* __restrict__ 
     if (lane == 0) out[j] = acc;
 }
 
+// Zeroes this thread's voxel of a row box: the body of k_opt_clear_box (rtd_optimize.hpp) and k_robust_clear_box (rtd_robust.hpp).
+__device__ inline void dijClearBoxVoxel(float* __restrict__ vol, int nx, int ny, const DijBox& box, long long nRows) {
+    const long long r = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (r < nRows) vol[dijBoxVoxel(r, nx, ny, box)] = 0.0f;
+}
+
 }  // namespace rtd

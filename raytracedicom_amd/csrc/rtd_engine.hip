@@ -25,7 +25,14 @@
 
 #include "../../include/rtd.h"
 #include "rtd_geometry.hpp"
-#include "rtd_kernels.hpp"
+#include "rtd_field_state.hpp"
+#include "rtd_trace.hpp"
+#include "rtd_plan_conv.hpp"
+#include "rtd_fill.hpp"
+#include "rtd_ks_plan.hpp"
+#include "rtd_nuclear.hpp"
+#include "rtd_superpose_mfma.hpp"
+#include "rtd_transfer.hpp"
 #include "rtd_sweep.hpp"
 #include "rtd_sweep_big.hpp"
 #include "rtd_uniform.hpp"
@@ -83,6 +90,26 @@ void fillInfo(const rtd_field_impl* f, const FieldState& st, rtd_field_info* inf
     if (f->fc.nuclearCorr && !f->remote) for (int i = 0; i < 3; ++i) { info->dose_box_min[i] = 0; info->dose_box_max[i] = (int32_t)f->doseDims[i] - 1; }
     info->live_steps = st.liveSteps; info->max_radius = st.maxRadius;
     info->uniform_sigma = st.uniformField;
+}
+
+
+// The BEV dose a field's transfer samples and its state record: the field's own, or the slab another GPU exported.
+struct FieldSlab { const float* bev; const FieldState* st; };
+FieldSlab fieldSlab(const rtd_field_impl* f) {
+    if (!f->remote) return {f->dBev, f->dState};
+    return {reinterpret_cast<const float*>(f->attached + kPackHeader), reinterpret_cast<const FieldState*>(f->attached)};
+}
+// Grid of k_transfer* / k_clear_box: they stride over the 32 x 8 x zChunk bricks of the device-side box; never more blocks than
+// bricks of the whole volume.
+unsigned brickGrid(const rtd_handle_impl* h, const rtd_field_impl* f, int zChunk) {
+    const size_t allBricks = (size_t)((f->doseDims[0] + 31) / 32) * ((f->doseDims[1] + 7) / 8) * ((f->doseDims[2] + zChunk - 1) / zChunk);
+    return (unsigned)std::min<size_t>(allBricks, (size_t)h->numCUs * 8 * 4);
+}
+// The transfer kernel of a lane mode — lanes run along the dose axis that moves fastest along BEV x, so that the gathers stay within
+// few BEV rows — that writes (init) or accumulates, handed to fn.
+template <typename Fn> void withTransferKernel(int mode, bool init, Fn&& fn) {
+    if (init) { if (mode == 0) fn(k_transfer<true>); else if (mode == 1) fn(k_transfer_t<1, true>); else fn(k_transfer_t<2, true>); }
+    else { if (mode == 0) fn(k_transfer<false>); else if (mode == 1) fn(k_transfer_t<1, false>); else fn(k_transfer_t<2, false>); }
 }
 
 }  // namespace
@@ -668,58 +695,23 @@ static int ensureCtBox(rtd_handle_impl* h, rtd_field_impl* f) {
     return RTD_OK;
 }
 
-int rtd_field_compute_bev(rtd_handle hh, rtd_field ff) {
-    auto* h = reinterpret_cast<rtd_handle_impl*>(hh);
-    auto* f = reinterpret_cast<rtd_field_impl*>(ff);
-    if (!h || !f) return RTD_ERR_INVALID_ARG;
-    if (f->remote) return fail(h, RTD_ERR_INVALID_ARG, "rtd_field_compute_bev: a remote field has no workspace (attach a slab instead)");
-    if (!h->dCt || !h->haveLuts) return fail(h, RTD_ERR_NOT_READY, "rtd_field_compute: set LUTs and CT first");
-    RTD_HIP(h, hipSetDevice(h->device));   // one host thread may drive handles on several devices
-    const FieldConst& fc = f->fc;
-    hipStream_t s = h->stream;
-    // The trace and the plan of a finished compute stand while CT, LUTs and options do (inputEpoch; a bound device CT rewritten in place
-    // is announced by rtd_set_ct* like any other change): the launches in front of the convolution are then left out. Not with the
-    // halo, not for spot maps beyond k_plan_conv's rows, not with RTD_SEPARATE_PLAN (the full sequence, deliberately: DESIGN.md section
-    // 4), and never into a capturing stream: a graph must not depend on what the field knew when it was captured.
-    bool reuse = f->traceUsable && f->traceEpoch == h->inputEpoch && !f->sw.noTraceReuse && !f->sw.separatePlan && !fc.nuclearCorr &&
-                 fc.spotNy <= kPlanConvMaxRows;
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    RTD_HIP(h, hipStreamIsCapturing(s, &cs));
-    const bool capturing = cs != hipStreamCaptureStatusNone;
-    if (capturing) reuse = false;
-    if (!reuse) {
-        const int st = ensureCtBox(h, f); if (st != RTD_OK) return st;
-        // (a captured launch runs when its graph does, not now: it leaves no record)
-        f->traceUsable = false; f->traceLaunched = !capturing; f->traceEpoch = h->inputEpoch;
-    }
-    f->launchedReuse = reuse;
-    // the uniform-sigma detection and kernel are skipped for a field that was found heterogeneous under the same CT / LUTs / options
-    const bool tryUniform = f->uniformEligible && !(f->uniformHint == 0 && f->hintEpoch == h->inputEpoch);
-    f->triedUniform = tryUniform;
-    f->launchEpoch = h->inputEpoch;
-    // ... and a field that was found uniform under the same inputs will be found uniform again (the test is exact arithmetic on
-    // the same values): the general superposition kernel, all of whose ~10^5 blocks would only look at the flag and leave, is not launched
-    const bool knownUniform = tryUniform && f->uniformHint == 1 && f->hintEpoch == h->inputEpoch;
-    f->launchedKnownUniform = knownUniform;
-    const bool timing = h->opt.fine_grained_timing != 0;
-    const dim3 blk(kSuperpTileX, kSuperpTileY);
-    const dim3 rayGrid(fc.W / kSuperpTileX, fc.H / kSuperpTileY);
-
+// What the stages of one compute share.
+struct ComputeJob {
+    rtd_handle_impl* h; rtd_field_impl* f;
+    bool reuse, tryUniform, knownUniform, timing;
+    ResetJob resetJob;
     // Stage boundaries are the start / stop timestamps of the kernels themselves (hipExtLaunchKernelGGL), not event
     // packets between them: no barrier packet and no idle gap is inserted into the stream by the timing.
-    auto ev = [&](int i) -> hipEvent_t { return timing ? f->ev[i] : nullptr; };
+    hipEvent_t ev(int i) const { return timing ? f->ev[i] : nullptr; }
+};
+
+// K1: the tracer's sampling pass in the field's lane direction, then the scan.
+static int launchTrace(const ComputeJob& c) {
+    rtd_handle_impl* h = c.h; rtd_field_impl* f = c.f; const FieldConst& fc = f->fc; hipStream_t s = h->stream;
     const size_t lutLds = (size_t)(h->lut.nDensity + h->lut.nSp) * sizeof(float);
     // dIdd doubles as the HU scratch of the tracer (it is written by k_fill only afterwards)
     const size_t tLds = lutLds + (size_t)3 * kTrRays * kTrPitch * sizeof(float);
     const size_t dLds = lutLds + (size_t)3 * kTdSteps * kTdPitch * sizeof(float);
-    const ResetJob resetJob{f->dLayers, fc.L, reinterpret_cast<unsigned int*>(f->dTileRad), f->tileRadWords, f->dActive, (size_t)4 * fc.L * fc.S,
-                            f->dNucIdd, f->dNucRs, fc.nuclearCorr ? (size_t)fc.nucW * fc.nucH * fc.L : (size_t)0,
-                            f->dSigMin, f->dSigMax, (size_t)fc.L * fc.S, f->dScanDbg};
-    if (reuse) {
-        // the spot -> ray convolution is the first launch; it carries the reset of what k_fill and the superposition's plan accumulate into
-        launchK(k_reset_conv, dim3(fc.W / 32, (fc.H / 8 + 3) / 4, fc.L), dim3(1024), (size_t)4 * fc.spotNy * 32 * sizeof(float), s, f->ev[0], ev(2),
-                (const float*)f->dSpotWeights, f->dRayWeights, (const LayerPlan*)f->dLayers, f->dState, resetJob, fc);
-    } else {
     if (f->traceMode == 2 && dLds <= 150 * 1024) {
         RTD_HIP(h, raiseLdsCap(h, k_trace_sample_d, dLds));
         launchK(k_trace_sample_d, dim3((unsigned)(fc.W / kTdRays), (unsigned)fc.H, (unsigned)((fc.S + kTdSteps - 1) / kTdSteps)), dim3(kTdThreads), dLds, s, f->ev[0], nullptr,
@@ -739,41 +731,60 @@ int rtd_field_compute_bev(rtd_handle hh, rtd_field ff) {
     }
     constexpr size_t scanLds = 2 * 2 * kScanChunk * 64 * sizeof(float);   // two buffers of 64 KiB: above the 64 KiB default cap of dynamic LDS
     RTD_HIP(h, raiseLdsCap(h, k_trace_scan, scanLds));
-    launchK(k_trace_scan, dim3((unsigned)(f->R / 64)), dim3(64, kScanWaves), scanLds, s, nullptr, ev(1), (const float*)f->dIdd, f->dWepl, fc.W, fc.H,
-            (unsigned)fc.S, f->dFirstInside, f->dFirstOutside, f->dState, f->dBlockWeplMin, resetJob);
-    if (fc.spotNy <= kPlanConvMaxRows && !f->sw.separatePlan) {
+    launchK(k_trace_scan, dim3((unsigned)(f->R / 64)), dim3(64, kScanWaves), scanLds, s, nullptr, c.ev(1), (const float*)f->dIdd, f->dWepl, fc.W, fc.H,
+            (unsigned)fc.S, f->dFirstInside, f->dFirstOutside, f->dState, f->dBlockWeplMin, c.resetJob);
+    return RTD_OK;
+}
+
+// K2-K4: the plan and the spot -> ray convolution.
+static void launchPlanConv(const ComputeJob& c) {
+    rtd_field_impl* f = c.f; const FieldConst& fc = f->fc; hipStream_t s = c.h->stream;
+    const dim3 blk(kSuperpTileX, kSuperpTileY);
+    if (c.reuse) {
+        // the spot -> ray convolution is the first launch; it carries the reset of what k_fill and the superposition's plan accumulate into
+        launchK(k_reset_conv, dim3(fc.W / 32, (fc.H / 8 + 3) / 4, fc.L), dim3(1024), (size_t)4 * fc.spotNy * 32 * sizeof(float), s, f->ev[0], c.ev(2),
+                (const float*)f->dSpotWeights, f->dRayWeights, (const LayerPlan*)f->dLayers, f->dState, c.resetJob, fc);
+    } else if (fc.spotNy <= kPlanConvMaxRows && !f->sw.separatePlan) {
         // the plan and the spot -> ray convolution in one launch (k_plan_conv): neither reads what the other writes
-        launchK(k_plan_conv, dim3(fc.W / 32, (fc.H / 8 + 3) / 4, fc.L + 1), dim3(1024), (size_t)4 * fc.spotNy * 32 * sizeof(float), s, nullptr, ev(2),
+        launchK(k_plan_conv, dim3(fc.W / 32, (fc.H / 8 + 3) / 4, fc.L + 1), dim3(1024), (size_t)4 * fc.spotNy * 32 * sizeof(float), s, nullptr, c.ev(2),
                 (const float*)f->dSpotWeights, f->dRayWeights, f->dLayers, f->dState, (const float*)f->dBlockWeplMin, (int)(f->R / 64), f->dWeplMin, fc);
     } else {
-    k_plan<<<1, 1024, 0, s>>>(f->dState, f->dLayers, (const float*)f->dBlockWeplMin, (int)(f->R / 64), f->dWeplMin, fc);
-    if (fc.spotNy <= kConvMaxRows) {
-        // both passes in one launch, the x pass staged in LDS (k_conv)
-        launchK(k_conv, dim3(fc.W / 32, fc.H / 8, fc.L), blk, (size_t)fc.spotNy * 32 * sizeof(float), s, nullptr, ev(2), (const float*)f->dSpotWeights,
-                f->dRayWeights, (const LayerPlan*)f->dLayers, (const FieldState*)f->dState, fc);
-    } else {
-        k_conv_x<<<dim3(fc.W / 32, (fc.spotNy + 7) / 8, fc.L), blk, 0, s>>>(f->dSpotWeights, f->dConvInterm, f->dLayers, f->dState, fc);
-        launchK(k_conv_y, dim3(fc.W / 32, fc.H / 8, fc.L), blk, 0, s, nullptr, ev(2), (const float*)f->dConvInterm, f->dRayWeights,
-                (const LayerPlan*)f->dLayers, (const FieldState*)f->dState, fc);
+        k_plan<<<1, 1024, 0, s>>>(f->dState, f->dLayers, (const float*)f->dBlockWeplMin, (int)(f->R / 64), f->dWeplMin, fc);
+        if (fc.spotNy <= kConvMaxRows) {
+            // both passes in one launch, the x pass staged in LDS (k_conv)
+            launchK(k_conv, dim3(fc.W / 32, fc.H / 8, fc.L), blk, (size_t)fc.spotNy * 32 * sizeof(float), s, nullptr, c.ev(2), (const float*)f->dSpotWeights,
+                    f->dRayWeights, (const LayerPlan*)f->dLayers, (const FieldState*)f->dState, fc);
+        } else {
+            k_conv_x<<<dim3(fc.W / 32, (fc.spotNy + 7) / 8, fc.L), blk, 0, s>>>(f->dSpotWeights, f->dConvInterm, f->dLayers, f->dState, fc);
+            launchK(k_conv_y, dim3(fc.W / 32, fc.H / 8, fc.L), blk, 0, s, nullptr, c.ev(2), (const float*)f->dConvInterm, f->dRayWeights,
+                    (const LayerPlan*)f->dLayers, (const FieldState*)f->dState, fc);
+        }
     }
-    }
-    }
-    {
-        const size_t fillLds = (size_t)(2 * h->lut.nSamples) * sizeof(float);   // the layer's two cumulative-IDD rows
-        const dim3 fillGrid(2 * rayGrid.x * rayGrid.y * fc.L);          // (layer, tile, role) items: sigma walk and dose walk of every tile; placement is decided in the kernel
-        const dim3 fillBlk = blk;
-        const NucFill nucFill{f->dNucSpotIdx, f->dNucRayWeights, f->dNucIdd, f->dNucRs};
-        auto launchFill = [&](auto kern, size_t lds) {
-            launchK(kern, fillGrid, fillBlk, lds, s, nullptr, ev(3), (const float*)f->dDensity, (const float*)f->dWepl, (const float*)f->dRrl, f->dIdd,
-                    f->dRSigma, (const float*)f->dRayWeights, (const int*)f->dFirstInside, (const int*)f->dFirstOutside,
-                    f->dFirstPassive, f->dTileRad, f->dLayers, f->dState, h->lut, f->fillGeom, fc, (const float*)f->dStepTab, f->dActive, h->numCUs, f->dFillDbg, nucFill, f->dSigMin, f->dSigMax, tryUniform ? 1 : 0);
-        };
-        const bool ldsLut = fillLds <= 56 * 1024;     // (+ ~1 KiB of static arrays: stays under the 64 KiB default cap of a block's LDS)
-        constexpr size_t sigLds = (size_t)2 * kFillBatch * 256 * sizeof(float);   // the sigma walk's exchange buffers share the dynamic LDS with the dose walk's LUT rows
-        const size_t dynLds = std::max(sigLds, ldsLut ? fillLds : (size_t)0);
-        if (fc.nuclearCorr) { if (ldsLut) launchFill((k_fill<true, true>), dynLds); else launchFill((k_fill<false, true>), dynLds); }
-        else { if (ldsLut) launchFill((k_fill<true, false>), dynLds); else launchFill((k_fill<false, false>), dynLds); }
-    }
+}
+
+// K5: the fill.
+static void launchFill(const ComputeJob& c) {
+    rtd_handle_impl* h = c.h; rtd_field_impl* f = c.f; const FieldConst& fc = f->fc;
+    const size_t fillLds = (size_t)(2 * h->lut.nSamples) * sizeof(float);   // the layer's two cumulative-IDD rows
+    // (layer, tile, role) items: sigma walk and dose walk of every tile; placement is decided in the kernel
+    const dim3 fillGrid(2 * (fc.W / kSuperpTileX) * (fc.H / kSuperpTileY) * fc.L), fillBlk(kSuperpTileX, kSuperpTileY);
+    const NucFill nucFill{f->dNucSpotIdx, f->dNucRayWeights, f->dNucIdd, f->dNucRs};
+    auto launchFill = [&](auto kern, size_t lds) {
+        launchK(kern, fillGrid, fillBlk, lds, h->stream, nullptr, c.ev(3), (const float*)f->dDensity, (const float*)f->dWepl, (const float*)f->dRrl, f->dIdd,
+                f->dRSigma, (const float*)f->dRayWeights, (const int*)f->dFirstInside, (const int*)f->dFirstOutside,
+                f->dFirstPassive, f->dTileRad, f->dLayers, f->dState, h->lut, f->fillGeom, fc, (const float*)f->dStepTab, f->dActive, h->numCUs, f->dFillDbg, nucFill, f->dSigMin, f->dSigMax, c.tryUniform ? 1 : 0);
+    };
+    const bool ldsLut = fillLds <= 56 * 1024;     // (+ ~1 KiB of static arrays: stays under the 64 KiB default cap of a block's LDS)
+    constexpr size_t sigLds = (size_t)2 * kFillBatch * 256 * sizeof(float);   // the sigma walk's exchange buffers share the dynamic LDS with the dose walk's LUT rows
+    const size_t dynLds = std::max(sigLds, ldsLut ? fillLds : (size_t)0);
+    if (fc.nuclearCorr) { if (ldsLut) launchFill((k_fill<true, true>), dynLds); else launchFill((k_fill<false, true>), dynLds); }
+    else { if (ldsLut) launchFill((k_fill<true, false>), dynLds); else launchFill((k_fill<false, false>), dynLds); }
+}
+
+// K6, K7: the superposition's plan, the halo, and the superposition itself (uniform, sweep, big sweep or mfma).
+static int launchSuperposition(const ComputeJob& c) {
+    rtd_handle_impl* h = c.h; rtd_field_impl* f = c.f; const FieldConst& fc = f->fc; hipStream_t s = h->stream;
+    const bool tryUniform = c.tryUniform, knownUniform = c.knownUniform;
     if (fc.nuclearCorr) {
         // the halo's plan runs first: its radius overflow (kernel_wrapper.cu:984) is reported in the primary state, which k_ks_plan mirrors
         k_nuc_plan<<<1, 256, 0, s>>>(f->dState, f->dStateNuc, (const LayerPlan*)f->dLayers, (const float*)f->dNucRs, f->dNucEffT, fc,
@@ -794,7 +805,7 @@ int rtd_field_compute_bev(rtd_handle hh, rtd_field ff) {
         k_nuc_superpose<<<(nPix + 255) / 256, 256, 0, s>>>((const float*)f->dNucIdd, (const float*)f->dNucRs, (const int*)f->dNucEffT,
                                                            (const FieldState*)f->dStateNuc, fc, f->dNucBev);
     }
-    hipEvent_t ksStart = ev(7);
+    hipEvent_t ksStart = c.ev(7);
     if (tryUniform) {
         // A field with one sigma per slice (water) is superposed as a separable convolution; whether this field is one is known
         // on the device only (FieldState::uniformField): the launch returns at once otherwise, k_superpose_mfma below when it is.
@@ -858,6 +869,50 @@ int rtd_field_compute_bev(rtd_handle hh, rtd_field ff) {
         };
         if (split == 1) launchKs(k_superpose_mfma<1>); else if (split == 2) launchKs(k_superpose_mfma<2>); else launchKs(k_superpose_mfma<4>);
     }
+    return RTD_OK;
+}
+
+int rtd_field_compute_bev(rtd_handle hh, rtd_field ff) {
+    auto* h = reinterpret_cast<rtd_handle_impl*>(hh);
+    auto* f = reinterpret_cast<rtd_field_impl*>(ff);
+    if (!h || !f) return RTD_ERR_INVALID_ARG;
+    if (f->remote) return fail(h, RTD_ERR_INVALID_ARG, "rtd_field_compute_bev: a remote field has no workspace (attach a slab instead)");
+    if (!h->dCt || !h->haveLuts) return fail(h, RTD_ERR_NOT_READY, "rtd_field_compute: set LUTs and CT first");
+    RTD_HIP(h, hipSetDevice(h->device));   // one host thread may drive handles on several devices
+    const FieldConst& fc = f->fc;
+    hipStream_t s = h->stream;
+    // The trace and the plan of a finished compute stand while CT, LUTs and options do (inputEpoch; a bound device CT rewritten in place
+    // is announced by rtd_set_ct* like any other change): the launches in front of the convolution are then left out. Not with the
+    // halo, not for spot maps beyond k_plan_conv's rows, not with RTD_SEPARATE_PLAN (the full sequence, deliberately: DESIGN.md section
+    // 4), and never into a capturing stream: a graph must not depend on what the field knew when it was captured.
+    bool reuse = f->traceUsable && f->traceEpoch == h->inputEpoch && !f->sw.noTraceReuse && !f->sw.separatePlan && !fc.nuclearCorr &&
+                 fc.spotNy <= kPlanConvMaxRows;
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    RTD_HIP(h, hipStreamIsCapturing(s, &cs));
+    const bool capturing = cs != hipStreamCaptureStatusNone;
+    if (capturing) reuse = false;
+    if (!reuse) {
+        const int st = ensureCtBox(h, f); if (st != RTD_OK) return st;
+        // (a captured launch runs when its graph does, not now: it leaves no record)
+        f->traceUsable = false; f->traceLaunched = !capturing; f->traceEpoch = h->inputEpoch;
+    }
+    f->launchedReuse = reuse;
+    // the uniform-sigma detection and kernel are skipped for a field that was found heterogeneous under the same CT / LUTs / options
+    const bool tryUniform = f->uniformEligible && !(f->uniformHint == 0 && f->hintEpoch == h->inputEpoch);
+    f->triedUniform = tryUniform;
+    f->launchEpoch = h->inputEpoch;
+    // ... and a field that was found uniform under the same inputs will be found uniform again (the test is exact arithmetic on
+    // the same values): the general superposition kernel, all of whose ~10^5 blocks would only look at the flag and leave, is not launched
+    const bool knownUniform = tryUniform && f->uniformHint == 1 && f->hintEpoch == h->inputEpoch;
+    f->launchedKnownUniform = knownUniform;
+    const ComputeJob c{h, f, reuse, tryUniform, knownUniform, h->opt.fine_grained_timing != 0,
+        ResetJob{f->dLayers, fc.L, reinterpret_cast<unsigned int*>(f->dTileRad), f->tileRadWords, f->dActive, (size_t)4 * fc.L * fc.S,
+        f->dNucIdd, f->dNucRs, fc.nuclearCorr ? (size_t)fc.nucW * fc.nucH * fc.L : (size_t)0,
+        f->dSigMin, f->dSigMax, (size_t)fc.L * fc.S, f->dScanDbg}};
+    if (!reuse) { const int st = launchTrace(c); if (st != RTD_OK) return st; }
+    launchPlanConv(c);
+    launchFill(c);
+    { const int st = launchSuperposition(c); if (st != RTD_OK) return st; }
     RTD_HIP(h, hipGetLastError());
     f->computed = true;
     f->transferred = false;
@@ -872,68 +927,37 @@ static ClipBox makeClip(const int32_t* lo, const int32_t* hi) {
 
 // Part 2: fan -> dose-grid transfer (:1185-1218) of the field's BEV dose — its own, or the slab another GPU exported —
 // into dev_dose, optionally restricted to a box of the dose grid (a GPU's slab of the plan's volume).
-static int transferImpl(rtd_handle hh, rtd_field ff, float* dev_dose, const int32_t clip_min[3], const int32_t clip_max[3], bool init);
-int rtd_field_transfer(rtd_handle hh, rtd_field ff, float* dev_dose, const int32_t clip_min[3], const int32_t clip_max[3]) {
-    return transferImpl(hh, ff, dev_dose, clip_min, clip_max, false);
-}
-// The same transfer for the FIRST field into a volume that is zero everywhere except possibly inside this field's dose box: the
-// box is written (dose or zero), not accumulated into — no separate clear, no read of the old values.
-int rtd_field_transfer_init(rtd_handle hh, rtd_field ff, float* dev_dose, const int32_t clip_min[3], const int32_t clip_max[3]) {
-    return transferImpl(hh, ff, dev_dose, clip_min, clip_max, true);
-}
 static int transferImpl(rtd_handle hh, rtd_field ff, float* dev_dose, const int32_t clip_min[3], const int32_t clip_max[3], bool init) {
     auto* h = reinterpret_cast<rtd_handle_impl*>(hh);
     auto* f = reinterpret_cast<rtd_field_impl*>(ff);
     if (!h || !f || !dev_dose) return RTD_ERR_INVALID_ARG;
     if (!f->computed) return fail(h, RTD_ERR_NOT_READY, "rtd_field_transfer: no BEV dose (compute the field or attach a slab first)");
     RTD_HIP(h, hipSetDevice(h->device));
-    const FieldConst& fc = f->fc;
-    hipStream_t s = h->stream;
-    const dim3 blk(kSuperpTileX, kSuperpTileY);
     const ClipBox clip = makeClip(clip_min, clip_max);
-    const float* bev = f->remote ? reinterpret_cast<const float*>(f->attached + kPackHeader) : f->dBev;
-    const FieldState* st = f->remote ? reinterpret_cast<const FieldState*>(f->attached) : f->dState;
+    const FieldSlab own = fieldSlab(f);
     // depth of a brick along the axis a thread walks: 16 for a whole dose box; a clipped transfer (a GPU's slab of a multi-GPU
     // plan) has a fraction of the bricks and is latency-bound on the 4 rounds of a 16-deep brick: 4 there (measured on the four
     // quarter-slab transfers of the bench plan: 36 -> 32 us plain, 47 -> 39 us transposed)
     const int zChunk = (clip_min && clip_max) ? 4 : 16;
-    {
-        // grid-stride over the bricks of the device-side box; never more blocks than bricks of the whole volume
-        const size_t allBricks = (size_t)((f->doseDims[0] + 31) / 32) * ((f->doseDims[1] + 7) / 8) * ((f->doseDims[2] + zChunk - 1) / zChunk);
-        const unsigned tg = (unsigned)std::min<size_t>(allBricks, (size_t)h->numCUs * 8 * 4);
-        const bool halo = !f->remote && fc.nuclearCorr != 0;
-        auto launchT = [&](auto kern, const float* slab, const FieldState* state, hipEvent_t startEv, hipEvent_t stopEv) {
-            launchK(kern, dim3(tg), blk, 0, s, startEv, stopEv, dev_dose, (int)f->doseDims[0], (int)f->doseDims[1],
-                    (int)f->doseDims[2], slab, state, fc, zChunk, clip);
-        };
-        // lanes run along the dose axis that moves fastest along BEV x, so that the gathers stay within few BEV rows
-        hipEvent_t e0 = f->remote ? f->ev[0] : nullptr, e1 = halo ? nullptr : f->ev[6];
-        if (init && halo) return fail(h, RTD_ERR_INVALID_ARG, "rtd_field_transfer_init: not with nuclear_corr (the halo's box differs from the primary's)");
-        if (init) {
-            switch (f->transferMode) {
-                case 0: launchT((k_transfer<true>), bev, st, e0, e1); break;
-                case 1: launchT((k_transfer_t<1, true>), bev, st, e0, e1); break;
-                default: launchT((k_transfer_t<2, true>), bev, st, e0, e1); break;
-            }
-        } else {
-            switch (f->transferMode) {
-                case 0: launchT((k_transfer<false>), bev, st, e0, e1); break;
-                case 1: launchT((k_transfer_t<1, false>), bev, st, e0, e1); break;
-                default: launchT((k_transfer_t<2, false>), bev, st, e0, e1); break;
-            }
-        }
-        if (halo) {   // NUCLEAR_CORR: nucTransfDiv (kernel_wrapper.cu:100-127, launch :1221-1254) after the primary transfer, like the reference
-            switch (f->transferModeNuc) {
-                case 0: launchT((k_transfer<false>), (const float*)f->dNucBev, (const FieldState*)f->dStateNuc, nullptr, f->ev[6]); break;
-                case 1: launchT((k_transfer_t<1, false>), (const float*)f->dNucBev, (const FieldState*)f->dStateNuc, nullptr, f->ev[6]); break;
-                default: launchT((k_transfer_t<2, false>), (const float*)f->dNucBev, (const FieldState*)f->dStateNuc, nullptr, f->ev[6]); break;
-            }
-        }
-    }
+    const bool halo = !f->remote && f->fc.nuclearCorr != 0;
+    if (init && halo) return fail(h, RTD_ERR_INVALID_ARG, "rtd_field_transfer_init: not with nuclear_corr (the halo's box differs from the primary's)");
+    auto launchT = [&](int mode, bool write, const float* slab, const FieldState* state, hipEvent_t startEv, hipEvent_t stopEv) {
+        withTransferKernel(mode, write, [&](auto kern) {
+            launchK(kern, dim3(brickGrid(h, f, zChunk)), dim3(kSuperpTileX, kSuperpTileY), 0, h->stream, startEv, stopEv, dev_dose, (int)f->doseDims[0],
+                    (int)f->doseDims[1], (int)f->doseDims[2], slab, state, f->fc, zChunk, clip);
+        });
+    };
+    launchT(f->transferMode, init, own.bev, own.st, f->remote ? f->ev[0] : nullptr, halo ? nullptr : f->ev[6]);
+    // NUCLEAR_CORR: nucTransfDiv (kernel_wrapper.cu:100-127, launch :1221-1254) after the primary transfer, like the reference
+    if (halo) launchT(f->transferModeNuc, false, (const float*)f->dNucBev, (const FieldState*)f->dStateNuc, nullptr, f->ev[6]);
     RTD_HIP(h, hipGetLastError());
     f->transferred = true;
     return RTD_OK;
 }
+int rtd_field_transfer(rtd_handle hh, rtd_field ff, float* dev_dose, const int32_t clip_min[3], const int32_t clip_max[3]) { return transferImpl(hh, ff, dev_dose, clip_min, clip_max, false); }
+// The same transfer for the FIRST field into a volume that is zero everywhere except possibly inside this field's dose box: the
+// box is written (dose or zero), not accumulated into — no separate clear, no read of the old values.
+int rtd_field_transfer_init(rtd_handle hh, rtd_field ff, float* dev_dose, const int32_t clip_min[3], const int32_t clip_max[3]) { return transferImpl(hh, ff, dev_dose, clip_min, clip_max, true); }
 
 // Several fields (own BEV doses and / or attached slabs) into one box of the dose grid in one launch: every voxel of the
 // box is written with 0 + field 0 + field 1 + ... (k_transfer_multi) — the loop of rtd_field_transfer over the fields into a
@@ -957,8 +981,7 @@ int rtd_fields_transfer_init(rtd_handle hh, const rtd_field* fields, uint32_t n_
         if (!f->remote && f->fc.nuclearCorr) return fail(h, RTD_ERR_INVALID_ARG, "rtd_fields_transfer_init: not with nuclear_corr (the halo is transferred separately)");
         if (i == 0) std::memcpy(dims, f->doseDims, sizeof dims);
         else if (std::memcmp(dims, f->doseDims, sizeof dims) != 0) return fail(h, RTD_ERR_INVALID_ARG, "rtd_fields_transfer_init: fields of different dose grids");
-        mf.bev[i] = f->remote ? reinterpret_cast<const float*>(f->attached + kPackHeader) : f->dBev;
-        mf.st[i] = f->remote ? reinterpret_cast<const FieldState*>(f->attached) : f->dState;
+        mf.bev[i] = fieldSlab(f).bev; mf.st[i] = fieldSlab(f).st;
         mf.mode[i] = f->transferMode;
         if (!f->remote || !lead) lead = f;                            // the last own field, else the first field
     }
@@ -991,14 +1014,10 @@ int rtd_field_clear_dose_box(rtd_handle hh, rtd_field ff, float* dev_dose, const
     if (!f->computed) return fail(h, RTD_ERR_NOT_READY, "rtd_field_clear_dose: field not computed");
     RTD_HIP(h, hipSetDevice(h->device));
     const int zChunk = 16;
-    const size_t allBricks = (size_t)((f->doseDims[0] + 31) / 32) * ((f->doseDims[1] + 7) / 8) * ((f->doseDims[2] + zChunk - 1) / zChunk);
-    const unsigned g = (unsigned)std::min<size_t>(allBricks, (size_t)h->numCUs * 8 * 4);
-    const FieldState* st = f->remote ? reinterpret_cast<const FieldState*>(f->attached) : f->dState;
-    k_clear_box<<<g, dim3(kSuperpTileX, kSuperpTileY), 0, h->stream>>>(dev_dose, (int)f->doseDims[0], (int)f->doseDims[1], st, zChunk,
-                                                                       makeClip(clip_min, clip_max));
+    const dim3 g(brickGrid(h, f, zChunk)), blk(kSuperpTileX, kSuperpTileY);
+    k_clear_box<<<g, blk, 0, h->stream>>>(dev_dose, (int)f->doseDims[0], (int)f->doseDims[1], fieldSlab(f).st, zChunk, makeClip(clip_min, clip_max));
     if (!f->remote && f->fc.nuclearCorr)     // the halo's dose box (its slice reaches further sideways than the primary's)
-        k_clear_box<<<g, dim3(kSuperpTileX, kSuperpTileY), 0, h->stream>>>(dev_dose, (int)f->doseDims[0], (int)f->doseDims[1],
-                                                                           (const FieldState*)f->dStateNuc, zChunk, makeClip(clip_min, clip_max));
+        k_clear_box<<<g, blk, 0, h->stream>>>(dev_dose, (int)f->doseDims[0], (int)f->doseDims[1], (const FieldState*)f->dStateNuc, zChunk, makeClip(clip_min, clip_max));
     RTD_HIP(h, hipGetLastError());
     return RTD_OK;
 }

@@ -1,0 +1,346 @@
+// rtd_fill.hpp — K5 of the dose path: the IDD + sigma fill, fillIddAndSigma (kernel_wrapper.cu:190-379), with the reductions and
+// the tile classification that follow it in the reference (:952-957, kernel_wrapper.cuh:256-313).
+//
+// Kernel: k_fill<LDS_LUT, NUC>.
+#pragma once
+#include "rtd_field_state.hpp"
+#include "rtd_plan_conv.hpp"   // rtd_pow_det: rtd_detmath.h as device code
+
+namespace rtd {
+
+// K5: IDD + sigma fill = fillIddAndSigma without NUCLEAR_CORR (kernel_wrapper.cu:190-379), all energy layers in
+// one launch, fused with the reductions and the classification that follow it in the reference: layerFirstPassive
+// (sliceMaxVar, :952-957) and the per-tile radius class + histogram (tileRadCalc, kernel_wrapper.cuh:256-313).
+//
+// Block = one (layer, 32x8 classification tile, ROLE) = 4 waves: every ray is walked by TWO threads (of different blocks).
+// The reference's step computes two things that share nothing but the liveness of the ray (a function of WEPL alone):
+//   role 0, the sigma walk:  residual-range power, betaP, thetaSq and the serial sums sigmaSq / incScat / incincScat /
+//                            incDiv (:276-303) -> 1/sigma; per batch of steps the tile's radius class and histogram;
+//   role 1, the dose walk:   cumulative-IDD lookup (:269-274), mass and the dose value (:305-322); per batch the rectangle
+//                            of the tile's rays that carry dose.
+// The serial chains exist once per (ray, layer) — L*R/64 = 2640 waves on C3, 2.6 per SIMD — which is why the single-role form
+// of this kernel sat at 61 % of its own instruction-issue bound; two roles double the waves per SIMD and halve each chain.
+//
+// INDEX WORK IS BIT-EXACT. 1/sigma feeds an integer: the tile minimum is thresholded into the radius class. Everything the
+// class depends on is therefore computed with correctly rounded IEEE operations in the reference's order: the power with
+// rtd_pow_det (include/rtd_detmath.h, shared with the host-side checker of the test suite — the reference's __powf is a hardware approximation),
+// both divisions of betaP / thetaSq with IEEE division, the sums as written. The per-ray 1/sigma that the superposition reads
+// for its weights uses the hardware sqrt / reciprocal (<= 2 ulp; the reference builds with -use_fast_math), but the tile's class
+// does not come from those values: x -> step/(sqrt2*(sqrt(x)+delta)) is monotone under correct rounding, so the tile
+// minimum of the exact 1/sigma equals that function of the tile MAXIMUM of sigmaSq, evaluated once per (step, tile) with
+// IEEE sqrt and division.
+
+constexpr int kFillBatch = 8;   // steps per batch: inputs fetched one batch ahead, one block barrier per batch
+constexpr int kFillSnakeRounds = 12;   // up to this many walks per CU the walks are dealt in rounds of alternating direction (k_fill's block placement)
+
+// NUCLEAR_CORR arguments of the fill (kernel_wrapper.cu:190-198). The reference constructs its fill parameters with a nuclear
+// memory step of 0 (:925), so every step of a ray overwrites the same voxel of the nuclear arrays (:367-373) and what remains
+// after a layer's launch is the value of the LAST step, in plane 0. The engine keeps exactly that: one plane per layer, written
+// once after the walk.
+struct NucFill {
+    const int* spotIdx;            // [H][W] the ray's spot on the nuclear grid, -1 if none (kernel_wrapper.cu:878-892)
+    const float* rayWeights;       // [L][nucH][nucW] padded spot weights (extendAndPadd, :51-66)
+    float* idd; float* rs;         // [L][nucH][nucW] plane 0 of the reference's nuclear arrays after layer l
+};
+
+// NUC: NUCLEAR_CORR compiled in (its table lookups and IEEE divisions cost registers: the default build keeps 6 blocks per CU)
+template <bool LDS_LUT, bool NUC>
+__global__ __launch_bounds__(256) void k_fill(const float* __restrict__ bevDensity, const float* __restrict__ bevCumulSp,
+                                               const float* __restrict__ bevRrl,
+                                               float* __restrict__ bevIdd, float* __restrict__ bevRSigmaEff,
+                                               const float* __restrict__ rayWeights, const int* __restrict__ firstInside,
+                                               const int* __restrict__ firstOutside, int* __restrict__ firstPassive,
+                                               unsigned char* __restrict__ tileRad, LayerPlan* layers, FieldState* st,
+                                               LutView lut, FillGeom fg, FieldConst fc, const float* __restrict__ stepTab,
+                                               int* __restrict__ active, int nCU, long long* __restrict__ dbg, NucFill nuc,
+                                               unsigned int* __restrict__ sigMin, unsigned int* __restrict__ sigMax, int trackUniform) {
+    extern __shared__ float sLutF[];                                 // dose walk: the layer's two cumulative-IDD rows
+    // diagnostic build only (RTD_FILL_DEBUG): per walk start / end clock, hardware id, item — no output value depends on it
+    // sigma walk: [buffer][step][ray] sigmaSq of the rays with a finite 1/sigma (-1: none) — in the same dynamic LDS as the dose walk's
+    // LUT rows (a block is one or the other: 16 KB instead of 16 + 8, a seventh block per CU where the walks outnumber the slots)
+    float (*sSig)[kFillBatch][256] = reinterpret_cast<float (*)[kFillBatch][256]>(sLutF);
+    __shared__ unsigned long long sDoseMask[2][kFillBatch][4];       // dose walk: [buffer][step][wave] ballot of the rays that carry dose
+    __shared__ int sHist[kMaxSuperpR + 2];
+    __shared__ int sClassLo[kMaxSuperpR + 2], sClassHi[kMaxSuperpR + 2];   // sigma walk: first / last step of this walk with a tile of that radius class
+    __shared__ int sUni;                                             // sigma walk: every tile of this block so far had ONE sigma^2 over its live rays
+
+    // Block placement. The walks differ in cost — the number of steps per layer (150..210 on C3), and a sigma walk is ~1.5 dose
+    // walks — while only 2*L*tiles blocks exist (5.2 per CU on C3), so a plain grid leaves the kernel waiting for the CUs that
+    // happened to receive the long walks (measured with per-block clock stamps: a CU with five sigma walks of the longest layers
+    // took 430 k cycles, one with five dose walks 200 k). When all blocks are co-resident the dispatcher places block b on CU
+    // b % nCU (measured: blocks b and b + nCU always share a CU), so the walks, taken in descending order of cost (k_plan), are
+    // dealt in rounds of nCU that alternate direction — a CU that got an expensive walk in one round gets a cheap one in the
+    // next — with the direction chosen so that the last, partial round (the cheapest walks) lands on the CUs that received the
+    // cheapest walks of the last full round. (Performance only: any placement gives the same result.)
+    // (More walks than can be co-resident — the reference's water cube: 2560 on 256 CUs — are still dealt this way, up to
+    //  kFillSnakeRounds per CU: the first rounds land as described, the rest wherever a slot frees. Measured and dropped there: as many
+    //  blocks as fit the GPU at once, each taking walk after walk from a ticket counter in descending order of cost — the loop costs
+    //  the kernel 23 registers, 5 blocks per CU instead of 7: 0.325 ms against 0.27.)
+    const int nTiles = fc.tilesX * fc.tilesY, nB = 2 * nTiles * fc.L;
+    const int tid = threadIdx.y * 32 + threadIdx.x;                  // ray of the tile
+    int item = blockIdx.x;
+    if (nB <= kFillSnakeRounds * nCU) {
+        const int rr = blockIdx.x / nCU, c = blockIdx.x % nCU, nFull = nB / nCU;
+        const bool reversed = rr < nFull && ((nFull - 1 - rr) & 1) == 0;       // the last full round: CU 0 gets its cheapest walk
+        item = rr * nCU + (reversed ? nCU - 1 - c : c);
+    }
+    const long long dbgT0 = dbg ? (long long)__builtin_amdgcn_s_memtime() : 0;
+    const int pr = st->fillItems[item / nTiles];
+    const int layer = pr >> 1;
+    const int role = pr & 1;                                         // block-uniform: 0 sigma walk, 1 dose walk
+    // (the tile is rotated with the walk's index: when the tile count divides the CU count — 64 tiles on 256 CUs, the reference's water
+    //  cube — block b and b + nCU would otherwise hold the same tile, and the CUs of the cheap edge tiles would get cheap walks in every round:
+    //  measured 1.2 M against 2.6 M block-cycles per CU)
+    const int tileNo = (item % nTiles + (item / nTiles) * 5) % nTiles, tileX = tileNo % fc.tilesX, tileY = tileNo / fc.tilesX;
+    const int wave = tid >> 6;
+    const int x = tileX * kSuperpTileX + threadIdx.x;
+    const int y = tileY * kSuperpTileY + threadIdx.y;
+    const int W = fc.W, H = fc.H;
+    const size_t memStep = (size_t)W * H;
+    const size_t layerOff = (size_t)layer * memStep * fc.S;
+    const size_t rayIdx = (size_t)y * W + x;
+    const unsigned int rayOff = (unsigned int)rayIdx;
+
+    const LayerPlan lp = layers[layer];
+    const unsigned int pFirst = (unsigned int)st->beamFirstInside;
+    const unsigned int pAfterLast = st->empty ? pFirst : (unsigned int)lp.afterLast;
+
+    // liveness of the ray (:236-243, :308-311): a function of WEPL, the ray weight and the cut-off steps — both roles track it
+    bool beamLive = true;
+    const int firstIn = firstInside[rayIdx];
+    const int fo = firstOutside[rayIdx];
+    unsigned int afterLast = (unsigned int)(fo < (int)pAfterLast ? fo : (int)pAfterLast);
+    const float rayWeight = rayWeights[(size_t)layer * memStep + rayIdx];
+    if (rayWeight < fc.rayWeightCutoff || afterLast < pFirst) { beamLive = false; afterLast = 0; }
+    const float cutDepth = lp.peakDepth * fc.bpDepthCutoff;
+    float cumulSpOld = 0.0f;
+    const float sqrt2 = 1.41421356f;
+
+    if (role == 0) {
+        // ================================ sigma walk ================================
+        if (tid < kMaxSuperpR + 2) { sHist[tid] = 0; sClassLo[tid] = 0x7fffffff; sClassHi[tid] = -1; }
+        if (tid == 0) sUni = trackUniform;                           // 0: the field is known not to be uniform (or not eligible): nothing is tracked
+        const float pInv = 0.5649718f, eCoef = 8.639415f;
+        // E_s^2 and the empirical widening per NUCLEAR_CORR variant (kernel_wrapper.cu:228-245)
+        const float eRefSq = !NUC ? 198.81f : fc.nuclearCorr == 1 ? 190.44f : fc.nuclearCorr == 2 ? 216.09f : fc.nuclearCorr == 3 ? 169.00f : 198.81f;
+        const float sigmaDeltaV = !NUC ? 0.21f : fc.nuclearCorr == 1 ? 0.0f : fc.nuclearCorr == 2 ? 0.08f : fc.nuclearCorr == 3 ? 0.06f : 0.21f;
+        const int nucIdx = NUC && fc.nuclearCorr ? nuc.spotIdx[rayIdx] : -1;
+        const float entrySigmaSq = lp.entrySigmaX * lp.entrySigmaX;  // FillIddAndSigmaParams::getEntrySigmaSq (:925, 4th argument)
+        float nucRSigmaEff = __int_as_float(0x7f800000);
+        float rSigmaEff = 0.0f, incScat = 0.0f, incincScat = 0.0f;
+        float incDiv = lp.sigmaSqAirLin + (2.0f * (float)pFirst - 1.0f) * lp.sigmaSqAirQuad;
+        float sigmaSq = -incDiv;
+        // Inputs are fetched one batch ahead of the walk (a round trip per batch was 290 cycles per step), in a rolling fashion:
+        // as soon as a step has consumed its register slot, the slot takes the load of the step one batch later.
+        float spB[kFillBatch], denB[kFillBatch], rrlB[kFillBatch];
+        auto fetch1 = [&](int j, unsigned int stepNo) {              // wave-uniform slice base + the lane's ray offset
+            spB[j] = 0.0f; denB[j] = 0.0f; rrlB[j] = 0.0f;
+            if (stepNo < pAfterLast) {
+                spB[j] = (bevCumulSp + (size_t)stepNo * memStep)[rayOff];
+                denB[j] = (bevDensity + (size_t)stepNo * memStep)[rayOff];
+                rrlB[j] = (bevRrl + (size_t)stepNo * memStep)[rayOff];
+            }
+        };
+#pragma unroll
+        for (int j = 0; j < kFillBatch; ++j) fetch1(j, pFirst + j);
+        __syncthreads();
+        int buf = 0;
+        for (unsigned int step0 = pFirst; step0 < pAfterLast; step0 += kFillBatch, buf ^= 1) {
+#pragma unroll
+            for (int j = 0; j < kFillBatch; ++j) {
+                const unsigned int stepNo = step0 + j;
+                if (stepNo >= pAfterLast) { sSig[buf][j][tid] = -1.0f; continue; }   // block-uniform
+                const float cumulSp = spB[j], density = denB[j], rRl = rrlB[j];
+                fetch1(j, stepNo + kFillBatch);
+                if (beamLive) {
+                    if (cumulSp < lp.peakDepth) {
+                        const float resE = eCoef * rtd_pow_det(lp.peakDepth - 0.5f * (cumulSp + cumulSpOld), pInv);
+                        const float betaP = resE + 938.3f - 938.3f * 938.3f / (resE + 938.3f);
+                        const float thetaSq = eRefSq / (betaP * betaP) * fg.stepLength * rRl;
+                        sigmaSq += incScat + incDiv;
+                        incincScat += 2.0f * thetaSq * fg.stepLength * fg.stepLength;
+                        incScat += incincScat;
+                        incDiv += 2.0f * lp.sigmaSqAirQuad;
+                    } else {
+                        if (!NUC || fc.nuclearCorr != 3) sigmaSq -= 1.5f * (incScat + incDiv) * density;   // (not for GAUSS_FIT, :300-302)
+                    }
+                    // stepTab[2k] = 0.5*(voxelWidth(k).x + voxelWidth(k).y): per-step constant evaluated once on the host with the
+                    // reference's expressions (fill_idd_and_sigma_params.cu:42-46). Hardware sqrt / reciprocal: this value only
+                    // weights the superposition; the radius class comes from sigmaSq itself (below).
+                    rSigmaEff = stepTab[2 * stepNo] * __builtin_amdgcn_rcpf(sqrt2 * (__builtin_amdgcn_sqrtf(sigmaSq) + sigmaDeltaV));
+                    if (NUC && nucIdx >= 0) {                        // :332-341 (IEEE: its tile minimum becomes a radius class too)
+                        const float nucSqSigma = sample2dClamp(lut.nucSqSigma, lut.nSamples, lut.nEnergies,
+                                                               0.5f * (cumulSp + cumulSpOld) * lp.energyScaleFact, lp.energyIdx);
+                        const Vec2 vw = fg.voxelWidth(stepNo);
+                        nucRSigmaEff = 0.5f * fc.spotDist * (vw.x + vw.y) / (sqrt2 * sqrtf(sigmaSq + nucSqSigma + entrySigmaSq));
+                    }
+                    if (cumulSp > cutDepth || stepNo == afterLast) { beamLive = false; afterLast = stepNo; }
+                    cumulSpOld = cumulSp;
+                }
+                float sig = sigmaSq;
+                if (!beamLive || (int)stepNo < (firstIn - 1)) { rSigmaEff = __int_as_float(0x7f800000); sig = -1.0f; nucRSigmaEff = __int_as_float(0x7f800000); }
+                (bevRSigmaEff + layerOff + (size_t)stepNo * memStep)[rayOff] = rSigmaEff;
+                sSig[buf][j][tid] = sig;
+            }
+            ldsBarrier();                                            // the only barrier of a batch (sSig is double-buffered)
+            {   // fused tileRadCalc: radius class of every (layer, step, tile) of the batch, 32 lanes per step
+                const int j = tid >> 5, l = tid & 31;                // step of the batch, lane of its 32-lane group
+                // (uniform-sigma detection, while the block has seen nothing else: the smallest sigma^2 of the live rays as well —
+                //  a block of a heterogeneous field drops this after its first batch)
+                const bool uni = sUni != 0;                          // block-uniform (written before the previous batch's barrier)
+                const float inf = __int_as_float(0x7f800000);
+                float m = sSig[buf][j][l];
+                float mn = m >= 0.0f ? m : inf;
+#pragma unroll
+                for (int k = 1; k < 8; ++k) {
+                    const float t = sSig[buf][j][l + 32 * k];
+                    m = t > m ? t : m;
+                    if (uni) { const float tl = t >= 0.0f ? t : inf; mn = tl < mn ? tl : mn; }
+                }
+                m = -halfWaveMin(-m);                                // lanes 31 / 63 hold the maximum of their 32-lane half
+                if (uni) mn = halfWaveMin(mn);
+                if (uni && l == 31 && step0 + j < pAfterLast && m >= 0.0f) {
+                    if (mn != m) { sUni = 0; st->nonUniform = 1; }
+                    else {
+                        const size_t si = (size_t)layer * fc.S + step0 + j;
+                        atomicMin(&sigMin[si], __float_as_uint(m));  // (sigma^2 >= 0: the bit patterns order like the values)
+                        atomicMax(&sigMax[si], __float_as_uint(m));
+                    }
+                }
+                if (l == 31 && step0 + j < pAfterLast) {
+                    // tile minimum of 1/sigma (= the reference's minVal, kernel_wrapper.cuh:282-297) from the tile maximum of
+                    // sigmaSq with IEEE sqrt and division, then the class exactly as the reference computes it (:300-305)
+                    const float minRs = m >= 0.0f ? stepTab[2 * (step0 + j)] / (sqrt2 * (sqrtf(m) + sigmaDeltaV)) : __int_as_float(0x7f800000);
+                    int rad = f2iSat(fc.ksSigmaCutoff / (sqrtf(2.0f) * minRs) + 0.5f);
+                    rad = rad > kMaxSuperpR + 1 ? kMaxSuperpR + 1 : rad;
+                    rad = rad < 0 ? 0 : rad;
+                    tileRad[((size_t)layer * fc.S + step0 + j) * nTiles + tileNo] = (unsigned char)rad;
+                    atomicAdd(&sHist[rad], 1);
+                    atomicMin(&sClassLo[rad], (int)(step0 + j));
+                    atomicMax(&sClassHi[rad], (int)(step0 + j));
+                }
+            }
+        }
+        firstPassive[(size_t)layer * memStep + rayIdx] = (int)afterLast;
+        if (NUC && nucIdx >= 0 && pFirst < pAfterLast) nuc.rs[(size_t)layer * fc.nucW * fc.nucH + nucIdx] = nucRSigmaEff;   // value of the last step (:367-373)
+        int mx = waveMaxI((int)afterLast);
+        if ((tid & (kWave - 1)) == 0) atomicMax(&layers[layer].layerFirstPassive, mx);
+        __syncthreads();
+        if (tid < kMaxSuperpR + 2 && sHist[tid] > 0) {
+            atomicAdd(&layers[layer].hist[tid], sHist[tid]);
+            atomicMin(&layers[layer].classLo[tid], sClassLo[tid]);
+            atomicMax(&layers[layer].classHi[tid], sClassHi[tid]);
+        }
+    } else {
+        // ================================ dose walk ================================
+        // cumulative IDD: rows floor(energyIdx), floor(energyIdx)+1 (CLAMP) and the row weight are layer constants
+        int ey0, ey1; float eay;
+        {
+            float py = lp.energyIdx, fy = floorf(py);
+            eay = py - fy; ey0 = (int)fy; ey1 = ey0 + 1;
+            if (!(py >= 0.0f)) { ey0 = 0; ey1 = 0; eay = 0.0f; }
+            ey0 = ey0 > lut.nEnergies - 1 ? lut.nEnergies - 1 : ey0;
+            ey1 = ey1 > lut.nEnergies - 1 ? lut.nEnergies - 1 : ey1;
+        }
+        const float* gRow0 = lut.cidd + (size_t)ey0 * lut.nSamples;
+        const float* gRow1 = lut.cidd + (size_t)ey1 * lut.nSamples;
+        float* sRow0 = sLutF;
+        float* sRow1 = sLutF + lut.nSamples;
+        if (LDS_LUT) for (int i = tid; i < lut.nSamples; i += 256) { sRow0[i] = gRow0[i]; sRow1[i] = gRow1[i]; }
+        float res = 0.0f, cumulDoseOld = 0.0f;
+        const int nucIdx = NUC && fc.nuclearCorr ? nuc.spotIdx[rayIdx] : -1;
+        const float nucRayWeight = nucIdx >= 0 ? nuc.rayWeights[(size_t)layer * fc.nucW * fc.nucH + nucIdx] : 0.0f;
+        float nucRes = 0.0f;
+        int actUni = 0x7fffffff;
+        float spB[kFillBatch], denB[kFillBatch];
+        auto fetch1 = [&](int j, unsigned int stepNo) {
+            spB[j] = 0.0f; denB[j] = 0.0f;
+            if (stepNo < pAfterLast) {
+                spB[j] = (bevCumulSp + (size_t)stepNo * memStep)[rayOff];
+                if (!fc.doseToWater) denB[j] = (bevDensity + (size_t)stepNo * memStep)[rayOff];
+            }
+        };
+#pragma unroll
+        for (int j = 0; j < kFillBatch; ++j) fetch1(j, pFirst + j);
+        __syncthreads();
+        int buf = 0;
+        for (unsigned int step0 = pFirst; step0 < pAfterLast; step0 += kFillBatch, buf ^= 1) {
+            unsigned long long doseMask[kFillBatch];
+#pragma unroll
+            for (int j = 0; j < kFillBatch; ++j) {
+                const unsigned int stepNo = step0 + j;
+                doseMask[j] = 0ull;
+                if (stepNo >= pAfterLast) continue;                  // block-uniform
+                const float cumulSp = spB[j], density = denB[j];
+                fetch1(j, stepNo + kFillBatch);
+                if (beamLive) {
+                    float cumulDose;
+                    {   // tex2D(cumulIddTex, ...) :269-274, rows and row weight hoisted
+                        float px = cumulSp * lp.energyScaleFact;
+                        float fx = floorf(px), ax = px - fx;
+                        int x0 = (int)fx, x1 = x0 + 1;
+                        if (!(px >= 0.0f)) { x0 = 0; x1 = 0; ax = 0.0f; }
+                        x0 = x0 > lut.nSamples - 1 ? lut.nSamples - 1 : x0; x1 = x1 > lut.nSamples - 1 ? lut.nSamples - 1 : x1;
+                        float r0 = LDS_LUT ? lerpW(ax, sRow0[x0], sRow0[x1]) : lerpW(ax, gRow0[x0], gRow0[x1]);
+                        float r1 = LDS_LUT ? lerpW(ax, sRow1[x0], sRow1[x1]) : lerpW(ax, gRow1[x0], gRow1[x1]);
+                        cumulDose = lerpW(eay, r0, r1);
+                    }
+                    if (cumulSp > cutDepth || stepNo == afterLast) { beamLive = false; afterLast = stepNo; }
+                    // stepTab[2k+1] = stepVol(k) (fill_idd_and_sigma_params.cu:72)
+                    const float stepVol = stepTab[2 * stepNo + 1];
+                    const float mass = fc.doseToWater ? (cumulSp - cumulSpOld) * stepVol : density * stepVol;
+                    // (the dose value feeds no threshold other than res > 0, which a reciprocal cannot change: hardware reciprocal, <= 1 ulp)
+                    if (!NUC || !fc.nuclearCorr) {
+                        if (mass > 1e-2f) res = rayWeight * (cumulDose - cumulDoseOld) * __builtin_amdgcn_rcpf(mass);
+                    } else if (mass > 1e-2f) {                       // :320-331: the primary keeps (1 - nucWeight), the halo gets nucWeight
+                        const float nucWeight = sample2dClamp(lut.nucWeight, lut.nSamples, lut.nEnergies,
+                                                              0.5f * (cumulSp + cumulSpOld) * lp.energyScaleFact, lp.energyIdx);
+                        res = (1.0f - nucWeight) * rayWeight * (cumulDose - cumulDoseOld) * __builtin_amdgcn_rcpf(mass);
+                        nucRes = nucWeight * nucRayWeight * (cumulDose - cumulDoseOld) / (mass * fc.spotDist * fc.spotDist);
+                    }
+                    cumulSpOld = cumulSp;
+                    cumulDoseOld = cumulDose;
+                }
+                if (!beamLive || (int)stepNo < (firstIn - 1)) { res = 0.0f; nucRes = 0.0f; }
+                (bevIdd + layerOff + (size_t)stepNo * memStep)[rayOff] = res;
+                doseMask[j] = __ballot(res > 0.0f);
+            }
+            if ((tid & (kWave - 1)) == 0) {
+#pragma unroll
+                for (int j = 0; j < kFillBatch; ++j) sDoseMask[buf][j][wave] = doseMask[j];
+            }
+            ldsBarrier();                                            // the only barrier of a batch (sDoseMask is double-buffered)
+            // rectangle of the tile's rays that carry dose at step j, as minima of (x, y, -x, -y): lanes 0..3 of the step's group,
+            // one component each, from the four waves' ballots (wave w holds rows 2w, 2w+1 of the tile: low / high 32 bits)
+            const int j = tid >> 5, l = tid & 31;
+            if (l < 4 && step0 + j < pAfterLast) {
+                unsigned int colMask = 0u, rowMask = 0u;             // columns / rows of the tile with dose
+#pragma unroll
+                for (int w = 0; w < 4; ++w) {
+                    const unsigned long long dm = sDoseMask[buf][j][w];
+                    const unsigned int lo = (unsigned int)dm, hi = (unsigned int)(dm >> 32);
+                    colMask |= lo | hi;
+                    rowMask |= (lo ? 1u : 0u) << (2 * w) | (hi ? 1u : 0u) << (2 * w + 1);
+                }
+                if (colMask) {
+                    const int x0t = tileX * kSuperpTileX, y0t = tileY * kSuperpTileY;
+                    const int v = l == 0 ? x0t + __builtin_ctz(colMask) : l == 1 ? y0t + __builtin_ctz(rowMask)
+                                : l == 2 ? -(x0t + 31 - __builtin_clz(colMask)) : -(y0t + 31 - __builtin_clz(rowMask));
+                    atomicMin(&active[((size_t)layer * fc.S + step0 + j) * 4 + l], v);
+                    actUni = min(actUni, v);
+                }
+            }
+        }
+        if ((tid & 31) < 4 && actUni != 0x7fffffff) atomicMin(&st->actUnion[tid & 3], actUni);
+        if (NUC && nucIdx >= 0 && pFirst < pAfterLast) nuc.idd[(size_t)layer * fc.nucW * fc.nucH + nucIdx] = nucRes;   // value of the last step (:367-373)
+    }
+    if (dbg && tid == 0) {
+        long long* q = dbg + 4 * (size_t)item;
+        q[0] = dbgT0; q[1] = (long long)__builtin_amdgcn_s_memtime();
+        q[2] = ((long long)__builtin_amdgcn_s_getreg((20 << 0) | (0 << 6) | (3 << 11)) << 32) | (unsigned)__builtin_amdgcn_s_getreg((4 << 0) | (0 << 6) | (31 << 11));
+        q[3] = ((long long)item << 8) | (long long)(role << 4) | 0;
+        (void)pAfterLast;
+    }
+}
+
+}  // namespace rtd

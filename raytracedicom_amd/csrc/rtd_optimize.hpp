@@ -111,8 +111,7 @@ __global__ __launch_bounds__(256) void k_obj_reduce(const double* __restrict__ p
 
 // Zeroes the box's voxels of a volume (the row box of a field other than the first, in front of the forward product).
 __global__ __launch_bounds__(256) void k_opt_clear_box(float* __restrict__ vol, int nx, int ny, DijBox box, long long nRows) {
-    const long long r = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (r < nRows) vol[dijBoxVoxel(r, nx, ny, box)] = 0.0f;
+    dijClearBoxVoxel(vol, nx, ny, box, nRows);
 }
 
 // part[c], part[nCh + c], part[2 nCh + c] = <s, s>, <s, y>, max |P(w - grad) - w| over chunk c.

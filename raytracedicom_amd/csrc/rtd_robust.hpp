@@ -60,8 +60,7 @@ static_assert(sizeof(RobustFwd) + 64 <= 4096 && sizeof(RobustAdj) + 64 <= 4096, 
 
 __global__ __launch_bounds__(256) void k_robust_clear_box(RobustClear a, int nx, int ny) {
     const int s = blockIdx.y;
-    const long long nRows = a.nRows[s], r = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (r < nRows) a.dose[s][dijBoxVoxel(r, nx, ny, a.box[s])] = 0.0f;
+    dijClearBoxVoxel(a.dose[s], nx, ny, a.box[s], a.nRows[s]);
 }
 
 // k_dijap_apply<INIT> with blockIdx.y the scenario. A block past the scenario's rows leaves (uniform: its first row decides).

@@ -2,7 +2,7 @@
 //
 // Same arithmetic as kernelSuperposition<rad> (reference src/kernel_wrapper.cuh:432-489): every source voxel s of a BEV slice adds
 // the separable patch  dose_s * e_s[|dy|] * e_s[|dx|],  |dy|, |dx| <= rho_s  (rho_s = batch radius of its 32 x 8 tile, e_s = the
-// erf-difference weights of ITS OWN 1/sigma, kernel_wrapper.cuh:459-467). k_superpose_mfma (rtd_kernels.hpp) owns OUTPUT tiles and
+// erf-difference weights of ITS OWN 1/sigma, kernel_wrapper.cuh:459-467). k_superpose_mfma (rtd_superpose_mfma.hpp) owns OUTPUT tiles and
 // visits, per 16 x 16 tile, every source quad whose patch touches it: 4 MFMAs per quad at rho ~ 8, ~13 vector + ~10 scalar
 // instructions of address arithmetic per MFMA, and every source's weight table built by each of the ~1.9 output tiles it reaches
 // (profiles/r02_pmc_sq_superpose.txt). This kernel turns the loops around:
@@ -33,7 +33,9 @@
 // Measured and dropped (C3, parity-green): 16 waves per block that leave their T in LDS and, after a barrier, gather the rows of the
 // tile they own (no ticket; tile in registers): one block per CU, so nothing overlaps the gather phases — 0.51 ms against 0.35 ms.
 #pragma once
-#include "rtd_kernels.hpp"
+#include "rtd_field_state.hpp"
+#include "rtd_plan_conv.hpp"   // rtd_erf_det
+#include "rtd_ks_plan.hpp"
 
 namespace rtd {
 

@@ -34,10 +34,11 @@
 // instructions of a wave ~4000 (two waves per SIMD). Spreading the loads over the column blocks moved the wait into the store
 // (0.19 ms, more registers): the layer's rows arrive at ~2.4 TB/s over all CUs, twice the unique bytes (the blocks' reaches overlap).
 #pragma once
-#include "rtd_kernels.hpp"
+#include "rtd_field_state.hpp"
 
 namespace rtd {
 
+constexpr int kUniMaxBevH = 256;                                     // a slice has at most 16 row blocks of 16 rows
 constexpr int kU2XB = 12;                            // output column blocks per wave (192 columns: the padded BEV of a 128-ray-wide grid)
 constexpr int kU2Reach = 5;                          // input column blocks within reach of an output block: cb - 4 .. cb at radius 32 (ray column = BEV column - 32)
 constexpr int kU2CB = kU2XB + kU2Reach - 1;          // input column blocks within reach of a strip
