@@ -33,6 +33,42 @@ namespace rtd {
 constexpr int kFillBatch = 8;   // steps per batch: inputs fetched one batch ahead, one block barrier per batch
 constexpr int kFillSnakeRounds = 12;   // up to this many walks per CU the walks are dealt in rounds of alternating direction (k_fill's block placement)
 
+// LANE PLACEMENT. The ray grid is the bounding rectangle of the spot map plus its margin, so most tiles hold rays that are dead from
+// the start (weight below the cut-off), and a wave does the per-step arithmetic for all its lanes as soon as one of them is alive.
+// The block therefore deals its tile's rays to its lanes by SEGMENTS of kFillSeg consecutive rays of one tile row: the segments with
+// a ray that is alive at the start of the walk first, in row-major order, then the others, in row-major order (a stable partition:
+// neighbouring rows and columns stay together, so a wave's loads and stores stay in few lines). The live rays of a tile fill whole
+// waves, and a wave without a live ray — from the start, or once all its rays have ended — only stores the values of a dead ray.
+// Only which lane walks which ray changes: the per-ray arithmetic is as written, and every output is the same to the bit
+// (RTD_NO_FILL_COMPACT: the identity table, for the tests and the A/B).
+constexpr int kFillSeg = 16;                          // rays per segment (8 or 16; 16 measured faster: with 8 a wave's accesses fall into 32-byte pieces)
+constexpr int kFillSegs = 256 / kFillSeg;             // segments of a tile
+constexpr int kFillSegsPerWave = kWave / kFillSeg, kFillSegsPerRow = kSuperpTileX / kFillSeg;
+static_assert(kFillSeg == 8 || kFillSeg == 16, "a segment is a whole fraction of a tile row and a wave's segments fit 8 bytes");
+
+// Dose walk: a wave's ballot (lane = slot of the placement) as the rectangle of its rays within the tile, from the segments the
+// wave's lanes were dealt (segs: the wave's part of the table in LDS): bytes 0..3 = first column, first row, 31 - last column,
+// 7 - last row (so that the tile's rectangle is the bytewise minimum over its waves); no ray: all ones. Wave-uniform values: scalar
+// work, and the table is read here, not kept in registers (the walk calls this only where its ballot changes).
+__device__ inline unsigned int fillWaveRect(unsigned long long ballot, const unsigned char* segs) {
+    if (!ballot) return 0xffffffffu;
+    unsigned long long waveSegs = 0ull;                   // one byte per segment
+#pragma unroll
+    for (int k = 0; k < kFillSegsPerWave; ++k) waveSegs |= (unsigned long long)segs[k] << (8 * k);
+    waveSegs = (unsigned long long)(unsigned int)__builtin_amdgcn_readfirstlane((int)(waveSegs >> 32)) << 32
+             | (unsigned int)__builtin_amdgcn_readfirstlane((int)waveSegs);
+    unsigned int col = 0u, row = 0u;
+#pragma unroll
+    for (int k = 0; k < kFillSegsPerWave; ++k) {
+        const unsigned int bits = (unsigned int)(ballot >> (k * kFillSeg)) & ((1u << kFillSeg) - 1u);
+        const unsigned int seg = (unsigned int)(waveSegs >> (8 * k)) & 0xffu;
+        col |= bits << ((seg % kFillSegsPerRow) * kFillSeg);
+        row |= (bits ? 1u : 0u) << (seg / kFillSegsPerRow);
+    }
+    return (unsigned int)__builtin_ctz(col) | (unsigned int)__builtin_ctz(row) << 8 | (unsigned int)__builtin_clz(col) << 16
+         | (unsigned int)(__builtin_clz(row) - 24) << 24;
+}
+
 // NUCLEAR_CORR arguments of the fill (kernel_wrapper.cu:190-198). The reference constructs its fill parameters with a nuclear
 // memory step of 0 (:925), so every step of a ray overwrites the same voxel of the nuclear arrays (:367-373) and what remains
 // after a layer's launch is the value of the LAST step, in plane 0. The engine keeps exactly that: one plane per layer, written
@@ -53,13 +89,16 @@ __global__ __launch_bounds__(256) void k_fill(const float* __restrict__ bevDensi
                                                unsigned char* __restrict__ tileRad, LayerPlan* layers, FieldState* st,
                                                LutView lut, FillGeom fg, FieldConst fc, const float* __restrict__ stepTab,
                                                int* __restrict__ active, int nCU, long long* __restrict__ dbg, NucFill nuc,
-                                               unsigned int* __restrict__ sigMin, unsigned int* __restrict__ sigMax, int trackUniform) {
+                                               unsigned int* __restrict__ sigMin, unsigned int* __restrict__ sigMax, int trackUniform,
+                                               int compact) {
     extern __shared__ float sLutF[];                                 // dose walk: the layer's two cumulative-IDD rows
     // diagnostic build only (RTD_FILL_DEBUG): per walk start / end clock, hardware id, item — no output value depends on it
     // sigma walk: [buffer][step][ray] sigmaSq of the rays with a finite 1/sigma (-1: none) — in the same dynamic LDS as the dose walk's
     // LUT rows (a block is one or the other: 16 KB instead of 16 + 8, a seventh block per CU where the walks outnumber the slots)
     float (*sSig)[kFillBatch][256] = reinterpret_cast<float (*)[kFillBatch][256]>(sLutF);
-    __shared__ unsigned long long sDoseMask[2][kFillBatch][4];       // dose walk: [buffer][step][wave] ballot of the rays that carry dose
+    __shared__ unsigned int sDoseRect[2][kFillBatch][4];             // dose walk: [buffer][step][wave] rectangle of the wave's rays that carry dose (fillWaveRect)
+    __shared__ unsigned int sSegLive[4];                             // lane placement: per wave, which of its segments (natural order) hold a live ray
+    __shared__ __attribute__((aligned(8))) unsigned char sSegOf[kFillSegs];   // ... slot -> segment of the tile
     __shared__ int sHist[kMaxSuperpR + 2];
     __shared__ int sClassLo[kMaxSuperpR + 2], sClassHi[kMaxSuperpR + 2];   // sigma walk: first / last step of this walk with a tile of that radius class
     __shared__ int sUni;                                             // sigma walk: every tile of this block so far had ONE sigma^2 over its live rays
@@ -77,7 +116,7 @@ __global__ __launch_bounds__(256) void k_fill(const float* __restrict__ bevDensi
     //  blocks as fit the GPU at once, each taking walk after walk from a ticket counter in descending order of cost — the loop costs
     //  the kernel 23 registers, 5 blocks per CU instead of 7: 0.325 ms against 0.27.)
     const int nTiles = fc.tilesX * fc.tilesY, nB = 2 * nTiles * fc.L;
-    const int tid = threadIdx.y * 32 + threadIdx.x;                  // ray of the tile
+    const int tid = threadIdx.y * 32 + threadIdx.x;                  // lane slot of the block (its ray: LANE PLACEMENT)
     int item = blockIdx.x;
     if (nB <= kFillSnakeRounds * nCU) {
         const int rr = blockIdx.x / nCU, c = blockIdx.x % nCU, nFull = nB / nCU;
@@ -93,25 +132,56 @@ __global__ __launch_bounds__(256) void k_fill(const float* __restrict__ bevDensi
     //  measured 1.2 M against 2.6 M block-cycles per CU)
     const int tileNo = (item % nTiles + (item / nTiles) * 5) % nTiles, tileX = tileNo % fc.tilesX, tileY = tileNo / fc.tilesX;
     const int wave = tid >> 6;
-    const int x = tileX * kSuperpTileX + threadIdx.x;
-    const int y = tileY * kSuperpTileY + threadIdx.y;
     const int W = fc.W, H = fc.H;
     const size_t memStep = (size_t)W * H;
     const size_t layerOff = (size_t)layer * memStep * fc.S;
-    const size_t rayIdx = (size_t)y * W + x;
-    const unsigned int rayOff = (unsigned int)rayIdx;
 
     const LayerPlan lp = layers[layer];
     const unsigned int pFirst = (unsigned int)st->beamFirstInside;
     const unsigned int pAfterLast = st->empty ? pFirst : (unsigned int)lp.afterLast;
 
+    // liveness of a ray at the start of its walk (:236-243): a function of the ray weight and the cut-off steps
+    auto liveAtStart = [&](float weight, int firstOut, unsigned int& last) {
+        last = (unsigned int)(firstOut < (int)pAfterLast ? firstOut : (int)pAfterLast);
+        if (weight < fc.rayWeightCutoff || last < pFirst) { last = 0; return false; }
+        return true;
+    };
+
+    // LANE PLACEMENT: which segments of the tile hold a live ray (every thread looks at the ray of its natural position, one ballot
+    // per wave), then the stable partition as a table slot -> segment. Both roles of a (layer, tile) derive the same table.
+    unsigned int segLive;                                            // (RTD_NO_FILL_COMPACT: all live, the identity table)
+    {
+        const size_t r0 = (size_t)(tileY * kSuperpTileY + threadIdx.y) * W + tileX * kSuperpTileX + threadIdx.x;
+        unsigned int last0;
+        const unsigned long long live0 = __ballot(liveAtStart(rayWeights[(size_t)layer * memStep + r0], firstOutside[r0], last0));
+        unsigned int flags = 0u;
+#pragma unroll
+        for (int k = 0; k < kFillSegsPerWave; ++k) flags |= ((live0 >> (k * kFillSeg)) & ((1ull << kFillSeg) - 1ull) ? 1u : 0u) << k;
+        if ((tid & (kWave - 1)) == 0) sSegLive[wave] = flags;
+        __syncthreads();
+        segLive = sSegLive[0] | sSegLive[1] << kFillSegsPerWave | sSegLive[2] << (2 * kFillSegsPerWave) | sSegLive[3] << (3 * kFillSegsPerWave);
+        if (!compact) segLive = 0xffffffffu >> (32 - kFillSegs);
+    }
+    if (tid < kFillSegs) {
+        const unsigned int below = (1u << tid) - 1u;
+        const int slot = (segLive >> tid & 1u) ? __popc(segLive & below) : __popc(segLive) + __popc(~segLive & below);
+        sSegOf[slot] = (unsigned char)tid;
+    }
+    __syncthreads();
+    const int nat = (int)sSegOf[tid / kFillSeg] * kFillSeg + tid % kFillSeg;   // the natural position of this lane's ray
+    const int x = tileX * kSuperpTileX + (nat & (kSuperpTileX - 1));
+    const int y = tileY * kSuperpTileY + nat / kSuperpTileX;
+    const unsigned int rayOff = (unsigned int)(y * W + x);
+    const size_t rayIdx = rayOff;
+
     // liveness of the ray (:236-243, :308-311): a function of WEPL, the ray weight and the cut-off steps — both roles track it
-    bool beamLive = true;
     const int firstIn = firstInside[rayIdx];
     const int fo = firstOutside[rayIdx];
-    unsigned int afterLast = (unsigned int)(fo < (int)pAfterLast ? fo : (int)pAfterLast);
     const float rayWeight = rayWeights[(size_t)layer * memStep + rayIdx];
-    if (rayWeight < fc.rayWeightCutoff || afterLast < pFirst) { beamLive = false; afterLast = 0; }
+    unsigned int afterLast;
+    bool beamLive = liveAtStart(rayWeight, fo, afterLast);
+    // wave-uniform: a lane of the wave is alive (refreshed after every batch). Once it is false the wave's steps only store.
+    bool waveLive = __ballot(beamLive) != 0ull;
     const float cutDepth = lp.peakDepth * fc.bpDepthCutoff;
     float cumulSpOld = 0.0f;
     const float sqrt2 = 1.41421356f;
@@ -142,10 +212,52 @@ __global__ __launch_bounds__(256) void k_fill(const float* __restrict__ bevDensi
             }
         };
 #pragma unroll
-        for (int j = 0; j < kFillBatch; ++j) fetch1(j, pFirst + j);
+        for (int j = 0; j < kFillBatch; ++j) {
+            if (waveLive) fetch1(j, pFirst + j);
+            else { spB[j] = 0.0f; denB[j] = 0.0f; rrlB[j] = 0.0f; }
+        }
         __syncthreads();
+        // after a batch's barrier — fused tileRadCalc: radius class of every (layer, step, tile) of the batch, 32 lanes per step
+        auto classify = [&](unsigned int step0, int buf) {
+            const int j = tid >> 5, l = tid & 31;                // step of the batch, lane of its 32-lane group
+            // (uniform-sigma detection, while the block has seen nothing else: the smallest sigma^2 of the live rays as well —
+            //  a block of a heterogeneous field drops this after its first batch)
+            const bool uni = sUni != 0;                          // block-uniform (written before the previous batch's barrier)
+            const float inf = __int_as_float(0x7f800000);
+            float m = sSig[buf][j][l];
+            float mn = m >= 0.0f ? m : inf;
+#pragma unroll
+            for (int k = 1; k < 8; ++k) {
+                const float t = sSig[buf][j][l + 32 * k];
+                m = t > m ? t : m;
+                if (uni) { const float tl = t >= 0.0f ? t : inf; mn = tl < mn ? tl : mn; }
+            }
+            m = -halfWaveMin(-m);                                // lanes 31 / 63 hold the maximum of their 32-lane half
+            if (uni) mn = halfWaveMin(mn);
+            if (uni && l == 31 && step0 + j < pAfterLast && m >= 0.0f) {
+                if (mn != m) { sUni = 0; st->nonUniform = 1; }
+                else {
+                    const size_t si = (size_t)layer * fc.S + step0 + j;
+                    atomicMin(&sigMin[si], __float_as_uint(m));  // (sigma^2 >= 0: the bit patterns order like the values)
+                    atomicMax(&sigMax[si], __float_as_uint(m));
+                }
+            }
+            if (l == 31 && step0 + j < pAfterLast) {
+                // tile minimum of 1/sigma (= the reference's minVal, kernel_wrapper.cuh:282-297) from the tile maximum of
+                // sigmaSq with IEEE sqrt and division, then the class exactly as the reference computes it (:300-305)
+                const float minRs = m >= 0.0f ? stepTab[2 * (step0 + j)] / (sqrt2 * (sqrtf(m) + sigmaDeltaV)) : __int_as_float(0x7f800000);
+                int rad = f2iSat(fc.ksSigmaCutoff / (sqrtf(2.0f) * minRs) + 0.5f);
+                rad = rad > kMaxSuperpR + 1 ? kMaxSuperpR + 1 : rad;
+                rad = rad < 0 ? 0 : rad;
+                tileRad[((size_t)layer * fc.S + step0 + j) * nTiles + tileNo] = (unsigned char)rad;
+                atomicAdd(&sHist[rad], 1);
+                atomicMin(&sClassLo[rad], (int)(step0 + j));
+                atomicMax(&sClassHi[rad], (int)(step0 + j));
+            }
+        };
+        unsigned int step0 = pFirst;
         int buf = 0;
-        for (unsigned int step0 = pFirst; step0 < pAfterLast; step0 += kFillBatch, buf ^= 1) {
+        for (; step0 < pAfterLast && waveLive; step0 += kFillBatch, buf ^= 1) {
 #pragma unroll
             for (int j = 0; j < kFillBatch; ++j) {
                 const unsigned int stepNo = step0 + j;
@@ -182,44 +294,24 @@ __global__ __launch_bounds__(256) void k_fill(const float* __restrict__ bevDensi
                 (bevRSigmaEff + layerOff + (size_t)stepNo * memStep)[rayOff] = rSigmaEff;
                 sSig[buf][j][tid] = sig;
             }
+            waveLive = __ballot(beamLive) != 0ull;
             ldsBarrier();                                            // the only barrier of a batch (sSig is double-buffered)
-            {   // fused tileRadCalc: radius class of every (layer, step, tile) of the batch, 32 lanes per step
-                const int j = tid >> 5, l = tid & 31;                // step of the batch, lane of its 32-lane group
-                // (uniform-sigma detection, while the block has seen nothing else: the smallest sigma^2 of the live rays as well —
-                //  a block of a heterogeneous field drops this after its first batch)
-                const bool uni = sUni != 0;                          // block-uniform (written before the previous batch's barrier)
-                const float inf = __int_as_float(0x7f800000);
-                float m = sSig[buf][j][l];
-                float mn = m >= 0.0f ? m : inf;
+            classify(step0, buf);
+        }
+        // The rest of the walk when no ray of the wave is alive (any more): what a dead ray's step leaves — 1/sigma = +inf in memory,
+        // -1 in the block's exchange buffers (those once per buffer) — without inputs and without arithmetic. The barriers and the
+        // wave's share of the classification stay.
+        for (int deadBufs = 0; step0 < pAfterLast; step0 += kFillBatch, buf ^= 1) {
+#pragma nounroll
+            for (int j = 0; j < kFillBatch; ++j)
+                if (step0 + j < pAfterLast) (bevRSigmaEff + layerOff + (size_t)(step0 + j) * memStep)[rayOff] = __int_as_float(0x7f800000);
+            if (deadBufs < 2) {
+                ++deadBufs;
 #pragma unroll
-                for (int k = 1; k < 8; ++k) {
-                    const float t = sSig[buf][j][l + 32 * k];
-                    m = t > m ? t : m;
-                    if (uni) { const float tl = t >= 0.0f ? t : inf; mn = tl < mn ? tl : mn; }
-                }
-                m = -halfWaveMin(-m);                                // lanes 31 / 63 hold the maximum of their 32-lane half
-                if (uni) mn = halfWaveMin(mn);
-                if (uni && l == 31 && step0 + j < pAfterLast && m >= 0.0f) {
-                    if (mn != m) { sUni = 0; st->nonUniform = 1; }
-                    else {
-                        const size_t si = (size_t)layer * fc.S + step0 + j;
-                        atomicMin(&sigMin[si], __float_as_uint(m));  // (sigma^2 >= 0: the bit patterns order like the values)
-                        atomicMax(&sigMax[si], __float_as_uint(m));
-                    }
-                }
-                if (l == 31 && step0 + j < pAfterLast) {
-                    // tile minimum of 1/sigma (= the reference's minVal, kernel_wrapper.cuh:282-297) from the tile maximum of
-                    // sigmaSq with IEEE sqrt and division, then the class exactly as the reference computes it (:300-305)
-                    const float minRs = m >= 0.0f ? stepTab[2 * (step0 + j)] / (sqrt2 * (sqrtf(m) + sigmaDeltaV)) : __int_as_float(0x7f800000);
-                    int rad = f2iSat(fc.ksSigmaCutoff / (sqrtf(2.0f) * minRs) + 0.5f);
-                    rad = rad > kMaxSuperpR + 1 ? kMaxSuperpR + 1 : rad;
-                    rad = rad < 0 ? 0 : rad;
-                    tileRad[((size_t)layer * fc.S + step0 + j) * nTiles + tileNo] = (unsigned char)rad;
-                    atomicAdd(&sHist[rad], 1);
-                    atomicMin(&sClassLo[rad], (int)(step0 + j));
-                    atomicMax(&sClassHi[rad], (int)(step0 + j));
-                }
+                for (int j = 0; j < kFillBatch; ++j) sSig[buf][j][tid] = -1.0f;
             }
+            ldsBarrier();
+            classify(step0, buf);
         }
         firstPassive[(size_t)layer * memStep + rayIdx] = (int)afterLast;
         if (NUC && nucIdx >= 0 && pFirst < pAfterLast) nuc.rs[(size_t)layer * fc.nucW * fc.nucH + nucIdx] = nucRSigmaEff;   // value of the last step (:367-373)
@@ -260,17 +352,44 @@ __global__ __launch_bounds__(256) void k_fill(const float* __restrict__ bevDensi
                 if (!fc.doseToWater) denB[j] = (bevDensity + (size_t)stepNo * memStep)[rayOff];
             }
         };
+        // the last ballot of the rays with dose that the wave turned into a rectangle (wave-uniform)
+        unsigned long long lastBallot = 0ull;
+        unsigned int lastRect = 0xffffffffu;
 #pragma unroll
-        for (int j = 0; j < kFillBatch; ++j) fetch1(j, pFirst + j);
+        for (int j = 0; j < kFillBatch; ++j) {
+            if (waveLive) fetch1(j, pFirst + j);
+            else { spB[j] = 0.0f; denB[j] = 0.0f; }
+        }
         __syncthreads();
+        // after a batch's barrier — rectangle of the tile's rays that carry dose at step j, as minima of (x, y, -x, -y): lanes 0..3 of
+        // the step's group, one component each, from the four waves' rectangles
+        auto rectangle = [&](unsigned int step0, int buf) {
+            const int j = tid >> 5, l = tid & 31;
+            if (l < 4 && step0 + j < pAfterLast) {
+                unsigned int b = 0xffu;
+#pragma unroll
+                for (int w = 0; w < 4; ++w) b = min(b, sDoseRect[buf][j][w] >> (8 * l) & 0xffu);
+                if (b != 0xffu) {
+                    const int x0t = tileX * kSuperpTileX, y0t = tileY * kSuperpTileY;
+                    const int v = l == 0 ? x0t + (int)b : l == 1 ? y0t + (int)b : l == 2 ? -(x0t + 31 - (int)b) : -(y0t + 7 - (int)b);
+                    atomicMin(&active[((size_t)layer * fc.S + step0 + j) * 4 + l], v);
+                    actUni = min(actUni, v);
+                }
+            }
+        };
+        unsigned int step0 = pFirst;
         int buf = 0;
-        for (unsigned int step0 = pFirst; step0 < pAfterLast; step0 += kFillBatch, buf ^= 1) {
-            unsigned long long doseMask[kFillBatch];
+        for (; step0 < pAfterLast && waveLive; step0 += kFillBatch, buf ^= 1) {
+            // lane kFillBatch - 1 - j: the wave's rectangle at step j of the batch (each step shifts the lanes up by one and enters at lane 0)
+            unsigned int rect = 0xffffffffu;
+            auto pushRect = [&](unsigned int r) {
+                rect = (unsigned int)__builtin_amdgcn_update_dpp(0, (int)rect, 0x111, 0xF, 0xF, true);   // row_shr:1
+                rect = (tid & (kWave - 1)) == 0 ? r : rect;
+            };
 #pragma unroll
             for (int j = 0; j < kFillBatch; ++j) {
                 const unsigned int stepNo = step0 + j;
-                doseMask[j] = 0ull;
-                if (stepNo >= pAfterLast) continue;                  // block-uniform
+                if (stepNo >= pAfterLast) { pushRect(0xffffffffu); continue; }   // block-uniform
                 const float cumulSp = spB[j], density = denB[j];
                 fetch1(j, stepNo + kFillBatch);
                 if (beamLive) {
@@ -303,33 +422,28 @@ __global__ __launch_bounds__(256) void k_fill(const float* __restrict__ bevDensi
                 }
                 if (!beamLive || (int)stepNo < (firstIn - 1)) { res = 0.0f; nucRes = 0.0f; }
                 (bevIdd + layerOff + (size_t)stepNo * memStep)[rayOff] = res;
-                doseMask[j] = __ballot(res > 0.0f);
+                // where in the tile the rays with dose are: decoded only when the ballot changes — where rays enter and where they end
+                const unsigned long long ballot = __ballot(res > 0.0f);
+                if (ballot != lastBallot) { lastBallot = ballot; lastRect = fillWaveRect(ballot, sSegOf + wave * kFillSegsPerWave); }
+                pushRect(lastRect);
             }
-            if ((tid & (kWave - 1)) == 0) {
-#pragma unroll
-                for (int j = 0; j < kFillBatch; ++j) sDoseMask[buf][j][wave] = doseMask[j];
+            if ((tid & (kWave - 1)) < kFillBatch) sDoseRect[buf][kFillBatch - 1 - (tid & (kWave - 1))][wave] = rect;
+            waveLive = __ballot(beamLive) != 0ull;
+            ldsBarrier();                                            // the only barrier of a batch (sDoseRect is double-buffered)
+            rectangle(step0, buf);
+        }
+        // The rest of the walk when no ray of the wave is alive (any more): dose 0 in memory, no ray with dose in the block's exchange
+        // buffers (those once per buffer) — without inputs and without arithmetic. The barriers and the wave's share of the rectangles stay.
+        for (int deadBufs = 0; step0 < pAfterLast; step0 += kFillBatch, buf ^= 1) {
+#pragma nounroll
+            for (int j = 0; j < kFillBatch; ++j)
+                if (step0 + j < pAfterLast) (bevIdd + layerOff + (size_t)(step0 + j) * memStep)[rayOff] = 0.0f;
+            if (deadBufs < 2) {
+                ++deadBufs;
+                if ((tid & (kWave - 1)) < kFillBatch) sDoseRect[buf][tid & (kWave - 1)][wave] = 0xffffffffu;
             }
-            ldsBarrier();                                            // the only barrier of a batch (sDoseMask is double-buffered)
-            // rectangle of the tile's rays that carry dose at step j, as minima of (x, y, -x, -y): lanes 0..3 of the step's group,
-            // one component each, from the four waves' ballots (wave w holds rows 2w, 2w+1 of the tile: low / high 32 bits)
-            const int j = tid >> 5, l = tid & 31;
-            if (l < 4 && step0 + j < pAfterLast) {
-                unsigned int colMask = 0u, rowMask = 0u;             // columns / rows of the tile with dose
-#pragma unroll
-                for (int w = 0; w < 4; ++w) {
-                    const unsigned long long dm = sDoseMask[buf][j][w];
-                    const unsigned int lo = (unsigned int)dm, hi = (unsigned int)(dm >> 32);
-                    colMask |= lo | hi;
-                    rowMask |= (lo ? 1u : 0u) << (2 * w) | (hi ? 1u : 0u) << (2 * w + 1);
-                }
-                if (colMask) {
-                    const int x0t = tileX * kSuperpTileX, y0t = tileY * kSuperpTileY;
-                    const int v = l == 0 ? x0t + __builtin_ctz(colMask) : l == 1 ? y0t + __builtin_ctz(rowMask)
-                                : l == 2 ? -(x0t + 31 - __builtin_clz(colMask)) : -(y0t + 31 - __builtin_clz(rowMask));
-                    atomicMin(&active[((size_t)layer * fc.S + step0 + j) * 4 + l], v);
-                    actUni = min(actUni, v);
-                }
-            }
+            ldsBarrier();
+            rectangle(step0, buf);
         }
         if ((tid & 31) < 4 && actUni != 0x7fffffff) atomicMin(&st->actUnion[tid & 3], actUni);
         if (NUC && nucIdx >= 0 && pFirst < pAfterLast) nuc.idd[(size_t)layer * fc.nucW * fc.nucH + nucIdx] = nucRes;   // value of the last step (:367-373)
