@@ -80,26 +80,30 @@ class OracleField:
         self.close()
 
 
-def run_field(scn, beam, dose, options=None, keep_layers=True):
-    """orc_field_run: one field of scenario scn accumulated into dose ([Z][Y][X] float32, modified in place)."""
+def run_field(scn, beam, dose, options=None, keep_layers=True, dose_dims=None):
+    """orc_field_run: one field of scenario scn accumulated into dose ([Z][Y][X] float32, modified in place). dose_dims (x, y, z):
+    the dose grid that beam.gantryToDoseIdx indexes, when it is not the CT grid (default: scn.dims)."""
     opt = options or abi.default_options()
     la = scn.luts.as_abi()
     ba = beam.as_abi()
     h = C.c_void_p()
     st = lib().orc_field_run(C.byref(la), abi.fptr(scn.ct), abi.uint3(scn.dims), C.byref(ba), abi.fptr(dose),
-                             abi.uint3(scn.dims), C.byref(opt), 1 if keep_layers else 0, C.byref(h))
+                             abi.uint3(scn.dims if dose_dims is None else dose_dims), C.byref(opt), 1 if keep_layers else 0, C.byref(h))
     return OracleField(h, st)
 
 
-def compute(scn, dose=None, options=None):
-    """orc_compute: all beams, reference-shaped (accumulates into dose)."""
+def compute(scn, dose=None, options=None, dose_dims=None):
+    """orc_compute: all beams, reference-shaped (accumulates into dose). dose_dims (x, y, z): the dose grid of the beams'
+    gantryToDoseIdx when it is not the CT grid (default: scn.dims)."""
     opt = options or abi.default_options()
+    dd = tuple(scn.dims if dose_dims is None else dose_dims)
     if dose is None:
-        dose = np.zeros_like(scn.ct)
+        dose = np.zeros((dd[2], dd[1], dd[0]), dtype=np.float32)
+    assert dose.shape == (dd[2], dd[1], dd[0])
     la = scn.luts.as_abi()
     ba = __import__("raytracedicom_amd.scenarios", fromlist=["beams_abi"]).beams_abi(scn.beams)
     st = lib().orc_compute(C.byref(la), abi.fptr(scn.ct), abi.uint3(scn.dims), ba, len(scn.beams), abi.fptr(dose),
-                           abi.uint3(scn.dims), C.byref(opt))
+                           abi.uint3(dd), C.byref(opt))
     if st != 0:
         raise RuntimeError("oracle status %d" % st)
     return dose

@@ -43,15 +43,16 @@ def _with_weights(b, w):
 
 
 class Rig:
-    """One engine with the scenario's CT and LUTs, a device dose volume and a device voxel-weight volume."""
+    """One engine with the scenario's CT and LUTs, a device dose volume and a device voxel-weight volume. dose_shape ([Z][Y][X]):
+    the dose grid of the beams' gantryToDoseIdx when it is not the CT's."""
 
-    def __init__(self, engine, scn, opt):
+    def __init__(self, engine, scn, opt, dose_shape=None):
         self.engine = engine
         self.eng = engine.Engine(0)
         self.eng.set_options(opt)
         self.eng.set_luts(scn.luts)
         self.eng.set_ct(scn.ct)
-        self.shape = scn.ct.shape
+        self.shape = scn.ct.shape if dose_shape is None else tuple(dose_shape)
         self.dims = (self.shape[2], self.shape[1], self.shape[0])
         self.nb = int(np.prod(self.shape)) * 4
         self.dDose = self.eng.device_alloc(self.nb)
@@ -101,8 +102,8 @@ class Rig:
 def rig_of(engine):
     rigs = []
 
-    def make(scn, opt):
-        r = Rig(engine, scn, opt)
+    def make(scn, opt, dose_shape=None):
+        r = Rig(engine, scn, opt, dose_shape)
         rigs.append(r)
         return r
     yield make

@@ -14,19 +14,22 @@ def nuc_luts():
     return luts.synth_luts(nuclear=True)
 
 
-def _run(orc, engine, scn, opt):
-    ref = np.zeros_like(scn.ct)
-    of = orc.run_field(scn, scn.beams[0], ref, options=opt, keep_layers=True)
+def _run(orc, engine, scn, opt, dose_dims=None, dose_spacing=None):
+    """dose_dims, dose_spacing: the dose grid of the beam's gantryToDoseIdx when it is not the CT's (default)."""
+    dose_dims = tuple(scn.dims if dose_dims is None else dose_dims)
+    dose_spacing = scn.spacing if dose_spacing is None else dose_spacing
+    ref = np.zeros((dose_dims[2], dose_dims[1], dose_dims[0]), dtype=np.float32)
+    of = orc.run_field(scn, scn.beams[0], ref, options=opt, keep_layers=True, dose_dims=dose_dims)
     assert of.status == 0, of.error
-    dose = np.zeros_like(scn.ct)
+    dose = np.zeros_like(ref)
     with engine.Engine(0) as eng:
         eng.set_options(opt)
         eng.set_luts(scn.luts)
         eng.set_ct(scn.ct)
-        n = scn.n_voxels
+        n = int(dose.size)
         d = eng.device_alloc(4 * n)
         eng.device_zero(d, 4 * n)
-        f = eng.create_field(scn.beams[0], scn.dims)
+        f = eng.create_field(scn.beams[0], dose_dims)
         f.compute(d)
         _, info = f.finish()
         eng.to_host(dose, d)
@@ -51,7 +54,7 @@ def _run(orc, engine, scn, opt):
     thr = ref > 1e-3 * mx
     assert (np.abs(dose - ref)[thr] <= 1e-4 * ref[thr] + 1e-6 * mx).all(), float((np.abs(dose - ref)[thr] / ref[thr]).max())
     assert np.abs(dose - ref).max() <= 2e-5 * mx
-    rate, n_eval, _ = orc.gamma_pass_rate(ref, dose, scn.spacing)
+    rate, n_eval, _ = orc.gamma_pass_rate(ref, dose, dose_spacing)
     assert rate == 1.0 and n_eval > 0
     return dose, ref, of.info
 

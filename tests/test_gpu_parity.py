@@ -11,6 +11,9 @@ Tolerances (stated per stage):
   * BEV dose, final dose: rtol 1e-4 on voxels above 1e-3 of the maximum (+ atol 1e-6*max) — the superposition sums the
     same terms in a different (fixed) order than the oracle and uses a Gaussian series for its weight tables;
     gamma(1 %/1 mm) >= 99 % is the north-star bar and is asserted at 100 %.
+
+_run_engine and _compare_field take an optional dose grid (dose_dims, dose_spacing) for beams whose gantryToDoseIdx is not their
+gantryToImIdx (tests/test_gpu_asym_grids.py); the default is the CT's grid, as every test of this file uses it.
 """
 import math
 
@@ -22,19 +25,20 @@ from raytracedicom_amd import abi, scenarios
 pytestmark = pytest.mark.gpu
 
 
-def _run_engine(engine, scn, beam, options=None):
+def _run_engine(engine, scn, beam, options=None, dose_dims=None):
+    dose_dims = tuple(scn.dims if dose_dims is None else dose_dims)
     eng = engine.Engine(0)
     if options is not None:
         eng.set_options(options)
     eng.set_luts(scn.luts)
     eng.set_ct(scn.ct)
-    n = scn.n_voxels
+    n = dose_dims[0] * dose_dims[1] * dose_dims[2]
     d_dose = eng.device_alloc(4 * n)
     eng.device_zero(d_dose, 4 * n)
-    fld = eng.create_field(beam, scn.dims)
+    fld = eng.create_field(beam, dose_dims)
     fld.compute(d_dose)
     timing, info = fld.finish()
-    dose = np.empty_like(scn.ct)
+    dose = np.empty((dose_dims[2], dose_dims[1], dose_dims[0]), dtype=np.float32)
     eng.to_host(dose, d_dose)
     return eng, fld, dose, timing, info, d_dose
 
@@ -49,11 +53,13 @@ def _rel_close(a, b, rtol, floor_frac=1e-3, atol_frac=1e-6):
     assert (err[~mask] <= 2 * rtol * floor_frac * mx + atol_frac * mx).all()
 
 
-def _compare_field(orc, engine, scn, beam, options=None):
-    dose_ref = np.zeros_like(scn.ct)
-    of = orc.run_field(scn, beam, dose_ref, options=options, keep_layers=True)
+def _compare_field(orc, engine, scn, beam, options=None, dose_dims=None, dose_spacing=None):
+    dose_dims = tuple(scn.dims if dose_dims is None else dose_dims)
+    dose_spacing = scn.spacing if dose_spacing is None else dose_spacing
+    dose_ref = np.zeros((dose_dims[2], dose_dims[1], dose_dims[0]), dtype=np.float32)
+    of = orc.run_field(scn, beam, dose_ref, options=options, keep_layers=True, dose_dims=dose_dims)
     assert of.status == 0
-    eng, fld, dose, timing, info, d_dose = _run_engine(engine, scn, beam, options)
+    eng, fld, dose, timing, info, d_dose = _run_engine(engine, scn, beam, options, dose_dims)
     try:
         oi = of.info
         for k in ("ray_dims", "beam_first_inside", "beam_first_outside", "beam_first_guaranteed_passive",
@@ -99,7 +105,7 @@ def _compare_field(orc, engine, scn, beam, options=None):
         bev_g, bev_o = fld.fetch("bev"), of.get("bev")
         _rel_close(bev_g, bev_o, rtol=1e-4)
         _rel_close(dose, dose_ref, rtol=1e-4)
-        rate, n_eval, gmax = orc.gamma_pass_rate(dose_ref, dose, scn.spacing)
+        rate, n_eval, gmax = orc.gamma_pass_rate(dose_ref, dose, dose_spacing)
         assert n_eval > 0 and rate == 1.0, (rate, n_eval, gmax)
         return dose, dose_ref, timing, info
     finally:
