@@ -305,6 +305,7 @@ int rtd_set_stream(rtd_handle h, void* hip_stream);
  * "eff_radius" [L][34] int32 (batch radius per tile radius); "bev" [S][H+64][W+64] float;
  * "layer_plan" [L][8] float (energyIdx, scaleFact, peakDepth, entrySigmaX, entrySigmaY, afterLast, 0, 0);
  * "trace_reused" int32[1]: 1 if the last launched compute reused the field's trace and plan (see rtd_field_compute).
+ * "target_bev" and "target_hit": see rtd_field_project_target below.
  * Returns the number of bytes the buffer holds via *bytes_needed when host_out is NULL.
  */
 int rtd_field_fetch(rtd_handle h, rtd_field f, const char* name, void* host_out, size_t bytes,
@@ -827,6 +828,79 @@ int rtd_roi_device(rtd_handle h, rtd_roi roi, const int32_t** dev_voxels, size_t
 int rtd_roi_fill_mask(rtd_handle h, rtd_roi roi, uint8_t* dev_mask);
 int rtd_roi_kernel_ms(rtd_handle h, rtd_roi roi, float* ms);
 int rtd_roi_destroy(rtd_handle h, rtd_roi roi);
+
+/*
+ * ---- Spots from a target: the target in beam's-eye view ----
+ *
+ * Additive to the blocks above (RTD_ABI_VERSION stays 3). A target on the dose grid (a byte mask, as rtd_roi_fill_mask writes it) is
+ * projected into the (ray, step) grid of a computed field, and the spots whose Bragg peak lands in it are marked: the way from a
+ * structure to the spot map of a field. Every decision below is a comparison of float32 values computed in the stated order, each
+ * product, quotient, sum and difference rounded, nothing contracted; all counting is integer. The same inputs give the same bits across
+ * calls, handles and processes, and the rule can be restated in a few lines (tests/target_reference.py does).
+ *
+ * Notation: W, H, L = rtd_field_info.ray_dims, S = tracer_steps, wepl[k][j][i] the field's cumulative water-equivalent depth
+ * (rtd_field_fetch "wepl": a sum of non-negative terms, so it does not decrease along a ray), (nx, ny, nz) = dose_dims.
+ *
+ * (a) Projection. For ray (i, j), 0 <= i < W, 0 <= j < H, and step 0 <= k < S, with f = (float(i), float(j), float(k)):
+ *         g = f * ray_res + ray_offset                                  (component-wise)
+ *         g.x = g.x * (1.0f - g.z / source_dist[0])     g.y = g.y * (1.0f - g.z / source_dist[1])      (g.z / inf = 0)
+ *         p.c = ((m[3c] * g.x + m[3c + 1] * g.y) + m[3c + 2] * g.z) + v[c]        with (m, v) = gantry_to_dose_idx, c = 0, 1, 2
+ *     (Float3FromFanTransform::transformPoint, float3_from_fan_transform.cu:37-42, with the ray grid as the fan index). Nearest voxel:
+ *     q.c = floorf(p.c + 0.5f). The sample is inside iff 0.0f <= q.x < float(nx), 0.0f <= q.y < float(ny), 0.0f <= q.z < float(nz)
+ *     (compared as floats before any conversion; a NaN is outside) and the mask byte at ((int q.z * ny) + int q.y) * nx + int q.x is
+ *     non-zero. Stored packed, uint32 [ceil(S / 32)][H][W]: bit k & 31 of word [k >> 5][j][i]; the bits of steps >= S are 0.
+ * (b) Summary over all inside samples: their number; the smallest and the largest wepl[k][j][i] (0, 0 when there is none); the
+ *     inclusive box of the rays (i, j) and the inclusive range of the steps k that have one (all 0 when there is none).
+ * (c) Layer hit, per layer l and ray (i, j). R = the layer's peak depth (rtd_field_fetch "layer_plan", column 2),
+ *     lo = R - distal_margin_mm, hi = R + proximal_margin_mm. kLo = the number of steps k with wepl[k][j][i] < lo,
+ *     kHi = min(the number of steps k with wepl[k][j][i] < hi, S - 1). No hit when kLo == S (the ray never reaches that depth); otherwise
+ *     a hit iff a bit of (a) is set for some step of [kLo, kHi] (lo <= hi, so the range is not empty). With both margins 0 that is the one
+ *     step at which the cumulative depth first reaches the peak depth. The test is on samples, not on a proximal / distal interval: a
+ *     hollow or two-part target is handled. So a layer is also taken when its peak lies up to distal_margin_mm beyond a target sample of
+ *     the ray, or up to proximal_margin_mm in front of one (give or take the step in which the depth is reached).
+ * (d) Spot (sx, sy) has the ray coordinates of the spot -> ray convolution:
+ *         cx = (spot_offset[0] - ray_offset[0]) / ray_res[0] + float(sx) * (spot_delta[0] / ray_res[0])        cy likewise with [1], sy
+ *     (spot_* = spot_idx_to_gantry; the product is rounded, then added). Its rays are the nearest ray (floorf(cx + 0.5f),
+ *     floorf(cy + 0.5f)) and, when lateral_margin_mm = m > 0, every ray (i, j) with dx * dx + dy * dy <= m * m, where
+ *     dx = (float(i) - cx) * ray_res[0], dy = (float(j) - cy) * ray_res[1] (the sum of the two rounded squares), both clipped to the
+ *     ray grid (the nearest ray compared as floats, like (a)). Spot (l, sy, sx) is selected iff some ray of its set has a hit for l.
+ *     The lateral margin is a distance in the isocentre plane, the plane of the ray grid: it ignores the divergence of the beam.
+ *
+ * rtd_field_project_target  dev_mask: nx ny nz bytes on this handle's device, x fastest, non-zero = inside. Stores (a) with the field,
+ *                           fills info with (b); synchronous (it returns a record). The field owns the projection: a later call
+ *                           replaces it, rtd_field_release and rtd_field_destroy free it. The buffers (4 bytes per ray and 32 steps,
+ *                           1 byte per ray and layer) are allocated by the first call.
+ * rtd_field_select_spots    (c) and (d) from the stored projection: WRITES every byte of dev_spot_mask ([L][ny][nx] as spot_weights,
+ *                           device memory), 1 selected, 0 not. opt == NULL: all margins 0. Two launches on the handle's stream: no
+ *                           allocation, no copy, no host synchronisation when n_selected is NULL (it can be captured into a graph);
+ *                           with n_selected a third launch counts, and the call waits and returns the number of selected spots. One
+ *                           projection serves any number of selections.
+ * Both read the trace (wepl) and the layer records the field holds when they run — those of its last compute — and write nothing that a
+ * later transfer, gradient or rtd_field_dose_influence reads. wepl_min / wepl_max bracket the peak depths worth offering to the field.
+ * rtd_field_fetch names: "target_bev" uint32 [ceil(S / 32)][H][W] after a projection, "target_hit" uint8 [L][H][W], the hits (c) of
+ * the last selection.
+ *
+ * RTD_ERR_NOT_READY: before any compute of the field; rtd_field_select_spots also before any projection. RTD_ERR_INVALID_ARG: a null
+ * pointer other than opt and n_selected, a remote field, nuclear_corr, a margin that is negative or not finite. After a refusal
+ * every object stays usable. Not on the rtd_plan_* path.
+ */
+typedef struct rtd_target_info {
+    uint64_t n_samples;            /* (ray, step) samples inside the target */
+    float wepl_min, wepl_max;      /* min / max of wepl over those samples (0, 0 when none) */
+    int32_t ray_lo[2], ray_hi[2];  /* inclusive box of rays (i, j) with at least one sample (all 0 when none) */
+    int32_t step_lo, step_hi;      /* inclusive range of steps with at least one sample */
+    int32_t reserved[4];
+} rtd_target_info;
+
+typedef struct rtd_target_options {
+    float lateral_margin_mm;       /* >= 0, in the isocentre plane (the ray grid's plane) */
+    float proximal_margin_mm;      /* >= 0, water-equivalent mm */
+    float distal_margin_mm;        /* >= 0, water-equivalent mm */
+    int32_t reserved[5];
+} rtd_target_options;
+
+int rtd_field_project_target(rtd_handle h, rtd_field f, const uint8_t* dev_mask, rtd_target_info* info);
+int rtd_field_select_spots(rtd_handle h, rtd_field f, const rtd_target_options* opt, uint8_t* dev_spot_mask, uint32_t* n_selected);
 
 /*
  * ---- Multi-GPU plans behind the boundary (SURVEY.md 8(b) "Threading": one handle and one host thread per device) ----

@@ -161,6 +161,20 @@ class RtdRoiInfo(C.Structure):
                 "n_slices_covered": int(self.n_slices_covered)}
 
 
+class RtdTargetInfo(C.Structure):
+    _fields_ = [("n_samples", C.c_uint64), ("wepl_min", C.c_float), ("wepl_max", C.c_float), ("ray_lo", C.c_int32 * 2),
+                ("ray_hi", C.c_int32 * 2), ("step_lo", C.c_int32), ("step_hi", C.c_int32), ("reserved", C.c_int32 * 4)]
+
+    def as_dict(self):
+        return {"n_samples": int(self.n_samples), "wepl_min": float(self.wepl_min), "wepl_max": float(self.wepl_max),
+                "ray_lo": list(self.ray_lo), "ray_hi": list(self.ray_hi), "step_lo": int(self.step_lo), "step_hi": int(self.step_hi)}
+
+
+class RtdTargetOptions(C.Structure):
+    _fields_ = [("lateral_margin_mm", C.c_float), ("proximal_margin_mm", C.c_float), ("distal_margin_mm", C.c_float),
+                ("reserved", C.c_int32 * 5)]
+
+
 def default_optimizer_options():
     """rtd_default_optimizer_options: the step bounds only keep the Barzilai-Borwein step finite."""
     o = RtdOptimizerOptions()

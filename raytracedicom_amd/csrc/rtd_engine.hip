@@ -44,6 +44,7 @@
 #include "rtd_robust.hpp"
 #include "rtd_voxelwise.hpp"
 #include "rtd_roi.hpp"
+#include "rtd_target.hpp"
 #include "rtd_engine_impl.hpp"
 
 namespace {
@@ -410,8 +411,8 @@ int rtd_field_release(rtd_handle hh, rtd_field ff) {
     (void)hipStreamSynchronize(h->stream);      // its kernels have drained: the next owner uploads with plain copies
     f->computed = false; f->transferred = false;
     f->traceLaunched = false; f->traceUsable = false;   // (the next owner of the workspace is a new field object anyway: nothing carries over)
-    freeBuffers(f, kGradient | kDiag | kDij | kDijOut);   // (not part of the shape's workspace)
-    f->gradDone = false;
+    freeBuffers(f, kGradient | kDiag | kDij | kDijOut | kTarget);   // (not part of the shape's workspace)
+    f->gradDone = false; f->targetProjected = false; f->targetSelected = false;
     f->dijDone = false; f->dijPrepared = false; f->dijCap = 0; f->dijNnz = 0; f->dijBatchOf.clear();
     f->released = shapeCounts(f);
     h->fieldCache.push_back(f);
@@ -1246,9 +1247,10 @@ int rtd_field_fetch(rtd_handle hh, rtd_field ff, const char* name, void* host_ou
     std::string nm(name);
     std::vector<char> staging;
     RTD_HIP(h, hipStreamSynchronize(h->stream));
-    bool found = false;   // (grad_* only after a gradient, *_debug only when allocated)
+    bool found = false;   // (grad_* only after a gradient, target_* only after a projection / selection, *_debug only when allocated)
     f->forEachBuffer([&](auto*& p, size_t count, BufClass c, bool, const char* fetchName) {
-        if (found || !fetchName || nm != fetchName || (c == kGradient && !f->gradDone) || (c == kDiag && !p)) return;
+        if (found || !fetchName || nm != fetchName || (c == kGradient && !f->gradDone) || (c == kDiag && !p) ||
+            (c == kTarget && !(nm == "target_bev" ? f->targetProjected : f->targetSelected))) return;
         found = true; src = p; n = count * sizeof *p;
     });
     if (found) {
@@ -1345,3 +1347,4 @@ int rtd_compute(rtd_handle hh, const rtd_beam* beams, int n_beams, float* dose_i
 #include "rtd_objective_host.hpp"
 #include "rtd_optimizer_host.hpp"
 #include "rtd_roi_host.hpp"
+#include "rtd_target_host.hpp"

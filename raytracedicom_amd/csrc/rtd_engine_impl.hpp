@@ -60,8 +60,9 @@ Switches readSwitches() {
 // Classes of a field's device buffers: the workspace that a field of the same shape takes over (rtd_field_release), the NUCLEAR_CORR
 // halo, the spot-weight gradient's (allocated by its first call), the RTD_*_DEBUG clock stamps, the dose-influence matrix's workspace
 // and its result (rtd_field_dose_influence: allocated by its first call, the result replaced by every call; the result's class also
-// holds what rtd_field_dose_influence_prepare builds from it, so that the two are freed together).
-enum BufClass : unsigned { kShape = 1, kNuclear = 2, kGradient = 4, kDiag = 8, kDij = 16, kDijOut = 32, kAllBufs = 63 };
+// holds what rtd_field_dose_influence_prepare builds from it, so that the two are freed together), the target in beam's-eye view
+// (rtd_field_project_target: allocated by its first call).
+enum BufClass : unsigned { kShape = 1, kNuclear = 2, kGradient = 4, kDiag = 8, kDij = 16, kDijOut = 32, kTarget = 64, kAllBufs = 127 };
 
 struct rtd_field_impl {
     Switches sw;
@@ -155,6 +156,12 @@ struct rtd_field_impl {
     int dijOwnBox[6] = {0, 0, 0, -1, -1, -1};   // the field's dose box (min, max) when the matrix was computed
     DijBox dijBox{};               // ... united with the bounding box of the matrix's rows: the voxels that have a row
     size_t dijRowsN = 0, dijChunks = 0;
+    // the target in beam's-eye view (rtd_field_project_target / rtd_field_select_spots, rtd_target.hpp): allocated by the first projection
+    unsigned int* dTargetBev = nullptr;      // [ceil(S / 32)][H][W] bit k & 31 of word k >> 5: sample (ray, step k) lies in the target
+    unsigned char* dTargetHit = nullptr;     // [L][H][W] the layer hits of the last selection
+    TargetSummary* dTargetSum = nullptr; unsigned int* dTargetCount = nullptr;
+    bool targetProjected = false;  // dTargetBev holds a projection
+    bool targetSelected = false;   // ... and dTargetHit the hits of a selection made from it
     std::vector<size_t> released; // released: the element counts of its shape buffers (a new field takes it over if its own are the same)
 
     bool uniform4() const { return fc.W <= 16 * (kU2XB - 4) && fc.W % 4 == 0 && !sw.uniformV2; }   // k_superpose_uniform4, else _uniform2
@@ -209,6 +216,8 @@ struct rtd_field_impl {
         visit(dDijCVals, ap * std::max<size_t>(dijNnz, 1), kDijOut, false, nullptr); visit(dDijChunkFirst, ap * (nSpot + 1), kDijOut, false, nullptr);
         visit(dDijChunkCol, ap * std::max<size_t>(dijChunks, 1), kDijOut, false, nullptr);
         visit(dDijPartial, ap * std::max<size_t>(dijChunks, 1), kDijOut, false, nullptr);
+        visit(dTargetBev, ((S + 31) / 32) * R, kTarget, false, "target_bev"); visit(dTargetHit, L * R, kTarget, false, "target_hit");
+        visit(dTargetSum, (size_t)1, kTarget, false, nullptr); visit(dTargetCount, (size_t)1, kTarget, false, nullptr);
         visit(dScanDbg, sw.scanDebug ? 8 * (R / 64) : 0, kDiag, true, "scan_debug");
         visit(dFillDbg, sw.fillDebug ? 4 * 2 * tiles * L : 0, kDiag, false, "fill_debug");
         visit(dUniDbg, sw.uniformDebug && uniformEligible && uniform4() ? 16 * S * nPartsU4 : 0, kDiag, true, "uniform_debug");

@@ -21,7 +21,7 @@ _LIB = None
 
 _FETCH_DTYPES = {"first_inside": np.int32, "first_outside": np.int32, "first_passive": np.int32,
                  "eff_radius": np.int32, "tile_radius": np.uint8, "fill_debug": np.int64, "sweep_debug": np.int64, "uniform_debug": np.int64, "sweep_big_debug": np.int64, "scan_debug": np.int64,
-                 "dij_batch": np.int32, "trace_reused": np.int32, "active": np.int32}
+                 "dij_batch": np.int32, "trace_reused": np.int32, "active": np.int32, "target_bev": np.uint32, "target_hit": np.uint8}
 
 
 class RtdError(RuntimeError):
@@ -116,6 +116,8 @@ def lib():
         L.rtd_roi_fill_mask.argtypes = [vp, vp, vp]
         L.rtd_roi_kernel_ms.argtypes = [vp, vp, C.POINTER(C.c_float)]
         L.rtd_roi_destroy.argtypes = [vp, vp]
+        L.rtd_field_project_target.argtypes = [vp, vp, vp, C.POINTER(abi.RtdTargetInfo)]
+        L.rtd_field_select_spots.argtypes = [vp, vp, C.POINTER(abi.RtdTargetOptions), vp, C.POINTER(C.c_uint32)]
         L.rtd_host_register.argtypes = [vp, C.c_size_t]
         L.rtd_host_unregister.argtypes = [vp]
         L.rtd_plan_create.argtypes = [C.POINTER(C.c_int), C.c_int, vpp]
@@ -296,6 +298,52 @@ class Field:
     def set_spot_weights(self, dev_spot_weights):
         """rtd_field_set_spot_weights: new [L][ny][nx] float32 weights from device memory (stream-ordered)."""
         self.eng._check(lib().rtd_field_set_spot_weights(self.eng._h, self._h, C.c_void_p(int(dev_spot_weights))))
+
+    def project_target(self, mask_or_roi):
+        """rtd_field_project_target: the target in the field's beam's-eye view, kept with the field for select_spots(); returns the
+        summary as a dict (n_samples, wepl_min, wepl_max, ray_lo, ray_hi, step_lo, step_hi). mask_or_roi: a device pointer (int) of a
+        uint8 mask on the dose grid (x fastest, non-zero = inside), a numpy [Z][Y][X] uint8 or bool array (uploaded), or a Roi (its
+        fill_mask). Needs a compute of the field; synchronous."""
+        n = self._dims[0] * self._dims[1] * self._dims[2]
+        own = None
+        if isinstance(mask_or_roi, Roi):
+            if tuple(mask_or_roi.dims) != self._dims:
+                raise ValueError("the ROI's grid %r is not the field's dose grid %r" % (mask_or_roi.dims, self._dims))
+            own = self.eng.device_alloc(n)
+            mask_or_roi.fill_mask(own)
+        elif isinstance(mask_or_roi, np.ndarray):
+            a = np.ascontiguousarray(mask_or_roi != 0, dtype=np.uint8)
+            if a.size != n:
+                raise ValueError("the mask has %d voxels, the dose grid %d" % (a.size, n))
+            own = self.eng.device_alloc(n)
+            self.eng.to_device(own, a)
+        info = abi.RtdTargetInfo()
+        try:
+            ptr = own if own is not None else (int(mask_or_roi) if mask_or_roi else None)
+            self.eng._check(lib().rtd_field_project_target(self.eng._h, self._h, C.c_void_p(ptr) if ptr else None, C.byref(info)))
+        finally:
+            if own is not None:
+                self.eng.device_free(own)      # (the call has waited for its kernel)
+        return info.as_dict()
+
+    def select_spots(self, lateral=0.0, proximal=0.0, distal=0.0, dev_out=None):
+        """rtd_field_select_spots: the [L][ny][nx] uint8 mask (1 = selected) of the spots whose layer's Bragg peak, widened by the
+        water-equivalent margins proximal / distal (mm), lands on the projected target on a ray within lateral (mm, isocentre plane)
+        of the spot. Without dev_out the mask is returned as a numpy array; with dev_out (device pointer, L * ny * nx bytes) it is
+        written there, launches only, and None is returned."""
+        o = abi.RtdTargetOptions()
+        o.lateral_margin_mm, o.proximal_margin_mm, o.distal_margin_mm = float(lateral), float(proximal), float(distal)
+        if dev_out is not None:
+            self.eng._check(lib().rtd_field_select_spots(self.eng._h, self._h, C.byref(o), C.c_void_p(int(dev_out)), None))
+            return None
+        out = np.empty(np.asarray(self._beam.spotWeights).shape, dtype=np.uint8)
+        d = self.eng.device_alloc(max(out.nbytes, 1))
+        try:
+            self.eng._check(lib().rtd_field_select_spots(self.eng._h, self._h, C.byref(o), C.c_void_p(d), None))
+            self.eng.to_host(out, d)
+        finally:
+            self.eng.device_free(d)
+        return out
 
     def clear_dose(self, dev_dose):
         """Zero the voxels of dev_dose that the last compute() of this field could have changed; asynchronous."""
