@@ -21,9 +21,7 @@ def _two_mm(b, n):
     r = (256.0 / n) / 2.0
     t = b.gantryToDoseIdx
     g = scenarios.Float3AffineTransform(r * t.m, r * t.v + 0.5 * (r - 1.0))
-    nb = scenarios.BeamSettings(b.spotWeights, b.beamEnergies, b.spotSigmas, b.raySpacing, b.tracerSteps, b.sourceDist,
-                                b.spotIdxToGantry, b.gantryToImIdx, g)
-    return nb, (128, 128, 128)
+    return b.replace(gantryToDoseIdx=g), (128, 128, 128)
 
 
 def run(name, scn, beam, dims, steps, hip):

@@ -62,6 +62,17 @@ class BeamSettings:
         self.gantryToImIdx = gantryToImIdx
         self.gantryToDoseIdx = gantryToDoseIdx
 
+    FIELDS = ("spotWeights", "beamEnergies", "spotSigmas", "raySpacing", "tracerSteps", "sourceDist", "spotIdxToGantry",
+              "gantryToImIdx", "gantryToDoseIdx")
+
+    def replace(self, **fields):
+        """A new BeamSettings with the named constructor fields replaced; it goes through __init__ again (float32 conversion,
+        shape assertions). Arrays that are not replaced are shared with self."""
+        unknown = sorted(set(fields) - set(self.FIELDS))
+        if unknown:
+            raise TypeError("BeamSettings.replace: unknown field(s) %s" % ", ".join(unknown))
+        return BeamSettings(*(fields.get(k, getattr(self, k)) for k in self.FIELDS))
+
     def as_abi(self):
         b = abi.RtdBeam()
         b.spot_weights = abi.fptr(self.spotWeights)

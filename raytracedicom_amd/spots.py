@@ -72,5 +72,4 @@ def place_spots(eng, beam, mask, dose_dims, lateral=0.0, proximal=0.0, distal=0.
     weights = sel[layers][:, y0:y1 + 1, x0:x1 + 1].astype(np.float32)
     t = beam.spotIdxToGantry
     shifted = scenarios.Float3IdxTransform(t.delta, (t.offset[0] + x0 * t.delta[0], t.offset[1] + y0 * t.delta[1], t.offset[2]))
-    return scenarios.BeamSettings(weights, beam.beamEnergies[layers], beam.spotSigmas[layers], beam.raySpacing, beam.tracerSteps,
-                                  beam.sourceDist, shifted, beam.gantryToImIdx, beam.gantryToDoseIdx)
+    return beam.replace(spotWeights=weights, beamEnergies=beam.beamEnergies[layers], spotSigmas=beam.spotSigmas[layers], spotIdxToGantry=shifted)

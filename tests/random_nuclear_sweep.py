@@ -1,5 +1,5 @@
 """Random sweep of the NUCLEAR_CORR restatement on a GPU box (not collected by pytest): seeded random scenarios, all three variants,
-through tests/test_gpu_nuclear._run — radius classes and batch radii bit for bit, IDD, dose and gamma against the CPU oracle.
+through tests/gpu_support.compare_nuclear_field — radius classes and batch radii bit for bit, IDD, dose and gamma against the CPU oracle.
 Usage: python tests/random_nuclear_sweep.py FIRST_SEED END_SEED."""
 import os, sys, math
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -8,7 +8,7 @@ import numpy as np, torch
 torch.zeros(1, device="cuda")
 from oracle import oracle as orc
 from raytracedicom_amd import abi, engine, luts, scenarios
-import test_gpu_nuclear as T
+import gpu_support as T
 orc.lib(); orc.set_threads(16)
 nuc = luts.synth_luts(nuclear=True)
 n_ok = 0
@@ -25,7 +25,7 @@ for seed in range(int(sys.argv[1]), int(sys.argv[2])):
         beam = scenarios.make_field(nuc, n, 256.0 / n, (-128.0, -128.0, -106.0), float(rng.choice([0.0, 90.0, 180.0])), spots, pitch, n_layers,
                                     int(rng.integers(1, 999)), start_z=150.0)
         scn = scenarios.Scenario("hetero_air_gap", nuc, ct, (256.0 / n,) * 3, [beam])
-    T._run(orc, engine, scn, opt)
+    T.compare_nuclear_field(orc, engine, scn, opt)
     n_ok += 1
     print("seed", seed, "ok", n, variant, spots, pitch, n_layers, flush=True)
 print("all", n_ok, "ok")

@@ -1,4 +1,4 @@
-"""Random parity sweep on a GPU box (not collected by pytest): seeded random scenarios through tests/test_gpu_parity._compare_field,
+"""Random parity sweep on a GPU box (not collected by pytest): seeded random scenarios through tests/gpu_support.compare_field,
 every intermediate and the dose against the CPU oracle. Usage: python tests/random_parity_sweep.py FIRST_SEED END_SEED [rays | angles].
 Ray weights and every integer are compared bit for bit; dose deviations confined to the tail are reported and the sweep goes on;
 anything else raises."""
@@ -9,7 +9,7 @@ import numpy as np, torch
 torch.zeros(1, device="cuda")
 from oracle import oracle as orc
 from raytracedicom_amd import engine, luts, scenarios
-import test_gpu_parity as T
+import gpu_support as T
 orc.lib(); orc.set_threads(16)
 synth = luts.synth_luts()
 n_ok = 0
@@ -32,7 +32,7 @@ for seed in range(int(sys.argv[1]), int(sys.argv[2])):
     scn = scenarios.hetero_ct(synth, n=n, spots=spots, pitch=pitch, n_layers=n_layers, angles=[deg], source_dist=dist, steps=steps, ct=ct,
                               ray_spacing=(rs, rs))
     try:
-        T._compare_field(orc, engine, scn, scn.beams[0])
+        T.compare_field(orc, engine, scn, scn.beams[0])
     except RuntimeError as e:
         if "larger than allowed" not in str(e):
             raise
@@ -42,11 +42,14 @@ for seed in range(int(sys.argv[1]), int(sys.argv[2])):
         import traceback
         tb = traceback.format_exc()
         if "of.status == 0" in tb:             # the oracle stopped (a radius class beyond 32, where the reference throws): the engine must report it too
+            rig = T.FieldRig(engine, scn, None)
             try:
-                T._run_engine(engine, scn, scn.beams[0])
+                rig.compute(rig.field(scn.beams[0]))
                 raise SystemExit("seed %d: the oracle reports an error, the engine does not" % seed)
             except RuntimeError as e2:
                 assert "larger than allowed" in str(e2), str(e2)
+            finally:
+                rig.close()
             print("seed", seed, "radius overflow: oracle and engine both report it, rays", rs)
             continue
         if "(1.0, 0, 0.0)" in str(e):          # pencil too thin for the gamma sampling grid: every other comparison passed

@@ -1,5 +1,5 @@
 """Random sweep of water fields on a GPU box (not collected by pytest): the device-side uniform-sigma detection and the separable
-superposition kernel (rtd_uniform.hpp) through tests/test_gpu_parity._compare_field — every intermediate, the BEV dose, the dose
+superposition kernel (rtd_uniform.hpp) through tests/gpu_support.compare_field — every intermediate, the BEV dose, the dose
 and gamma against the CPU oracle — for seeded random water cubes (size, spots, pitch, layers, steps, homogeneous density); the field
 must report uniform_sigma = 1 when the beam is parallel, 0 when it diverges. Usage: FIRST_SEED END_SEED."""
 import os, sys, math
@@ -9,7 +9,7 @@ import numpy as np, torch
 torch.zeros(1, device="cuda")
 from oracle import oracle as orc
 from raytracedicom_amd import engine, luts, scenarios
-import test_gpu_parity as T
+import gpu_support as T
 orc.lib(); orc.set_threads(16)
 synth = luts.synth_luts()
 n_ok = n_uni = 0
@@ -29,7 +29,7 @@ for seed in range(int(sys.argv[1]), int(sys.argv[2])):
                                ray_spacing=(rs, rs))
     scn.ct[:] = float(rng.choice([1000.0, 1000.0, 900.0, 1150.0]))       # homogeneous, not necessarily water
     try:
-        dose, ref, timing, info = T._compare_field(orc, engine, scn, scn.beams[0])
+        dose, ref, timing, info = T.compare_field(orc, engine, scn, scn.beams[0])
     except AssertionError as e:
         if "(1.0, 0, 0.0)" in str(e):
             print("seed", seed, "gamma had no voxels to evaluate (all other comparisons passed)"); n_ok += 1; continue

@@ -16,8 +16,7 @@ def scene(luts, name):
     scn = S.scene(luts, name)
     b = scn.beams[0]
     energies, sigmas = scenarios.water_cube_energies(luts, 8, e0=70.0, e1=125.0)
-    scn.beams = [scenarios.BeamSettings(np.ones((8, 7, 9), dtype=np.float32), energies, sigmas, b.raySpacing, b.tracerSteps, b.sourceDist,
-                                        b.spotIdxToGantry, b.gantryToImIdx, b.gantryToDoseIdx)]
+    scn.beams = [b.replace(spotWeights=np.ones((8, 7, 9), dtype=np.float32), beamEnergies=energies, spotSigmas=sigmas)]
     return scn
 
 
@@ -76,5 +75,4 @@ def with_last_energy(luts, beam, energy):
     energies[-1] = energy
     sigmas = beam.spotSigmas.copy()
     sigmas[-1] = scenarios.water_cube_energies(luts, 1, e0=energy)[1][0]
-    return scenarios.BeamSettings(beam.spotWeights, energies, sigmas, beam.raySpacing, beam.tracerSteps, beam.sourceDist, beam.spotIdxToGantry,
-                                  beam.gantryToImIdx, beam.gantryToDoseIdx)
+    return beam.replace(beamEnergies=energies, spotSigmas=sigmas)

@@ -115,3 +115,23 @@ def test_lattice_grid_samples_the_ct_grid_dose(runs, name):
     i_ct = float(d_ct.astype(np.float64).sum() * np.prod(scn_ct.dose_spacing))
     print("scene %s: integral %.5g on the coarse grid, %.5g on the CT grid" % (name, i_coarse, i_ct))
     assert 0.9 * i_ct <= i_coarse <= i_ct
+
+
+def test_beam_settings_replace(synth):
+    """BeamSettings.replace changes the named field and keeps the other eight; the new beam goes through __init__ again (the shape
+    assertion fires on a weight array of another layer count); a name that is no constructor field is a TypeError."""
+    b = S.scene(synth, "A").beams[0]
+    w = np.full(b.spotWeights.shape, 2.0)                             # float64: converted like a constructor argument
+    c = b.replace(spotWeights=w)
+    assert c is not b and c.spotWeights.dtype == np.float32 and np.array_equal(c.spotWeights, w)
+    assert not np.array_equal(b.spotWeights, w)                       # the original is untouched
+    for k in ("beamEnergies", "spotIdxToGantry", "gantryToImIdx", "gantryToDoseIdx"):
+        assert getattr(c, k) is getattr(b, k), k
+    assert np.shares_memory(c.spotSigmas, b.spotSigmas) and c.spotSigmas.shape == b.spotSigmas.shape
+    assert (c.raySpacing, c.tracerSteps, c.sourceDist) == (b.raySpacing, b.tracerSteps, b.sourceDist)
+    t = object()
+    assert b.replace(gantryToDoseIdx=t).gantryToDoseIdx is t and b.replace().spotWeights is b.spotWeights
+    with pytest.raises(AssertionError):
+        b.replace(spotWeights=np.ones((b.spotWeights.shape[0] + 1,) + b.spotWeights.shape[1:]))
+    with pytest.raises(TypeError):
+        b.replace(spotWeight=w)

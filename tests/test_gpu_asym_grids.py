@@ -10,23 +10,12 @@ import pytest
 import asym_scenes as S
 import dvh_reference as D
 import optimizer_reference as R
-from test_gpu_dose_influence_apply import Rig as ProductRig
-from test_gpu_dose_influence_apply import _box_mask, _col_bound, _gamma, _row_bound, _with_weights, _worst_ratio
-from test_gpu_gradient import Rig as GradientRig
-from test_gpu_gradient import _end_to_end, _stage_identities
-from test_gpu_nuclear import _run as _compare_nuclear_field
-from test_gpu_optimizer import _bits
-from test_gpu_parity import _compare_field, _rel_close
+from gpu_support import (FieldRig, bits, box_mask, col_bound, compare_field, compare_nuclear_field, end_to_end, gamma, nuc_luts,  # noqa: F401
+                         rel_close, row_bound, stage_identities, worst_ratio)
 
 pytestmark = pytest.mark.gpu
 
 NAN_BITS = np.float32(np.nan).view(np.uint32)
-
-
-@pytest.fixture(scope="module")
-def nuc_luts():
-    from raytracedicom_amd import luts
-    return luts.synth_luts(nuclear=True)
 
 
 @pytest.fixture(scope="module")
@@ -61,12 +50,12 @@ def _same_bits(a, b):
 
 @pytest.mark.parametrize("name", ["A", "B", "C", "D", "F", "H", "W", "U"])
 def test_stage_parity_with_the_oracle(orc, engine, synth, name):
-    """test_gpu_parity._compare_field, every assertion of it, with the dose grid apart from the CT's: tracer outputs, ray weights,
+    """gpu_support.compare_field, every assertion of it, with the dose grid apart from the CT's: tracer outputs, ray weights,
     first_passive, tile and batch radii bit-exact; layer_plan 1e-6; idd, 1/sigma 2e-5; BEV, dose 1e-4; gamma 100 % with the dose
     grid's own anisotropic spacing. F has radii above 16 (second sweep launch); U is the one scene with one sigma per slice (the
     separable kernels); W, water as well, is not: its oblique divergent beam has per-ray sigmas."""
     scn = S.scene(synth, name)
-    dose, ref, _, info = _compare_field(orc, engine, scn, scn.beams[0], dose_dims=scn.dose_dims, dose_spacing=scn.dose_spacing)
+    dose, ref, _, info = compare_field(orc, engine, scn, scn.beams[0], dose_dims=scn.dose_dims, dose_spacing=scn.dose_spacing)
     assert dose.shape == scn.dose_shape and dose.max() > 0
     assert info["uniform_sigma"] == (1 if name == "U" else 0)
     if name == "F":
@@ -77,7 +66,7 @@ def test_stage_parity_with_nuclear_correction(orc, engine, nuc_luts):
     """Scene N: W with the nuclear tables and RTD_NUC_SOUKUP, through test_gpu_nuclear's comparison (radius classes bit-exact, idd 2e-5,
     dose 1e-4 / 2e-5 of the maximum, gamma 100 %)."""
     scn = S.scene(nuc_luts, "N")
-    dose, ref, info = _compare_nuclear_field(orc, engine, scn, S.options("N"), dose_dims=scn.dose_dims, dose_spacing=scn.dose_spacing)
+    dose, ref, info = compare_nuclear_field(orc, engine, scn, S.options("N"), dose_dims=scn.dose_dims, dose_spacing=scn.dose_spacing)
     assert dose.shape == scn.dose_shape
     assert info["beam_first_inside"] == 0                             # the beam starts in the water: the halo's slice 0 is deposited
 
@@ -107,7 +96,7 @@ def test_deferred_ct_upload_on_the_non_cubic_ct(engine, synth, name):
 
 
 def test_reference_shaped_call_and_in_process_plan(orc, engine, synth):
-    """Two beams (A and H) on the coarse grid: rtd_compute against orc_compute (_rel_close, 1e-4); rtd_plan_compute with two and three
+    """Two beams (A and H) on the coarse grid: rtd_compute against orc_compute (rel_close, 1e-4); rtd_plan_compute with two and three
     handles equal to it bit for bit — 37 dose slices give uneven z-slabs."""
     scn = S.scene(synth, "AH")
     assert scn.dose_dims == (45, 52, 37)
@@ -119,7 +108,7 @@ def test_reference_shaped_call_and_in_process_plan(orc, engine, synth):
         eng.set_ct(scn.ct)
         eng.compute(scn.beams, want)
     assert want.max() > 1e-6
-    _rel_close(want, ref, rtol=1e-4)
+    rel_close(want, ref, rtol=1e-4)
     for devices in ([0, 0], [0, 0, 0]):
         got = base.copy()
         with engine.Plan(devices) as plan:
@@ -134,7 +123,7 @@ def test_reference_shaped_call_and_in_process_plan(orc, engine, synth):
 
 def test_transfers_and_clip_boxes(engine, synth, oracle_dose):
     """Fields A and H on the coarse grid (k_transfer<INIT>, k_transfer / k_transfer_t, k_clear_box, k_transfer_multi with nx != ny != nz):
-    transfer_init into a NaN-filled volume and transfer onto a random base against the oracle's dose (_rel_close, 1e-4); the same two
+    transfer_init into a NaN-filled volume and transfer onto a random base against the oracle's dose (rel_close, 1e-4); the same two
     clipped to the inclusive box (5, 3, 2)-(37, 44, 30) — six different bounds, none on a brick edge — change nothing outside it and
     give the unclipped bits inside; clear_dose_box zeroes the part of the dose box inside it and nothing else; transfer_fields_init of
     both fields equals transfer_init + transfer bit for bit, on the whole grid and in the box."""
@@ -165,9 +154,9 @@ def test_transfers_and_clip_boxes(engine, synth, oracle_dose):
             assert (box & clip).any() and (box & ~clip).any()
             init = run(nans, f.transfer_init)
             assert (init.view(np.uint32)[~box] == NAN_BITS).all() and np.isfinite(init[box]).all()
-            _rel_close(np.where(box, init, np.float32(0.0)), ref, rtol=1e-4)
+            rel_close(np.where(box, init, np.float32(0.0)), ref, rtol=1e-4)
             acc = run(base, f.transfer)
-            _rel_close(acc, base + ref, rtol=1e-4)
+            rel_close(acc, base + ref, rtol=1e-4)
             assert _same_bits(acc[~box], base[~box])
             # clipped: outside the box nothing changes, inside it the unclipped bits
             init_c = run(nans, f.transfer_init, lo, hi)
@@ -206,14 +195,14 @@ def test_transposed_path(engine, synth, name):
     and the adjoint superposition with the dose dims apart from the CT's. U takes the separable kernels, F radii above 16."""
     scn = S.scene(synth, name)
     g = (np.random.default_rng(3).random(scn.dose_shape) - 0.3).astype(np.float32)
-    rig = GradientRig(engine, scn, S.options(name, cutoff=0.0), dose_shape=scn.dose_shape)
+    rig = FieldRig(engine, scn, S.options(name, cutoff=0.0), dims=scn.dose_dims)
     try:
         assert rig.dims == scn.dose_dims
-        _, _, _, info = _stage_identities(rig, scn.beams[0], g, 1e-5)
+        _, _, _, info = stage_identities(rig, scn.beams[0], g, 1e-5)
         assert info["uniform_sigma"] == (1 if name == "U" else 0)
         if name == "F":
             assert info["max_radius"] > 16
-        _end_to_end(rig, scn.beams[0], g, seed=4, tol=1e-5)
+        end_to_end(rig, scn.beams[0], g, seed=4, tol=1e-5)
     finally:
         rig.close()
 
@@ -223,12 +212,13 @@ def test_host_form_of_the_gradient(engine, synth):
     test_gpu_gradient.test_host_form_equals_the_field_calls)."""
     scn = S.scene(synth, "AH")
     g = (np.random.default_rng(9).random(scn.dose_shape) - 0.3).astype(np.float32)
-    rig = GradientRig(engine, scn, S.options(cutoff=0.0), dose_shape=scn.dose_shape)
+    rig = FieldRig(engine, scn, S.options(cutoff=0.0), dims=scn.dose_dims)
     try:
         per = []
         for b in scn.beams:
-            f, _, _ = rig.forward(b)
-            per.append(rig.grad(f, b, g))
+            f = rig.field(b)
+            rig.compute(f)
+            per.append(rig.grad(f, g))
         host = rig.eng.spot_gradient(scn.beams, g)
         assert len(host) == 2
         for p, q in zip(per, host):
@@ -248,7 +238,7 @@ def test_dose_influence_and_its_products(engine, synth, oracle_dose, name):
     test_apply_t_is_the_gradient); apply(init = 1) into NaNs writes the dose box and nothing else."""
     scn, ref = oracle_dose(name, 0.0)
     b = scn.beams[0]
-    rig = ProductRig(engine, scn, S.options(name, cutoff=0.0), dims=scn.dose_dims)
+    rig = FieldRig(engine, scn, S.options(name, cutoff=0.0), dims=scn.dose_dims)
     try:
         f = rig.field(b)
         d = f.dose_influence()
@@ -264,7 +254,7 @@ def test_dose_influence_and_its_products(engine, synth, oracle_dose, name):
         for p in [(0, 0, 0), (L - 1, ny - 1, nx - 1), (1, 1, 2)]:
             e = np.zeros(b.spotWeights.shape, dtype=np.float32)
             e[p] = 1.0
-            dense = rig.dose(_with_weights(b, e)).reshape(-1)
+            dense = rig.dose(b.replace(spotWeights=e)).reshape(-1)
             col = np.zeros(d.shape[0], dtype=np.float32)
             rows, vals = d.column((p[0] * ny + p[1]) * nx + p[2])
             col[rows] = vals
@@ -272,14 +262,14 @@ def test_dose_influence_and_its_products(engine, synth, oracle_dose, name):
             assert float(np.abs(col - dense).max()) <= 1e-6 * float(dense.max()), (p, float(np.abs(col - dense).max()), float(dense.max()))
         # apply = the forward at other weights
         w = (b.spotWeights * (0.5 + np.random.default_rng(11).random(b.spotWeights.shape))).astype(np.float32)
-        dw, _ = rig.compute(rig.field(_with_weights(b, w)))
+        dw, _, _ = rig.compute(rig.field(b.replace(spotWeights=w)))
         fwd = dw.reshape(-1).astype(np.float64)
         got = rig.product(f, w)
-        nr, sr = _row_bound(d, w)
+        nr, sr = row_bound(d, w)
         err = np.abs(got.astype(np.float64) - fwd)
-        assert fwd.max() > 0 and np.all(err <= 1e-5 * fwd.max() + _gamma(nr) * sr), float(np.max(err - _gamma(nr) * sr)) / fwd.max()
+        assert fwd.max() > 0 and np.all(err <= 1e-5 * fwd.max() + gamma(nr) * sr), float(np.max(err - gamma(nr) * sr)) / fwd.max()
         # apply(init = 1) into NaNs: the dose box is written (sum or 0), nothing outside it
-        box = _box_mask(rig, info)
+        box = box_mask(rig, info)
         assert box.any()
         into_nan = rig.apply(f, w)
         assert (into_nan.view(np.uint32)[~box] == NAN_BITS).all()
@@ -289,10 +279,10 @@ def test_dose_influence_and_its_products(engine, synth, oracle_dose, name):
         g = (np.random.default_rng(6).random(rig.shape) - 0.3).astype(np.float32)
         grad = rig.grad(f, g).reshape(-1).astype(np.float64)
         got_t = rig.apply_t(f, g).reshape(-1).astype(np.float64)
-        nc, sc = _col_bound(d, g)
+        nc, sc = col_bound(d, g)
         assert (sc > 0).sum() > 0
         err_t = np.abs(got_t - grad)
-        assert np.all(err_t <= (1e-5 + _gamma(nc)) * sc + 1e-30), _worst_ratio(err_t, (1e-5 + _gamma(nc)) * sc)
+        assert np.all(err_t <= (1e-5 + gamma(nc)) * sc + 1e-30), worst_ratio(err_t, (1e-5 + gamma(nc)) * sc)
     finally:
         rig.close()
 
@@ -386,7 +376,7 @@ def test_optimizer_and_dvh_on_the_coarse_grid(engine, synth):
                   % (it, hist[it], rep["step"], a_ref, rel, (n + 2) * 2.0 ** -52))
             assert a_ref > 0 and rel <= (n + 2) * 2.0 ** -52
             w_new = np.concatenate([opt.weights(q).reshape(-1) for q in range(2)])
-            assert np.array_equal(_bits(w_new), _bits(R.update(w, grad, rep["step"])))
+            assert np.array_equal(bits(w_new), bits(R.update(w, grad, rep["step"])))
             assert not np.array_equal(w_new, w)
             w_prev, grad_prev = w, grad
         # the DVH of the volume of the last iteration

@@ -4,112 +4,16 @@ Dij is checked against the engine's two other paths: Dij w = D(w) (the forward) 
 transposed path). Dot products and sums are float64 on the host; tolerances are relative to sum |a| |b| of the pair compared. The
 ray-weight cut-off is 0 unless stated otherwise (Dij needs it)."""
 import ctypes as C
-import math
 
 import numpy as np
 import pytest
 
+from gpu_support import FieldRig, hetero_scene, options, radii_above_16, rig_fixture
 from raytracedicom_amd import abi, scenarios
 
 pytestmark = pytest.mark.gpu
 
-
-def _opts(cutoff=0.0):
-    o = abi.default_options()
-    o.ray_weight_cutoff = cutoff
-    return o
-
-
-def _with_weights(b, w):
-    return scenarios.BeamSettings(np.ascontiguousarray(w, dtype=np.float32), b.beamEnergies, b.spotSigmas, b.raySpacing, b.tracerSteps,
-                                  b.sourceDist, b.spotIdxToGantry, b.gantryToImIdx, b.gantryToDoseIdx)
-
-
-def _with_dose_grid(b, t):
-    return scenarios.BeamSettings(b.spotWeights, b.beamEnergies, b.spotSigmas, b.raySpacing, b.tracerSteps, b.sourceDist,
-                                  b.spotIdxToGantry, b.gantryToImIdx, t)
-
-
-def _hetero(synth, n=96, angle=30.0, source_dist=(math.inf, math.inf), spots=5, pitch=8.0, layers=3, seed=5, **kw):
-    ct, _ = scenarios.hetero_phantom(n)
-    return scenarios.hetero_ct(synth, n=n, spots=spots, pitch=pitch, n_layers=layers, angles=[angle], ct=ct, source_dist=source_dist,
-                               seed=seed, **kw)
-
-
-def _radii_above_16(synth):
-    ct, _ = scenarios.hetero_phantom(96)
-    beam = scenarios.make_field(synth, 96, 256.0 / 96, (-128.0, -128.0, -106.0), 0.0, 4, 6.0, 3, 21, steps=200, ray_spacing=(0.5, 0.5),
-                                weight_lo=400.0)
-    return scenarios.Scenario("rays 0.5 mm", synth, ct, (256.0 / 96,) * 3, [beam])
-
-
-class Rig:
-    """One engine with the scenario's CT and LUTs and device volumes on the dose grid dims (x, y, z)."""
-
-    def __init__(self, engine, scn, opt, dims=None):
-        self.engine = engine
-        self.eng = engine.Engine(0)
-        self.eng.set_options(opt)
-        self.eng.set_luts(scn.luts)
-        self.eng.set_ct(scn.ct)
-        self.dims = tuple(dims or scn.dims)
-        self.shape = (self.dims[2], self.dims[1], self.dims[0])
-        self.nb = int(np.prod(self.shape)) * 4
-        self.dDose = self.eng.device_alloc(self.nb)
-        self.dG = self.eng.device_alloc(self.nb)
-        self.fields = []
-
-    def field(self, beam):
-        f = self.eng.create_field(beam, self.dims)
-        self.fields.append(f)
-        return f
-
-    def compute(self, f):
-        self.eng.device_zero(self.dDose, self.nb)
-        f.compute(self.dDose)
-        _, info = f.finish()
-        dose = np.empty(self.shape, dtype=np.float32)
-        self.eng.to_host(dose, self.dDose)
-        return dose, info
-
-    def dose(self, beam):
-        f = self.field(beam)
-        d, _ = self.compute(f)
-        self.fields.remove(f)
-        f.destroy()
-        return d
-
-    def grad(self, f, g):
-        self.eng.to_device(self.dG, np.ascontiguousarray(g, dtype=np.float32))
-        shape = f._beam.spotWeights.shape
-        dOut = self.eng.device_alloc(int(np.prod(shape)) * 4)
-        try:
-            f.spot_gradient(self.dG, dOut)
-            out = np.empty(shape, dtype=np.float32)
-            self.eng.to_host(out, dOut)
-        finally:
-            self.eng.device_free(dOut)
-        return out
-
-    def close(self):
-        for f in self.fields:
-            f.destroy()
-        self.eng.device_free(self.dDose)
-        self.eng.device_free(self.dG)
-        self.eng.close()
-
-
-@pytest.fixture
-def rig_of(engine):
-    rigs = []
-
-    def make(scn, opt, dims=None):
-        r = Rig(engine, scn, opt, dims)
-        rigs.append(r)
-        return r
-    yield make
-    for r in rigs:
-        r.close()
+rig_of = rig_fixture(FieldRig)
 
 
 def _check_csc(d):
@@ -126,7 +30,7 @@ def _linearity(rig, beam, seed, tol=1e-5):
     d = f.dose_influence()
     _check_csc(d)
     w = (beam.spotWeights * (0.5 + np.random.default_rng(seed).random(beam.spotWeights.shape))).astype(np.float32)
-    dw, info = rig.compute(rig.field(_with_weights(beam, w)))
+    dw, info, _ = rig.compute(rig.field(beam.replace(spotWeights=w)))
     a = d.matvec(w)
     b = dw.reshape(-1).astype(np.float64)
     scale = float(np.abs(b).max())
@@ -138,9 +42,9 @@ def _linearity(rig, beam, seed, tol=1e-5):
 def test_columns_are_single_spot_doses(rig_of, synth):
     """Column j at threshold 0 is the dose of a fresh field with one-hot weights e_j: edge spots and interior spots, at least two of
     them in one batch, within 1e-6 of the column maximum (the other spots of a batch add exact zeros)."""
-    scn = _hetero(synth, angle=20.0, spots=(4, 3), pitch=50.0, layers=2)    # (spots far apart: their grown footprints can share a batch)
+    scn = hetero_scene(synth, 96, [20.0], spots=(4, 3), pitch=50.0, layers=2)    # (spots far apart: their grown footprints can share a batch)
     b = scn.beams[0]
-    rig = rig_of(scn, _opts(0.0))
+    rig = rig_of(scn, options(0.0))
     f = rig.field(b)
     d = f.dose_influence()
     batch = f.fetch("dij_batch")
@@ -154,7 +58,7 @@ def test_columns_are_single_spot_doses(rig_of, synth):
     for j, p in zip(js, picks):
         e = np.zeros(b.spotWeights.shape, dtype=np.float32)
         e[p] = 1.0
-        dense = rig.dose(_with_weights(b, e)).reshape(-1)
+        dense = rig.dose(b.replace(spotWeights=e)).reshape(-1)
         col = np.zeros(d.shape[0], dtype=np.float32)
         rows, vals = d.column(j)
         col[rows] = vals
@@ -173,23 +77,23 @@ def test_linearity(rig_of, synth, case):
     """Dij w = D(w) for random w, on every superposition / transfer path and on a half-resolution dose grid."""
     dims = None
     if case == "row_sweep":
-        scn = _hetero(synth, angle=0.0)
+        scn = hetero_scene(synth, 96, [0.0])
     elif case == "radii_above_16":
-        scn = _radii_above_16(synth)
+        scn = radii_above_16(synth)
     elif case == "water_uniform":
         scn = scenarios.water_cube(synth, n=96, n_layers=3, spots=6, pitch=5.0)
     elif case == "beam_along_x":
-        scn = _hetero(synth, angle=90.0)
+        scn = hetero_scene(synth, 96, [90.0])
     elif case == "finite_source":
-        scn = _hetero(synth, angle=20.0, source_dist=(1800.0, 2100.0))
+        scn = hetero_scene(synth, 96, [20.0], source_dist=(1800.0, 2100.0))
     else:
-        scn = _hetero(synth, angle=30.0)
+        scn = hetero_scene(synth, 96, [30.0])
         t = scn.beams[0].gantryToDoseIdx
         # dose voxel i covers CT voxels 2i, 2i + 1: index = 0.5 * ct index - 0.25
         half = scenarios.Float3AffineTransform(0.5 * t.m, 0.5 * t.v - 0.25)
-        scn.beams[0] = _with_dose_grid(scn.beams[0], half)
+        scn.beams[0] = scn.beams[0].replace(gantryToDoseIdx=half)
         dims = (48, 48, 48)
-    rig = rig_of(scn, _opts(0.0), dims)
+    rig = rig_of(scn, options(0.0), dims)
     _, _, info = _linearity(rig, scn.beams[0], seed=11)
     if case == "radii_above_16":
         assert info["max_radius"] > 16
@@ -200,9 +104,9 @@ def test_linearity(rig_of, synth, case):
 @pytest.mark.parametrize("case", ["row_sweep", "finite_source"])
 def test_transpose_is_the_gradient(rig_of, synth, case):
     """Dij^T g = rtd_field_spot_gradient(g) per spot, relative to sum |Dij[:, j]| |g|."""
-    scn = _hetero(synth, angle=0.0) if case == "row_sweep" else _hetero(synth, angle=25.0, source_dist=(1900.0, 2200.0))
+    scn = hetero_scene(synth, 96, [0.0]) if case == "row_sweep" else hetero_scene(synth, 96, [25.0], source_dist=(1900.0, 2200.0))
     b = scn.beams[0]
-    rig = rig_of(scn, _opts(0.0))
+    rig = rig_of(scn, options(0.0))
     f = rig.field(b)
     d = f.dose_influence()
     g = (np.random.default_rng(6).random(rig.shape) - 0.3).astype(np.float32)
@@ -218,7 +122,7 @@ def test_transpose_is_the_gradient(rig_of, synth, case):
 def test_against_the_cpu_oracle(rig_of, synth, orc):
     """C1 (water 128^3, one layer): Dij w = the oracle's dose at cut-off 0."""
     scn = scenarios.water_cube(synth, n=128, n_layers=1)
-    opt = _opts(0.0)
+    opt = options(0.0)
     rig = rig_of(scn, opt)
     d = rig.field(scn.beams[0]).dose_influence()
     ref = orc.compute(scn, options=opt).reshape(-1).astype(np.float64)
@@ -229,24 +133,24 @@ def test_against_the_cpu_oracle(rig_of, synth, orc):
 def test_dense_spots_force_many_batches(rig_of, synth):
     """A 2 mm spot pitch: the grown footprints overlap, so the spots need many batches; every column is a proper set of voxels, and
     the columns sum to the forward at w = 1."""
-    scn = _hetero(synth, angle=10.0, spots=9, pitch=2.0, layers=2)
+    scn = hetero_scene(synth, 96, [10.0], spots=9, pitch=2.0, layers=2)
     b = scn.beams[0]
-    rig = rig_of(scn, _opts(0.0))
+    rig = rig_of(scn, options(0.0))
     f = rig.field(b)
     d = f.dose_influence()
     batch = f.fetch("dij_batch")
     assert batch.max() + 1 > 1
     _check_csc(d)
     ones = np.ones(b.spotWeights.shape, dtype=np.float32)
-    d1 = rig.dose(_with_weights(b, ones)).reshape(-1).astype(np.float64)
+    d1 = rig.dose(b.replace(spotWeights=ones)).reshape(-1).astype(np.float64)
     a = d.matvec(ones)
     assert float(np.abs(a - d1).max()) <= 1e-5 * float(d1.max())
 
 
 def test_threshold(rig_of, synth):
     """Kept entries are >= t * column max; what t drops from the t = 0 matrix is below it; nnz is monotone in t."""
-    scn = _hetero(synth, angle=0.0)
-    rig = rig_of(scn, _opts(0.0))
+    scn = hetero_scene(synth, 96, [0.0])
+    rig = rig_of(scn, options(0.0))
     f = rig.field(scn.beams[0])
     d0 = f.dose_influence(0.0)
     last = d0.nnz
@@ -268,11 +172,11 @@ def test_threshold(rig_of, synth):
 
 def test_reproducible_and_without_side_effects(rig_of, synth):
     """Two calls give identical arrays; the field's BEV dose, a following transfer and gradient are bit-identical to before."""
-    scn = _hetero(synth, angle=30.0, layers=2)
+    scn = hetero_scene(synth, 96, [30.0], layers=2)
     b = scn.beams[0]
-    rig = rig_of(scn, _opts(0.0))
+    rig = rig_of(scn, options(0.0))
     f = rig.field(b)
-    dose0, _ = rig.compute(f)
+    dose0, _, _ = rig.compute(f)
     bev0 = f.fetch("bev").copy()
     g = (np.random.default_rng(2).random(rig.shape) - 0.5).astype(np.float32)
     grad0 = rig.grad(f, g)
@@ -292,9 +196,9 @@ def test_reproducible_and_without_side_effects(rig_of, synth):
 
 def test_without_a_prior_compute(rig_of, synth):
     """A field never computed: the call runs the forward itself, and the field then transfers its own dose."""
-    scn = _hetero(synth, angle=0.0, layers=2)
+    scn = hetero_scene(synth, 96, [0.0], layers=2)
     b = scn.beams[0]
-    rig = rig_of(scn, _opts(0.0))
+    rig = rig_of(scn, options(0.0))
     ref = rig.dose(b)
     f = rig.field(b)
     d = f.dose_influence()
@@ -311,9 +215,9 @@ def test_without_a_prior_compute(rig_of, synth):
 def test_set_spot_weights(rig_of, synth, cutoff):
     """After set_spot_weights a compute equals a fresh field with those weights bit for bit, and so does its gradient. Under cut-off 1
     the new weights change the live set (spots below the cut-off): the hints of the last compute must not survive."""
-    scn = _hetero(synth, angle=15.0, layers=2)
+    scn = hetero_scene(synth, 96, [15.0], layers=2)
     b = scn.beams[0]
-    rig = rig_of(scn, _opts(cutoff))
+    rig = rig_of(scn, options(cutoff))
     f = rig.field(b)
     rig.compute(f)
     rig.compute(f)                                                    # (a finished compute: the field holds its hints)
@@ -326,10 +230,10 @@ def test_set_spot_weights(rig_of, synth, cutoff):
     finally:
         rig.eng.sync()
         rig.eng.device_free(dW)
-    got, _ = rig.compute(f)
-    b2 = _with_weights(b, w)
+    got, _, _ = rig.compute(f)
+    b2 = b.replace(spotWeights=w)
     f2 = rig.field(b2)
-    ref, _ = rig.compute(f2)
+    ref, _, _ = rig.compute(f2)
     assert np.array_equal(got, ref)
     assert not np.array_equal(got, rig.dose(b))
     g = (np.random.default_rng(4).random(rig.shape) - 0.3).astype(np.float32)
@@ -338,10 +242,10 @@ def test_set_spot_weights(rig_of, synth, cutoff):
 
 def test_engine_form(engine, synth):
     """Engine.dose_influence: one DoseInfluence per beam, each equal to the field call."""
-    scn = _hetero(synth, n=64, angle=0.0, spots=3, layers=1)
+    scn = hetero_scene(synth, 64, [0.0], spots=3, layers=1)
     eng = engine.Engine(0)
     try:
-        eng.set_options(_opts(0.0))
+        eng.set_options(options(0.0))
         eng.set_luts(synth)
         eng.set_ct(scn.ct)
         ds = eng.dose_influence(scn.beams + scn.beams, scn.dims)
@@ -356,20 +260,20 @@ def test_errors(engine, synth):
     """Each refusal returns its status and leaves the field usable: cut-off != 0, nuclear_corr, a remote field, null pointers, a
     threshold outside [0, 1); copy before any result is NOT_READY."""
     L = engine.lib()
-    scn = _hetero(synth, n=64, angle=0.0, spots=3, layers=1)
+    scn = hetero_scene(synth, 64, [0.0], spots=3, layers=1)
     b = scn.beams[0]
     dims = scn.dims
     eng = engine.Engine(0)
     try:
         eng.set_luts(synth)
         eng.set_ct(scn.ct)
-        eng.set_options(_opts(1.0))
+        eng.set_options(options(1.0))
         f1 = eng.create_field(b, dims)
         with pytest.raises(engine.RtdError) as e:
             f1.dose_influence()
         assert e.value.status == abi.RTD_ERR_INVALID_ARG and "ray_weight_cutoff" in str(e.value)
         f1.destroy()
-        eng.set_options(_opts(0.0))
+        eng.set_options(options(0.0))
         f = eng.create_field(b, dims)
         nnz = C.c_size_t(0)
         i64 = np.zeros(16, dtype=np.int64)
@@ -393,7 +297,7 @@ def test_errors(engine, synth):
     from raytracedicom_amd import luts
     nl = luts.synth_luts(nuclear=True)
     scn = scenarios.water_cube(nl, n=64, n_layers=1, spots=5, pitch=6.0)
-    o = _opts(0.0)
+    o = options(0.0)
     o.nuclear_corr = 1                                                # RTD_NUC_SOUKUP
     eng = engine.Engine(0)
     try:

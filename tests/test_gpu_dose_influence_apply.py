@@ -6,189 +6,29 @@ gamma(n) = (n + 1) u / (1 - (n + 1) u), u = 2^-24, n the number of entries of th
 float64 on the host. It is derived, not measured; the fixed trees of the kernels do far better, and the tests print the worst
 observed ratio. The ray-weight cut-off is 0 throughout (Dij needs it)."""
 import ctypes as C
-import math
 
 import numpy as np
 import pytest
 
+from gpu_support import (FieldRig, box_mask, col_bound, col_of_entry, gamma, hetero_scene, options, radii_above_16, rig_fixture, row_bound,
+                         worst_ratio)
 from raytracedicom_amd import abi, scenarios
 
 pytestmark = pytest.mark.gpu
 
-U = 2.0 ** -24
-
-
-def _gamma(n):
-    k = (np.asarray(n, dtype=np.float64) + 1.0) * U
-    return k / (1.0 - k)
-
-
-def _opts(cutoff=0.0):
-    o = abi.default_options()
-    o.ray_weight_cutoff = cutoff
-    return o
-
-
-def _with_weights(b, w):
-    return scenarios.BeamSettings(np.ascontiguousarray(w, dtype=np.float32), b.beamEnergies, b.spotSigmas, b.raySpacing, b.tracerSteps,
-                                  b.sourceDist, b.spotIdxToGantry, b.gantryToImIdx, b.gantryToDoseIdx)
-
-
-def _with_dose_grid(b, t):
-    return scenarios.BeamSettings(b.spotWeights, b.beamEnergies, b.spotSigmas, b.raySpacing, b.tracerSteps, b.sourceDist,
-                                  b.spotIdxToGantry, b.gantryToImIdx, t)
-
-
-def _hetero(synth, n=96, angle=30.0, source_dist=(math.inf, math.inf), spots=5, pitch=8.0, layers=3, seed=5, **kw):
-    ct, _ = scenarios.hetero_phantom(n)
-    return scenarios.hetero_ct(synth, n=n, spots=spots, pitch=pitch, n_layers=layers, angles=[angle], ct=ct, source_dist=source_dist,
-                               seed=seed, **kw)
-
-
-def _radii_above_16(synth):
-    ct, _ = scenarios.hetero_phantom(96)
-    beam = scenarios.make_field(synth, 96, 256.0 / 96, (-128.0, -128.0, -106.0), 0.0, 4, 6.0, 3, 21, steps=200, ray_spacing=(0.5, 0.5),
-                                weight_lo=400.0)
-    return scenarios.Scenario("rays 0.5 mm", synth, ct, (256.0 / 96,) * 3, [beam])
-
-
-class Rig:
-    """One engine with the scenario's CT and LUTs, device volumes on the dose grid dims (x, y, z) and the products' plumbing."""
-
-    def __init__(self, engine, scn, opt, dims=None):
-        self.engine = engine
-        self.eng = engine.Engine(0)
-        self.eng.set_options(opt)
-        self.eng.set_luts(scn.luts)
-        self.eng.set_ct(scn.ct)
-        self.dims = tuple(dims or scn.dims)
-        self.shape = (self.dims[2], self.dims[1], self.dims[0])
-        self.nb = int(np.prod(self.shape)) * 4
-        self.dDose = self.eng.device_alloc(self.nb)
-        self.dG = self.eng.device_alloc(self.nb)
-        self.fields = []
-
-    def field(self, beam):
-        f = self.eng.create_field(beam, self.dims)
-        self.fields.append(f)
-        return f
-
-    def compute(self, f):
-        self.eng.device_zero(self.dDose, self.nb)
-        f.compute(self.dDose)
-        _, info = f.finish()
-        dose = np.empty(self.shape, dtype=np.float32)
-        self.eng.to_host(dose, self.dDose)
-        return dose, info
-
-    def dose(self, beam):
-        f = self.field(beam)
-        d, _ = self.compute(f)
-        self.fields.remove(f)
-        f.destroy()
-        return d
-
-    def _spot_call(self, f, call, g):
-        self.eng.to_device(self.dG, np.ascontiguousarray(g, dtype=np.float32))
-        shape = f._beam.spotWeights.shape
-        dOut = self.eng.device_alloc(int(np.prod(shape)) * 4)
-        try:
-            call(self.dG, dOut)
-            out = np.empty(shape, dtype=np.float32)
-            self.eng.to_host(out, dOut)
-        finally:
-            self.eng.device_free(dOut)
-        return out
-
-    def grad(self, f, g):
-        return self._spot_call(f, f.spot_gradient, g)
-
-    def apply_t(self, f, g):
-        """Dij^T g on the device -> [L][ny][nx] float32."""
-        return self._spot_call(f, f.dose_influence_apply_t, g)
-
-    def apply(self, f, w, into=None, init=True):
-        """Dij w on the device into a copy of `into` (default: a NaN-filled volume) -> the volume."""
-        vol = np.full(self.shape, np.nan, dtype=np.float32) if into is None else np.ascontiguousarray(into, dtype=np.float32)
-        w = np.ascontiguousarray(w, dtype=np.float32)
-        dW = self.eng.device_alloc(w.nbytes)
-        try:
-            self.eng.to_device(dW, w)
-            self.eng.to_device(self.dDose, vol)
-            f.dose_influence_apply(dW, self.dDose, init=init)
-            out = np.empty(self.shape, dtype=np.float32)
-            self.eng.to_host(out, self.dDose)
-        finally:
-            self.eng.device_free(dW)
-        return out
-
-    def product(self, f, w):
-        """Dij w as a flat float32 volume with zeros where nothing was written."""
-        return self.apply(f, w, into=np.zeros(self.shape, dtype=np.float32), init=True).reshape(-1)
-
-    def close(self):
-        for f in self.fields:
-            f.destroy()
-        self.eng.device_free(self.dDose)
-        self.eng.device_free(self.dG)
-        self.eng.close()
-
-
-@pytest.fixture
-def rig_of(engine):
-    rigs = []
-
-    def make(scn, opt, dims=None):
-        r = Rig(engine, scn, opt, dims)
-        rigs.append(r)
-        return r
-    yield make
-    for r in rigs:
-        r.close()
-
-
-def _col_of_entry(d):
-    return np.repeat(np.arange(d.shape[1], dtype=np.int64), np.diff(d.indptr))
-
-
-def _row_bound(d, w):
-    """Per voxel: (entries of the row, sum |a| |w| in float64)."""
-    n = np.bincount(d.indices, minlength=d.shape[0])
-    s = np.bincount(d.indices, weights=np.abs(d.data.astype(np.float64)) * np.abs(np.asarray(w, dtype=np.float64).reshape(-1))[_col_of_entry(d)],
-                    minlength=d.shape[0])
-    return n, s
-
-
-def _col_bound(d, g):
-    """Per spot: (entries of the column, sum |a| |g| in float64)."""
-    n = np.diff(d.indptr)
-    s = np.bincount(_col_of_entry(d), weights=np.abs(d.data.astype(np.float64)) * np.abs(np.asarray(g, dtype=np.float64).reshape(-1))[d.indices],
-                    minlength=d.shape[1])
-    return n, s
-
-
-def _worst_ratio(err, bound):
-    live = bound > 0
-    return float(np.max(err[live] / bound[live])) if live.any() else 0.0
-
-
-def _box_mask(rig, info):
-    lo, hi = info["dose_box_min"], info["dose_box_max"]
-    m = np.zeros(rig.shape, dtype=bool)
-    m[lo[2]:hi[2] + 1, lo[1]:hi[1] + 1, lo[0]:hi[0] + 1] = True
-    return m
+rig_of = rig_fixture(FieldRig)
 
 
 def test_one_hot_products_are_exact(rig_of, synth):
     """apply(e_j, init=1) into NaNs is column j scattered into zeros inside the dose box, NaN outside it; apply_t(e_v) is row v; both
     bit for bit. Doubling the input doubles the output bit for bit."""
-    scn = _hetero(synth, angle=0.0, spots=(7, 3), pitch=50.0, layers=2)   # (the outermost spot columns lie 22 mm outside the CT: empty)
+    scn = hetero_scene(synth, 96, [0.0], spots=(7, 3), pitch=50.0, layers=2)   # (the outermost spot columns lie 22 mm outside the CT: empty)
     b = scn.beams[0]
-    rig = rig_of(scn, _opts(0.0))
+    rig = rig_of(scn, options(0.0))
     f = rig.field(b)
     d = f.dose_influence()
     _, info = f.finish()
-    box = _box_mask(rig, info).reshape(-1)
+    box = box_mask(rig, info).reshape(-1)
     assert box.any() and not box.all()
     lens = np.diff(d.indptr)
     L, ny, nx = b.spotWeights.shape
@@ -213,7 +53,7 @@ def test_one_hot_products_are_exact(rig_of, synth):
     v_one = int(np.nonzero(counts == counts[counts > 0].min())[0][0])
     v_none = int(np.nonzero((counts == 0) & box)[0][0])
     assert counts[v_many] > 1 and counts[v_one] == 1
-    col = _col_of_entry(d)
+    col = col_of_entry(d)
     for v in (v_many, v_one, v_none):
         g = np.zeros(d.shape[0], dtype=np.float32)
         g[v] = 1.0
@@ -235,27 +75,27 @@ def test_one_hot_products_are_exact(rig_of, synth):
 
 def test_against_float64(rig_of, synth):
     """Random w >= 0 and random signed g: every output element within gamma(n) * sum |a| |x| of the float64 host product."""
-    scn = _hetero(synth, angle=30.0)
+    scn = hetero_scene(synth, 96, [30.0])
     b = scn.beams[0]
-    rig = rig_of(scn, _opts(0.0))
+    rig = rig_of(scn, options(0.0))
     f = rig.field(b)
     d = f.dose_influence()
     rng = np.random.default_rng(17)
     w = (100.0 * rng.random(b.spotWeights.shape)).astype(np.float32)
     got = rig.product(f, w).astype(np.float64)
-    n, s = _row_bound(d, w)
+    n, s = row_bound(d, w)
     err = np.abs(got - d.matvec(w))
-    ratio_a = _worst_ratio(err, _gamma(n) * s)
+    ratio_a = worst_ratio(err, gamma(n) * s)
     print("apply: worst |gpu - ref| / bound = %.3g, longest row %d" % (ratio_a, int(n.max())))
-    assert np.all(err <= _gamma(n) * s), ratio_a
+    assert np.all(err <= gamma(n) * s), ratio_a
     g = (rng.random(rig.shape) - 0.5).astype(np.float32)
     got_t = rig.apply_t(f, g).reshape(-1).astype(np.float64)
-    nt, st = _col_bound(d, g)
+    nt, st = col_bound(d, g)
     err_t = np.abs(got_t - d.rmatvec(g))
-    ratio_t = _worst_ratio(err_t, _gamma(nt) * st)
+    ratio_t = worst_ratio(err_t, gamma(nt) * st)
     print("apply_t: worst |gpu - ref| / bound = %.3g, longest column %d" % (ratio_t, int(nt.max())))
     assert nt.max() > 2048                                            # (columns of several chunks)
-    assert np.all(err_t <= _gamma(nt) * st), ratio_t
+    assert np.all(err_t <= gamma(nt) * st), ratio_t
 
 
 CASES = ["row_sweep", "radii_above_16", "water_uniform", "beam_along_x", "finite_source", "coarse_dose_grid"]
@@ -266,34 +106,34 @@ def test_apply_is_the_forward(rig_of, synth, case):
     """apply(w) = rtd_field_compute of a field at w, within 1e-5 of the dose maximum plus the float32 summation bound of the row."""
     dims = None
     if case == "row_sweep":
-        scn = _hetero(synth, angle=0.0)
+        scn = hetero_scene(synth, 96, [0.0])
     elif case == "radii_above_16":
-        scn = _radii_above_16(synth)
+        scn = radii_above_16(synth)
     elif case == "water_uniform":
         scn = scenarios.water_cube(synth, n=96, n_layers=3, spots=6, pitch=5.0)
     elif case == "beam_along_x":
-        scn = _hetero(synth, angle=90.0)
+        scn = hetero_scene(synth, 96, [90.0])
     elif case == "finite_source":
-        scn = _hetero(synth, angle=20.0, source_dist=(1800.0, 2100.0))
+        scn = hetero_scene(synth, 96, [20.0], source_dist=(1800.0, 2100.0))
     else:
-        scn = _hetero(synth, angle=30.0)
+        scn = hetero_scene(synth, 96, [30.0])
         t = scn.beams[0].gantryToDoseIdx
         half = scenarios.Float3AffineTransform(0.5 * t.m, 0.5 * t.v - 0.25)     # dose voxel i covers CT voxels 2i, 2i + 1
-        scn.beams[0] = _with_dose_grid(scn.beams[0], half)
+        scn.beams[0] = scn.beams[0].replace(gantryToDoseIdx=half)
         dims = (48, 48, 48)
     b = scn.beams[0]
-    rig = rig_of(scn, _opts(0.0), dims)
+    rig = rig_of(scn, options(0.0), dims)
     f = rig.field(b)
     d = f.dose_influence()
     w = (b.spotWeights * (0.5 + np.random.default_rng(11).random(b.spotWeights.shape))).astype(np.float32)
-    dw, info = rig.compute(rig.field(_with_weights(b, w)))
+    dw, info, _ = rig.compute(rig.field(b.replace(spotWeights=w)))
     ref = dw.reshape(-1).astype(np.float64)
     got = rig.product(f, w).astype(np.float64)
-    n, s = _row_bound(d, w)
+    n, s = row_bound(d, w)
     scale = float(ref.max())
     assert scale > 0
     err = np.abs(got - ref)
-    assert np.all(err <= 1e-5 * scale + _gamma(n) * s), float(np.max(err - _gamma(n) * s)) / scale
+    assert np.all(err <= 1e-5 * scale + gamma(n) * s), float(np.max(err - gamma(n) * s)) / scale
     if case == "radii_above_16":
         assert info["max_radius"] > 16
     if case == "water_uniform":
@@ -303,18 +143,18 @@ def test_apply_is_the_forward(rig_of, synth, case):
 @pytest.mark.parametrize("case", ["row_sweep", "finite_source"])
 def test_apply_t_is_the_gradient(rig_of, synth, case):
     """apply_t(g) = rtd_field_spot_gradient(g) per spot, within 1e-5 * sum |Dij[:, j]| |g| plus the float32 summation bound."""
-    scn = _hetero(synth, angle=0.0) if case == "row_sweep" else _hetero(synth, angle=25.0, source_dist=(1900.0, 2200.0))
+    scn = hetero_scene(synth, 96, [0.0]) if case == "row_sweep" else hetero_scene(synth, 96, [25.0], source_dist=(1900.0, 2200.0))
     b = scn.beams[0]
-    rig = rig_of(scn, _opts(0.0))
+    rig = rig_of(scn, options(0.0))
     f = rig.field(b)
     d = f.dose_influence()
     g = (np.random.default_rng(6).random(rig.shape) - 0.3).astype(np.float32)
     grad = rig.grad(f, g).reshape(-1).astype(np.float64)
     got = rig.apply_t(f, g).reshape(-1).astype(np.float64)
-    n, s = _col_bound(d, g)
+    n, s = col_bound(d, g)
     assert (s > 0).sum() > 0
     err = np.abs(got - grad)
-    assert np.all(err <= (1e-5 + _gamma(n)) * s + 1e-30), float(np.max(err / np.maximum(s, 1e-300)))
+    assert np.all(err <= (1e-5 + gamma(n)) * s + 1e-30), float(np.max(err / np.maximum(s, 1e-300)))
 
 
 def test_semantics(rig_of, synth):
@@ -323,7 +163,7 @@ def test_semantics(rig_of, synth):
     ct, _ = scenarios.hetero_phantom(96)
     scn = scenarios.hetero_ct(synth, n=96, spots=5, pitch=8.0, n_layers=3, angles=[0.0, 90.0], ct=ct, seed=5)
     b1, b2 = scn.beams
-    rig = rig_of(scn, _opts(0.0))
+    rig = rig_of(scn, options(0.0))
     f1, f2 = rig.field(b1), rig.field(b2)
     d1, d2 = f1.dose_influence(), f2.dose_influence()
     rng = np.random.default_rng(23)
@@ -340,10 +180,10 @@ def test_semantics(rig_of, synth):
     # two fields into one volume
     both = rig.apply(f1, w1, into=np.zeros(rig.shape, dtype=np.float32), init=False)
     both = rig.apply(f2, w2, into=both, init=False).reshape(-1).astype(np.float64)
-    n1, a1 = _row_bound(d1, w1)
-    n2, a2 = _row_bound(d2, w2)
+    n1, a1 = row_bound(d1, w1)
+    n2, a2 = row_bound(d2, w2)
     err = np.abs(both - (d1.matvec(w1) + d2.matvec(w2)))
-    assert np.all(err <= _gamma(n1 + n2) * (a1 + a2)), _worst_ratio(err, _gamma(n1 + n2) * (a1 + a2))
+    assert np.all(err <= gamma(n1 + n2) * (a1 + a2)), worst_ratio(err, gamma(n1 + n2) * (a1 + a2))
     assert np.count_nonzero((n1 > 0) & (n2 > 0)) > 0                  # (the fields do overlap)
     # set_spot_weights leaves the matrix and the companion valid
     g = (rng.random(rig.shape) - 0.5).astype(np.float32)
@@ -361,28 +201,28 @@ def test_semantics(rig_of, synth):
     dt = f1.dose_influence(0.1)
     assert 0 < dt.nnz < d1.nnz
     st = rig.product(f1, w1)
-    nt, at = _row_bound(dt, w1)
-    assert np.all(np.abs(st.astype(np.float64) - dt.matvec(w1)) <= _gamma(nt) * at)
+    nt, at = row_bound(dt, w1)
+    assert np.all(np.abs(st.astype(np.float64) - dt.matvec(w1)) <= gamma(nt) * at)
     assert not np.array_equal(st, s1)
     tt = rig.apply_t(f1, g).reshape(-1).astype(np.float64)
-    nc, ac = _col_bound(dt, g)
-    assert np.all(np.abs(tt - dt.rmatvec(g)) <= _gamma(nc) * ac)
+    nc, ac = col_bound(dt, g)
+    assert np.all(np.abs(tt - dt.rmatvec(g)) <= gamma(nc) * ac)
     assert f1.dose_influence_device()[3] == dt.nnz
 
 
 def test_reproducible_and_without_side_effects(rig_of, synth):
     """Each product twice and on a second engine: identical bits, with and without an explicit prepare; the field's BEV dose, a
     following transfer and gradient and the copied CSC arrays are bit-identical to before."""
-    scn = _hetero(synth, angle=30.0, layers=2)
+    scn = hetero_scene(synth, 96, [30.0], layers=2)
     b = scn.beams[0]
     rng = np.random.default_rng(2)
     w = (100.0 * rng.random(b.spotWeights.shape)).astype(np.float32)
     g = (rng.random(scn.ct.shape) - 0.5).astype(np.float32)
     results = []
     for explicit in (True, False):
-        rig = rig_of(scn, _opts(0.0))
+        rig = rig_of(scn, options(0.0))
         f = rig.field(b)
-        dose0, _ = rig.compute(f)
+        dose0, _, _ = rig.compute(f)
         d = f.dose_influence()
         bev0 = f.fetch("bev").copy()
         grad0 = rig.grad(f, g)
@@ -417,11 +257,11 @@ def test_products_are_hipgraph_capturable(engine, synth):
     give the bits of the direct calls."""
     import torch
     n = 96
-    scn = _hetero(synth, n=n, angle=25.0, layers=2)
+    scn = hetero_scene(synth, n, [25.0], layers=2)
     b = scn.beams[0]
     dev = torch.device("cuda:0")
     eng = engine.Engine(0)
-    eng.set_options(_opts(0.0))
+    eng.set_options(options(0.0))
     eng.set_luts(scn.luts)
     eng.set_ct(scn.ct)
     fld = eng.create_field(b, scn.dims)
@@ -480,9 +320,9 @@ def _descent(matvec, rmatvec, target, w, steps):
 def test_projected_gradient_descent_on_the_device(rig_of, synth):
     """The loop the products exist for: thirty steps with apply / apply_t; the objective never increases and ends at no more than
     half its start. The same steps with the float64 host products run beside it; the difference is reported, not bounded."""
-    scn = _hetero(synth, angle=0.0, spots=5, pitch=8.0, layers=3)
+    scn = hetero_scene(synth, 96, [0.0], spots=5, pitch=8.0, layers=3)
     b = scn.beams[0]
-    rig = rig_of(scn, _opts(0.0))
+    rig = rig_of(scn, options(0.0))
     f = rig.field(b)
     d = f.dose_influence()
     f.dose_influence_prepare()
@@ -503,11 +343,11 @@ def test_errors_and_an_empty_matrix(engine, synth):
     """NOT_READY before any matrix; INVALID_ARG for each null pointer and for a remote field; the field stays usable; an all-empty
     matrix gives zeros / no change."""
     L = engine.lib()
-    scn = _hetero(synth, n=64, angle=0.0, spots=3, layers=1)
+    scn = hetero_scene(synth, 64, [0.0], spots=3, layers=1)
     b = scn.beams[0]
     eng = engine.Engine(0)
     try:
-        eng.set_options(_opts(0.0))
+        eng.set_options(options(0.0))
         eng.set_luts(synth)
         eng.set_ct(scn.ct)
         f = eng.create_field(b, scn.dims)
@@ -542,8 +382,8 @@ def test_errors_and_an_empty_matrix(engine, synth):
         f.dose_influence_apply(dSp, dVol, init=False)
         out = np.empty(nvox, dtype=np.float32)
         eng.to_host(out, dVol)
-        n, s = _row_bound(d, w)
-        assert out.max() > 0 and np.all(np.abs(out.astype(np.float64) - d.matvec(w)) <= _gamma(n) * s)
+        n, s = row_bound(d, w)
+        assert out.max() > 0 and np.all(np.abs(out.astype(np.float64) - d.matvec(w)) <= gamma(n) * s)
         f.destroy()
         # every spot 70 mm outside the CT: no ray meets the phantom, the matrix has no entries
         miss = scenarios.make_field(synth, 64, 4.0, (-128.0, -128.0, -106.0), 0.0, 2, 400.0, 1, 3)

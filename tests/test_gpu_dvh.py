@@ -13,8 +13,9 @@ import pytest
 
 import dvh_reference as D
 import optimizer_reference as R
+from gpu_plan_rigs import OptimizerRig
+from gpu_support import bits, hetero_scene, rig_fixture
 from raytracedicom_amd import abi
-from test_gpu_optimizer import Rig, _bits, _hetero
 
 pytestmark = pytest.mark.gpu
 
@@ -22,7 +23,7 @@ NAN_BITS = np.uint32(0x7FC00123)
 FRACTIONS = (None, 0.02, 0.5, 0.95, 0.98, 1.0)        # None: 1 / N of the ROI
 
 
-class DvhRig(Rig):
+class DvhRig(OptimizerRig):
     """The engine, fields and matrices of the optimiser tests' rig, with objectives of this file's own making beside them."""
 
     def __init__(self, engine, scn):
@@ -71,17 +72,7 @@ class DvhRig(Rig):
         super().close()
 
 
-@pytest.fixture
-def rig_of(engine):
-    rigs = []
-
-    def make(scn):
-        r = DvhRig(engine, scn)
-        rigs.append(r)
-        return r
-    yield make
-    for r in rigs:
-        r.close()
+rig_of = rig_fixture(DvhRig)
 
 
 def _four_rois(rig):
@@ -103,7 +94,7 @@ def test_dose_at_volume_is_the_kth_largest_bit_for_bit(engine, rig_of, synth):
     """Every ROI x fraction in one call, on the field's dose and on a volume of 16 distinct values (ties everywhere); the same bits
     from a second call, from a second engine and from a replayed graph; 64 queries in one call."""
     import torch
-    scn = _hetero(synth, angles=(0.0,))
+    scn = hetero_scene(synth, 96, (0.0,))
     rig = rig_of(scn)
     rois, sizes = _four_rois(rig)
     obj, ref = rig.objective(rois, [])
@@ -119,19 +110,19 @@ def test_dose_at_volume_is_the_kth_largest_bit_for_bit(engine, rig_of, synth):
         got[name] = obj.dose_at_volume(dev, qs)
         for (r, v), a, b in zip(qs, got[name], want):
             print("%s: ROI %d (N %d), v %.6g, k %d: device %.9g restated %.9g" % (name, r, sizes[r], v, D.rank(v, sizes[r]), a, b))
-        assert got[name].dtype == np.float32 and np.array_equal(_bits(got[name]), _bits(want)), name
-        assert np.array_equal(_bits(obj.dose_at_volume(dev, qs)), _bits(want))              # the histograms were left clear
+        assert got[name].dtype == np.float32 and np.array_equal(bits(got[name]), bits(want)), name
+        assert np.array_equal(bits(obj.dose_at_volume(dev, qs)), bits(want))              # the histograms were left clear
     for r, n in enumerate(sizes):                                                           # v = 1 the minimum, 1 / N the maximum
         dv = field[rois[r].reshape(-1)]
         assert got["field"][6 * r] == dv.max() and got["field"][6 * r + 5] == dv.min()
     many = [(r % 4, (1 + r) / 64.0) for r in range(64)]
-    assert np.array_equal(_bits(obj.dose_at_volume(dField, many)), _bits(ref.dose_at_volume(field, many)))
+    assert np.array_equal(bits(obj.dose_at_volume(dField, many)), bits(ref.dose_at_volume(field, many)))
     # a second engine
     other = rig_of(scn)
     obj2, _ = other.objective(rois, [])
     dField2, field2 = other.field_dose()
-    assert np.array_equal(_bits(field2), _bits(field))
-    assert np.array_equal(_bits(obj2.dose_at_volume(dField2, qs)), _bits(got["field"]))
+    assert np.array_equal(bits(field2), bits(field))
+    assert np.array_equal(bits(obj2.dose_at_volume(dField2, qs)), bits(got["field"]))
     # a graph: the call is launches only
     dOut = rig.alloc(4 * 64)
     s = torch.cuda.Stream()
@@ -148,13 +139,13 @@ def test_dose_at_volume_is_the_kth_largest_bit_for_bit(engine, rig_of, synth):
     rig.eng.set_stream(None)
     out = np.empty(64, dtype=np.float32)
     rig.eng.to_host(out, dOut)
-    assert np.array_equal(_bits(out[:24]), _bits(got["field"]))
+    assert np.array_equal(bits(out[:24]), bits(got["field"]))
 
 
 def test_cumulative_histogram_is_exact(rig_of, synth):
     """counts[roi][b] = #(double(d) >= (b * dose_max) / n_bins), as integers: on the field's dose with voxels set to the float32
     nearest to edges (just below, on or just above them) and doses above dose_max; on a volume whose values are edges exactly."""
-    rig = rig_of(_hetero(synth, angles=(0.0,)))
+    rig = rig_of(hetero_scene(synth, 96, (0.0,)))
     rois, sizes = _four_rois(rig)
     obj, ref = rig.objective(rois, [])
     _, field = rig.field_dose()
@@ -189,7 +180,7 @@ def _eval(rig, obj, dDose):
 
 
 def test_eval_with_mixed_terms_on_overlapping_rois(rig_of, synth):
-    rig = rig_of(_hetero(synth, angles=(0.0,)))
+    rig = rig_of(hetero_scene(synth, 96, (0.0,)))
     rois, sizes = _four_rois(rig)
     dField, field = rig.field_dose()
     # the dose of a plan in the making: the field's dose, modulated so that both DVH constraints are violated
@@ -207,10 +198,10 @@ def test_eval_with_mixed_terms_on_overlapping_rois(rig_of, synth):
     obj, ref = rig.objective(rois, terms)
     values, g = _eval(rig, obj, dDose)
     v2, g2 = _eval(rig, obj, dDose)
-    assert np.array_equal(_bits(values), _bits(v2)) and np.array_equal(_bits(g), _bits(g2))
+    assert np.array_equal(bits(values), bits(v2)) and np.array_equal(bits(g), bits(g2))
     rv, rg, gabs = ref.eval(dose)
     union = ref.union()
-    assert np.all(_bits(g)[~union] == NAN_BITS) and 0 < union.sum() < rig.nvox
+    assert np.all(bits(g)[~union] == NAN_BITS) and 0 < union.sum() < rig.nvox
     assert rv[8] == 0.0 and np.all(rv[1:8] > 0)                      # the last term is satisfied, the others cost
     nt = [sizes[t[1]] for t in terms]
     for t, n in enumerate(nt):
@@ -235,7 +226,7 @@ def test_eval_with_mixed_terms_on_overlapping_rois(rig_of, synth):
     vb, gb = _eval(rig, beside, dDose)
     theirs = rig.has | rois[3]
     assert disjoint.sum() > 1000 and not (disjoint & theirs).any()
-    assert np.array_equal(_bits(va[1:5]), _bits(vb[1:5])) and np.array_equal(_bits(ga[theirs]), _bits(gb[theirs]))
+    assert np.array_equal(bits(va[1:5]), bits(vb[1:5])) and np.array_equal(bits(ga[theirs]), bits(gb[theirs]))
     assert vb[5] > 0 and vb[0] == va[0] + vb[5] and np.all(gb[disjoint & (dose <= 0)] > 0)
 
 
@@ -311,7 +302,7 @@ def test_optimizer_iterations_against_the_restatement(rig_of, synth):
     """Iterations 0, 1 and 2 of the resident loop on a target term + MIN_DVH on the target + MAX_DVH on the surrounding rows, the
     restatement fed the device's own dose and gradient: f within the summation bound, alpha within (n + 2) * 2^-52 relative (as
     test_gpu_optimizer.py derives it), the weights bit for bit."""
-    rig = rig_of(_hetero(synth, angles=(30.0,)))
+    rig = rig_of(hetero_scene(synth, 96, (30.0,)))
     obj, ref = _plan(rig)
     f, n = rig.fields[0], rig.sizes[0]
     opt = rig.optimizer_of(obj)
@@ -337,7 +328,7 @@ def test_optimizer_iterations_against_the_restatement(rig_of, synth):
               % (k, hist[k], rep["step"], a_ref, rel, (n + 2) * 2.0 ** -52))
         assert a_ref > 0 and rel <= (n + 2) * 2.0 ** -52
         w_new = rig.weights(opt)[0].reshape(-1)
-        assert np.array_equal(_bits(w_new), _bits(R.update(w, grad, rep["step"]))) and not np.array_equal(w_new, w)
+        assert np.array_equal(bits(w_new), bits(R.update(w, grad, rep["step"]))) and not np.array_equal(w_new, w)
         w_prev, grad_prev = w, grad
 
 
@@ -346,7 +337,7 @@ def test_optimizer_with_dvh_terms_stays_resident_and_converges(rig_of, synth):
     iterations from w = 0 reduce the objective to within a factor 2 of what the restatement with float64 host products of the same
     matrix reaches in thirty (float32 products may send a non-monotone iteration along another path; both ratios are printed)."""
     import torch
-    rig = rig_of(_hetero(synth, angles=(0.0,)))
+    rig = rig_of(hetero_scene(synth, 96, (0.0,)))
     obj, ref = _plan(rig)
     a, b = rig.optimizer_of(obj, start=0.0), rig.optimizer_of(obj, start=0.0)
     a.run(30)
@@ -354,9 +345,9 @@ def test_optimizer_with_dvh_terms_stays_resident_and_converges(rig_of, synth):
     for _ in range(3):
         b.run(10)
     rb, hb = b.result()
-    assert ra == rb and ha.size == 30 and np.array_equal(_bits(ha), _bits(hb))
+    assert ra == rb and ha.size == 30 and np.array_equal(bits(ha), bits(hb))
     for best in (False, True):
-        assert np.array_equal(_bits(rig.weights(a, best)[0]), _bits(rig.weights(b, best)[0]))
+        assert np.array_equal(bits(rig.weights(a, best)[0]), bits(rig.weights(b, best)[0]))
     direct, captured = rig.optimizer_of(obj, start=0.0), rig.optimizer_of(obj, start=0.0)
     s = torch.cuda.Stream()
     torch.cuda.synchronize()
@@ -373,8 +364,8 @@ def test_optimizer_with_dvh_terms_stays_resident_and_converges(rig_of, synth):
     rd, hd = direct.result()
     rg, hg = captured.result()
     rig.eng.set_stream(None)
-    assert rd == rg and hd.size == 5 and np.array_equal(_bits(hd), _bits(hg)) and np.array_equal(_bits(hd), _bits(ha[:5]))
-    assert np.array_equal(_bits(rig.weights(direct)[0]), _bits(rig.weights(captured)[0]))
+    assert rd == rg and hd.size == 5 and np.array_equal(bits(hd), bits(hg)) and np.array_equal(bits(hd), bits(ha[:5]))
+    assert np.array_equal(bits(rig.weights(direct)[0]), bits(rig.weights(captured)[0]))
     host = R.ReferenceOptimizer(ref, rig.matvec, rig.rmatvec, np.zeros(rig.sizes[0])).run(30)
     dev_ratio, host_ratio = ra["f_best"] / ha[0], host.f_best / host.history[0]
     print("device: f_0 %.6g, f_best %.6g at iteration %d, ratio %.4g; restated with float64 products: f_0 %.6g, f_best %.6g at iteration %d, ratio %.4g"

@@ -7,6 +7,7 @@ everything the fill writes and in everything computed from it: no tolerance anyw
 import numpy as np
 import pytest
 
+from gpu_support import FieldRig, options
 from raytracedicom_amd import abi, luts, scenarios
 
 pytestmark = pytest.mark.gpu
@@ -16,12 +17,6 @@ SEGS_PER_WAVE = 64 // SEG
 SEGS_PER_TILE = 256 // SEG
 
 _FETCHED = ("idd", "rsigma", "first_passive", "tile_radius", "active", "bev", "eff_radius", "layer_plan", "ray_weights")
-
-
-def _opts(nuclear=0):
-    o = abi.default_options()
-    o.nuclear_corr = nuclear
-    return o
 
 
 def _thinned(scn, share, seed=5):
@@ -52,46 +47,30 @@ def _scene(synth, k):
     raise ValueError(k)
 
 
-def _compute(eng, scn, monkeypatch, **env):
-    """One field of the scenario's beam, created with the given RTD_* switches in the environment (they are read at creation),
-    computed into a zeroed volume: everything the comparison looks at."""
-    for k, v in env.items():
-        monkeypatch.setenv(k, v)
-    try:
-        f = eng.create_field(scn.beams[0], scn.dims)
-    finally:
-        for k in env:
-            monkeypatch.delenv(k)
-    nb = int(scn.ct.size) * 4
-    d = eng.device_alloc(nb)
-    try:
-        eng.device_zero(d, nb)
-        f.compute(d)
-        _, info = f.finish()
-        out = {"info": info, "dose": np.empty(scn.ct.shape, dtype=np.float32)}
-        eng.to_host(out["dose"], d)
-        for nm in _FETCHED:
-            out[nm] = f.fetch(nm).copy()
-        # idd and rsigma: the steps the fill walks, [entry step, the layer's last step) — it writes nothing outside them
-        W, H, L = info["ray_dims"]
-        plan = out["layer_plan"].reshape(L, 8)
-        for nm in ("idd", "rsigma"):
-            v = out[nm].reshape(L, scn.beams[0].tracerSteps, H, W)
-            out[nm] = np.concatenate([v[l, info["beam_first_inside"]:int(plan[l, 5])].ravel() for l in range(L)])
-    finally:
-        eng.sync()
-        f.destroy()
-        eng.device_free(d)
+def _compute(rig, beam, **env):
+    """One field of the beam, created with the given RTD_* switches in the environment, computed into a zeroed volume: everything
+    the comparison looks at."""
+    f = rig.field(beam, **env)
+    dose, info, _ = rig.compute(f)
+    out = {"info": info, "dose": dose}
+    for nm in _FETCHED:
+        out[nm] = f.fetch(nm).copy()
+    # idd and rsigma: the steps the fill walks, [entry step, the layer's last step) — it writes nothing outside them
+    W, H, L = info["ray_dims"]
+    plan = out["layer_plan"].reshape(L, 8)
+    for nm in ("idd", "rsigma"):
+        v = out[nm].reshape(L, beam.tracerSteps, H, W)
+        out[nm] = np.concatenate([v[l, info["beam_first_inside"]:int(plan[l, 5])].ravel() for l in range(L)])
     return out
 
 
-def _both_layouts(engine, scn, monkeypatch, opt):
-    with engine.Engine(0) as eng:
-        eng.set_options(opt)
-        eng.set_luts(scn.luts)
-        eng.set_ct(scn.ct)
-        new = _compute(eng, scn, monkeypatch)
-        old = _compute(eng, scn, monkeypatch, RTD_NO_FILL_COMPACT="1")
+def _both_layouts(engine, scn, opt):
+    rig = FieldRig(engine, scn, opt)
+    try:
+        new = _compute(rig, scn.beams[0])
+        old = _compute(rig, scn.beams[0], RTD_NO_FILL_COMPACT="1")
+    finally:
+        rig.close()
     assert new["info"] == old["info"]
     for nm in ("dose",) + _FETCHED:
         np.testing.assert_array_equal(new[nm], old[nm], err_msg=nm)
@@ -106,30 +85,30 @@ def _live_segments(out, cutoff=1.0):
 
 
 @pytest.mark.parametrize("k", [1, 2, 3, 4, 5])
-def test_heterogeneous_scenes(engine, synth, monkeypatch, k):
+def test_heterogeneous_scenes(engine, synth, k):
     """Partly live tiles of every kind (test_scenes_cover_the_tile_states says which), oblique gantry, anisotropic ray spacing."""
-    out = _both_layouts(engine, _scene(synth, k), monkeypatch, _opts())
+    out = _both_layouts(engine, _scene(synth, k), options(1.0))
     assert out["dose"].max() > 0 and out["info"]["uniform_sigma"] == 0
     if k == 5:
         assert out["info"]["max_radius"] > 16                         # the second sweep launch runs behind this fill
 
 
-def test_water_cube(engine, synth, monkeypatch):
+def test_water_cube(engine, synth):
     """The uniform-sigma tracking of the sigma walk (sigMin / sigMax, nonUniform) and the separable superposition behind it."""
-    out = _both_layouts(engine, _scene(synth, 6), monkeypatch, _opts())
+    out = _both_layouts(engine, _scene(synth, 6), options(1.0))
     assert out["dose"].max() > 0 and out["info"]["uniform_sigma"] == 1
 
 
-def test_nuclear_corr(engine, monkeypatch):
+def test_nuclear_corr(engine):
     """k_fill<*, true>: the halo's planes reach the comparison through the dose volume."""
     scn = scenarios.water_cube(luts.synth_luts(nuclear=True), n=64, n_layers=3, spots=7, pitch=6.0)
-    out = _both_layouts(engine, scn, monkeypatch, _opts(abi.RTD_NUC_SOUKUP))
+    out = _both_layouts(engine, scn, options(1.0, nuclear=abi.RTD_NUC_SOUKUP))
     assert out["dose"].max() > 0
 
 
-def test_all_rays_below_the_cutoff(engine, synth, monkeypatch):
+def test_all_rays_below_the_cutoff(engine, synth):
     """Every wave is dead from the start: the fill only stores, and the result is zeros."""
-    out = _both_layouts(engine, _scene(synth, 8), monkeypatch, _opts())
+    out = _both_layouts(engine, _scene(synth, 8), options(1.0))
     assert _live_segments(out).max() == 0
     assert out["dose"].max() == 0 and (out["idd"] == 0).all() and np.isinf(out["rsigma"]).all()
 
@@ -140,7 +119,7 @@ def test_scenes_cover_the_tile_states(engine, synth):
     comparisons above pass over nothing."""
     counts = []
     with engine.Engine(0) as eng:
-        eng.set_options(_opts())
+        eng.set_options(options(1.0))
         eng.set_luts(synth)
         for k in (1, 2, 3, 4, 5):
             scn = _scene(synth, k)

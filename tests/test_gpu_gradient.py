@@ -3,152 +3,25 @@
 Dot products are taken in float64 on the host; every tolerance is relative to sum |a| |b| of the pair compared. Unless stated
 otherwise the ray-weight cut-off is 0, so the live set does not depend on the weights (the gradient is then exact for every
 delta >= 0)."""
-import math
 
 import numpy as np
 import pytest
 
+from gpu_support import FieldRig, close, dot, end_to_end, hetero_scene, options, radii_above_16, rig_fixture, stage_identities
 from raytracedicom_amd import abi, scenarios
 
 pytestmark = pytest.mark.gpu
 
-
-def _dot(a, b):
-    a = np.asarray(a).reshape(-1)
-    b = np.asarray(b).reshape(-1)
-    s = m = 0.0
-    for i in range(0, a.size, 1 << 24):
-        x, y = a[i:i + (1 << 24)].astype(np.float64), b[i:i + (1 << 24)].astype(np.float64)
-        s += float(np.dot(x, y))
-        m += float(np.dot(np.abs(x), np.abs(y)))
-    return s, m
-
-
-def _close(p, q, tol):
-    (a, ma), (b, mb) = p, q
-    scale = max(ma, mb)
-    assert scale > 0
-    assert abs(a - b) <= tol * scale, "%.9g vs %.9g (diff %.3g of scale %.3g)" % (a, b, abs(a - b), scale)
-
-
-def _opts(cutoff=0.0):
-    o = abi.default_options()
-    o.ray_weight_cutoff = cutoff
-    return o
-
-
-def _with_weights(b, w):
-    return scenarios.BeamSettings(np.ascontiguousarray(w, dtype=np.float32), b.beamEnergies, b.spotSigmas, b.raySpacing, b.tracerSteps,
-                                  b.sourceDist, b.spotIdxToGantry, b.gantryToImIdx, b.gantryToDoseIdx)
-
-
-class Rig:
-    """One engine with the scenario's CT and LUTs, a device dose volume and a device voxel-weight volume. dose_shape ([Z][Y][X]):
-    the dose grid of the beams' gantryToDoseIdx when it is not the CT's."""
-
-    def __init__(self, engine, scn, opt, dose_shape=None):
-        self.engine = engine
-        self.eng = engine.Engine(0)
-        self.eng.set_options(opt)
-        self.eng.set_luts(scn.luts)
-        self.eng.set_ct(scn.ct)
-        self.shape = scn.ct.shape if dose_shape is None else tuple(dose_shape)
-        self.dims = (self.shape[2], self.shape[1], self.shape[0])
-        self.nb = int(np.prod(self.shape)) * 4
-        self.dDose = self.eng.device_alloc(self.nb)
-        self.dG = self.eng.device_alloc(self.nb)
-        self.dOut = None
-        self.fields = []
-
-    def forward(self, beam):
-        """(field, dose) of one beam into a zeroed volume."""
-        f = self.eng.create_field(beam, self.dims)
-        self.fields.append(f)
-        self.eng.device_zero(self.dDose, self.nb)
-        f.compute(self.dDose)
-        _, info = f.finish()
-        dose = np.empty(self.shape, dtype=np.float32)
-        self.eng.to_host(dose, self.dDose)
-        return f, dose, info
-
-    def dose(self, beam):
-        f, d, _ = self.forward(beam)
-        self.fields.remove(f)
-        f.destroy()
-        return d
-
-    def grad(self, f, beam, g):
-        self.eng.to_device(self.dG, np.ascontiguousarray(g, dtype=np.float32))
-        shape = np.asarray(beam.spotWeights).shape
-        n = int(np.prod(shape)) * 4
-        dOut = self.eng.device_alloc(n)
-        try:
-            f.spot_gradient(self.dG, dOut)
-            out = np.empty(shape, dtype=np.float32)
-            self.eng.to_host(out, dOut)
-        finally:
-            self.eng.device_free(dOut)
-        return out
-
-    def close(self):
-        for f in self.fields:
-            f.destroy()
-        self.eng.device_free(self.dDose)
-        self.eng.device_free(self.dG)
-        self.eng.close()
-
-
-@pytest.fixture
-def rig_of(engine):
-    rigs = []
-
-    def make(scn, opt, dose_shape=None):
-        r = Rig(engine, scn, opt, dose_shape)
-        rigs.append(r)
-        return r
-    yield make
-    for r in rigs:
-        r.close()
-
-
-def _hetero(synth, n=96, angle=30.0, source_dist=(math.inf, math.inf), spots=5, pitch=8.0, layers=3, seed=5, **kw):
-    ct, _ = scenarios.hetero_phantom(n)
-    return scenarios.hetero_ct(synth, n=n, spots=spots, pitch=pitch, n_layers=layers, angles=[angle], ct=ct, source_dist=source_dist,
-                               seed=seed, **kw)
-
-
-def _stage_identities(rig, beam, g, tol):
-    f, dose, info = rig.forward(beam)
-    assert dose.max() > 0
-    grad = rig.grad(f, beam, g)
-    bev, gbev = f.fetch("bev"), f.fetch("grad_bev")
-    rw, grw = f.fetch("ray_weights"), f.fetch("grad_ray_weights")
-    _close(_dot(g, dose), _dot(gbev, bev), tol)
-    _close(_dot(gbev, bev), _dot(grw, rw), tol)
-    _close(_dot(grw, rw), _dot(grad, beam.spotWeights), tol)
-    return f, dose, grad, info
+rig_of = rig_fixture(FieldRig)
 
 
 def test_stage_transposes_from_one_forward_run(rig_of, synth):
     """<g, D> = <grad_bev, bev> = <grad_ray_weights, ray_weights> = <grad, w>: heterogeneous CT, rotated divergent beam."""
-    scn = _hetero(synth, angle=30.0, source_dist=(2000.0, 2300.0))
+    scn = hetero_scene(synth, 96, [30.0], source_dist=(2000.0, 2300.0))
     rng = np.random.default_rng(1)
-    b = _with_weights(scn.beams[0], 20.0 + 80.0 * rng.random(scn.beams[0].spotWeights.shape))
+    b = scn.beams[0].replace(spotWeights=20.0 + 80.0 * rng.random(scn.beams[0].spotWeights.shape))
     g = rng.random(scn.ct.shape).astype(np.float32)
-    _stage_identities(rig_of(scn, _opts(0.0)), b, g, 1e-5)
-
-
-def _end_to_end(rig, beam, g, seed, tol=1e-5):
-    rng = np.random.default_rng(seed)
-    w = beam.spotWeights
-    delta = (0.5 * w * rng.random(w.shape)).astype(np.float32)
-    f, d0, info = rig.forward(beam)
-    grad = rig.grad(f, beam, g)
-    d1 = rig.dose(_with_weights(beam, w + delta))
-    dd = (d1.astype(np.float64) - d0.astype(np.float64))
-    assert np.abs(dd).max() > 0
-    _close(_dot(dd, g), _dot(delta, grad), tol)
-    return info
+    stage_identities(rig_of(scn, options(0.0)), b, g, 1e-5)
 
 
 CASES = ["row_sweep", "radii_above_16", "water_uniform", "beam_along_x", "finite_source", "infinite_source"]
@@ -158,27 +31,24 @@ CASES = ["row_sweep", "radii_above_16", "water_uniform", "beam_along_x", "finite
 def test_end_to_end_dot_product(rig_of, synth, case):
     """<D(w + delta) - D(w), g> = <delta, grad(w)> for random delta >= 0 and signed g, on every superposition / transfer path."""
     if case == "row_sweep":
-        scn = _hetero(synth, angle=0.0)
+        scn = hetero_scene(synth, 96, [0.0])
     elif case == "radii_above_16":
-        ct, _ = scenarios.hetero_phantom(96)
-        beam = scenarios.make_field(synth, 96, 256.0 / 96, (-128.0, -128.0, -106.0), 0.0, 4, 6.0, 3, 21, steps=200, ray_spacing=(0.5, 0.5),
-                                    weight_lo=400.0)
-        scn = scenarios.Scenario("rays 0.5 mm", synth, ct, (256.0 / 96,) * 3, [beam])
+        scn = radii_above_16(synth)
     elif case == "water_uniform":
         scn = scenarios.water_cube(synth, n=96, n_layers=3, spots=6, pitch=5.0)
     elif case == "beam_along_x":
-        scn = _hetero(synth, angle=90.0)
+        scn = hetero_scene(synth, 96, [90.0])
         # the host routes a transfer to k_transfer_t when the BEV x index moves more than 0.8x as fast along dose y or z as along x
         # (rtd_engine.hip, kTransferAxisRatio): here it does not move along dose x at all
         m = np.linalg.inv(np.asarray(scn.beams[0].gantryToDoseIdx.m, dtype=np.float64))[0]   # gantry x per dose-index step
         assert max(abs(m[1]), abs(m[2])) > 100.0 * abs(m[0])
     elif case == "finite_source":
-        scn = _hetero(synth, angle=20.0, source_dist=(1800.0, 2100.0))
+        scn = hetero_scene(synth, 96, [20.0], source_dist=(1800.0, 2100.0))
     else:
-        scn = _hetero(synth, angle=20.0)
+        scn = hetero_scene(synth, 96, [20.0])
     g = (np.random.default_rng(3).random(scn.ct.shape) - 0.3).astype(np.float32)
-    rig = rig_of(scn, _opts(0.0))
-    info = _end_to_end(rig, scn.beams[0], g, seed=4)
+    rig = rig_of(scn, options(0.0))
+    info = end_to_end(rig, scn.beams[0], g, seed=4)
     if case == "radii_above_16":
         assert info["max_radius"] > 16
     if case == "water_uniform":
@@ -194,25 +64,26 @@ def test_zero_weight_spots(rig_of, synth):
     layers and steps — stay well away from the edge row: the test first checks that a good part of those spots' dose lies outside
     the dose box of D(w), i.e. that an adjoint culled with any of those extents would fail here. An interior spot of weight 0 sits
     among its neighbours."""
-    scn = _hetero(synth, angle=15.0, spots=(6, 9), pitch=7.0, layers=2)
+    scn = hetero_scene(synth, 96, [15.0], spots=(6, 9), pitch=7.0, layers=2)
     b = scn.beams[0]
     w = b.spotWeights.copy()
     w[:, :5, :] = 0.0                                                # rows 0 .. 4, in every layer
     w[1, 6, 3] = 0.0                                                 # an interior spot
-    b = _with_weights(b, w)
+    b = b.replace(spotWeights=w)
     g = (0.1 + np.random.default_rng(8).random(scn.ct.shape)).astype(np.float32)
-    rig = rig_of(scn, _opts(0.0))
-    f, d0, info = rig.forward(b)
+    rig = rig_of(scn, options(0.0))
+    f = rig.field(b)
+    d0, info, _ = rig.compute(f)
     lo, hi = info["dose_box_min"], info["dose_box_max"]               # [x, y, z]; arrays are [z][y][x]
     inside = np.zeros(scn.ct.shape, dtype=bool)
     inside[lo[2]:hi[2] + 1, lo[1]:hi[1] + 1, lo[0]:hi[0] + 1] = True
-    grad = rig.grad(f, b, g)
+    grad = rig.grad(f, g)
     h = 50.0
     for idx, edge in [((1, 0, 2), True), ((0, 0, 4), True), ((1, 1, 0), True), ((1, 6, 3), False)]:
         w1 = w.copy()
         w1[idx] += h
-        dd = rig.dose(_with_weights(b, w1)).astype(np.float64) - d0.astype(np.float64)
-        fd, scale = _dot(dd, g)
+        dd = rig.dose(b.replace(spotWeights=w1)).astype(np.float64) - d0.astype(np.float64)
+        fd, scale = dot(dd, g)
         if edge:                                                     # the guard is not hollow: the box of D(w) misses much of this spot's dose
             outside = float(np.dot(np.abs(dd[~inside]), g[~inside].astype(np.float64)))
             assert outside > 0.05 * scale, (idx, outside, scale)
@@ -223,27 +94,28 @@ def test_zero_weight_spots(rig_of, synth):
 def test_independent_of_the_gpu_forward(rig_of, synth, orc):
     """The identity of the end-to-end test with D from the CPU oracle (C1 size: water 128^3, one layer)."""
     scn = scenarios.water_cube(synth, n=128, n_layers=1)
-    opt = _opts(0.0)
+    opt = options(0.0)
     b = scn.beams[0]
     rng = np.random.default_rng(12)
     delta = (0.5 * b.spotWeights * rng.random(b.spotWeights.shape)).astype(np.float32)
     g = (rng.random(scn.ct.shape) - 0.4).astype(np.float32)
     rig = rig_of(scn, opt)
-    f, _, _ = rig.forward(b)
-    grad = rig.grad(f, b, g)
+    f = rig.field(b)
+    rig.compute(f)
+    grad = rig.grad(f, g)
     d0 = orc.compute(scn, options=opt)
-    scn1 = scenarios.Scenario("c1 + delta", scn.luts, scn.ct, scn.spacing, [_with_weights(b, b.spotWeights + delta)])
+    scn1 = scenarios.Scenario("c1 + delta", scn.luts, scn.ct, scn.spacing, [b.replace(spotWeights=b.spotWeights + delta)])
     d1 = orc.compute(scn1, options=opt)
-    _close(_dot(d1.astype(np.float64) - d0.astype(np.float64), g), _dot(delta, grad), 1e-4)
+    close(dot(d1.astype(np.float64) - d0.astype(np.float64), g), dot(delta, grad), 1e-4)
 
 
 def test_default_cutoff_keeps_the_stage_identities(rig_of, synth):
     """With ray_weight_cutoff = 1 some rays are dead (their weights are below it): the identities still hold."""
-    scn = _hetero(synth, angle=30.0, source_dist=(2000.0, 2300.0))
+    scn = hetero_scene(synth, 96, [30.0], source_dist=(2000.0, 2300.0))
     rng = np.random.default_rng(2)
-    b = _with_weights(scn.beams[0], 20.0 + 80.0 * rng.random(scn.beams[0].spotWeights.shape))
+    b = scn.beams[0].replace(spotWeights=20.0 + 80.0 * rng.random(scn.beams[0].spotWeights.shape))
     g = rng.random(scn.ct.shape).astype(np.float32)
-    f, _, _, _ = _stage_identities(rig_of(scn, _opts(1.0)), b, g, 1e-5)
+    f, _, _, _ = stage_identities(rig_of(scn, options(1.0)), b, g, 1e-5)
     rw = f.fetch("ray_weights")
     assert (rw < 1.0).any() and (rw >= 1.0).any()
 
@@ -251,17 +123,18 @@ def test_default_cutoff_keeps_the_stage_identities(rig_of, synth):
 def test_reproducible_and_without_side_effects(rig_of, synth):
     """Two gradient calls give identical bits; the field's BEV dose and what it transfers afterwards are unchanged; calls with
     different g are independent."""
-    scn = _hetero(synth, angle=30.0)
+    scn = hetero_scene(synth, 96, [30.0])
     b = scn.beams[0]
     rng = np.random.default_rng(6)
     g1 = rng.random(scn.ct.shape).astype(np.float32)
     g2 = (rng.random(scn.ct.shape) - 0.5).astype(np.float32)
-    rig = rig_of(scn, _opts(0.0))
-    f, dose, _ = rig.forward(b)
+    rig = rig_of(scn, options(0.0))
+    f = rig.field(b)
+    dose, _, _ = rig.compute(f)
     bev0 = f.fetch("bev").copy()
-    a = rig.grad(f, b, g1)
-    c = rig.grad(f, b, g2)
-    a2 = rig.grad(f, b, g1)
+    a = rig.grad(f, g1)
+    c = rig.grad(f, g2)
+    a2 = rig.grad(f, g1)
     assert np.abs(a).max() > 0
     assert np.array_equal(a.view(np.uint32), a2.view(np.uint32))
     assert not np.array_equal(a, c)
@@ -279,11 +152,12 @@ def test_host_form_equals_the_field_calls(rig_of, synth):
     ct, _ = scenarios.hetero_phantom(96)
     scn = scenarios.hetero_ct(synth, n=96, spots=5, pitch=8.0, n_layers=2, angles=[0.0, 70.0], ct=ct)
     g = np.random.default_rng(9).random(scn.ct.shape).astype(np.float32)
-    rig = rig_of(scn, _opts(0.0))
+    rig = rig_of(scn, options(0.0))
     per = []
     for b in scn.beams:
-        f, _, _ = rig.forward(b)
-        per.append(rig.grad(f, b, g))
+        f = rig.field(b)
+        rig.compute(f)
+        per.append(rig.grad(f, g))
     host = rig.eng.spot_gradient(scn.beams, g)
     assert len(host) == 2
     for p, q in zip(per, host):
@@ -294,11 +168,11 @@ def test_host_form_equals_the_field_calls(rig_of, synth):
 def test_errors(engine, synth):
     """NOT_READY before a compute; INVALID_ARG for null pointers, remote fields and nuclear_corr; a radius overflow of the forward
     is reported."""
-    scn = _hetero(synth, n=64, angle=0.0, spots=3, layers=1)
+    scn = hetero_scene(synth, 64, [0.0], spots=3, layers=1)
     b = scn.beams[0]
     eng = engine.Engine(0)
     try:
-        eng.set_options(_opts(0.0))
+        eng.set_options(options(0.0))
         eng.set_luts(synth)
         eng.set_ct(scn.ct)
         dims = (64, 64, 64)
@@ -345,7 +219,7 @@ def test_errors(engine, synth):
     scn = scenarios.water_cube(nl, n=64, n_layers=1, spots=5, pitch=6.0)
     eng = engine.Engine(0)
     try:
-        opt = _opts(0.0)
+        opt = options(0.0)
         opt.nuclear_corr = abi.RTD_NUC_SOUKUP
         eng.set_options(opt)
         eng.set_luts(nl)
@@ -369,28 +243,29 @@ def test_errors(engine, synth):
 def test_projected_gradient_descent(rig_of, synth):
     """Optimiser smoke test: 96^3 heterogeneous field, target D* = D(w_true), start from uniform weights; ten steps of projected
     gradient descent on f(w) = 1/2 |D(w) - D*|^2 with exact line search. f decreases at every step and ends at most half its start."""
-    scn = _hetero(synth, angle=0.0, spots=5, pitch=8.0, layers=3)
+    scn = hetero_scene(synth, 96, [0.0], spots=5, pitch=8.0, layers=3)
     b = scn.beams[0]
     rng = np.random.default_rng(21)
     w_true = (40.0 + 120.0 * rng.random(b.spotWeights.shape)).astype(np.float32)
-    rig = rig_of(scn, _opts(0.0))
-    target = rig.dose(_with_weights(b, w_true)).astype(np.float64)
+    rig = rig_of(scn, options(0.0))
+    target = rig.dose(b.replace(spotWeights=w_true)).astype(np.float64)
     w = np.full(w_true.shape, float(w_true.mean()), dtype=np.float32)
 
     def objective(wv):
-        f, d, _ = rig.forward(_with_weights(b, wv))
+        f = rig.field(b.replace(spotWeights=wv))
+        d, _, _ = rig.compute(f)
         r = d.astype(np.float64) - target
         return f, d.astype(np.float64), r, 0.5 * float(np.dot(r.reshape(-1), r.reshape(-1)))
 
     f, d, r, fv = objective(w)
     f0 = fv
     for _ in range(10):
-        grad = rig.grad(f, _with_weights(b, w), r.astype(np.float32)).astype(np.float64)
+        grad = rig.grad(f, r.astype(np.float32)).astype(np.float64)
         step = -grad
         step[(w <= 0.0) & (step < 0.0)] = 0.0                        # bound-active spots stay at 0
         # A step (D is linear in w >= 0 with cut-off 0): A p = D(p+) - D(p-)
         pp, pm = np.maximum(step, 0.0), np.maximum(-step, 0.0)
-        ap = rig.dose(_with_weights(b, pp)).astype(np.float64) - rig.dose(_with_weights(b, pm)).astype(np.float64)
+        ap = rig.dose(b.replace(spotWeights=pp)).astype(np.float64) - rig.dose(b.replace(spotWeights=pm)).astype(np.float64)
         t = -float(np.dot(r.reshape(-1), ap.reshape(-1))) / float(np.dot(ap.reshape(-1), ap.reshape(-1)))
         neg = step < 0.0
         if neg.any():
@@ -407,4 +282,4 @@ def test_stage_identities_full_size(rig_of, synth):
     scn = scenarios.hetero_ct(synth, n=512)
     b = scn.beams[0]
     g = np.random.default_rng(31).random(scn.ct.shape, dtype=np.float32)
-    _stage_identities(rig_of(scn, _opts(0.0)), b, g, 1e-5)
+    stage_identities(rig_of(scn, options(0.0)), b, g, 1e-5)

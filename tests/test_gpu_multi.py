@@ -6,6 +6,7 @@ import math
 import numpy as np
 import pytest
 
+from gpu_support import switches
 from raytracedicom_amd import abi, scenarios
 
 pytestmark = pytest.mark.gpu
@@ -331,7 +332,7 @@ def test_released_workspace_is_taken_over(engine, synth):
             eng.device_free(p)
 
 
-def test_released_workspace_is_not_taken_over_by_a_transposed_ray_grid(engine, synth, monkeypatch):
+def test_released_workspace_is_not_taken_over_by_a_transposed_ray_grid(engine, synth):
     """Two beams with the same number of rays, steps, layers and spots but transposed ray grids (64 x 32 against 32 x 64). A released
     workspace goes to a new field only if every buffer has the size the new field needs. The padded BEV cube, (W + 64) x (H + 64) x S,
     and the sweep's buffers have the same sizes here; under RTD_NO_SWEEP the node counters of k_superpose_mfma scale with
@@ -346,30 +347,27 @@ def test_released_workspace_is_not_taken_over_by_a_transposed_ray_grid(engine, s
     scn = scenarios.hetero_ct(synth, n=64, spots=2, pitch=4.0, n_layers=2, angles=[0.0], steps=160, ct=ct)
     n = scn.n_voxels
     for no_sweep in (None, "1"):
-        if no_sweep is None:
-            monkeypatch.delenv("RTD_NO_SWEEP", raising=False)
-        else:
-            monkeypatch.setenv("RTD_NO_SWEEP", no_sweep)
-        want = _sequential(engine, scenarios.Scenario("b", synth, ct, scn.spacing, [b]))
-        with engine.Engine(0) as eng:
-            eng.set_luts(synth)
-            eng.set_ct(ct)
-            d = eng.device_alloc(4 * n)
-            fa = eng.create_field(a, scn.dims)
-            eng.device_zero(d, 4 * n)
-            fa.compute(d)
-            _, ia = fa.finish()
-            fa.release()
-            fb = eng.create_field(b, scn.dims)
-            eng.device_zero(d, 4 * n)
-            fb.compute(d)
-            _, ib = fb.finish()
-            assert ia["ray_dims"][:2] == [64, 32] and ib["ray_dims"][:2] == [32, 64], (ia["ray_dims"], ib["ray_dims"])
-            out = np.empty_like(ct)
-            eng.to_host(out, d)
-            np.testing.assert_array_equal(out, want)
-            fb.release()
-            eng.device_free(d)
+        with switches(RTD_NO_SWEEP=no_sweep):
+            want = _sequential(engine, scenarios.Scenario("b", synth, ct, scn.spacing, [b]))
+            with engine.Engine(0) as eng:
+                eng.set_luts(synth)
+                eng.set_ct(ct)
+                d = eng.device_alloc(4 * n)
+                fa = eng.create_field(a, scn.dims)
+                eng.device_zero(d, 4 * n)
+                fa.compute(d)
+                _, ia = fa.finish()
+                fa.release()
+                fb = eng.create_field(b, scn.dims)
+                eng.device_zero(d, 4 * n)
+                fb.compute(d)
+                _, ib = fb.finish()
+                assert ia["ray_dims"][:2] == [64, 32] and ib["ray_dims"][:2] == [32, 64], (ia["ray_dims"], ib["ray_dims"])
+                out = np.empty_like(ct)
+                eng.to_host(out, d)
+                np.testing.assert_array_equal(out, want)
+                fb.release()
+                eng.device_free(d)
 
 
 def test_uniform_hint_belongs_to_the_inputs_of_the_launch(orc, engine, synth):

@@ -4,59 +4,10 @@ behaves — including its nuclear memory step of 0 (kernel_wrapper.cu:925), whic
 import numpy as np
 import pytest
 
+from gpu_support import compare_nuclear_field, nuc_luts  # noqa: F401  (nuc_luts: a fixture)
 from raytracedicom_amd import abi, luts, scenarios
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def nuc_luts():
-    return luts.synth_luts(nuclear=True)
-
-
-def _run(orc, engine, scn, opt, dose_dims=None, dose_spacing=None):
-    """dose_dims, dose_spacing: the dose grid of the beam's gantryToDoseIdx when it is not the CT's (default)."""
-    dose_dims = tuple(scn.dims if dose_dims is None else dose_dims)
-    dose_spacing = scn.spacing if dose_spacing is None else dose_spacing
-    ref = np.zeros((dose_dims[2], dose_dims[1], dose_dims[0]), dtype=np.float32)
-    of = orc.run_field(scn, scn.beams[0], ref, options=opt, keep_layers=True, dose_dims=dose_dims)
-    assert of.status == 0, of.error
-    dose = np.zeros_like(ref)
-    with engine.Engine(0) as eng:
-        eng.set_options(opt)
-        eng.set_luts(scn.luts)
-        eng.set_ct(scn.ct)
-        n = int(dose.size)
-        d = eng.device_alloc(4 * n)
-        eng.device_zero(d, 4 * n)
-        f = eng.create_field(scn.beams[0], dose_dims)
-        f.compute(d)
-        _, info = f.finish()
-        eng.to_host(dose, d)
-        W, H, L = of.info["ray_dims"]
-        S = scn.beams[0].tracerSteps
-        # the sigma chain with the variant's constants: radius classes stay bit-exact (over the steps the reference classifies)
-        plan = of.get("layer_plan").reshape(L, 8)
-        tr_g = f.fetch("tile_radius").reshape(L, S, H // 8, W // 32)
-        tr_o = of.get("tile_radius").reshape(L, S, H // 8, W // 32)
-        for l in range(L):
-            a0, lfp = of.info["beam_first_inside"], int(plan[l, 6])
-            np.testing.assert_array_equal(tr_g[l, a0:lfp], tr_o[l, a0:lfp])
-        np.testing.assert_array_equal(f.fetch("eff_radius"), of.get("eff_radius"))
-        idd_g, idd_o = f.fetch("idd").reshape(L, S, H, W), of.get("idd").reshape(L, S, H, W)
-        for l in range(L):
-            a0, a1 = of.info["beam_first_inside"], int(plan[l, 5])
-            np.testing.assert_allclose(idd_g[l, a0:a1], idd_o[l, a0:a1], rtol=2e-5, atol=1e-12)
-        f.destroy()
-        eng.device_free(d)
-    mx = float(ref.max())
-    assert mx > 0
-    thr = ref > 1e-3 * mx
-    assert (np.abs(dose - ref)[thr] <= 1e-4 * ref[thr] + 1e-6 * mx).all(), float((np.abs(dose - ref)[thr] / ref[thr]).max())
-    assert np.abs(dose - ref).max() <= 2e-5 * mx
-    rate, n_eval, _ = orc.gamma_pass_rate(ref, dose, dose_spacing)
-    assert rate == 1.0 and n_eval > 0
-    return dose, ref, of.info
 
 
 @pytest.mark.parametrize("variant", [abi.RTD_NUC_SOUKUP, abi.RTD_NUC_FLUKA, abi.RTD_NUC_GAUSS_FIT])
@@ -66,7 +17,7 @@ def test_nuclear_variants_beam_starting_inside_the_patient(orc, engine, nuc_luts
     scn = scenarios.water_cube(nuc_luts, n=64, n_layers=3, spots=7, pitch=6.0)
     opt = abi.default_options()
     opt.nuclear_corr = variant
-    dose, ref, info = _run(orc, engine, scn, opt)
+    dose, ref, info = compare_nuclear_field(orc, engine, scn, opt)
     assert info["beam_first_inside"] == 0
     base = np.zeros_like(scn.ct)
     orc.run_field(scn, scn.beams[0], base, keep_layers=False).close()
@@ -83,7 +34,7 @@ def test_nuclear_beam_entering_from_outside(orc, engine, nuc_luts, variant):
     scn = scenarios.Scenario("hetero96_air_gap", nuc_luts, ct, (256.0 / 96,) * 3, [beam])
     opt = abi.default_options()
     opt.nuclear_corr = variant
-    dose, ref, info = _run(orc, engine, scn, opt)
+    dose, ref, info = compare_nuclear_field(orc, engine, scn, opt)
     assert info["beam_first_inside"] > 0
 
 

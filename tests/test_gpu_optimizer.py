@@ -7,145 +7,20 @@ import numpy as np
 import pytest
 
 import optimizer_reference as R
-from raytracedicom_amd import abi, scenarios
+from gpu_plan_rigs import OptimizerRig
+from gpu_support import bits, hetero_scene, rig_fixture
+from raytracedicom_amd import abi
 
 pytestmark = pytest.mark.gpu
 
-
-def _opts():
-    o = abi.default_options()
-    o.ray_weight_cutoff = 0.0
-    return o
-
-
-def _hetero(synth, n=96, angles=(0.0,), spots=5, pitch=8.0, layers=3, seed=5):
-    ct, _ = scenarios.hetero_phantom(n)
-    return scenarios.hetero_ct(synth, n=n, spots=spots, pitch=pitch, n_layers=layers, angles=list(angles), ct=ct, source_dist=(math.inf, math.inf), seed=seed)
-
-
-class Rig:
-    """One engine, the scenario's fields with their matrices, and the plan objective of the convergence test: the target is where
-    Dij w_true exceeds half its maximum (SQ_DEVIATION to its mean there, weight 1, + SQ_UNDERDOSE at 95 %, weight 5), the other voxels
-    that have rows carry SQ_OVERDOSE at 30 % (weight 1) + MEAN (weight 1e-3 x level)."""
-
-    def __init__(self, engine, scn, pure_overdose=False):
-        self.engine = engine
-        self.eng = engine.Engine(0)
-        self.eng.set_options(_opts())
-        self.eng.set_luts(scn.luts)
-        self.eng.set_ct(scn.ct)
-        self.dims = tuple(scn.dims)
-        self.nvox = int(np.prod(self.dims))
-        self.fields = [self.eng.create_field(b, self.dims) for b in scn.beams]
-        self.mats = [f.dose_influence() for f in self.fields]
-        self.shapes = [b.spotWeights.shape for b in scn.beams]
-        self.sizes = [int(np.prod(s)) for s in self.shapes]
-        self.w_true = [(40.0 + 120.0 * np.random.default_rng(21 + i).random(s)).astype(np.float32) for i, s in enumerate(self.shapes)]
-        dose_true = sum(d.matvec(w) for d, w in zip(self.mats, self.w_true))
-        has = sum(np.bincount(d.indices, minlength=self.nvox) for d in self.mats) > 0
-        target = dose_true > 0.5 * dose_true.max()
-        other = has & ~target
-        self.level = float(dose_true[target].mean())
-        self.obj = self.eng.create_objective(self.dims)
-        self.ref = R.ReferenceObjective(self.nvox)
-        if pure_overdose:
-            terms = [(R.SQ_OVERDOSE, 0, 1.0, 0.3 * self.level)]
-            rois = [has]
-        else:
-            terms = [(R.SQ_DEVIATION, 0, 1.0, self.level), (R.SQ_UNDERDOSE, 0, 5.0, 0.95 * self.level),
-                     (R.SQ_OVERDOSE, 1, 1.0, 0.3 * self.level), (R.MEAN, 1, 1e-3 * self.level, 0.0)]
-            rois = [target, other]
-        for m in rois:
-            self.obj.add_roi(m)
-            self.ref.add_roi(m)
-        for t in terms:
-            self.obj.add_term(*t)
-            self.ref.add_term(*t)
-        self.opts = []
-        self.bufs = []
-
-    def alloc(self, nbytes, zero=True):
-        p = self.eng.device_alloc(nbytes)
-        self.bufs.append(p)
-        if zero:
-            self.eng.device_zero(p, nbytes)
-        return p
-
-    def optimizer(self, start=None, options=None):
-        """start: None (the fields' own weights), or a scalar / per-field list of arrays set through set_weights."""
-        o = self.eng.create_optimizer(self.fields, self.obj, options)
-        self.opts.append(o)
-        if start is not None:
-            self.set_weights(o, start)
-        return o
-
-    def set_weights(self, o, start):
-        for i, s in enumerate(self.shapes):
-            w = np.full(s, start, dtype=np.float32) if np.isscalar(start) else np.ascontiguousarray(start[i], dtype=np.float32)
-            d = self.alloc(w.nbytes, zero=False)
-            self.eng.to_device(d, w)
-            o.set_weights(i, d)
-        self.eng.sync()
-
-    def weights(self, o, best=False):
-        return [o.weights(i, best=best) for i in range(len(self.fields))]
-
-    def volume(self, ptr):
-        out = np.empty(self.nvox, dtype=np.float32)
-        self.eng.to_host(out, ptr)
-        return out
-
-    def dose_of(self, ws, dDose):
-        """Zero, then apply(init = 0) per field in list order, into dDose."""
-        self.eng.device_zero(dDose, 4 * self.nvox)
-        for f, w in zip(self.fields, ws):
-            d = self.alloc(w.nbytes, zero=False)
-            self.eng.to_device(d, np.ascontiguousarray(w, dtype=np.float32))
-            f.dose_influence_apply(d, dDose, init=False)
-        self.eng.sync()
-
-    def matvec(self, w):
-        w = np.asarray(w, dtype=np.float64)
-        offs = np.cumsum([0] + self.sizes)
-        return sum(d.matvec(w[a:b]) for d, a, b in zip(self.mats, offs, offs[1:]))
-
-    def rmatvec(self, g):
-        return np.concatenate([d.rmatvec(g) for d in self.mats])
-
-    def close(self):
-        for o in self.opts:
-            o.destroy()
-        self.obj.destroy()
-        for p in self.bufs:
-            self.eng.device_free(p)
-        for f in self.fields:
-            f.destroy()
-        self.eng.close()
-
-
-@pytest.fixture
-def rig_of(engine):
-    rigs = []
-
-    def make(scn, **kw):
-        r = Rig(engine, scn, **kw)
-        rigs.append(r)
-        return r
-    yield make
-    for r in rigs:
-        r.close()
-
-
-def _bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view(np.uint32 if a.dtype == np.float32 else np.uint64)
+rig_of = rig_fixture(OptimizerRig)
 
 
 def test_one_iteration_against_the_restatement(rig_of, synth):
     """Iterations 0, 1 and 2 (the first rule, then Barzilai-Borwein twice), the restatement fed the device's own dose and gradient:
     f within the summation bound of the objective, alpha within (n + 2) * 2^-52 relative (two float64 dot products of n entries and
     a quotient), the new weights equal to P(w - float32(alpha) * grad) bit for bit at the device's alpha."""
-    rig = rig_of(_hetero(synth, angles=(30.0,)))
+    rig = rig_of(hetero_scene(synth, 96, (30.0,)))
     f, n = rig.fields[0], rig.sizes[0]
     opt = rig.optimizer()
     dG, dGrad = rig.alloc(4 * rig.nvox), rig.alloc(4 * n)
@@ -172,7 +47,7 @@ def test_one_iteration_against_the_restatement(rig_of, synth):
               % (k, hist[k], rep["step"], a_ref, rel, (n + 2) * 2.0 ** -52))
         assert a_ref > 0 and rel <= (n + 2) * 2.0 ** -52
         w_new = rig.weights(opt)[0].reshape(-1)
-        assert np.array_equal(_bits(w_new), _bits(R.update(w, grad, rep["step"])))
+        assert np.array_equal(bits(w_new), bits(R.update(w, grad, rep["step"])))
         assert not np.array_equal(w_new, w)
         w_prev, grad_prev = w, grad
 
@@ -181,7 +56,7 @@ def test_dose_is_the_sum_of_the_fields_every_iteration(rig_of, synth):
     """Two overlapping fields (0 and 90 degrees): after each of three iterations the optimiser's volume equals, bit for bit, a zeroed
     volume followed by apply(init = 0) of the fields in list order at the weights that entered the iteration (what field 1 added
     outside field 0's box an iteration earlier must be gone)."""
-    rig = rig_of(_hetero(synth, angles=(0.0, 90.0)))
+    rig = rig_of(hetero_scene(synth, 96, (0.0, 90.0)))
     n0 = np.bincount(rig.mats[0].indices, minlength=rig.nvox) > 0
     n1 = np.bincount(rig.mats[1].indices, minlength=rig.nvox) > 0
     assert (n0 & n1).any() and (n1 & ~n0).any() and (n0 & ~n1).any()
@@ -194,7 +69,7 @@ def test_dose_is_the_sum_of_the_fields_every_iteration(rig_of, synth):
         got = rig.volume(opt.dose())
         rig.dose_of(ws, dDose)
         want = rig.volume(dDose)
-        assert want.max() > 0 and np.array_equal(_bits(got), _bits(want)), k
+        assert want.max() > 0 and np.array_equal(bits(got), bits(want)), k
         seen.append(got)
     assert not np.array_equal(seen[0], seen[1]) and not np.array_equal(seen[1], seen[2])
 
@@ -203,7 +78,7 @@ def test_convergence_from_zero(rig_of, synth):
     """Thirty iterations from w = 0 on the plan objective: f_best at no more than half of f_0 (the project's bar for thirty steps of
     this loop), the best-iterate bookkeeping exact, the weights feasible, and w_best reproducing f_best bit for bit through apply +
     eval. The restatement with float64 products runs beside it: printed, not bounded (Barzilai-Borwein amplifies last-bit differences)."""
-    rig = rig_of(_hetero(synth, angles=(0.0,)))
+    rig = rig_of(hetero_scene(synth, 96, (0.0,)))
     opt = rig.optimizer(start=0.0)
     opt.run(30)
     rep, hist = opt.result()
@@ -228,7 +103,7 @@ def test_resident_means_resident(engine, rig_of, synth):
     """run(30) = run(10) three times, bit for bit; a second engine gives the same history; run(5) captured into a graph on a caller's
     stream and replayed once gives the bits of the direct call."""
     import torch
-    scn = _hetero(synth, angles=(0.0,))
+    scn = hetero_scene(synth, 96, (0.0,))
     rig = rig_of(scn)
     a, b = rig.optimizer(start=0.0), rig.optimizer(start=0.0)
     a.run(30)
@@ -237,14 +112,14 @@ def test_resident_means_resident(engine, rig_of, synth):
         b.run(10)
         b.run(0)
     rb, hb = b.result()
-    assert ra == rb and np.array_equal(_bits(ha), _bits(hb)) and ha.size == 30
+    assert ra == rb and np.array_equal(bits(ha), bits(hb)) and ha.size == 30
     for best in (False, True):
-        assert np.array_equal(_bits(rig.weights(a, best)[0]), _bits(rig.weights(b, best)[0]))
+        assert np.array_equal(bits(rig.weights(a, best)[0]), bits(rig.weights(b, best)[0]))
     other = rig_of(scn)
     c = other.optimizer(start=0.0)
     c.run(30)
     rc, hc = c.result()
-    assert rc == ra and np.array_equal(_bits(hc), _bits(ha))
+    assert rc == ra and np.array_equal(bits(hc), bits(ha))
     # graph capture: one run(5) = 5 iterations of launches, nothing else
     direct, captured = rig.optimizer(start=0.0), rig.optimizer(start=0.0)
     s = torch.cuda.Stream()
@@ -262,14 +137,14 @@ def test_resident_means_resident(engine, rig_of, synth):
     rd, hd = direct.result()
     rg, hg = captured.result()
     rig.eng.set_stream(None)
-    assert rd == rg and hd.size == 5 and np.array_equal(_bits(hd), _bits(hg)) and np.array_equal(_bits(hd), _bits(ha[:5]))
-    assert np.array_equal(_bits(rig.weights(direct)[0]), _bits(rig.weights(captured)[0]))
+    assert rd == rg and hd.size == 5 and np.array_equal(bits(hd), bits(hg)) and np.array_equal(bits(hd), bits(ha[:5]))
+    assert np.array_equal(bits(rig.weights(direct)[0]), bits(rig.weights(captured)[0]))
 
 
 def test_errors_stationary_start_and_guard(engine, synth):
     L = engine.lib()
-    scn = _hetero(synth, n=64, angles=(0.0,), spots=3, layers=1)
-    rig = Rig(engine, scn)
+    scn = hetero_scene(synth, 64, (0.0,), spots=3, layers=1)
+    rig = OptimizerRig(engine, scn)
     try:
         eng, h = rig.eng, rig.eng._h
         f = rig.fields[0]
@@ -328,7 +203,7 @@ def test_errors_stationary_start_and_guard(engine, synth):
         print("after weights of 1e30: f %.6g then %.6g, guards taken %d" % (h7[5], h7[6], r7["guarded"]))
         assert math.isfinite(h7[6]) and not np.isnan(rig.weights(opt)[0]).any() and r7["f_best"] <= r5["f_best"]
         if r7["best_iteration"] == r5["best_iteration"]:
-            assert np.array_equal(_bits(rig.weights(opt, best=True)[0]), _bits(best5))
+            assert np.array_equal(bits(rig.weights(opt, best=True)[0]), bits(best5))
         # weights of +inf: the dose and f are not finite, the guard of step 7 is taken: w = w_best, and the next f is f_best again
         rig.set_weights(opt, math.inf)
         opt.run(2)
@@ -349,7 +224,7 @@ def test_errors_stationary_start_and_guard(engine, synth):
     finally:
         rig.close()
     # a stationary start: w = 0 under a pure overdose penalty
-    rig = Rig(engine, scn, pure_overdose=True)
+    rig = OptimizerRig(engine, scn, pure_overdose=True)
     try:
         opt = rig.optimizer(start=0.0)
         opt.run(1)
@@ -358,6 +233,6 @@ def test_errors_stationary_start_and_guard(engine, synth):
         opt.run(4)
         r5, h5 = opt.result()
         w = rig.weights(opt)[0]
-        assert np.all(h5 == 0.0) and np.array_equal(_bits(w), _bits(np.zeros_like(w))) and r5["best_iteration"] == 0 and r5["guarded"] == 0
+        assert np.all(h5 == 0.0) and np.array_equal(bits(w), bits(np.zeros_like(w))) and r5["best_iteration"] == 0 and r5["guarded"] == 0
     finally:
         rig.close()

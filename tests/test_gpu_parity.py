@@ -12,106 +12,19 @@ Tolerances (stated per stage):
     same terms in a different (fixed) order than the oracle and uses a Gaussian series for its weight tables;
     gamma(1 %/1 mm) >= 99 % is the north-star bar and is asserted at 100 %.
 
-_run_engine and _compare_field take an optional dose grid (dose_dims, dose_spacing) for beams whose gantryToDoseIdx is not their
-gantryToImIdx (tests/test_gpu_asym_grids.py); the default is the CT's grid, as every test of this file uses it.
+The comparison itself is gpu_support.compare_field, which tests/test_gpu_asym_grids.py uses too.
 """
 import math
 
 import numpy as np
 import pytest
 
+from gpu_support import FieldRig, compare_field, rel_close, rig_fixture
 from raytracedicom_amd import abi, scenarios
 
 pytestmark = pytest.mark.gpu
 
-
-def _run_engine(engine, scn, beam, options=None, dose_dims=None):
-    dose_dims = tuple(scn.dims if dose_dims is None else dose_dims)
-    eng = engine.Engine(0)
-    if options is not None:
-        eng.set_options(options)
-    eng.set_luts(scn.luts)
-    eng.set_ct(scn.ct)
-    n = dose_dims[0] * dose_dims[1] * dose_dims[2]
-    d_dose = eng.device_alloc(4 * n)
-    eng.device_zero(d_dose, 4 * n)
-    fld = eng.create_field(beam, dose_dims)
-    fld.compute(d_dose)
-    timing, info = fld.finish()
-    dose = np.empty((dose_dims[2], dose_dims[1], dose_dims[0]), dtype=np.float32)
-    eng.to_host(dose, d_dose)
-    return eng, fld, dose, timing, info, d_dose
-
-
-def _rel_close(a, b, rtol, floor_frac=1e-3, atol_frac=1e-6):
-    a = a.astype(np.float64); b = b.astype(np.float64)
-    mx = np.abs(b).max()
-    mask = np.abs(b) > floor_frac * mx
-    err = np.abs(a - b)
-    assert (err[mask] <= rtol * np.abs(b[mask]) + atol_frac * mx).all(), \
-        "max rel err %g" % (err[mask] / np.abs(b[mask])).max()
-    assert (err[~mask] <= 2 * rtol * floor_frac * mx + atol_frac * mx).all()
-
-
-def _compare_field(orc, engine, scn, beam, options=None, dose_dims=None, dose_spacing=None):
-    dose_dims = tuple(scn.dims if dose_dims is None else dose_dims)
-    dose_spacing = scn.spacing if dose_spacing is None else dose_spacing
-    dose_ref = np.zeros((dose_dims[2], dose_dims[1], dose_dims[0]), dtype=np.float32)
-    of = orc.run_field(scn, beam, dose_ref, options=options, keep_layers=True, dose_dims=dose_dims)
-    assert of.status == 0
-    eng, fld, dose, timing, info, d_dose = _run_engine(engine, scn, beam, options, dose_dims)
-    try:
-        oi = of.info
-        for k in ("ray_dims", "beam_first_inside", "beam_first_outside", "beam_first_guaranteed_passive",
-                  "beam_first_calculated_passive", "bbox_min", "bbox_max", "live_steps", "max_radius"):
-            assert info[k] == oi[k], (k, info[k], oi[k])
-        np.testing.assert_array_equal(np.array(info["ray_offset"], np.float32), np.array(oi["ray_offset"], np.float32))
-        W, H, L = oi["ray_dims"]
-        S = beam.tracerSteps
-        # stage 1: tracer — bit-exact
-        for name in ("density", "wepl", "first_inside", "first_outside", "wepl_min"):
-            np.testing.assert_array_equal(fld.fetch(name), of.get(name), err_msg=name)
-        # stage 2: plan + spot->ray weights
-        np.testing.assert_allclose(fld.fetch("layer_plan").reshape(L, 8)[:, :6], of.get("layer_plan").reshape(L, 8)[:, :6], rtol=1e-6)
-        np.testing.assert_array_equal(fld.fetch("ray_weights"), of.get("ray_weights"))
-        # stage 3: fill
-        first, calc = oi["beam_first_inside"], oi["beam_first_calculated_passive"]
-        np.testing.assert_array_equal(fld.fetch("first_passive"), of.get("first_passive"))
-        plan = of.get("layer_plan").reshape(L, 8)
-        idd_g, idd_o = fld.fetch("idd").reshape(L, S, H, W), of.get("idd").reshape(L, S, H, W)
-        rs_g, rs_o = fld.fetch("rsigma").reshape(L, S, H, W), of.get("rsigma").reshape(L, S, H, W)
-        tr_g = fld.fetch("tile_radius").reshape(L, S, H // 8, W // 32)
-        tr_o = of.get("tile_radius").reshape(L, S, H // 8, W // 32)
-        for l in range(L):
-            a0, a1 = first, int(plan[l, 5])
-            np.testing.assert_allclose(idd_g[l, a0:a1], idd_o[l, a0:a1], rtol=2e-5, atol=1e-12, err_msg="idd layer %d" % l)
-            fin = np.isfinite(rs_o[l, a0:a1])
-            np.testing.assert_array_equal(np.isfinite(rs_g[l, a0:a1]), fin)
-            np.testing.assert_allclose(rs_g[l, a0:a1][fin], rs_o[l, a0:a1][fin], rtol=2e-5)
-            lfp = int(plan[l, 6])
-            # index work: radius class of every (step, tile) bit-exact (tileRadCalc, kernel_wrapper.cuh:256-313)
-            if not np.array_equal(tr_g[l, a0:lfp], tr_o[l, a0:lfp]):
-                ks, tys, txs = np.nonzero(tr_g[l, a0:lfp] != tr_o[l, a0:lfp])
-                k, ty, tx = int(ks[0]) + a0, int(tys[0]), int(txs[0])
-                mg = rs_g[l, k, 8 * ty:8 * ty + 8, 32 * tx:32 * tx + 32].min()
-                mo = rs_o[l, k, 8 * ty:8 * ty + 8, 32 * tx:32 * tx + 32].min()
-                raise AssertionError("tile_radius differs on %d (step, tile) of layer %d; first at step %d tile (%d, %d): engine %d, oracle %d; "
-                                     "tile minimum of 1/sigma: engine %r (0x%08x), oracle %r (0x%08x)"
-                                     % (ks.size, l, k, tx, ty, tr_g[l, k, ty, tx], tr_o[l, k, ty, tx], float(mg), np.float32(mg).view(np.uint32),
-                                        float(mo), np.float32(mo).view(np.uint32)))
-        # batch radius per radius class (host batching rule, kernel_wrapper.cu:966-976)
-        np.testing.assert_array_equal(fld.fetch("eff_radius").reshape(L, -1), of.get("eff_radius").reshape(L, -1))
-        # stage 4/5: BEV and final dose
-        bev_g, bev_o = fld.fetch("bev"), of.get("bev")
-        _rel_close(bev_g, bev_o, rtol=1e-4)
-        _rel_close(dose, dose_ref, rtol=1e-4)
-        rate, n_eval, gmax = orc.gamma_pass_rate(dose_ref, dose, dose_spacing)
-        assert n_eval > 0 and rate == 1.0, (rate, n_eval, gmax)
-        return dose, dose_ref, timing, info
-    finally:
-        fld.destroy()
-        eng.device_free(d_dose)
-        eng.close()
+rig_of = rig_fixture(FieldRig)
 
 
 @pytest.fixture(scope="module")
@@ -128,7 +41,7 @@ def test_c3_hetero_512_bench_workload(orc, engine, synth, ct512):
     """BASELINE.json configs[2] = the bench.py workload: 512^3 heterogeneous CT, one field, 10x10 spots x 20 layers. Every
     intermediate, the BEV dose, the dose and gamma against the oracle."""
     scn = scenarios.hetero_ct(synth, n=512, angles=[0.0], ct=ct512)
-    dose, ref, timing, info = _compare_field(orc, engine, scn, scn.beams[0])
+    dose, ref, timing, info = compare_field(orc, engine, scn, scn.beams[0])
     assert info["ray_dims"] == [96, 88, 20] and info["live_steps"] > 3000
     assert info["uniform_sigma"] == 0                                # heterogeneous CT: per-voxel-sigma superposition
 
@@ -138,7 +51,7 @@ def test_c4_fields_of_the_four_angle_plan(orc, engine, synth, ct512, deg):
     """BASELINE.json configs[3], field by field at full size: the along-beam tracer (k_trace_sample_t) and the transposed
     transfer (k_transfer_t) run at 90 / 270 degrees."""
     scn = scenarios.hetero_ct(synth, n=512, angles=[0.0, 90.0, 180.0, 270.0], ct=ct512)
-    _compare_field(orc, engine, scn, scn.beams[int(deg // 90)])
+    compare_field(orc, engine, scn, scn.beams[int(deg // 90)])
 
 
 def test_c4_four_field_plan_sum(orc, engine, synth, ct512):
@@ -150,7 +63,7 @@ def test_c4_four_field_plan_sum(orc, engine, synth, ct512):
         eng.set_luts(scn.luts)
         eng.set_ct(scn.ct)
         eng.compute(scn.beams, dose)
-    _rel_close(dose, ref, rtol=1e-4)
+    rel_close(dose, ref, rtol=1e-4)
     rate, n_eval, gmax = orc.gamma_pass_rate(ref, dose, scn.spacing)
     assert rate == 1.0 and n_eval > 1000000, (rate, n_eval, gmax)
 
@@ -159,13 +72,13 @@ def test_c4_four_field_plan_sum(orc, engine, synth, ct512):
 def test_c5_hetero_768_fields(orc, engine, synth, ct768, idx):
     """BASELINE.json configs[4]: 768^3 CT (voxel 1/3 mm), every field of the eight-angle plan (0, 45, ..., 315 degrees)."""
     scn = scenarios.hetero_ct(synth, n=768, n_fields=8, ct=ct768)
-    _compare_field(orc, engine, scn, scn.beams[idx])
+    compare_field(orc, engine, scn, scn.beams[idx])
 
 
 def test_c1_water_cube_128_single_layer(orc, engine, synth):
     """BASELINE.json configs[0]: water cube 128^3, single G000 field, one energy layer."""
     scn = scenarios.water_cube(synth, n=128, n_layers=1)
-    dose, ref, timing, info = _compare_field(orc, engine, scn, scn.beams[0])
+    dose, ref, timing, info = compare_field(orc, engine, scn, scn.beams[0])
     assert dose.max() > 0 and timing["total_ms"] > 0
 
 
@@ -174,7 +87,7 @@ def test_water_cube_multi_layer_fine_timing(orc, engine, synth):
     scn = scenarios.water_cube(synth, n=128, n_layers=4, spots=17, pitch=4.0)
     opt = abi.default_options()
     opt.fine_grained_timing = 1
-    dose, ref, timing, info = _compare_field(orc, engine, scn, scn.beams[0], options=opt)
+    dose, ref, timing, info = compare_field(orc, engine, scn, scn.beams[0], options=opt)
     parts = sum(timing[k] for k in ("raytracing_ms", "prepare_energy_loop_ms", "fill_idd_sigma_ms", "prepare_superp_ms",
                                     "superp_ms", "transforming_ms"))
     assert parts == pytest.approx(timing["total_ms"], rel=0.05)
@@ -186,7 +99,7 @@ def test_heterogeneous_rotated_divergent(orc, engine, synth, deg, dist):
     """Heterogeneous phantom (air gap, lung, bone, cavity), rotated gantry, finite source distance."""
     ct, _ = scenarios.hetero_phantom(128)
     scn = scenarios.hetero_ct(synth, n=128, spots=6, pitch=7.0, n_layers=3, angles=[deg], source_dist=dist, ct=ct)
-    _compare_field(orc, engine, scn, scn.beams[0])
+    compare_field(orc, engine, scn, scn.beams[0])
 
 
 @pytest.mark.parametrize("rot,steps", [(((0, 0, 1), (1, 0, 0), (0, 1, 0)), 300), (((0, 0, -1), (0.8, -0.6, 0), (-0.6, -0.8, 0)), 300),
@@ -198,7 +111,7 @@ def test_beam_axes_other_than_rotation_about_y(orc, engine, synth, rot, steps):
     ct, _ = scenarios.hetero_phantom(96)
     scn = scenarios.hetero_ct(synth, n=96, spots=5, pitch=7.0, n_layers=3, angles=[0.0], source_dist=(1500.0, 2100.0), steps=steps, ct=ct,
                               gantry_rot=rot)
-    _compare_field(orc, engine, scn, scn.beams[0])
+    compare_field(orc, engine, scn, scn.beams[0])
 
 
 @pytest.mark.parametrize("dist", [(math.inf, math.inf), (1400.0, 1900.0)])
@@ -215,7 +128,7 @@ def test_beam_along_dose_y_fine_voxels(orc, engine, synth, dist):
     # 284 lies 0.7 steps in front of the entry slice: the launch's over-run rows receive ~12 % of the maximum dose
     beam = scenarios.make_field(synth, n, voxel, (-128.0, -128.0, -106.0), 0.0, 5, 7.0, 3, 11, dist, 300, start_z=60.633, gantry_rot=rot)
     scn = scenarios.Scenario("beam along -y", synth, ct, (voxel,) * 3, [beam])
-    dose, ref, timing, info = _compare_field(orc, engine, scn, scn.beams[0])
+    dose, ref, timing, info = compare_field(orc, engine, scn, scn.beams[0])
     ymax = info["bbox_max"][1]
     cov = min(info["bbox_min"][1] + ((ymax - info["bbox_min"][1] + 1 + 7) // 8) * 8 - 1, scn.dims[1] - 1)
     assert cov > ymax                                                 # the launch does run past maxIdx.y in this geometry
@@ -229,7 +142,7 @@ def test_spot_map_taller_than_the_lds_tile(orc, engine, synth):
     the intermediate buffer instead of the fused k_conv (gpu_convolution_2d.cu:16-59 is two launches as well); ray weights bit-exact."""
     ct, _ = scenarios.hetero_phantom(64)
     scn = scenarios.hetero_ct(synth, n=64, spots=(3, 400), pitch=0.6, n_layers=2, angles=[0.0], steps=120, ct=ct)
-    _, _, _, info = _compare_field(orc, engine, scn, scn.beams[0])
+    _, _, _, info = compare_field(orc, engine, scn, scn.beams[0])
     assert info["ray_dims"][1] >= 240
 
 
@@ -238,7 +151,7 @@ def test_c3_through_the_output_stationary_kernel(orc, engine, synth, ct512, monk
     as a second implementation of the superposition that the sweep is compared with — keeps its full-size parity evidence."""
     monkeypatch.setenv("RTD_NO_SWEEP", "1")
     scn = scenarios.hetero_ct(synth, n=512, angles=[0.0], ct=ct512)
-    _compare_field(orc, engine, scn, scn.beams[0])
+    compare_field(orc, engine, scn, scn.beams[0])
 
 
 @pytest.mark.parametrize("spacing,want_big", [((0.5, 0.5), True), ((1.0, 1.0), False)])
@@ -252,7 +165,7 @@ def test_large_radii_go_through_the_second_sweep_launch(orc, engine, synth, spac
     scn = scenarios.hetero_ct(synth, n=96, spots=4, pitch=6.0, n_layers=3, angles=[0.0], steps=200, ct=ct)
     beam = scenarios.make_field(synth, 96, 256.0 / 96, (-128.0, -128.0, -106.0), 0.0, 4, 6.0, 3, 21, steps=200, ray_spacing=spacing, weight_lo=400.0)
     scn = scenarios.Scenario("rays %g mm" % spacing[0], synth, ct, scn.spacing, [beam])
-    dose, ref, timing, info = _compare_field(orc, engine, scn, beam)
+    dose, ref, timing, info = compare_field(orc, engine, scn, beam)
     assert (info["max_radius"] > 16) == want_big, info["max_radius"]
     if want_big:
         assert info["max_radius"] == 32
@@ -274,7 +187,7 @@ def test_large_radii_go_through_the_second_sweep_launch(orc, engine, synth, spac
 
 
 @pytest.mark.parametrize("case", ["radii <= 16", "radii up to 32"])
-def test_the_two_general_superposition_kernels_agree(orc, engine, synth, monkeypatch, case):
+def test_the_two_general_superposition_kernels_agree(orc, rig_of, synth, case):
     """The row sweep (k_superpose_sweep + k_superpose_sweep_big: source rows swept, T[|dy|][x] on the matrix cores) and k_superpose_mfma
     (output tiles visited) on the same heterogeneous field — 17 layers with radii within the first launch's reach, and 0.5 mm rays
     with radii up to 32, where the second launch adds the tiles of radius 17 .. 32: BEV doses within 1e-5 of each other relative to
@@ -293,25 +206,19 @@ def test_the_two_general_superposition_kernels_agree(orc, engine, synth, monkeyp
     obev = of.get("bev").reshape(-1, H + 64, W + 64)
     res = {}
     for name, env in (("sweep", None), ("mfma", "1")):
-        if env is None:
-            monkeypatch.delenv("RTD_NO_SWEEP", raising=False)
-        else:
-            monkeypatch.setenv("RTD_NO_SWEEP", env)
-        eng, fld, dose, timing, info, d_dose = _run_engine(engine, scn, scn.beams[0])
+        rig = rig_of(scn, None)
+        fld = rig.field(scn.beams[0], RTD_NO_SWEEP=env)
+        dose, info, _ = rig.compute(fld)
         assert (info["max_radius"] > 16) == (case != "radii <= 16")
-        try:
-            res[name] = (fld.fetch("bev").reshape(-1, H + 64, W + 64).copy(), dose.copy())
-        finally:
-            fld.destroy(); eng.device_free(d_dose); eng.close()
-    monkeypatch.delenv("RTD_NO_SWEEP", raising=False)
+        res[name] = (fld.fetch("bev").reshape(-1, H + 64, W + 64).copy(), dose)
     (bs, ds), (bm, dm) = res["sweep"], res["mfma"]
     big = obev > 1e-3 * obev.max()
     assert (np.abs(bs.astype(np.float64) - bm)[big] / obev[big]).max() <= 1e-5
     np.testing.assert_array_equal(bs[first_slice(of):] == 0, bm[first_slice(of):] == 0)
     for b in (bs, bm):
-        _rel_close(b, obev, rtol=1e-4)
-    _rel_close(ds, ref, rtol=1e-4)
-    _rel_close(dm, ref, rtol=1e-4)
+        rel_close(b, obev, rtol=1e-4)
+    rel_close(ds, ref, rtol=1e-4)
+    rel_close(dm, ref, rtol=1e-4)
 
 
 def first_slice(of):
@@ -323,7 +230,7 @@ def test_wide_field_many_tiles(orc, engine, synth):
     order) and 1568 fill blocks (> 4 per CU: the plain longest-first placement); every intermediate still matches."""
     ct, _ = scenarios.hetero_phantom(64)
     scn = scenarios.hetero_ct(synth, n=64, spots=70, pitch=6.0, n_layers=2, angles=[0.0], steps=160, ct=ct)
-    _, _, _, info = _compare_field(orc, engine, scn, scn.beams[0])
+    _, _, _, info = compare_field(orc, engine, scn, scn.beams[0])
     assert info["ray_dims"][0] * info["ray_dims"][1] >= 400 * 400
 
 
@@ -338,7 +245,7 @@ def test_options_switches(orc, engine, synth):
     opt.ks_sigma_cutoff = 2.5
     opt.conv_sigma_cutoff = 2.5
     opt.ray_weight_cutoff = 1.2
-    _compare_field(orc, engine, scn, scn.beams[0], options=opt)
+    compare_field(orc, engine, scn, scn.beams[0], options=opt)
 
 
 def test_reference_shaped_call_accumulates_two_beams(orc, engine, synth):
@@ -352,7 +259,7 @@ def test_reference_shaped_call_accumulates_two_beams(orc, engine, synth):
     log = io.StringIO()
     engine.cudaWrapperProtons(scn.ct, dose, scn.beams, scn.luts, log)
     assert "Total global execution time" in log.getvalue()
-    _rel_close(dose, ref, rtol=1e-4)
+    rel_close(dose, ref, rtol=1e-4)
     assert dose.min() >= 1e-7 * 0.999
 
 
@@ -375,7 +282,7 @@ def test_lut_directory_loader_matches_arrays(orc, engine, synth, tmp_path):
         eng.compute(scn.beams, dose)
         doses.append(dose)
         eng.close()
-    _rel_close(doses[0], doses[1], rtol=1e-5)
+    rel_close(doses[0], doses[1], rtol=1e-5)
     assert doses[0].max() > 0
 
 
@@ -450,7 +357,7 @@ def test_seeded_random_scenarios(orc, engine, synth, seed):
     dist = (math.inf, math.inf) if rng.random() < 0.4 else (float(rng.uniform(900, 3000)), float(rng.uniform(900, 3000)))
     steps = int(rng.choice([97, 200, 256, 333]))
     scn = scenarios.hetero_ct(synth, n=n, spots=spots, pitch=pitch, n_layers=n_layers, angles=[deg], source_dist=dist, steps=steps, ct=ct)
-    _compare_field(orc, engine, scn, scn.beams[0])
+    compare_field(orc, engine, scn, scn.beams[0])
 
 
 @pytest.mark.parametrize("n_samples,n_hu", [(6144, 3072), (2048, 9000)])
@@ -461,10 +368,10 @@ def test_lookup_tables_too_large_for_lds(orc, engine, n_samples, n_hu):
     big = luts.synth_luts(n_energies=40, n_samples=n_samples, n_hu=n_hu)
     ct, _ = scenarios.hetero_phantom(64)
     scn = scenarios.hetero_ct(big, n=64, spots=5, pitch=7.0, n_layers=3, angles=[15.0], ct=ct)
-    _compare_field(orc, engine, scn, scn.beams[0])
+    compare_field(orc, engine, scn, scn.beams[0])
 
 
-def test_c1_bev_dose_against_the_reference_cpu_convolution(orc, engine, synth):
+def test_c1_bev_dose_against_the_reference_cpu_convolution(orc, rig_of, synth):
     """BASELINE.json configs[0] (water cube 128^3, one G000 field, one energy layer) against the REFERENCE'S OWN CPU code: in water
     a BEV slice has one sigma, so its superposition is xConvCpuScat + yConvCpu of the slice (src/cpu_convolution_1d.cpp, compiled from
     the reference's sources into oracle/_ref/libref.so, which travels to the GPU box as a built file; the oracle's restatement of the
@@ -479,22 +386,19 @@ def test_c1_bev_dose_against_the_reference_cpu_convolution(orc, engine, synth):
     sep = ref_cpu_path.separable_bev(of, scn.beams[0], which=which)
     assert sep is not None
     sep_bev, _, n_slices, max_rad = sep
-    eng, fld, dose, timing, info, d_dose = _run_engine(engine, scn, scn.beams[0])
-    try:
-        W, H, L = info["ray_dims"]
-        gbev = fld.fetch("bev").reshape(-1, H + 64, W + 64)
-        sb = sep_bev[:gbev.shape[0]]
-        assert n_slices > 50 and sb.max() > 0
-        big = sb > 1e-3 * sb.max()
-        rel = np.abs(gbev.astype(np.float64) - sb)[big] / sb[big]
-        assert info["uniform_sigma"] == 1                            # water: the separable superposition kernel took the field
-        print("HIP BEV vs %s CPU convolution: %d slices, radius <= %d, max rel diff %.3g" % (which, n_slices, max_rad, rel.max()))
-        assert rel.max() <= 2e-5
-        assert np.abs(gbev.astype(np.float64) - sb).max() <= 2e-6 * sb.max()
-    finally:
-        fld.destroy()
-        eng.device_free(d_dose)
-        eng.close()
+    rig = rig_of(scn, None)
+    fld = rig.field(scn.beams[0])
+    _, info, _ = rig.compute(fld)
+    W, H, L = info["ray_dims"]
+    gbev = fld.fetch("bev").reshape(-1, H + 64, W + 64)
+    sb = sep_bev[:gbev.shape[0]]
+    assert n_slices > 50 and sb.max() > 0
+    big = sb > 1e-3 * sb.max()
+    rel = np.abs(gbev.astype(np.float64) - sb)[big] / sb[big]
+    assert info["uniform_sigma"] == 1                                # water: the separable superposition kernel took the field
+    print("HIP BEV vs %s CPU convolution: %d slices, radius <= %d, max rel diff %.3g" % (which, n_slices, max_rad, rel.max()))
+    assert rel.max() <= 2e-5
+    assert np.abs(gbev.astype(np.float64) - sb).max() <= 2e-6 * sb.max()
 
 
 @pytest.mark.parametrize("case", ["rows staged in LDS", "wave per row block", "wide ray grid: two strips", "fine rays: radii above 16",
@@ -518,7 +422,7 @@ def test_uniform_sigma_kernels(orc, engine, synth, monkeypatch, case):
         scn = scenarios.water_cube(synth, n=64, n_layers=40, spots=9, pitch=3.0)      # (the shallow slices are crossed by all 40: kU4TabLayers = 32)
     else:
         scn = scenarios.water_cube(synth, n=128, n_layers=4)
-    _, _, _, info = _compare_field(orc, engine, scn, scn.beams[0])
+    _, _, _, info = compare_field(orc, engine, scn, scn.beams[0])
     assert info["uniform_sigma"] == 1
     if case == "wide ray grid: two strips":
         assert info["ray_dims"][0] > 128
@@ -526,7 +430,7 @@ def test_uniform_sigma_kernels(orc, engine, synth, monkeypatch, case):
         assert info["ray_dims"][0] <= 128 and info["max_radius"] > 16, info
 
 
-def test_uniform_sigma_path_equals_the_general_superposition(orc, engine, synth, monkeypatch):
+def test_uniform_sigma_path_equals_the_general_superposition(orc, engine, rig_of, synth):
     """A water field is superposed by the separable kernels of rtd_uniform.hpp (one sigma per slice), decided on the device. With
     the path disabled (RTD_NO_UNIFORM_PATH, read at field creation) the same field goes through the row sweep: both BEV doses agree
     to rounding (same weights, different order of the sums), both are within the parity tolerance of the oracle, and the dose too.
@@ -538,34 +442,28 @@ def test_uniform_sigma_path_equals_the_general_superposition(orc, engine, synth,
     obev = of.get("bev").reshape(-1, H + 64, W + 64)
     res = {}
     for name, env in (("uniform", None), ("general", "1")):
-        if env is None:
-            monkeypatch.delenv("RTD_NO_UNIFORM_PATH", raising=False)
-        else:
-            monkeypatch.setenv("RTD_NO_UNIFORM_PATH", env)
-        eng, fld, dose, timing, info, d_dose = _run_engine(engine, scn, scn.beams[0])
-        try:
-            assert info["uniform_sigma"] == (1 if env is None else 0)
-            res[name] = (fld.fetch("bev").reshape(-1, H + 64, W + 64).copy(), dose.copy())
-        finally:
-            fld.destroy(); eng.device_free(d_dose); eng.close()
-    monkeypatch.delenv("RTD_NO_UNIFORM_PATH", raising=False)
+        rig = rig_of(scn, None)
+        fld = rig.field(scn.beams[0], RTD_NO_UNIFORM_PATH=env)
+        dose, info, _ = rig.compute(fld)
+        assert info["uniform_sigma"] == (1 if env is None else 0)
+        res[name] = (fld.fetch("bev").reshape(-1, H + 64, W + 64).copy(), dose)
     bu, du = res["uniform"]; bg, dg = res["general"]
     big = obev > 1e-3 * obev.max()
     assert (np.abs(bu.astype(np.float64) - bg)[big] / obev[big]).max() <= 1e-5
     np.testing.assert_array_equal(bu == 0, bg == 0)                  # same support: same radii
     for b in (bu, bg):
-        _rel_close(b, obev, rtol=1e-4)
-    _rel_close(du, ref, rtol=1e-4)
-    _rel_close(dg, ref, rtol=1e-4)
+        rel_close(b, obev, rtol=1e-4)
+    rel_close(du, ref, rtol=1e-4)
+    rel_close(dg, ref, rtol=1e-4)
     # half of the water replaced by a density step across the field: slices are no longer uniform
     ct2 = scn.ct.copy()
     ct2[:, :, : ct2.shape[2] // 2] *= 1.3
     scn2 = scenarios.Scenario("water with a density step", scn.luts, ct2, scn.spacing, scn.beams)
-    dose2, ref2, timing, info = _compare_field(orc, engine, scn2, scn2.beams[0])
+    dose2, ref2, timing, info = compare_field(orc, engine, scn2, scn2.beams[0])
     assert info["uniform_sigma"] == 0
     # a divergent beam into the same water: the rays' step lengths differ, so do their sigmas — general path, same parity bar
     scn3 = scenarios.water_cube(synth, n=128, n_layers=3, source_dist=(1800.0, 2200.0))
-    dose3, ref3, timing, info = _compare_field(orc, engine, scn3, scn3.beams[0])
+    dose3, ref3, timing, info = compare_field(orc, engine, scn3, scn3.beams[0])
     assert info["uniform_sigma"] == 0
     # One field object across computes: what it learned about its input (uniform: the general kernel is not even launched the next
     # time; heterogeneous: no detection, no separable launch) must not outlive that input — a new CT on the handle resets it.

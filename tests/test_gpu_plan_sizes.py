@@ -15,13 +15,10 @@ import dvh_reference as D
 import optimizer_reference as R
 import robust_reference as Q
 import tree_reference as T
+from gpu_plan_rigs import MODES, OptimizerRig, RobustRig
+from gpu_support import FieldRig, bits, box_mask, col_bound, col_of_entry, hetero_scene, options, row_bound, worst_ratio
 from raytracedicom_amd import abi, robust, scenarios
 from raytracedicom_amd import engine as E
-from test_gpu_dose_influence_apply import Rig as ProductRig
-from test_gpu_dose_influence_apply import _box_mask, _col_bound, _col_of_entry, _opts, _row_bound, _with_dose_grid, _worst_ratio
-from test_gpu_optimizer import Rig as OptRig
-from test_gpu_optimizer import _bits, _hetero
-from test_gpu_robust import MODES, RobustRig
 
 pytestmark = pytest.mark.gpu
 
@@ -37,30 +34,30 @@ def _check_products(rig, f, d, info, seed):
     rng = np.random.default_rng(seed)
     w = (100.0 * rng.random(shape)).astype(np.float32)
     g = (rng.random(rig.shape) - 0.5).astype(np.float32)
-    box = _box_mask(rig, info).reshape(-1)
+    box = box_mask(rig, info).reshape(-1)
     assert np.all(box[d.indices])                                     # (the row box is the dose box: nRows is its volume)
     got = rig.apply(f, w).reshape(-1)
     tree = T.apply_tree(d.indptr, d.indices, d.data, w, n_rows=nvox)
     want = np.full(nvox, np.nan, dtype=np.float32)
     want[box] = tree[box]
-    n, s = _row_bound(d, w)
+    n, s = row_bound(d, w)
     assert ((n == 0) & box).any() and not box.all()
-    differ = np.flatnonzero(_bits(got) != _bits(want))
+    differ = np.flatnonzero(bits(got) != bits(want))
     print("apply: %d of %d voxels differ from the restated tree (first %s)" % (differ.size, nvox, differ[:4]))
     assert differ.size == 0
     err = np.abs(np.where(box, got, 0.0).astype(np.float64) - d.matvec(w))
     bound = T.tree_bound(T.apply_depth(n), s)
-    print("apply: worst |gpu - float64| / tree-depth bound %.3g, longest row %d" % (_worst_ratio(err, bound), int(n.max())))
+    print("apply: worst |gpu - float64| / tree-depth bound %.3g, longest row %d" % (worst_ratio(err, bound), int(n.max())))
     assert np.all(err <= bound)
     got_t = rig.apply_t(f, g).reshape(-1)
     tree_t = T.apply_t_tree(d.indptr, d.indices, d.data, g)
-    differ = np.flatnonzero(_bits(got_t) != _bits(tree_t))
+    differ = np.flatnonzero(bits(got_t) != bits(tree_t))
     print("apply_t: %d of %d spots differ from the restated tree (first %s)" % (differ.size, got_t.size, differ[:4]))
     assert differ.size == 0
-    nt, st = _col_bound(d, g)
+    nt, st = col_bound(d, g)
     err_t = np.abs(got_t.astype(np.float64) - d.rmatvec(g))
     bound_t = T.tree_bound(T.apply_t_depth(nt), st)
-    print("apply_t: worst |gpu - float64| / tree-depth bound %.3g, longest column %d" % (_worst_ratio(err_t, bound_t), int(nt.max())))
+    print("apply_t: worst |gpu - float64| / tree-depth bound %.3g, longest column %d" % (worst_ratio(err_t, bound_t), int(nt.max())))
     assert np.abs(got_t).max() > 0 and np.all(err_t <= bound_t)
 
 
@@ -68,10 +65,10 @@ def test_products_large_box_and_long_columns(engine, synth):
     """A 192^3 dose grid (three dose voxels per CT voxel) over the 64^3 phantom, nine spots 45 mm apart: a row box of more than 2^20
     rows whose count is no multiple of 4096 or 16 (k_dijap_scan_blocks with several block sums per thread, the last scan block cut
     inside a thread's 16 rows) and a column of more than 64 chunks (the second trip of k_dijap_reduce_t)."""
-    scn = _hetero(synth, n=64, angles=(20.0,), spots=3, pitch=45.0, layers=1)
+    scn = hetero_scene(synth, 64, (20.0,), spots=3, pitch=45.0, layers=1)
     t = scn.beams[0].gantryToDoseIdx
-    b = _with_dose_grid(scn.beams[0], scenarios.Float3AffineTransform(3.0 * t.m, 3.0 * t.v + 1.0))   # dose voxels 3i .. 3i + 2 cover CT voxel i
-    rig = ProductRig(engine, scn, _opts(0.0), (192, 192, 192))
+    b = scn.beams[0].replace(gantryToDoseIdx=scenarios.Float3AffineTransform(3.0 * t.m, 3.0 * t.v + 1.0))   # dose voxels 3i .. 3i + 2 cover CT voxel i
+    rig = FieldRig(engine, scn, options(0.0), (192, 192, 192))
     try:
         f = rig.field(b)
         d = f.dose_influence()
@@ -92,8 +89,8 @@ def test_products_large_box_and_long_columns(engine, synth):
 def test_products_long_rows(engine, synth):
     """13 x 13 spots 2 mm apart in one layer: a voxel hit by more than 128 spots, so k_dijap_sort's lanes take a third trip; the
     bit comparison pins the ascending column order it writes. apply_t of the unit vector at the longest row is that row, exactly."""
-    scn = _hetero(synth, n=64, angles=(0.0,), spots=13, pitch=2.0, layers=1)
-    rig = ProductRig(engine, scn, _opts(0.0))
+    scn = hetero_scene(synth, 64, (0.0,), spots=13, pitch=2.0, layers=1)
+    rig = FieldRig(engine, scn, options(0.0))
     try:
         f = rig.field(scn.beams[0])
         d = f.dose_influence()
@@ -107,8 +104,8 @@ def test_products_long_rows(engine, synth):
         e[v] = 1.0
         want = np.zeros(d.shape[1], dtype=np.float32)
         hit = d.indices == v
-        want[_col_of_entry(d)[hit]] = d.data[hit]
-        assert np.array_equal(_bits(rig.apply_t(f, e).reshape(-1)), _bits(want))
+        want[col_of_entry(d)[hit]] = d.data[hit]
+        assert np.array_equal(bits(rig.apply_t(f, e).reshape(-1)), bits(want))
     finally:
         rig.close()
 
@@ -118,7 +115,7 @@ def test_products_long_rows(engine, synth):
 REL_THRESHOLD = 0.05
 
 
-class PlanRig(OptRig):
+class PlanRig(OptimizerRig):
     """Fields whose matrices stay on the device (the restatements need vectors, not matrices), optionally under set-up shifts as
     further scenarios, and the plan objective of the optimiser tests built from the device's own dose of w_true."""
 
@@ -126,7 +123,7 @@ class PlanRig(OptRig):
         self.engine = engine
         ct, _ = scenarios.hetero_phantom(64)
         self.eng = engine.Engine(0)
-        self.eng.set_options(_opts(0.0))
+        self.eng.set_options(options(0.0))
         self.eng.set_luts(synth)
         self.eng.set_ct(ct)
         self.dims = (64, 64, 64)
@@ -239,7 +236,7 @@ def _plain_iterations(rig):
         assert a_ref > 0 and rel <= (n + 2) * 2.0 ** -52
         assert rep["step"] == a_tree
         w_new = rig.all_weights(opt)
-        assert w_new.size == n and np.array_equal(_bits(w_new), _bits(R.update(w, grad, rep["step"])))
+        assert w_new.size == n and np.array_equal(bits(w_new), bits(R.update(w, grad, rep["step"])))
         assert not np.array_equal(w_new, w)
         edge = rig.sizes[0]                                           # (the update crosses the field boundary inside a block)
         assert not np.array_equal(w_new[edge - 8:edge], w[edge - 8:edge]) and not np.array_equal(w_new[edge:edge + 8], w[edge:edge + 8])
@@ -279,16 +276,16 @@ def test_robust_several_chunks(plan_rig, mode):
             v, g = rig.scenario_grad(s, opt.scenario_dose(s), dG, dGrad)
             values.append(v[0])
             grads.append(g)
-        assert np.array_equal(_bits(np.array(values)), _bits(vals)) and len(set(values)) == rig.S
+        assert np.array_equal(bits(np.array(values)), bits(vals)) and len(set(values)) == rig.S
         lam_ref, F_ref, worst_ref = Q.decide(values, mode, p)
-        assert np.array_equal(_bits(lam_ref), _bits(lam)) and worst_ref == worst
+        assert np.array_equal(bits(lam_ref), bits(lam)) and worst_ref == worst
         assert F_ref == hist[k] and hist[k] == rep["f_last"] and rep["guarded"] == 0
         grad = Q.combine(grads, lam_ref)
         a_ref = Q.step_length_tree(w, w_prev, grad, grad_prev, k > 0)
         print("iteration %d, mode %d: F %.9g, lambda %s, alpha %.17g on the device, %.17g restated" % (k, mode, hist[k], lam, rep["step"], a_ref))
         assert a_ref > 0 and rep["step"] == a_ref
         w_new = rig.all_weights(opt)
-        assert w_new.size == rig.n and np.array_equal(_bits(w_new), _bits(R.update(w, grad, rep["step"]))) and not np.array_equal(w_new, w)
+        assert w_new.size == rig.n and np.array_equal(bits(w_new), bits(R.update(w, grad, rep["step"]))) and not np.array_equal(w_new, w)
         w_prev, grad_prev = w, grad
 
 
@@ -304,7 +301,7 @@ class Rig32(RobustRig):
     """The smallest field of the robust tests (3 x 3 x 1 spots, 64^3) under RTD_ROBUST_MAX_SCENARIOS = 32 set-up shifts."""
 
     def __init__(self, engine, scn):
-        OptRig.__init__(self, engine, scn)
+        OptimizerRig.__init__(self, engine, scn)
         self.sfields, self.smats = [self.fields], [self.mats]
         for beams in robust.scenario_beams(scn.beams, SHIFTS_32[1:]):
             self._add(beams)
@@ -321,7 +318,7 @@ class Rig32(RobustRig):
 
 @pytest.fixture(scope="module")
 def rig32(engine, synth):
-    rig = Rig32(engine, _hetero(synth, n=64, angles=(0.0,), spots=3, layers=1))
+    rig = Rig32(engine, hetero_scene(synth, 64, (0.0,), spots=3, layers=1))
     yield rig
     rig.close()
 
@@ -351,7 +348,7 @@ def test_32_scenarios_doses_and_values(rig32, mode):
             got = rig.volume(opt.scenario_dose(s))
             rig.scenario_dose_of(s, ws, dDose)
             want = rig.volume(dDose)
-            assert want.max() > 0 and np.array_equal(_bits(got), _bits(want)), (k, s)
+            assert want.max() > 0 and np.array_equal(bits(got), bits(want)), (k, s)
             assert rig.obj.eval(dDose, dG)[0] == vals[s], (k, s)
             seen.append(got)
         assert all(not np.array_equal(seen[s], seen[s + 1]) for s in range(rig.S - 1))
@@ -359,7 +356,7 @@ def test_32_scenarios_doses_and_values(rig32, mode):
         assert worst == int(np.argmax(vals)) and opt.result()[0]["f_last"] == Q.decide(vals, mode)[1]
         assert worst >= 16
         want_lam = np.where(np.arange(rig.S) == worst, 1.0, 0.0) if mode == abi.RTD_ROBUST_WORST_CASE else np.full(rig.S, 1.0 / rig.S)
-        assert np.array_equal(_bits(lam), _bits(want_lam))
+        assert np.array_equal(bits(lam), bits(want_lam))
 
 
 @pytest.mark.parametrize("mode", MODES)
@@ -375,16 +372,16 @@ def test_32_scenarios_batched_equals_unbatched(rig32, mode):
     b.run(12)
     ra, ha = a.result()
     rb, hb = b.result()
-    assert ra == rb and np.array_equal(_bits(ha), _bits(hb))
+    assert ra == rb and np.array_equal(bits(ha), bits(hb))
     for best in (False, True):
         for x, y in zip(rig.weights(a, best), rig.weights(b, best)):
-            assert np.array_equal(_bits(x), _bits(y))
+            assert np.array_equal(bits(x), bits(y))
     assert ra["iterations"] == 12 and np.all(np.isfinite(ha)) and ra["f_best"] < ha[0]
     va, vb = a.scenario_values(), b.scenario_values()
     print("mode %d: worst scenario after twelve iterations %d, values %s" % (mode, va[2], va[0]))
-    assert np.array_equal(_bits(va[0]), _bits(vb[0])) and np.array_equal(_bits(va[1]), _bits(vb[1])) and va[2] == vb[2]
+    assert np.array_equal(bits(va[0]), bits(vb[0])) and np.array_equal(bits(va[1]), bits(vb[1])) and va[2] == vb[2]
     for s in range(rig.S):
-        assert np.array_equal(_bits(rig.volume(a.scenario_dose(s))), _bits(rig.volume(b.scenario_dose(s))))
+        assert np.array_equal(bits(rig.volume(a.scenario_dose(s))), bits(rig.volume(b.scenario_dose(s))))
 
 
 # ---- 5. DVH on values and sizes the field never produces ---------------------------------------------------------------------
@@ -477,8 +474,8 @@ def test_dose_at_volume_on_synthetic_values(dvh_case):
     for r, idx in enumerate(rois):
         asc = _ascending(vol[idx])
         n = asc.size
-        bits = asc.view(np.uint32)
-        run_end = np.flatnonzero(np.concatenate([bits[1:] != bits[:-1], [True]]))
+        pat = asc.view(np.uint32)
+        run_end = np.flatnonzero(np.concatenate([pat[1:] != pat[:-1], [True]]))
         run_len = np.diff(np.concatenate([[-1], run_end]))
         j = int(np.argmax(run_len))
         top, bottom = n - int(run_end[j]), n - int(run_end[j]) + int(run_len[j]) - 1       # the ranks (from the top) the longest run spans
@@ -493,8 +490,8 @@ def test_dose_at_volume_on_synthetic_values(dvh_case):
     got = obj.dose_at_volume(dVol, queries)
     for (r, v), a, b in zip(queries, got, want):
         print("ROI %d (N %d), k %d: device %r (%08x) sorted %r (%08x)" % (r, sizes[r], D.rank(v, sizes[r]), float(a), a.view(np.uint32), float(b), b.view(np.uint32)))
-    assert got.dtype == np.float32 and np.array_equal(_bits(got), _bits(want))
-    assert np.array_equal(_bits(obj.dose_at_volume(dVol, queries)), _bits(want))
+    assert got.dtype == np.float32 and np.array_equal(bits(got), bits(want))
+    assert np.array_equal(bits(obj.dose_at_volume(dVol, queries)), bits(want))
     seen = set(want.view(np.uint32).tolist())
     assert int(NANS[1]) in seen or int(NANS[0]) in seen or int(NANS[2]) in seen      # k = 1 of the large ROI: a NaN with the sign bit clear
     assert 0x80000000 in seen or 0x00000000 in seen                                  # a zero was selected

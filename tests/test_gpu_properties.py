@@ -44,8 +44,7 @@ def test_exact_linearity_in_spot_weights(engine, synth):
     opt.ray_weight_cutoff = 0.0
     d1 = _dose(engine, scn, options=opt)
     b = scn.beams[0]
-    b2 = scenarios.BeamSettings(b.spotWeights * np.float32(4.0), b.beamEnergies, b.spotSigmas, b.raySpacing, b.tracerSteps, b.sourceDist,
-                                b.spotIdxToGantry, b.gantryToImIdx, b.gantryToDoseIdx)
+    b2 = b.replace(spotWeights=b.spotWeights * np.float32(4.0))
     d2 = _dose(engine, scn, beams=[b2], options=opt)
     assert d1.max() > 0
     np.testing.assert_array_equal(d2, d1 * np.float32(4.0))

@@ -1,178 +1,38 @@
 """GPU tests of the robust optimiser (rtd_optimizer_create_robust, rtd_optimizer_scenario_values, rtd_optimizer_scenario_dose;
 include/rtd.h) through the C ABI, against the numpy restatement of its iteration (tests/robust_reference.py).
 The 96^3 heterogeneous phantom of the optimiser tests, ray_weight_cutoff = 0, five scenarios: nominal, the patient displaced by
-+-SHIFT_MM across the beam (gantry x), and the stopping-power table scaled by 0.965 and 1.035."""
++-5 mm across the beam (gantry x), and the stopping-power table scaled by 0.965 and 1.035."""
 import ctypes as C
 import math
-import os
 
 import numpy as np
 import pytest
 
-import dvh_reference as D
 import optimizer_reference as R
 import robust_reference as Q
+from gpu_plan_rigs import MODES, RobustRig, same
+from gpu_support import bits, hetero_scene, rig_fixture
 from raytracedicom_amd import abi, robust, scenarios
-from test_gpu_optimizer import Rig, _bits, _hetero
 
 pytestmark = pytest.mark.gpu
 
-SHIFT_MM = 5.0
-FACTORS = (0.965, 1.035)
-MODES = (abi.RTD_ROBUST_EXPECTED, abi.RTD_ROBUST_WORST_CASE)
-
-
-class RobustRig(Rig):
-    """The rig of the optimiser tests (its fields are scenario 0) with four more scenarios of the same beams beside it, every field
-    with its matrix. Objectives are the rig's own (section 12) or made here (with DVH terms, as tests/test_gpu_dvh.py makes its plan)."""
-
-    def __init__(self, engine, scn, shift=SHIFT_MM):
-        super().__init__(engine, scn)
-        self.sfields, self.smats = [self.fields], [self.mats]
-        for beams in robust.scenario_beams(scn.beams, [(shift, 0.0, 0.0), (-shift, 0.0, 0.0)]):
-            self._add(beams)
-        for factor in FACTORS:
-            self.eng.set_luts(robust.range_scaled_luts(scn.luts, factor))
-            self._add(scn.beams)
-        self.eng.set_luts(scn.luts)
-        self.S = len(self.sfields)
-        self.objs = []
-        self.n = sum(self.sizes)
-
-    def _add(self, beams):
-        fs = [self.eng.create_field(b, self.dims) for b in beams]
-        self.sfields.append(fs)
-        self.smats.append([f.dose_influence() for f in fs])
-
-    def dvh_objective(self):
-        """The plan of tests/test_gpu_dvh.py on the nominal scenario's dose of w_true."""
-        dose_true = self.matvec(np.concatenate([w.reshape(-1) for w in self.w_true]))
-        has = sum(np.bincount(d.indices, minlength=self.nvox) for d in self.mats) > 0
-        target = dose_true > 0.5 * dose_true.max()
-        other = has & ~target
-        L = float(dose_true[target].mean())
-        d25 = float(np.sort(dose_true[other].astype(np.float32))[::-1][D.rank(0.25, int(other.sum())) - 1])
-        obj, ref = self.eng.create_objective(self.dims), D.DvhReferenceObjective(self.nvox)
-        self.objs.append(obj)
-        for m in (target, other):
-            obj.add_roi(m)
-            ref.add_roi(m)
-        for t in ((R.SQ_DEVIATION, 0, 1.0, L), (D.MIN_DVH, 0, 5.0, 0.95 * L, 0.98), (D.MAX_DVH, 1, 3.0, 0.5 * d25, 0.25)):
-            for o in (obj, ref):
-                (o.add_dvh_term if len(t) == 5 else o.add_term)(*t)
-        return obj, ref
-
-    def margin_objective(self, half_width_mm):
-        """The rig's objective (section 12's terms and weights) with the target cut to the voxels within half_width_mm of the beam
-        axis across the beam (world x at gantry angle 0; the grid spans 256 mm from -128): a target narrower than the spot pattern,
-        so that a plan has spots left to paint a margin with. -> (device, restated)."""
-        dose_true = self.matvec(np.concatenate([w.reshape(-1) for w in self.w_true]))
-        has = sum(np.bincount(d.indices, minlength=self.nvox) for d in self.mats) > 0
-        x = (np.arange(self.nvox) % self.dims[0]) * (256.0 / self.dims[0]) - 128.0
-        target = (dose_true > 0.5 * dose_true.max()) & (np.abs(x) <= half_width_mm)
-        other = has & ~target
-        L = float(dose_true[target].mean())
-        obj, ref = self.eng.create_objective(self.dims), R.ReferenceObjective(self.nvox)
-        self.objs.append(obj)
-        for o in (obj, ref):
-            o.add_roi(target)
-            o.add_roi(other)
-            for t in ((R.SQ_DEVIATION, 0, 1.0, L), (R.SQ_UNDERDOSE, 0, 5.0, 0.95 * L), (R.SQ_OVERDOSE, 1, 1.0, 0.3 * L), (R.MEAN, 1, 1e-3 * L, 0.0)):
-                o.add_term(*t)
-        return obj, ref
-
-    def robust(self, mode, start=None, probabilities=None, scen=None, obj=None, no_batch=False):
-        sf = self.sfields if scen is None else [self.sfields[s] for s in scen]
-        if no_batch:
-            os.environ["RTD_ROBUST_NO_BATCH"] = "1"
-        try:
-            o = self.eng.create_robust_optimizer(sf, self.obj if obj is None else obj, mode, probabilities)
-        finally:
-            os.environ.pop("RTD_ROBUST_NO_BATCH", None)
-        self.opts.append(o)
-        if start is not None:
-            self.set_weights(o, start)
-        return o
-
-    def all_weights(self, o, best=False):
-        return np.concatenate([w.reshape(-1) for w in self.weights(o, best)])
-
-    def scenario_dose_of(self, s, ws, dDose):
-        """Zero, then apply(init = 0) per field of scenario s in list order, into dDose."""
-        self.eng.device_zero(dDose, 4 * self.nvox)
-        for f, w in zip(self.sfields[s], ws):
-            d = self.alloc(w.nbytes, zero=False)
-            self.eng.to_device(d, np.ascontiguousarray(w, dtype=np.float32))
-            f.dose_influence_apply(d, dDose, init=False)
-        self.eng.sync()
-
-    def scenario_grad(self, obj, s, dose_ptr, dG, dGrad):
-        """rtd_objective_eval on a volume and apply_t of scenario s's fields on its g -> (values, concatenated float32 gradient)."""
-        self.eng.device_zero(dG, 4 * self.nvox)
-        vals = obj.eval(dose_ptr, dG)
-        out = []
-        for f, n in zip(self.sfields[s], self.sizes):
-            f.dose_influence_apply_t(dG, dGrad)
-            g = np.empty(n, dtype=np.float32)
-            self.eng.to_host(g, dGrad)
-            out.append(g)
-        return vals, np.concatenate(out)
-
-    def host_products(self):
-        offs = np.cumsum([0] + self.sizes)
-        mv = [(lambda w, ms=ms: sum(d.matvec(np.asarray(w, dtype=np.float64)[a:b]) for d, a, b in zip(ms, offs, offs[1:]))) for ms in self.smats]
-        rmv = [(lambda g, ms=ms: np.concatenate([d.rmatvec(g) for d in ms])) for ms in self.smats]
-        return mv, rmv
-
-    def close(self):
-        for o in self.opts:
-            o.destroy()
-        self.opts = []
-        for o in self.objs:
-            o.destroy()
-        for fs in self.sfields[1:]:
-            for f in fs:
-                f.destroy()
-        super().close()
-
-
-@pytest.fixture
-def rrig_of(engine):
-    rigs = []
-
-    def make(scn, **kw):
-        r = RobustRig(engine, scn, **kw)
-        rigs.append(r)
-        return r
-    yield make
-    for r in rigs:
-        r.close()
-
-
-def _same(rig, a, b):
-    ra, ha = a.result()
-    rb, hb = b.result()
-    assert ra == rb and np.array_equal(_bits(ha), _bits(hb))
-    for best in (False, True):
-        for x, y in zip(rig.weights(a, best), rig.weights(b, best)):
-            assert np.array_equal(_bits(x), _bits(y))
-    return ra, ha
+rrig_of = rig_fixture(RobustRig, "rrig_of")
 
 
 @pytest.mark.parametrize("dvh", [False, True])
 def test_one_scenario_is_the_plain_optimiser(rrig_of, synth, dvh):
     """S = 1, EXPECTED, p = [1.0]: after 10 iterations history, w, w_best and the report are those of rtd_optimizer_create, bit for
     bit; with the objective of section 12 and with the DVH objective of tests/test_gpu_dvh.py."""
-    rig = rrig_of(_hetero(synth, angles=(0.0, 90.0)))
+    rig = rrig_of(hetero_scene(synth, 96, (0.0, 90.0)))
     obj = rig.dvh_objective()[0] if dvh else rig.obj
     plain = rig.eng.create_optimizer(rig.fields, obj, None)
     rig.opts.append(plain)
     one = rig.robust(abi.RTD_ROBUST_EXPECTED, probabilities=[1.0], scen=[0], obj=obj)
     plain.run(10)
     one.run(10)
-    rep, hist = _same(rig, plain, one)
+    rep, hist = same(rig, plain, one)
     assert rep["iterations"] == 10 and hist.size == 10 and np.all(np.isfinite(hist)) and hist.min() < hist[0]
-    assert np.array_equal(_bits(rig.volume(plain.dose())), _bits(rig.volume(one.dose())))
+    assert np.array_equal(bits(rig.volume(plain.dose())), bits(rig.volume(one.dose())))
     v, l, worst = one.scenario_values()
     assert v.size == 1 and v[0] == rep["f_last"] and l[0] == 1.0 and worst == 0
     v, l, worst = plain.scenario_values()                              # a plain optimiser is a set of one scenario
@@ -184,7 +44,7 @@ def test_scenario_doses_and_values(rrig_of, synth, mode):
     """After run(1): scenario_dose(s) is a zeroed volume followed by apply(init = 0) per field of scenario s, bit for bit;
     scenario_values()[s] is rtd_objective_eval on that volume, bit for bit; rtd_optimizer_dose is scenario 0. Twice, so that the
     second forward product runs over what the first left."""
-    rig = rrig_of(_hetero(synth, angles=(0.0, 90.0)))
+    rig = rrig_of(hetero_scene(synth, 96, (0.0, 90.0)))
     opt = rig.robust(mode)
     dDose, dG = rig.alloc(4 * rig.nvox), rig.alloc(4 * rig.nvox)
     for k in range(2):
@@ -197,7 +57,7 @@ def test_scenario_doses_and_values(rrig_of, synth, mode):
             got = rig.volume(opt.scenario_dose(s))
             rig.scenario_dose_of(s, ws, dDose)
             want = rig.volume(dDose)
-            assert want.max() > 0 and np.array_equal(_bits(got), _bits(want)), (k, s)
+            assert want.max() > 0 and np.array_equal(bits(got), bits(want)), (k, s)
             assert rig.obj.eval(dDose, dG)[0] == vals[s], (k, s)
             seen.append(got)
         assert not np.array_equal(seen[0], seen[1]) and not np.array_equal(seen[0], seen[3]) and not np.array_equal(seen[3], seen[4])
@@ -210,7 +70,7 @@ def test_the_iteration_against_the_restatement(rrig_of, synth, mode):
     """Two crossing fields, iterations 0, 1 and 2, the restatement fed the device's own per-scenario values and per-scenario gradients
     (apply_t on g_s): lambda, F and the combined gradient bit for bit (the gradient through the weights it produces), the step length
     bit for bit against the restatement that sums in the device's order, the updated weights bit for bit."""
-    rig = rrig_of(_hetero(synth, angles=(0.0, 90.0)))
+    rig = rrig_of(hetero_scene(synth, 96, (0.0, 90.0)))
     p = [0.4, 0.15, 0.15, 0.15, 0.15] if mode == abi.RTD_ROBUST_EXPECTED else None
     opt = rig.robust(mode, probabilities=p)
     dG, dGrad = rig.alloc(4 * rig.nvox), rig.alloc(4 * max(rig.sizes))
@@ -225,16 +85,16 @@ def test_the_iteration_against_the_restatement(rrig_of, synth, mode):
             v, g = rig.scenario_grad(rig.obj, s, opt.scenario_dose(s), dG, dGrad)
             values.append(v[0])
             grads.append(g)
-        assert np.array_equal(_bits(np.array(values)), _bits(vals))
+        assert np.array_equal(bits(np.array(values)), bits(vals))
         lam_ref, F_ref, worst_ref = Q.decide(values, mode, p)
-        assert np.array_equal(_bits(lam_ref), _bits(lam)) and worst_ref == worst
+        assert np.array_equal(bits(lam_ref), bits(lam)) and worst_ref == worst
         assert F_ref == hist[k] and hist[k] == rep["f_last"] and rep["guarded"] == 0
         grad = Q.combine(grads, lam_ref)
         a_ref = Q.step_length_tree(w, w_prev, grad, grad_prev, k > 0)
         print("iteration %d, mode %d: F %.9g, lambda %s, alpha %.17g on the device, %.17g restated" % (k, mode, hist[k], lam, rep["step"], a_ref))
         assert a_ref > 0 and rep["step"] == a_ref
         w_new = rig.all_weights(opt)
-        assert np.array_equal(_bits(w_new), _bits(R.update(w, grad, rep["step"]))) and not np.array_equal(w_new, w)
+        assert np.array_equal(bits(w_new), bits(R.update(w, grad, rep["step"]))) and not np.array_equal(w_new, w)
         w_prev, grad_prev = w, grad
 
 
@@ -242,24 +102,24 @@ def test_the_iteration_against_the_restatement(rrig_of, synth, mode):
 def test_batched_equals_unbatched(rrig_of, synth, mode):
     """The same twelve iterations with RTD_ROBUST_NO_BATCH set before creation (the single-matrix launches, scenario by scenario):
     the same history, weights and scenario doses, bit for bit. With the DVH objective under WORST_CASE, the plain one under EXPECTED."""
-    rig = rrig_of(_hetero(synth, angles=(0.0, 90.0)))
+    rig = rrig_of(hetero_scene(synth, 96, (0.0, 90.0)))
     obj = rig.dvh_objective()[0] if mode == abi.RTD_ROBUST_WORST_CASE else rig.obj
     a, b = rig.robust(mode, start=0.0, obj=obj), rig.robust(mode, start=0.0, obj=obj, no_batch=True)
     a.run(12)
     b.run(12)
-    rep, hist = _same(rig, a, b)
+    rep, hist = same(rig, a, b)
     assert rep["iterations"] == 12 and np.all(np.isfinite(hist)) and rep["f_best"] < hist[0]
     va, vb = a.scenario_values(), b.scenario_values()
-    assert np.array_equal(_bits(va[0]), _bits(vb[0])) and np.array_equal(_bits(va[1]), _bits(vb[1])) and va[2] == vb[2]
+    assert np.array_equal(bits(va[0]), bits(vb[0])) and np.array_equal(bits(va[1]), bits(vb[1])) and va[2] == vb[2]
     for s in range(rig.S):
-        assert np.array_equal(_bits(rig.volume(a.scenario_dose(s))), _bits(rig.volume(b.scenario_dose(s))))
+        assert np.array_equal(bits(rig.volume(a.scenario_dose(s))), bits(rig.volume(b.scenario_dose(s))))
 
 
 def test_reproducible_and_capturable(engine, rrig_of, synth):
     """run(30) = run(10) three times; a second engine gives the same history; run(5) captured into a graph on a caller's stream and
     replayed once gives the bits of the direct call."""
     import torch
-    scn = _hetero(synth, angles=(0.0,))
+    scn = hetero_scene(synth, 96, (0.0,))
     rig = rrig_of(scn)
     mode = abi.RTD_ROBUST_WORST_CASE
     a, b = rig.robust(mode, start=0.0), rig.robust(mode, start=0.0)
@@ -267,13 +127,13 @@ def test_reproducible_and_capturable(engine, rrig_of, synth):
     for _ in range(3):
         b.run(10)
         b.run(0)
-    ra, ha = _same(rig, a, b)
+    ra, ha = same(rig, a, b)
     assert ha.size == 30
     other = rrig_of(scn)
     c = other.robust(mode, start=0.0)
     c.run(30)
     rc, hc = c.result()
-    assert rc == ra and np.array_equal(_bits(hc), _bits(ha))
+    assert rc == ra and np.array_equal(bits(hc), bits(ha))
     for m in MODES:
         direct, captured = rig.robust(m, start=0.0), rig.robust(m, start=0.0)
         s = torch.cuda.Stream()
@@ -291,16 +151,16 @@ def test_reproducible_and_capturable(engine, rrig_of, synth):
         rd, hd = direct.result()
         rg, hg = captured.result()
         rig.eng.set_stream(None)
-        assert rd == rg and hd.size == 5 and np.array_equal(_bits(hd), _bits(hg))
+        assert rd == rg and hd.size == 5 and np.array_equal(bits(hd), bits(hg))
         if m == mode:
-            assert np.array_equal(_bits(hd), _bits(ha[:5]))
-        assert np.array_equal(_bits(rig.weights(direct)[0]), _bits(rig.weights(captured)[0]))
+            assert np.array_equal(bits(hd), bits(ha[:5]))
+        assert np.array_equal(bits(rig.weights(direct)[0]), bits(rig.weights(captured)[0]))
 
 
 @pytest.mark.parametrize("mode", MODES)
 def test_guard(rrig_of, synth, mode):
     """Weights of +inf give an F that is not finite: the guard is taken, the next iterate is w_best and reproduces F_best bit for bit."""
-    rig = rrig_of(_hetero(synth, n=64, angles=(0.0,), spots=3, layers=1))
+    rig = rrig_of(hetero_scene(synth, 64, (0.0,), spots=3, layers=1))
     opt = rig.robust(mode)
     opt.run(5)
     r5, h5 = opt.result()
@@ -310,7 +170,7 @@ def test_guard(rrig_of, synth, mode):
     opt.run(2)
     r7, h7 = opt.result()
     assert not math.isfinite(h7[5]) and r7["guarded"] == 1 and h7[6] == r7["f_best"] == r5["f_best"] and math.isfinite(r7["step"])
-    assert np.array_equal(_bits(rig.weights(opt, best=True)[0]), _bits(best5))
+    assert np.array_equal(bits(rig.weights(opt, best=True)[0]), bits(best5))
     vals, lam, worst = opt.scenario_values()
     assert np.all(np.isfinite(vals)) and Q.decide(vals, mode)[1] == h7[6]
     opt.run(3)
@@ -340,7 +200,7 @@ def test_the_point_of_it(rrig_of, synth):
     that target its ratios were 0.55 / 0.78 at shifts of 5 mm, and enlarging the shifts does not bring them down (0.53 / 0.72 at
     8 mm, 0.63 / 0.77 at 12 mm, 0.72 / 0.82 at 16 mm, float64 products of the CPU oracle's columns). A target of +-8 mm leaves the
     spots at +-16 mm as a margin wider than the 5 mm shift; the same restatement then gives 0.17 / 0.32."""
-    rig = rrig_of(_hetero(synth, angles=(0.0,)))
+    rig = rrig_of(hetero_scene(synth, 96, (0.0,)))
     zeros = np.zeros(rig.n)
     obj, ref = rig.margin_objective(TARGET_HALF_WIDTH_MM)
     plain = rig.eng.create_optimizer(rig.fields, obj, None)
@@ -406,7 +266,7 @@ def test_range_scaled_luts_move_the_distal_edge(engine, synth):
 
 def test_refusals(engine, synth):
     L = engine.lib()
-    scn = _hetero(synth, n=64, angles=(0.0, 90.0), spots=3, layers=1)
+    scn = hetero_scene(synth, 64, (0.0, 90.0), spots=3, layers=1)
     rig = RobustRig(engine, scn)
     try:
         eng, h = rig.eng, rig.eng._h
@@ -414,7 +274,7 @@ def test_refusals(engine, synth):
         remote = eng.create_field(scn.beams[0], rig.dims, remote=True)
         coarse = eng.create_field(scn.beams[0], (32, 32, 32))
         coarse.dose_influence()
-        other_shape = eng.create_field(_hetero(synth, n=64, angles=(0.0,), spots=4, layers=1).beams[0], rig.dims)
+        other_shape = eng.create_field(hetero_scene(synth, 64, (0.0,), spots=4, layers=1).beams[0], rig.dims)
         other_shape.dose_influence()
         f = rig.sfields
         arr = lambda *fs: (C.c_void_p * 80)(*[x._h for x in fs])   # noqa: E731

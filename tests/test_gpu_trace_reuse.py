@@ -8,30 +8,12 @@ import math
 import numpy as np
 import pytest
 
+from gpu_support import FieldRig, hetero_scene, options, rig_fixture
 from raytracedicom_amd import abi, luts, scenarios
 
 pytestmark = pytest.mark.gpu
 
 _FETCHED = ("bev", "tile_radius", "eff_radius", "layer_plan", "first_passive", "first_inside", "first_outside", "wepl_min", "density", "wepl")
-
-
-def _opts(cutoff=1.0, timing=0, nuclear=0):
-    o = abi.default_options()
-    o.ray_weight_cutoff = cutoff
-    o.fine_grained_timing = timing
-    o.nuclear_corr = nuclear
-    return o
-
-
-def _with_weights(b, w):
-    return scenarios.BeamSettings(np.ascontiguousarray(w, dtype=np.float32), b.beamEnergies, b.spotSigmas, b.raySpacing, b.tracerSteps,
-                                  b.sourceDist, b.spotIdxToGantry, b.gantryToImIdx, b.gantryToDoseIdx)
-
-
-def _hetero(synth, n=128, angle=0.0, source_dist=(math.inf, math.inf), spots=7, pitch=6.0, layers=3, seed=5, **kw):
-    ct, _ = scenarios.hetero_phantom(n)
-    return scenarios.hetero_ct(synth, n=n, spots=spots, pitch=pitch, n_layers=layers, angles=[angle], ct=ct, source_dist=source_dist,
-                               seed=seed, **kw)
 
 
 def _missing(synth, n=128):
@@ -41,64 +23,16 @@ def _missing(synth, n=128):
     return scenarios.Scenario("beam beside the volume", synth, ct, (voxel,) * 3, [beam])
 
 
-class Rig:
-    """One engine with the scenario's LUTs and CT (a host upload unless told otherwise) and one device dose volume."""
-
-    def __init__(self, engine, scn, opt, set_ct=True):
-        self.eng = engine.Engine(0)
-        self.eng.set_options(opt)
-        self.eng.set_luts(scn.luts)
-        if set_ct:
-            self.eng.set_ct(scn.ct)
-        self.dims = tuple(scn.dims)
-        self.shape = scn.ct.shape
-        self.nb = int(scn.ct.size) * 4
-        self.dDose = self.eng.device_alloc(self.nb)
-        self.fields = []
-
-    def field(self, beam, monkeypatch=None, **env):
-        """A field created with the given RTD_* switches in the environment (they are read at creation)."""
-        for k, v in env.items():
-            monkeypatch.setenv(k, v)
-        try:
-            f = self.eng.create_field(beam, self.dims)
-        finally:
-            for k in env:
-                monkeypatch.delenv(k)
-        self.fields.append(f)
-        return f
-
-    def compute(self, f, names=_FETCHED):
-        """One compute with a finish: (trace_reused, {dose, info, timing, the fetched arrays})."""
-        self.eng.device_zero(self.dDose, self.nb)
-        f.compute(self.dDose)
-        timing, info = f.finish()
-        out = {"info": info, "timing": timing}
-        dose = np.empty(self.shape, dtype=np.float32)
-        self.eng.to_host(dose, self.dDose)
-        out["dose"] = dose
-        for nm in names:
-            out[nm] = f.fetch(nm).copy()
-        return int(f.fetch("trace_reused")[0]), out
-
-    def close(self):
-        for f in self.fields:
-            f.destroy()
-        self.eng.device_free(self.dDose)
-        self.eng.close()
+rig_of = rig_fixture(FieldRig)
 
 
-@pytest.fixture
-def rig_of(engine):
-    rigs = []
-
-    def make(scn, opt, **kw):
-        r = Rig(engine, scn, opt, **kw)
-        rigs.append(r)
-        return r
-    yield make
-    for r in rigs:
-        r.close()
+def _compute(rig, f, names=_FETCHED):
+    """One compute with a finish: (trace_reused, {dose, info, timing, the fetched arrays})."""
+    dose, info, timing = rig.compute(f)
+    out = {"info": info, "timing": timing, "dose": dose}
+    for nm in names:
+        out[nm] = f.fetch(nm).copy()
+    return int(f.fetch("trace_reused")[0]), out
 
 
 def _same(a, b, names=_FETCHED):
@@ -107,14 +41,14 @@ def _same(a, b, names=_FETCHED):
         np.testing.assert_array_equal(a[nm], b[nm], err_msg=nm)
 
 
-def _three_computes(rig, beam, monkeypatch, expect=(0, 1, 1), **env):
+def _three_computes(rig, beam, expect=(0, 1, 1), **env):
     """Three computes of one field with a finish in between, compared with each other and with a field that never reuses."""
-    f = rig.field(beam, monkeypatch, **env)
-    runs = [rig.compute(f) for _ in range(3)]
+    f = rig.field(beam, **env)
+    runs = [_compute(rig, f) for _ in range(3)]
     assert tuple(r for r, _ in runs) == tuple(expect)
     env = dict(env, RTD_NO_TRACE_REUSE="1")
-    g = rig.field(beam, monkeypatch, **env)
-    refs = [rig.compute(g) for _ in range(2)]
+    g = rig.field(beam, **env)
+    refs = [_compute(rig, g) for _ in range(2)]
     assert [r for r, _ in refs] == [0, 0]
     for _, out in runs + refs[1:]:
         _same(out, refs[0][1])
@@ -122,7 +56,7 @@ def _three_computes(rig, beam, monkeypatch, expect=(0, 1, 1), **env):
 
 
 @pytest.mark.parametrize("case", ["across", "diagonal", "along", "water", "missing"])
-def test_reused_equals_traced(rig_of, synth, monkeypatch, case):
+def test_reused_equals_traced(rig_of, synth, case):
     """The three sampling kernels (0 degrees; 37 degrees with a finite source distance; 90 degrees), the known-uniform path (water)
     and an empty field (the beam misses the volume)."""
     if case == "water":
@@ -131,9 +65,9 @@ def test_reused_equals_traced(rig_of, synth, monkeypatch, case):
         scn = _missing(synth)
     else:
         deg, dist = {"across": (0.0, (math.inf, math.inf)), "diagonal": (37.0, (2000.0, 2500.0)), "along": (90.0, (math.inf, math.inf))}[case]
-        scn = _hetero(synth, angle=deg, source_dist=dist)
-    rig = rig_of(scn, _opts())
-    out = _three_computes(rig, scn.beams[0], monkeypatch)
+        scn = hetero_scene(synth, 128, [deg], source_dist=dist, spots=7, pitch=6.0)
+    rig = rig_of(scn, options(1.0))
+    out = _three_computes(rig, scn.beams[0])
     if case == "water":
         assert out["info"]["uniform_sigma"] == 1 and out["dose"].max() > 0
     elif case == "missing":
@@ -142,36 +76,36 @@ def test_reused_equals_traced(rig_of, synth, monkeypatch, case):
         assert out["info"]["uniform_sigma"] == 0 and out["dose"].max() > 0
 
 
-def test_separate_ks_plan_reuses(rig_of, synth, monkeypatch):
+def test_separate_ks_plan_reuses(rig_of, synth):
     """RTD_SEPARATE_KS_PLAN moves the superposition's plan only: the trace is reused under it."""
-    scn = _hetero(synth, angle=20.0)
-    _three_computes(rig_of(scn, _opts()), scn.beams[0], monkeypatch, RTD_SEPARATE_KS_PLAN="1")
+    scn = hetero_scene(synth, 128, [20.0], spots=7, pitch=6.0)
+    _three_computes(rig_of(scn, options(1.0)), scn.beams[0], RTD_SEPARATE_KS_PLAN="1")
 
 
 @pytest.mark.parametrize("case", ["nuclear_corr", "rows_above_64", "RTD_SEPARATE_PLAN"])
-def test_fallback_configurations(rig_of, synth, monkeypatch, case):
+def test_fallback_configurations(rig_of, synth, case):
     """What falls back to the full sequence, deliberately: every compute traces (trace_reused = 0) and the results stand."""
     if case == "nuclear_corr":
         nl = luts.synth_luts(nuclear=True)
         scn = scenarios.water_cube(nl, n=64, n_layers=3, spots=7, pitch=6.0)
-        rig = rig_of(scn, _opts(nuclear=abi.RTD_NUC_SOUKUP))
-        _three_computes(rig, scn.beams[0], monkeypatch, expect=(0, 0, 0))
+        rig = rig_of(scn, options(1.0, nuclear=abi.RTD_NUC_SOUKUP))
+        _three_computes(rig, scn.beams[0], expect=(0, 0, 0))
     elif case == "rows_above_64":
-        scn = _hetero(synth, angle=0.0, spots=(5, 70), pitch=(8.0, 1.5), layers=2)
-        _three_computes(rig_of(scn, _opts()), scn.beams[0], monkeypatch, expect=(0, 0, 0))
+        scn = hetero_scene(synth, 128, [0.0], spots=(5, 70), pitch=(8.0, 1.5), layers=2)
+        _three_computes(rig_of(scn, options(1.0)), scn.beams[0], expect=(0, 0, 0))
     else:
-        scn = _hetero(synth, angle=0.0)
-        _three_computes(rig_of(scn, _opts()), scn.beams[0], monkeypatch, expect=(0, 0, 0), RTD_SEPARATE_PLAN="1")
+        scn = hetero_scene(synth, 128, [0.0], spots=7, pitch=6.0)
+        _three_computes(rig_of(scn, options(1.0)), scn.beams[0], expect=(0, 0, 0), RTD_SEPARATE_PLAN="1")
 
 
 @pytest.mark.parametrize("cutoff", [0.0, 1.0])
 def test_reweighting(rig_of, synth, cutoff):
     """After rtd_field_set_spot_weights the next compute reuses the trace and equals a fresh field with those weights."""
-    scn = _hetero(synth, angle=15.0)
+    scn = hetero_scene(synth, 128, [15.0], spots=7, pitch=6.0)
     b = scn.beams[0]
-    rig = rig_of(scn, _opts(cutoff))
+    rig = rig_of(scn, options(cutoff))
     f = rig.field(b)
-    assert rig.compute(f)[0] == 0
+    assert _compute(rig, f)[0] == 0
     w = (b.spotWeights * np.random.default_rng(9).random(b.spotWeights.shape)).astype(np.float32)
     w[:, :2, :] = 0.5                                                 # below a cut-off of 1: those rays die
     dW = rig.eng.device_alloc(w.nbytes)
@@ -182,21 +116,21 @@ def test_reweighting(rig_of, synth, cutoff):
         rig.eng.sync()
         rig.eng.device_free(dW)
     names = tuple(n for n in _FETCHED if n != "bev")                  # (slices outside [entry, passive) of a BEV buffer hold what earlier computes left)
-    reused, got = rig.compute(f, names)
+    reused, got = _compute(rig, f, names)
     assert reused == 1
-    r2, ref = rig.compute(rig.field(_with_weights(b, w)), names)
+    r2, ref = _compute(rig, rig.field(b.replace(spotWeights=w)), names)
     assert r2 == 0
     _same(got, ref, names)
-    assert not np.array_equal(got["dose"], rig.compute(rig.field(b), names)[1]["dose"])
+    assert not np.array_equal(got["dose"], _compute(rig, rig.field(b), names)[1]["dose"])
 
 
 @pytest.mark.parametrize("case", ["other_device_ct", "same_pointer", "set_luts", "set_options"])
 def test_invalidation(rig_of, synth, case):
     """Every rtd_set_ct*, LUT or options call drops the trace: the next compute traces again and equals a fresh field under the new
     inputs; the compute after it reuses again."""
-    scn = _hetero(synth, angle=10.0)
+    scn = hetero_scene(synth, 128, [10.0], spots=7, pitch=6.0)
     b = scn.beams[0]
-    rig = rig_of(scn, _opts(), set_ct=False)
+    rig = rig_of(scn, options(1.0), set_ct=False)
     n = scn.ct.size * 4
     ct2 = scn.ct.copy()
     ct2[:, :, : scn.ct.shape[2] // 2] *= 0.9                           # a lighter half: other WEPL, other entry sigma chain
@@ -206,8 +140,8 @@ def test_invalidation(rig_of, synth, case):
         rig.eng.to_device(dB, ct2)
         rig.eng.set_ct_device(dA, scn.dims)
         f = rig.field(b)
-        assert rig.compute(f)[0] == 0
-        r1, before = rig.compute(f)
+        assert _compute(rig, f)[0] == 0
+        r1, before = _compute(rig, f)
         assert r1 == 1
         changed = True
         if case == "other_device_ct":
@@ -220,21 +154,21 @@ def test_invalidation(rig_of, synth, case):
             rig.eng.set_luts(scn.luts)
             changed = False
         else:
-            rig.eng.set_options(_opts())                              # (a field keeps the options it was created under: the same values)
+            rig.eng.set_options(options(1.0))                              # (a field keeps the options it was created under: the same values)
             changed = False
         names = tuple(nm for nm in _FETCHED if nm != "bev")
-        r2, after = rig.compute(f, names)
+        r2, after = _compute(rig, f, names)
         assert r2 == 0
         fresh = rig.field(b)
-        r3, ref = rig.compute(fresh, names)
+        r3, ref = _compute(rig, fresh, names)
         assert r3 == 0
         _same(after, ref, names)
         assert changed == (not np.array_equal(after["wepl"], before["wepl"]))
         assert changed == (not np.array_equal(after["dose"], before["dose"]))
-        r4, again = rig.compute(f, names)
+        r4, again = _compute(rig, f, names)
         assert r4 == 1
         _same(again, ref, names)
-        r5, again = rig.compute(f, names)
+        r5, again = _compute(rig, f, names)
         assert r5 == 1
         _same(again, ref, names)
     finally:
@@ -246,16 +180,16 @@ def test_invalidation(rig_of, synth, case):
         rig.eng.device_free(dB)
 
 
-def test_dose_influence(rig_of, synth, monkeypatch):
+def test_dose_influence(rig_of, synth):
     """The matrix is the same with and without reuse (its batches are re-weighted computes of one field), and the field's state
     afterwards is that of a compute at its own weights."""
-    scn = _hetero(synth, n=96, angle=30.0, spots=5, pitch=8.0, layers=2)
+    scn = hetero_scene(synth, 96, [30.0], spots=5, pitch=8.0, layers=2)
     b = scn.beams[0]
-    rig = rig_of(scn, _opts(0.0))
+    rig = rig_of(scn, options(0.0))
     mats, states = [], []
     for env in ({}, {"RTD_NO_TRACE_REUSE": "1"}):
-        f = rig.field(b, monkeypatch, **env)
-        _, before = rig.compute(f)
+        f = rig.field(b, **env)
+        _, before = _compute(rig, f)
         d = f.dose_influence(0.0)
         assert d.nnz > 0
         assert int(f.fetch("trace_reused")[0]) == (0 if env else 1)   # (the restoring forward at the field's own weights)
@@ -275,11 +209,11 @@ def test_dose_influence(rig_of, synth, monkeypatch):
     _same(states[0], states[1])
 
 
-def test_gradient(rig_of, synth, monkeypatch):
+def test_gradient(rig_of, synth):
     """rtd_field_spot_gradient behind a reused forward equals the one behind a traced forward."""
-    scn = _hetero(synth, n=96, angle=30.0, spots=5, pitch=8.0, layers=2)
+    scn = hetero_scene(synth, 96, [30.0], spots=5, pitch=8.0, layers=2)
     b = scn.beams[0]
-    rig = rig_of(scn, _opts(0.0))
+    rig = rig_of(scn, options(0.0))
     g = (np.random.default_rng(2).random(rig.shape) - 0.5).astype(np.float32)
     dG = rig.eng.device_alloc(rig.nb)
     dOut = rig.eng.device_alloc(b.spotWeights.nbytes)
@@ -287,9 +221,9 @@ def test_gradient(rig_of, synth, monkeypatch):
     try:
         rig.eng.to_device(dG, g)
         for env, expect in (({}, 1), ({"RTD_NO_TRACE_REUSE": "1"}, 0)):
-            f = rig.field(b, monkeypatch, **env)
-            rig.compute(f)
-            assert rig.compute(f)[0] == expect
+            f = rig.field(b, **env)
+            _compute(rig, f)
+            assert _compute(rig, f)[0] == expect
             f.spot_gradient(dG, dOut)
             out = np.empty(b.spotWeights.shape, dtype=np.float32)
             rig.eng.to_host(out, dOut)
@@ -305,10 +239,10 @@ def test_gradient(rig_of, synth, monkeypatch):
 def test_timing_of_a_reused_compute(rig_of, synth):
     """No tracer stage; the six buckets still sum to total_ms (the 5 % rule of test_gpu_parity.py); all keys stay."""
     scn = scenarios.water_cube(synth, n=128, n_layers=4, spots=17, pitch=4.0)
-    rig = rig_of(scn, _opts(timing=1))
+    rig = rig_of(scn, options(1.0, timing=1))
     f = rig.field(scn.beams[0])
-    r0, first = rig.compute(f, ())
-    r1, second = rig.compute(f, ())
+    r0, first = _compute(rig, f, ())
+    r1, second = _compute(rig, f, ())
     assert (r0, r1) == (0, 1)
     assert first["timing"]["raytracing_ms"] > 0
     t = second["timing"]
@@ -323,16 +257,16 @@ def test_timing_of_a_reused_compute(rig_of, synth):
 def test_two_streams(rig_of, synth):
     """Computed on stream A, finished, then on stream B: the second compute reuses what the first one left, with identical results."""
     import torch
-    scn = _hetero(synth, angle=37.0, source_dist=(2000.0, 2500.0))
-    rig = rig_of(scn, _opts())
+    scn = hetero_scene(synth, 128, [37.0], source_dist=(2000.0, 2500.0), spots=7, pitch=6.0)
+    rig = rig_of(scn, options(1.0))
     dev = torch.device("cuda", 0)
     sa, sb = torch.cuda.Stream(device=dev), torch.cuda.Stream(device=dev)
     f = rig.field(scn.beams[0])
     try:
         rig.eng.set_stream(sa.cuda_stream)
-        ra, a = rig.compute(f)
+        ra, a = _compute(rig, f)
         rig.eng.set_stream(sb.cuda_stream)
-        rb, b = rig.compute(f)
+        rb, b = _compute(rig, f)
     finally:
         rig.eng.sync()
         rig.eng.set_stream(0)                                         # (the handle's own stream)

@@ -8,7 +8,6 @@ some order, so |gpu - ref| <= N * 2^-52 * ref; the objective adds T terms more. 
 a float64 sum of at most 64 separately rounded products: 64 * 2^-52 * sum_t |c_t x_t| covers any order and both sides."""
 import ctypes as C
 import math
-import os
 
 import numpy as np
 import pytest
@@ -16,9 +15,9 @@ import pytest
 import optimizer_reference as R
 import robust_reference as Q
 import voxelwise_reference as V
+from gpu_plan_rigs import RobustRig, same
+from gpu_support import bits, hetero_scene, switches
 from raytracedicom_amd import abi
-from test_gpu_optimizer import _bits, _hetero
-from test_gpu_robust import RobustRig, _same
 
 pytestmark = pytest.mark.gpu
 
@@ -101,11 +100,11 @@ def test_eval_voxelwise_against_the_restatement(case, S):
     values, active, g = case.eval(d)
     rv, G, ractive, Gabs = V.eval_voxelwise(case.ref, d)
     union = case.ref.union()
-    assert union.sum() == 982 and np.all(_bits(g)[:, ~union] == SENTINEL)              # nothing is written outside the union
-    assert not np.any(_bits(g)[:, union] == SENTINEL)                                  # and all S volumes at every voxel of it
+    assert union.sum() == 982 and np.all(bits(g)[:, ~union] == SENTINEL)              # nothing is written outside the union
+    assert not np.any(bits(g)[:, union] == SENTINEL)                                  # and all S volumes at every voxel of it
     g32 = G.astype(np.float32)
     assert np.array_equal(g[:, union] != 0, g32[:, union] != 0) and not g32[:, ~union].any()
-    assert np.all(_bits(g)[:, union][g[:, union] == 0] == 0)                           # what is not received is +0
+    assert np.all(bits(g)[:, union][g[:, union] == 0] == 0)                           # what is not received is +0
     assert active == ractive and active == sum(1 << s for s in range(S) if np.any(g[s][union] != 0))
     lo, s_lo, hi, s_hi = V.extremes(d)
     if S > 1:
@@ -132,7 +131,7 @@ def test_eval_voxelwise_against_the_restatement(case, S):
     if S == 1:                                                                         # one scenario: rtd_objective_eval to the bit
         case.eng.to_device(case.dG[1], np.full(NVOX, SENTINEL, dtype=np.uint32))
         plain = case.obj.eval(case.dD[0], case.dG[1])
-        assert np.array_equal(_bits(plain), _bits(values)) and np.array_equal(_bits(case.fetch(case.dG[1])), _bits(g[0]))
+        assert np.array_equal(bits(plain), bits(values)) and np.array_equal(bits(case.fetch(case.dG[1])), bits(g[0]))
     else:                                                                              # the composite is at least every scenario's own value
         fs = np.array([case.ref.eval(d[s])[0][0] for s in range(S)])
         assert np.all(values[0] >= fs * (1.0 - 600 * 2.0 ** -52))
@@ -148,7 +147,7 @@ def test_eval_voxelwise_with_a_nan(case, S):
     assert math.isnan(g[s][NAN_AT]) and not np.delete(g[:, NAN_AT], s).any()
     assert np.array_equal(np.isnan(values), np.isnan(rv)) and np.isnan(values[1:]).sum() == 4    # the four terms of ROI 0 and ROI 1
     union = case.ref.union()
-    assert np.array_equal(g[:, union] != 0, G.astype(np.float32)[:, union] != 0) and np.all(_bits(g)[:, ~union] == SENTINEL)
+    assert np.array_equal(g[:, union] != 0, G.astype(np.float32)[:, union] != 0) and np.all(bits(g)[:, ~union] == SENTINEL)
 
 
 @pytest.mark.parametrize("S", [1, 2, 5, 32])
@@ -160,9 +159,9 @@ def test_dose_extremes(case, S):
             case.eng.to_device(p, np.full(NVOX, SENTINEL, dtype=np.uint32))
         case.eng.dose_extremes(case.dD[:S], NVOX, case.dLo, case.dHi)
         lo, s_lo, hi, s_hi = V.extremes(d)
-        assert np.array_equal(_bits(case.fetch(case.dLo)), _bits(lo)) and np.array_equal(_bits(case.fetch(case.dHi)), _bits(hi))
+        assert np.array_equal(bits(case.fetch(case.dLo)), bits(lo)) and np.array_equal(bits(case.fetch(case.dHi)), bits(hi))
         if nan:
-            assert _bits(lo)[NAN_AT] == NAN_BITS and _bits(hi)[NAN_AT] == NAN_BITS
+            assert bits(lo)[NAN_AT] == NAN_BITS and bits(hi)[NAN_AT] == NAN_BITS
         assert np.signbit(lo[ZEROS]) and np.signbit(hi[ZEROS])
     # either output may be NULL; a shorter range leaves the rest alone
     for p in (case.dLo, case.dHi):
@@ -170,8 +169,8 @@ def test_dose_extremes(case, S):
     case.eng.dose_extremes(case.dD[:S], 300, None, case.dHi)
     case.eng.dose_extremes(case.dD[:S], 257, case.dLo, None)
     got_lo, got_hi = case.fetch(case.dLo), case.fetch(case.dHi)
-    assert np.array_equal(_bits(got_hi)[:300], _bits(hi)[:300]) and np.all(_bits(got_hi)[300:] == SENTINEL)
-    assert np.array_equal(_bits(got_lo)[:257], _bits(lo)[:257]) and np.all(_bits(got_lo)[257:] == SENTINEL)
+    assert np.array_equal(bits(got_hi)[:300], bits(hi)[:300]) and np.all(bits(got_hi)[300:] == SENTINEL)
+    assert np.array_equal(bits(got_lo)[:257], bits(lo)[:257]) and np.all(bits(got_lo)[257:] == SENTINEL)
 
 
 def test_eval_and_extremes_capture(case):
@@ -202,22 +201,18 @@ def test_eval_and_extremes_capture(case):
         torch.cuda.synchronize()
     finally:
         case.eng.set_stream(None)
-    assert np.array_equal(_bits(case.fetch(case.dV, np.float64, 1 + len(TERMS))), _bits(values))
+    assert np.array_equal(bits(case.fetch(case.dV, np.float64, 1 + len(TERMS))), bits(values))
     assert int(case.fetch(case.dA, np.uint32, 1)[0]) == active
-    assert np.array_equal(_bits(np.stack([case.fetch(case.dG[k]) for k in range(S)])), _bits(g))
-    assert np.array_equal(_bits(case.fetch(case.dLo)), _bits(lo)) and np.array_equal(_bits(case.fetch(case.dHi)), _bits(hi))
+    assert np.array_equal(bits(np.stack([case.fetch(case.dG[k]) for k in range(S)])), bits(g))
+    assert np.array_equal(bits(case.fetch(case.dLo)), bits(lo)) and np.array_equal(bits(case.fetch(case.dHi)), bits(hi))
 
 
 # ---- the optimiser ----
 
 def _vox(rig, start=None, scen=None, obj=None, no_batch=False):
     sf = rig.sfields if scen is None else [rig.sfields[s] for s in scen]
-    if no_batch:
-        os.environ["RTD_ROBUST_NO_BATCH"] = "1"
-    try:
+    with switches(**({"RTD_ROBUST_NO_BATCH": "1"} if no_batch else {})):
         o = rig.eng.create_voxelwise_optimizer(sf, rig.obj if obj is None else obj)
-    finally:
-        os.environ.pop("RTD_ROBUST_NO_BATCH", None)
     rig.opts.append(o)
     if start is not None:
         rig.set_weights(o, start)
@@ -234,7 +229,7 @@ def _retire(rig):
 @pytest.fixture(scope="module")
 def rig2(engine, synth):
     """Two crossing fields, five scenarios."""
-    r = RobustRig(engine, _hetero(synth, angles=(0.0, 90.0)))
+    r = RobustRig(engine, hetero_scene(synth, 96, (0.0, 90.0)))
     yield r
     r.close()
 
@@ -242,7 +237,7 @@ def rig2(engine, synth):
 @pytest.fixture(scope="module")
 def rig1(engine, synth):
     """One field, five scenarios."""
-    r = RobustRig(engine, _hetero(synth, angles=(0.0,)))
+    r = RobustRig(engine, hetero_scene(synth, 96, (0.0,)))
     yield r
     r.close()
 
@@ -256,9 +251,9 @@ def test_one_scenario_is_the_plain_optimiser(rig2):
         one = _vox(rig, scen=[0])
         plain.run(10)
         one.run(10)
-        rep, hist = _same(rig, plain, one)
+        rep, hist = same(rig, plain, one)
         assert rep["iterations"] == 10 and hist.size == 10 and np.all(np.isfinite(hist)) and hist.min() < hist[0]
-        assert np.array_equal(_bits(rig.volume(plain.dose())), _bits(rig.volume(one.dose())))
+        assert np.array_equal(bits(rig.volume(plain.dose())), bits(rig.volume(one.dose())))
         v, l, worst = one.scenario_values()
         assert v.size == 1 and v[0] == rep["f_last"] and l[0] == 1.0 and worst == 0 and one.scenario_dose(0) == one.dose()
     finally:
@@ -287,15 +282,15 @@ def test_the_iteration_against_the_restatement(rig2):
             d = np.stack([rig.volume(p) for p in ptrs])
             for s in range(S):
                 rig.scenario_dose_of(s, ws, dDose)
-                assert d[s].max() > 0 and np.array_equal(_bits(d[s]), _bits(rig.volume(dDose))), (k, s)
+                assert d[s].max() > 0 and np.array_equal(bits(d[s]), bits(rig.volume(dDose))), (k, s)
             values, active = rig.obj.eval_voxelwise(ptrs, dG)
             g = np.stack([rig.volume(p) for p in dG])
             rv, G, ractive, _ = V.eval_voxelwise(rig.ref, d)
             assert active == ractive and np.array_equal(g != 0, G.astype(np.float32) != 0)
             assert abs(values[0] - rv[0]) <= (rig.nvox + 4) * 2.0 ** -52 * rv[0]
             f_ref, lam_ref, worst_ref = V.decide(values[0], active, S)
-            assert np.array_equal(_bits(f_ref), _bits(vals)) and np.array_equal(_bits(lam_ref), _bits(lam)) and worst_ref == worst
-            assert _bits(np.array([values[0]]))[0] == _bits(hist[k:k + 1])[0] and hist[k] == rep["f_last"] and rep["guarded"] == 0
+            assert np.array_equal(bits(f_ref), bits(vals)) and np.array_equal(bits(lam_ref), bits(lam)) and worst_ref == worst
+            assert bits(np.array([values[0]]))[0] == bits(hist[k:k + 1])[0] and hist[k] == rep["f_last"] and rep["guarded"] == 0
             grads = []
             for s in range(S):
                 out = []
@@ -312,7 +307,7 @@ def test_the_iteration_against_the_restatement(rig2):
             assert bin(active).count("1") >= 2                             # more than one scenario supplies an extreme somewhere
             assert a_ref > 0 and rep["step"] == a_ref
             w_new = rig.all_weights(opt)
-            assert np.array_equal(_bits(w_new), _bits(R.update(w, grad, rep["step"]))) and not np.array_equal(w_new, w)
+            assert np.array_equal(bits(w_new), bits(R.update(w, grad, rep["step"]))) and not np.array_equal(w_new, w)
             w_prev, grad_prev = w, grad
     finally:
         _retire(rig)
@@ -325,12 +320,12 @@ def test_batched_equals_unbatched(rig2):
         a, b = _vox(rig, start=0.0), _vox(rig, start=0.0, no_batch=True)
         a.run(12)
         b.run(12)
-        rep, hist = _same(rig, a, b)
+        rep, hist = same(rig, a, b)
         assert rep["iterations"] == 12 and np.all(np.isfinite(hist)) and rep["f_best"] < hist[0]
         va, vb = a.scenario_values(), b.scenario_values()
-        assert np.array_equal(_bits(va[0]), _bits(vb[0])) and np.array_equal(_bits(va[1]), _bits(vb[1])) and va[2] == vb[2]
+        assert np.array_equal(bits(va[0]), bits(vb[0])) and np.array_equal(bits(va[1]), bits(vb[1])) and va[2] == vb[2]
         for s in range(rig.S):
-            assert np.array_equal(_bits(rig.volume(a.scenario_dose(s))), _bits(rig.volume(b.scenario_dose(s))))
+            assert np.array_equal(bits(rig.volume(a.scenario_dose(s))), bits(rig.volume(b.scenario_dose(s))))
     finally:
         _retire(rig)
 
@@ -347,13 +342,13 @@ def test_reproducible_and_capturable(engine, synth, rig1):
         for _ in range(3):
             b.run(10)
             b.run(0)
-        ra, ha = _same(rig, a, b)
+        ra, ha = same(rig, a, b)
         assert ha.size == 30
-        other = RobustRig(engine, _hetero(synth, angles=(0.0,)))
+        other = RobustRig(engine, hetero_scene(synth, 96, (0.0,)))
         c = _vox(other, start=0.0)
         c.run(30)
         rc, hc = c.result()
-        assert rc == ra and np.array_equal(_bits(hc), _bits(ha))
+        assert rc == ra and np.array_equal(bits(hc), bits(ha))
         direct, captured = _vox(rig, start=0.0), _vox(rig, start=0.0)
         s = torch.cuda.Stream()
         torch.cuda.synchronize()
@@ -372,8 +367,8 @@ def test_reproducible_and_capturable(engine, synth, rig1):
             rg, hg = captured.result()
         finally:
             rig.eng.set_stream(None)
-        assert rd == rg and hd.size == 5 and np.array_equal(_bits(hd), _bits(hg)) and np.array_equal(_bits(hd), _bits(ha[:5]))
-        assert np.array_equal(_bits(rig.weights(direct)[0]), _bits(rig.weights(captured)[0]))
+        assert rd == rg and hd.size == 5 and np.array_equal(bits(hd), bits(hg)) and np.array_equal(bits(hd), bits(ha[:5]))
+        assert np.array_equal(bits(rig.weights(direct)[0]), bits(rig.weights(captured)[0]))
     finally:
         _retire(rig)
         if other is not None:
@@ -382,7 +377,7 @@ def test_reproducible_and_capturable(engine, synth, rig1):
 
 def test_guard(engine, synth):
     """Weights of +inf give an F that is not finite: the guard is taken, the next iterate is w_best and reproduces F_best bit for bit."""
-    rig = RobustRig(engine, _hetero(synth, n=64, angles=(0.0,), spots=3, layers=1))
+    rig = RobustRig(engine, hetero_scene(synth, 64, (0.0,), spots=3, layers=1))
     try:
         opt = _vox(rig)
         opt.run(5)
@@ -393,7 +388,7 @@ def test_guard(engine, synth):
         opt.run(2)
         r7, h7 = opt.result()
         assert not math.isfinite(h7[5]) and r7["guarded"] == 1 and h7[6] == r7["f_best"] == r5["f_best"] and math.isfinite(r7["step"])
-        assert np.array_equal(_bits(rig.weights(opt, best=True)[0]), _bits(best5))
+        assert np.array_equal(bits(rig.weights(opt, best=True)[0]), bits(best5))
         vals, lam, worst = opt.scenario_values()
         assert np.all(vals == h7[6]) and lam[worst] == 1.0
         opt.run(3)
@@ -454,7 +449,7 @@ def test_the_point_of_it(rig1):
 
 def test_refusals(engine, synth):
     L = engine.lib()
-    scn = _hetero(synth, n=64, angles=(0.0, 90.0), spots=3, layers=1)
+    scn = hetero_scene(synth, 64, (0.0, 90.0), spots=3, layers=1)
     rig = RobustRig(engine, scn)
     try:
         eng, h = rig.eng, rig.eng._h
@@ -498,7 +493,7 @@ def test_refusals(engine, synth):
         remote = eng.create_field(scn.beams[0], rig.dims, remote=True)
         coarse = eng.create_field(scn.beams[0], (32, 32, 32))
         coarse.dose_influence()
-        other_shape = eng.create_field(_hetero(synth, n=64, angles=(0.0,), spots=4, layers=1).beams[0], rig.dims)
+        other_shape = eng.create_field(hetero_scene(synth, 64, (0.0,), spots=4, layers=1).beams[0], rig.dims)
         other_shape.dose_influence()
         f = rig.sfields
         arr = lambda *fs: (C.c_void_p * 80)(*[x._h for x in fs])   # noqa: E731
