@@ -903,6 +903,79 @@ int rtd_field_project_target(rtd_handle h, rtd_field f, const uint8_t* dev_mask,
 int rtd_field_select_spots(rtd_handle h, rtd_field f, const rtd_target_options* opt, uint8_t* dev_spot_mask, uint32_t* n_selected);
 
 /*
+ * ---- Gamma index of two dose volumes ----
+ *
+ * Additive to the blocks above (RTD_ABI_VERSION stays 3). The comparison of an evaluated dose with a reference dose on one grid: per
+ * reference voxel the smallest combined distance / dose-difference measure over a search cube, with the evaluated dose interpolated
+ * between grid nodes when asked. Both volumes, the optional mask and map and the result record live on the handle's device; volumes are
+ * x fastest, dims and spacing_mm are (x, y, z). Every number below is a float32 operation in the stated order, each product, quotient,
+ * sum and difference rounded, nothing contracted; `/` and sqrtf are correctly rounded, the minimum and the maximum are order-free and
+ * all counting is integer: the same inputs give the same bits across calls, handles and processes, and the rule can be restated in a
+ * few lines (tests/gamma_reference.py does).
+ *
+ * Normalisation. norm = norm_dose if that is > 0, otherwise the largest ref[v] over the WHOLE grid (not only the mask), starting from
+ *     0.0f. thr = threshold_fraction * norm, dd_global = dd_fraction * norm. If !(norm > 0): n_evaluated = n_passed = 0, max_gamma = 0
+ *     and every voxel of the map is -1.0f.
+ * Radii. r_a = (int)ceilf(search_mult * dta_mm / spacing_mm[a]) per axis a, at most RTD_GAMMA_MAX_RADIUS. With k = interp the offsets
+ *     are the integers i_a in [-k r_a, k r_a], in units of spacing_mm[a] / (float)k.
+ * Evaluated voxels. v is evaluated iff ref[v] >= thr, and dev_mask is NULL or dev_mask[v] != 0 (a byte mask as rtd_roi_fill_mask
+ *     writes it: a pass rate per structure is one call), and ref[v] > 0 when local is set.
+ * Sample of voxel v = (v_x, v_y, v_z) at offset (i_x, i_y, i_z). Per axis: b = floor_div(i, k), t = (float)(i - b k) / (float)k (exact:
+ *     k is a power of two), p = v_a + b. The sample is skipped if p < 0 or p > n_a - 1, or if p == n_a - 1 and t != 0. The upper
+ *     neighbour is node min(p + 1, n_a - 1). e = the trilinear blend of the 8 nodes of eval, each blend a + t * (b - a) (one difference,
+ *     one product, one sum), along x, then along y, then along z; with k = 1 every t is 0 and e is the node's value.
+ *         o_a   = (float)i_a * (spacing_mm[a] / (float)k)
+ *         dist2 = (o_x * o_x + o_y * o_y) + o_z * o_z
+ *         dv    = e - r,  r = ref[v]            dd = dd_global, or dd_fraction * r when local is set
+ *         g2    = dist2 / (dta_mm * dta_mm) + (dv * dv) / (dd * dd)
+ * Gamma. best = the smallest g2 over the samples that are not skipped (the one at offset 0 never is), gamma = sqrtf(best); the voxel
+ *     passes iff gamma <= 1.0f. max_gamma = the largest gamma (0 when nothing is evaluated).
+ * With k = 1, search_mult = 1.5, no mask, global and norm_dose = 0 this is the plain node-by-node search of the test suite's CPU
+ * checker, operation for operation. Inputs are finite doses; what non-finite input yields is unspecified, but nothing faults.
+ *
+ * rtd_default_gamma_options   1 % / 1 mm above 10 %, search_mult 1.5, global, norm_dose 0, interp 1.
+ * rtd_dose_gamma              asynchronous on the handle's stream: clears *dev_result, then launches only — no allocation after the
+ *                             first call, no copy, no host synchronisation (it can be captured into a graph, like the DVH calls; a
+ *                             captured call is not timed). dev_gamma_map (or NULL): dims[0] dims[1] dims[2] floats, EVERY one written:
+ *                             gamma where evaluated, -1.0f elsewhere. *dev_result: the counts, max_gamma and the norm that was used;
+ *                             the pass rate is n_passed / n_evaluated.
+ * rtd_dose_gamma_kernel_ms    the time of the search kernel of the handle's last rtd_dose_gamma (hipEvents on the handle's stream; it
+ *                             waits for that kernel), for reports. RTD_ERR_NOT_READY before any call.
+ *
+ * Kernels (rtd_gamma.hpp): the grid maximum by an integer atomicMax on the float's bit pattern (doses are not negative); the search by
+ * bricks of 32 x 4 x 4 reference voxels, one per lane, over a tile of eval with its halo staged in LDS once, the offsets visited in
+ * growing distance per axis and left, per wave, once the distance term alone rules out an improvement for every lane (this cannot change
+ * a minimum). Counts: ballots and popcounts kept in registers while a block walks its bricks, then per block one 64-bit integer atomicAdd per
+ * counter and an integer atomicMax on the bit pattern of its largest gamma. No float atomics. Environment: RTD_GAMMA_NAIVE (read by rtd_create) selects the plain second implementation — one lane per voxel, the
+ * nested loops above over global memory, no pruning — which gives the same bits.
+ *
+ * RTD_ERR_INVALID_ARG, after which nothing has been written: a null h, dev_ref, dev_eval, dims, spacing_mm, opt or dev_result; a zero
+ * dim; a spacing, dd_fraction, dta_mm or search_mult that is not > 0 (and finite); threshold_fraction < 0; norm_dose < 0; interp not in
+ * {1, 2, 4, 8}; local > 1; a non-zero reserved word; a radius above RTD_GAMMA_MAX_RADIUS.
+ */
+#define RTD_GAMMA_MAX_RADIUS 10u   /* search radius in grid nodes, per axis */
+typedef struct rtd_gamma_options {
+    float    dd_fraction;         /* 0.01 */
+    float    dta_mm;              /* 1.0 */
+    float    threshold_fraction;  /* 0.10 */
+    float    search_mult;         /* 1.5: the search cube reaches search_mult * dta */
+    float    norm_dose;           /* 0: max(ref) found on the device; > 0: this dose normalises dd and the threshold */
+    uint32_t local;               /* 0 global: dd = dd_fraction * norm; 1 local: dd = dd_fraction * ref[v] */
+    uint32_t interp;              /* 1, 2, 4 or 8 samples per grid step of the evaluated dose */
+    uint32_t reserved[5];         /* zero */
+} rtd_gamma_options;              /* 48 bytes */
+typedef struct rtd_gamma_result { /* lives on the DEVICE */
+    uint64_t n_evaluated, n_passed;
+    float    max_gamma, norm_dose;
+    uint32_t reserved[2];
+} rtd_gamma_result;               /* 32 bytes */
+void rtd_default_gamma_options(rtd_gamma_options* out);
+int rtd_dose_gamma(rtd_handle h, const float* dev_ref, const float* dev_eval, const uint32_t dims[3], const float spacing_mm[3],
+                   const rtd_gamma_options* opt, const uint8_t* dev_mask /* or NULL */, float* dev_gamma_map /* or NULL */,
+                   rtd_gamma_result* dev_result);
+int rtd_dose_gamma_kernel_ms(rtd_handle h, float* ms);   /* the search kernel of the last call, as rtd_roi_kernel_ms */
+
+/*
  * ---- Multi-GPU plans behind the boundary (SURVEY.md 8(b) "Threading": one handle and one host thread per device) ----
  *
  * rtd_plan is the reference-shaped call on several GPUs of one process: the 4-beam cudaWrapperProtons of the C++ shim uses

@@ -175,6 +175,34 @@ class RtdTargetOptions(C.Structure):
                 ("reserved", C.c_int32 * 5)]
 
 
+class RtdGammaOptions(C.Structure):
+    _fields_ = [("dd_fraction", C.c_float), ("dta_mm", C.c_float), ("threshold_fraction", C.c_float), ("search_mult", C.c_float),
+                ("norm_dose", C.c_float), ("local", C.c_uint32), ("interp", C.c_uint32), ("reserved", C.c_uint32 * 5)]
+
+
+class RtdGammaResult(C.Structure):
+    _fields_ = [("n_evaluated", C.c_uint64), ("n_passed", C.c_uint64), ("max_gamma", C.c_float), ("norm_dose", C.c_float),
+                ("reserved", C.c_uint32 * 2)]
+
+    def as_dict(self):
+        return {"n_evaluated": int(self.n_evaluated), "n_passed": int(self.n_passed), "max_gamma": float(self.max_gamma),
+                "norm_dose": float(self.norm_dose)}
+
+
+RTD_GAMMA_MAX_RADIUS = 10
+
+
+def default_gamma_options():
+    """rtd_default_gamma_options: 1 % / 1 mm above 10 % of max(ref), global, node samples only."""
+    o = RtdGammaOptions()
+    o.dd_fraction = 0.01
+    o.dta_mm = 1.0
+    o.threshold_fraction = 0.10
+    o.search_mult = 1.5
+    o.interp = 1
+    return o
+
+
 def default_optimizer_options():
     """rtd_default_optimizer_options: the step bounds only keep the Barzilai-Borwein step finite."""
     o = RtdOptimizerOptions()

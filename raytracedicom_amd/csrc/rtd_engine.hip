@@ -45,6 +45,7 @@
 #include "rtd_voxelwise.hpp"
 #include "rtd_roi.hpp"
 #include "rtd_target.hpp"
+#include "rtd_gamma.hpp"
 #include "rtd_engine_impl.hpp"
 
 namespace {
@@ -147,6 +148,7 @@ int rtd_create(int device_id, rtd_handle* out) {
         return RTD_ERR_HIP;
     }
     h->stream = h->ownStream;
+    h->gammaNaive = std::getenv("RTD_GAMMA_NAIVE") != nullptr;
     if (hipDeviceGetAttribute(&h->numCUs, hipDeviceAttributeMultiprocessorCount, device_id) != hipSuccess || h->numCUs <= 0) h->numCUs = 256;
     *out = reinterpret_cast<rtd_handle>(h);
     return RTD_OK;
@@ -159,6 +161,7 @@ int rtd_destroy(rtd_handle hh) {
     (void)hipStreamSynchronize(h->stream);
     while (!h->fieldCache.empty()) { rtd_field_impl* c = h->fieldCache.back(); h->fieldCache.pop_back(); rtd_field_destroy(hh, reinterpret_cast<rtd_field>(c)); }
     h->clearCtBoxes();
+    for (hipEvent_t e : h->gammaEv) if (e) (void)hipEventDestroy(e);
     if (h->dLutBlock) (void)hipFree(h->dLutBlock);
     if (h->dCtOwned) (void)hipFree(h->dCtOwned);
     if (h->ownStream) (void)hipStreamDestroy(h->ownStream);
@@ -1348,3 +1351,4 @@ int rtd_compute(rtd_handle hh, const rtd_beam* beams, int n_beams, float* dose_i
 #include "rtd_optimizer_host.hpp"
 #include "rtd_roi_host.hpp"
 #include "rtd_target_host.hpp"
+#include "rtd_gamma_host.hpp"

@@ -35,6 +35,10 @@ struct rtd_handle_impl {
     struct CtBox { std::array<int, 6> box; hipEvent_t done; hipStream_t stream; };
     std::vector<CtBox> ctBoxes;                    // boxes of ctHost already on the device (x0, y0, z0, x1, y1, z1 inclusive), each with the
                                                    // event of its upload and the stream it was issued on (a consumer on another stream waits for it)
+    // rtd_dose_gamma (rtd_gamma_host.hpp)
+    bool gammaNaive = false;                       // RTD_GAMMA_NAIVE, read when the handle is created: the plain second implementation
+    hipEvent_t gammaEv[2] = {};                    // around the search kernel of the last call that was not captured (created by the first call)
+    bool gammaTimed = false;                       // ... and such a call has been made
     void clearCtBoxes() { for (auto& b : ctBoxes) if (b.done) (void)hipEventDestroy(b.done); ctBoxes.clear(); }
 };
 

@@ -118,6 +118,10 @@ def lib():
         L.rtd_roi_destroy.argtypes = [vp, vp]
         L.rtd_field_project_target.argtypes = [vp, vp, vp, C.POINTER(abi.RtdTargetInfo)]
         L.rtd_field_select_spots.argtypes = [vp, vp, C.POINTER(abi.RtdTargetOptions), vp, C.POINTER(C.c_uint32)]
+        L.rtd_default_gamma_options.argtypes = [C.POINTER(abi.RtdGammaOptions)]
+        L.rtd_default_gamma_options.restype = None
+        L.rtd_dose_gamma.argtypes = [vp, vp, vp, u3, C.POINTER(C.c_float), C.POINTER(abi.RtdGammaOptions), vp, vp, vp]
+        L.rtd_dose_gamma_kernel_ms.argtypes = [vp, C.POINTER(C.c_float)]
         L.rtd_host_register.argtypes = [vp, C.c_size_t]
         L.rtd_host_unregister.argtypes = [vp]
         L.rtd_plan_create.argtypes = [C.POINTER(C.c_int), C.c_int, vpp]
@@ -777,6 +781,77 @@ class Engine:
         arr = (C.c_void_p * len(fields))(*[f._h for f in fields])
         lo, hi = Field._clip(box_min, box_max)
         self._check(lib().rtd_fields_transfer_init(self._h, arr, len(fields), C.c_void_p(int(dev_dose)), lo, hi))
+
+    _GAMMA_NAMES = {"dd": "dd_fraction", "dta": "dta_mm", "threshold": "threshold_fraction"}
+
+    def gamma_device(self, ref_ptr, eval_ptr, dims, spacing, result_ptr, *, mask=None, gamma_map=None, opt=None, **options):
+        """rtd_dose_gamma: the gamma index of the device volume eval_ptr against ref_ptr (float32, dims (x, y, z), spacing (x, y, z) mm)
+        into the 32-byte device record result_ptr (abi.RtdGammaResult); asynchronous. mask: device bytes, non-zero = evaluate;
+        gamma_map: device floats, every one written (-1 where nothing is evaluated). options: the fields of abi.RtdGammaOptions over
+        their defaults (dd, dta and threshold are short for dd_fraction, dta_mm and threshold_fraction), or a whole record as opt."""
+        if opt is None:
+            opt = abi.RtdGammaOptions()
+            lib().rtd_default_gamma_options(C.byref(opt))
+        for k, val in options.items():
+            name = self._GAMMA_NAMES.get(k, k)
+            if name not in ("dd_fraction", "dta_mm", "threshold_fraction", "search_mult", "norm_dose", "local", "interp"):
+                raise TypeError("gamma_device: unknown option %r" % k)
+            setattr(opt, name, int(val) if name in ("local", "interp") else float(val))
+        sp = (C.c_float * 3)(*[float(s) for s in spacing])
+        self._check(lib().rtd_dose_gamma(self._h, C.c_void_p(int(ref_ptr)), C.c_void_p(int(eval_ptr)), abi.uint3(dims), sp, C.byref(opt),
+                                         C.c_void_p(int(mask)) if mask else None, C.c_void_p(int(gamma_map)) if gamma_map else None,
+                                         C.c_void_p(int(result_ptr))))
+
+    def gamma(self, ref, ev, spacing, dd=0.01, dta=1.0, threshold=0.10, *, local=False, interp=1, norm_dose=0.0, search_mult=1.5, mask=None,
+              want_map=False):
+        """The gamma(dd, dta mm) index of the host volume ev against ref ([Z][Y][X] float32, spacing (x, y, z) mm) above
+        threshold * norm, on the device -> (pass_rate, n_evaluated, max_gamma) (what the CPU checker of the tests returns), and the map
+        ([Z][Y][X] float32, -1 where nothing is evaluated) as a fourth entry with want_map. mask: a [Z][Y][X] array, non-zero = evaluate.
+        pass_rate is 1.0 when nothing is evaluated."""
+        ref, ev = abi.f32(ref), abi.f32(ev)
+        assert ref.ndim == 3 and ref.shape == ev.shape
+        dims = (ref.shape[2], ref.shape[1], ref.shape[0])
+        bufs = []
+
+        def up(a):
+            p = self.device_alloc(a.nbytes)
+            bufs.append(p)
+            self.to_device(p, a)
+            return p
+        try:
+            d_ref, d_ev = up(ref), up(ev)
+            d_mask = None
+            if mask is not None:
+                m = np.ascontiguousarray(np.asarray(mask) != 0, dtype=np.uint8)
+                assert m.shape == ref.shape
+                d_mask = up(m)
+            d_map = None
+            if want_map:
+                d_map = self.device_alloc(ref.nbytes)
+                bufs.append(d_map)
+            d_res = self.device_alloc(C.sizeof(abi.RtdGammaResult))
+            bufs.append(d_res)
+            self.gamma_device(d_ref, d_ev, dims, spacing, d_res, mask=d_mask, gamma_map=d_map, dd=dd, dta=dta, threshold=threshold,
+                              local=bool(local), interp=interp, norm_dose=norm_dose, search_mult=search_mult)
+            res = abi.RtdGammaResult()
+            self._check(lib().rtd_copy_to_host(self._h, C.byref(res), C.c_void_p(d_res), C.sizeof(res)))
+            n, n_pass = int(res.n_evaluated), int(res.n_passed)
+            out = (n_pass / n if n else 1.0, n, float(res.max_gamma))
+            if want_map:
+                gmap = np.empty(ref.shape, dtype=np.float32)
+                self.to_host(gmap, d_map)
+                out = out + (gmap,)
+            return out
+        finally:
+            self.sync()
+            for p in bufs:
+                self.device_free(p)
+
+    def gamma_kernel_ms(self):
+        """rtd_dose_gamma_kernel_ms: the search kernel of the last gamma / gamma_device call, in ms (waits for it)."""
+        ms = C.c_float(0)
+        self._check(lib().rtd_dose_gamma_kernel_ms(self._h, C.byref(ms)))
+        return float(ms.value)
 
     # device buffers owned by the handle
     def device_alloc(self, nbytes):
