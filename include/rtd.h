@@ -225,6 +225,17 @@ int rtd_compute(rtd_handle h, const rtd_beam* beams, int n_beams, float* dose_in
  * place must be announced (rtd_set_ct_device above). Not kept: across rtd_field_release; with nuclear_corr; for spot maps of more
  * than 64 rows; by launches into a capturing stream (a graph holds the full sequence). rtd_timing of such a compute: raytracing_ms
  * = 0, total_ms from its first launch. rtd_field_fetch "trace_reused" tells which kind the last launched compute was.
+ *
+ * With the trace a field keeps a sigma record: what the fill's sigma recurrence gives for every (layer, step, ray) when the spot
+ * weights are left out of it (a ray below ray_weight_cutoff is masked afterwards). The first compute that reuses the trace records
+ * it in front of its fill (inside fill_idd_sigma_ms) and replays it; the computes after a finished such compute replay it under
+ * their own weights, bit for bit the result of the recurrence. Same validity as the trace (kept by rtd_field_set_spot_weights and by
+ * the batches of rtd_field_dose_influence; dropped by rtd_set_ct*, LUT and options calls and by rtd_field_release; never with
+ * nuclear_corr, spot maps of more than 64 rows, or in a capturing stream). Memory per field, allocated by that first compute: 4
+ * bytes x layers x rays x (steps from the entry step to the last step a layer can reach) + 4 bytes x layers x rays, about 135 MB on
+ * a 96 x 88 x 20 ray grid with 200 such steps; if the allocation fails the field keeps computing the recurrence and no error is
+ * raised. RTD_NO_SIGMA_REUSE in the environment when the field is created: every compute runs the recurrence.
+ * rtd_field_fetch "sigma_reused" tells what the last launched compute did.
  */
 int rtd_field_create(rtd_handle h, const rtd_beam* beam, const uint32_t dose_dims[3], rtd_field* out);
 int rtd_field_compute(rtd_handle h, rtd_field f, float* dev_dose);
@@ -305,6 +316,7 @@ int rtd_set_stream(rtd_handle h, void* hip_stream);
  * "eff_radius" [L][34] int32 (batch radius per tile radius); "bev" [S][H+64][W+64] float;
  * "layer_plan" [L][8] float (energyIdx, scaleFact, peakDepth, entrySigmaX, entrySigmaY, afterLast, 0, 0);
  * "trace_reused" int32[1]: 1 if the last launched compute reused the field's trace and plan (see rtd_field_compute).
+ * "sigma_reused" int32[1]: the sigma recurrence of the last launched compute: 0 walked, 1 recorded and replayed, 2 replayed.
  * "target_bev" and "target_hit": see rtd_field_project_target below.
  * Returns the number of bytes the buffer holds via *bytes_needed when host_out is NULL.
  */

@@ -142,6 +142,7 @@ int rtd_field_dose_influence(rtd_handle hh, rtd_field ff, float rel_threshold, s
         if (e == hipSuccess) e = hipMemcpyAsync(&count, f->dDijMisc, sizeof(int), hipMemcpyDeviceToHost, s);
         if (e == hipSuccess) e = hipStreamSynchronize(s);
         if (e != hipSuccess) { hipFail(e); break; }
+        sigmaRecordFinished(f, f->hState->errorFlags);                // (the batch's forward has drained: the later batches only replay)
         if ((size_t)(total + count) > f->dijCap) {                   // grow the batch-major staging geometrically (the stream is idle)
             size_t cap = f->dijCap;
             while (cap < (size_t)(total + count)) cap *= 2;

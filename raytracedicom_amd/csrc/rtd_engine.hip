@@ -414,7 +414,8 @@ int rtd_field_release(rtd_handle hh, rtd_field ff) {
     (void)hipStreamSynchronize(h->stream);      // its kernels have drained: the next owner uploads with plain copies
     f->computed = false; f->transferred = false;
     f->traceLaunched = false; f->traceUsable = false;   // (the next owner of the workspace is a new field object anyway: nothing carries over)
-    freeBuffers(f, kGradient | kDiag | kDij | kDijOut | kTarget);   // (not part of the shape's workspace)
+    freeBuffers(f, kGradient | kDiag | kDij | kDijOut | kTarget | kSigmaRec);   // (not part of the shape's workspace)
+    f->sigRecSteps = 0; f->sigRecLaunched = false; f->sigRecUsable = false; f->launchedSigma = 0;
     f->gradDone = false; f->targetProjected = false; f->targetSelected = false;
     f->dijDone = false; f->dijPrepared = false; f->dijCap = 0; f->dijNnz = 0; f->dijBatchOf.clear();
     f->released = shapeCounts(f);
@@ -703,6 +704,7 @@ static int ensureCtBox(rtd_handle_impl* h, rtd_field_impl* f) {
 struct ComputeJob {
     rtd_handle_impl* h; rtd_field_impl* f;
     bool reuse, tryUniform, knownUniform, timing;
+    int sigma;                    // k_fill's sigma role: 0 walks, 1 records and replays, 2 replays (sigmaMode)
     ResetJob resetJob;
     // Stage boundaries are the start / stop timestamps of the kernels themselves (hipExtLaunchKernelGGL), not event
     // packets between them: no barrier packet and no idle gap is inserted into the stream by the timing.
@@ -766,6 +768,31 @@ static void launchPlanConv(const ComputeJob& c) {
     }
 }
 
+// The sigma record of a compute that reuses the trace (rtd_engine_impl.hpp) -> 0 walk, 1 record and replay, 2 replay. Allocates the
+// record when the field has none that fits its plan; a failed allocation is no error: the field keeps walking.
+static int sigmaMode(rtd_handle_impl* h, rtd_field_impl* f, bool reuse) {
+    if (!reuse || f->sw.noSigmaReuse || f->sigRecFailed) return 0;
+    const size_t need = (size_t)std::max(f->planSteps, 1);
+    if (f->sigRecSteps >= need && f->sigRecUsable && f->sigRecEpoch == h->inputEpoch) return 2;
+    if (f->sigRecSteps < need) {
+        if (f->dSigRec) {                                             // a smaller record is replaced: an earlier compute may still read it
+            (void)hipStreamSynchronize(h->stream);
+            freeBuffers(f, kSigmaRec);
+        }
+        f->sigRecSteps = need;
+        hipError_t e = hipMalloc((void**)&f->dSigRec, need * f->R * (size_t)f->fc.L * sizeof(unsigned int));
+        if (e == hipSuccess) e = hipMalloc((void**)&f->dSigRecLast, f->R * (size_t)f->fc.L * sizeof(int));
+        if (e != hipSuccess) {
+            (void)hipGetLastError();                                  // (out of memory is not sticky: cleared here)
+            freeBuffers(f, kSigmaRec);
+            f->sigRecSteps = 0; f->sigRecFailed = true; f->sigRecLaunched = false; f->sigRecUsable = false;
+            return 0;
+        }
+    }
+    f->sigRecLaunched = true; f->sigRecEpoch = h->inputEpoch; f->sigRecUsable = false;
+    return 1;
+}
+
 // K5: the fill.
 static void launchFill(const ComputeJob& c) {
     rtd_handle_impl* h = c.h; rtd_field_impl* f = c.f; const FieldConst& fc = f->fc;
@@ -773,16 +800,21 @@ static void launchFill(const ComputeJob& c) {
     // (layer, tile, role) items: sigma walk and dose walk of every tile; placement is decided in the kernel
     const dim3 fillGrid(2 * (fc.W / kSuperpTileX) * (fc.H / kSuperpTileY) * fc.L), fillBlk(kSuperpTileX, kSuperpTileY);
     const NucFill nucFill{f->dNucSpotIdx, f->dNucRayWeights, f->dNucIdd, f->dNucRs};
-    auto launchFill = [&](auto kern, size_t lds) {
-        launchK(kern, fillGrid, fillBlk, lds, h->stream, nullptr, c.ev(3), (const float*)f->dDensity, (const float*)f->dWepl, (const float*)f->dRrl, f->dIdd,
+    const SigmaRec rec{f->dSigRec, f->dSigRecLast, (int)f->sigRecSteps};
+    auto launchFillOn = [&](auto kern, dim3 grid, size_t lds, hipEvent_t stopEv) {
+        launchK(kern, grid, fillBlk, lds, h->stream, nullptr, stopEv, (const float*)f->dDensity, (const float*)f->dWepl, (const float*)f->dRrl, f->dIdd,
                 f->dRSigma, (const float*)f->dRayWeights, (const int*)f->dFirstInside, (const int*)f->dFirstOutside,
                 f->dFirstPassive, f->dTileRad, f->dLayers, f->dState, h->lut, f->fillGeom, fc, (const float*)f->dStepTab, f->dActive, h->numCUs, f->dFillDbg, nucFill, f->dSigMin, f->dSigMax, c.tryUniform ? 1 : 0,
-                f->sw.noFillCompact ? 0 : 1);
+                f->sw.noFillCompact ? 0 : 1, rec);
     };
+    auto launchFill = [&](auto kern, size_t lds) { launchFillOn(kern, fillGrid, lds, c.ev(3)); };
     const bool ldsLut = fillLds <= 56 * 1024;     // (+ ~1 KiB of static arrays: stays under the 64 KiB default cap of a block's LDS)
     constexpr size_t sigLds = (size_t)2 * kFillBatch * 256 * sizeof(float);   // the sigma walk's exchange buffers share the dynamic LDS with the dose walk's LUT rows
     const size_t dynLds = std::max(sigLds, ldsLut ? fillLds : (size_t)0);
-    if (fc.nuclearCorr) { if (ldsLut) launchFill((k_fill<true, true>), dynLds); else launchFill((k_fill<false, true>), dynLds); }
+    // the record pass: the sigma walk of every (layer, tile) alone, in front of the fill that replays it (inside the fill's timing bucket)
+    if (c.sigma == 1) launchFillOn((k_fill<false, false, kFillRecord>), dim3(fillGrid.x / 2), (size_t)0, nullptr);
+    if (c.sigma) { if (ldsLut) launchFill((k_fill<true, false, kFillReplay>), dynLds); else launchFill((k_fill<false, false, kFillReplay>), dynLds); }
+    else if (fc.nuclearCorr) { if (ldsLut) launchFill((k_fill<true, true>), dynLds); else launchFill((k_fill<false, true>), dynLds); }
     else { if (ldsLut) launchFill((k_fill<true, false>), dynLds); else launchFill((k_fill<false, false>), dynLds); }
 }
 
@@ -910,7 +942,8 @@ int rtd_field_compute_bev(rtd_handle hh, rtd_field ff) {
     // the same values): the general superposition kernel, all of whose ~10^5 blocks would only look at the flag and leave, is not launched
     const bool knownUniform = tryUniform && f->uniformHint == 1 && f->hintEpoch == h->inputEpoch;
     f->launchedKnownUniform = knownUniform;
-    const ComputeJob c{h, f, reuse, tryUniform, knownUniform, h->opt.fine_grained_timing != 0,
+    f->launchedSigma = sigmaMode(h, f, reuse);
+    const ComputeJob c{h, f, reuse, tryUniform, knownUniform, h->opt.fine_grained_timing != 0, f->launchedSigma,
         ResetJob{f->dLayers, fc.L, reinterpret_cast<unsigned int*>(f->dTileRad), f->tileRadWords, f->dActive, (size_t)4 * fc.L * fc.S,
         f->dNucIdd, f->dNucRs, fc.nuclearCorr ? (size_t)fc.nucW * fc.nucH * fc.L : (size_t)0,
         f->dSigMin, f->dSigMax, (size_t)fc.L * fc.S, f->dScanDbg}};
@@ -1264,6 +1297,10 @@ int rtd_field_fetch(rtd_handle hh, rtd_field ff, const char* name, void* host_ou
         std::memcpy(staging.data(), f->dijBatchOf.data(), n);
     } else if (nm == "trace_reused") {
         const int32_t v = f->computed && f->launchedReuse ? 1 : 0;   // the last launched compute left out the tracer, the scan and the plan
+        n = sizeof v; staging.resize(n);
+        std::memcpy(staging.data(), &v, n);
+    } else if (nm == "sigma_reused") {
+        const int32_t v = f->computed ? f->launchedSigma : 0;        // the last launched compute: 0 walked, 1 recorded and replayed, 2 replayed
         n = sizeof v; staging.resize(n);
         std::memcpy(staging.data(), &v, n);
     } else if (nm == "eff_radius" || nm == "layer_plan") {

@@ -44,10 +44,12 @@ struct rtd_handle_impl {
 
 // The engine's RTD_* switches (diagnostics, and the second implementations the tests compare with): read once, when a field is
 // created. RTD_NO_UNIFORM_PATH, RTD_UNIFORM_V2, RTD_NO_SWEEP, RTD_SEPARATE_PLAN, RTD_SEPARATE_KS_PLAN, RTD_NO_TRACE_REUSE (every compute
-// traces and plans the field again), RTD_NO_FILL_COMPACT (k_fill deals a tile's rays to its lanes in their natural order),
+// traces and plans the field again), RTD_NO_SIGMA_REUSE (every compute walks the sigma recurrence: no sigma record), RTD_NO_FILL_COMPACT
+// (k_fill deals a tile's rays to its lanes in their natural order),
 // RTD_*_DEBUG (per-block clock stamps), and the overrides RTD_TRACE_MODE, RTD_TRACE_DIAG_B, RTD_KS_GROUPS, RTD_SW_GROUPS.
 struct Switches {
     bool noUniformPath = false, uniformV2 = false, noSweep = false, separatePlan = false, separateKsPlan = false, noTraceReuse = false, noFillCompact = false;
+    bool noSigmaReuse = false;
     bool scanDebug = false, fillDebug = false, uniformDebug = false, sweepDebug = false;
     std::optional<int> traceMode, traceDiagB, ksGroups, swGroups;
 };
@@ -56,7 +58,7 @@ Switches readSwitches() {
     auto on = [](const char* name) { return std::getenv(name) != nullptr; };
     auto num = [](const char* name) { const char* v = std::getenv(name); return v ? std::optional<int>(std::atoi(v)) : std::nullopt; };
     return Switches{on("RTD_NO_UNIFORM_PATH"), on("RTD_UNIFORM_V2"), on("RTD_NO_SWEEP"), on("RTD_SEPARATE_PLAN"), on("RTD_SEPARATE_KS_PLAN"),
-                    on("RTD_NO_TRACE_REUSE"), on("RTD_NO_FILL_COMPACT"),
+                    on("RTD_NO_TRACE_REUSE"), on("RTD_NO_FILL_COMPACT"), on("RTD_NO_SIGMA_REUSE"),
                     on("RTD_SCAN_DEBUG"), on("RTD_FILL_DEBUG"), on("RTD_UNIFORM_DEBUG"), on("RTD_SWEEP_DEBUG"),
                     num("RTD_TRACE_MODE"), num("RTD_TRACE_DIAG_B"), num("RTD_KS_GROUPS"), num("RTD_SW_GROUPS")};
 }
@@ -65,8 +67,8 @@ Switches readSwitches() {
 // halo, the spot-weight gradient's (allocated by its first call), the RTD_*_DEBUG clock stamps, the dose-influence matrix's workspace
 // and its result (rtd_field_dose_influence: allocated by its first call, the result replaced by every call; the result's class also
 // holds what rtd_field_dose_influence_prepare builds from it, so that the two are freed together), the target in beam's-eye view
-// (rtd_field_project_target: allocated by its first call).
-enum BufClass : unsigned { kShape = 1, kNuclear = 2, kGradient = 4, kDiag = 8, kDij = 16, kDijOut = 32, kTarget = 64, kAllBufs = 127 };
+// (rtd_field_project_target: allocated by its first call), the sigma record (allocated by the first compute that reuses the trace).
+enum BufClass : unsigned { kShape = 1, kNuclear = 2, kGradient = 4, kDiag = 8, kDij = 16, kDijOut = 32, kTarget = 64, kSigmaRec = 128, kAllBufs = 255 };
 
 struct rtd_field_impl {
     Switches sw;
@@ -107,6 +109,18 @@ struct rtd_field_impl {
     unsigned traceEpoch = 0;      // handle->inputEpoch of that launch
     bool traceUsable = false;     // ... and a finished compute under that epoch has been seen without a device error (takeFindings)
     bool launchedReuse = false;   // the compute in flight reused the trace: ev[1] is not recorded (rtd_field_fetch "trace_reused")
+    // The sigma record (rtd_fill.hpp): what k_fill's sigma walk computes without looking at the spot weights, kept under the trace's
+    // rule. The first compute that reuses the trace records it in front of its fill and replays it; the computes after a FINISHED such
+    // compute only replay, while handle->inputEpoch stands. [L][sigRecSteps][R] words + [L][R] end steps, allocated by that first
+    // compute (a failed allocation: the field keeps walking), freed by rtd_field_release / _destroy.
+    int planFirst = 0, planSteps = 0;   // beamFirstInside and the steps up to firstGuaranteedPassive of the trace in use (takeFindings)
+    unsigned int* dSigRec = nullptr; int* dSigRecLast = nullptr;
+    size_t sigRecSteps = 0;       // extent of the record's step axis (0: no record allocated)
+    bool sigRecFailed = false;    // the allocation failed once: not tried again
+    bool sigRecLaunched = false;  // a record pass has been launched under sigRecEpoch
+    unsigned sigRecEpoch = 0;
+    bool sigRecUsable = false;    // ... and a compute launched behind it under that epoch has been seen finished (sigmaRecordFinished)
+    int launchedSigma = 0;        // the compute in flight: 0 walked, 1 recorded and replayed, 2 replayed (rtd_field_fetch "sigma_reused")
     // NUCLEAR_CORR (default off): the halo on the spot-resolution grid
     int* dNucSpotIdx = nullptr; float *dNucRayWeights = nullptr, *dNucIdd = nullptr, *dNucRs = nullptr, *dNucBev = nullptr;
     int* dNucEffT = nullptr;
@@ -222,6 +236,7 @@ struct rtd_field_impl {
         visit(dDijPartial, ap * std::max<size_t>(dijChunks, 1), kDijOut, false, nullptr);
         visit(dTargetBev, ((S + 31) / 32) * R, kTarget, false, "target_bev"); visit(dTargetHit, L * R, kTarget, false, "target_hit");
         visit(dTargetSum, (size_t)1, kTarget, false, nullptr); visit(dTargetCount, (size_t)1, kTarget, false, nullptr);
+        visit(dSigRec, sigRecSteps * R * L, kSigmaRec, false, nullptr); visit(dSigRecLast, sigRecSteps ? R * L : (size_t)0, kSigmaRec, false, nullptr);
         visit(dScanDbg, sw.scanDebug ? 8 * (R / 64) : 0, kDiag, true, "scan_debug");
         visit(dFillDbg, sw.fillDebug ? 4 * 2 * tiles * L : 0, kDiag, false, "fill_debug");
         visit(dUniDbg, sw.uniformDebug && uniformEligible && uniform4() ? 16 * S * nPartsU4 : 0, kDiag, true, "uniform_debug");
@@ -292,7 +307,19 @@ hipError_t raiseLdsCap(rtd_handle_impl* h, K kernel, size_t bytes) {
 
 // What a finished plan tells the host (its state record, mirrored into pinned host memory). The hints belong to the inputs the
 // compute was LAUNCHED under: CT, LUTs or options may have changed since.
+// The launched compute is known to be finished, with the device-side error flags of its state record: a record pass launched in
+// front of it (or of an earlier compute) under its inputs is complete. Like the trace, the record is not trusted after a device error.
+void sigmaRecordFinished(rtd_field_impl* f, int errorFlags) {
+    if (errorFlags) { f->sigRecUsable = false; f->sigRecLaunched = false; return; }
+    if (f->sigRecLaunched && f->sigRecEpoch == f->launchEpoch) f->sigRecUsable = true;
+}
+
 int takeFindings(rtd_handle_impl* h, rtd_field_impl* f, const FieldState& st) {
+    sigmaRecordFinished(f, st.errorFlags);
+    if (!st.errorFlags && !f->remote) {   // (what the scan and the plan found: the same for every compute that reuses them)
+        f->planFirst = st.beamFirstInside;
+        f->planSteps = st.empty ? 0 : std::max(st.firstGuaranteedPassive - st.beamFirstInside, 0);
+    }
     if (f->triedUniform) { f->uniformHint = st.uniformField ? 1 : 0; f->hintEpoch = f->launchEpoch; }
     else if (f->hintEpoch != f->launchEpoch) { f->uniformHint = -1; f->hintEpoch = f->launchEpoch; }
     f->radiusHint = (st.errorFlags || st.empty) ? -1 : st.maxRadius;   // (valid under hintEpoch, like the uniform hint)

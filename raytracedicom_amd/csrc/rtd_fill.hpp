@@ -1,7 +1,7 @@
 // rtd_fill.hpp — K5 of the dose path: the IDD + sigma fill, fillIddAndSigma (kernel_wrapper.cu:190-379), with the reductions and
 // the tile classification that follow it in the reference (:952-957, kernel_wrapper.cuh:256-313).
 //
-// Kernel: k_fill<LDS_LUT, NUC>.
+// Kernel: k_fill<LDS_LUT, NUC, MODE>.
 #pragma once
 #include "rtd_field_state.hpp"
 #include "rtd_plan_conv.hpp"   // rtd_pow_det: rtd_detmath.h as device code
@@ -31,6 +31,17 @@ namespace rtd {
 // IEEE sqrt and division.
 
 constexpr int kFillBatch = 8;   // steps per batch: inputs fetched one batch ahead, one block barrier per batch
+// NO BRANCH AROUND A PREFETCH. The compiler counts the loads and stores in flight (s_waitcnt vmcnt(N)) along straight paths only; where
+// two paths that issued different numbers of them meet, it waits for all of them — vmcnt(0), the loads issued a step ago and the
+// stores' acknowledgements included: with "if (step < afterLast) load" and "if (step >= afterLast) continue" in every step both walks
+// drained memory at the head of every batch (the dose walk of the replaying build in most steps), a full round trip each. So every
+// prefetch of the replaying build is issued unconditionally at a clamped step (a value fetched for a step beyond the layer's last is
+// never used), and a batch that lies wholly within the layer's steps runs a body without the per-step test (only the layer's last
+// batch keeps it): the waits become counted ones, up to vmcnt(20). The second body costs the replaying build registers and waves per
+// SIMD, and costs the walking build more than it gives, so the walking and recording builds keep their loops as they were (the
+// figures of every build and what was measured: DESIGN.md section 4 K5).
+struct FillFullBatch { static constexpr bool full = true; };
+struct FillTailBatch { static constexpr bool full = false; };
 constexpr int kFillSnakeRounds = 12;   // up to this many walks per CU the walks are dealt in rounds of alternating direction (k_fill's block placement)
 
 // LANE PLACEMENT. The ray grid is the bounding rectangle of the spot map plus its margin, so most tiles hold rays that are dead from
@@ -79,8 +90,29 @@ struct NucFill {
     float* idd; float* rs;         // [L][nucH][nucW] plane 0 of the reference's nuclear arrays after layer l
 };
 
+// THE SIGMA RECORD. The sigma walk's recurrence — sigmaSq, the step at which a ray ends, the mask in front of its entry — is a
+// function of the trace, the layer's constants and the options. The spot weights enter in one place only: a ray whose weight is below
+// the cut-off is dead from the start. A field that computes again under the same CT, LUTs and options (the trace and the plan are
+// reused: rtd_engine.hip) therefore keeps, per (layer, step - beamFirstInside, ray), what the walk hands to the block's exchange
+// buffer when the weight test is left out: the bits of sigmaSq after the step, or kSigMasked where the ray is dead for another reason
+// (ended, outside, in front of its entry); and per (layer, ray) the step at which the walk ends. "Masked" is a bit pattern of its own
+// (an all-ones NaN, which no operation of the walk produces from its finite inputs), not a value: behind the peak sigmaSq may be
+// negative, and such a ray is stored as rcp(sqrt(negative)) = NaN while it is no ray to the classification.
+//   kFillRecord: the sigma walk of every (layer, tile) with the weight test left out, into the record: no outputs, no
+//                classification, no atomics, no dose walk (grid: L * tiles blocks). Launched once, in front of a replaying fill.
+//   kFillReplay: role 0 is a replay of the record under the weights of this compute: per step one load, the weight mask, 1/sigma
+//                from the same expression with the same hardware sqrt / reciprocal, the store, the exchange buffer, the unchanged
+//                classification. No serial chain. Every output is the same to the bit as the walk's.
+constexpr int kFillWalk = 0, kFillRecord = 1, kFillReplay = 2;
+constexpr unsigned int kSigMasked = 0xFFFFFFFFu;
+struct SigmaRec {
+    unsigned int* sig;             // [L][steps][H][W]: step index = step - beamFirstInside
+    int* last;                     // [L][H][W]: the step at which the ray's walk ends (0: dead from the start whatever its weight)
+    int steps;                     // extent of the step axis (accesses beyond it are left out)
+};
+
 // NUC: NUCLEAR_CORR compiled in (its table lookups and IEEE divisions cost registers: the default build keeps 6 blocks per CU)
-template <bool LDS_LUT, bool NUC>
+template <bool LDS_LUT, bool NUC, int MODE = kFillWalk>
 __global__ __launch_bounds__(256) void k_fill(const float* __restrict__ bevDensity, const float* __restrict__ bevCumulSp,
                                                const float* __restrict__ bevRrl,
                                                float* __restrict__ bevIdd, float* __restrict__ bevRSigmaEff,
@@ -90,7 +122,8 @@ __global__ __launch_bounds__(256) void k_fill(const float* __restrict__ bevDensi
                                                LutView lut, FillGeom fg, FieldConst fc, const float* __restrict__ stepTab,
                                                int* __restrict__ active, int nCU, long long* __restrict__ dbg, NucFill nuc,
                                                unsigned int* __restrict__ sigMin, unsigned int* __restrict__ sigMax, int trackUniform,
-                                               int compact) {
+                                               int compact, SigmaRec rec) {
+    static_assert(!NUC || MODE == kFillWalk, "the halo's fields always walk");
     extern __shared__ float sLutF[];                                 // dose walk: the layer's two cumulative-IDD rows
     // diagnostic build only (RTD_FILL_DEBUG): per walk start / end clock, hardware id, item — no output value depends on it
     // sigma walk: [buffer][step][ray] sigmaSq of the rays with a finite 1/sigma (-1: none) — in the same dynamic LDS as the dose walk's
@@ -115,7 +148,7 @@ __global__ __launch_bounds__(256) void k_fill(const float* __restrict__ bevDensi
     //  kFillSnakeRounds per CU: the first rounds land as described, the rest wherever a slot frees. Measured and dropped there: as many
     //  blocks as fit the GPU at once, each taking walk after walk from a ticket counter in descending order of cost — the loop costs
     //  the kernel 23 registers, 5 blocks per CU instead of 7: 0.325 ms against 0.27.)
-    const int nTiles = fc.tilesX * fc.tilesY, nB = 2 * nTiles * fc.L;
+    const int nTiles = fc.tilesX * fc.tilesY, nB = (MODE == kFillRecord ? 1 : 2) * nTiles * fc.L;
     const int tid = threadIdx.y * 32 + threadIdx.x;                  // lane slot of the block (its ray: LANE PLACEMENT)
     int item = blockIdx.x;
     if (nB <= kFillSnakeRounds * nCU) {
@@ -124,9 +157,9 @@ __global__ __launch_bounds__(256) void k_fill(const float* __restrict__ bevDensi
         item = rr * nCU + (reversed ? nCU - 1 - c : c);
     }
     const long long dbgT0 = dbg ? (long long)__builtin_amdgcn_s_memtime() : 0;
-    const int pr = st->fillItems[item / nTiles];
+    const int pr = MODE == kFillRecord ? (item / nTiles) << 1 : (int)st->fillItems[item / nTiles];   // (record: sigma walks only, in layer order)
     const int layer = pr >> 1;
-    const int role = pr & 1;                                         // block-uniform: 0 sigma walk, 1 dose walk
+    const int role = pr & 1;                                         // block-uniform: 0 sigma walk (or its replay), 1 dose walk
     // (the tile is rotated with the walk's index: when the tile count divides the CU count — 64 tiles on 256 CUs, the reference's water
     //  cube — block b and b + nCU would otherwise hold the same tile, and the CUs of the cheap edge tiles would get cheap walks in every round:
     //  measured 1.2 M against 2.6 M block-cycles per CU)
@@ -143,7 +176,7 @@ __global__ __launch_bounds__(256) void k_fill(const float* __restrict__ bevDensi
     // liveness of a ray at the start of its walk (:236-243): a function of the ray weight and the cut-off steps
     auto liveAtStart = [&](float weight, int firstOut, unsigned int& last) {
         last = (unsigned int)(firstOut < (int)pAfterLast ? firstOut : (int)pAfterLast);
-        if (weight < fc.rayWeightCutoff || last < pFirst) { last = 0; return false; }
+        if ((MODE != kFillRecord && weight < fc.rayWeightCutoff) || last < pFirst) { last = 0; return false; }   // (record: whatever its weight)
         return true;
     };
 
@@ -188,6 +221,7 @@ __global__ __launch_bounds__(256) void k_fill(const float* __restrict__ bevDensi
 
     if (role == 0) {
         // ================================ sigma walk ================================
+        const size_t recOff = MODE == kFillWalk ? (size_t)0 : (size_t)layer * (size_t)rec.steps * memStep;
         if (tid < kMaxSuperpR + 2) { sHist[tid] = 0; sClassLo[tid] = 0x7fffffff; sClassHi[tid] = -1; }
         if (tid == 0) sUni = trackUniform;                           // 0: the field is known not to be uniform (or not eligible): nothing is tracked
         const float pInv = 0.5649718f, eCoef = 8.639415f;
@@ -211,9 +245,20 @@ __global__ __launch_bounds__(256) void k_fill(const float* __restrict__ bevDensi
                 rrlB[j] = (bevRrl + (size_t)stepNo * memStep)[rayOff];
             }
         };
+        // replay: the record's words of the batch ahead, in the same rolling fashion; the step at which the ray's walk ended
+        unsigned int recB[kFillBatch];
+        auto fetchRec = [&](int j, unsigned int stepNo) {
+            const unsigned int k = stepNo - pFirst;                  // (clamped into the record: NO BRANCH AROUND A PREFETCH)
+            recB[j] = (rec.sig + recOff + (size_t)(k < (unsigned int)rec.steps ? k : (unsigned int)rec.steps - 1u) * memStep)[rayOff];
+        };
+        if (MODE == kFillReplay) {
+            afterLast = beamLive ? (unsigned int)rec.last[(size_t)layer * memStep + rayIdx] : 0u;
+            waveLive = __ballot(beamLive && pFirst < afterLast) != 0ull;   // a ray of the wave has a step that is not masked
+        }
 #pragma unroll
         for (int j = 0; j < kFillBatch; ++j) {
-            if (waveLive) fetch1(j, pFirst + j);
+            if (MODE == kFillReplay) { if (waveLive) fetchRec(j, pFirst + j); else recB[j] = kSigMasked; }
+            else if (waveLive) fetch1(j, pFirst + j);
             else { spB[j] = 0.0f; denB[j] = 0.0f; rrlB[j] = 0.0f; }
         }
         __syncthreads();
@@ -257,11 +302,32 @@ __global__ __launch_bounds__(256) void k_fill(const float* __restrict__ bevDensi
         };
         unsigned int step0 = pFirst;
         int buf = 0;
-        for (; step0 < pAfterLast && waveLive; step0 += kFillBatch, buf ^= 1) {
+        auto replayBatch = [&](auto kind) {
 #pragma unroll
             for (int j = 0; j < kFillBatch; ++j) {
                 const unsigned int stepNo = step0 + j;
-                if (stepNo >= pAfterLast) { sSig[buf][j][tid] = -1.0f; continue; }   // block-uniform
+                if (!decltype(kind)::full && stepNo >= pAfterLast) { sSig[buf][j][tid] = -1.0f; continue; }   // block-uniform
+                const unsigned int r = recB[j];
+                fetchRec(j, stepNo + kFillBatch);
+                const bool masked = !beamLive || r == kSigMasked;   // the weight mask of this compute, the record's own
+                const float sig = __uint_as_float(r);
+                const float rs = stepTab[2 * stepNo] * __builtin_amdgcn_rcpf(sqrt2 * (__builtin_amdgcn_sqrtf(sig) + sigmaDeltaV));   // the walk's expression
+                (bevRSigmaEff + layerOff + (size_t)stepNo * memStep)[rayOff] = masked ? __int_as_float(0x7f800000) : rs;
+                sSig[buf][j][tid] = masked ? -1.0f : sig;
+                __builtin_amdgcn_sched_barrier(0);                   // (a step's instructions stay within the step)
+            }
+        };
+        if (MODE == kFillReplay) for (; step0 < pAfterLast && waveLive; step0 += kFillBatch, buf ^= 1) {
+            if (step0 + kFillBatch <= pAfterLast) replayBatch(FillFullBatch{}); else replayBatch(FillTailBatch{});
+            waveLive = __ballot(beamLive && step0 + kFillBatch < afterLast) != 0ull;   // (the steps from afterLast on are masked)
+            ldsBarrier();
+            classify(step0, buf);
+        }
+        else for (; step0 < pAfterLast && waveLive; step0 += kFillBatch, buf ^= 1) {
+#pragma unroll
+            for (int j = 0; j < kFillBatch; ++j) {
+                const unsigned int stepNo = step0 + j;
+                if (stepNo >= pAfterLast) { if (MODE != kFillRecord) sSig[buf][j][tid] = -1.0f; continue; }   // block-uniform
                 const float cumulSp = spB[j], density = denB[j], rRl = rrlB[j];
                 fetch1(j, stepNo + kFillBatch);
                 if (beamLive) {
@@ -290,18 +356,34 @@ __global__ __launch_bounds__(256) void k_fill(const float* __restrict__ bevDensi
                     cumulSpOld = cumulSp;
                 }
                 float sig = sigmaSq;
-                if (!beamLive || (int)stepNo < (firstIn - 1)) { rSigmaEff = __int_as_float(0x7f800000); sig = -1.0f; nucRSigmaEff = __int_as_float(0x7f800000); }
-                (bevRSigmaEff + layerOff + (size_t)stepNo * memStep)[rayOff] = rSigmaEff;
-                sSig[buf][j][tid] = sig;
+                const bool masked = !beamLive || (int)stepNo < (firstIn - 1);
+                if (masked) { rSigmaEff = __int_as_float(0x7f800000); sig = -1.0f; nucRSigmaEff = __int_as_float(0x7f800000); }
+                if (MODE == kFillRecord) {
+                    if (stepNo - pFirst < (unsigned int)rec.steps)
+                        (rec.sig + recOff + (size_t)(stepNo - pFirst) * memStep)[rayOff] = masked ? kSigMasked : __float_as_uint(sigmaSq);
+                } else {
+                    (bevRSigmaEff + layerOff + (size_t)stepNo * memStep)[rayOff] = rSigmaEff;
+                    sSig[buf][j][tid] = sig;
+                }
             }
             waveLive = __ballot(beamLive) != 0ull;
-            ldsBarrier();                                            // the only barrier of a batch (sSig is double-buffered)
-            classify(step0, buf);
+            if (MODE != kFillRecord) {
+                ldsBarrier();                                        // the only barrier of a batch (sSig is double-buffered)
+                classify(step0, buf);
+            }
         }
         // The rest of the walk when no ray of the wave is alive (any more): what a dead ray's step leaves — 1/sigma = +inf in memory,
         // -1 in the block's exchange buffers (those once per buffer) — without inputs and without arithmetic. The barriers and the
         // wave's share of the classification stay.
+        // (record: "masked" into the record, and nothing else)
         for (int deadBufs = 0; step0 < pAfterLast; step0 += kFillBatch, buf ^= 1) {
+            if (MODE == kFillRecord) {
+#pragma nounroll
+                for (int j = 0; j < kFillBatch; ++j)
+                    if (step0 + j < pAfterLast && step0 + j - pFirst < (unsigned int)rec.steps)
+                        (rec.sig + recOff + (size_t)(step0 + j - pFirst) * memStep)[rayOff] = kSigMasked;
+                continue;
+            }
 #pragma nounroll
             for (int j = 0; j < kFillBatch; ++j)
                 if (step0 + j < pAfterLast) (bevRSigmaEff + layerOff + (size_t)(step0 + j) * memStep)[rayOff] = __int_as_float(0x7f800000);
@@ -313,6 +395,7 @@ __global__ __launch_bounds__(256) void k_fill(const float* __restrict__ bevDensi
             ldsBarrier();
             classify(step0, buf);
         }
+        if (MODE == kFillRecord) { rec.last[(size_t)layer * memStep + rayIdx] = (int)afterLast; return; }
         firstPassive[(size_t)layer * memStep + rayIdx] = (int)afterLast;
         if (NUC && nucIdx >= 0 && pFirst < pAfterLast) nuc.rs[(size_t)layer * fc.nucW * fc.nucH + nucIdx] = nucRSigmaEff;   // value of the last step (:367-373)
         int mx = waveMaxI((int)afterLast);
@@ -345,7 +428,16 @@ __global__ __launch_bounds__(256) void k_fill(const float* __restrict__ bevDensi
         float nucRes = 0.0f;
         int actUni = 0x7fffffff;
         float spB[kFillBatch], denB[kFillBatch];
+        const float* __restrict__ denSrc = fc.doseToWater ? bevCumulSp : bevDensity;
         auto fetch1 = [&](int j, unsigned int stepNo) {
+            if (MODE == kFillReplay) {
+                // (NO BRANCH AROUND A PREFETCH: dose to water has no use for the density and fetches the stopping power twice, the
+                //  second time from the line the first one brought)
+                const size_t so = (size_t)(stepNo < (unsigned int)fc.S ? stepNo : (unsigned int)fc.S - 1u) * memStep;
+                spB[j] = (bevCumulSp + so)[rayOff];
+                denB[j] = (denSrc + so)[rayOff];
+                return;
+            }
             spB[j] = 0.0f; denB[j] = 0.0f;
             if (stepNo < pAfterLast) {
                 spB[j] = (bevCumulSp + (size_t)stepNo * memStep)[rayOff];
@@ -386,47 +478,51 @@ __global__ __launch_bounds__(256) void k_fill(const float* __restrict__ bevDensi
                 rect = (unsigned int)__builtin_amdgcn_update_dpp(0, (int)rect, 0x111, 0xF, 0xF, true);   // row_shr:1
                 rect = (tid & (kWave - 1)) == 0 ? r : rect;
             };
-#pragma unroll
-            for (int j = 0; j < kFillBatch; ++j) {
-                const unsigned int stepNo = step0 + j;
-                if (stepNo >= pAfterLast) { pushRect(0xffffffffu); continue; }   // block-uniform
-                const float cumulSp = spB[j], density = denB[j];
-                fetch1(j, stepNo + kFillBatch);
-                if (beamLive) {
-                    float cumulDose;
-                    {   // tex2D(cumulIddTex, ...) :269-274, rows and row weight hoisted
-                        float px = cumulSp * lp.energyScaleFact;
-                        float fx = floorf(px), ax = px - fx;
-                        int x0 = (int)fx, x1 = x0 + 1;
-                        if (!(px >= 0.0f)) { x0 = 0; x1 = 0; ax = 0.0f; }
-                        x0 = x0 > lut.nSamples - 1 ? lut.nSamples - 1 : x0; x1 = x1 > lut.nSamples - 1 ? lut.nSamples - 1 : x1;
-                        float r0 = LDS_LUT ? lerpW(ax, sRow0[x0], sRow0[x1]) : lerpW(ax, gRow0[x0], gRow0[x1]);
-                        float r1 = LDS_LUT ? lerpW(ax, sRow1[x0], sRow1[x1]) : lerpW(ax, gRow1[x0], gRow1[x1]);
-                        cumulDose = lerpW(eay, r0, r1);
+            auto doseBatch = [&](auto kind) {
+    #pragma unroll
+                for (int j = 0; j < kFillBatch; ++j) {
+                    const unsigned int stepNo = step0 + j;
+                    if (!decltype(kind)::full && stepNo >= pAfterLast) { pushRect(0xffffffffu); continue; }   // block-uniform
+                    const float cumulSp = spB[j], density = denB[j];
+                    fetch1(j, stepNo + kFillBatch);
+                    if (beamLive) {
+                        float cumulDose;
+                        {   // tex2D(cumulIddTex, ...) :269-274, rows and row weight hoisted
+                            float px = cumulSp * lp.energyScaleFact;
+                            float fx = floorf(px), ax = px - fx;
+                            int x0 = (int)fx, x1 = x0 + 1;
+                            if (!(px >= 0.0f)) { x0 = 0; x1 = 0; ax = 0.0f; }
+                            x0 = x0 > lut.nSamples - 1 ? lut.nSamples - 1 : x0; x1 = x1 > lut.nSamples - 1 ? lut.nSamples - 1 : x1;
+                            float r0 = LDS_LUT ? lerpW(ax, sRow0[x0], sRow0[x1]) : lerpW(ax, gRow0[x0], gRow0[x1]);
+                            float r1 = LDS_LUT ? lerpW(ax, sRow1[x0], sRow1[x1]) : lerpW(ax, gRow1[x0], gRow1[x1]);
+                            cumulDose = lerpW(eay, r0, r1);
+                        }
+                        if (cumulSp > cutDepth || stepNo == afterLast) { beamLive = false; afterLast = stepNo; }
+                        // stepTab[2k+1] = stepVol(k) (fill_idd_and_sigma_params.cu:72)
+                        const float stepVol = stepTab[2 * stepNo + 1];
+                        const float mass = fc.doseToWater ? (cumulSp - cumulSpOld) * stepVol : density * stepVol;
+                        // (the dose value feeds no threshold other than res > 0, which a reciprocal cannot change: hardware reciprocal, <= 1 ulp)
+                        if (!NUC || !fc.nuclearCorr) {
+                            if (mass > 1e-2f) res = rayWeight * (cumulDose - cumulDoseOld) * __builtin_amdgcn_rcpf(mass);
+                        } else if (mass > 1e-2f) {                       // :320-331: the primary keeps (1 - nucWeight), the halo gets nucWeight
+                            const float nucWeight = sample2dClamp(lut.nucWeight, lut.nSamples, lut.nEnergies,
+                                                                  0.5f * (cumulSp + cumulSpOld) * lp.energyScaleFact, lp.energyIdx);
+                            res = (1.0f - nucWeight) * rayWeight * (cumulDose - cumulDoseOld) * __builtin_amdgcn_rcpf(mass);
+                            nucRes = nucWeight * nucRayWeight * (cumulDose - cumulDoseOld) / (mass * fc.spotDist * fc.spotDist);
+                        }
+                        cumulSpOld = cumulSp;
+                        cumulDoseOld = cumulDose;
                     }
-                    if (cumulSp > cutDepth || stepNo == afterLast) { beamLive = false; afterLast = stepNo; }
-                    // stepTab[2k+1] = stepVol(k) (fill_idd_and_sigma_params.cu:72)
-                    const float stepVol = stepTab[2 * stepNo + 1];
-                    const float mass = fc.doseToWater ? (cumulSp - cumulSpOld) * stepVol : density * stepVol;
-                    // (the dose value feeds no threshold other than res > 0, which a reciprocal cannot change: hardware reciprocal, <= 1 ulp)
-                    if (!NUC || !fc.nuclearCorr) {
-                        if (mass > 1e-2f) res = rayWeight * (cumulDose - cumulDoseOld) * __builtin_amdgcn_rcpf(mass);
-                    } else if (mass > 1e-2f) {                       // :320-331: the primary keeps (1 - nucWeight), the halo gets nucWeight
-                        const float nucWeight = sample2dClamp(lut.nucWeight, lut.nSamples, lut.nEnergies,
-                                                              0.5f * (cumulSp + cumulSpOld) * lp.energyScaleFact, lp.energyIdx);
-                        res = (1.0f - nucWeight) * rayWeight * (cumulDose - cumulDoseOld) * __builtin_amdgcn_rcpf(mass);
-                        nucRes = nucWeight * nucRayWeight * (cumulDose - cumulDoseOld) / (mass * fc.spotDist * fc.spotDist);
-                    }
-                    cumulSpOld = cumulSp;
-                    cumulDoseOld = cumulDose;
+                    if (!beamLive || (int)stepNo < (firstIn - 1)) { res = 0.0f; nucRes = 0.0f; }
+                    (bevIdd + layerOff + (size_t)stepNo * memStep)[rayOff] = res;
+                    // where in the tile the rays with dose are: decoded only when the ballot changes — where rays enter and where they end
+                    const unsigned long long ballot = __ballot(res > 0.0f);
+                    if (ballot != lastBallot) { lastBallot = ballot; lastRect = fillWaveRect(ballot, sSegOf + wave * kFillSegsPerWave); }
+                    pushRect(lastRect);
+                    if (MODE == kFillReplay) __builtin_amdgcn_sched_barrier(0);   // (a step's instructions stay within the step)
                 }
-                if (!beamLive || (int)stepNo < (firstIn - 1)) { res = 0.0f; nucRes = 0.0f; }
-                (bevIdd + layerOff + (size_t)stepNo * memStep)[rayOff] = res;
-                // where in the tile the rays with dose are: decoded only when the ballot changes — where rays enter and where they end
-                const unsigned long long ballot = __ballot(res > 0.0f);
-                if (ballot != lastBallot) { lastBallot = ballot; lastRect = fillWaveRect(ballot, sSegOf + wave * kFillSegsPerWave); }
-                pushRect(lastRect);
-            }
+            };
+            if (MODE == kFillReplay && step0 + kFillBatch <= pAfterLast) doseBatch(FillFullBatch{}); else doseBatch(FillTailBatch{});
             if ((tid & (kWave - 1)) < kFillBatch) sDoseRect[buf][kFillBatch - 1 - (tid & (kWave - 1))][wave] = rect;
             waveLive = __ballot(beamLive) != 0ull;
             ldsBarrier();                                            // the only barrier of a batch (sDoseRect is double-buffered)
