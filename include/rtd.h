@@ -827,7 +827,7 @@ typedef struct rtd_contour_set {
 typedef struct rtd_roi_info {
     uint64_t n_voxels;
     uint32_t box_lo[3], box_hi[3];   /* inclusive, (i, j, k) */
-    uint32_t n_planes, n_slices_covered;
+    uint32_t n_planes, n_slices_covered;   /* of the contour input; both 0 for a derived ROI (rtd_roi_margin, _combine, _from_mask) */
     int32_t reserved[2];
 } rtd_roi_info;
 
@@ -986,6 +986,56 @@ int rtd_dose_gamma(rtd_handle h, const float* dev_ref, const float* dev_eval, co
                    const rtd_gamma_options* opt, const uint8_t* dev_mask /* or NULL */, float* dev_gamma_map /* or NULL */,
                    rtd_gamma_result* dev_result);
 int rtd_dose_gamma_kernel_ms(rtd_handle h, float* ms);   /* the search kernel of the last call, as rtd_roi_kernel_ms */
+
+/*
+ * ---- Derived ROIs: margins, boolean algebra, an ROI from a mask ----
+ *
+ * Additive to the blocks above (RTD_ABI_VERSION stays 3). The structures nobody draws: a target plus a margin, a ring around it, an
+ * organ without the target, the body contracted, an isodose volume. Everything is decided by integers and by comparisons of float32
+ * values computed in the stated order, each rounded to float32, nothing contracted: the same inputs give the same bits across calls,
+ * handles and processes, and tests/roi_ops_reference.py restates the rule in numpy.
+ *
+ * Inputs of a margin. An ROI A on a grid (nx, ny, nz); spacing_mm[3], positive and finite; margin_mm[6] in the order
+ * (-x, +x, -y, +y, -z, +z) of the grid's index axes, every margin finite and >= 0.
+ * Cost tables, one per axis a, made on the host in float64 from the float32 inputs: c_a[0] = 0; for d = 1, 2, ... on a side with
+ *     margin m > 0: q = (double(d) * double(s_a)) / double(m), c = float(q * q); the table holds d while c <= 1.0f and ends at the
+ *     first d where that fails. A side with m == 0 holds only d = 0. c_a[+d] uses the + margin, c_a[-d] the - margin. A side whose
+ *     farthest d would exceed 127 refuses the call. (The rule is exact: at spacing float32(1.2) and margin 6, d = 5 is out, because
+ *     the float32 spacing lies above 1.2 and the cost rounds above 1.)
+ * Expand (contract == 0). A voxel p of the grid is in the result iff there is a q in A such that every component of d = p - q lies
+ *     inside its table and fl32(fl32(c_x[d_x] + c_y[d_y]) + c_z[d_z]) <= 1.0f, the additions in exactly that order. The +x margin
+ *     moves the +x surface outward; the element is an ellipsoid with a semi-axis of its own on each of the six sides.
+ * Contract (contract == 1). p is in the result iff p is in A and no grid voxel q outside A has
+ *     fl32(fl32(c_x[d_x] + c_y[d_y]) + c_z[d_z]) <= 1.0f for d = q - p inside the tables. The +x margin moves the +x surface inward.
+ *     Voxels outside the grid count as inside A: the grid boundary does not erode a structure the grid cuts off. Equivalently: the
+ *     complement within the grid of expand(complement of A within the grid, the two sides of every axis swapped), which is how it
+ *     is computed.
+ * The minimum over q separates exactly, because rounding is monotone:
+ *     min_q fl(fl(c_x + c_y) + c_z) = min_dz fl(min_dy fl(min_dx c_x + c_y) + c_z);  the kernels (rtd_roi_ops.hpp) use this.
+ *
+ * rtd_roi_margin      expand or contract src. All margins zero (or below one spacing) give a copy.
+ * rtd_roi_combine     op: RTD_ROI_OR, RTD_ROI_AND, RTD_ROI_ANDNOT (a without b), RTD_ROI_XOR; a and b of equal dims.
+ * rtd_roi_from_mask   the voxels whose byte of dev_mask (device memory, dims[0] dims[1] dims[2] bytes, x fastest: the layout
+ *                     rtd_roi_fill_mask writes) is non-zero.
+ * All three are synchronous set-up calls like rtd_roi_rasterize (allocations, one wait for the total, the emit). Every result is a full
+ * rtd_roi: rtd_roi_get_info, _voxels, _device, _fill_mask, _kernel_ms (the kernels of the call that made it) and _destroy work on it;
+ * the list is strictly ascending, the box is the box of the voxels; n_planes and n_slices_covered describe contour input and are 0.
+ * An empty result (a contraction that eats the structure, an AND of disjoint structures) is a valid ROI with n_voxels == 0. A result
+ * may be an input again. The sources stay valid and unchanged.
+ * Environment: RTD_ROI_MARGIN_NAIVE (read by rtd_create) selects the plain second implementation of the margin: one lane per voxel of
+ * the working region, the nested table loops of the definition.
+ *
+ * RTD_ERR_INVALID_ARG, with *out = NULL, after which every object stays usable: a null pointer, a spacing that is not positive and
+ * finite, a margin that is negative or not finite, a table side beyond 127, contract other than 0 or 1, an unknown op, ROIs of
+ * different dims, a zero dimension or more than 2^31 - 1 voxels in rtd_roi_from_mask.
+ */
+#define RTD_ROI_OR     0
+#define RTD_ROI_AND    1
+#define RTD_ROI_ANDNOT 2   /* a without b */
+#define RTD_ROI_XOR    3
+int rtd_roi_margin(rtd_handle h, rtd_roi src, const float spacing_mm[3], const float margin_mm[6], int contract, rtd_roi* out);
+int rtd_roi_combine(rtd_handle h, rtd_roi a, rtd_roi b, int op, rtd_roi* out);
+int rtd_roi_from_mask(rtd_handle h, const uint32_t dims[3], const uint8_t* dev_mask, rtd_roi* out);
 
 /*
  * ---- Multi-GPU plans behind the boundary (SURVEY.md 8(b) "Threading": one handle and one host thread per device) ----

@@ -191,6 +191,9 @@ class RtdGammaResult(C.Structure):
 
 RTD_GAMMA_MAX_RADIUS = 10
 
+# rtd_roi_combine
+RTD_ROI_OR, RTD_ROI_AND, RTD_ROI_ANDNOT, RTD_ROI_XOR = 0, 1, 2, 3
+
 
 def default_gamma_options():
     """rtd_default_gamma_options: 1 % / 1 mm above 10 % of max(ref), global, node samples only."""

@@ -44,6 +44,7 @@
 #include "rtd_robust.hpp"
 #include "rtd_voxelwise.hpp"
 #include "rtd_roi.hpp"
+#include "rtd_roi_ops.hpp"
 #include "rtd_target.hpp"
 #include "rtd_gamma.hpp"
 #include "rtd_engine_impl.hpp"
@@ -149,6 +150,7 @@ int rtd_create(int device_id, rtd_handle* out) {
     }
     h->stream = h->ownStream;
     h->gammaNaive = std::getenv("RTD_GAMMA_NAIVE") != nullptr;
+    h->roiMarginNaive = std::getenv("RTD_ROI_MARGIN_NAIVE") != nullptr;
     if (hipDeviceGetAttribute(&h->numCUs, hipDeviceAttributeMultiprocessorCount, device_id) != hipSuccess || h->numCUs <= 0) h->numCUs = 256;
     *out = reinterpret_cast<rtd_handle>(h);
     return RTD_OK;
@@ -1387,5 +1389,6 @@ int rtd_compute(rtd_handle hh, const rtd_beam* beams, int n_beams, float* dose_i
 #include "rtd_objective_host.hpp"
 #include "rtd_optimizer_host.hpp"
 #include "rtd_roi_host.hpp"
+#include "rtd_roi_ops_host.hpp"
 #include "rtd_target_host.hpp"
 #include "rtd_gamma_host.hpp"

@@ -37,6 +37,7 @@ struct rtd_handle_impl {
                                                    // event of its upload and the stream it was issued on (a consumer on another stream waits for it)
     // rtd_dose_gamma (rtd_gamma_host.hpp)
     bool gammaNaive = false;                       // RTD_GAMMA_NAIVE, read when the handle is created: the plain second implementation
+    bool roiMarginNaive = false;                   // RTD_ROI_MARGIN_NAIVE, likewise: k_roi_margin_naive instead of the separable passes
     hipEvent_t gammaEv[2] = {};                    // around the search kernel of the last call that was not captured (created by the first call)
     bool gammaTimed = false;                       // ... and such a call has been made
     void clearCtBoxes() { for (auto& b : ctBoxes) if (b.done) (void)hipEventDestroy(b.done); ctBoxes.clear(); }

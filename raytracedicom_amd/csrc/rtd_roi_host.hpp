@@ -14,6 +14,62 @@ struct rtd_roi_impl {
     DevBuf<unsigned> dRowMask; DevBuf<int> dSliceSlot, dVoxels;
 };
 
+// What every ROI ends with once its packed row mask is on the stream: count, scan, one wait for the total, emit, info. The kernels and
+// their order are those rtd_roi_rasterize has always launched; derived ROIs (rtd_roi_ops_host.hpp) end the same way.
+struct RoiTail {
+    DevBuf<unsigned> dWork; DevBuf<RoiBox> dBox;                       // scratch: freed with this object
+    hipEvent_t ev[4] = {};
+    int nRows = 0, nRowBlocks = 0;
+    ~RoiTail() { for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e); }
+    // work: rowCnt[nRows] | rowOff[nRows] | blockSum[nRowBlocks] | total[1]
+    hipError_t alloc(int rows) {
+        nRows = rows; nRowBlocks = (rows + kRoiBlock - 1) / kRoiBlock;
+        RoiBox box;
+        for (int a = 0; a < 3; ++a) { box.lo[a] = 0xffffffffu; box.hi[a] = 0u; }
+        hipError_t e = dWork.alloc(2 * (size_t)nRows + (size_t)nRowBlocks + 1);
+        if (e == hipSuccess) e = dBox.alloc(1);
+        if (e == hipSuccess) e = hipMemcpy(dBox, &box, sizeof box, hipMemcpyHostToDevice);
+        for (hipEvent_t& evt : ev) if (e == hipSuccess) e = hipEventCreate(&evt);
+        return e;
+    }
+    void begin(rtd_handle_impl* h) { (void)hipEventRecord(ev[0], h->stream); }   // before the kernels that write the row mask
+    // r->dRowMask holds nRows rows (slot-major) on the stream; dSlots: the slots' slices. Sets the list, n_voxels, the box and kernelMs.
+    hipError_t finish(rtd_handle_impl* h, rtd_roi_impl* r, const RoiSlot* dSlots) {
+        const int nx = (int)r->dims[0], ny = (int)r->dims[1];
+        unsigned *dRowCnt = dWork, *dRowOff = dWork + nRows, *dBlockSum = dWork + 2 * (size_t)nRows, *dTotal = dBlockSum + nRowBlocks;
+        unsigned total = 0u;
+        RoiBox box;
+        k_roi_count<<<(unsigned)nRowBlocks, kRoiBlock, 0, h->stream>>>((const unsigned*)r->dRowMask, dSlots, ny, r->maskWords, nRows, dRowCnt, dBlockSum, dBox);
+        k_roi_sums<<<1, kRoiBlock, 0, h->stream>>>(dBlockSum, nRowBlocks, dTotal);
+        k_roi_row_offsets<<<(unsigned)nRowBlocks, kRoiBlock, 0, h->stream>>>((const unsigned*)dRowCnt, (const unsigned*)dBlockSum, nRows, dRowOff);
+        (void)hipEventRecord(ev[1], h->stream);
+        hipError_t e = hipGetLastError();
+        if (e == hipSuccess) e = hipMemcpyAsync(&total, dTotal, sizeof total, hipMemcpyDeviceToHost, h->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(&box, dBox, sizeof box, hipMemcpyDeviceToHost, h->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+        if (e == hipSuccess && total) {
+            e = r->dVoxels.alloc(total);
+            if (e == hipSuccess) {
+                (void)hipEventRecord(ev[2], h->stream);
+                k_roi_emit<<<(unsigned)((nRows + kRoiBlock / 64 - 1) / (kRoiBlock / 64)), kRoiBlock, 0, h->stream>>>((const unsigned*)r->dRowMask, dSlots, (const unsigned*)dRowCnt,
+                                                                                                                    (const unsigned*)dRowOff, nx, ny, r->maskWords, nRows, r->dVoxels);
+                (void)hipEventRecord(ev[3], h->stream);
+                e = hipGetLastError();
+                if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+            }
+        }
+        if (e != hipSuccess) return e;
+        float a = 0.0f, b = 0.0f;
+        (void)hipEventElapsedTime(&a, ev[0], ev[1]);
+        if (total) (void)hipEventElapsedTime(&b, ev[2], ev[3]);
+        r->kernelMs = a + b;
+        r->nVoxels = total;
+        r->info.n_voxels = total;
+        if (total) for (int i = 0; i < 3; ++i) { r->info.box_lo[i] = box.lo[i]; r->info.box_hi[i] = box.hi[i]; }
+        return hipSuccess;
+    }
+};
+
 }  // namespace
 
 extern "C" {
@@ -96,68 +152,31 @@ int rtd_roi_rasterize(rtd_handle hh, const rtd_roi_grid* grid, const rtd_contour
     r->maskWords = (int)((nx + 31u) / 32u);
     r->info.n_planes = (uint32_t)planeKc.size();
     r->info.n_slices_covered = (uint32_t)slots.size();
-    const int nRows = r->nSlots * (int)ny, nRowBlocks = (nRows + kRoiBlock - 1) / kRoiBlock;   // (rows: at most nz * ny < 2^31)
-    DevBuf<RoiEdge> dEdges; DevBuf<RoiSlot> dSlots; DevBuf<unsigned> dWork; DevBuf<RoiBox> dBox;   // scratch: freed when this call returns
-    struct Events { hipEvent_t ev[4] = {}; ~Events() { for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e); } } events;
-    hipEvent_t (&ev)[4] = events.ev;
+    const int nRows = r->nSlots * (int)ny;                             // (rows: at most nz * ny < 2^31)
+    DevBuf<RoiEdge> dEdges; DevBuf<RoiSlot> dSlots;                    // scratch: freed when this call returns
+    RoiTail tail;
     hipError_t e = hipSetDevice(h->device);
     if (e == hipSuccess) e = r->dSliceSlot.alloc(nz);
     if (e == hipSuccess) e = hipMemcpy(r->dSliceSlot, sliceSlot.data(), (size_t)nz * sizeof(int), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = r->dVoxels.alloc(1);      // (replaced below when the list is not empty)
-    unsigned total = 0u;
-    RoiBox box;
-    for (int a = 0; a < 3; ++a) { box.lo[a] = 0xffffffffu; box.hi[a] = 0u; }
+    if (e == hipSuccess) e = r->dVoxels.alloc(1);      // (replaced by the tail when the list is not empty)
     if (e == hipSuccess && nRows > 0) {
-        // work: rowCnt[nRows] | rowOff[nRows] | blockSum[nRowBlocks] | total[1]
-        const size_t workWords = 2 * (size_t)nRows + (size_t)nRowBlocks + 1;
         e = r->dRowMask.alloc((size_t)nRows * r->maskWords);
         if (e == hipSuccess) e = dEdges.alloc(edges.size());
         if (e == hipSuccess) e = dSlots.alloc(slots.size());
-        if (e == hipSuccess) e = dWork.alloc(workWords);
-        if (e == hipSuccess) e = dBox.alloc(1);
+        if (e == hipSuccess) e = tail.alloc(nRows);
         if (e == hipSuccess) e = hipMemcpy(dEdges, edges.data(), edges.size() * sizeof(RoiEdge), hipMemcpyHostToDevice);
         if (e == hipSuccess) e = hipMemcpy(dSlots, slots.data(), slots.size() * sizeof(RoiSlot), hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMemcpy(dBox, &box, sizeof box, hipMemcpyHostToDevice);
-        for (hipEvent_t& evt : ev) if (e == hipSuccess) e = hipEventCreate(&evt);
-        unsigned *dRowCnt = dWork, *dRowOff = dWork + nRows, *dBlockSum = dWork + 2 * (size_t)nRows, *dTotal = dBlockSum + nRowBlocks;
         if (e == hipSuccess) {
             const int nGroups = (int)((ny + kRoiRows - 1) / kRoiRows), nSegs = (int)((nx + kRoiSegBits - 1) / kRoiSegBits);
             const size_t nScanBlocks = (size_t)r->nSlots * nGroups * nSegs;    // (every block holds a voxel of its own: below 2^31)
-            (void)hipEventRecord(ev[0], h->stream);
+            tail.begin(h);
             for (size_t base = 0; base < nScanBlocks; base += kRoiMaxBlocks)
                 k_roi_scan<<<(unsigned)std::min<size_t>(kRoiMaxBlocks, nScanBlocks - base), kRoiBlock, 0, h->stream>>>(dEdges, dSlots, (int)nx, (int)ny, nGroups, nSegs, r->maskWords,
                                                                                                                      (unsigned)base, r->dRowMask);
-            k_roi_count<<<(unsigned)nRowBlocks, kRoiBlock, 0, h->stream>>>((const unsigned*)r->dRowMask, dSlots, (int)ny, r->maskWords, nRows, dRowCnt, dBlockSum, dBox);
-            k_roi_sums<<<1, kRoiBlock, 0, h->stream>>>(dBlockSum, nRowBlocks, dTotal);
-            k_roi_row_offsets<<<(unsigned)nRowBlocks, kRoiBlock, 0, h->stream>>>((const unsigned*)dRowCnt, (const unsigned*)dBlockSum, nRows, dRowOff);
-            (void)hipEventRecord(ev[1], h->stream);
-            e = hipGetLastError();
-            if (e == hipSuccess) e = hipMemcpyAsync(&total, dTotal, sizeof total, hipMemcpyDeviceToHost, h->stream);
-            if (e == hipSuccess) e = hipMemcpyAsync(&box, dBox, sizeof box, hipMemcpyDeviceToHost, h->stream);
-            if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-        }
-        if (e == hipSuccess && total) {
-            e = r->dVoxels.alloc(total);
-            if (e == hipSuccess) {
-                (void)hipEventRecord(ev[2], h->stream);
-                k_roi_emit<<<(unsigned)((nRows + kRoiBlock / 64 - 1) / (kRoiBlock / 64)), kRoiBlock, 0, h->stream>>>((const unsigned*)r->dRowMask, dSlots, (const unsigned*)dRowCnt,
-                                                                                                                    (const unsigned*)dRowOff, (int)nx, (int)ny, r->maskWords, nRows, r->dVoxels);
-                (void)hipEventRecord(ev[3], h->stream);
-                e = hipGetLastError();
-                if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-            }
-        }
-        if (e == hipSuccess) {
-            float a = 0.0f, b = 0.0f;
-            (void)hipEventElapsedTime(&a, ev[0], ev[1]);
-            if (total) (void)hipEventElapsedTime(&b, ev[2], ev[3]);
-            r->kernelMs = a + b;
+            e = tail.finish(h, r, dSlots);
         }
     }
     if (e != hipSuccess) { delete r; RTD_HIP(h, e); }
-    r->nVoxels = total;
-    r->info.n_voxels = total;
-    if (total) for (int a = 0; a < 3; ++a) { r->info.box_lo[a] = box.lo[a]; r->info.box_hi[a] = box.hi[a]; }
     *out = reinterpret_cast<rtd_roi>(r);
     return RTD_OK;
 }

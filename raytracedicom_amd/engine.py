@@ -116,6 +116,9 @@ def lib():
         L.rtd_roi_fill_mask.argtypes = [vp, vp, vp]
         L.rtd_roi_kernel_ms.argtypes = [vp, vp, C.POINTER(C.c_float)]
         L.rtd_roi_destroy.argtypes = [vp, vp]
+        L.rtd_roi_margin.argtypes = [vp, vp, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int, vpp]
+        L.rtd_roi_combine.argtypes = [vp, vp, vp, C.c_int, vpp]
+        L.rtd_roi_from_mask.argtypes = [vp, u3, vp, vpp]
         L.rtd_field_project_target.argtypes = [vp, vp, vp, C.POINTER(abi.RtdTargetInfo)]
         L.rtd_field_select_spots.argtypes = [vp, vp, C.POINTER(abi.RtdTargetOptions), vp, C.POINTER(C.c_uint32)]
         L.rtd_default_gamma_options.argtypes = [C.POINTER(abi.RtdGammaOptions)]
@@ -525,9 +528,79 @@ class Roi:
         s.offsets = offs.ctypes.data_as(C.POINTER(C.c_uint32))
         s.n_contours = len(cs)
         eng._check(lib().rtd_roi_rasterize(eng._h, C.byref(g), C.byref(s), C.byref(self._h)))
+        self._read_info()
+
+    def _read_info(self):
         i = abi.RtdRoiInfo()
-        eng._check(lib().rtd_roi_get_info(eng._h, self._h, C.byref(i)))
+        self.eng._check(lib().rtd_roi_get_info(self.eng._h, self._h, C.byref(i)))
         self.info = i.as_dict()
+
+    @classmethod
+    def _adopt(cls, eng, dims, handle):
+        """The Roi of a handle that a call returned (rtd_roi_margin, rtd_roi_combine, rtd_roi_from_mask): it owns the handle."""
+        r = cls.__new__(cls)
+        r.eng = eng
+        r._h = handle
+        r.dims = tuple(int(d) for d in dims)
+        r._read_info()
+        return r
+
+    @staticmethod
+    def _six(margin_mm):
+        """A scalar, 3 values (one per axis, both sides) or 6 values (-x, +x, -y, +y, -z, +z) -> 6 floats."""
+        m = np.atleast_1d(np.asarray(margin_mm, dtype=np.float32)).reshape(-1)
+        if m.size == 1:
+            m = np.repeat(m, 6)
+        elif m.size == 3:
+            m = np.repeat(m, 2)
+        elif m.size != 6:
+            raise ValueError("margin_mm: a scalar, 3 or 6 values, not %d" % m.size)
+        return (C.c_float * 6)(*[float(v) for v in m])
+
+    def _margin(self, margin_mm, spacing_mm, contract):
+        sp = (C.c_float * 3)(*[float(np.float32(v)) for v in spacing_mm])
+        out = C.c_void_p()
+        self.eng._check(lib().rtd_roi_margin(self.eng._h, self._h, sp, self._six(margin_mm), int(contract), C.byref(out)))
+        return Roi._adopt(self.eng, self.dims, out)
+
+    def expand(self, margin_mm, spacing_mm):
+        """rtd_roi_margin: the ROI grown by margin_mm (a scalar, one value per axis, or (-x, +x, -y, +y, -z, +z)) on the grid of
+        spacing_mm (x, y, z) -> a new Roi; this one is unchanged."""
+        return self._margin(margin_mm, spacing_mm, 0)
+
+    def contract(self, margin_mm, spacing_mm):
+        """rtd_roi_margin with contract = 1: the +x margin moves the +x surface inward; the grid boundary does not erode."""
+        return self._margin(margin_mm, spacing_mm, 1)
+
+    def _combine(self, o, op):
+        out = C.c_void_p()
+        self.eng._check(lib().rtd_roi_combine(self.eng._h, self._h, o._h, int(op), C.byref(out)))
+        return Roi._adopt(self.eng, self.dims, out)
+
+    def union(self, o):
+        return self._combine(o, abi.RTD_ROI_OR)
+
+    def intersect(self, o):
+        return self._combine(o, abi.RTD_ROI_AND)
+
+    def subtract(self, o):
+        """The voxels of this ROI that are not in o."""
+        return self._combine(o, abi.RTD_ROI_ANDNOT)
+
+    def xor(self, o):
+        return self._combine(o, abi.RTD_ROI_XOR)
+
+    def ring(self, inner_mm, outer_mm, spacing_mm):
+        """expand(outer_mm) without expand(inner_mm); the two expansions are closed."""
+        outer = self.expand(outer_mm, spacing_mm)
+        try:
+            inner = self.expand(inner_mm, spacing_mm)
+            try:
+                return outer.subtract(inner)
+            finally:
+                inner.close()
+        finally:
+            outer.close()
 
     def voxels(self):
         """The linear voxel indices ((k ny + j) nx + i, strictly ascending) as a numpy int32 array."""
@@ -753,6 +826,30 @@ class Engine:
         contours a list of (n, 3) arrays of xyz mm (closed polygons, each planar in the grid's k); plane_thickness_mm the slice spacing
         of the contoured image. Returns a Roi."""
         return Roi(self, dims, world_to_idx, contours, plane_thickness_mm)
+
+    def roi_from_mask(self, t, dims=None):
+        """rtd_roi_from_mask: the Roi of the non-zero bytes of a device mask on the grid (x fastest, as Roi.fill_mask writes it). t: a
+        torch.uint8 tensor on this device ([Z][Y][X]; dims default to its shape reversed) or a device pointer (int) with dims (x, y, z).
+        The mask is read on the engine's stream: whatever wrote it must have finished (or the engine be on that stream, set_stream)."""
+        if hasattr(t, "data_ptr"):
+            if dims is None:
+                if len(t.shape) != 3:
+                    raise ValueError("roi_from_mask: dims are needed for a tensor of shape %r" % (tuple(t.shape),))
+                dims = (t.shape[2], t.shape[1], t.shape[0])
+            if t.element_size() != 1 or not t.is_contiguous():
+                raise ValueError("roi_from_mask: a contiguous one-byte tensor is needed")
+            if t.numel() != int(dims[0]) * int(dims[1]) * int(dims[2]):
+                raise ValueError("roi_from_mask: %d bytes do not fill dims %r" % (t.numel(), tuple(int(d) for d in dims)))
+            if not t.is_cuda:
+                raise ValueError("roi_from_mask: the tensor must be on the device, not on %s" % (t.device,))
+            ptr = t.data_ptr()
+        else:
+            if dims is None:
+                raise ValueError("roi_from_mask: a device pointer needs dims")
+            ptr = int(t)
+        out = C.c_void_p()
+        self._check(lib().rtd_roi_from_mask(self._h, abi.uint3(dims), C.c_void_p(ptr), C.byref(out)))
+        return Roi._adopt(self, dims, out)
 
     def create_optimizer(self, fields, objective, options=None):
         return Optimizer(self, fields, objective, options)
