@@ -619,6 +619,74 @@ int rtd_objective_dose_at_volume(rtd_handle h, rtd_objective obj, const float* d
 int rtd_objective_dvh(rtd_handle h, rtd_objective obj, const float* dev_dose, uint32_t n_bins, double dose_max, uint32_t* dev_counts);
 
 /*
+ * ---- Generalised equivalent uniform dose and EUD objectives ----
+ *
+ * Additive to the blocks above (RTD_ABI_VERSION stays 3; rtd_objective_term and rtd_objective_dvh_term keep their layouts): the gEUD
+ * of a structure, reported and penalised on the device. "The parotid's gEUD with a = 1 below 26 Gy", "the cord's near-maximum
+ * (a = 16) below 45 Gy", "the target's cold-spot dose (a = -10) at least 95 %".
+ *
+ * Arithmetic (the contract; everything is float64). For a term or query on a ROI of N voxels, with L = dose_level (the level of a
+ * term, the normalisation of a query), a = exponent, lo = 2^-15 and hi = 2^15:
+ *   1. x_i = double(d_i) / L; if x_i < lo then x_i = lo; if x_i > hi then x_i = hi. A NaN fails both comparisons and stays a NaN: the
+ *      objective is then not finite and the optimiser's guard acts as before. Voxel i is CLAMPED when either comparison was true.
+ *   2. p_i = pow(x_i, a). With |a| <= 64 it lies in [2^-960, 2^960]: sums of up to 2^31 such values do not overflow, nothing
+ *      underflows, and a zero or negative dose under a negative exponent is harmless (it is clamped to lo first).
+ *   3. S = (sum_i p_i) / N, summed by one fixed tree (chunks of 2048 ROI voxels: thread t of 256 adds the chunk's voxels t, t + 256,
+ *      ... in order, wave butterfly (32, ..., 1), the four waves as (0 + 1) + (2 + 3); the chunk sums the same way, chunk c to thread
+ *      c mod 256). E = L * pow(S, 1 / a): the generalised equivalent uniform dose. a = 1 is the mean, a -> +inf the maximum, a -> -inf
+ *      the minimum of the ROI.
+ *   4. y = E - L; RTD_OBJ_SQ_MAX_EUD: y = y < 0 ? 0 : y ("E at most L"); RTD_OBJ_SQ_MIN_EUD: y = y > 0 ? 0 : y ("E at least L");
+ *      RTD_OBJ_SQ_EUD keeps y. values[1 + t] = weight * y * y: not divided by N, E is a mean already.
+ *   5. Gradient: K = ((2 * weight * y) * E) / ((L * double(N)) * S), evaluated once per term in exactly that association. Voxel i of
+ *      the ROI adds K * (p_i / x_i) to g[v] if it is not clamped; a clamped voxel adds +0.0 (the subgradient of the clamp), and every
+ *      voxel adds +0.0 when y == 0. p_i is the pow of step 2 evaluated again on the same x_i and a: the same bits. The additions per
+ *      voxel are in term order, from 0.0, rounded to float32 once, as for every other kind.
+ * No float atomics: the same inputs give the same bits across calls, handles, processes and graph replays. The device's pow is the
+ * device library's; a host restatement agrees within that function's error bound, not bit for bit.
+ *
+ * rtd_objective_add_eud_term   a term of kind RTD_OBJ_SQ_EUD, _SQ_MAX_EUD or _SQ_MIN_EUD. It counts towards RTD_OBJ_MAX_TERMS and takes
+ *                              the next term number, mixed with the terms of the two other add_* calls in the order added.
+ * rtd_objective_eud            queries: host memory, 1 <= n <= RTD_EUD_MAX_QUERIES of (roi, dose_level = L, exponent; reserved = 0);
+ *                              dev_out[q] = E of query q (float64, device). The parameters travel as kernel arguments: once the
+ *                              tables exist the call is two launches on the handle's stream (no allocation, copy or synchronisation)
+ *                              and can be captured into a graph. The first call after an add_roi builds the ROI index lists
+ *                              (shared with the dose-volume calls) and is synchronous that once.
+ * rtd_objective_eval           of an objective with EUD terms: after the DVH selection (if it has DVH terms) two launches (the sums,
+ *                              then E, K and the value of every EUD term) in front of the two of before; still no allocation, copy
+ *                              or host synchronisation after the first eval, still capturable. An objective without EUD terms
+ *                              launches what it launched before and gives the same bits.
+ * rtd_optimizer_create, _create_robust: accept such objectives (a scenario is evaluated like any dose). rtd_optimizer_create_voxelwise
+ * and rtd_objective_eval_voxelwise refuse them: E couples the voxels of a ROI, so the objective of the per-voxel worst dose is not
+ * the sum over voxels the voxel-wise composite needs.
+ *
+ * RTD_ERR_INVALID_ARG: a null pointer, a kind other than the three (and any of the three passed to rtd_objective_add_term or
+ * rtd_objective_add_dvh_term), an unknown ROI, a weight that is not positive and finite, a dose_level that is not finite or not
+ * greater than 0, an exponent that is not finite or with |exponent| outside [2^-4, 64], reserved != 0, a 65th term, n = 0 or
+ * n > RTD_EUD_MAX_QUERIES. After a refusal the objective is what it was.
+ */
+enum { RTD_OBJ_SQ_EUD = 6, RTD_OBJ_SQ_MAX_EUD = 7, RTD_OBJ_SQ_MIN_EUD = 8 };   /* accepted by rtd_objective_add_eud_term only */
+#define RTD_EUD_MAX_QUERIES 64
+
+typedef struct rtd_objective_eud_term {
+    int32_t kind;             /* RTD_OBJ_SQ_EUD, RTD_OBJ_SQ_MAX_EUD or RTD_OBJ_SQ_MIN_EUD */
+    int32_t roi;
+    double weight;            /* > 0 */
+    double dose_level;        /* L: finite, > 0 */
+    double exponent;          /* a: 2^-4 <= |a| <= 64 */
+    double reserved;          /* 0 */
+} rtd_objective_eud_term;
+
+typedef struct rtd_eud_query {
+    int32_t roi;
+    int32_t reserved;
+    double dose_level;        /* the normalisation L: finite, > 0; any dose of the ROI's order of magnitude */
+    double exponent;          /* a: 2^-4 <= |a| <= 64 */
+} rtd_eud_query;
+
+int rtd_objective_add_eud_term(rtd_handle h, rtd_objective obj, const rtd_objective_eud_term* t);
+int rtd_objective_eud(rtd_handle h, rtd_objective obj, const float* dev_dose, const rtd_eud_query* queries, uint32_t n, double* dev_out);
+
+/*
  * ---- Robust spot-weight optimisation over error scenarios ----
  *
  * Additive to the two blocks above (RTD_ABI_VERSION stays 3). A scenario is one realisation of the plan under an error: the same

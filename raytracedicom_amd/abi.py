@@ -23,6 +23,8 @@ RTD_OBJ_MAX_TERMS = 64
 RTD_OPT_MAX_FIELDS = 16
 RTD_OBJ_MAX_DVH, RTD_OBJ_MIN_DVH = 4, 5     # rtd_objective_add_dvh_term only
 RTD_DVH_MAX_QUERIES = 64
+RTD_OBJ_SQ_EUD, RTD_OBJ_SQ_MAX_EUD, RTD_OBJ_SQ_MIN_EUD = 6, 7, 8     # rtd_objective_add_eud_term only
+RTD_EUD_MAX_QUERIES = 64
 RTD_ROBUST_EXPECTED, RTD_ROBUST_WORST_CASE = 0, 1
 RTD_ROBUST_MAX_SCENARIOS = 32
 
@@ -126,6 +128,15 @@ class RtdObjectiveDvhTerm(C.Structure):
 
 class RtdDvhQuery(C.Structure):
     _fields_ = [("roi", C.c_int32), ("reserved", C.c_int32), ("volume_fraction", C.c_double)]
+
+
+class RtdObjectiveEudTerm(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("roi", C.c_int32), ("weight", C.c_double), ("dose_level", C.c_double), ("exponent", C.c_double),
+                ("reserved", C.c_double)]
+
+
+class RtdEudQuery(C.Structure):
+    _fields_ = [("roi", C.c_int32), ("reserved", C.c_int32), ("dose_level", C.c_double), ("exponent", C.c_double)]
 
 
 class RtdOptimizerOptions(C.Structure):

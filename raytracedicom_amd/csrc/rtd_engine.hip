@@ -41,6 +41,7 @@
 #include "rtd_dij_apply.hpp"
 #include "rtd_optimize.hpp"
 #include "rtd_dvh.hpp"
+#include "rtd_eud.hpp"
 #include "rtd_robust.hpp"
 #include "rtd_voxelwise.hpp"
 #include "rtd_roi.hpp"

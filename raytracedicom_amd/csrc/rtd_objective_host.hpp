@@ -1,5 +1,6 @@
-// rtd_objective_host.hpp — host side of the dose objectives, their DVH queries and the voxel-wise worst case (include/rtd.h, DESIGN.md
-// sections 12, 13 and 15; kernels in rtd_optimize.hpp, rtd_dvh.hpp and rtd_voxelwise.hpp). Part of rtd_engine.hip's translation unit.
+// rtd_objective_host.hpp — host side of the dose objectives, their DVH and EUD queries and the voxel-wise worst case (include/rtd.h,
+// DESIGN.md sections 12, 13, 15 and 20; kernels in rtd_optimize.hpp, rtd_dvh.hpp, rtd_eud.hpp and rtd_voxelwise.hpp). Part of
+// rtd_engine.hip's translation unit.
 // Plain owned allocations (DevBuf): an objective is no field, so it does not go through a field's buffer table.
 #pragma once
 
@@ -9,8 +10,9 @@ struct rtd_objective_impl {
     uint32_t dims[3] = {0, 0, 0};
     size_t nVox = 0;
     std::vector<std::vector<int32_t>> rois;
-    std::vector<rtd_objective_term> terms;   // kinds 4 and 5 (DVH terms) among them, in the order added
+    std::vector<rtd_objective_term> terms;   // kinds 4 and 5 (DVH terms) and 6 to 8 (EUD terms) among them, in the order added
     std::vector<double> vfrac;    // per term: the volume fraction of a DVH term, 0 for the others
+    std::vector<double> expo;     // per term: the exponent of an EUD term, 0 for the others
     bool built = false;           // the device tables belong to rois / terms as they are
     int nU = 0, nBlocks = 0;      // union voxels; blocks of k_obj_eval
     struct Tables { DevBuf<int> dUv, dTPtr; DevBuf<unsigned char> dTIdx; DevBuf<ObjTerm> dTerms; DevBuf<double> dPartial; } tab;   // (tab = {} frees them)
@@ -21,7 +23,15 @@ struct rtd_objective_impl {
     struct Dvh { DevBuf<int> dRoiIdx, dRoiOff; DevBuf<unsigned> dSelHist; DevBuf<float> dThr; } dvh;
     DvhSel evalSel{};             // the selections of eval: one per DVH term, in term order, slot = the term
     int nEvalSel = 0;
+    // EUD (section 20): the chunk sums of k_eud_sum (kEudMaxSel x nChMax) and {E, K, value} per term; the ROI index lists are those of
+    // the DVH. Built when an EUD term or a query first needs them; they depend on the ROIs alone.
+    bool eudBuilt = false;
+    int nChMax = 0;               // chunks of the largest ROI
+    struct Eud { DevBuf<double> dPartial, dTerm; } eud;
+    EudSel eudSel{};              // the selections of eval: one per EUD term, in term order, slot = the term
+    int nEudSel = 0;
     bool hasDvhTerms() const { for (double v : vfrac) if (v > 0.0) return true; return false; }
+    bool hasEudTerms() const { for (double a : expo) if (a != 0.0) return true; return false; }
 };
 
 // k of "the k-th largest of n" for a volume fraction v in (0, 1]: min(n, max(1, ceil(v n))), the product in float64.
@@ -57,6 +67,34 @@ int buildDvh(rtd_handle_impl* h, rtd_objective_impl* o) {
     return RTD_OK;
 }
 
+// The ROI index lists (buildDvh) and the two arrays of the EUD kernels. Synchronous.
+int buildEud(rtd_handle_impl* h, rtd_objective_impl* o) {
+    if (o->eudBuilt && o->dvhBuilt) return RTD_OK;
+    const int st = buildDvh(h, o);
+    if (st != RTD_OK) return st;
+    o->eud = {};
+    size_t nMax = 1;
+    for (const auto& r : o->rois) nMax = std::max(nMax, r.size());
+    o->nChMax = (int)((nMax + kEudChunk - 1) / kEudChunk);
+    hipError_t e = o->eud.dPartial.alloc((size_t)kEudMaxSel * o->nChMax);
+    if (e == hipSuccess) e = o->eud.dTerm.alloc((size_t)3 * kObjMaxTerms);
+    if (e == hipSuccess) e = hipMemset(o->eud.dTerm, 0, (size_t)3 * kObjMaxTerms * sizeof(double));
+    if (e != hipSuccess) { o->eud = {}; RTD_HIP(h, e); }
+    o->eudBuilt = true;
+    return RTD_OK;
+}
+
+// One call's EUD selections: the chunk sums, then E per selection (and K and the value of a term). Launches only.
+int eudSelect(rtd_handle_impl* h, rtd_objective_impl* o, const float* dDose, const EudSel& sel, int nSel, double* dQueryOut) {
+    int nMax = 0;
+    for (int i = 0; i < nSel; ++i) nMax = std::max(nMax, sel.n[i]);
+    const dim3 grid((unsigned)((nMax + kEudChunk - 1) / kEudChunk), (unsigned)nSel);
+    k_eud_sum<<<grid, 256, 0, h->stream>>>((const int*)o->dvh.dRoiIdx, dDose, sel, o->nChMax, o->eud.dPartial);
+    k_eud_finish<<<(unsigned)nSel, 256, 0, h->stream>>>(sel, (const double*)o->eud.dPartial, o->nChMax, o->eud.dTerm, dQueryOut);
+    RTD_HIP(h, hipGetLastError());
+    return RTD_OK;
+}
+
 // The union of the ROIs ascending and, per union voxel, its terms in term order (CSR); set-up work, on the host. Synchronous.
 int buildObjective(rtd_handle_impl* h, rtd_objective_impl* o) {
     RTD_HIP(h, hipSetDevice(h->device));
@@ -82,6 +120,7 @@ int buildObjective(rtd_handle_impl* h, rtd_objective_impl* o) {
     for (size_t t = 0; t < terms.size(); ++t) {
         const double N = (double)o->rois[(size_t)o->terms[t].roi].size(), wt = o->terms[t].weight;
         terms[t] = ObjTerm{o->terms[t].dose_level, 2.0 * wt / N, wt / N, o->terms[t].kind, 0};
+        if (o->expo[t] != 0.0) terms[t].c = o->expo[t];              // (an EUD term: k_obj_eval reads its exponent here, its K from eud.dTerm)
     }
     o->nU = (int)uv.size();
     o->nBlocks = (o->nU + 255) / 256;
@@ -107,6 +146,16 @@ int buildObjective(rtd_handle_impl* h, rtd_objective_impl* o) {
         if (st != RTD_OK) { o->tab = {}; return st; }
         for (int i = 0; i < o->nEvalSel; ++i) o->evalSel.off[i] = o->roiOff[(size_t)o->evalSel.off[i]];
     }
+    o->nEudSel = 0;
+    for (size_t t = 0; t < o->terms.size(); ++t)
+        if (o->expo[t] != 0.0) {
+            if (o->nEudSel == 0) { const int st = buildEud(h, o); if (st != RTD_OK) { o->tab = {}; return st; } }
+            const int i = o->nEudSel++;
+            const size_t r = (size_t)o->terms[t].roi;
+            o->eudSel.off[i] = o->roiOff[r]; o->eudSel.n[i] = o->roiOff[r + 1] - o->roiOff[r]; o->eudSel.slot[i] = (int)t;
+            o->eudSel.kind[i] = o->terms[t].kind; o->eudSel.level[i] = o->terms[t].dose_level; o->eudSel.expo[i] = o->expo[t];
+            o->eudSel.weight[i] = o->terms[t].weight;
+        }
     o->built = true;
     return RTD_OK;
 }
@@ -124,19 +173,33 @@ int dvhSelect(rtd_handle_impl* h, rtd_objective_impl* o, const float* dDose, con
     return RTD_OK;
 }
 
-// eval without the argument checks of the entry point: two launches once the tables exist.
+// eval without the argument checks of the entry point: two launches once the tables exist, the DVH selection (four) and the EUD
+// sums (two) in front of them where the objective has such terms.
+template <bool kDvh, bool kEud> void launchObjEval(rtd_handle_impl* h, rtd_objective_impl* o, const float* dDose, float* dGrad) {
+    k_obj_eval<kDvh, kEud><<<(unsigned)o->nBlocks, 256, 0, h->stream>>>((const int*)o->tab.dUv, (const int*)o->tab.dTPtr, (const unsigned char*)o->tab.dTIdx,
+                                                                        (const ObjTerm*)o->tab.dTerms, (int)o->terms.size(), o->nU, dDose, dGrad, o->tab.dPartial,
+                                                                        o->nBlocks, kDvh ? (const float*)o->dvh.dThr : nullptr,
+                                                                        kEud ? (const double*)o->eud.dTerm : nullptr);
+}
 int evalObjective(rtd_handle_impl* h, rtd_objective_impl* o, const float* dDose, double* dValues, float* dGrad) {
     if (!o->built) { const int st = buildObjective(h, o); if (st != RTD_OK) return st; }
     const int nTerms = (int)o->terms.size();
     if (o->nEvalSel) {                                                // DVH terms: their doses at volume of this dose first
         const int st = dvhSelect(h, o, dDose, o->evalSel, o->nEvalSel, o->dvh.dThr);
         if (st != RTD_OK) return st;
-        k_obj_eval<true><<<(unsigned)o->nBlocks, 256, 0, h->stream>>>((const int*)o->tab.dUv, (const int*)o->tab.dTPtr, (const unsigned char*)o->tab.dTIdx,
-                                                                      (const ObjTerm*)o->tab.dTerms, nTerms, o->nU, dDose, dGrad, o->tab.dPartial, o->nBlocks,
-                                                                      (const float*)o->dvh.dThr);
-    } else if (o->nBlocks)
-        k_obj_eval<false><<<(unsigned)o->nBlocks, 256, 0, h->stream>>>((const int*)o->tab.dUv, (const int*)o->tab.dTPtr, (const unsigned char*)o->tab.dTIdx,
-                                                                       (const ObjTerm*)o->tab.dTerms, nTerms, o->nU, dDose, dGrad, o->tab.dPartial, o->nBlocks, nullptr);
+    }
+    if (o->nEudSel) {                                                 // EUD terms: E, K and the value of each, of this dose
+        const int st = eudSelect(h, o, dDose, o->eudSel, o->nEudSel, nullptr);
+        if (st != RTD_OK) return st;
+        if (o->nEvalSel) launchObjEval<true, true>(h, o, dDose, dGrad);
+        else launchObjEval<false, true>(h, o, dDose, dGrad);
+        k_obj_reduce_eud<<<1, 256, 0, h->stream>>>((const double*)o->tab.dPartial, o->nBlocks, (const ObjTerm*)o->tab.dTerms, nTerms, dValues,
+                                                   (const double*)o->eud.dTerm);
+        RTD_HIP(h, hipGetLastError());
+        return RTD_OK;
+    }
+    if (o->nEvalSel) launchObjEval<true, false>(h, o, dDose, dGrad);
+    else if (o->nBlocks) launchObjEval<false, false>(h, o, dDose, dGrad);
     k_obj_reduce<<<1, 256, 0, h->stream>>>((const double*)o->tab.dPartial, o->nBlocks, (const ObjTerm*)o->tab.dTerms, nTerms, dValues);
     RTD_HIP(h, hipGetLastError());
     return RTD_OK;
@@ -145,6 +208,7 @@ int evalObjective(rtd_handle_impl* h, rtd_objective_impl* o, const float* dDose,
 // eval_voxelwise without the null-pointer checks of the entry point: a clear of the word and two launches once the tables exist.
 int evalVoxelwise(rtd_handle_impl* h, rtd_objective_impl* o, const float* const* dDoses, int nScen, double* dValues, float* const* dGrads, unsigned* dActive) {
     if (o->hasDvhTerms()) return fail(h, RTD_ERR_INVALID_ARG, "rtd_objective_eval_voxelwise: an objective with DVH terms has no voxel-wise worst case");
+    if (o->hasEudTerms()) return fail(h, RTD_ERR_INVALID_ARG, "rtd_objective_eval_voxelwise: an objective with EUD terms has no voxel-wise worst case");
     if (!o->built) { const int st = buildObjective(h, o); if (st != RTD_OK) return st; }
     VoxelwiseVols a{};
     const int padded = (nScen + kVoxelwiseUnroll - 1) / kVoxelwiseUnroll * kVoxelwiseUnroll;
@@ -190,6 +254,7 @@ int rtd_objective_add_roi(rtd_handle hh, rtd_objective oo, const int32_t* voxels
     o->rois.emplace_back(voxels, voxels + n);
     o->built = false;
     o->dvhBuilt = false;
+    o->eudBuilt = false;
     *roi_id = (int32_t)o->rois.size() - 1;
     return RTD_OK;
 }
@@ -206,6 +271,7 @@ int rtd_objective_add_term(rtd_handle hh, rtd_objective oo, const rtd_objective_
     if (o->terms.size() >= (size_t)kObjMaxTerms) return fail(h, RTD_ERR_INVALID_ARG, "rtd_objective_add_term: more than RTD_OBJ_MAX_TERMS terms");
     o->terms.push_back(*t);
     o->vfrac.push_back(0.0);
+    o->expo.push_back(0.0);
     o->built = false;
     return RTD_OK;
 }
@@ -223,6 +289,7 @@ int rtd_objective_add_dvh_term(rtd_handle hh, rtd_objective oo, const rtd_object
     if (o->terms.size() >= (size_t)kObjMaxTerms) return fail(h, RTD_ERR_INVALID_ARG, "rtd_objective_add_dvh_term: more than RTD_OBJ_MAX_TERMS terms");
     o->terms.push_back(rtd_objective_term{t->kind, t->roi, t->weight, t->dose_level});
     o->vfrac.push_back(t->volume_fraction);
+    o->expo.push_back(0.0);
     o->built = false;
     return RTD_OK;
 }
@@ -247,6 +314,55 @@ int rtd_objective_dose_at_volume(rtd_handle hh, rtd_objective oo, const float* d
         sel.off[q] = o->roiOff[r]; sel.n[q] = o->roiOff[r + 1] - o->roiOff[r]; sel.k[q] = dvhRank(queries[q].volume_fraction, sel.n[q]); sel.slot[q] = (int)q;
     }
     return dvhSelect(h, o, dev_dose, sel, (int)n, dev_out);
+}
+
+// What add_eud_term and eud refuse about a (level, exponent) pair; nullptr: fine.
+static const char* eudArgError(double level, double exponent) {
+    if (!std::isfinite(level) || !(level > 0.0)) return "the dose level must be finite and greater than 0";
+    if (!std::isfinite(exponent) || !(std::fabs(exponent) >= 0.0625 && std::fabs(exponent) <= 64.0)) return "|exponent| must lie in [2^-4, 64]";
+    return nullptr;
+}
+
+int rtd_objective_add_eud_term(rtd_handle hh, rtd_objective oo, const rtd_objective_eud_term* t) {
+    auto* h = reinterpret_cast<rtd_handle_impl*>(hh);
+    auto* o = reinterpret_cast<rtd_objective_impl*>(oo);
+    if (!h) return RTD_ERR_INVALID_ARG;
+    if (!o || !t) return fail(h, RTD_ERR_INVALID_ARG, "rtd_objective_add_eud_term: null pointer");
+    if (t->kind < RTD_OBJ_SQ_EUD || t->kind > RTD_OBJ_SQ_MIN_EUD)
+        return fail(h, RTD_ERR_INVALID_ARG, "rtd_objective_add_eud_term: the kind must be RTD_OBJ_SQ_EUD, RTD_OBJ_SQ_MAX_EUD or RTD_OBJ_SQ_MIN_EUD");
+    if (t->roi < 0 || (size_t)t->roi >= o->rois.size()) return fail(h, RTD_ERR_INVALID_ARG, "rtd_objective_add_eud_term: unknown ROI");
+    if (!(t->weight > 0.0) || !std::isfinite(t->weight)) return fail(h, RTD_ERR_INVALID_ARG, "rtd_objective_add_eud_term: the weight must be positive and finite");
+    if (const char* why = eudArgError(t->dose_level, t->exponent)) return fail(h, RTD_ERR_INVALID_ARG, std::string("rtd_objective_add_eud_term: ") + why);
+    if (t->reserved != 0.0) return fail(h, RTD_ERR_INVALID_ARG, "rtd_objective_add_eud_term: reserved must be 0");
+    if (o->terms.size() >= (size_t)kObjMaxTerms) return fail(h, RTD_ERR_INVALID_ARG, "rtd_objective_add_eud_term: more than RTD_OBJ_MAX_TERMS terms");
+    o->terms.push_back(rtd_objective_term{t->kind, t->roi, t->weight, t->dose_level});
+    o->vfrac.push_back(0.0);
+    o->expo.push_back(t->exponent);
+    o->built = false;
+    return RTD_OK;
+}
+
+int rtd_objective_eud(rtd_handle hh, rtd_objective oo, const float* dev_dose, const rtd_eud_query* queries, uint32_t n, double* dev_out) {
+    auto* h = reinterpret_cast<rtd_handle_impl*>(hh);
+    auto* o = reinterpret_cast<rtd_objective_impl*>(oo);
+    if (!h) return RTD_ERR_INVALID_ARG;
+    if (!o || !dev_dose || !queries || !dev_out) return fail(h, RTD_ERR_INVALID_ARG, "rtd_objective_eud: null pointer");
+    if (n < 1 || n > RTD_EUD_MAX_QUERIES) return fail(h, RTD_ERR_INVALID_ARG, "rtd_objective_eud: 1 to RTD_EUD_MAX_QUERIES queries");
+    for (uint32_t q = 0; q < n; ++q) {
+        if (queries[q].roi < 0 || (size_t)queries[q].roi >= o->rois.size()) return fail(h, RTD_ERR_INVALID_ARG, "rtd_objective_eud: unknown ROI");
+        if (queries[q].reserved != 0) return fail(h, RTD_ERR_INVALID_ARG, "rtd_objective_eud: reserved must be 0");
+        if (const char* why = eudArgError(queries[q].dose_level, queries[q].exponent)) return fail(h, RTD_ERR_INVALID_ARG, std::string("rtd_objective_eud: ") + why);
+    }
+    RTD_HIP(h, hipSetDevice(h->device));
+    const int st = buildEud(h, o);
+    if (st != RTD_OK) return st;
+    EudSel sel{};
+    for (uint32_t q = 0; q < n; ++q) {
+        const size_t r = (size_t)queries[q].roi;
+        sel.off[q] = o->roiOff[r]; sel.n[q] = o->roiOff[r + 1] - o->roiOff[r]; sel.slot[q] = (int)q; sel.kind[q] = -1;
+        sel.level[q] = queries[q].dose_level; sel.expo[q] = queries[q].exponent;
+    }
+    return eudSelect(h, o, dev_dose, sel, (int)n, dev_out);
 }
 
 int rtd_objective_dvh(rtd_handle hh, rtd_objective oo, const float* dev_dose, uint32_t n_bins, double dose_max, uint32_t* dev_counts) {

@@ -5,7 +5,7 @@
 //                   terms in term order -> g[v] (a float64 sum rounded once), and per term the sum of phi over the block (wave butterfly,
 //                   then the four wave sums through LDS);
 //   k_obj_reduce    one wave per term: the block sums (block b to lane b mod 64, ascending, butterfly), times weight / N; the terms
-//                   added in term order -> values[0];
+//                   added in term order -> values[0]; k_obj_reduce_eud is the same body for an objective with EUD terms (section 20);
 //   k_opt_partials  one wave per chunk of kOptChunk entries of the concatenated weights: <s, s>, <s, y> and max |P(w - grad) - w|;
 //   k_opt_step      one wave: the chunk results, the objective value and the state record -> this iteration's decisions (improved?
 //                   guard? alpha), the history entry;
@@ -19,7 +19,9 @@ namespace rtd {
 constexpr int kObjMaxTerms = 64;      // RTD_OBJ_MAX_TERMS
 constexpr int kOptChunk = 2048;       // entries per chunk of k_opt_partials (32 per lane), as kDijApChunk
 
-struct ObjTerm { double level, c, wn; int kind, pad; };   // c = 2 weight / N, wn = weight / N (host, float64)
+struct ObjTerm { double level, c, wn; int kind, pad; };   // c = 2 weight / N, wn = weight / N (host, float64); an EUD term: c = its exponent
+
+__device__ inline double eudVoxelGrad(double d, double level, double a, double K);   // rtd_eud.hpp
 
 // What an iteration decides, and what the next one needs of it.
 struct OptState {
@@ -45,10 +47,14 @@ __device__ inline double optWaveMax(double v) {
 // partial[t * nBlocks + block] = the block's sum of phi_t. Threads past the union and voxels outside a term add +0.0 (exact).
 // kDvh: the objective has DVH terms (RTD_OBJ_MAX_DVH / _MIN_DVH, rtd_dvh.hpp); thr[t] is then term t's dose at volume of this dose.
 // Without them the instantiation is the kernel as it was, and thr is not read.
-template <bool kDvh>
+// kEud: the objective has EUD terms (RTD_OBJ_SQ_EUD / _SQ_MAX_EUD / _SQ_MIN_EUD, rtd_eud.hpp); eud[3 t + 1] is then term t's K of this
+// dose, left by k_eud_finish. Such a term adds +0.0 to the partials (k_obj_reduce_eud takes its value from eud) and K (p / x) to g.
+// Without them nothing of this is compiled in, and eud is not read.
+template <bool kDvh, bool kEud = false>
 __global__ __launch_bounds__(256) void k_obj_eval(const int* __restrict__ uv, const int* __restrict__ tPtr, const unsigned char* __restrict__ tIdx,
                                                   const ObjTerm* __restrict__ terms, int nTerms, int nU, const float* __restrict__ dose,
-                                                  float* __restrict__ g, double* __restrict__ partial, int nBlocks, const float* __restrict__ thr) {
+                                                  float* __restrict__ g, double* __restrict__ partial, int nBlocks, const float* __restrict__ thr,
+                                                  const double* __restrict__ eud) {
     __shared__ double sh[4][kObjMaxTerms];
     const int i = blockIdx.x * 256 + threadIdx.x, lane = threadIdx.x % 64, wave = threadIdx.x / 64;
     int v = 0, e = 0, end = 0;
@@ -63,6 +69,7 @@ __global__ __launch_bounds__(256) void k_obj_eval(const int* __restrict__ uv, co
             if (mine) {
                 const ObjTerm tm = terms[t];
                 if (tm.kind == RTD_OBJ_MEAN) { phi = d; gs += tm.wn; }
+                else if (kEud && tm.kind >= RTD_OBJ_SQ_EUD) gs += eudVoxelGrad(d, tm.level, tm.c, eud[3 * t + 1]);
                 else if (kDvh && tm.kind >= RTD_OBJ_MAX_DVH) {
                     const double D = (double)thr[t];
                     double x = d;                                     // (a NaN stays a NaN)
@@ -90,16 +97,22 @@ __global__ __launch_bounds__(256) void k_obj_eval(const int* __restrict__ uv, co
     if (t < nTerms) partial[(size_t)t * nBlocks + blockIdx.x] = (sh[0][t] + sh[1][t]) + (sh[2][t] + sh[3][t]);
 }
 
-// One block: wave w takes the terms w, w + 4, ...; values[1 + t] = wn_t * sum, values[0] = their sum in term order.
-__global__ __launch_bounds__(256) void k_obj_reduce(const double* __restrict__ partial, int nBlocks, const ObjTerm* __restrict__ terms, int nTerms,
-                                                    double* __restrict__ values) {
+// One block: wave w takes the terms w, w + 4, ...; values[1 + t] = wn_t * sum, values[0] = their sum in term order. kEud: the value of
+// an EUD term is eud[3 t + 2] (k_eud_finish) instead; the sum in term order is the same.
+template <bool kEud>
+__device__ inline void objReduce(const double* __restrict__ partial, int nBlocks, const ObjTerm* __restrict__ terms, int nTerms,
+                                 double* __restrict__ values, const double* __restrict__ eud) {
     __shared__ double sh[kObjMaxTerms];
     const int lane = threadIdx.x % 64, wave = threadIdx.x / 64;
     for (int t = wave; t < nTerms; t += 4) {
         double acc = 0.0;
         for (int b = lane; b < nBlocks; b += 64) acc += partial[(size_t)t * nBlocks + b];
         acc = optWaveSum(acc);
-        if (lane == 0) { const double val = terms[t].wn * acc; sh[t] = val; values[1 + t] = val; }
+        if (lane == 0) {
+            double val = terms[t].wn * acc;
+            if (kEud && terms[t].kind >= RTD_OBJ_SQ_EUD) val = eud[3 * t + 2];
+            sh[t] = val; values[1 + t] = val;
+        }
     }
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -107,6 +120,14 @@ __global__ __launch_bounds__(256) void k_obj_reduce(const double* __restrict__ p
         for (int t = 0; t < nTerms; ++t) f += sh[t];
         values[0] = f;
     }
+}
+__global__ __launch_bounds__(256) void k_obj_reduce(const double* __restrict__ partial, int nBlocks, const ObjTerm* __restrict__ terms, int nTerms,
+                                                    double* __restrict__ values) {
+    objReduce<false>(partial, nBlocks, terms, nTerms, values, nullptr);
+}
+__global__ __launch_bounds__(256) void k_obj_reduce_eud(const double* __restrict__ partial, int nBlocks, const ObjTerm* __restrict__ terms, int nTerms,
+                                                        double* __restrict__ values, const double* __restrict__ eud) {
+    objReduce<true>(partial, nBlocks, terms, nTerms, values, eud);
 }
 
 // Zeroes the box's voxels of a volume (the row box of a field other than the first, in front of the forward product).

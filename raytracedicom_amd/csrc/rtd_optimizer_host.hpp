@@ -168,6 +168,7 @@ int optCreate(rtd_handle hh, const rtd_field* fields, uint32_t n_fields, const r
     }
     if (o->terms.empty()) return fail(h, RTD_ERR_INVALID_ARG, "rtd_optimizer_create: the objective has no terms");
     if (voxelwise && o->hasDvhTerms()) return fail(h, RTD_ERR_INVALID_ARG, "rtd_optimizer_create_voxelwise: an objective with DVH terms has no voxel-wise worst case");
+    if (voxelwise && o->hasEudTerms()) return fail(h, RTD_ERR_INVALID_ARG, "rtd_optimizer_create_voxelwise: an objective with EUD terms has no voxel-wise worst case");
     for (uint32_t i = 0; i < nAll; ++i)
         if (!reinterpret_cast<rtd_field_impl*>(fields[i])->dijDone)
             return fail(h, RTD_ERR_NOT_READY, "rtd_optimizer_create: a field has no dose-influence matrix (call rtd_field_dose_influence first)");

@@ -94,6 +94,8 @@ def lib():
         L.rtd_objective_add_dvh_term.argtypes = [vp, vp, C.POINTER(abi.RtdObjectiveDvhTerm)]
         L.rtd_objective_dose_at_volume.argtypes = [vp, vp, vp, C.POINTER(abi.RtdDvhQuery), C.c_uint32, vp]
         L.rtd_objective_dvh.argtypes = [vp, vp, vp, C.c_uint32, C.c_double, vp]
+        L.rtd_objective_add_eud_term.argtypes = [vp, vp, C.POINTER(abi.RtdObjectiveEudTerm)]
+        L.rtd_objective_eud.argtypes = [vp, vp, vp, C.POINTER(abi.RtdEudQuery), C.c_uint32, vp]
         L.rtd_default_optimizer_options.argtypes = [C.POINTER(abi.RtdOptimizerOptions)]
         L.rtd_default_optimizer_options.restype = None
         L.rtd_optimizer_create.argtypes = [vp, vpp, C.c_uint32, vp, C.POINTER(abi.RtdOptimizerOptions), vpp]
@@ -389,7 +391,8 @@ class Field:
 class Objective:
     """rtd_objective_*: ROIs and penalty terms on one dose grid; eval() gives the objective, its terms and the voxel gradient on the
     device. Kinds: abi.RTD_OBJ_SQ_DEVIATION / _SQ_OVERDOSE / _SQ_UNDERDOSE / _MEAN; through add_dvh_term abi.RTD_OBJ_MAX_DVH / _MIN_DVH.
-    dose_at_volume() and dvh() report on a dose volume in dose-volume terms."""
+    dose_at_volume() and dvh() report on a dose volume in dose-volume terms. Through add_eud_term abi.RTD_OBJ_SQ_EUD / _SQ_MAX_EUD /
+    _SQ_MIN_EUD; eud() reports the generalised equivalent uniform dose of ROIs."""
 
     def __init__(self, eng, dose_dims):
         self.eng = eng
@@ -432,6 +435,32 @@ class Objective:
             self.eng._check(lib().rtd_objective_dose_at_volume(self.eng._h, self._h, C.c_void_p(int(dev_dose)), arr, len(qs), C.c_void_p(int(do))))
             if own:
                 out = np.empty(len(qs), dtype=np.float32)
+                self.eng.to_host(out, do)
+                return out
+        finally:
+            if own:
+                self.eng.device_free(do)
+        return None
+
+    def add_eud_term(self, kind, roi, weight, level, exponent):
+        """A term on the ROI's generalised equivalent uniform dose E = level * mean((d / level)^exponent)^(1 / exponent):
+        RTD_OBJ_SQ_EUD (E equal to level), RTD_OBJ_SQ_MAX_EUD (at most) or RTD_OBJ_SQ_MIN_EUD (at least); weight * (E - level)^2. It
+        takes the next term number, like add_term."""
+        t = abi.RtdObjectiveEudTerm(int(kind), int(roi), float(weight), float(level), float(exponent), 0.0)
+        self.eng._check(lib().rtd_objective_add_eud_term(self.eng._h, self._h, C.byref(t)))
+        self.n_terms += 1
+
+    def eud(self, dev_dose, queries, dev_out=None):
+        """rtd_objective_eud: queries = [(roi, level, exponent), ...] (at most abi.RTD_EUD_MAX_QUERIES; level is the normalisation).
+        With dev_out (device pointer, float64[n]) asynchronous, returns None; without, returns the gEUDs as a float64 array."""
+        qs = list(queries)
+        arr = (abi.RtdEudQuery * max(1, len(qs)))(*[abi.RtdEudQuery(int(r), 0, float(lv), float(a)) for r, lv, a in qs])
+        own = dev_out is None
+        do = self.eng.device_alloc(8 * abi.RTD_EUD_MAX_QUERIES) if own else dev_out
+        try:
+            self.eng._check(lib().rtd_objective_eud(self.eng._h, self._h, C.c_void_p(int(dev_dose)), arr, len(qs), C.c_void_p(int(do))))
+            if own:
+                out = np.empty(len(qs), dtype=np.float64)
                 self.eng.to_host(out, do)
                 return out
         finally:
@@ -861,7 +890,7 @@ class Engine:
 
     def create_voxelwise_optimizer(self, scenario_fields, objective, options=None):
         """rtd_optimizer_create_voxelwise: the voxel-wise worst case over the scenarios (every voxel takes, per term, the scenario
-        dose that is worst for it). scenario_fields as create_robust_optimizer; the objective must not have DVH terms."""
+        dose that is worst for it). scenario_fields as create_robust_optimizer; the objective must not have DVH or EUD terms."""
         return Optimizer(self, None, objective, options, scenario_fields=scenario_fields, voxelwise=True)
 
     def dose_extremes(self, dose_ptrs, n_voxels, d_min=None, d_max=None):
