@@ -40,8 +40,7 @@ int rtd_field_dose_influence(rtd_handle hh, rtd_field ff, float rel_threshold, s
     { const int st = takeFindings(h, f, own); if (st != RTD_OK) return st; }
     if (own.errorFlags & kErrRadiusOverflow) return fail(h, RTD_ERR_RADIUS_OVERFLOW, "Found larger than allowed kernel superposition radius");
     const int rMax = own.maxRadius;
-    const int saveUniform = f->uniformHint, saveRadius = f->radiusHint;
-    const unsigned saveEpoch = f->hintEpoch;
+    const FieldHints savedHints = f->memory.savedHints();
     // 2. footprints, exactly as the convolution's loops visit the spots
     std::vector<int> footX(2 * nSpot / fc.spotNy), footY(2 * nSpot / fc.spotNx);
     {
@@ -108,7 +107,7 @@ int rtd_field_dose_influence(rtd_handle hh, rtd_field ff, float rel_threshold, s
         if (e == hipSuccess) e = hipStreamSynchronize(s);             // (the host vectors above are pageable)
         if (e != hipSuccess) hipFail(e);
         // the batches run without the field's hints: each one is planned (uniform-sigma detection, second sweep launch) on its own
-        f->uniformHint = -1; f->radiusHint = -1;
+        f->memory.forgetHints();
     }
     // 4. per batch: unit weights, owner map, forward + transfer into the scratch volume, split, clear of its dose box
     for (size_t k = 0; k < members.size() && st == RTD_OK; ++k) {
@@ -120,7 +119,7 @@ int rtd_field_dose_influence(rtd_handle hh, rtd_field ff, float rel_threshold, s
         k_dij_weights<<<(n + 255) / 256, 256, 0, s>>>(f->dSpotWeights, dList, n);
         k_dij_owner<<<n, 256, 0, s>>>(f->dDijOwner, bevW, f->dDijBoxes + 4 * first[k]);
         if ((e = hipGetLastError()) != hipSuccess) { hipFail(e); break; }
-        f->uniformHint = -1; f->radiusHint = -1;
+        f->memory.forgetHints();
         st = rtd_field_compute_bev(hh, ff);
         if (st == RTD_OK) st = transferImpl(hh, ff, f->dDijDose, nullptr, nullptr, false);
         if (st != RTD_OK) break;
@@ -142,7 +141,7 @@ int rtd_field_dose_influence(rtd_handle hh, rtd_field ff, float rel_threshold, s
         if (e == hipSuccess) e = hipMemcpyAsync(&count, f->dDijMisc, sizeof(int), hipMemcpyDeviceToHost, s);
         if (e == hipSuccess) e = hipStreamSynchronize(s);
         if (e != hipSuccess) { hipFail(e); break; }
-        sigmaRecordFinished(f, f->hState->errorFlags);                // (the batch's forward has drained: the later batches only replay)
+        f->memory.sigmaFinished(f->hState->errorFlags);               // (the batch's forward has drained: the later batches only replay)
         if ((size_t)(total + count) > f->dijCap) {                   // grow the batch-major staging geometrically (the stream is idle)
             size_t cap = f->dijCap;
             while (cap < (size_t)(total + count)) cap *= 2;
@@ -170,7 +169,7 @@ int rtd_field_dose_influence(rtd_handle hh, rtd_field ff, float rel_threshold, s
         }
         const std::string keep = h->error;
         const hipError_t re = hipMemcpyAsync(f->dSpotWeights, f->dDijSave, nSpot * sizeof(float), hipMemcpyDeviceToDevice, s);
-        f->uniformHint = saveUniform; f->radiusHint = saveRadius; f->hintEpoch = saveEpoch;
+        f->memory.restoreHints(savedHints);
         int rst = re == hipSuccess ? rtd_field_compute_bev(hh, ff) : RTD_ERR_HIP;
         if (rst == RTD_OK && hipStreamSynchronize(s) != hipSuccess) rst = RTD_ERR_HIP;
         if (st == RTD_OK && rst != RTD_OK) { st = rst; if (h->error == keep) h->error = "HIP error (dose influence): restoring the field's forward failed"; }

@@ -48,6 +48,7 @@
 #include "rtd_roi_ops.hpp"
 #include "rtd_target.hpp"
 #include "rtd_gamma.hpp"
+#include "rtd_field_memory.hpp"
 #include "rtd_engine_impl.hpp"
 
 namespace {
@@ -415,10 +416,11 @@ int rtd_field_release(rtd_handle hh, rtd_field ff) {
     if (f->remote || f->fc.nuclearCorr || h->fieldCache.size() >= 4) return rtd_field_destroy(hh, ff);
     (void)hipSetDevice(h->device);
     (void)hipStreamSynchronize(h->stream);      // its kernels have drained: the next owner uploads with plain copies
+    // The next owner of the workspace is a new field object, and this one is deleted when it takes over: nothing carries over, and
+    // nothing in between reads these. They make a call on the stale field handle answer "not computed" instead of using freed buffers.
     f->computed = false; f->transferred = false;
-    f->traceLaunched = false; f->traceUsable = false;   // (the next owner of the workspace is a new field object anyway: nothing carries over)
     freeBuffers(f, kGradient | kDiag | kDij | kDijOut | kTarget | kSigmaRec);   // (not part of the shape's workspace)
-    f->sigRecSteps = 0; f->sigRecLaunched = false; f->sigRecUsable = false; f->launchedSigma = 0;
+    f->memory = FieldMemory{};
     f->gradDone = false; f->targetProjected = false; f->targetSelected = false;
     f->dijDone = false; f->dijPrepared = false; f->dijCap = 0; f->dijNnz = 0; f->dijBatchOf.clear();
     f->released = shapeCounts(f);
@@ -529,8 +531,8 @@ static int createField(rtd_handle hh, const rtd_beam* b, const uint32_t dose_dim
     }
 
     if (remote) {
-        hipError_t e = hipEventCreate(&f->ev[0]);
-        if (e == hipSuccess) e = hipEventCreate(&f->ev[6]);
+        hipError_t e = hipEventCreate(&f->ev[kEvStart]);
+        if (e == hipSuccess) e = hipEventCreate(&f->ev[kEvTransfer]);
         if (e != hipSuccess) { h->error = std::string("HIP error: ") + hipGetErrorString(e); rtd_field_destroy(hh, reinterpret_cast<rtd_field>(f)); return RTD_ERR_HIP; }
         *out = reinterpret_cast<rtd_field>(f);
         return RTD_OK;
@@ -706,12 +708,12 @@ static int ensureCtBox(rtd_handle_impl* h, rtd_field_impl* f) {
 // What the stages of one compute share.
 struct ComputeJob {
     rtd_handle_impl* h; rtd_field_impl* f;
-    bool reuse, tryUniform, knownUniform, timing;
-    int sigma;                    // k_fill's sigma role: 0 walks, 1 records and replays, 2 replays (sigmaMode)
+    const ComputeInFlight& is;    // what this launch was decided to be (f->memory.flight)
+    bool timing;
     ResetJob resetJob;
     // Stage boundaries are the start / stop timestamps of the kernels themselves (hipExtLaunchKernelGGL), not event
     // packets between them: no barrier packet and no idle gap is inserted into the stream by the timing.
-    hipEvent_t ev(int i) const { return timing ? f->ev[i] : nullptr; }
+    hipEvent_t ev(FieldEvent i) const { return timing ? f->ev[i] : nullptr; }
 };
 
 // K1: the tracer's sampling pass in the field's lane direction, then the scan.
@@ -723,24 +725,24 @@ static int launchTrace(const ComputeJob& c) {
     const size_t dLds = lutLds + (size_t)3 * kTdSteps * kTdPitch * sizeof(float);
     if (f->traceMode == 2 && dLds <= 150 * 1024) {
         RTD_HIP(h, raiseLdsCap(h, k_trace_sample_d, dLds));
-        launchK(k_trace_sample_d, dim3((unsigned)(fc.W / kTdRays), (unsigned)fc.H, (unsigned)((fc.S + kTdSteps - 1) / kTdSteps)), dim3(kTdThreads), dLds, s, f->ev[0], nullptr,
+        launchK(k_trace_sample_d, dim3((unsigned)(fc.W / kTdRays), (unsigned)fc.H, (unsigned)((fc.S + kTdSteps - 1) / kTdSteps)), dim3(kTdThreads), dLds, s, f->ev[kEvStart], nullptr,
                 (const float*)h->dCt, (int)h->ctDims[0], (int)h->ctDims[1], (int)h->ctDims[2], h->lut, f->tracer, fc.W, fc.H, f->dDensity, f->dWepl, f->dIdd,
                 f->dRrl, h->rrlScale, f->dState, (const float*)f->dSegPos, f->traceDiagB);
     } else if (f->traceMode == 1 && tLds <= 144 * 1024) {
         // the beam runs along the CT x axis: lanes on consecutive steps of one ray (see k_trace_sample_t); 16 rays per block
         // measured best (4 .. 12 rays: 0.107 - 0.133 ms for the stage, 16: 0.100 ms)
         RTD_HIP(h, raiseLdsCap(h, k_trace_sample_t, tLds));
-        launchK(k_trace_sample_t, dim3((unsigned)((f->R + kTrRays - 1) / kTrRays)), dim3(64, kTrRays), tLds, s, f->ev[0], nullptr,
+        launchK(k_trace_sample_t, dim3((unsigned)((f->R + kTrRays - 1) / kTrRays)), dim3(64, kTrRays), tLds, s, f->ev[kEvStart], nullptr,
                 (const float*)h->dCt, (int)h->ctDims[0], (int)h->ctDims[1], (int)h->ctDims[2], h->lut, f->tracer, fc.W, fc.H, f->dDensity, f->dWepl, f->dIdd,
                 f->dRrl, h->rrlScale, f->dState);
     } else {
-        launchK(k_trace_sample, dim3((unsigned)(f->R / 256), (fc.S + kTraceSeg * kTraceSegsPerBlock - 1) / (kTraceSeg * kTraceSegsPerBlock)), dim3(256, kTraceSegsPerBlock), lutLds, s, f->ev[0], nullptr,
+        launchK(k_trace_sample, dim3((unsigned)(f->R / 256), (fc.S + kTraceSeg * kTraceSegsPerBlock - 1) / (kTraceSeg * kTraceSegsPerBlock)), dim3(256, kTraceSegsPerBlock), lutLds, s, f->ev[kEvStart], nullptr,
                 (const float*)h->dCt, (int)h->ctDims[0], (int)h->ctDims[1], (int)h->ctDims[2], h->lut, f->tracer, fc.W, fc.H, f->dDensity, f->dWepl, f->dIdd,
                 f->dRrl, h->rrlScale, f->dState, (const float*)f->dSegPos);
     }
     constexpr size_t scanLds = 2 * 2 * kScanChunk * 64 * sizeof(float);   // two buffers of 64 KiB: above the 64 KiB default cap of dynamic LDS
     RTD_HIP(h, raiseLdsCap(h, k_trace_scan, scanLds));
-    launchK(k_trace_scan, dim3((unsigned)(f->R / 64)), dim3(64, kScanWaves), scanLds, s, nullptr, c.ev(1), (const float*)f->dIdd, f->dWepl, fc.W, fc.H,
+    launchK(k_trace_scan, dim3((unsigned)(f->R / 64)), dim3(64, kScanWaves), scanLds, s, nullptr, c.ev(kEvTrace), (const float*)f->dIdd, f->dWepl, fc.W, fc.H,
             (unsigned)fc.S, f->dFirstInside, f->dFirstOutside, f->dState, f->dBlockWeplMin, c.resetJob);
     return RTD_OK;
 }
@@ -749,51 +751,42 @@ static int launchTrace(const ComputeJob& c) {
 static void launchPlanConv(const ComputeJob& c) {
     rtd_field_impl* f = c.f; const FieldConst& fc = f->fc; hipStream_t s = c.h->stream;
     const dim3 blk(kSuperpTileX, kSuperpTileY);
-    if (c.reuse) {
+    if (c.is.reuse) {
         // the spot -> ray convolution is the first launch; it carries the reset of what k_fill and the superposition's plan accumulate into
-        launchK(k_reset_conv, dim3(fc.W / 32, (fc.H / 8 + 3) / 4, fc.L), dim3(1024), (size_t)4 * fc.spotNy * 32 * sizeof(float), s, f->ev[0], c.ev(2),
+        launchK(k_reset_conv, dim3(fc.W / 32, (fc.H / 8 + 3) / 4, fc.L), dim3(1024), (size_t)4 * fc.spotNy * 32 * sizeof(float), s, f->ev[kEvStart], c.ev(kEvConv),
                 (const float*)f->dSpotWeights, f->dRayWeights, (const LayerPlan*)f->dLayers, f->dState, c.resetJob, fc);
     } else if (fc.spotNy <= kPlanConvMaxRows && !f->sw.separatePlan) {
         // the plan and the spot -> ray convolution in one launch (k_plan_conv): neither reads what the other writes
-        launchK(k_plan_conv, dim3(fc.W / 32, (fc.H / 8 + 3) / 4, fc.L + 1), dim3(1024), (size_t)4 * fc.spotNy * 32 * sizeof(float), s, nullptr, c.ev(2),
+        launchK(k_plan_conv, dim3(fc.W / 32, (fc.H / 8 + 3) / 4, fc.L + 1), dim3(1024), (size_t)4 * fc.spotNy * 32 * sizeof(float), s, nullptr, c.ev(kEvConv),
                 (const float*)f->dSpotWeights, f->dRayWeights, f->dLayers, f->dState, (const float*)f->dBlockWeplMin, (int)(f->R / 64), f->dWeplMin, fc);
     } else {
         k_plan<<<1, 1024, 0, s>>>(f->dState, f->dLayers, (const float*)f->dBlockWeplMin, (int)(f->R / 64), f->dWeplMin, fc);
         if (fc.spotNy <= kConvMaxRows) {
             // both passes in one launch, the x pass staged in LDS (k_conv)
-            launchK(k_conv, dim3(fc.W / 32, fc.H / 8, fc.L), blk, (size_t)fc.spotNy * 32 * sizeof(float), s, nullptr, c.ev(2), (const float*)f->dSpotWeights,
+            launchK(k_conv, dim3(fc.W / 32, fc.H / 8, fc.L), blk, (size_t)fc.spotNy * 32 * sizeof(float), s, nullptr, c.ev(kEvConv), (const float*)f->dSpotWeights,
                     f->dRayWeights, (const LayerPlan*)f->dLayers, (const FieldState*)f->dState, fc);
         } else {
             k_conv_x<<<dim3(fc.W / 32, (fc.spotNy + 7) / 8, fc.L), blk, 0, s>>>(f->dSpotWeights, f->dConvInterm, f->dLayers, f->dState, fc);
-            launchK(k_conv_y, dim3(fc.W / 32, fc.H / 8, fc.L), blk, 0, s, nullptr, c.ev(2), (const float*)f->dConvInterm, f->dRayWeights,
+            launchK(k_conv_y, dim3(fc.W / 32, fc.H / 8, fc.L), blk, 0, s, nullptr, c.ev(kEvConv), (const float*)f->dConvInterm, f->dRayWeights,
                     (const LayerPlan*)f->dLayers, (const FieldState*)f->dState, fc);
         }
     }
 }
 
-// The sigma record of a compute that reuses the trace (rtd_engine_impl.hpp) -> 0 walk, 1 record and replay, 2 replay. Allocates the
-// record when the field has none that fits its plan; a failed allocation is no error: the field keeps walking.
-static int sigmaMode(rtd_handle_impl* h, rtd_field_impl* f, bool reuse) {
-    if (!reuse || f->sw.noSigmaReuse || f->sigRecFailed) return 0;
-    const size_t need = (size_t)std::max(f->planSteps, 1);
-    if (f->sigRecSteps >= need && f->sigRecUsable && f->sigRecEpoch == h->inputEpoch) return 2;
-    if (f->sigRecSteps < need) {
-        if (f->dSigRec) {                                             // a smaller record is replaced: an earlier compute may still read it
-            (void)hipStreamSynchronize(h->stream);
-            freeBuffers(f, kSigmaRec);
-        }
-        f->sigRecSteps = need;
-        hipError_t e = hipMalloc((void**)&f->dSigRec, need * f->R * (size_t)f->fc.L * sizeof(unsigned int));
-        if (e == hipSuccess) e = hipMalloc((void**)&f->dSigRecLast, f->R * (size_t)f->fc.L * sizeof(int));
-        if (e != hipSuccess) {
-            (void)hipGetLastError();                                  // (out of memory is not sticky: cleared here)
-            freeBuffers(f, kSigmaRec);
-            f->sigRecSteps = 0; f->sigRecFailed = true; f->sigRecLaunched = false; f->sigRecUsable = false;
-            return 0;
-        }
+// The sigma record of a field that has none that fits its plan (SigmaRecord::kAllocateThenRecord, rtd_field_memory.hpp): `need` steps
+// long. A failed allocation is no error: the field keeps walking.
+static void allocSigmaRecord(rtd_handle_impl* h, rtd_field_impl* f, size_t need) {
+    if (f->dSigRec) {                                                 // a smaller record is replaced: an earlier compute may still read it
+        (void)hipStreamSynchronize(h->stream);
+        freeBuffers(f, kSigmaRec);
     }
-    f->sigRecLaunched = true; f->sigRecEpoch = h->inputEpoch; f->sigRecUsable = false;
-    return 1;
+    hipError_t e = hipMalloc((void**)&f->dSigRec, need * f->R * (size_t)f->fc.L * sizeof(unsigned int));
+    if (e == hipSuccess) e = hipMalloc((void**)&f->dSigRecLast, f->R * (size_t)f->fc.L * sizeof(int));
+    if (e != hipSuccess) {
+        (void)hipGetLastError();                                      // (out of memory is not sticky: cleared here)
+        freeBuffers(f, kSigmaRec);
+        f->memory.sigmaAllocationFailed();
+    }
 }
 
 // K5: the fill.
@@ -803,20 +796,20 @@ static void launchFill(const ComputeJob& c) {
     // (layer, tile, role) items: sigma walk and dose walk of every tile; placement is decided in the kernel
     const dim3 fillGrid(2 * (fc.W / kSuperpTileX) * (fc.H / kSuperpTileY) * fc.L), fillBlk(kSuperpTileX, kSuperpTileY);
     const NucFill nucFill{f->dNucSpotIdx, f->dNucRayWeights, f->dNucIdd, f->dNucRs};
-    const SigmaRec rec{f->dSigRec, f->dSigRecLast, (int)f->sigRecSteps};
+    const SigmaRec rec{f->dSigRec, f->dSigRecLast, (int)f->memory.sigmaSteps};
     auto launchFillOn = [&](auto kern, dim3 grid, size_t lds, hipEvent_t stopEv) {
         launchK(kern, grid, fillBlk, lds, h->stream, nullptr, stopEv, (const float*)f->dDensity, (const float*)f->dWepl, (const float*)f->dRrl, f->dIdd,
                 f->dRSigma, (const float*)f->dRayWeights, (const int*)f->dFirstInside, (const int*)f->dFirstOutside,
-                f->dFirstPassive, f->dTileRad, f->dLayers, f->dState, h->lut, f->fillGeom, fc, (const float*)f->dStepTab, f->dActive, h->numCUs, f->dFillDbg, nucFill, f->dSigMin, f->dSigMax, c.tryUniform ? 1 : 0,
+                f->dFirstPassive, f->dTileRad, f->dLayers, f->dState, h->lut, f->fillGeom, fc, (const float*)f->dStepTab, f->dActive, h->numCUs, f->dFillDbg, nucFill, f->dSigMin, f->dSigMax, c.is.tryUniform ? 1 : 0,
                 f->sw.noFillCompact ? 0 : 1, rec);
     };
-    auto launchFill = [&](auto kern, size_t lds) { launchFillOn(kern, fillGrid, lds, c.ev(3)); };
+    auto launchFill = [&](auto kern, size_t lds) { launchFillOn(kern, fillGrid, lds, c.ev(kEvFill)); };
     const bool ldsLut = fillLds <= 56 * 1024;     // (+ ~1 KiB of static arrays: stays under the 64 KiB default cap of a block's LDS)
     constexpr size_t sigLds = (size_t)2 * kFillBatch * 256 * sizeof(float);   // the sigma walk's exchange buffers share the dynamic LDS with the dose walk's LUT rows
     const size_t dynLds = std::max(sigLds, ldsLut ? fillLds : (size_t)0);
     // the record pass: the sigma walk of every (layer, tile) alone, in front of the fill that replays it (inside the fill's timing bucket)
-    if (c.sigma == 1) launchFillOn((k_fill<false, false, kFillRecord>), dim3(fillGrid.x / 2), (size_t)0, nullptr);
-    if (c.sigma) { if (ldsLut) launchFill((k_fill<true, false, kFillReplay>), dynLds); else launchFill((k_fill<false, false, kFillReplay>), dynLds); }
+    if (c.is.sigma == 1) launchFillOn((k_fill<false, false, kFillRecord>), dim3(fillGrid.x / 2), (size_t)0, nullptr);
+    if (c.is.sigma) { if (ldsLut) launchFill((k_fill<true, false, kFillReplay>), dynLds); else launchFill((k_fill<false, false, kFillReplay>), dynLds); }
     else if (fc.nuclearCorr) { if (ldsLut) launchFill((k_fill<true, true>), dynLds); else launchFill((k_fill<false, true>), dynLds); }
     else { if (ldsLut) launchFill((k_fill<true, false>), dynLds); else launchFill((k_fill<false, false>), dynLds); }
 }
@@ -824,7 +817,7 @@ static void launchFill(const ComputeJob& c) {
 // K6, K7: the superposition's plan, the halo, and the superposition itself (uniform, sweep, big sweep or mfma).
 static int launchSuperposition(const ComputeJob& c) {
     rtd_handle_impl* h = c.h; rtd_field_impl* f = c.f; const FieldConst& fc = f->fc; hipStream_t s = h->stream;
-    const bool tryUniform = c.tryUniform, knownUniform = c.knownUniform;
+    const bool tryUniform = c.is.tryUniform, knownUniform = c.is.knownUniform;
     if (fc.nuclearCorr) {
         // the halo's plan runs first: its radius overflow (kernel_wrapper.cu:984) is reported in the primary state, which k_ks_plan mirrors
         k_nuc_plan<<<1, 256, 0, s>>>(f->dState, f->dStateNuc, (const LayerPlan*)f->dLayers, (const float*)f->dNucRs, f->dNucEffT, fc,
@@ -836,16 +829,16 @@ static int launchSuperposition(const ComputeJob& c) {
     // Once the host knows that the field is not a uniform-sigma one (and without the halo), the sweep's launch plans for itself
     // (k_superpose_sweep<true>: its block 0 is the plan): one launch and its gap less on the critical path.
     const bool selfPlan = f->sweepEnabled && !tryUniform && !fc.nuclearCorr && !f->sw.separateKsPlan;
-    f->selfPlanned = selfPlan;
+    f->memory.planInsideSweep(selfPlan);
     // (a field that may be a uniform-sigma one has its 2 x L x S sigma extremes compared by this one block: 1024 threads make that
     //  three memory round trips instead of ten)
-    if (!selfPlan) launchK(k_ks_plan, dim3(1), dim3(tryUniform ? 1024 : 256), 0, s, nullptr, f->ev[4], ksArgs, fc);
+    if (!selfPlan) launchK(k_ks_plan, dim3(1), dim3(tryUniform ? 1024 : 256), 0, s, nullptr, f->ev[kEvKsPlan], ksArgs, fc);
     if (fc.nuclearCorr) {
         const int nPix = (fc.nucW + 2 * kMaxSuperpR) * (fc.nucH + 2 * kMaxSuperpR);
         k_nuc_superpose<<<(nPix + 255) / 256, 256, 0, s>>>((const float*)f->dNucIdd, (const float*)f->dNucRs, (const int*)f->dNucEffT,
                                                            (const FieldState*)f->dStateNuc, fc, f->dNucBev);
     }
-    hipEvent_t ksStart = c.ev(7);
+    hipEvent_t ksStart = c.ev(kEvSuperpStart);
     if (tryUniform) {
         // A field with one sigma per slice (water) is superposed as a separable convolution; whether this field is one is known
         // on the device only (FieldState::uniformField): the launch returns at once otherwise, k_superpose_mfma below when it is.
@@ -856,12 +849,12 @@ static int launchSuperposition(const ComputeJob& c) {
             const int nPartsU4 = (nYB + kU4RB - 1) / kU4RB;
             RTD_HIP(h, raiseLdsCap(h, k_superpose_uniform4, (kU4Rows + kU4Slack) * (16 * (kU2XB - 4) + 16) * sizeof(float)));   // (the widest grid's)
             launchK(k_superpose_uniform4, dim3((unsigned)(fc.S * nPartsU4)), dim3(64 * kU4Waves), (size_t)(kU4Rows + kU4Slack) * (fc.W + 16) * sizeof(float), s, ksStart,
-                    knownUniform ? f->ev[5] : nullptr, (const float*)f->dIdd, (const LayerPlan*)f->dLayers, (const FieldState*)f->dState, fc,
+                    knownUniform ? f->ev[kEvSuperp] : nullptr, (const float*)f->dIdd, (const LayerPlan*)f->dLayers, (const FieldState*)f->dState, fc,
                     (const unsigned int*)f->dSigMin, (const float*)f->dStepTab, f->dBev, f->dUniDbg);
         } else {
             // (rtd_uniform.hpp: one wave per 16 rows x 192 columns of a slice, no staging, no barrier in its loop)
             const int nXS = (fc.bevW + 16 * kU2XB - 1) / (16 * kU2XB), nParts = ((fc.bevH + 15) / 16 + 3) / 4;
-            launchK(k_superpose_uniform2, dim3((unsigned)(fc.S * nXS * nParts)), dim3(256), 0, s, ksStart, knownUniform ? f->ev[5] : nullptr, (const float*)f->dIdd,
+            launchK(k_superpose_uniform2, dim3((unsigned)(fc.S * nXS * nParts)), dim3(256), 0, s, ksStart, knownUniform ? f->ev[kEvSuperp] : nullptr, (const float*)f->dIdd,
                     (const LayerPlan*)f->dLayers, (const FieldState*)f->dState, fc, (const unsigned int*)f->dSigMin, (const float*)f->dStepTab, f->dBev, nXS);
         }
         ksStart = nullptr;
@@ -871,9 +864,8 @@ static int launchSuperposition(const ComputeJob& c) {
     // such a rest is known on the device (FieldState::maxRadius, k_ks_plan): the second launch returns at once if not — and is left out
     // once a finished compute has told the host, under the same CT / LUTs / options, that it does not. (RTD_NO_SWEEP: k_superpose_mfma,
     // round 2's output-stationary kernel, takes everything — kept as a second implementation the tests compare the sweep with.)
-    const bool radiusKnown = f->radiusHint >= 0 && f->hintEpoch == h->inputEpoch;
     const bool runSweep = !knownUniform && f->sweepEnabled;
-    const bool runBig = runSweep && !(radiusKnown && f->radiusHint <= kSwMaxR);
+    const bool runBig = runSweep && !f->memory.radiusWithin(kSwMaxR);
     const bool runMfma = !knownUniform && !f->sweepEnabled;
     if (runSweep) {
         constexpr size_t swLds = (size_t)kSwLdsWords * sizeof(float);
@@ -882,7 +874,7 @@ static int launchSuperposition(const ComputeJob& c) {
         RTD_HIP(h, raiseLdsCap(h, k_superpose_sweep<true>, swLds));
         const unsigned nSwBlocks = (unsigned)(fc.S * f->swPX * f->swPY * f->swGroups) + (selfPlan ? 1u : 0u);
         auto launchSweep = [&](auto kern) {
-            launchK(kern, dim3(nSwBlocks), dim3(64 * kSwWaves), swLds, s, ksStart, runBig ? nullptr : f->ev[5],
+            launchK(kern, dim3(nSwBlocks), dim3(64 * kSwWaves), swLds, s, ksStart, runBig ? nullptr : f->ev[kEvSuperp],
                     (const float*)f->dIdd, (const float*)f->dRSigma, (const unsigned char*)f->dTileRad, (const LayerPlan*)f->dLayers, (const FieldState*)f->dState, fc,
                     f->swGroups, f->swPX, f->swPY, (const int*)f->dActive, f->dSwSlots, f->dSwCount, f->dBev, f->dSweepDbg, (const KsPlanArgs*)f->dKsArgs);
         };
@@ -892,7 +884,7 @@ static int launchSuperposition(const ComputeJob& c) {
     if (runBig) {
         constexpr size_t bgLds = (size_t)kBgLdsWords * sizeof(float);
         RTD_HIP(h, raiseLdsCap(h, k_superpose_sweep_big, bgLds));
-        launchK(k_superpose_sweep_big, dim3((unsigned)(fc.S * f->swPX * f->swPY * f->bgGroups)), dim3(64 * kSwWaves), bgLds, s, nullptr, f->ev[5],
+        launchK(k_superpose_sweep_big, dim3((unsigned)(fc.S * f->swPX * f->swPY * f->bgGroups)), dim3(64 * kSwWaves), bgLds, s, nullptr, f->ev[kEvSuperp],
                 (const float*)f->dIdd, (const float*)f->dRSigma, (const unsigned char*)f->dTileRad, (const LayerPlan*)f->dLayers, (const FieldState*)f->dState, fc,
                 f->bgGroups, f->swPX, f->swPY, (const int*)f->dActive, f->dSwSlotsBig, f->dSwCountBig, f->dBev, f->dSweepBigDbg);
     }
@@ -903,7 +895,7 @@ static int launchSuperposition(const ComputeJob& c) {
         // few layers -> few, long work items: deal each item's chunks to 2 or 4 waves (the live items are a fraction of nItems)
         const int split = nItems >= 48 * 1024 ? 1 : (nItems >= 20 * 1024 ? 2 : 4);
         auto launchKs = [&](auto kernel) {
-            launchK(kernel, dim3(nItems), dim3(64 * split), 0, s, ksStart, f->ev[5], (const float*)f->dIdd, (const float*)f->dRSigma,
+            launchK(kernel, dim3(nItems), dim3(64 * split), 0, s, ksStart, f->ev[kEvSuperp], (const float*)f->dIdd, (const float*)f->dRSigma,
                     f->dBevPart, (const unsigned char*)f->dTileRad, (const LayerPlan*)f->dLayers, (const FieldState*)f->dState, fc, nTX, nTY, G,
                     (const int*)f->dActive, f->dBev, f->dNodeCount, -1);
         };
@@ -925,32 +917,20 @@ int rtd_field_compute_bev(rtd_handle hh, rtd_field ff) {
     // is announced by rtd_set_ct* like any other change): the launches in front of the convolution are then left out. Not with the
     // halo, not for spot maps beyond k_plan_conv's rows, not with RTD_SEPARATE_PLAN (the full sequence, deliberately: DESIGN.md section
     // 4), and never into a capturing stream: a graph must not depend on what the field knew when it was captured.
-    bool reuse = f->traceUsable && f->traceEpoch == h->inputEpoch && !f->sw.noTraceReuse && !f->sw.separatePlan && !fc.nuclearCorr &&
-                 fc.spotNy <= kPlanConvMaxRows;
+    const bool reuseAllowed = !f->sw.noTraceReuse && !f->sw.separatePlan && !fc.nuclearCorr && fc.spotNy <= kPlanConvMaxRows;
     hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
     RTD_HIP(h, hipStreamIsCapturing(s, &cs));
-    const bool capturing = cs != hipStreamCaptureStatusNone;
-    if (capturing) reuse = false;
-    if (!reuse) {
-        const int st = ensureCtBox(h, f); if (st != RTD_OK) return st;
-        // (a captured launch runs when its graph does, not now: it leaves no record)
-        f->traceUsable = false; f->traceLaunched = !capturing; f->traceEpoch = h->inputEpoch;
-    }
-    f->launchedReuse = reuse;
-    // the uniform-sigma detection and kernel are skipped for a field that was found heterogeneous under the same CT / LUTs / options
-    const bool tryUniform = f->uniformEligible && !(f->uniformHint == 0 && f->hintEpoch == h->inputEpoch);
-    f->triedUniform = tryUniform;
-    f->launchEpoch = h->inputEpoch;
-    // ... and a field that was found uniform under the same inputs will be found uniform again (the test is exact arithmetic on
-    // the same values): the general superposition kernel, all of whose ~10^5 blocks would only look at the flag and leave, is not launched
-    const bool knownUniform = tryUniform && f->uniformHint == 1 && f->hintEpoch == h->inputEpoch;
-    f->launchedKnownUniform = knownUniform;
-    f->launchedSigma = sigmaMode(h, f, reuse);
-    const ComputeJob c{h, f, reuse, tryUniform, knownUniform, h->opt.fine_grained_timing != 0, f->launchedSigma,
+    // What the field knows decides what is left out (rtd_field_memory.hpp): the launches in front of the convolution, the uniform-sigma
+    // detection and kernel, the general superposition kernel (all of whose ~10^5 blocks would only look at a flag and leave), the sigma walk.
+    const LaunchDecision d = f->memory.decide(LaunchInputs{h->inputEpoch, cs != hipStreamCaptureStatusNone, reuseAllowed, f->uniformEligible, f->sw.noSigmaReuse});
+    if (!d.flight.reuse) { const int st = ensureCtBox(h, f); if (st != RTD_OK) return st; }
+    f->memory.launched(d);
+    if (d.sigma == SigmaRecord::kAllocateThenRecord) allocSigmaRecord(h, f, d.need);
+    const ComputeJob c{h, f, f->memory.flight, h->opt.fine_grained_timing != 0,
         ResetJob{f->dLayers, fc.L, reinterpret_cast<unsigned int*>(f->dTileRad), f->tileRadWords, f->dActive, (size_t)4 * fc.L * fc.S,
         f->dNucIdd, f->dNucRs, fc.nuclearCorr ? (size_t)fc.nucW * fc.nucH * fc.L : (size_t)0,
         f->dSigMin, f->dSigMax, (size_t)fc.L * fc.S, f->dScanDbg}};
-    if (!reuse) { const int st = launchTrace(c); if (st != RTD_OK) return st; }
+    if (!c.is.reuse) { const int st = launchTrace(c); if (st != RTD_OK) return st; }
     launchPlanConv(c);
     launchFill(c);
     { const int st = launchSuperposition(c); if (st != RTD_OK) return st; }
@@ -988,9 +968,9 @@ static int transferImpl(rtd_handle hh, rtd_field ff, float* dev_dose, const int3
                     (int)f->doseDims[1], (int)f->doseDims[2], slab, state, f->fc, zChunk, clip);
         });
     };
-    launchT(f->transferMode, init, own.bev, own.st, f->remote ? f->ev[0] : nullptr, halo ? nullptr : f->ev[6]);
+    launchT(f->transferMode, init, own.bev, own.st, f->remote ? f->ev[kEvStart] : nullptr, halo ? nullptr : f->ev[kEvTransfer]);
     // NUCLEAR_CORR: nucTransfDiv (kernel_wrapper.cu:100-127, launch :1221-1254) after the primary transfer, like the reference
-    if (halo) launchT(f->transferModeNuc, false, (const float*)f->dNucBev, (const FieldState*)f->dStateNuc, nullptr, f->ev[6]);
+    if (halo) launchT(f->transferModeNuc, false, (const float*)f->dNucBev, (const FieldState*)f->dStateNuc, nullptr, f->ev[kEvTransfer]);
     RTD_HIP(h, hipGetLastError());
     f->transferred = true;
     return RTD_OK;
@@ -1035,7 +1015,7 @@ int rtd_fields_transfer_init(rtd_handle hh, const rtd_field* fields, uint32_t n_
     const size_t bricks = (size_t)((box.hi[0] - box.lo[0]) / 16 + 1) * ((box.hi[1] - box.lo[1]) / 16 + 1) * ((box.hi[2] - box.lo[2]) / 16 + 1);
     const unsigned g = (unsigned)std::min<size_t>(bricks, (size_t)h->numCUs * 8 * 4);
     for (uint32_t i = 0; i < n_fields; ++i) reinterpret_cast<rtd_field_impl*>(fields[i])->transferred = false;
-    launchK(k_transfer_multi, dim3(g), dim3(256), 0, h->stream, lead->remote ? lead->ev[0] : nullptr, lead->ev[6], dev_dose, (int)dims[0], (int)dims[1],
+    launchK(k_transfer_multi, dim3(g), dim3(256), 0, h->stream, lead->remote ? lead->ev[kEvStart] : nullptr, lead->ev[kEvTransfer], dev_dose, (int)dims[0], (int)dims[1],
             (int)dims[2], mf, box);
     RTD_HIP(h, hipGetLastError());
     lead->transferred = true;
@@ -1075,7 +1055,7 @@ int rtd_field_wait_plan(rtd_handle hh, rtd_field ff, rtd_field_info* info, size_
     if (!h || !f) return RTD_ERR_INVALID_ARG;
     if (!f->computed || f->remote) return fail(h, RTD_ERR_NOT_READY, "rtd_field_wait_plan: field not computed on this handle");
     RTD_HIP(h, hipSetDevice(h->device));
-    RTD_HIP(h, hipEventSynchronize(f->selfPlanned ? f->ev[5] : f->ev[4]));   // (a launch that planned for itself: its plan is complete when the superposition is)
+    RTD_HIP(h, hipEventSynchronize(f->planKnownEv()));   // (a launch that planned for itself: its plan is complete when the superposition is)
     const FieldState st = *f->hState;                                // mirrored by the plan into pinned host memory
     { const int r = takeFindings(h, f, st); if (r != RTD_OK) return r; }
     if (info) fillInfo(f, st, info);
@@ -1130,12 +1110,12 @@ int rtd_field_finish(rtd_handle hh, rtd_field ff, rtd_timing* timing, rtd_field_
     RTD_HIP(h, hipSetDevice(h->device));
     if (f->remote) {
         // a slab from another GPU: the state record is the message header (device memory) — copy it once the transfer is done
-        if (f->transferred) RTD_HIP(h, hipEventSynchronize(f->ev[6]));
+        if (f->transferred) RTD_HIP(h, hipEventSynchronize(f->ev[kEvTransfer]));
         FieldState st;
         RTD_HIP(h, hipMemcpy(&st, f->attached, sizeof st, hipMemcpyDeviceToHost));
         if (timing) {
             std::memset(timing, 0, sizeof *timing);
-            if (f->transferred) { RTD_HIP(h, hipEventElapsedTime(&timing->transforming_ms, f->ev[0], f->ev[6])); timing->total_ms = timing->transforming_ms; }
+            if (f->transferred) { RTD_HIP(h, hipEventElapsedTime(&timing->transforming_ms, f->ev[kEvStart], f->ev[kEvTransfer])); timing->total_ms = timing->transforming_ms; }
         }
         if (info) fillInfo(f, st, info);
         if (st.errorFlags & kErrPackOverflow) return fail(h, RTD_ERR_INVALID_ARG, "BEV message buffer too small for the exported slab");
@@ -1143,23 +1123,23 @@ int rtd_field_finish(rtd_handle hh, rtd_field ff, rtd_timing* timing, rtd_field_
             return fail(h, RTD_ERR_RADIUS_OVERFLOW, "Found larger than allowed kernel superposition radius");
         return RTD_OK;
     }
-    const int last = f->transferred ? 6 : 5;                         // BEV only: the superposition's reduce is the last kernel
+    const FieldEvent last = f->transferred ? kEvTransfer : kEvSuperp;                        // BEV only: the superposition's reduce is the last kernel
     RTD_HIP(h, hipEventSynchronize(f->ev[last]));
     const FieldState st = *f->hState;                                // mirrored by k_ks_plan into pinned host memory
     { const int r = takeFindings(h, f, st); if (r != RTD_OK) return r; }
     if (timing) {
         std::memset(timing, 0, sizeof *timing);
-        RTD_HIP(h, hipEventElapsedTime(&timing->total_ms, f->ev[0], f->ev[last]));
+        RTD_HIP(h, hipEventElapsedTime(&timing->total_ms, f->ev[kEvStart], f->ev[last]));
         if (h->opt.fine_grained_timing) {
             // (a compute that reused the trace: no tracer stage, the convolution's launch is the first)
-            if (!f->launchedReuse) RTD_HIP(h, hipEventElapsedTime(&timing->raytracing_ms, f->ev[0], f->ev[1]));
-            RTD_HIP(h, hipEventElapsedTime(&timing->prepare_energy_loop_ms, f->launchedReuse ? f->ev[0] : f->ev[1], f->ev[2]));
-            RTD_HIP(h, hipEventElapsedTime(&timing->fill_idd_sigma_ms, f->ev[2], f->ev[3]));
-            hipEvent_t planEnd = f->selfPlanned ? f->ev[7] : f->ev[4];   // (self-planned: the plan is inside the superposition launch)
-            RTD_HIP(h, hipEventElapsedTime(&timing->prepare_superp_ms, f->ev[3], planEnd));
-            RTD_HIP(h, hipEventElapsedTime(&timing->superp_ms, planEnd, f->ev[5]));
-            RTD_HIP(h, hipEventElapsedTime(&timing->superp_kernel_ms, f->ev[7], f->ev[5]));
-            if (f->transferred) RTD_HIP(h, hipEventElapsedTime(&timing->transforming_ms, f->ev[5], f->ev[6]));
+            if (!f->memory.flight.reuse) RTD_HIP(h, hipEventElapsedTime(&timing->raytracing_ms, f->ev[kEvStart], f->ev[kEvTrace]));
+            RTD_HIP(h, hipEventElapsedTime(&timing->prepare_energy_loop_ms, f->memory.flight.reuse ? f->ev[kEvStart] : f->ev[kEvTrace], f->ev[kEvConv]));
+            RTD_HIP(h, hipEventElapsedTime(&timing->fill_idd_sigma_ms, f->ev[kEvConv], f->ev[kEvFill]));
+            hipEvent_t planEnd = f->memory.flight.planInSweep ? f->ev[kEvSuperpStart] : f->ev[kEvKsPlan];   // (self-planned: the plan is inside the superposition launch)
+            RTD_HIP(h, hipEventElapsedTime(&timing->prepare_superp_ms, f->ev[kEvFill], planEnd));
+            RTD_HIP(h, hipEventElapsedTime(&timing->superp_ms, planEnd, f->ev[kEvSuperp]));
+            RTD_HIP(h, hipEventElapsedTime(&timing->superp_kernel_ms, f->ev[kEvSuperpStart], f->ev[kEvSuperp]));
+            if (f->transferred) RTD_HIP(h, hipEventElapsedTime(&timing->transforming_ms, f->ev[kEvSuperp], f->ev[kEvTransfer]));
         }
         timing->superp_launches = 1;   // k_superpose_mfma, all layers and radii (the reference: up to 33 launches per layer)
         timing->ray_dims[0] = (uint32_t)f->fc.W; timing->ray_dims[1] = (uint32_t)f->fc.H;
@@ -1185,7 +1165,7 @@ int rtd_field_spot_gradient(rtd_handle hh, rtd_field ff, const float* dev_voxel_
     if (f->fc.nuclearCorr) return fail(h, RTD_ERR_INVALID_ARG, "rtd_field_spot_gradient: not available with nuclear_corr");
     if (!f->computed) return fail(h, RTD_ERR_NOT_READY, "rtd_field_spot_gradient: field not computed");
     RTD_HIP(h, hipSetDevice(h->device));
-    RTD_HIP(h, hipEventSynchronize(f->selfPlanned ? f->ev[5] : f->ev[4]));   // the plan's state record, mirrored into pinned host memory
+    RTD_HIP(h, hipEventSynchronize(f->planKnownEv()));   // the plan's state record, mirrored into pinned host memory
     if (f->hState->errorFlags & kErrRadiusOverflow)
         return fail(h, RTD_ERR_RADIUS_OVERFLOW, "Found larger than allowed kernel superposition radius");
     const FieldConst& fc = f->fc;
@@ -1272,7 +1252,7 @@ int rtd_field_set_spot_weights(rtd_handle hh, rtd_field ff, const float* dev_spo
             RTD_HIP(h, hipMemcpy2DAsync(f->dNucRayWeights + (size_t)l * fc.nucW * fc.nucH, (size_t)fc.nucW * sizeof(float),
                                         dev_spot_weights + (size_t)l * nx * ny, nx * sizeof(float), nx * sizeof(float), ny,
                                         hipMemcpyDeviceToDevice, h->stream));
-    f->uniformHint = -1; f->radiusHint = -1;
+    f->memory.forgetHints();
     return RTD_OK;
 }
 
@@ -1299,11 +1279,11 @@ int rtd_field_fetch(rtd_handle hh, rtd_field ff, const char* name, void* host_ou
         n = f->dijBatchOf.size() * sizeof(int); staging.resize(std::max<size_t>(n, 1));
         std::memcpy(staging.data(), f->dijBatchOf.data(), n);
     } else if (nm == "trace_reused") {
-        const int32_t v = f->computed && f->launchedReuse ? 1 : 0;   // the last launched compute left out the tracer, the scan and the plan
+        const int32_t v = f->computed && f->memory.flight.reuse ? 1 : 0;   // the last launched compute left out the tracer, the scan and the plan
         n = sizeof v; staging.resize(n);
         std::memcpy(staging.data(), &v, n);
     } else if (nm == "sigma_reused") {
-        const int32_t v = f->computed ? f->launchedSigma : 0;        // the last launched compute: 0 walked, 1 recorded and replayed, 2 replayed
+        const int32_t v = f->computed ? f->memory.flight.sigma : 0;       // the last launched compute: 0 walked, 1 recorded and replayed, 2 replayed
         n = sizeof v; staging.resize(n);
         std::memcpy(staging.data(), &v, n);
     } else if (nm == "eff_radius" || nm == "layer_plan") {

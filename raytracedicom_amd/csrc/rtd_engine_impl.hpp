@@ -71,6 +71,11 @@ Switches readSwitches() {
 // (rtd_field_project_target: allocated by its first call), the sigma record (allocated by the first compute that reuses the trace).
 enum BufClass : unsigned { kShape = 1, kNuclear = 2, kGradient = 4, kDiag = 8, kDij = 16, kDijOut = 32, kTarget = 64, kSigmaRec = 128, kAllBufs = 255 };
 
+// A field's events: the start of a compute's first launch, the ends of its stages, the end of the transfer, and the start of the
+// superposition's first launch. kEvTrace is not recorded by a compute that reused the trace, kEvKsPlan not by one whose sweep launch
+// planned for itself, kEvTrace .. kEvFill and kEvSuperpStart only with fine_grained_timing.
+enum FieldEvent { kEvStart, kEvTrace, kEvConv, kEvFill, kEvKsPlan, kEvSuperp, kEvTransfer, kEvSuperpStart, kEvCount };
+
 struct rtd_field_impl {
     Switches sw;
     FieldConst fc{};
@@ -98,30 +103,11 @@ struct rtd_field_impl {
     int* dActive = nullptr;      // [L][S][4] minima of (x, y, -x, -y) over rays with dose > 0
     unsigned int *dSigMin = nullptr, *dSigMax = nullptr;   // [L][S] bits of the smallest / largest tile-uniform sigma^2 (uniform-sigma detection)
     bool uniformEligible = false; // the separable superposition may take the field (no nuclear halo, BEV height within its accumulators)
-    int uniformHint = -1;         // what the last finished compute found: 0 heterogeneous, 1 one sigma per slice, -1 unknown
-    unsigned hintEpoch = 0;       // ... under this handle->inputEpoch
-    unsigned launchEpoch = 0;     // handle->inputEpoch when the compute in flight was launched (what its findings are valid for)
-    bool launchedKnownUniform = false;   // the compute in flight skipped the general superposition kernel on the strength of the hint
-    bool triedUniform = false;    // the compute in flight ran the detection
-    // The trace and the plan (density, WEPL, radiation length, entry / exit steps, WEPL minima, the plan's part of the state record and
-    // of the layer records) depend on CT, LUTs, options and geometry only, not on the spot weights: a compute under the inputs of a
-    // FINISHED compute that produced them launches neither the tracer nor the scan nor the plan (rtd_field_compute_bev).
-    bool traceLaunched = false;   // a compute that traces has been launched (not into a capturing stream) under traceEpoch
-    unsigned traceEpoch = 0;      // handle->inputEpoch of that launch
-    bool traceUsable = false;     // ... and a finished compute under that epoch has been seen without a device error (takeFindings)
-    bool launchedReuse = false;   // the compute in flight reused the trace: ev[1] is not recorded (rtd_field_fetch "trace_reused")
-    // The sigma record (rtd_fill.hpp): what k_fill's sigma walk computes without looking at the spot weights, kept under the trace's
-    // rule. The first compute that reuses the trace records it in front of its fill and replays it; the computes after a FINISHED such
-    // compute only replay, while handle->inputEpoch stands. [L][sigRecSteps][R] words + [L][R] end steps, allocated by that first
-    // compute (a failed allocation: the field keeps walking), freed by rtd_field_release / _destroy.
-    int planFirst = 0, planSteps = 0;   // beamFirstInside and the steps up to firstGuaranteedPassive of the trace in use (takeFindings)
+    // What the field learned from its computes (hints, the compute in flight, the trace and plan it reuses, the sigma record's state)
+    // and every decision taken from it: rtd_field_memory.hpp. The sigma record itself ([L][memory.sigmaSteps][R] words + [L][R] end
+    // steps) is allocated by the first compute that reuses the trace, freed by rtd_field_release / _destroy.
+    FieldMemory memory;
     unsigned int* dSigRec = nullptr; int* dSigRecLast = nullptr;
-    size_t sigRecSteps = 0;       // extent of the record's step axis (0: no record allocated)
-    bool sigRecFailed = false;    // the allocation failed once: not tried again
-    bool sigRecLaunched = false;  // a record pass has been launched under sigRecEpoch
-    unsigned sigRecEpoch = 0;
-    bool sigRecUsable = false;    // ... and a compute launched behind it under that epoch has been seen finished (sigmaRecordFinished)
-    int launchedSigma = 0;        // the compute in flight: 0 walked, 1 recorded and replayed, 2 replayed (rtd_field_fetch "sigma_reused")
     // NUCLEAR_CORR (default off): the halo on the spot-resolution grid
     int* dNucSpotIdx = nullptr; float *dNucRayWeights = nullptr, *dNucIdd = nullptr, *dNucRs = nullptr, *dNucBev = nullptr;
     int* dNucEffT = nullptr;
@@ -138,10 +124,11 @@ struct rtd_field_impl {
     FieldState* hState = nullptr;      // pinned host mirror of *dState (written by k_ks_plan), and its device-side address
     FieldState* dHostState = nullptr;
     std::vector<LayerPlan> hLayers;
-    hipEvent_t ev[8] = {};       // 0..6 stage ends, 7 start of the superposition (its first launch)
-    bool selfPlanned = false;    // the last compute had no k_ks_plan launch: block 0 of k_superpose_sweep's launch was the plan (ev[4] not recorded)
+    hipEvent_t ev[kEvCount] = {};   // (FieldEvent)
+    // The event after which the plan's state record is on the host (a launch that planned for itself: when the superposition is done).
+    hipEvent_t planKnownEv() const { return ev[memory.flight.planInSweep ? kEvSuperp : kEvKsPlan]; }
     bool computed = false;       // the BEV dose and the state record of the last rtd_field_compute[_bev] exist (or a slab is attached)
-    bool transferred = false;    // a transfer has been launched since (ev[6] is recorded)
+    bool transferred = false;    // a transfer has been launched since (kEvTransfer is recorded)
     bool remote = false;         // geometry only: the BEV slab comes from another GPU (rtd_field_attach_bev)
     const unsigned char* attached = nullptr;   // remote: the packed message [FieldState | slab]
     int ksGroups = 14;   // layer groups of the superposition (partial BEV buffers); RTD_KS_GROUPS overrides
@@ -151,7 +138,6 @@ struct rtd_field_impl {
     // k_superpose_sweep_big (rtd_sweep_big.hpp), the sources of batch radius 17 .. 32: its own layer groups, partial tiles [step][patch][group][128 x 128], counters
     int bgGroups = kBgMaxGroups;
     float* dSwSlotsBig = nullptr; int* dSwCountBig = nullptr;
-    int radiusHint = -1;          // largest batch radius the last finished compute found (-1 unknown), under hintEpoch like uniformHint
     bool sweepEnabled = true;     // RTD_NO_SWEEP: every field through k_superpose_mfma
     // spot-weight gradient (rtd_field_spot_gradient, rtd_adjoint.hpp): allocated by the first call, reused after it
     float *dGradBev = nullptr, *dGradRw = nullptr, *dAdjPart = nullptr, *dAdjInterm = nullptr;
@@ -237,7 +223,7 @@ struct rtd_field_impl {
         visit(dDijPartial, ap * std::max<size_t>(dijChunks, 1), kDijOut, false, nullptr);
         visit(dTargetBev, ((S + 31) / 32) * R, kTarget, false, "target_bev"); visit(dTargetHit, L * R, kTarget, false, "target_hit");
         visit(dTargetSum, (size_t)1, kTarget, false, nullptr); visit(dTargetCount, (size_t)1, kTarget, false, nullptr);
-        visit(dSigRec, sigRecSteps * R * L, kSigmaRec, false, nullptr); visit(dSigRecLast, sigRecSteps ? R * L : (size_t)0, kSigmaRec, false, nullptr);
+        visit(dSigRec, memory.sigmaSteps * R * L, kSigmaRec, false, nullptr); visit(dSigRecLast, memory.sigmaSteps ? R * L : (size_t)0, kSigmaRec, false, nullptr);
         visit(dScanDbg, sw.scanDebug ? 8 * (R / 64) : 0, kDiag, true, "scan_debug");
         visit(dFillDbg, sw.fillDebug ? 4 * 2 * tiles * L : 0, kDiag, false, "fill_debug");
         visit(dUniDbg, sw.uniformDebug && uniformEligible && uniform4() ? 16 * S * nPartsU4 : 0, kDiag, true, "uniform_debug");
@@ -306,29 +292,12 @@ hipError_t raiseLdsCap(rtd_handle_impl* h, K kernel, size_t bytes) {
     return e;
 }
 
-// What a finished plan tells the host (its state record, mirrored into pinned host memory). The hints belong to the inputs the
-// compute was LAUNCHED under: CT, LUTs or options may have changed since.
-// The launched compute is known to be finished, with the device-side error flags of its state record: a record pass launched in
-// front of it (or of an earlier compute) under its inputs is complete. Like the trace, the record is not trusted after a device error.
-void sigmaRecordFinished(rtd_field_impl* f, int errorFlags) {
-    if (errorFlags) { f->sigRecUsable = false; f->sigRecLaunched = false; return; }
-    if (f->sigRecLaunched && f->sigRecEpoch == f->launchEpoch) f->sigRecUsable = true;
-}
-
+// What a finished plan tells the host (its state record, mirrored into pinned host memory): handed to the field's memory. Never
+// reached for a remote field (every caller refuses those first).
 int takeFindings(rtd_handle_impl* h, rtd_field_impl* f, const FieldState& st) {
-    sigmaRecordFinished(f, st.errorFlags);
-    if (!st.errorFlags && !f->remote) {   // (what the scan and the plan found: the same for every compute that reuses them)
-        f->planFirst = st.beamFirstInside;
-        f->planSteps = st.empty ? 0 : std::max(st.firstGuaranteedPassive - st.beamFirstInside, 0);
-    }
-    if (f->triedUniform) { f->uniformHint = st.uniformField ? 1 : 0; f->hintEpoch = f->launchEpoch; }
-    else if (f->hintEpoch != f->launchEpoch) { f->uniformHint = -1; f->hintEpoch = f->launchEpoch; }
-    f->radiusHint = (st.errorFlags || st.empty) ? -1 : st.maxRadius;   // (valid under hintEpoch, like the uniform hint)
-    // the field's trace and plan are complete and stand for the inputs of the launch (a later compute may run on another stream)
-    f->traceUsable = f->traceLaunched && f->launchEpoch == f->traceEpoch && !st.errorFlags && !f->remote;
-    // A compute that skipped the general kernel (hint: uniform) on a field the device then found heterogeneous has written no BEV
-    // dose: only possible when the caller changed a bound device volume in place (rtd_set_ct_device) without telling the handle.
-    if (f->launchedKnownUniform && !st.uniformField && !st.errorFlags && !st.empty)
+    const bool notUniform = f->memory.finished(FieldFindings{st.errorFlags, st.empty != 0, st.uniformField != 0, st.maxRadius, st.beamFirstInside,
+                                                             st.firstGuaranteedPassive});
+    if (notUniform)
         return fail(h, RTD_ERR_NOT_READY, "the field was launched as a uniform-sigma field but is not one: its inputs were modified in place; call rtd_set_ct* again and recompute");
     return RTD_OK;
 }

@@ -209,6 +209,30 @@ def test_dose_influence(rig_of, synth):
     _same(states[0], states[1])
 
 
+def test_two_computes_in_flight(rig_of, synth):
+    """Two launches with no finish between them: the second one traces again (nothing has been seen finished), the finish behind it
+    makes its trace usable, the compute after that reuses it and records the sigma walk, the one after that replays the record."""
+    scn = hetero_scene(synth, 96, [30.0], spots=5, pitch=8.0, layers=2)
+    b = scn.beams[0]
+    rig = rig_of(scn, options(1.0))
+    f = rig.field(b)
+
+    def flags():
+        return int(f.fetch("trace_reused")[0]), int(f.fetch("sigma_reused")[0])
+    f.compute_bev()
+    f.compute_bev()
+    assert flags() == (0, 0)
+    f.finish()
+    _, third = _compute(rig, f)
+    assert flags() == (1, 1)
+    _, fourth = _compute(rig, f)
+    assert flags() == (1, 2)
+    r, ref = _compute(rig, rig.field(b, RTD_NO_TRACE_REUSE="1"))
+    assert r == 0 and ref["dose"].max() > 0
+    _same(third, ref)
+    _same(fourth, ref)
+
+
 def test_gradient(rig_of, synth):
     """rtd_field_spot_gradient behind a reused forward equals the one behind a traced forward."""
     scn = hetero_scene(synth, 96, [30.0], spots=5, pitch=8.0, layers=2)
