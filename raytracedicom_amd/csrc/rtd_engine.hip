@@ -804,9 +804,10 @@ static void launchFill(const ComputeJob& c) {
                 f->sw.noFillCompact ? 0 : 1, rec);
     };
     auto launchFill = [&](auto kern, size_t lds) { launchFillOn(kern, fillGrid, lds, c.ev(kEvFill)); };
-    const bool ldsLut = fillLds <= 56 * 1024;     // (+ ~1 KiB of static arrays: stays under the 64 KiB default cap of a block's LDS)
-    constexpr size_t sigLds = (size_t)2 * kFillBatch * 256 * sizeof(float);   // the sigma walk's exchange buffers share the dynamic LDS with the dose walk's LUT rows
-    const size_t dynLds = std::max(sigLds, ldsLut ? fillLds : (size_t)0);
+    const size_t tabLds = (size_t)fillTabFloats(fc.S) * sizeof(float);      // the block's copy of the step table, behind the rest (S <= kMaxSteps: 16 KiB at most)
+    const bool ldsLut = fillLds + tabLds <= 56 * 1024;   // (+ ~1 KiB of static arrays: stays under the 64 KiB default cap of a block's LDS)
+    // the sigma walk's exchange buffers share the dynamic LDS with the dose walk's LUT rows (fillTabOffset: the kernel's view of the same layout)
+    const size_t dynLds = (size_t)fillTabOffset(ldsLut, h->lut.nSamples) * sizeof(float) + tabLds;
     // the record pass: the sigma walk of every (layer, tile) alone, in front of the fill that replays it (inside the fill's timing bucket)
     if (c.is.sigma == 1) launchFillOn((k_fill<false, false, kFillRecord>), dim3(fillGrid.x / 2), (size_t)0, nullptr);
     if (c.is.sigma) { if (ldsLut) launchFill((k_fill<true, false, kFillReplay>), dynLds); else launchFill((k_fill<false, false, kFillReplay>), dynLds); }

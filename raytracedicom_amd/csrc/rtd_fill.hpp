@@ -32,14 +32,26 @@ namespace rtd {
 
 constexpr int kFillBatch = 8;   // steps per batch: inputs fetched one batch ahead, one block barrier per batch
 // NO BRANCH AROUND A PREFETCH. The compiler counts the loads and stores in flight (s_waitcnt vmcnt(N)) along straight paths only; where
-// two paths that issued different numbers of them meet, it waits for all of them — vmcnt(0), the loads issued a step ago and the
-// stores' acknowledgements included: with "if (step < afterLast) load" and "if (step >= afterLast) continue" in every step both walks
-// drained memory at the head of every batch (the dose walk of the replaying build in most steps), a full round trip each. So every
-// prefetch of the replaying build is issued unconditionally at a clamped step (a value fetched for a step beyond the layer's last is
-// never used), and a batch that lies wholly within the layer's steps runs a body without the per-step test (only the layer's last
-// batch keeps it): the waits become counted ones, up to vmcnt(20). The second body costs the replaying build registers and waves per
-// SIMD, and costs the walking build more than it gives, so the walking and recording builds keep their loops as they were (the
-// figures of every build and what was measured: DESIGN.md section 4 K5).
+// two paths meet it keeps, per register, the smaller count of the two, and a path that skipped a load makes the load in front of it "the
+// last one issued": vmcnt(0), the loads issued a step ago and the stores' acknowledgements included. With "if (step < afterLast) load"
+// and "if (step >= afterLast) continue" in every step both walks drained memory at the head of every batch (the dose walk of the
+// replaying build in most steps), a full round trip each; "if (waveLive) load" in front of the loop did the same to the loop's head. So
+// every prefetch of the replaying build is issued unconditionally at a clamped step (a value fetched for a step beyond the layer's last,
+// or by a wave without a live ray, is never used).
+// ONE PATH THROUGH THE LOOP. The replaying build runs the batches that lie wholly within the layer's steps in a loop of their own,
+// whose body has no per-step test, and the layer's last batch (which keeps the test and its waits) once behind it. A step refills its
+// prefetch slot after the last use of the slot's value, so the load lands in the register the next batch reads it from: one set of
+// prefetch registers, no copies at the back-edge, and every wait of the loop is a counted one (sigma replay vmcnt(7)..(14), dose walk
+// vmcnt(14)..(22)). With both bodies inside one loop the compiler kept a second register set, copied it under vmcnt(0) at the back-edge
+// and hoisted the first step's arithmetic above the branch between the bodies (under another vmcnt(0)): 82 VGPRs, five waves per SIMD;
+// now 66 and seven. The walking and recording builds keep their loops as they were (the figures of every build and what was measured:
+// DESIGN.md section 4 K5).
+// Dynamic LDS of a block, in floats: the LUT rows of the dose walk or the exchange buffers of the sigma walk (one or the other), then
+// the block's copy of the step table (THE STEP TABLE IN LDS): one entry per step of the field, up to a whole number of batches.
+__host__ __device__ constexpr int fillTabOffset(bool ldsLut, int nSamples) {
+    return ldsLut && 2 * nSamples > 2 * kFillBatch * 256 ? 2 * nSamples : 2 * kFillBatch * 256;
+}
+__host__ __device__ constexpr int fillTabFloats(int S) { return (S + kFillBatch - 1) / kFillBatch * kFillBatch; }
 struct FillFullBatch { static constexpr bool full = true; };
 struct FillTailBatch { static constexpr bool full = false; };
 constexpr int kFillSnakeRounds = 12;   // up to this many walks per CU the walks are dealt in rounds of alternating direction (k_fill's block placement)
@@ -219,6 +231,31 @@ __global__ __launch_bounds__(256) void k_fill(const float* __restrict__ bevDensi
     float cumulSpOld = 0.0f;
     const float sqrt2 = 1.41421356f;
 
+    // THE STEP TABLE IN LDS. stepTab is a per-field constant, but read from memory it is a scalar-cache round trip in every step of either
+    // walk and a global load behind the batch barrier in classify, each with a wait of its own on the block's critical path. The block
+    // copies the entries of its walk's steps and of its role (2k: sigma walk, 2k + 1: dose walk) behind the dynamic LDS that the LUT rows
+    // and sSig share, up to a whole number of batches (the read index clamped to the table: such an entry is never used). A batch takes
+    // its kFillBatch entries in front of its first step (loadTab: wave-uniform, into scalar registers); classify reads its entry from
+    // the same copy. The floats are the same ones.
+    float* const sTab = sLutF + fillTabOffset(LDS_LUT, lut.nSamples);
+    // (The replaying build only. The walking build keeps its reads of stepTab where they were: with the table taken per batch in both
+    //  walks its first compute of a field measured 5 us slower, with the table in the sigma walk alone it needs 74 registers, a wave
+    //  per SIMD less)
+    if (MODE == kFillReplay) {
+        unsigned int nTab = pFirst < pAfterLast ? (pAfterLast - pFirst + (kFillBatch - 1)) & ~(unsigned int)(kFillBatch - 1) : 0u;
+        nTab = nTab < (unsigned int)fillTabFloats(fc.S) ? nTab : (unsigned int)fillTabFloats(fc.S);
+        for (unsigned int i = tid; i < nTab; i += 256) {
+            const unsigned int k = pFirst + i < (unsigned int)fc.S ? pFirst + i : (unsigned int)fc.S - 1u;
+            sTab[i] = stepTab[2 * k + role];
+        }
+    }
+    float tabB[kFillBatch];                                          // the batch's entries (wave-uniform)
+    auto loadTab = [&](unsigned int step0) {
+#pragma unroll
+        for (int j = 0; j < kFillBatch; ++j)
+            tabB[j] = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(sTab[step0 - pFirst + j])));
+    };
+
     if (role == 0) {
         // ================================ sigma walk ================================
         const size_t recOff = MODE == kFillWalk ? (size_t)0 : (size_t)layer * (size_t)rec.steps * memStep;
@@ -257,7 +294,7 @@ __global__ __launch_bounds__(256) void k_fill(const float* __restrict__ bevDensi
         }
 #pragma unroll
         for (int j = 0; j < kFillBatch; ++j) {
-            if (MODE == kFillReplay) { if (waveLive) fetchRec(j, pFirst + j); else recB[j] = kSigMasked; }
+            if (MODE == kFillReplay) fetchRec(j, pFirst + j);        // (NO BRANCH AROUND A PREFETCH: a wave without a live ray never looks at it)
             else if (waveLive) fetch1(j, pFirst + j);
             else { spB[j] = 0.0f; denB[j] = 0.0f; rrlB[j] = 0.0f; }
         }
@@ -290,7 +327,7 @@ __global__ __launch_bounds__(256) void k_fill(const float* __restrict__ bevDensi
             if (l == 31 && step0 + j < pAfterLast) {
                 // tile minimum of 1/sigma (= the reference's minVal, kernel_wrapper.cuh:282-297) from the tile maximum of
                 // sigmaSq with IEEE sqrt and division, then the class exactly as the reference computes it (:300-305)
-                const float minRs = m >= 0.0f ? stepTab[2 * (step0 + j)] / (sqrt2 * (sqrtf(m) + sigmaDeltaV)) : __int_as_float(0x7f800000);
+                const float minRs = m >= 0.0f ? (MODE == kFillReplay ? sTab[step0 + j - pFirst] : stepTab[2 * (step0 + j)]) / (sqrt2 * (sqrtf(m) + sigmaDeltaV)) : __int_as_float(0x7f800000);
                 int rad = f2iSat(fc.ksSigmaCutoff / (sqrtf(2.0f) * minRs) + 0.5f);
                 rad = rad > kMaxSuperpR + 1 ? kMaxSuperpR + 1 : rad;
                 rad = rad < 0 ? 0 : rad;
@@ -303,25 +340,34 @@ __global__ __launch_bounds__(256) void k_fill(const float* __restrict__ bevDensi
         unsigned int step0 = pFirst;
         int buf = 0;
         auto replayBatch = [&](auto kind) {
+            loadTab(step0);
 #pragma unroll
             for (int j = 0; j < kFillBatch; ++j) {
                 const unsigned int stepNo = step0 + j;
                 if (!decltype(kind)::full && stepNo >= pAfterLast) { sSig[buf][j][tid] = -1.0f; continue; }   // block-uniform
                 const unsigned int r = recB[j];
-                fetchRec(j, stepNo + kFillBatch);
                 const bool masked = !beamLive || r == kSigMasked;   // the weight mask of this compute, the record's own
                 const float sig = __uint_as_float(r);
-                const float rs = stepTab[2 * stepNo] * __builtin_amdgcn_rcpf(sqrt2 * (__builtin_amdgcn_sqrtf(sig) + sigmaDeltaV));   // the walk's expression
+                const float rs = tabB[j] * __builtin_amdgcn_rcpf(sqrt2 * (__builtin_amdgcn_sqrtf(sig) + sigmaDeltaV));   // the walk's expression
                 (bevRSigmaEff + layerOff + (size_t)stepNo * memStep)[rayOff] = masked ? __int_as_float(0x7f800000) : rs;
                 sSig[buf][j][tid] = masked ? -1.0f : sig;
+                // (the slot takes the word of the step one batch later once its own is dead: ONE PATH THROUGH THE LOOP)
+                __builtin_amdgcn_sched_barrier(0);
+                fetchRec(j, stepNo + kFillBatch);
                 __builtin_amdgcn_sched_barrier(0);                   // (a step's instructions stay within the step)
             }
         };
-        if (MODE == kFillReplay) for (; step0 < pAfterLast && waveLive; step0 += kFillBatch, buf ^= 1) {
-            if (step0 + kFillBatch <= pAfterLast) replayBatch(FillFullBatch{}); else replayBatch(FillTailBatch{});
+        auto replayTrip = [&](auto kind) {
+            replayBatch(kind);
             waveLive = __ballot(beamLive && step0 + kFillBatch < afterLast) != 0ull;   // (the steps from afterLast on are masked)
             ldsBarrier();
             classify(step0, buf);
+            step0 += kFillBatch; buf ^= 1;
+        };
+        // (ONE PATH THROUGH THE LOOP: the full batches, then the layer's last batch)
+        if (MODE == kFillReplay) {
+            while (step0 + kFillBatch <= pAfterLast && waveLive) replayTrip(FillFullBatch{});
+            if (step0 < pAfterLast && waveLive) replayTrip(FillTailBatch{});
         }
         else for (; step0 < pAfterLast && waveLive; step0 += kFillBatch, buf ^= 1) {
 #pragma unroll
@@ -449,7 +495,7 @@ __global__ __launch_bounds__(256) void k_fill(const float* __restrict__ bevDensi
         unsigned int lastRect = 0xffffffffu;
 #pragma unroll
         for (int j = 0; j < kFillBatch; ++j) {
-            if (waveLive) fetch1(j, pFirst + j);
+            if (MODE == kFillReplay || waveLive) fetch1(j, pFirst + j);   // (replay: NO BRANCH AROUND A PREFETCH, a wave without a live ray never looks at it)
             else { spB[j] = 0.0f; denB[j] = 0.0f; }
         }
         __syncthreads();
@@ -471,7 +517,7 @@ __global__ __launch_bounds__(256) void k_fill(const float* __restrict__ bevDensi
         };
         unsigned int step0 = pFirst;
         int buf = 0;
-        for (; step0 < pAfterLast && waveLive; step0 += kFillBatch, buf ^= 1) {
+        auto doseTrip = [&](auto kind) {
             // lane kFillBatch - 1 - j: the wave's rectangle at step j of the batch (each step shifts the lanes up by one and enters at lane 0)
             unsigned int rect = 0xffffffffu;
             auto pushRect = [&](unsigned int r) {
@@ -479,12 +525,13 @@ __global__ __launch_bounds__(256) void k_fill(const float* __restrict__ bevDensi
                 rect = (tid & (kWave - 1)) == 0 ? r : rect;
             };
             auto doseBatch = [&](auto kind) {
+                if (MODE == kFillReplay) loadTab(step0);
     #pragma unroll
                 for (int j = 0; j < kFillBatch; ++j) {
                     const unsigned int stepNo = step0 + j;
                     if (!decltype(kind)::full && stepNo >= pAfterLast) { pushRect(0xffffffffu); continue; }   // block-uniform
                     const float cumulSp = spB[j], density = denB[j];
-                    fetch1(j, stepNo + kFillBatch);
+                    if (MODE != kFillReplay) fetch1(j, stepNo + kFillBatch);
                     if (beamLive) {
                         float cumulDose;
                         {   // tex2D(cumulIddTex, ...) :269-274, rows and row weight hoisted
@@ -499,7 +546,7 @@ __global__ __launch_bounds__(256) void k_fill(const float* __restrict__ bevDensi
                         }
                         if (cumulSp > cutDepth || stepNo == afterLast) { beamLive = false; afterLast = stepNo; }
                         // stepTab[2k+1] = stepVol(k) (fill_idd_and_sigma_params.cu:72)
-                        const float stepVol = stepTab[2 * stepNo + 1];
+                        const float stepVol = MODE == kFillReplay ? tabB[j] : stepTab[2 * stepNo + 1];
                         const float mass = fc.doseToWater ? (cumulSp - cumulSpOld) * stepVol : density * stepVol;
                         // (the dose value feeds no threshold other than res > 0, which a reciprocal cannot change: hardware reciprocal, <= 1 ulp)
                         if (!NUC || !fc.nuclearCorr) {
@@ -519,15 +566,26 @@ __global__ __launch_bounds__(256) void k_fill(const float* __restrict__ bevDensi
                     const unsigned long long ballot = __ballot(res > 0.0f);
                     if (ballot != lastBallot) { lastBallot = ballot; lastRect = fillWaveRect(ballot, sSegOf + wave * kFillSegsPerWave); }
                     pushRect(lastRect);
-                    if (MODE == kFillReplay) __builtin_amdgcn_sched_barrier(0);   // (a step's instructions stay within the step)
+                    if (MODE == kFillReplay) {                       // (the slots are refilled once their values are dead)
+                        __builtin_amdgcn_sched_barrier(0);
+                        fetch1(j, stepNo + kFillBatch);
+                        __builtin_amdgcn_sched_barrier(0);           // (a step's instructions stay within the step)
+                    }
                 }
             };
-            if (MODE == kFillReplay && step0 + kFillBatch <= pAfterLast) doseBatch(FillFullBatch{}); else doseBatch(FillTailBatch{});
+            doseBatch(kind);
             if ((tid & (kWave - 1)) < kFillBatch) sDoseRect[buf][kFillBatch - 1 - (tid & (kWave - 1))][wave] = rect;
             waveLive = __ballot(beamLive) != 0ull;
             ldsBarrier();                                            // the only barrier of a batch (sDoseRect is double-buffered)
             rectangle(step0, buf);
+            step0 += kFillBatch; buf ^= 1;
+        };
+        // (replay: ONE PATH THROUGH THE LOOP)
+        if (MODE == kFillReplay) {
+            while (step0 + kFillBatch <= pAfterLast && waveLive) doseTrip(FillFullBatch{});
+            if (step0 < pAfterLast && waveLive) doseTrip(FillTailBatch{});
         }
+        else while (step0 < pAfterLast && waveLive) doseTrip(FillTailBatch{});
         // The rest of the walk when no ray of the wave is alive (any more): dose 0 in memory, no ray with dose in the block's exchange
         // buffers (those once per buffer) — without inputs and without arithmetic. The barriers and the wave's share of the rectangles stay.
         for (int deadBufs = 0; step0 < pAfterLast; step0 += kFillBatch, buf ^= 1) {
