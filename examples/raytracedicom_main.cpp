@@ -26,6 +26,10 @@
 // BeamSettings through include/rtd_plan.hpp and their dose is written to dose.dat on the CT grid. The reference's own DICOM
 // path stops after printing the plan, with zero spot weights (main.cu:105-190).
 //   --start_depth MM / --tracer_steps N   override the tracer range that is otherwise fitted to the CT along each beam axis
+// After dose.dat, in either mode (examples/rtdose_export.hpp; without these switches the output is what it was):
+//   --rtdose [--rtdose_bits 16|32]        the dose is quantised on the device and written as dose.dcm (RT Dose) on the CT grid's affine
+//   --reference_rtdose FILE [--gamma DD_PERCENT,DTA_MM]   another system's RT Dose is resampled onto the dose grid on the device and
+//                           compared (global gamma above 10 %, default 3,3): "gamma(3%/3mm): 99.12 % of 123456 voxels, max 1.08"
 #include <sys/stat.h>
 
 #include <map>
@@ -45,6 +49,7 @@ struct Config {
     unsigned int water_cube_edge = 256, layers = 20;
     float start_depth = 0.0f;       // DICOM mode: gantry z of tracer step 0 (0 = just upstream of the CT)
     unsigned int tracer_steps = 0;  // DICOM mode: 0 = as many as it takes to cross the CT
+    DoseExport dose_export;         // --rtdose, --rtdose_bits, --reference_rtdose, --gamma
 };
 
 bool isDir(const std::string& p) { struct stat st; return ::stat(p.c_str(), &st) == 0 && S_ISDIR(st.st_mode); }
@@ -95,7 +100,11 @@ void printHelp() {
                  "  --start_depth FLOAT         DICOM input: gantry z (mm) of tracer step 0 (default: just upstream of the CT).\n"
                  "  --tracer_steps UINT         DICOM input: number of 1 mm tracer steps (default: enough to cross the CT).\n"
                  "  --spot_list TEXT:FILE       With --water_cube: plan from a spot-list text file (E x y fwhm_x fwhm_y meterset).\n"
-                 "  --dump_spot_list TEXT       Write the built-in water-cube plan as a spot list and exit.\n";
+                 "  --dump_spot_list TEXT       Write the built-in water-cube plan as a spot list and exit.\n"
+                 "  --rtdose                    Also write the dose as dose.dcm (DICOM RT Dose) in the output directory.\n"
+                 "  --rtdose_bits UINT          Bits per dose pixel of dose.dcm: 16 (default) or 32.\n"
+                 "  --reference_rtdose TEXT:FILE  RT Dose file to compare the dose with (gamma index on the dose grid).\n"
+                 "  --gamma FLOAT,FLOAT         Dose difference in percent and distance to agreement in mm (3,3).\n";
 }
 
 unsigned long parseUInt(const std::string& key, const std::string& v, unsigned long maxV) {
@@ -132,6 +141,26 @@ void assign(Config& c, const std::string& key, const std::vector<std::string>& v
     else if (key == "layers") c.layers = (unsigned int)parseUInt(key, one(), 256);
     else if (key == "tracer_steps") c.tracer_steps = (unsigned int)parseUInt(key, one(), 4096);
     else if (key == "start_depth") { char* end = nullptr; c.start_depth = std::strtof(one().c_str(), &end); if (*end) usageError("--start_depth: not a number"); }
+    else if (key == "rtdose") {
+        if (vals.empty()) c.dose_export.rtdose = true;
+        else { const std::string v = vals[0]; c.dose_export.rtdose = (v == "true" || v == "1" || v == "on" || v == "yes"); }
+    }
+    else if (key == "rtdose_bits") {
+        c.dose_export.bits = (int)parseUInt(key, one(), 64);
+        if (c.dose_export.bits != 16 && c.dose_export.bits != 32) usageError("--rtdose_bits: must be 16 or 32");
+    }
+    else if (key == "reference_rtdose") c.dose_export.referenceRtdose = one();
+    else if (key == "gamma") {
+        const std::string& v = one();
+        char* end = nullptr;
+        c.dose_export.ddPercent = std::strtof(v.c_str(), &end);
+        if (end == v.c_str() || *end != ',') usageError("--gamma: expected DD_PERCENT,DTA_MM, e.g. 3,3");
+        const char* second = end + 1;
+        c.dose_export.dtaMm = std::strtof(second, &end);
+        if (end == second || *end != '\0') usageError("--gamma: expected DD_PERCENT,DTA_MM, e.g. 3,3");
+        if (!(c.dose_export.ddPercent > 0.0f) || !(c.dose_export.dtaMm > 0.0f) || !std::isfinite(c.dose_export.ddPercent) || !std::isfinite(c.dose_export.dtaMm))
+            usageError("--gamma: both criteria must be positive");
+    }
     else usageError("The following argument was not expected: --" + key);
     seen[key] = true;
 }
@@ -167,6 +196,12 @@ std::string configToStr(const Config& c) {                            // like CL
     o << "water_cube_edge=" << c.water_cube_edge << "\n";
     o << "layers=" << c.layers << "\n";
     o << "spot_list=\"" << c.spot_list << "\"\n";
+    if (c.dose_export.any()) {                                          // (only then: without the switches the echo is what it was)
+        o << "rtdose=" << (c.dose_export.rtdose ? "true" : "false") << "\n";
+        o << "rtdose_bits=" << c.dose_export.bits << "\n";
+        o << "reference_rtdose=\"" << c.dose_export.referenceRtdose << "\"\n";
+        o << "gamma=" << c.dose_export.ddPercent << "," << c.dose_export.dtaMm << "\n";
+    }
     return o.str();
 }
 
@@ -217,6 +252,10 @@ int main(int argc, char** argv) {
     if (!isDir(config.lut_dir)) usageError("--lut_dir: Directory does not exist: " + config.lut_dir);
     if (!config.spot_list.empty() && !isFile(config.spot_list)) usageError("--spot_list: File does not exist: " + config.spot_list);
     if (!config.spot_list.empty() && !config.water_cube) usageError("--spot_list requires --water_cube (CT input is not built yet)");
+    if (seen.count("rtdose_bits") && !config.dose_export.rtdose) usageError("--rtdose_bits requires --rtdose");
+    if (seen.count("gamma") && config.dose_export.referenceRtdose.empty()) usageError("--gamma requires --reference_rtdose");
+    if (!config.dose_export.referenceRtdose.empty() && !isFile(config.dose_export.referenceRtdose))
+        usageError("--reference_rtdose: File does not exist: " + config.dose_export.referenceRtdose);
     std::cout << configToStr(config) << std::endl;
 
     const std::vector<int> gpus = config.gpu_ids.empty() ? std::vector<int>{(int)config.gpu_id} : config.gpu_ids;
@@ -226,7 +265,7 @@ int main(int argc, char** argv) {
     try {
         if (!config.water_cube) {                                       // DICOM input (SURVEY section 8 rows f2 + f3)
             runDicomPlan(config.lut_dir, config.output_directory, config.ct_dir, config.rtplan, config.beams, gpus,
-                         config.start_depth, (int)config.tracer_steps, nullptr, &opt);
+                         config.start_depth, (int)config.tracer_steps, nullptr, &opt, &config.dose_export);
             return 0;
         }
         if (!config.dump_spot_list.empty()) {
@@ -236,9 +275,9 @@ int main(int argc, char** argv) {
             return 0;
         }
         if (!config.spot_list.empty())
-            runSpotListOnWaterCube(config.lut_dir, config.output_directory, config.water_cube_edge, config.spot_list, gpus, &opt);
+            runSpotListOnWaterCube(config.lut_dir, config.output_directory, config.water_cube_edge, config.spot_list, gpus, &opt, &config.dose_export);
         else
-        runWaterCube(config.lut_dir, config.output_directory, config.water_cube_edge, config.layers, gpus, &opt);
+        runWaterCube(config.lut_dir, config.output_directory, config.water_cube_edge, config.layers, gpus, &opt, &config.dose_export);
     } catch (const std::exception& e) {
         std::cerr << "error: " << e.what() << std::endl;
         return 1;

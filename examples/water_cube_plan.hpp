@@ -13,6 +13,7 @@
 #include <sstream>
 
 #include "rtd_dicom.hpp"
+#include "rtdose_export.hpp"
 #include "rtd_plan.hpp"
 #include "rtd_types.hpp"
 #include "rtd_wrapper.hpp"
@@ -132,7 +133,7 @@ inline void readSpotList(const std::string& path, std::vector<rtd_plan::Spot>& s
 // startDepth / tracerSteps <= 0 mean "cover the CT along the beam axis".
 inline void runDicomPlan(const std::string& lutDir, const std::string& outDir, const std::string& ctDir, const std::string& planFile,
                          const std::vector<std::string>& beamNamesIn, const std::vector<int>& gpuIds, float startDepth, int tracerSteps, std::vector<float>* doseOut = nullptr,
-                         const rtd_options* opt = nullptr) {
+                         const rtd_options* opt = nullptr, const DoseExport* ex = nullptr) {
     clock_t t = clock();
     EnergyStruct ciddData = energyReader(lutDir, /*waterCubeTest=*/false);
     std::cout << "Read energy matrix: " << static_cast<float>(clock() - t) / CLOCKS_PER_SEC << " seconds.\n\n";
@@ -176,11 +177,13 @@ inline void runDicomPlan(const std::string& lutDir, const std::string& outDir, c
     fout.close();
     std::cout << "Written " << outDir << "/dose.dat with size " << ct.dim.x << "x" << ct.dim.y << "x" << ct.dim.z << "\n\n";
     std::cout << "Max:" << *std::max_element(dose.begin(), dose.end()) << std::endl;
+    if (ex) exportDose(*ex, outDir, dose, ct.dim, ct.imIdxToWorld, ct.frameOfReferenceUid, gpuIds.empty() ? 0 : gpuIds[0]);
     if (doseOut) *doseOut = dose;
 }
 
 // Dose of a plan given as a spot list on the water cube (CT input proper is SURVEY section 8 row f3).
-inline void runSpotListOnWaterCube(const std::string& lutDir, const std::string& outDir, unsigned int n, const std::string& spotFile, const std::vector<int>& gpuIds, const rtd_options* opt = nullptr) {
+inline void runSpotListOnWaterCube(const std::string& lutDir, const std::string& outDir, unsigned int n, const std::string& spotFile, const std::vector<int>& gpuIds, const rtd_options* opt = nullptr,
+                                   const DoseExport* ex = nullptr) {
     EnergyStruct ciddData = energyReader(lutDir, /*waterCubeTest=*/true);
     WaterCube w(n);
     std::vector<rtd_plan::Spot> spots;
@@ -198,9 +201,11 @@ inline void runSpotListOnWaterCube(const std::string& lutDir, const std::string&
     cudaWrapperProtons(&imVol, &doseVol, beams, ciddData, std::cout, gpuIds, opt);
     std::cout << "Done!\n\n";
     writeDoseAndReport(w, outDir);
+    if (ex) exportDose(*ex, outDir, w.dose, w.dim, w.imIdxToWorld, std::string(), gpuIds.empty() ? 0 : gpuIds[0]);
 }
 
-inline void runWaterCube(const std::string& lutDir, const std::string& outDir, unsigned int n, unsigned int nLayers, const std::vector<int>& gpuIds, const rtd_options* opt = nullptr) {
+inline void runWaterCube(const std::string& lutDir, const std::string& outDir, unsigned int n, unsigned int nLayers, const std::vector<int>& gpuIds, const rtd_options* opt = nullptr,
+                         const DoseExport* ex = nullptr) {
     EnergyStruct ciddData = energyReader(lutDir, /*waterCubeTest=*/true);
     const uint3 dim = make_uint3(n, n, n);
     const size_t N = (size_t)n * n * n;
@@ -243,4 +248,5 @@ inline void runWaterCube(const std::string& lutDir, const std::string& outDir, u
     fout.close();
     std::cout << "Written " << outDir << "/dose.dat with size " << dim.x << "x" << dim.y << "x" << dim.z << "\n\n";
     std::cout << "Max:" << *std::max_element(doseData.begin(), doseData.end()) << std::endl;
+    if (ex) exportDose(*ex, outDir, doseData, dim, imIdxToWorld, std::string(), gpuIds.empty() ? 0 : gpuIds[0]);
 }

@@ -1106,6 +1106,73 @@ int rtd_roi_combine(rtd_handle h, rtd_roi a, rtd_roi b, int op, rtd_roi* out);
 int rtd_roi_from_mask(rtd_handle h, const uint32_t dims[3], const uint8_t* dev_mask, rtd_roi* out);
 
 /*
+ * ---- Dose volumes between grids: resampling through an index map, quantising for RT Dose ----
+ *
+ * Additive to the blocks above (RTD_ABI_VERSION stays 3). A dose that lives on another grid — another system's RT Dose file, a boost
+ * plan, a previous course — is brought onto a destination grid through the affine map from destination voxel index to source voxel
+ * index (rtd_dicom::idxToIdx, raytracedicom_amd.grids.index_map make it from the two index-to-world transforms), so that it can be
+ * compared (rtd_dose_gamma wants one grid) or summed. The source is float32 or the quantised 16 / 32-bit pixels of an RT Dose file as
+ * they stand; the destination is float32; both are x fastest, dims are (x, y, z), both live on the handle's device. Every operation
+ * below is float32 in the stated order, each product, sum and difference rounded, nothing contracted: the same inputs give the same
+ * bits across calls, handles and processes, and the rule can be restated in a few lines (tests/resample_reference.py does).
+ *
+ * Position. For destination voxel (x, y, z) and source axis a = 0, 1, 2, with (m, v) = dst_idx_to_src_idx and (n_0, n_1, n_2) = src_dims:
+ *         p_a = ((m[3a] * float(x) + m[3a + 1] * float(y)) + m[3a + 2] * float(z)) + v[a]
+ * Outside. The voxel is outside iff, for some a, not (p_a > -1.0f and p_a < float(n_a)); a NaN is outside. An outside voxel is written
+ *     +0.0f, or left untouched when accumulate is set; nothing of the source is read for it.
+ * Nodes. f_a = floorf(p_a), t_a = p_a - f_a; the nodes are f_a and f_a + 1 per axis. A node outside [0, n_a - 1] has the value +0.0f
+ *     and is not read: the dose is zero beyond the grid it was computed on, so the result fades to zero over the last half voxel.
+ *     A node inside has the value src[node] for RTD_DOSE_F32 and float(double(raw) * src_scale) for RTD_DOSE_U16 / RTD_DOSE_U32.
+ * Blend. e = the trilinear blend of the 8 nodes, each blend a + t * (b - a) (one difference, one product, one sum), along x, then
+ *     along y, then along z.
+ * Output. out = scale * e;  dst[voxel] = out, or dst[voxel] + out when accumulate is set.
+ * The map is only applied, never inverted: a singular one is legal. Source and destination must not overlap. dev_dst needs the
+ * alignment of a float only (callers pass views into larger volumes).
+ *
+ * rtd_default_resample_options  RTD_DOSE_F32, no accumulation, scale 1, src_scale 1.
+ * rtd_dose_resample             asynchronous on the handle's stream and launches only: no allocation, no copy, no host
+ *                               synchronisation (it can be captured into a graph; a captured call is not timed).
+ * rtd_dose_resample_kernel_ms   the time of the kernel of the handle's last rtd_dose_resample (hipEvents on the handle's stream; it
+ *                               waits for that kernel), for reports. RTD_ERR_NOT_READY before any call.
+ * RTD_ERR_INVALID_ARG, after which nothing has been written: a null pointer; a zero dimension or more than 2^31 - 1 voxels on either
+ * side; an affine entry that is not finite; an unknown src_type; accumulate > 1; a scale that is not finite; an integer source with
+ * src_scale not finite and > 0; a non-zero reserved word.
+ *
+ * rtd_dose_quantize             the write side of RT Dose: dev_dose (n_voxels floats) -> dev_out (n_voxels uint16 or uint32). Synchronous
+ *                               (the scale is needed on the host). With *scaling_inout == 0 the scale is chosen: max = the largest
+ *                               finite dose (from +0.0f; an integer atomicMax on the bit pattern), qmax = 2^bits - 1, s = the double
+ *                               that strtod returns for the "%.10g" text of double(max) / qmax — the text an RT Dose writer stores as
+ *                               DoseGridScaling, so that reader and writer agree on the double — and s = 1 when max == 0. (Ten
+ *                               digits can round the quotient down by 5e-10 of itself, two steps at the top of 32 bits: while
+ *                               rint(double(max) / s) > qmax the quotient is multiplied by 1 + 1e-10 and the text made again.) With
+ *                               *scaling_inout > 0 that scale is used as given. On return *scaling_inout is the scale that was used.
+ *                               q = rint(double(d) / s) in float64, ties to even; stored: 0 when q < 0 or d is a NaN, qmax when
+ *                               q > qmax, q otherwise. *n_clamped (host, or NULL) = the number of voxels with not (0 <= q <= qmax):
+ *                               the clamped ones and the NaNs, an integer count. The first call allocates 16 bytes on the device.
+ * RTD_ERR_INVALID_ARG: a null h, dev_dose, scaling_inout or dev_out; n_voxels == 0; bits other than 16 and 32; a scaling that is
+ * negative or not finite.
+ *
+ * Kernel (rtd_resample.hpp): one lane per destination voxel, lanes along x; the outside test precedes every load; the destination is
+ * written once with non-temporal stores, which leaves the caches to the source nodes that neighbouring lanes and rows share.
+ */
+enum { RTD_DOSE_F32 = 0, RTD_DOSE_U16 = 1, RTD_DOSE_U32 = 2 };
+typedef struct rtd_resample_options {
+    uint32_t src_type;     /* RTD_DOSE_* */
+    uint32_t accumulate;   /* 0: dst[v] = out; 1: dst[v] = dst[v] + out, voxels outside the source untouched */
+    float    scale;        /* 1.0: out = scale * e */
+    uint32_t reserved0;    /* zero */
+    double   src_scale;    /* DoseGridScaling of an integer source; ignored for RTD_DOSE_F32 */
+    uint32_t reserved[2];  /* zero */
+} rtd_resample_options;    /* 32 bytes */
+void rtd_default_resample_options(rtd_resample_options* out);
+int rtd_dose_resample(rtd_handle h, const void* dev_src, const uint32_t src_dims[3], const rtd_affine* dst_idx_to_src_idx,
+                      float* dev_dst, const uint32_t dst_dims[3], const rtd_resample_options* opt);
+int rtd_dose_resample_kernel_ms(rtd_handle h, float* ms);   /* as rtd_dose_gamma_kernel_ms */
+int rtd_dose_quantize(rtd_handle h, const float* dev_dose, size_t n_voxels, int bits /* 16 | 32 */,
+                      double* scaling_inout /* in: > 0 use it, 0 choose; out: the one used */,
+                      void* dev_out /* uint16 or uint32 [n_voxels] */, uint64_t* n_clamped /* host, may be NULL */);
+
+/*
  * ---- Multi-GPU plans behind the boundary (SURVEY.md 8(b) "Threading": one handle and one host thread per device) ----
  *
  * rtd_plan is the reference-shaped call on several GPUs of one process: the 4-beam cudaWrapperProtons of the C++ shim uses

@@ -12,8 +12,19 @@
 // else (big endian, deflate, encapsulated / compressed pixel data) is rejected with a message.
 // Parity: there is no ITK here to compare with, so this reader is pinned by its own writer-side fixtures only
 // (tests/dicom_fixture.py); DESIGN.md says so.
+// RT Dose (readRtDose, writeRtDose) is the one object that is also written: multi-frame, 16 or 32 unsigned bits,
+// MONOCHROME2, one sample per pixel, equally spaced frames in ascending or descending order, relative or absolute frame offsets; the
+// pixels stay integers. Not read: signed or 8-bit pixels, unequal frame steps, per-frame functional groups, compressed transfer
+// syntaxes; DVH and referenced-plan sequences are skipped on input and not written. Parity: this pair is not pinned by each other
+// alone. tests/rtdose_fixture.py holds a Python writer and a Python reader that share no code with this file, the tests cross them
+// with this side in both directions, and one known-answer file is spelled out byte by byte in tests/test_rtdose_io.py. No third-party
+// DICOM toolkit is present to compare with; the files follow PS3.3 C.8.8.3 (RT Dose module) and PS3.5 section 7.1 (element encoding).
 #pragma once
 #include <dirent.h>
+
+#include <cmath>
+#include <cstdio>
+#include <cstdlib>
 
 #include <cstdint>
 #include <cstring>
@@ -63,6 +74,10 @@ inline const char* dictionaryVr(uint32_t t) {
         case 0x300A0394u: case 0x300A0396u: case 0x300A0398u: case 0x300A030Au:
             return "FL";                                              // scan spot position map, meterset weights, spot size, VSAD
         case 0x7FE00010u: return "OW";
+        // RT Dose: frame increment pointer (a tag), number of frames, grid frame offset vector, dose grid scaling
+        case 0x00280009u: return "AT";
+        case 0x00280008u: return "IS";
+        case 0x3004000Cu: case 0x3004000Eu: return "DS";
         default: return nullptr;
     }
 }
@@ -205,6 +220,7 @@ struct CtVolume {
     Float3AffineTransform imIdxToWorld;
     std::string seriesUid, patientPosition;                          // (0018,5100), e.g. HFS
     float3 spacing{0, 0, 0};
+    std::string frameOfReferenceUid;                                  // (0020,0052): what a dose written on this grid refers to
 };
 
 inline CtVolume readCtSeries(const std::string& dir) {
@@ -254,6 +270,7 @@ inline CtVolume readCtSeries(const std::string& dir) {
         throw std::runtime_error(f0.path + ": pixel data shorter than rows x columns");
     ct.dim = make_uint3(nx, ny, nz);
     ct.patientPosition = str(f0.find(tag(0x0018, 0x5100)));
+    ct.frameOfReferenceUid = str(f0.find(tag(0x0020, 0x0052)));
     ct.huPlus1000.resize((size_t)nx * ny * nz);
     for (unsigned int k = 0; k < nz; ++k) {
         const File& f = sl[k].f;
@@ -281,6 +298,240 @@ inline CtVolume readCtSeries(const std::string& dir) {
     ct.imIdxToWorld = Float3AffineTransform(dirM * Matrix3x3(ct.spacing.x, ct.spacing.y, ct.spacing.z),
                                             make_float3((float)sl.front().pos[0], (float)sl.front().pos[1], (float)sl.front().pos[2]));
     return ct;
+}
+
+// ---- RT Dose: a multi-frame dose grid, in and out ----
+// The pixels stay the unsigned 16 / 32-bit integers of the file (rtd_dose_resample reads them as they are, rtd_dose_quantize makes
+// them); dose = raw * DoseGridScaling. idxToWorld is built like imIdxToWorld above: Direction * diag(Spacing), Origin, with the frames
+// in file order — GridFrameOffsetVector may descend, which makes spacing.z and the third column negative.
+struct DoseVolume {
+    uint3 dim{0, 0, 0};
+    Float3AffineTransform idxToWorld;
+    float3 spacing{0, 0, 0};                                          // x = column spacing, y = row spacing, z = the signed frame step
+    int bitsAllocated = 16;                                           // 16 or 32
+    double doseGridScaling = 1.0;
+    std::string doseUnits = "GY", doseType = "PHYSICAL", doseSummationType = "PLAN", frameOfReferenceUid;
+    std::vector<uint16_t> raw16;                                      // x fastest, then y, then frame; the one of the two that bitsAllocated names
+    std::vector<uint32_t> raw32;
+    std::vector<float> toFloat() const {
+        std::vector<float> out((size_t)dim.x * dim.y * dim.z);
+        if (bitsAllocated == 16) for (size_t i = 0; i < out.size(); ++i) out[i] = float(double(raw16[i]) * doseGridScaling);
+        else for (size_t i = 0; i < out.size(); ++i) out[i] = float(double(raw32[i]) * doseGridScaling);
+        return out;
+    }
+};
+
+// UIDs of a written dose; an empty one is derived from the content (writeRtDose).
+struct RtDoseIds { std::string sopInstanceUid, seriesInstanceUid, studyInstanceUid; };
+
+inline DoseVolume readRtDose(const std::string& path) {
+    const File f = readFile(path);
+    const std::string modality = str(f.find(tag(0x0008, 0x0060)));
+    if (modality != "RTDOSE") throw std::runtime_error(path + ": Unknown modality " + modality);
+    auto one = [&](uint16_t g, uint16_t e, const char* what) -> double {
+        const std::vector<double> v = numbers(f.find(tag(g, e)));
+        if (v.size() != 1 || !std::isfinite(v[0])) throw std::runtime_error(path + ": " + what + " is missing");
+        return v[0];
+    };
+    const double rows = one(0x0028, 0x0010, "Rows"), cols = one(0x0028, 0x0011, "Columns"), bits = one(0x0028, 0x0100, "BitsAllocated");
+    const std::vector<double> rep = numbers(f.find(tag(0x0028, 0x0103))), spp = numbers(f.find(tag(0x0028, 0x0002)));
+    if (!rep.empty() && rep[0] != 0.0) throw std::runtime_error(path + ": PixelRepresentation must be 0 (unsigned dose pixels)");
+    if (!spp.empty() && spp[0] != 1.0) throw std::runtime_error(path + ": SamplesPerPixel must be 1");
+    if (bits != 16.0 && bits != 32.0) throw std::runtime_error(path + ": BitsAllocated must be 16 or 32");
+    const std::vector<double> nf = numbers(f.find(tag(0x0028, 0x0008)));
+    const double frames = nf.empty() ? 1.0 : nf[0];
+    if (!(frames >= 1.0) || frames > 2147483647.0 || frames != std::floor(frames)) throw std::runtime_error(path + ": NumberOfFrames must be at least 1");
+    if (!(rows >= 1.0) || !(cols >= 1.0)) throw std::runtime_error(path + ": Rows and Columns must be at least 1");
+    const std::vector<double> off = numbers(f.find(tag(0x3004, 0x000C)));
+    if ((double)off.size() != frames) throw std::runtime_error(path + ": GridFrameOffsetVector needs NumberOfFrames entries");
+    const Element* px = f.find(tag(0x7FE0, 0x0010));
+    const size_t nz = (size_t)frames, frameBytes = (size_t)rows * (size_t)cols * (size_t)(bits / 8.0);   // (at most 2^34)
+    if (!px || px->value.size() / frameBytes < nz)                   // before any allocation sized by the header
+        throw std::runtime_error(path + ": pixel data shorter than rows x columns x frames");
+    const std::vector<double> iop = numbers(f.find(tag(0x0020, 0x0037))), ipp = numbers(f.find(tag(0x0020, 0x0032))), ps = numbers(f.find(tag(0x0028, 0x0030)));
+    if (iop.size() != 6 || ipp.size() != 3 || ps.size() != 2 || !(ps[0] > 0.0) || !(ps[1] > 0.0)) throw std::runtime_error(path + ": incomplete image geometry");
+    const double scaling = one(0x3004, 0x000E, "DoseGridScaling");
+    if (!(scaling > 0.0)) throw std::runtime_error(path + ": DoseGridScaling must be positive");
+    // offsets: relative to the first frame when the first entry is 0, otherwise positions along the normal; either way frame 0 lies at
+    // ImagePositionPatient and the step is what counts
+    double dz = 1.0;
+    if (nz > 1) {
+        dz = (off.back() - off.front()) / double(nz - 1);
+        for (size_t k = 1; k < nz; ++k)
+            if (!(std::fabs((off[k] - off[k - 1]) - dz) <= 1e-3 * std::fabs(dz) + 1e-4)) throw std::runtime_error(path + ": frames are not equally spaced");
+        if (!(std::fabs(dz) > 1e-4)) throw std::runtime_error(path + ": frames are not equally spaced (zero step)");
+    } else {
+        const std::vector<double> th = numbers(f.find(tag(0x0018, 0x0050)));
+        if (!th.empty() && th[0] > 0.0) dz = th[0];
+    }
+    DoseVolume d;
+    d.dim = make_uint3((unsigned int)cols, (unsigned int)rows, (unsigned int)nz);
+    d.bitsAllocated = (int)bits;
+    d.doseGridScaling = scaling;
+    d.doseUnits = str(f.find(tag(0x3004, 0x0002))); d.doseType = str(f.find(tag(0x3004, 0x0004))); d.doseSummationType = str(f.find(tag(0x3004, 0x000A)));
+    d.frameOfReferenceUid = str(f.find(tag(0x0020, 0x0052)));
+    const double rx[3] = {iop[0], iop[1], iop[2]}, cx[3] = {iop[3], iop[4], iop[5]};
+    const double nrm[3] = {rx[1] * cx[2] - rx[2] * cx[1], rx[2] * cx[0] - rx[0] * cx[2], rx[0] * cx[1] - rx[1] * cx[0]};
+    d.spacing = make_float3((float)ps[1], (float)ps[0], (float)dz);   // PixelSpacing = (row spacing, column spacing) = (y, x)
+    const Matrix3x3 dirM(make_float3((float)rx[0], (float)cx[0], (float)nrm[0]), make_float3((float)rx[1], (float)cx[1], (float)nrm[1]),
+                         make_float3((float)rx[2], (float)cx[2], (float)nrm[2]));
+    d.idxToWorld = Float3AffineTransform(dirM * Matrix3x3(d.spacing.x, d.spacing.y, d.spacing.z), make_float3((float)ipp[0], (float)ipp[1], (float)ipp[2]));
+    const size_t n = (size_t)d.dim.x * d.dim.y * nz;
+    if (d.bitsAllocated == 16) { d.raw16.resize(n); std::memcpy(d.raw16.data(), px->value.data(), n * 2); }
+    else { d.raw32.resize(n); std::memcpy(d.raw32.data(), px->value.data(), n * 4); }
+    return d;
+}
+
+namespace detail {
+
+// A decimal string (DS, at most 16 characters) that strtod reads back as exactly v: the shortest "%.{p}g" that does.
+inline std::string exactDs(double v, const std::string& what) {
+    for (int p = 1; p <= 17; ++p) {
+        char text[40];
+        std::snprintf(text, sizeof text, "%.*g", p, v);
+        if (std::strlen(text) <= 16 && std::strtod(text, nullptr) == v) return text;
+    }
+    throw std::runtime_error(what + " cannot be written in the 16 characters of a decimal string without changing it");
+}
+inline std::string ds(double v) { char text[40]; std::snprintf(text, sizeof text, "%.10g", v); return text; }   // (at most 16 characters)
+
+inline uint64_t fnv1a(uint64_t h, const void* p, size_t n) {
+    const unsigned char* b = static_cast<const unsigned char*>(p);
+    for (size_t i = 0; i < n; ++i) { h ^= b[i]; h *= 1099511628211ull; }
+    return h;
+}
+
+// One element in Explicit VR Little Endian; the value is padded to even length (UI with a zero byte, the others with a space).
+inline void putElement(std::string& out, uint16_t g, uint16_t e, const char* vr, std::string value) {
+    const bool binary = !std::strcmp(vr, "US") || !std::strcmp(vr, "UL") || !std::strcmp(vr, "AT") || !std::strcmp(vr, "OB") || !std::strcmp(vr, "OW");
+    if (value.size() & 1) value += (!std::strcmp(vr, "UI") || binary) ? '\0' : ' ';
+    auto u16 = [&](uint16_t v) { out.append(reinterpret_cast<const char*>(&v), 2); };
+    auto u32 = [&](uint32_t v) { out.append(reinterpret_cast<const char*>(&v), 4); };
+    u16(g); u16(e); out.append(vr, 2);
+    if (longVr(vr)) { u16(0); u32((uint32_t)value.size()); } else u16((uint16_t)value.size());
+    out += value;
+}
+inline std::string us(uint16_t v) { return std::string(reinterpret_cast<const char*>(&v), 2); }
+
+}  // namespace detail
+
+// Writes the volume as an RT Dose Storage object, Explicit VR Little Endian, relative frame offsets from 0. Nothing in the file
+// comes from a clock or a random source: the same volume and ids give the same bytes. An empty id is "2.25." + the decimal of a
+// 64-bit FNV-1a hash of the geometry and the pixels (salted per id, so that the three differ).
+inline void writeRtDose(const std::string& path, const DoseVolume& d, const RtDoseIds& ids = RtDoseIds()) {
+    const size_t n = (size_t)d.dim.x * d.dim.y * d.dim.z;
+    if (!n || d.dim.x > 65535u || d.dim.y > 65535u) throw std::runtime_error(path + ": a dose grid needs 1 to 65535 columns and rows and at least one frame");
+    if (d.bitsAllocated != 16 && d.bitsAllocated != 32) throw std::runtime_error(path + ": BitsAllocated must be 16 or 32");
+    const size_t have = d.bitsAllocated == 16 ? d.raw16.size() : d.raw32.size(), bytes = n * (size_t)(d.bitsAllocated / 8);
+    if (have != n) throw std::runtime_error(path + ": the pixel vector does not have columns x rows x frames entries");
+    if (bytes >= 0xFFFFFFFEull) throw std::runtime_error(path + ": pixel data of 4 GiB or more cannot be written uncompressed");
+    if (!(d.doseGridScaling > 0.0) || !std::isfinite(d.doseGridScaling)) throw std::runtime_error(path + ": DoseGridScaling must be positive and finite");
+    // the grid's axes: the columns of the matrix
+    const Matrix3x3 m = d.idxToWorld.getMatrix();
+    const float3 r0 = m.row0(), r1 = m.row1(), r2 = m.row2(), o = d.idxToWorld.getOffset();
+    const double col[3][3] = {{r0.x, r1.x, r2.x}, {r0.y, r1.y, r2.y}, {r0.z, r1.z, r2.z}};
+    double len[3], unit[3][3];
+    for (int a = 0; a < 3; ++a) {
+        len[a] = std::sqrt(col[a][0] * col[a][0] + col[a][1] * col[a][1] + col[a][2] * col[a][2]);
+        if (!(len[a] > 0.0) || !std::isfinite(len[a])) throw std::runtime_error(path + ": the dose grid has an axis of zero length");
+        for (int c = 0; c < 3; ++c) unit[a][c] = col[a][c] / len[a];
+    }
+    auto dot = [](const double* a, const double* b) { return a[0] * b[0] + a[1] * b[1] + a[2] * b[2]; };
+    if (std::fabs(dot(unit[0], unit[1])) > 1e-4 || std::fabs(dot(unit[0], unit[2])) > 1e-4 || std::fabs(dot(unit[1], unit[2])) > 1e-4)
+        throw std::runtime_error(path + ": the dose grid is not orthogonal: RT Dose cannot hold it");
+    const double nrm[3] = {unit[0][1] * unit[1][2] - unit[0][2] * unit[1][1], unit[0][2] * unit[1][0] - unit[0][0] * unit[1][2],
+                           unit[0][0] * unit[1][1] - unit[0][1] * unit[1][0]};
+    const double along = dot(unit[2], nrm);
+    if (std::fabs(std::fabs(along) - 1.0) > 1e-4) throw std::runtime_error(path + ": the frame axis is not parallel to the slice normal");
+    const double dz = along > 0.0 ? len[2] : -len[2];
+    auto joined = [](std::initializer_list<double> v) { std::string s; for (double x : v) { if (!s.empty()) s += '\\'; s += detail::ds(x); } return s; };
+    std::string offsets;
+    for (unsigned int k = 0; k < d.dim.z; ++k) { if (k) offsets += '\\'; offsets += detail::ds(double(k) * dz); }
+    const std::string scalingText = detail::exactDs(d.doseGridScaling, path + ": DoseGridScaling");
+    const void* pixels = d.bitsAllocated == 16 ? static_cast<const void*>(d.raw16.data()) : static_cast<const void*>(d.raw32.data());
+
+    uint64_t h = 14695981039346656037ull;
+    h = detail::fnv1a(h, &d.dim, sizeof d.dim);
+    h = detail::fnv1a(h, col, sizeof col);
+    const double origin[3] = {o.x, o.y, o.z};
+    h = detail::fnv1a(h, origin, sizeof origin);
+    h = detail::fnv1a(h, &d.bitsAllocated, sizeof d.bitsAllocated);
+    h = detail::fnv1a(h, scalingText.data(), scalingText.size());
+    h = detail::fnv1a(h, pixels, bytes);
+    auto uid = [&](const std::string& given, char salt) { return given.empty() ? "2.25." + std::to_string(detail::fnv1a(h, &salt, 1)) : given; };
+    const std::string sop = uid(ids.sopInstanceUid, 'i'), series = uid(ids.seriesInstanceUid, 's'), study = uid(ids.studyInstanceUid, 't');
+    const char* sopClass = "1.2.840.10008.5.1.4.1.1.481.2";          // RT Dose Storage
+
+    std::string meta, data;
+    detail::putElement(meta, 0x0002, 0x0001, "OB", std::string("\0\1", 2));
+    detail::putElement(meta, 0x0002, 0x0002, "UI", sopClass);
+    detail::putElement(meta, 0x0002, 0x0003, "UI", sop);
+    detail::putElement(meta, 0x0002, 0x0010, "UI", "1.2.840.10008.1.2.1");
+    detail::putElement(meta, 0x0002, 0x0012, "UI", "2.25.207496127334810872591512738041279405");   // implementation class: this writer
+    detail::putElement(data, 0x0008, 0x0016, "UI", sopClass);
+    detail::putElement(data, 0x0008, 0x0018, "UI", sop);
+    detail::putElement(data, 0x0008, 0x0060, "CS", "RTDOSE");
+    detail::putElement(data, 0x0020, 0x000D, "UI", study);
+    detail::putElement(data, 0x0020, 0x000E, "UI", series);
+    detail::putElement(data, 0x0020, 0x0032, "DS", joined({origin[0], origin[1], origin[2]}));
+    detail::putElement(data, 0x0020, 0x0037, "DS", joined({unit[0][0], unit[0][1], unit[0][2], unit[1][0], unit[1][1], unit[1][2]}));
+    detail::putElement(data, 0x0020, 0x0052, "UI", d.frameOfReferenceUid);
+    detail::putElement(data, 0x0028, 0x0002, "US", detail::us(1));
+    detail::putElement(data, 0x0028, 0x0004, "CS", "MONOCHROME2");
+    detail::putElement(data, 0x0028, 0x0008, "IS", std::to_string(d.dim.z));
+    detail::putElement(data, 0x0028, 0x0009, "AT", detail::us(0x3004) + detail::us(0x000C));
+    detail::putElement(data, 0x0028, 0x0010, "US", detail::us((uint16_t)d.dim.y));
+    detail::putElement(data, 0x0028, 0x0011, "US", detail::us((uint16_t)d.dim.x));
+    detail::putElement(data, 0x0028, 0x0030, "DS", joined({len[1], len[0]}));                           // (row spacing, column spacing)
+    detail::putElement(data, 0x0028, 0x0100, "US", detail::us((uint16_t)d.bitsAllocated));
+    detail::putElement(data, 0x0028, 0x0101, "US", detail::us((uint16_t)d.bitsAllocated));
+    detail::putElement(data, 0x0028, 0x0102, "US", detail::us((uint16_t)(d.bitsAllocated - 1)));
+    detail::putElement(data, 0x0028, 0x0103, "US", detail::us(0));
+    detail::putElement(data, 0x3004, 0x0002, "CS", d.doseUnits.empty() ? "GY" : d.doseUnits);
+    detail::putElement(data, 0x3004, 0x0004, "CS", d.doseType.empty() ? "PHYSICAL" : d.doseType);
+    detail::putElement(data, 0x3004, 0x000A, "CS", d.doseSummationType.empty() ? "PLAN" : d.doseSummationType);
+    detail::putElement(data, 0x3004, 0x000C, "DS", offsets);
+    detail::putElement(data, 0x3004, 0x000E, "DS", scalingText);
+    detail::putElement(data, 0x7FE0, 0x0010, "OW", std::string(static_cast<const char*>(pixels), bytes));
+
+    std::string file(128, '\0');
+    file += "DICM";
+    const uint32_t metaLen = (uint32_t)meta.size();
+    detail::putElement(file, 0x0002, 0x0000, "UL", std::string(reinterpret_cast<const char*>(&metaLen), 4));
+    file += meta;
+    file += data;
+    std::ofstream out(path.c_str(), std::ios::binary | std::ios::trunc);
+    out.write(file.data(), (std::streamsize)file.size());
+    out.close();
+    if (!out) throw std::runtime_error("Failed to write " + path);
+}
+
+// The map from a voxel index of the destination grid to the voxel index of the source grid at the same place:
+// inverse(srcIdxToWorld) o dstIdxToWorld, composed in double and rounded to float once. This is the rtd_affine rtd_dose_resample takes.
+inline Float3AffineTransform idxToIdx(const Float3AffineTransform& dstIdxToWorld, const Float3AffineTransform& srcIdxToWorld) {
+    auto rows = [](const Float3AffineTransform& t, double m[3][3], double v[3]) {
+        const Matrix3x3 mm = t.getMatrix();
+        const float3 r[3] = {mm.row0(), mm.row1(), mm.row2()}, o = t.getOffset();
+        for (int i = 0; i < 3; ++i) { m[i][0] = r[i].x; m[i][1] = r[i].y; m[i][2] = r[i].z; }
+        v[0] = o.x; v[1] = o.y; v[2] = o.z;
+    };
+    double md[3][3], vd[3], ms[3][3], vs[3];
+    rows(dstIdxToWorld, md, vd); rows(srcIdxToWorld, ms, vs);
+    auto cross = [](const double* a, const double* b, double* c) { c[0] = a[1] * b[2] - a[2] * b[1]; c[1] = a[2] * b[0] - a[0] * b[2]; c[2] = a[0] * b[1] - a[1] * b[0]; };
+    double c0[3], c1[3], c2[3];                                        // the columns of the adjugate: r1 x r2, r2 x r0, r0 x r1
+    cross(ms[1], ms[2], c0); cross(ms[2], ms[0], c1); cross(ms[0], ms[1], c2);
+    const double det = ms[0][0] * c0[0] + ms[0][1] * c0[1] + ms[0][2] * c0[2];
+    if (det == 0.0 || !std::isfinite(det)) throw std::runtime_error("idxToIdx: the source grid's index-to-world matrix is singular");
+    double inv[3][3];
+    for (int i = 0; i < 3; ++i) { inv[i][0] = c0[i] / det; inv[i][1] = c1[i] / det; inv[i][2] = c2[i] / det; }
+    float3 outRows[3]; float outV[3];
+    for (int i = 0; i < 3; ++i) {
+        double e[3];
+        for (int j = 0; j < 3; ++j) e[j] = inv[i][0] * md[0][j] + inv[i][1] * md[1][j] + inv[i][2] * md[2][j];
+        outRows[i] = make_float3((float)e[0], (float)e[1], (float)e[2]);
+        outV[i] = (float)(inv[i][0] * (vd[0] - vs[0]) + inv[i][1] * (vd[1] - vs[1]) + inv[i][2] * (vd[2] - vs[2]));
+    }
+    return Float3AffineTransform(Matrix3x3(outRows[0], outRows[1], outRows[2]), make_float3(outV[0], outV[1], outV[2]));
 }
 
 // ---- RT Ion Plan -> spots + geometry of one beam (main.cu:105-181) ----

@@ -217,6 +217,23 @@ def default_gamma_options():
     return o
 
 
+class RtdResampleOptions(C.Structure):
+    _fields_ = [("src_type", C.c_uint32), ("accumulate", C.c_uint32), ("scale", C.c_float), ("reserved0", C.c_uint32),
+                ("src_scale", C.c_double), ("reserved", C.c_uint32 * 2)]
+
+
+# rtd_resample_options.src_type
+RTD_DOSE_F32, RTD_DOSE_U16, RTD_DOSE_U32 = 0, 1, 2
+
+
+def default_resample_options():
+    """rtd_default_resample_options: a float32 source, written (not accumulated), unscaled."""
+    o = RtdResampleOptions()
+    o.scale = 1.0
+    o.src_scale = 1.0
+    return o
+
+
 def default_optimizer_options():
     """rtd_default_optimizer_options: the step bounds only keep the Barzilai-Borwein step finite."""
     o = RtdOptimizerOptions()

@@ -48,6 +48,7 @@
 #include "rtd_roi_ops.hpp"
 #include "rtd_target.hpp"
 #include "rtd_gamma.hpp"
+#include "rtd_resample.hpp"
 #include "rtd_field_memory.hpp"
 #include "rtd_engine_impl.hpp"
 
@@ -166,6 +167,8 @@ int rtd_destroy(rtd_handle hh) {
     while (!h->fieldCache.empty()) { rtd_field_impl* c = h->fieldCache.back(); h->fieldCache.pop_back(); rtd_field_destroy(hh, reinterpret_cast<rtd_field>(c)); }
     h->clearCtBoxes();
     for (hipEvent_t e : h->gammaEv) if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : h->resampleEv) if (e) (void)hipEventDestroy(e);
+    if (h->dQuantScratch) (void)hipFree(h->dQuantScratch);
     if (h->dLutBlock) (void)hipFree(h->dLutBlock);
     if (h->dCtOwned) (void)hipFree(h->dCtOwned);
     if (h->ownStream) (void)hipStreamDestroy(h->ownStream);
@@ -1374,3 +1377,4 @@ int rtd_compute(rtd_handle hh, const rtd_beam* beams, int n_beams, float* dose_i
 #include "rtd_roi_ops_host.hpp"
 #include "rtd_target_host.hpp"
 #include "rtd_gamma_host.hpp"
+#include "rtd_resample_host.hpp"

@@ -40,6 +40,10 @@ struct rtd_handle_impl {
     bool roiMarginNaive = false;                   // RTD_ROI_MARGIN_NAIVE, likewise: k_roi_margin_naive instead of the separable passes
     hipEvent_t gammaEv[2] = {};                    // around the search kernel of the last call that was not captured (created by the first call)
     bool gammaTimed = false;                       // ... and such a call has been made
+    // rtd_dose_resample, rtd_dose_quantize (rtd_resample_host.hpp)
+    hipEvent_t resampleEv[2] = {};                 // around the kernel of the last rtd_dose_resample that was not captured
+    bool resampleTimed = false;
+    void* dQuantScratch = nullptr;                 // 16 bytes: the bits of the largest dose, the count of clamped voxels (first rtd_dose_quantize)
     void clearCtBoxes() { for (auto& b : ctBoxes) if (b.done) (void)hipEventDestroy(b.done); ctBoxes.clear(); }
 };
 

@@ -127,6 +127,11 @@ def lib():
         L.rtd_default_gamma_options.restype = None
         L.rtd_dose_gamma.argtypes = [vp, vp, vp, u3, C.POINTER(C.c_float), C.POINTER(abi.RtdGammaOptions), vp, vp, vp]
         L.rtd_dose_gamma_kernel_ms.argtypes = [vp, C.POINTER(C.c_float)]
+        L.rtd_default_resample_options.argtypes = [C.POINTER(abi.RtdResampleOptions)]
+        L.rtd_default_resample_options.restype = None
+        L.rtd_dose_resample.argtypes = [vp, vp, u3, C.POINTER(abi.RtdAffine), vp, u3, C.POINTER(abi.RtdResampleOptions)]
+        L.rtd_dose_resample_kernel_ms.argtypes = [vp, C.POINTER(C.c_float)]
+        L.rtd_dose_quantize.argtypes = [vp, vp, C.c_size_t, C.c_int, C.POINTER(C.c_double), vp, C.POINTER(C.c_uint64)]
         L.rtd_host_register.argtypes = [vp, C.c_size_t]
         L.rtd_host_unregister.argtypes = [vp]
         L.rtd_plan_create.argtypes = [C.POINTER(C.c_int), C.c_int, vpp]
@@ -978,6 +983,82 @@ class Engine:
         ms = C.c_float(0)
         self._check(lib().rtd_dose_gamma_kernel_ms(self._h, C.byref(ms)))
         return float(ms.value)
+
+    _DOSE_TYPES = {np.dtype(np.float32): abi.RTD_DOSE_F32, np.dtype(np.uint16): abi.RTD_DOSE_U16, np.dtype(np.uint32): abi.RTD_DOSE_U32}
+
+    def resample_dose_device(self, src_ptr, src_dims, affine, dst_ptr, dst_dims, *, opt=None, **options):
+        """rtd_dose_resample: the device volume src_ptr (dims (x, y, z); float32, or uint16 / uint32 with src_type and src_scale) onto
+        the float32 device volume dst_ptr through affine, the map from destination voxel index to source voxel index (an
+        abi.RtdAffine, or (m, v) for abi.make_affine; grids.index_map makes one from two grids); asynchronous. options: the fields of
+        abi.RtdResampleOptions over their defaults, or a whole record as opt."""
+        if opt is None:
+            opt = abi.RtdResampleOptions()
+            lib().rtd_default_resample_options(C.byref(opt))
+        for k, val in options.items():
+            if k not in ("src_type", "accumulate", "scale", "src_scale"):
+                raise TypeError("resample_dose_device: unknown option %r" % k)
+            setattr(opt, k, int(val) if k in ("src_type", "accumulate") else float(val))
+        if not isinstance(affine, abi.RtdAffine):
+            affine = abi.make_affine(*affine)
+        self._check(lib().rtd_dose_resample(self._h, C.c_void_p(int(src_ptr)) if src_ptr else None, abi.uint3(src_dims), C.byref(affine),
+                                            C.c_void_p(int(dst_ptr)) if dst_ptr else None, abi.uint3(dst_dims), C.byref(opt)))
+
+    def resample_dose(self, src, affine, dst_dims, *, dst=None, **options):
+        """The host volume src ([Z][Y][X]; float32, uint16 or uint32 — the integer ones with src_scale) resampled onto a grid of
+        dst_dims (x, y, z) -> [Z][Y][X] float32. dst: the volume to accumulate into with accumulate=1 (it is not modified)."""
+        src = np.ascontiguousarray(src)
+        if src.dtype not in self._DOSE_TYPES:
+            src = src.astype(np.float32)
+        assert src.ndim == 3
+        shape = (int(dst_dims[2]), int(dst_dims[1]), int(dst_dims[0]))
+        out = np.zeros(shape, dtype=np.float32) if dst is None else abi.f32(dst).copy()
+        assert out.shape == shape
+        d_src, d_dst = self.device_alloc(src.nbytes), None
+        try:
+            d_dst = self.device_alloc(out.nbytes)
+            self.to_device(d_src, src)
+            self.to_device(d_dst, out)
+            self.resample_dose_device(d_src, (src.shape[2], src.shape[1], src.shape[0]), affine, d_dst, dst_dims,
+                                      src_type=self._DOSE_TYPES[src.dtype], **options)
+            self.to_host(out, d_dst)
+            return out
+        finally:
+            self.sync()
+            for p in (d_src, d_dst):
+                if p:
+                    self.device_free(p)
+
+    def resample_kernel_ms(self):
+        """rtd_dose_resample_kernel_ms: the kernel of the last resample_dose / resample_dose_device call, in ms (waits for it)."""
+        ms = C.c_float(0)
+        self._check(lib().rtd_dose_resample_kernel_ms(self._h, C.byref(ms)))
+        return float(ms.value)
+
+    def quantize_dose_device(self, dose_ptr, n_voxels, out_ptr, bits=16, scaling=0.0):
+        """rtd_dose_quantize on device buffers -> (scaling used, n_clamped); synchronous."""
+        s, n = C.c_double(float(scaling)), C.c_uint64(0)
+        self._check(lib().rtd_dose_quantize(self._h, C.c_void_p(int(dose_ptr)), int(n_voxels), int(bits), C.byref(s), C.c_void_p(int(out_ptr)), C.byref(n)))
+        return float(s.value), int(n.value)
+
+    def quantize_dose(self, dose, bits=16, scaling=0.0):
+        """The host dose (float32, any shape) as the unsigned integers of an RT Dose file -> (ints of the same shape, scaling,
+        n_clamped): ints * scaling is the dose to within scaling / 2. scaling 0: chosen from the largest dose."""
+        dose = abi.f32(dose)
+        if bits not in (16, 32):
+            raise RtdError(abi.RTD_ERR_INVALID_ARG, "quantize_dose: bits must be 16 or 32")
+        out = np.empty(dose.shape, dtype=np.uint16 if bits == 16 else np.uint32)
+        d_dose, d_out = self.device_alloc(dose.nbytes), None
+        try:
+            d_out = self.device_alloc(out.nbytes)
+            self.to_device(d_dose, dose)
+            s, n = self.quantize_dose_device(d_dose, dose.size, d_out, bits, scaling)
+            self.to_host(out, d_out)
+            return out, s, n
+        finally:
+            self.sync()
+            for p in (d_dose, d_out):
+                if p:
+                    self.device_free(p)
 
     # device buffers owned by the handle
     def device_alloc(self, nbytes):
