@@ -600,6 +600,11 @@ static int createField(rtd_handle hh, const rtd_beam* b, const uint32_t dose_dim
     hipError_t e = hipMemcpy(f->dSpotWeights, b->spot_weights, nSpot * sizeof(float), hipMemcpyHostToDevice);   // :851
     if (e == hipSuccess) e = hipMemcpy(f->dLayers, f->hLayers.data(), (size_t)L * sizeof(LayerPlan), hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemset(f->dState, 0, sizeof(FieldState));
+    // (k_fill's dead-store bytes describe what the dose and 1/sigma arrays hold: a workspace taken over starts, like a fresh one, with
+    //  none set. Defensive: only a replaying fill reads them, and the walking compute in front of it, a field's first, clears them.)
+    const size_t nDeadBytes = (size_t)L * tilesX * tilesY * kFillSegs;
+    if (e == hipSuccess && !fresh) e = hipMemset(f->dFillDeadSig, 0, nDeadBytes);
+    if (e == hipSuccess && !fresh) e = hipMemset(f->dFillDeadDose, 0, nDeadBytes);
     if (e == hipSuccess) {   // the sample positions at the segment boundaries of k_trace_sample: geometry only, walked once
         k_trace_segpos<<<(unsigned)((R + 255) / 256), 256, 0, h->stream>>>(f->tracer, fc.W, (int)R, f->dSegPos);
         e = hipGetLastError();
@@ -800,11 +805,12 @@ static void launchFill(const ComputeJob& c) {
     const dim3 fillGrid(2 * (fc.W / kSuperpTileX) * (fc.H / kSuperpTileY) * fc.L), fillBlk(kSuperpTileX, kSuperpTileY);
     const NucFill nucFill{f->dNucSpotIdx, f->dNucRayWeights, f->dNucIdd, f->dNucRs};
     const SigmaRec rec{f->dSigRec, f->dSigRecLast, (int)f->memory.sigmaSteps};
+    const FillDead dead = f->sw.noDeadSkip ? FillDead{nullptr, nullptr} : FillDead{f->dFillDeadSig, f->dFillDeadDose};
     auto launchFillOn = [&](auto kern, dim3 grid, size_t lds, hipEvent_t stopEv) {
         launchK(kern, grid, fillBlk, lds, h->stream, nullptr, stopEv, (const float*)f->dDensity, (const float*)f->dWepl, (const float*)f->dRrl, f->dIdd,
                 f->dRSigma, (const float*)f->dRayWeights, (const int*)f->dFirstInside, (const int*)f->dFirstOutside,
                 f->dFirstPassive, f->dTileRad, f->dLayers, f->dState, h->lut, f->fillGeom, fc, (const float*)f->dStepTab, f->dActive, h->numCUs, f->dFillDbg, nucFill, f->dSigMin, f->dSigMax, c.is.tryUniform ? 1 : 0,
-                f->sw.noFillCompact ? 0 : 1, rec);
+                f->sw.noFillCompact ? 0 : 1, rec, dead);
     };
     auto launchFill = [&](auto kern, size_t lds) { launchFillOn(kern, fillGrid, lds, c.ev(kEvFill)); };
     const size_t tabLds = (size_t)fillTabFloats(fc.S) * sizeof(float);      // the block's copy of the step table, behind the rest (S <= kMaxSteps: 16 KiB at most)
@@ -933,7 +939,10 @@ int rtd_field_compute_bev(rtd_handle hh, rtd_field ff) {
     const ComputeJob c{h, f, f->memory.flight, h->opt.fine_grained_timing != 0,
         ResetJob{f->dLayers, fc.L, reinterpret_cast<unsigned int*>(f->dTileRad), f->tileRadWords, f->dActive, (size_t)4 * fc.L * fc.S,
         f->dNucIdd, f->dNucRs, fc.nuclearCorr ? (size_t)fc.nucW * fc.nucH * fc.L : (size_t)0,
-        f->dSigMin, f->dSigMax, (size_t)fc.L * fc.S, f->dScanDbg}};
+        f->dSigMin, f->dSigMax, (size_t)fc.L * fc.S, f->dScanDbg,
+        // (a fill that walks stores every dead value and touches no dead-store byte: the reset in front of it leaves none set)
+        reinterpret_cast<unsigned int*>(f->dFillDeadSig), reinterpret_cast<unsigned int*>(f->dFillDeadDose),
+        f->memory.flight.sigma == 0 && !f->sw.noDeadSkip ? (size_t)fc.L * fc.tilesX * fc.tilesY * kFillSegs / 4 : (size_t)0}};
     if (!c.is.reuse) { const int st = launchTrace(c); if (st != RTD_OK) return st; }
     launchPlanConv(c);
     launchFill(c);

@@ -50,11 +50,11 @@ struct rtd_handle_impl {
 // The engine's RTD_* switches (diagnostics, and the second implementations the tests compare with): read once, when a field is
 // created. RTD_NO_UNIFORM_PATH, RTD_UNIFORM_V2, RTD_NO_SWEEP, RTD_SEPARATE_PLAN, RTD_SEPARATE_KS_PLAN, RTD_NO_TRACE_REUSE (every compute
 // traces and plans the field again), RTD_NO_SIGMA_REUSE (every compute walks the sigma recurrence: no sigma record), RTD_NO_FILL_COMPACT
-// (k_fill deals a tile's rays to its lanes in their natural order),
+// (k_fill deals a tile's rays to its lanes in their natural order), RTD_NO_DEAD_SKIP (k_fill stores every dead value: rtd_fill.hpp, DEAD STORES),
 // RTD_*_DEBUG (per-block clock stamps), and the overrides RTD_TRACE_MODE, RTD_TRACE_DIAG_B, RTD_KS_GROUPS, RTD_SW_GROUPS.
 struct Switches {
     bool noUniformPath = false, uniformV2 = false, noSweep = false, separatePlan = false, separateKsPlan = false, noTraceReuse = false, noFillCompact = false;
-    bool noSigmaReuse = false;
+    bool noSigmaReuse = false, noDeadSkip = false;
     bool scanDebug = false, fillDebug = false, uniformDebug = false, sweepDebug = false;
     std::optional<int> traceMode, traceDiagB, ksGroups, swGroups;
 };
@@ -63,7 +63,7 @@ Switches readSwitches() {
     auto on = [](const char* name) { return std::getenv(name) != nullptr; };
     auto num = [](const char* name) { const char* v = std::getenv(name); return v ? std::optional<int>(std::atoi(v)) : std::nullopt; };
     return Switches{on("RTD_NO_UNIFORM_PATH"), on("RTD_UNIFORM_V2"), on("RTD_NO_SWEEP"), on("RTD_SEPARATE_PLAN"), on("RTD_SEPARATE_KS_PLAN"),
-                    on("RTD_NO_TRACE_REUSE"), on("RTD_NO_FILL_COMPACT"), on("RTD_NO_SIGMA_REUSE"),
+                    on("RTD_NO_TRACE_REUSE"), on("RTD_NO_FILL_COMPACT"), on("RTD_NO_SIGMA_REUSE"), on("RTD_NO_DEAD_SKIP"),
                     on("RTD_SCAN_DEBUG"), on("RTD_FILL_DEBUG"), on("RTD_UNIFORM_DEBUG"), on("RTD_SWEEP_DEBUG"),
                     num("RTD_TRACE_MODE"), num("RTD_TRACE_DIAG_B"), num("RTD_KS_GROUPS"), num("RTD_SW_GROUPS")};
 }
@@ -105,6 +105,8 @@ struct rtd_field_impl {
     LayerPlan* dLayers = nullptr;
     float* dStepTab = nullptr;
     int* dActive = nullptr;      // [L][S][4] minima of (x, y, -x, -y) over rays with dose > 0
+    // k_fill's DEAD STORES (rtd_fill.hpp): per role [L][tiles][kFillSegs] "the segment's steps hold the dead value"; zero when allocated and when taken over
+    unsigned char *dFillDeadSig = nullptr, *dFillDeadDose = nullptr;
     unsigned int *dSigMin = nullptr, *dSigMax = nullptr;   // [L][S] bits of the smallest / largest tile-uniform sigma^2 (uniform-sigma detection)
     bool uniformEligible = false; // the separable superposition may take the field (no nuclear halo, BEV height within its accumulators)
     // What the field learned from its computes (hints, the compute in flight, the trace and plan it reuses, the sigma record's state)
@@ -204,6 +206,7 @@ struct rtd_field_impl {
         visit(dTileRad, tileRadWords * 4, kShape, false, "tile_radius");
         visit(dLayers, L, kShape, false, nullptr); visit(dState, (size_t)1, kShape, false, nullptr); visit(dStepTab, 2 * S, kShape, false, nullptr);
         visit(dActive, 4 * L * S, kShape, false, "active"); visit(dSigMin, L * S, kShape, false, nullptr); visit(dSigMax, L * S, kShape, false, nullptr);
+        visit(dFillDeadSig, L * tiles * kFillSegs, kShape, true, nullptr); visit(dFillDeadDose, L * tiles * kFillSegs, kShape, true, nullptr);
         visit(dNucSpotIdx, nuc * R, kNuclear, false, nullptr); visit(dNucRayWeights, nucR * L, kNuclear, false, nullptr);
         visit(dNucIdd, nucR * L, kNuclear, false, nullptr); visit(dNucRs, nucR * L, kNuclear, false, nullptr);
         visit(dNucBev, nuc * nucBev, kNuclear, false, nullptr); visit(dNucEffT, nucTiles * L, kNuclear, false, nullptr);

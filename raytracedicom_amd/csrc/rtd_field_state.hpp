@@ -231,6 +231,8 @@ struct ResetJob {
     float* nucIdd; float* nucRs; size_t nNuc;      // NUCLEAR_CORR: (0, inf) = the reference's fills at kernel_wrapper.cu:862-863
     unsigned int* sigMin; unsigned int* sigMax; size_t nSig;   // per (layer, step): bits of the smallest / largest tile-uniform sigma^2
     long long* scanDbg;             // diagnostic build only (RTD_SCAN_DEBUG): clock stamps of k_trace_scan's blocks, 8 per block
+    // k_fill's dead-store bytes (rtd_fill.hpp, DEAD STORES), as words, in front of a fill that walks (0 words otherwise): none set
+    unsigned int* deadSig; unsigned int* deadDose; size_t nDeadWords;
 };
 template <bool kKeepPlan = false>
 __device__ inline void resetFieldArrays(const ResetJob& j, size_t t, size_t nT) {
@@ -243,6 +245,7 @@ __device__ inline void resetFieldArrays(const ResetJob& j, size_t t, size_t nT) 
     for (size_t i = t; i < j.nActive; i += nT) j.active[i] = 0x7f7f7f7f;             // empty dose rectangles (+large minima)
     for (size_t i = t; i < j.nNuc; i += nT) { j.nucIdd[i] = 0.0f; j.nucRs[i] = __int_as_float(0x7f800000); }
     for (size_t i = t; i < j.nSig; i += nT) { j.sigMin[i] = 0x7f800000u; j.sigMax[i] = 0u; }
+    for (size_t i = t; i < j.nDeadWords; i += nT) { j.deadSig[i] = 0u; j.deadDose[i] = 0u; }
 }
 
 }  // namespace rtd

@@ -123,6 +123,20 @@ struct SigmaRec {
     int steps;                     // extent of the step axis (accesses beyond it are left out)
 };
 
+// DEAD STORES. A wave without a live ray stores what a dead ray's step leaves: 1/sigma = +inf, dose 0. Under a reused trace most of
+// these stores rewrite what memory already holds, and the replaying build — it alone: the walking and recording builds hold none of
+// this code — leaves them out in two cases (the argument in full: DESIGN.md section 4 K5, "Dead stores").
+//   The tail of a walk: a wave that had a live ray and lost it stores nothing from the last of the end steps of ALL its rays on,
+//   alive under this compute's weights or not (SigmaRec::last: a function of the trace, the same step for both roles).
+//   A wave dead from the start, by bytes that describe memory: one per (layer, tile, segment of kFillSeg rays) and role. A set byte
+//   says: the steps [pFirst, pAfterLast) of the segment's rays hold this role's dead value in this layer. A replaying wave with a
+//   live ray at its start clears the bytes of its segments before its first output store; one dead from the start sets them behind
+//   its last store, and runs its loop without stores when it finds them all set (barriers, exchange buffers and its share of the
+//   classification or the rectangles stay). A walking fill stores everything and sets nothing: the reset in front of it
+//   (ResetJob, rtd_field_state.hpp) clears every byte, which claims nothing. Read when the kernel runs: a graph stays correct.
+// (RTD_NO_DEAD_SKIP: null pointers — every store as before, no bytes.)
+struct FillDead { unsigned char* sig; unsigned char* dose; };       // [L][tiles][kFillSegs] each
+
 // NUC: NUCLEAR_CORR compiled in (its table lookups and IEEE divisions cost registers: the default build keeps 6 blocks per CU)
 template <bool LDS_LUT, bool NUC, int MODE = kFillWalk>
 __global__ __launch_bounds__(256) void k_fill(const float* __restrict__ bevDensity, const float* __restrict__ bevCumulSp,
@@ -134,7 +148,7 @@ __global__ __launch_bounds__(256) void k_fill(const float* __restrict__ bevDensi
                                                LutView lut, FillGeom fg, FieldConst fc, const float* __restrict__ stepTab,
                                                int* __restrict__ active, int nCU, long long* __restrict__ dbg, NucFill nuc,
                                                unsigned int* __restrict__ sigMin, unsigned int* __restrict__ sigMax, int trackUniform,
-                                               int compact, SigmaRec rec) {
+                                               int compact, SigmaRec rec, FillDead dead) {
     static_assert(!NUC || MODE == kFillWalk, "the halo's fields always walk");
     extern __shared__ float sLutF[];                                 // dose walk: the layer's two cumulative-IDD rows
     // diagnostic build only (RTD_FILL_DEBUG): per walk start / end clock, hardware id, item — no output value depends on it
@@ -249,6 +263,31 @@ __global__ __launch_bounds__(256) void k_fill(const float* __restrict__ bevDensi
             sTab[i] = stepTab[2 * k + role];
         }
     }
+    // DEAD STORES (the replaying build only): called once the wave knows whether it has a live ray at its start; wave-uniform throughout
+    unsigned char* const deadBytes = MODE != kFillReplay || !dead.sig ? nullptr
+                                     : (role == 0 ? dead.sig : dead.dose) + ((size_t)layer * nTiles + tileNo) * kFillSegs;
+    bool deadAtStart = false, deadSkip = false;
+    unsigned int waveEnd = 0xffffffffu;                              // the tail of a walk: the last of the steps at which the wave's rays end
+    auto deadOpen = [&]() {
+        if (MODE != kFillReplay) return;
+        deadAtStart = !waveLive;
+        if (!deadBytes) return;
+        const int seg = sSegOf[wave * kFillSegsPerWave + (tid & (kFillSegsPerWave - 1))];
+        if (waveLive) {
+            if ((tid & (kWave - 1)) < kFillSegsPerWave) deadBytes[seg] = 0;
+            waveEnd = (unsigned int)waveMaxI(rec.last[(size_t)layer * memStep + rayIdx]);   // (EVERY lane's ray)
+        }
+        else deadSkip = __ballot(deadBytes[seg] == 0) == 0ull;
+    };
+    auto deadStores = [&](unsigned int step0) {
+        if (MODE != kFillReplay) return true;
+        return deadAtStart ? !deadSkip : !(deadBytes && step0 >= waveEnd);
+    };
+    auto deadClose = [&]() {
+        if (MODE != kFillReplay) return;
+        if (deadBytes && deadAtStart && !deadSkip && (tid & (kWave - 1)) < kFillSegsPerWave)
+            deadBytes[sSegOf[wave * kFillSegsPerWave + (tid & (kFillSegsPerWave - 1))]] = 1;
+    };
     float tabB[kFillBatch];                                          // the batch's entries (wave-uniform)
     auto loadTab = [&](unsigned int step0) {
 #pragma unroll
@@ -292,6 +331,7 @@ __global__ __launch_bounds__(256) void k_fill(const float* __restrict__ bevDensi
             afterLast = beamLive ? (unsigned int)rec.last[(size_t)layer * memStep + rayIdx] : 0u;
             waveLive = __ballot(beamLive && pFirst < afterLast) != 0ull;   // a ray of the wave has a step that is not masked
         }
+        deadOpen();
 #pragma unroll
         for (int j = 0; j < kFillBatch; ++j) {
             if (MODE == kFillReplay) fetchRec(j, pFirst + j);        // (NO BRANCH AROUND A PREFETCH: a wave without a live ray never looks at it)
@@ -430,9 +470,11 @@ __global__ __launch_bounds__(256) void k_fill(const float* __restrict__ bevDensi
                         (rec.sig + recOff + (size_t)(step0 + j - pFirst) * memStep)[rayOff] = kSigMasked;
                 continue;
             }
+            if (deadStores(step0)) {                                      // (DEAD STORES)
 #pragma nounroll
-            for (int j = 0; j < kFillBatch; ++j)
-                if (step0 + j < pAfterLast) (bevRSigmaEff + layerOff + (size_t)(step0 + j) * memStep)[rayOff] = __int_as_float(0x7f800000);
+                for (int j = 0; j < kFillBatch; ++j)
+                    if (step0 + j < pAfterLast) (bevRSigmaEff + layerOff + (size_t)(step0 + j) * memStep)[rayOff] = __int_as_float(0x7f800000);
+            }
             if (deadBufs < 2) {
                 ++deadBufs;
 #pragma unroll
@@ -442,6 +484,7 @@ __global__ __launch_bounds__(256) void k_fill(const float* __restrict__ bevDensi
             classify(step0, buf);
         }
         if (MODE == kFillRecord) { rec.last[(size_t)layer * memStep + rayIdx] = (int)afterLast; return; }
+        deadClose();
         firstPassive[(size_t)layer * memStep + rayIdx] = (int)afterLast;
         if (NUC && nucIdx >= 0 && pFirst < pAfterLast) nuc.rs[(size_t)layer * fc.nucW * fc.nucH + nucIdx] = nucRSigmaEff;   // value of the last step (:367-373)
         int mx = waveMaxI((int)afterLast);
@@ -493,6 +536,7 @@ __global__ __launch_bounds__(256) void k_fill(const float* __restrict__ bevDensi
         // the last ballot of the rays with dose that the wave turned into a rectangle (wave-uniform)
         unsigned long long lastBallot = 0ull;
         unsigned int lastRect = 0xffffffffu;
+        deadOpen();
 #pragma unroll
         for (int j = 0; j < kFillBatch; ++j) {
             if (MODE == kFillReplay || waveLive) fetch1(j, pFirst + j);   // (replay: NO BRANCH AROUND A PREFETCH, a wave without a live ray never looks at it)
@@ -589,9 +633,11 @@ __global__ __launch_bounds__(256) void k_fill(const float* __restrict__ bevDensi
         // The rest of the walk when no ray of the wave is alive (any more): dose 0 in memory, no ray with dose in the block's exchange
         // buffers (those once per buffer) — without inputs and without arithmetic. The barriers and the wave's share of the rectangles stay.
         for (int deadBufs = 0; step0 < pAfterLast; step0 += kFillBatch, buf ^= 1) {
+            if (deadStores(step0)) {                                      // (DEAD STORES)
 #pragma nounroll
-            for (int j = 0; j < kFillBatch; ++j)
-                if (step0 + j < pAfterLast) (bevIdd + layerOff + (size_t)(step0 + j) * memStep)[rayOff] = 0.0f;
+                for (int j = 0; j < kFillBatch; ++j)
+                    if (step0 + j < pAfterLast) (bevIdd + layerOff + (size_t)(step0 + j) * memStep)[rayOff] = 0.0f;
+            }
             if (deadBufs < 2) {
                 ++deadBufs;
                 if ((tid & (kWave - 1)) < kFillBatch) sDoseRect[buf][tid & (kWave - 1)][wave] = 0xffffffffu;
@@ -599,6 +645,7 @@ __global__ __launch_bounds__(256) void k_fill(const float* __restrict__ bevDensi
             ldsBarrier();
             rectangle(step0, buf);
         }
+        deadClose();
         if ((tid & 31) < 4 && actUni != 0x7fffffff) atomicMin(&st->actUnion[tid & 3], actUni);
         if (NUC && nucIdx >= 0 && pFirst < pAfterLast) nuc.idd[(size_t)layer * fc.nucW * fc.nucH + nucIdx] = nucRes;   // value of the last step (:367-373)
     }
