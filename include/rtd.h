@@ -1173,6 +1173,79 @@ int rtd_dose_quantize(rtd_handle h, const float* dev_dose, size_t n_voxels, int 
                       void* dev_out /* uint16 or uint32 [n_voxels] */, uint64_t* n_clamped /* host, may be NULL */);
 
 /*
+ * ---- Dose-averaged LET: the LET-weighted influence matrix, LETd, a LET objective ----
+ *
+ * Additive to the blocks above (RTD_ABI_VERSION stays 3). The convention is the analytical one: the LET of spot j at voxel v is the
+ * LET of that spot's energy at the voxel's water-equivalent depth along the field. With D the field's dose-influence matrix, the
+ * LET-weighted matrix is N[v][j] = float32(D[v][j] * L(l(j), depth[v])) on the SAME sparsity structure; N w is the LET-weighted dose
+ * (keV/um x dose unit, matRad's mLETDose) and LETd = (sum_f N_f w_f) / (sum_f D_f w_f) voxel by voxel. Every rule below is float32 in
+ * the stated order, nothing contracted; tests/let_reference.py restates them in numpy.
+ *
+ * rtd_set_let_table        the table [n_energies][n_energy_samples] float32 in keV/um: the rows of energies_per_u and the depth
+ *                          sampling of cidd_matrix (sample index = depth in mm * scale_facts[e]). Copied into a device allocation of
+ *                          its own. It is not an input of the dose: nothing a compute reuses is invalidated. RTD_ERR_INVALID_ARG when
+ *                          the LUTs are not set, the dimensions differ from the handle's LUTs, or an entry is not finite or is negative.
+ *                          NULL removes the table. Synchronous. A field's LET values belong to the table they were made from: after a
+ *                          new table the products answer RTD_ERR_NOT_READY until rtd_field_let_influence has run again.
+ * rtd_field_water_depth    WRITES, for every voxel of the field's dose box (the box rtd_field_clear_dose clears) and nothing outside it,
+ *                          the field's water-equivalent depth at the voxel in mm into dev_depth (a volume on the field's dose grid).
+ *     Position. p = getFanIdx of the field's transfer parameters at the voxel (what the transfer samples the BEV dose at), moved into
+ *         the indices of the [S][H][W] trace arrays: i = p.x - 32.0f, j = p.y - 32.0f, k = p.z + float(beam_first_inside).
+ *     Depth of trace sample (k, j, i). 0.5f * (wepl[k] + old), old = wepl[k - 1] for k > beam_first_inside and 0 otherwise: the
+ *         mid-point of the cumulative depth before and after the step, where the fill deposits the step's dose.
+ *     Blend. Per axis with extent n: a position that is not >= 0 takes node 0, one >= n - 1 node n - 1, both with weight 0 (CLAMP at
+ *         all six faces; a voxel behind the last step takes the last depth); otherwise nodes floorf(p), floorf(p) + 1 and weight
+ *         a = p - floorf(p). Each blend is (1 - a) * v0 + a * v1, along x, then y, then z.
+ *                          One launch on the handle's stream, no allocation, no synchronisation. RTD_ERR_NOT_READY before any compute
+ *                          of the field; RTD_ERR_INVALID_ARG for a remote field, nuclear_corr or a null pointer. It writes nothing a
+ *                          later transfer, gradient or Dij call reads.
+ * rtd_field_let_influence  computes N for the matrix of the field's last rtd_field_dose_influence (rtd_field_dose_influence_prepare runs
+ *                          first where it has not): the depth above over the matrix's row box, then one values array for the CSC and
+ *                          one for the row-major companion by the same expression (a voxel has one depth and a column one layer: the
+ *                          two hold the same bits; 4 bytes per entry each, no new index arrays).
+ *     Table. L(l, d): rows floor(energyIdx_l) and the next one, clamped to the table, with the fill's row weight
+ *         energyIdx_l - floor(energyIdx_l); within a row the position d * energyScaleFact_l clamped to [0, n_samples - 1] (a NaN to
+ *         0), nodes floor and the next, blends as above: first inside each row, then between the rows.
+ *                          Launches only once its three buffers exist (the first call after a new matrix allocates them).
+ *                          RTD_ERR_NOT_READY without a matrix or without a table; RTD_ERR_OUT_OF_MEMORY when the allocation fails (the
+ *                          matrix stays usable). The values live with the matrix: a new rtd_field_dose_influence discards them, release
+ *                          or destroy frees them. It uses the trace of the field's last compute.
+ * rtd_field_let_influence_apply / _apply_t   N w and N^T g: the kernels of rtd_field_dose_influence_apply / _apply_t launched with the
+ *                          LET values: their summation trees, the init semantics and the box are those. Launches only.
+ *                          RTD_ERR_NOT_READY before rtd_field_let_influence (of the current matrix and table).
+ * rtd_field_let_influence_device   the device pointer of the CSC LET values; the indices are those of rtd_field_dose_influence_device.
+ * rtd_let_average          out[v] = dose[v] > dose_floor ? let_dose[v] / dose[v] : 0 (a float32 division): LETd. One launch; in place on
+ *                          either input is allowed. RTD_ERR_INVALID_ARG for a null pointer or a dose_floor that is not >= 0.
+ * rtd_optimizer_set_let_objective   a second objective on the same dose grid for a plain optimiser, evaluated on the volume
+ *                          sum_f N_f w_f: its ROIs and terms are ordinary ones, so an over-dose term on an organ at risk is a cap on
+ *                          LET x D there. Per iteration the LET-weighted dose is formed the way the dose is, both objectives are
+ *                          evaluated, f = f_dose + f_let in float64, Dij^T g_dose and N^T g_let are computed separately and
+ *                          grad = float32(a + b) per entry in that order; everything after that is unchanged. The optimiser owns one
+ *                          more dose volume, one more g volume and one more gradient vector, allocated in this call, never in
+ *                          rtd_optimizer_run, which stays launches-only and capturable. The objective must outlive its use and be an
+ *                          object other than the optimiser's own. RTD_ERR_NOT_READY unless every field has its LET matrix;
+ *                          RTD_ERR_INVALID_ARG for a robust or voxel-wise optimiser, other dims or an objective without terms. NULL
+ *                          removes it (synchronous): without one the optimiser's bits are what they are without this block.
+ * rtd_optimizer_let_dose   the LET-weighted dose volume of the last iteration (owned by the optimiser).
+ * rtd_optimizer_let_values [f, f_dose, f_let] of the last iteration (synchronous). Both RTD_ERR_NOT_READY without a LET objective.
+ *
+ * Out of scope: LET through the rtd_plan_* path, with nuclear_corr or for remote fields (refused as the matrix itself refuses them);
+ * LET objectives in the robust and voxel-wise optimisers; a command-line flag; a file format for LET tables; variable-RBE models (a
+ * caller builds them voxel-wise from LETd and dose).
+ */
+enum { RTD_ERR_OUT_OF_MEMORY = -7 };   /* a device allocation failed and the call says what stays usable */
+int rtd_set_let_table(rtd_handle h, const float* let_matrix, int32_t n_energies, int32_t n_energy_samples);
+int rtd_field_water_depth(rtd_handle h, rtd_field f, float* dev_depth);
+int rtd_field_let_influence(rtd_handle h, rtd_field f);
+int rtd_field_let_influence_apply(rtd_handle h, rtd_field f, const float* dev_w, float* dev_out, int init);
+int rtd_field_let_influence_apply_t(rtd_handle h, rtd_field f, const float* dev_g, float* dev_spot_grad);
+int rtd_field_let_influence_device(rtd_handle h, rtd_field f, const float** values, size_t* nnz);
+int rtd_let_average(rtd_handle h, const float* dev_let_dose, const float* dev_dose, size_t n_voxels, float dose_floor, float* dev_out);
+int rtd_optimizer_set_let_objective(rtd_handle h, rtd_optimizer opt, rtd_objective let_objective);
+int rtd_optimizer_let_dose(rtd_handle h, rtd_optimizer opt, const float** dev);
+int rtd_optimizer_let_values(rtd_handle h, rtd_optimizer opt, double values[3]);
+
+/*
  * ---- Multi-GPU plans behind the boundary (SURVEY.md 8(b) "Threading": one handle and one host thread per device) ----
  *
  * rtd_plan is the reference-shaped call on several GPUs of one process: the 4-beam cudaWrapperProtons of the C++ shim uses

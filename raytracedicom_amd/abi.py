@@ -17,6 +17,7 @@ RTD_ERR_RADIUS_OVERFLOW = -3
 RTD_ERR_NOT_READY = -4
 RTD_ERR_IO = -5
 RTD_ERR_NO_DEVICE = -6
+RTD_ERR_OUT_OF_MEMORY = -7     # the LET block
 RTD_NUC_OFF, RTD_NUC_SOUKUP, RTD_NUC_FLUKA, RTD_NUC_GAUSS_FIT = 0, 1, 2, 3
 RTD_OBJ_SQ_DEVIATION, RTD_OBJ_SQ_OVERDOSE, RTD_OBJ_SQ_UNDERDOSE, RTD_OBJ_MEAN = 0, 1, 2, 3
 RTD_OBJ_MAX_TERMS = 64

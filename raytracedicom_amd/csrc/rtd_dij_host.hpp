@@ -3,6 +3,35 @@
 // run through its rtd_field_compute_bev and transferImpl. The matrix's buffers are the field's (classes kDij, kDijOut of its table).
 #pragma once
 
+namespace {
+
+// The two products' launches with a values array of the matrix's structure: the dose's (rtd_field_dose_influence_apply / _apply_t) or
+// the LET-weighted one (rtd_let_host.hpp). cVals: the row-major companion's values; vals: the CSC's.
+int dijApplyLaunch(rtd_handle_impl* h, rtd_field_impl* f, const float* cVals, const float* dev_spot_weights, float* dev_dose, int init) {
+    const long long nRows = (long long)f->dijRowsN;
+    if (nRows == 0 || (!init && f->dijNnz == 0)) return RTD_OK;       // nothing to write: no launch
+    const unsigned g = (unsigned)((nRows * kDijApGroup + 255) / 256);
+    auto launch = [&](auto kern) {
+        kern<<<g, 256, 0, h->stream>>>((const long long*)f->dDijRowPtr, (const int*)f->dDijCCols, cVals, dev_spot_weights, dev_dose,
+                                       (int)f->doseDims[0], (int)f->doseDims[1], f->dijBox, nRows);
+    };
+    if (init) launch(k_dijap_apply<true>); else launch(k_dijap_apply<false>);
+    RTD_HIP(h, hipGetLastError());
+    return RTD_OK;
+}
+int dijApplyTLaunch(rtd_handle_impl* h, rtd_field_impl* f, const float* vals, const float* dev_voxel_weights, float* dev_spot_grad) {
+    const int nSpot = f->fc.spotNx * f->fc.spotNy * f->fc.L, nChunks = (int)f->dijChunks;
+    if (nChunks)
+        k_dijap_apply_t<<<(unsigned)((nChunks + 3) / 4), 256, 0, h->stream>>>((const long long*)f->dDijColPtr, (const int*)f->dDijRows, vals,
+                                                                            (const int*)f->dDijChunkCol, (const int*)f->dDijChunkFirst, dev_voxel_weights,
+                                                                            f->dDijPartial, nChunks);
+    k_dijap_reduce_t<<<(unsigned)((nSpot + 3) / 4), 256, 0, h->stream>>>((const int*)f->dDijChunkFirst, (const float*)f->dDijPartial, dev_spot_grad, nSpot);
+    RTD_HIP(h, hipGetLastError());
+    return RTD_OK;
+}
+
+}  // namespace
+
 extern "C" {
 
 // Dose-influence matrix of a field (include/rtd.h; kernels in rtd_dij.hpp). One forward at the field's own
@@ -27,7 +56,7 @@ int rtd_field_dose_influence(rtd_handle hh, rtd_field ff, float rel_threshold, s
     RTD_HIP(h, hipSetDevice(h->device));
     hipStream_t s = h->stream;
     const size_t nSpot = (size_t)fc.spotNx * fc.spotNy * fc.L;
-    f->dijDone = false;
+    f->dijDone = false; f->letDone = false;                           // (the LET values belong to the matrix that is replaced)
     if (!f->dDijSave) {
         f->dijCap = (size_t)1 << 20;
         const int st = allocBuffers(h, f, kDij);
@@ -182,7 +211,7 @@ int rtd_field_dose_influence(rtd_handle hh, rtd_field ff, float rel_threshold, s
     std::vector<long long> colPtr(nSpot + 1, 0);
     for (size_t j = 0; j < nSpot; ++j) colPtr[j + 1] = colPtr[j] + colLen[j];
     freeBuffers(f, kDijOut);                                          // (with it what rtd_field_dose_influence_prepare built)
-    f->dijPrepared = false;
+    f->dijPrepared = false; f->letAlloc = false;
     { const FieldState& fin = *f->hState; for (int i = 0; i < 3; ++i) { f->dijOwnBox[i] = fin.tboxMin[i]; f->dijOwnBox[3 + i] = fin.tboxMax[i]; } }
     f->dijNnz = (size_t)colPtr[nSpot];
     { const int ast = allocBuffers(h, f, kDijOut); if (ast != RTD_OK) { freeBuffers(f, kDijOut); f->dijNnz = 0; return ast; } }
@@ -334,16 +363,7 @@ int rtd_field_dose_influence_apply(rtd_handle hh, rtd_field ff, const float* dev
     if (!f->dijDone) return fail(h, RTD_ERR_NOT_READY, "rtd_field_dose_influence_apply: no dose-influence matrix (call rtd_field_dose_influence first)");
     if (!f->dijPrepared) { const int st = rtd_field_dose_influence_prepare(hh, ff); if (st != RTD_OK) return st; }
     RTD_HIP(h, hipSetDevice(h->device));
-    const long long nRows = (long long)f->dijRowsN;
-    if (nRows == 0 || (!init && f->dijNnz == 0)) return RTD_OK;       // nothing to write: no launch
-    const unsigned g = (unsigned)((nRows * kDijApGroup + 255) / 256);
-    auto launch = [&](auto kern) {
-        kern<<<g, 256, 0, h->stream>>>((const long long*)f->dDijRowPtr, (const int*)f->dDijCCols, (const float*)f->dDijCVals, dev_spot_weights, dev_dose,
-                                       (int)f->doseDims[0], (int)f->doseDims[1], f->dijBox, nRows);
-    };
-    if (init) launch(k_dijap_apply<true>); else launch(k_dijap_apply<false>);
-    RTD_HIP(h, hipGetLastError());
-    return RTD_OK;
+    return dijApplyLaunch(h, f, f->dDijCVals, dev_spot_weights, dev_dose, init);
 }
 
 // Dij^T g on the handle's stream (the chunk sums, then their sums per column).
@@ -356,14 +376,7 @@ int rtd_field_dose_influence_apply_t(rtd_handle hh, rtd_field ff, const float* d
     if (!f->dijDone) return fail(h, RTD_ERR_NOT_READY, "rtd_field_dose_influence_apply_t: no dose-influence matrix (call rtd_field_dose_influence first)");
     if (!f->dijPrepared) { const int st = rtd_field_dose_influence_prepare(hh, ff); if (st != RTD_OK) return st; }
     RTD_HIP(h, hipSetDevice(h->device));
-    const int nSpot = f->fc.spotNx * f->fc.spotNy * f->fc.L, nChunks = (int)f->dijChunks;
-    if (nChunks)
-        k_dijap_apply_t<<<(unsigned)((nChunks + 3) / 4), 256, 0, h->stream>>>((const long long*)f->dDijColPtr, (const int*)f->dDijRows, (const float*)f->dDijVals,
-                                                                            (const int*)f->dDijChunkCol, (const int*)f->dDijChunkFirst, dev_voxel_weights,
-                                                                            f->dDijPartial, nChunks);
-    k_dijap_reduce_t<<<(unsigned)((nSpot + 3) / 4), 256, 0, h->stream>>>((const int*)f->dDijChunkFirst, (const float*)f->dDijPartial, dev_spot_grad, nSpot);
-    RTD_HIP(h, hipGetLastError());
-    return RTD_OK;
+    return dijApplyTLaunch(h, f, f->dDijVals, dev_voxel_weights, dev_spot_grad);
 }
 
 }  // extern "C"

@@ -49,6 +49,7 @@
 #include "rtd_target.hpp"
 #include "rtd_gamma.hpp"
 #include "rtd_resample.hpp"
+#include "rtd_let.hpp"
 #include "rtd_field_memory.hpp"
 #include "rtd_engine_impl.hpp"
 
@@ -169,6 +170,7 @@ int rtd_destroy(rtd_handle hh) {
     for (hipEvent_t e : h->gammaEv) if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : h->resampleEv) if (e) (void)hipEventDestroy(e);
     if (h->dQuantScratch) (void)hipFree(h->dQuantScratch);
+    if (h->dLetTable) (void)hipFree(h->dLetTable);
     if (h->dLutBlock) (void)hipFree(h->dLutBlock);
     if (h->dCtOwned) (void)hipFree(h->dCtOwned);
     if (h->ownStream) (void)hipStreamDestroy(h->ownStream);
@@ -426,6 +428,7 @@ int rtd_field_release(rtd_handle hh, rtd_field ff) {
     f->memory = FieldMemory{};
     f->gradDone = false; f->targetProjected = false; f->targetSelected = false;
     f->dijDone = false; f->dijPrepared = false; f->dijCap = 0; f->dijNnz = 0; f->dijBatchOf.clear();
+    f->letAlloc = false; f->letDone = false;
     f->released = shapeCounts(f);
     h->fieldCache.push_back(f);
     return RTD_OK;
@@ -1387,3 +1390,4 @@ int rtd_compute(rtd_handle hh, const rtd_beam* beams, int n_beams, float* dose_i
 #include "rtd_target_host.hpp"
 #include "rtd_gamma_host.hpp"
 #include "rtd_resample_host.hpp"
+#include "rtd_let_host.hpp"

@@ -44,6 +44,11 @@ struct rtd_handle_impl {
     hipEvent_t resampleEv[2] = {};                 // around the kernel of the last rtd_dose_resample that was not captured
     bool resampleTimed = false;
     void* dQuantScratch = nullptr;                 // 16 bytes: the bits of the largest dose, the count of clamped voxels (first rtd_dose_quantize)
+    // rtd_set_let_table (rtd_let_host.hpp): an allocation of its own, [letEnergies][letSamples]; not an input of the dose (no epoch of
+    // the above moves with it). letEpoch counts the tables set: a field's LET values belong to the table they were made from.
+    float* dLetTable = nullptr;
+    int letEnergies = 0, letSamples = 0;
+    unsigned letEpoch = 0;
     void clearCtBoxes() { for (auto& b : ctBoxes) if (b.done) (void)hipEventDestroy(b.done); ctBoxes.clear(); }
 };
 
@@ -167,6 +172,12 @@ struct rtd_field_impl {
     int dijOwnBox[6] = {0, 0, 0, -1, -1, -1};   // the field's dose box (min, max) when the matrix was computed
     DijBox dijBox{};               // ... united with the bounding box of the matrix's rows: the voxels that have a row
     size_t dijRowsN = 0, dijChunks = 0;
+    // the LET-weighted values on the matrix's structure (rtd_field_let_influence, rtd_let.hpp): a second values array for the CSC, one
+    // for the row-major companion, and the water-equivalent depth of the voxels of dijBox. With the matrix's result (class kDijOut).
+    float *dLetVals = nullptr, *dLetCVals = nullptr, *dLetDepth = nullptr;
+    bool letAlloc = false;         // the buffer table lists the three
+    bool letDone = false;          // ... and they hold the values of the CSC result under the handle's table number letEpoch
+    unsigned letEpoch = 0;
     // the target in beam's-eye view (rtd_field_project_target / rtd_field_select_spots, rtd_target.hpp): allocated by the first projection
     unsigned int* dTargetBev = nullptr;      // [ceil(S / 32)][H][W] bit k & 31 of word k >> 5: sample (ray, step k) lies in the target
     unsigned char* dTargetHit = nullptr;     // [L][H][W] the layer hits of the last selection
@@ -228,6 +239,9 @@ struct rtd_field_impl {
         visit(dDijCVals, ap * std::max<size_t>(dijNnz, 1), kDijOut, false, nullptr); visit(dDijChunkFirst, ap * (nSpot + 1), kDijOut, false, nullptr);
         visit(dDijChunkCol, ap * std::max<size_t>(dijChunks, 1), kDijOut, false, nullptr);
         visit(dDijPartial, ap * std::max<size_t>(dijChunks, 1), kDijOut, false, nullptr);
+        const size_t lt = letAlloc ? 1 : 0;      // (only after rtd_field_let_influence)
+        visit(dLetVals, lt * std::max<size_t>(dijNnz, 1), kDijOut, false, nullptr); visit(dLetCVals, lt * std::max<size_t>(dijNnz, 1), kDijOut, false, nullptr);
+        visit(dLetDepth, lt * std::max<size_t>(dijRowsN, 1), kDijOut, false, nullptr);
         visit(dTargetBev, ((S + 31) / 32) * R, kTarget, false, "target_bev"); visit(dTargetHit, L * R, kTarget, false, "target_hit");
         visit(dTargetSum, (size_t)1, kTarget, false, nullptr); visit(dTargetCount, (size_t)1, kTarget, false, nullptr);
         visit(dSigRec, memory.sigmaSteps * R * L, kSigmaRec, false, nullptr); visit(dSigRecLast, memory.sigmaSteps ? R * L : (size_t)0, kSigmaRec, false, nullptr);

@@ -29,6 +29,11 @@ struct rtd_optimizer_impl {
     // The voxel-wise worst case (section 15): a robust optimiser whose steps 2 and 3 are one composite evaluation and its own decision.
     bool voxelwise = false;
     DevBuf<unsigned> dActive;               // one word: the scenarios that received a non-zero voxel gradient
+    // The LET objective of a plain optimiser (section 22; rtd_optimizer_set_let_objective in rtd_let_host.hpp allocates all of it): the
+    // LET-weighted dose sum_f N_f w_f, its voxel gradient, N^T g_let, and [values of letObj (1 + kObjMaxTerms) | f, f_dose, f_let].
+    rtd_objective_impl* letObj = nullptr;
+    DevBuf<float> dLetDose, dLetG, dLetGrad;
+    DevBuf<double> dLetValues;
     rtd_field_impl* sf(int s, size_t i) const { return sfields[(size_t)s * fields.size() + i]; }
     float* w() const { return dVec; }
     float* wPrev() const { return dVec + n; }
@@ -49,6 +54,27 @@ int scenarioForward(rtd_handle hh, rtd_handle_impl* h, rtd_optimizer_impl* p, in
     }
     for (size_t i = 0; i < p->fields.size(); ++i) {
         const int st = rtd_field_dose_influence_apply(hh, reinterpret_cast<rtd_field>(p->sf(s, i)), p->w() + p->offset[i], p->doseS[s], i == 0 ? 1 : 0);
+        if (st != RTD_OK) return st;
+    }
+    return RTD_OK;
+}
+// The same two products with the LET-weighted values of the fields (a plain optimiser with a LET objective): dLetDose = sum_f N_f w_f
+// formed the way scenarioForward forms the dose, dLetGrad[offset[i] ..] = N_i^T g_let.
+int letForward(rtd_handle hh, rtd_handle_impl* h, rtd_optimizer_impl* p) {
+    for (size_t i = 1; i < p->fields.size(); ++i) {
+        const rtd_field_impl* f = p->fields[i];
+        const long long nRows = (long long)f->dijRowsN;
+        if (nRows) k_opt_clear_box<<<(unsigned)((nRows + 255) / 256), 256, 0, h->stream>>>(p->dLetDose, (int)f->doseDims[0], (int)f->doseDims[1], f->dijBox, nRows);
+    }
+    for (size_t i = 0; i < p->fields.size(); ++i) {
+        const int st = rtd_field_let_influence_apply(hh, reinterpret_cast<rtd_field>(p->fields[i]), p->w() + p->offset[i], p->dLetDose, i == 0 ? 1 : 0);
+        if (st != RTD_OK) return st;
+    }
+    return RTD_OK;
+}
+int letAdjoint(rtd_handle hh, rtd_optimizer_impl* p) {
+    for (size_t i = 0; i < p->fields.size(); ++i) {
+        const int st = rtd_field_let_influence_apply_t(hh, reinterpret_cast<rtd_field>(p->fields[i]), p->dLetG, p->dLetGrad + p->offset[i]);
         if (st != RTD_OK) return st;
     }
     return RTD_OK;
@@ -332,6 +358,10 @@ int rtd_optimizer_run(rtd_handle hh, rtd_optimizer pp, uint32_t n_iterations) {
     if (!h) return RTD_ERR_INVALID_ARG;
     if (!p) return fail(h, RTD_ERR_INVALID_ARG, "rtd_optimizer_run: null pointer");
     if (p->obj->terms.empty()) return fail(h, RTD_ERR_INVALID_ARG, "rtd_optimizer_run: the objective has no terms");
+    if (p->letObj)                                                    // (in front of the first launch: a refused run launches nothing)
+        for (const rtd_field_impl* f : p->fields)
+            if (!(f->dijDone && f->letDone && h->dLetTable && f->letEpoch == h->letEpoch))
+                return fail(h, RTD_ERR_NOT_READY, "rtd_optimizer_run: a field's LET-weighted matrix is not that of its matrix and the handle's table (call rtd_field_let_influence again)");
     RTD_HIP(h, hipSetDevice(h->device));
     hipStream_t s = h->stream;
     for (uint32_t k = 0; k < n_iterations; ++k) {
@@ -340,6 +370,14 @@ int rtd_optimizer_run(rtd_handle hh, rtd_optimizer pp, uint32_t n_iterations) {
             st = scenarioForward(hh, h, p, 0);                                            // 1.
             if (st == RTD_OK) st = evalObjective(h, p->obj, p->dDose, p->dValues, p->dG); // 2.
             if (st == RTD_OK) st = scenarioAdjoint(hh, p, 0, p->grad());                  // 3.
+            if (st == RTD_OK && p->letObj) {                                              // the same three on the LET-weighted dose; then f and grad are the sums
+                st = letForward(hh, h, p);
+                if (st == RTD_OK) st = evalObjective(h, p->letObj, p->dLetDose, p->dLetValues, p->dLetG);
+                if (st == RTD_OK) st = letAdjoint(hh, p);
+                if (st == RTD_OK)
+                    k_let_add<<<(unsigned)std::max((p->n + 255) / 256, 1), 256, 0, s>>>(p->grad(), (const float*)p->dLetGrad, p->n, p->dValues,
+                                                                                       (const double*)p->dLetValues, p->dLetValues + 1 + kObjMaxTerms);
+            }
         } else {                              // sections 14 and 15, steps 1.-5.: they differ in the evaluation and in who decides on it
             st = robustForward(hh, h, p);
             if (p->voxelwise) {

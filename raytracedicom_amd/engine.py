@@ -132,6 +132,16 @@ def lib():
         L.rtd_dose_resample.argtypes = [vp, vp, u3, C.POINTER(abi.RtdAffine), vp, u3, C.POINTER(abi.RtdResampleOptions)]
         L.rtd_dose_resample_kernel_ms.argtypes = [vp, C.POINTER(C.c_float)]
         L.rtd_dose_quantize.argtypes = [vp, vp, C.c_size_t, C.c_int, C.POINTER(C.c_double), vp, C.POINTER(C.c_uint64)]
+        L.rtd_set_let_table.argtypes = [vp, abi.c_float_p, C.c_int32, C.c_int32]
+        L.rtd_field_water_depth.argtypes = [vp, vp, vp]
+        L.rtd_field_let_influence.argtypes = [vp, vp]
+        L.rtd_field_let_influence_apply.argtypes = [vp, vp, vp, vp, C.c_int]
+        L.rtd_field_let_influence_apply_t.argtypes = [vp, vp, vp, vp]
+        L.rtd_field_let_influence_device.argtypes = [vp, vp, vpp, C.POINTER(C.c_size_t)]
+        L.rtd_let_average.argtypes = [vp, vp, vp, C.c_size_t, C.c_float, vp]
+        L.rtd_optimizer_set_let_objective.argtypes = [vp, vp, vp]
+        L.rtd_optimizer_let_dose.argtypes = [vp, vp, vpp]
+        L.rtd_optimizer_let_values.argtypes = [vp, vp, C.POINTER(C.c_double)]
         L.rtd_host_register.argtypes = [vp, C.c_size_t]
         L.rtd_host_unregister.argtypes = [vp]
         L.rtd_plan_create.argtypes = [C.POINTER(C.c_int), C.c_int, vpp]
@@ -308,6 +318,31 @@ class Field:
         cp, ri, va, n = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_size_t(0)
         self.eng._check(lib().rtd_field_dose_influence_device(self.eng._h, self._h, C.byref(cp), C.byref(ri), C.byref(va), C.byref(n)))
         return int(cp.value or 0), int(ri.value or 0), int(va.value or 0), int(n.value)
+
+    def water_depth(self, dev_depth):
+        """rtd_field_water_depth: WRITES the field's water-equivalent depth (mm) of every voxel of its dose box into dev_depth (a
+        volume on the dose grid, device pointer); nothing outside the box is touched. One launch after a compute of the field."""
+        self.eng._check(lib().rtd_field_water_depth(self.eng._h, self._h, C.c_void_p(int(dev_depth))))
+
+    def let_influence(self):
+        """rtd_field_let_influence: the LET-weighted values N = float32(D * L) on the structure of the last dose_influence() matrix,
+        from the engine's LET table (Engine.set_let_table). They live with the matrix."""
+        self.eng._check(lib().rtd_field_let_influence(self.eng._h, self._h))
+
+    def let_apply(self, dev_w, dev_out, init=False):
+        """rtd_field_let_influence_apply: N w, the LET-weighted dose (keV/um x dose unit); arguments as dose_influence_apply."""
+        self.eng._check(lib().rtd_field_let_influence_apply(self.eng._h, self._h, C.c_void_p(int(dev_w)), C.c_void_p(int(dev_out)), int(bool(init))))
+
+    def let_apply_t(self, dev_g, dev_out):
+        """rtd_field_let_influence_apply_t: N^T g; arguments as dose_influence_apply_t."""
+        self.eng._check(lib().rtd_field_let_influence_apply_t(self.eng._h, self._h, C.c_void_p(int(dev_g)), C.c_void_p(int(dev_out))))
+
+    def let_influence_device(self):
+        """rtd_field_let_influence_device: (values, nnz) — the device pointer of the CSC LET values as an int and the entry count; the
+        indices are those of dose_influence_device()."""
+        va, n = C.c_void_p(), C.c_size_t(0)
+        self.eng._check(lib().rtd_field_let_influence_device(self.eng._h, self._h, C.byref(va), C.byref(n)))
+        return int(va.value or 0), int(n.value)
 
     def set_spot_weights(self, dev_spot_weights):
         """rtd_field_set_spot_weights: new [L][ny][nx] float32 weights from device memory (stream-ordered)."""
@@ -742,6 +777,25 @@ class Optimizer:
         self.eng._check(lib().rtd_optimizer_dose(self.eng._h, self._h, C.byref(p)))
         return int(p.value or 0)
 
+    def set_let_objective(self, let_objective):
+        """rtd_optimizer_set_let_objective: a second Objective, evaluated on the LET-weighted dose sum_f N_f w_f (every field needs
+        let_influence() first); None removes it. Everything it needs is allocated here, never in run()."""
+        h = let_objective._h if let_objective is not None else None
+        self.eng._check(lib().rtd_optimizer_set_let_objective(self.eng._h, self._h, h))
+        self.let_objective = let_objective
+
+    def let_dose(self):
+        """Device pointer of the optimiser's LET-weighted dose volume (of the iterate that entered the last iteration)."""
+        p = C.c_void_p()
+        self.eng._check(lib().rtd_optimizer_let_dose(self.eng._h, self._h, C.byref(p)))
+        return int(p.value or 0)
+
+    def let_values(self):
+        """Waits; float64 [f, f_dose, f_let] of the last iteration."""
+        v = np.zeros(3, dtype=np.float64)
+        self.eng._check(lib().rtd_optimizer_let_values(self.eng._h, self._h, v.ctypes.data_as(C.POINTER(C.c_double))))
+        return v
+
     def scenario_values(self):
         """Waits; (values float64[S], lambdas float64[S], worst): every scenario's objective, its share of the combined gradient and
         the worst scenario, of the iterate that entered the last iteration. A plain optimiser is a set of one scenario."""
@@ -794,6 +848,22 @@ class Engine:
     def set_luts(self, es):
         la = es.as_abi()
         self._check(lib().rtd_set_luts(self._h, C.byref(la)))
+
+    def set_let_table(self, table):
+        """rtd_set_let_table: the LET table [n_energies][n_energy_samples] float32 in keV/um on the rows and the depth sampling of the
+        LUTs' cidd_matrix (luts.synth_let makes one); None removes it. Not an input of the dose."""
+        if table is None:
+            self._check(lib().rtd_set_let_table(self._h, None, 0, 0))
+            return
+        t = abi.f32(table)
+        if t.ndim != 2:
+            raise ValueError("the LET table is [n_energies][n_energy_samples]")
+        self._check(lib().rtd_set_let_table(self._h, abi.fptr(t), int(t.shape[0]), int(t.shape[1])))
+
+    def let_average(self, dev_let_dose, dev_dose, n_voxels, dev_out, dose_floor=0.0):
+        """rtd_let_average: LETd = let_dose / dose where dose > dose_floor, 0 elsewhere (device pointers; in place is allowed)."""
+        self._check(lib().rtd_let_average(self._h, C.c_void_p(int(dev_let_dose)), C.c_void_p(int(dev_dose)), int(n_voxels), C.c_float(dose_floor),
+                                          C.c_void_p(int(dev_out))))
 
     def load_luts_dir(self, directory, water_cube_test=False):
         self._check(lib().rtd_load_luts_dir(self._h, directory.encode(), int(water_cube_test)))

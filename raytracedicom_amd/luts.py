@@ -200,3 +200,23 @@ def synth_luts(n_energies=147, n_samples=1024, n_hu=3072, seed=0, nuclear=False)
         nw = 0.12 * np.clip(frac, 0.0, 1.0) * (peaks[:, None] / peaks.max()) ** 0.5
         nq = (0.023 * peaks[:, None] * np.clip(frac, 0.0, 1.3)) ** 2 + 1.0
     return EnergyStruct(energies, peaks, scale, cidd, 1.0, dens, 1.0, sp, 1000.0, rrl, nw, nq)
+
+
+LET_P = 1.77            # Bragg-Kleeman exponent of the range-energy relation R = alpha E^p (protons in water)
+LET_ALPHA = 0.0022      # cm MeV^-p
+LET_R_MIN_MM = 0.1      # floor of the residual range: the table is finite and stays at its cap behind the peak
+
+
+def synth_let(es):
+    """A deterministic LET table [nEnergies][nEnergySamples] float32 in keV/um for an EnergyStruct, from the Bragg-Kleeman relation.
+
+    With R = alpha E^p the stopping power at residual range r is -dE/dz = r^(1/p - 1) / (p alpha^(1/p)) (MeV/cm, r in cm), and
+    1 MeV/cm = 0.1 keV/um. Row i is sampled like ciddMatrix: sample j lies at depth z_j = j / scaleFacts[i] mm, and
+        r_j = max(peakDepths[i] - z_j, LET_R_MIN_MM) / 10        (cm)
+        LET[i][j] = 0.1 * r_j^(1/p - 1) / (p * alpha^(1/p))
+    with p = LET_P = 1.77, alpha = LET_ALPHA = 0.0022 cm MeV^-p and LET_R_MIN_MM = 0.1 mm (a cap of about 13 keV/um). Evaluated in
+    float64 and rounded once: non-decreasing in depth up to the peak, constant at the cap behind it."""
+    j = np.arange(es.nEnergySamples, dtype=np.float64)[None, :]
+    z = j / es.scaleFacts.astype(np.float64)[:, None]
+    r = np.maximum(es.peakDepths.astype(np.float64)[:, None] - z, LET_R_MIN_MM) / 10.0
+    return abi.f32(0.1 * r ** (1.0 / LET_P - 1.0) / (LET_P * LET_ALPHA ** (1.0 / LET_P)))
