@@ -236,6 +236,18 @@ int rtd_compute(rtd_handle h, const rtd_beam* beams, int n_beams, float* dose_in
  * a 96 x 88 x 20 ray grid with 200 such steps; if the allocation fails the field keeps computing the recurrence and no error is
  * raised. RTD_NO_SIGMA_REUSE in the environment when the field is created: every compute runs the recurrence.
  * rtd_field_fetch "sigma_reused" tells what the last launched compute did.
+ *
+ * Beside the sigma record a field whose fill fits the GPU at once — 2 x layers x (ray grid / 256) blocks of 256 threads all
+ * resident: about 1800 blocks on an MI355X; larger fields keep none and compute their dose as before — keeps a dose record of the
+ * same extent (as many bytes again, so budget twice the figure above for such a field): per (layer, step, ray) the
+ * difference of the cumulative depth dose that the fill's dose walk looks up, or a mark where the walk forces the dose to 0. It is
+ * allocated, recorded, valid and dropped with the sigma record, and the replay forms the dose from it with the walk's own operations:
+ * bit for bit the walk's result. If its allocation alone fails the field replays sigma and walks the dose; no error is raised.
+ * RTD_NO_DOSE_REPLAY in the environment when the field is created: no dose record (RTD_NO_SIGMA_REUSE and RTD_NO_TRACE_REUSE leave
+ * it out too). rtd_field_fetch "dose_reused" tells what the last launched compute did. A compute that records or replays both
+ * records checks that every step of every layer lies inside them; if not (the inputs were changed in place without rtd_set_ct*),
+ * rtd_field_finish, rtd_field_wait_plan and rtd_field_dose_influence return RTD_ERR_NOT_READY, the records and the trace are
+ * dropped, and the next compute traces and walks again.
  */
 int rtd_field_create(rtd_handle h, const rtd_beam* beam, const uint32_t dose_dims[3], rtd_field* out);
 int rtd_field_compute(rtd_handle h, rtd_field f, float* dev_dose);
@@ -317,6 +329,7 @@ int rtd_set_stream(rtd_handle h, void* hip_stream);
  * "layer_plan" [L][8] float (energyIdx, scaleFact, peakDepth, entrySigmaX, entrySigmaY, afterLast, 0, 0);
  * "trace_reused" int32[1]: 1 if the last launched compute reused the field's trace and plan (see rtd_field_compute).
  * "sigma_reused" int32[1]: the sigma recurrence of the last launched compute: 0 walked, 1 recorded and replayed, 2 replayed.
+ * "dose_reused" int32[1]: the dose walk of the last launched compute, likewise (never ahead of "sigma_reused").
  * "target_bev" and "target_hit": see rtd_field_project_target below.
  * Returns the number of bytes the buffer holds via *bytes_needed when host_out is NULL.
  */

@@ -171,6 +171,9 @@ int rtd_field_dose_influence(rtd_handle hh, rtd_field ff, float rel_threshold, s
         if (e == hipSuccess) e = hipStreamSynchronize(s);
         if (e != hipSuccess) { hipFail(e); break; }
         f->memory.sigmaFinished(f->hState->errorFlags);               // (the batch's forward has drained: the later batches only replay)
+        if (f->hState->errorFlags & kErrRecordExtent) {               // (reported as takeFindings reports it)
+            h->error = "a layer's steps exceed the field's sigma and dose records (inputs modified in place?): the records and the trace are dropped, recompute"; st = RTD_ERR_NOT_READY; break;
+        }
         if ((size_t)(total + count) > f->dijCap) {                   // grow the batch-major staging geometrically (the stream is idle)
             size_t cap = f->dijCap;
             while (cap < (size_t)(total + count)) cap *= 2;

@@ -786,7 +786,9 @@ static void launchPlanConv(const ComputeJob& c) {
 
 // The sigma record of a field that has none that fits its plan (SigmaRecord::kAllocateThenRecord, rtd_field_memory.hpp): `need` steps
 // long. A failed allocation is no error: the field keeps walking.
-static void allocSigmaRecord(rtd_handle_impl* h, rtd_field_impl* f, size_t need) {
+// The dose record (LaunchDecision::dose) is allocated with it, at the same extent; if that allocation alone fails the field keeps the
+// sigma record and walks the dose.
+static void allocSigmaRecord(rtd_handle_impl* h, rtd_field_impl* f, size_t need, bool withDose) {
     if (f->dSigRec) {                                                 // a smaller record is replaced: an earlier compute may still read it
         (void)hipStreamSynchronize(h->stream);
         freeBuffers(f, kSigmaRec);
@@ -797,7 +799,33 @@ static void allocSigmaRecord(rtd_handle_impl* h, rtd_field_impl* f, size_t need)
         (void)hipGetLastError();                                      // (out of memory is not sticky: cleared here)
         freeBuffers(f, kSigmaRec);
         f->memory.sigmaAllocationFailed();
+        return;
     }
+    if (withDose && hipMalloc((void**)&f->dDoseRec, need * f->R * (size_t)f->fc.L * sizeof(unsigned int)) != hipSuccess) {
+        (void)hipGetLastError();
+        f->dDoseRec = nullptr;
+        f->memory.doseAllocationFailed();
+    }
+}
+
+// Where the dose record pays. A replayed dose step has fewer instructions and no LDS round trip, but its record is 4 bytes per
+// (LAYER, step, ray) from memory where the walk's inputs are shared by all layers of a step. While every block of the fill is resident
+// at once the launch lasts as long as its longest block, a serial chain of steps, and the shorter step wins (C3: -8 us). With more
+// blocks than fit the GPU the launch is bound by what all blocks move and issue together, and the record's bytes cost more than the
+// arithmetic saves (C2, 2560 blocks on 256 CUs: +8 us with the record). So the dose record is kept only by a field whose fill fits.
+static bool doseReplayPays(rtd_handle_impl* h, rtd_field_impl* f) {
+    const FieldConst& fc = f->fc;
+    if (f->fillResident < 0 && f->sw.doseReplayBlocks) f->fillResident = std::max(*f->sw.doseReplayBlocks, 0);   // (RTD_DOSE_REPLAY_BLOCKS)
+    if (f->fillResident < 0) {
+        int perCU = 0;
+        const size_t lds = (size_t)(fillTabOffset(false, 0) + fillTabFloats(fc.S)) * sizeof(float);
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCU, k_fill_dr<false, false, kFillReplay>, kSuperpTileX * kSuperpTileY, lds) != hipSuccess) {
+            (void)hipGetLastError();
+            perCU = 0;
+        }
+        f->fillResident = perCU * h->numCUs;
+    }
+    return 2 * (fc.W / kSuperpTileX) * (fc.H / kSuperpTileY) * fc.L <= f->fillResident;
 }
 
 // K5: the fill.
@@ -807,22 +835,29 @@ static void launchFill(const ComputeJob& c) {
     // (layer, tile, role) items: sigma walk and dose walk of every tile; placement is decided in the kernel
     const dim3 fillGrid(2 * (fc.W / kSuperpTileX) * (fc.H / kSuperpTileY) * fc.L), fillBlk(kSuperpTileX, kSuperpTileY);
     const NucFill nucFill{f->dNucSpotIdx, f->dNucRayWeights, f->dNucIdd, f->dNucRs};
+    // (the dose record is handed to the launches of a compute that records or replays it, and to no other)
     const SigmaRec rec{f->dSigRec, f->dSigRecLast, (int)f->memory.sigmaSteps};
+    unsigned int* const recDose = c.is.dose ? f->dDoseRec : nullptr;
     const FillDead dead = f->sw.noDeadSkip ? FillDead{nullptr, nullptr} : FillDead{f->dFillDeadSig, f->dFillDeadDose};
-    auto launchFillOn = [&](auto kern, dim3 grid, size_t lds, hipEvent_t stopEv) {
+    auto launchFillOn = [&](auto kern, dim3 grid, size_t lds, hipEvent_t stopEv, auto... more) {   // (more: k_fill_dr's recDose)
         launchK(kern, grid, fillBlk, lds, h->stream, nullptr, stopEv, (const float*)f->dDensity, (const float*)f->dWepl, (const float*)f->dRrl, f->dIdd,
                 f->dRSigma, (const float*)f->dRayWeights, (const int*)f->dFirstInside, (const int*)f->dFirstOutside,
                 f->dFirstPassive, f->dTileRad, f->dLayers, f->dState, h->lut, f->fillGeom, fc, (const float*)f->dStepTab, f->dActive, h->numCUs, f->dFillDbg, nucFill, f->dSigMin, f->dSigMax, c.is.tryUniform ? 1 : 0,
-                f->sw.noFillCompact ? 0 : 1, rec, dead);
+                f->sw.noFillCompact ? 0 : 1, rec, dead, more...);
     };
     auto launchFill = [&](auto kern, size_t lds) { launchFillOn(kern, fillGrid, lds, c.ev(kEvFill)); };
     const size_t tabLds = (size_t)fillTabFloats(fc.S) * sizeof(float);      // the block's copy of the step table, behind the rest (S <= kMaxSteps: 16 KiB at most)
     const bool ldsLut = fillLds + tabLds <= 56 * 1024;   // (+ ~1 KiB of static arrays: stays under the 64 KiB default cap of a block's LDS)
     // the sigma walk's exchange buffers share the dynamic LDS with the dose walk's LUT rows (fillTabOffset: the kernel's view of the same layout)
     const size_t dynLds = (size_t)fillTabOffset(ldsLut, h->lut.nSamples) * sizeof(float) + tabLds;
-    // the record pass: the sigma walk of every (layer, tile) alone, in front of the fill that replays it (inside the fill's timing bucket)
-    if (c.is.sigma == 1) launchFillOn((k_fill<false, false, kFillRecord>), dim3(fillGrid.x / 2), (size_t)0, nullptr);
-    if (c.is.sigma) { if (ldsLut) launchFill((k_fill<true, false, kFillReplay>), dynLds); else launchFill((k_fill<false, false, kFillReplay>), dynLds); }
+    // the record pass: the sigma walk of every (layer, tile) alone — with a dose record to fill, the dose walk of each as well — in front
+    // of the fill that replays it (inside the fill's timing bucket)
+    // (k_fill_dr: the kernel that holds the dose record's code; k_fill's builds are what they were without it)
+    if (c.is.sigma == 1 && c.is.dose) launchFillOn((k_fill_dr<false, false, kFillRecord>), fillGrid, (size_t)0, nullptr, recDose);
+    else if (c.is.sigma == 1) launchFillOn((k_fill<false, false, kFillRecord>), dim3(fillGrid.x / 2), (size_t)0, nullptr);
+    // (a replayed dose step looks nothing up: the block's dynamic LDS is the sigma role's exchange buffers and the step table)
+    if (c.is.dose) launchFillOn((k_fill_dr<false, false, kFillReplay>), fillGrid, (size_t)fillTabOffset(false, h->lut.nSamples) * sizeof(float) + tabLds, c.ev(kEvFill), recDose);
+    else if (c.is.sigma) { if (ldsLut) launchFill((k_fill<true, false, kFillReplay>), dynLds); else launchFill((k_fill<false, false, kFillReplay>), dynLds); }
     else if (fc.nuclearCorr) { if (ldsLut) launchFill((k_fill<true, true>), dynLds); else launchFill((k_fill<false, true>), dynLds); }
     else { if (ldsLut) launchFill((k_fill<true, false>), dynLds); else launchFill((k_fill<false, false>), dynLds); }
 }
@@ -935,10 +970,11 @@ int rtd_field_compute_bev(rtd_handle hh, rtd_field ff) {
     RTD_HIP(h, hipStreamIsCapturing(s, &cs));
     // What the field knows decides what is left out (rtd_field_memory.hpp): the launches in front of the convolution, the uniform-sigma
     // detection and kernel, the general superposition kernel (all of whose ~10^5 blocks would only look at a flag and leave), the sigma walk.
-    const LaunchDecision d = f->memory.decide(LaunchInputs{h->inputEpoch, cs != hipStreamCaptureStatusNone, reuseAllowed, f->uniformEligible, f->sw.noSigmaReuse});
+    const LaunchDecision d = f->memory.decide(LaunchInputs{h->inputEpoch, cs != hipStreamCaptureStatusNone, reuseAllowed, f->uniformEligible, f->sw.noSigmaReuse,
+                                                            f->sw.noDoseReplay || !doseReplayPays(h, f)});
     if (!d.flight.reuse) { const int st = ensureCtBox(h, f); if (st != RTD_OK) return st; }
     f->memory.launched(d);
-    if (d.sigma == SigmaRecord::kAllocateThenRecord) allocSigmaRecord(h, f, d.need);
+    if (d.sigma == SigmaRecord::kAllocateThenRecord) allocSigmaRecord(h, f, d.need, d.dose);
     const ComputeJob c{h, f, f->memory.flight, h->opt.fine_grained_timing != 0,
         ResetJob{f->dLayers, fc.L, reinterpret_cast<unsigned int*>(f->dTileRad), f->tileRadWords, f->dActive, (size_t)4 * fc.L * fc.S,
         f->dNucIdd, f->dNucRs, fc.nuclearCorr ? (size_t)fc.nucW * fc.nucH * fc.L : (size_t)0,
@@ -1135,6 +1171,7 @@ int rtd_field_finish(rtd_handle hh, rtd_field ff, rtd_timing* timing, rtd_field_
         }
         if (info) fillInfo(f, st, info);
         if (st.errorFlags & kErrPackOverflow) return fail(h, RTD_ERR_INVALID_ARG, "BEV message buffer too small for the exported slab");
+        if (st.errorFlags & kErrRecordExtent) return fail(h, RTD_ERR_NOT_READY, "a layer's steps exceed the field's sigma and dose records (inputs modified in place?): the records and the trace are dropped, recompute");
         if (st.errorFlags & kErrRadiusOverflow)
             return fail(h, RTD_ERR_RADIUS_OVERFLOW, "Found larger than allowed kernel superposition radius");
         return RTD_OK;
@@ -1300,6 +1337,10 @@ int rtd_field_fetch(rtd_handle hh, rtd_field ff, const char* name, void* host_ou
         std::memcpy(staging.data(), &v, n);
     } else if (nm == "sigma_reused") {
         const int32_t v = f->computed ? f->memory.flight.sigma : 0;       // the last launched compute: 0 walked, 1 recorded and replayed, 2 replayed
+        n = sizeof v; staging.resize(n);
+        std::memcpy(staging.data(), &v, n);
+    } else if (nm == "dose_reused") {
+        const int32_t v = f->computed ? f->memory.flight.dose : 0;        // ... its dose walk likewise
         n = sizeof v; staging.resize(n);
         std::memcpy(staging.data(), &v, n);
     } else if (nm == "eff_radius" || nm == "layer_plan") {

@@ -56,21 +56,24 @@ struct rtd_handle_impl {
 // created. RTD_NO_UNIFORM_PATH, RTD_UNIFORM_V2, RTD_NO_SWEEP, RTD_SEPARATE_PLAN, RTD_SEPARATE_KS_PLAN, RTD_NO_TRACE_REUSE (every compute
 // traces and plans the field again), RTD_NO_SIGMA_REUSE (every compute walks the sigma recurrence: no sigma record), RTD_NO_FILL_COMPACT
 // (k_fill deals a tile's rays to its lanes in their natural order), RTD_NO_DEAD_SKIP (k_fill stores every dead value: rtd_fill.hpp, DEAD STORES),
-// RTD_*_DEBUG (per-block clock stamps), and the overrides RTD_TRACE_MODE, RTD_TRACE_DIAG_B, RTD_KS_GROUPS, RTD_SW_GROUPS.
+// RTD_NO_DOSE_REPLAY (no dose record: the dose role of every compute walks; RTD_NO_SIGMA_REUSE and RTD_NO_TRACE_REUSE leave it out too),
+// RTD_*_DEBUG (per-block clock stamps), and the overrides RTD_TRACE_MODE, RTD_TRACE_DIAG_B, RTD_KS_GROUPS, RTD_SW_GROUPS,
+// RTD_DOSE_REPLAY_BLOCKS (the number of k_fill blocks taken to be resident at once: a field with more keeps no dose record, doseReplayPays.
+// It exists for tests/test_gpu_dose_replay.py, which has no other way to a field whose fill does not fit; not a user-facing switch.)
 struct Switches {
     bool noUniformPath = false, uniformV2 = false, noSweep = false, separatePlan = false, separateKsPlan = false, noTraceReuse = false, noFillCompact = false;
-    bool noSigmaReuse = false, noDeadSkip = false;
+    bool noSigmaReuse = false, noDeadSkip = false, noDoseReplay = false;
     bool scanDebug = false, fillDebug = false, uniformDebug = false, sweepDebug = false;
-    std::optional<int> traceMode, traceDiagB, ksGroups, swGroups;
+    std::optional<int> traceMode, traceDiagB, ksGroups, swGroups, doseReplayBlocks;
 };
 
 Switches readSwitches() {
     auto on = [](const char* name) { return std::getenv(name) != nullptr; };
     auto num = [](const char* name) { const char* v = std::getenv(name); return v ? std::optional<int>(std::atoi(v)) : std::nullopt; };
     return Switches{on("RTD_NO_UNIFORM_PATH"), on("RTD_UNIFORM_V2"), on("RTD_NO_SWEEP"), on("RTD_SEPARATE_PLAN"), on("RTD_SEPARATE_KS_PLAN"),
-                    on("RTD_NO_TRACE_REUSE"), on("RTD_NO_FILL_COMPACT"), on("RTD_NO_SIGMA_REUSE"), on("RTD_NO_DEAD_SKIP"),
+                    on("RTD_NO_TRACE_REUSE"), on("RTD_NO_FILL_COMPACT"), on("RTD_NO_SIGMA_REUSE"), on("RTD_NO_DEAD_SKIP"), on("RTD_NO_DOSE_REPLAY"),
                     on("RTD_SCAN_DEBUG"), on("RTD_FILL_DEBUG"), on("RTD_UNIFORM_DEBUG"), on("RTD_SWEEP_DEBUG"),
-                    num("RTD_TRACE_MODE"), num("RTD_TRACE_DIAG_B"), num("RTD_KS_GROUPS"), num("RTD_SW_GROUPS")};
+                    num("RTD_TRACE_MODE"), num("RTD_TRACE_DIAG_B"), num("RTD_KS_GROUPS"), num("RTD_SW_GROUPS"), num("RTD_DOSE_REPLAY_BLOCKS")};
 }
 
 // Classes of a field's device buffers: the workspace that a field of the same shape takes over (rtd_field_release), the NUCLEAR_CORR
@@ -119,6 +122,8 @@ struct rtd_field_impl {
     // steps) is allocated by the first compute that reuses the trace, freed by rtd_field_release / _destroy.
     FieldMemory memory;
     unsigned int* dSigRec = nullptr; int* dSigRecLast = nullptr;
+    unsigned int* dDoseRec = nullptr;   // the dose record, [L][memory.doseSteps][R] words: allocated and freed with the sigma record
+    int fillResident = -1;              // blocks of the dose-replaying k_fill that the GPU holds at once (-1: not asked yet; doseReplayPays)
     // NUCLEAR_CORR (default off): the halo on the spot-resolution grid
     int* dNucSpotIdx = nullptr; float *dNucRayWeights = nullptr, *dNucIdd = nullptr, *dNucRs = nullptr, *dNucBev = nullptr;
     int* dNucEffT = nullptr;
@@ -245,6 +250,7 @@ struct rtd_field_impl {
         visit(dTargetBev, ((S + 31) / 32) * R, kTarget, false, "target_bev"); visit(dTargetHit, L * R, kTarget, false, "target_hit");
         visit(dTargetSum, (size_t)1, kTarget, false, nullptr); visit(dTargetCount, (size_t)1, kTarget, false, nullptr);
         visit(dSigRec, memory.sigmaSteps * R * L, kSigmaRec, false, nullptr); visit(dSigRecLast, memory.sigmaSteps ? R * L : (size_t)0, kSigmaRec, false, nullptr);
+        visit(dDoseRec, memory.doseSteps * R * L, kSigmaRec, false, nullptr);
         visit(dScanDbg, sw.scanDebug ? 8 * (R / 64) : 0, kDiag, true, "scan_debug");
         visit(dFillDbg, sw.fillDebug ? 4 * 2 * tiles * L : 0, kDiag, false, "fill_debug");
         visit(dUniDbg, sw.uniformDebug && uniformEligible && uniform4() ? 16 * S * nPartsU4 : 0, kDiag, true, "uniform_debug");
@@ -318,6 +324,10 @@ hipError_t raiseLdsCap(rtd_handle_impl* h, K kernel, size_t bytes) {
 int takeFindings(rtd_handle_impl* h, rtd_field_impl* f, const FieldState& st) {
     const bool notUniform = f->memory.finished(FieldFindings{st.errorFlags, st.empty != 0, st.uniformField != 0, st.maxRadius, st.beamFirstInside,
                                                              st.firstGuaranteedPassive});
+    // (k_fill_dr: a layer has steps beyond the records it recorded or replayed. The error flag has just dropped the records and the
+    //  trace in the memory above; every caller that takes findings — rtd_field_finish, rtd_field_wait_plan, rtd_field_dose_influence —
+    //  reports it from here.)
+    if (st.errorFlags & kErrRecordExtent) return fail(h, RTD_ERR_NOT_READY, "a layer's steps exceed the field's sigma and dose records (inputs modified in place?): the records and the trace are dropped, recompute");
     if (notUniform)
         return fail(h, RTD_ERR_NOT_READY, "the field was launched as a uniform-sigma field but is not one: its inputs were modified in place; call rtd_set_ct* again and recompute");
     return RTD_OK;

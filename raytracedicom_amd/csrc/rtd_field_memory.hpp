@@ -55,6 +55,7 @@ struct ComputeInFlight {
     bool knownUniform = false;    // the general superposition kernel was left out on the strength of the hint
     int sigma = 0;                // k_fill's sigma role: 0 walked, 1 recorded and replayed, 2 replayed (rtd_field_fetch "sigma_reused")
     bool planInSweep = false;     // no k_ks_plan launch: block 0 of k_superpose_sweep's launch was the plan
+    int dose = 0;                 // k_fill's dose role, likewise (rtd_field_fetch "dose_reused"): never ahead of `sigma`
 };
 
 // What a launch is decided from, besides the memory.
@@ -64,6 +65,7 @@ struct LaunchInputs {
     bool traceReuseAllowed;       // the field's configuration lets a compute go without tracer, scan and plan at all
     bool uniformEligible;         // the separable superposition may take the field
     bool noSigmaReuse;            // RTD_NO_SIGMA_REUSE
+    bool noDoseReplay = false;    // RTD_NO_DOSE_REPLAY
 };
 
 enum class SigmaRecord { kWalk, kAllocateThenRecord, kRecord, kReplay };   // no record / make room for `need` steps first / record / replay
@@ -73,6 +75,7 @@ struct LaunchDecision {
     bool capturing;
     SigmaRecord sigma;
     size_t need;                  // kAllocateThenRecord: the step extent to allocate
+    bool dose = false;            // the dose record goes with the sigma record: allocated, recorded or replayed as `sigma` says
 };
 
 // What a finished compute's state record tells the host.
@@ -90,6 +93,10 @@ struct FieldMemory {
     int planFirst = 0, planSteps = 0;   // beamFirstInside and the steps up to firstGuaranteedPassive of the trace in use
     size_t sigmaSteps = 0;        // extent of the sigma record's step axis (0: no record allocated)
     bool sigmaFailed = false;     // its allocation failed once: not tried again
+    // The dose record (rtd_fill.hpp) shares the sigma record's life: allocated with it at the same extent, recorded by the same pass,
+    // usable under the same epoch, dropped by the same events. It has no state of its own but whether it exists beside the sigma record.
+    size_t doseSteps = 0;         // extent of the dose record's step axis: sigmaSteps, or 0 (no dose record: the dose role walks)
+    bool doseFailed = false;      // its allocation alone failed once: the field replays sigma and walks the dose, not tried again
 
     // The launch of a compute under `in`, decided and not yet recorded (the caller may still fail in front of its first launch).
     LaunchDecision decide(const LaunchInputs& in) const {
@@ -112,17 +119,23 @@ struct FieldMemory {
             else d.sigma = sigma.usableUnder(in.epoch) ? SigmaRecord::kReplay : SigmaRecord::kRecord;
         }
         c.sigma = d.sigma == SigmaRecord::kWalk ? 0 : (d.sigma == SigmaRecord::kReplay ? 2 : 1);
+        // (a record allocated anew gets its dose record with it; one that stands has it or not)
+        d.dose = d.sigma != SigmaRecord::kWalk && !in.noDoseReplay && !doseFailed &&
+                 (d.sigma == SigmaRecord::kAllocateThenRecord || doseSteps == sigmaSteps);
+        c.dose = d.dose ? c.sigma : 0;
         return d;
     }
     // The compute is launched as decided. (kAllocateThenRecord: the caller allocates next, and reports a failure.)
     void launched(const LaunchDecision& d) {
         flight = d.flight;
         if (!d.flight.reuse) trace.launch(d.flight.epoch, !d.capturing);
-        if (d.sigma == SigmaRecord::kAllocateThenRecord) sigmaSteps = d.need;
+        if (d.sigma == SigmaRecord::kAllocateThenRecord) { sigmaSteps = d.need; doseSteps = d.dose ? d.need : 0; }
         if (d.sigma == SigmaRecord::kAllocateThenRecord || d.sigma == SigmaRecord::kRecord) sigma.launch(d.flight.epoch);
     }
     // The allocation asked for failed: no error, the compute in flight and every later one walk the recurrence.
-    void sigmaAllocationFailed() { sigmaSteps = 0; sigmaFailed = true; sigma.drop(); flight.sigma = 0; }
+    void sigmaAllocationFailed() { sigmaSteps = 0; sigmaFailed = true; sigma.drop(); flight.sigma = 0; doseSteps = 0; flight.dose = 0; }
+    // The dose record's allocation alone failed: no error, the sigma record stands, the dose role of this and every later compute walks.
+    void doseAllocationFailed() { doseSteps = 0; doseFailed = true; flight.dose = 0; }
     void planInsideSweep(bool inSweep) { flight.planInSweep = inSweep; }
     // The sweep's second launch (batch radius beyond maxR) can be left out of the compute in flight.
     bool radiusWithin(int maxR) const { return hints.radiusWithin(flight.epoch, maxR); }

@@ -25,7 +25,7 @@ constexpr int kMaxLayers = 256;
 constexpr int kMaxSteps = 4096;
 constexpr int kNoRadius = 0xFF;
 
-enum FieldError : int { kErrRadiusOverflow = 1, kErrPackOverflow = 2 };
+enum FieldError : int { kErrRadiusOverflow = 1, kErrPackOverflow = 2, kErrRecordExtent = 4 };   // (kErrRecordExtent: k_fill_dr, a layer's steps are not all in the records)
 
 struct LutView {
     const float* density; int nDensity;
