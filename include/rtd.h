@@ -1259,6 +1259,86 @@ int rtd_optimizer_let_dose(rtd_handle h, rtd_optimizer opt, const float** dev);
 int rtd_optimizer_let_values(rtd_handle h, rtd_optimizer opt, double values[3]);
 
 /*
+ * ---- Variable-RBE dose: LQ models on dose and LETd, resident in the optimiser ----
+ *
+ * Additive to the blocks above (RTD_ABI_VERSION stays 3). Proton plans are prescribed in RBE-weighted dose. For every LQ model whose
+ * RBEmax and RBEmin are lines in LETd (McNamara, Wedenberg, Carabe, the constant 1.1) the biological effect is a quadratic in two
+ * volumes that exist on the device: d = sum_f Dij_f w_f, the dose, and n = sum_f N_f w_f, the LET-weighted dose of the block above
+ * (n = LETd * d). The interface knows no model names. A tissue class carries the photon parameters alpha_x (1/Gy) and beta_x (1/Gy^2)
+ * and the two lines RBEmax = rbe_max[0] + rbe_max[1] * LETd, RBEmin = rbe_min[0] + rbe_min[1] * LETd; with alpha = alpha_x * RBEmax
+ * and sqrt(beta) = sqrt(beta_x) * RBEmin:
+ *
+ *     A = a0*d + a1*n          a0 = alpha_x*rbe_max[0]        a1 = alpha_x*rbe_max[1]
+ *     B = b0*d + b1*n          b0 = sqrt(beta_x)*rbe_min[0]   b1 = sqrt(beta_x)*rbe_min[1]
+ *     e = A + B*B                                   (biological effect)
+ *     s = sqrt(alpha_x*alpha_x + (4*beta_x)*e)
+ *     R = (2*e) / (s + alpha_x)                     (RBE-weighted dose; this form does not cancel at small e)
+ *     k = 1 / s                                     (dR/de)
+ *     fd = k * (a0 + (2*B)*b0)                      (dR/dd)
+ *     fn = k * (a1 + (2*B)*b1)                      (dR/dn)
+ *
+ * The host forms a0 .. b1 in float64 from the float fields of the tissue (sqrt(beta_x) in float64) and rounds each once to float32.
+ * Everything per voxel is float32 in exactly the order written, nothing contracted; the division and the square root are the correctly
+ * rounded ones. A voxel whose e is not >= 0 (a negative or NaN input) gives R = 0, fd = 0, fn = 0. e == 0 takes the formulas (R = 0,
+ * k = 1/alpha_x): a voxel that starts without dose still has a gradient. Backward: g_d[v] = g_R[v] * fd, g_n[v] = g_R[v] * fn.
+ * tests/rbe_reference.py restates all of it in numpy; raytracedicom_amd/rbe.py has the four named models.
+ *
+ * rtd_rbe_create           an object on a dose grid: one uint8 class per voxel (class 0, default_tissue, everywhere) and a table of at
+ *                          most 256 x 6 floats; no per-voxel coefficient volumes. Synchronous.
+ * rtd_rbe_add_tissue       one more class; class_id receives 1 .. 255. Synchronous.
+ * rtd_rbe_assign_voxels    the class of a list of linear voxel indices ((z ny + y) nx + x, any order). Synchronous.
+ * rtd_rbe_assign_roi       the class of an ROI's voxels, from its resident list (no copy to the host): one launch on the handle's stream.
+ *                          A later assignment overwrites an earlier one: that is the priority rule for overlapping structures.
+ * rtd_rbe_classes_device   the device pointer of the class volume (owned by the object).
+ * rtd_rbe_dose             WRITES R of the voxels of box (inclusive min[3], max[3], as dose_box_min / dose_box_max; NULL: the grid)
+ *                          into dev_rbe_dose; voxels outside the box are not touched. dev_rbe_dose may be dev_dose or dev_let_dose.
+ * rtd_rbe_backward         WRITES g_d and g_n of the voxels of box. dev_g_dose and dev_g_let must be two volumes; either may be any of
+ *                          the three inputs (a voxel's outputs depend on that voxel only, and it is read before it is written).
+ *                          Both: one launch on the handle's stream, no allocation, no synchronisation.
+ *                          The RBE factor R / d needs no call of its own: rtd_let_average(R, d, floor) is the same division.
+ * rtd_rbe_destroy          waits for the stream and frees the object. It must outlive its use by an optimiser.
+ * rtd_optimizer_set_rbe    a plain optimiser then evaluates its objective on R instead of d. Allocated in this call, never in
+ *                          rtd_optimizer_run: the n volume, the R volume, the g_R volume, the g_n volume and a second gradient vector;
+ *                          the union of the fields' matrix row boxes is computed once, and everything outside it stays at the zero it
+ *                          was allocated with. An iteration: d = sum_f Dij_f w_f and n = sum_f N_f w_f as in the block above;
+ *                          rtd_rbe_dose on the box; the objective on R, which gives g_R; rtd_rbe_backward on the box into g_d and g_n;
+ *                          Dij^T g_d and N^T g_n; grad = float32(a + b) per entry in that order; everything after that is unchanged.
+ *                          rtd_optimizer_run stays launches-only and capturable, and refuses (RTD_ERR_NOT_READY, before its first
+ *                          launch) when a field's LET values are not those of its matrix and the handle's table. RTD_ERR_NOT_READY
+ *                          unless every field has its LET matrix; RTD_ERR_INVALID_ARG for a robust or voxel-wise optimiser, for an
+ *                          object on other dims, and when the optimiser has a LET objective (rtd_optimizer_set_let_objective likewise
+ *                          refuses an optimiser that has an RBE model: one or the other). NULL removes it (synchronous): the
+ *                          optimiser's bits are then those of one that never had one. rtd_optimizer_dose keeps returning d.
+ * rtd_optimizer_rbe_dose   the R volume of the last iteration (owned by the optimiser); RTD_ERR_NOT_READY without a model.
+ *
+ * RTD_ERR_INVALID_ARG: a null pointer; a zero dimension or more than 2^31 - 1 voxels; alpha_x or beta_x not finite or not > 0; a
+ * non-finite line coefficient; non-zero reserved words; an unknown class; a voxel index outside the grid; an ROI on other dims; a box
+ * outside the grid or with min > max; a 257th class. After a refusal nothing has been written and every object stays usable.
+ *
+ * Out of scope: RBE in the robust and voxel-wise optimisers; RBE together with a LET objective; the rtd_plan_* path, nuclear_corr and
+ * remote fields (refused as the matrix itself refuses them); per-voxel alpha_x / beta_x maps; models that are not linear in LETd; a
+ * command-line flag.
+ */
+typedef struct rtd_rbe_tissue {
+    float alpha_x, beta_x;    /* photon LQ parameters, 1/Gy and 1/Gy^2 */
+    float rbe_max[2];         /* RBEmax = rbe_max[0] + rbe_max[1] * LETd (LETd in keV/um) */
+    float rbe_min[2];         /* RBEmin = rbe_min[0] + rbe_min[1] * LETd */
+    uint32_t reserved[2];     /* zero */
+} rtd_rbe_tissue;             /* 32 bytes */
+typedef struct rtd_rbe_s* rtd_rbe;
+int rtd_rbe_create(rtd_handle h, const uint32_t dose_dims[3], const rtd_rbe_tissue* default_tissue, rtd_rbe* out);
+int rtd_rbe_add_tissue(rtd_handle h, rtd_rbe rbe, const rtd_rbe_tissue* tissue, int32_t* class_id);
+int rtd_rbe_assign_voxels(rtd_handle h, rtd_rbe rbe, const int32_t* host_voxels, size_t n, int32_t class_id);
+int rtd_rbe_assign_roi(rtd_handle h, rtd_rbe rbe, rtd_roi roi, int32_t class_id);
+int rtd_rbe_classes_device(rtd_handle h, rtd_rbe rbe, const uint8_t** dev_classes);
+int rtd_rbe_dose(rtd_handle h, rtd_rbe rbe, const float* dev_dose, const float* dev_let_dose, const int32_t box[6], float* dev_rbe_dose);
+int rtd_rbe_backward(rtd_handle h, rtd_rbe rbe, const float* dev_dose, const float* dev_let_dose, const float* dev_g_rbe, const int32_t box[6],
+                     float* dev_g_dose, float* dev_g_let);
+int rtd_rbe_destroy(rtd_handle h, rtd_rbe rbe);
+int rtd_optimizer_set_rbe(rtd_handle h, rtd_optimizer opt, rtd_rbe rbe);
+int rtd_optimizer_rbe_dose(rtd_handle h, rtd_optimizer opt, const float** dev);
+
+/*
  * ---- Multi-GPU plans behind the boundary (SURVEY.md 8(b) "Threading": one handle and one host thread per device) ----
  *
  * rtd_plan is the reference-shaped call on several GPUs of one process: the 4-beam cudaWrapperProtons of the C++ shim uses

@@ -235,6 +235,16 @@ def default_resample_options():
     return o
 
 
+class RtdRbeTissue(C.Structure):
+    """rtd_rbe_tissue: photon alpha_x (1/Gy), beta_x (1/Gy^2) and the lines RBEmax / RBEmin = c[0] + c[1] * LETd (32 bytes)."""
+    _fields_ = [("alpha_x", C.c_float), ("beta_x", C.c_float), ("rbe_max", C.c_float * 2), ("rbe_min", C.c_float * 2),
+                ("reserved", C.c_uint32 * 2)]
+
+
+# rtd_rbe_add_tissue: classes 0 (the default tissue) .. 255
+RTD_RBE_MAX_CLASSES = 256
+
+
 def default_optimizer_options():
     """rtd_default_optimizer_options: the step bounds only keep the Barzilai-Borwein step finite."""
     o = RtdOptimizerOptions()

@@ -50,6 +50,7 @@
 #include "rtd_gamma.hpp"
 #include "rtd_resample.hpp"
 #include "rtd_let.hpp"
+#include "rtd_rbe.hpp"
 #include "rtd_field_memory.hpp"
 #include "rtd_engine_impl.hpp"
 
@@ -1432,3 +1433,4 @@ int rtd_compute(rtd_handle hh, const rtd_beam* beams, int n_beams, float* dose_i
 #include "rtd_gamma_host.hpp"
 #include "rtd_resample_host.hpp"
 #include "rtd_let_host.hpp"
+#include "rtd_rbe_host.hpp"

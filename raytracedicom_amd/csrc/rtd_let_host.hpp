@@ -163,9 +163,11 @@ int rtd_optimizer_set_let_objective(rtd_handle hh, rtd_optimizer pp, rtd_objecti
     if (!o) {                                                         // removes it (the stream may still read the volumes)
         RTD_HIP(h, hipStreamSynchronize(h->stream));
         p->letObj = nullptr;
-        p->dLetDose.reset(); p->dLetG.reset(); p->dLetGrad.reset(); p->dLetValues.reset();
+        if (!p->rbe) { p->dLetDose.reset(); p->dLetG.reset(); p->dLetGrad.reset(); }   // (an RBE model uses the three: section 23)
+        p->dLetValues.reset();
         return RTD_OK;
     }
+    if (p->rbe) return fail(h, RTD_ERR_INVALID_ARG, "rtd_optimizer_set_let_objective: the optimiser has an RBE model (one or the other)");
     if (p->robust) return fail(h, RTD_ERR_INVALID_ARG, "rtd_optimizer_set_let_objective: not available for a robust or voxel-wise optimiser");
     for (int a = 0; a < 3; ++a)
         if (o->dims[a] != p->obj->dims[a]) return fail(h, RTD_ERR_INVALID_ARG, "rtd_optimizer_set_let_objective: the LET objective must be on the optimiser's dose grid");

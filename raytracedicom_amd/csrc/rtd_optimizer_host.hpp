@@ -34,6 +34,12 @@ struct rtd_optimizer_impl {
     rtd_objective_impl* letObj = nullptr;
     DevBuf<float> dLetDose, dLetG, dLetGrad;
     DevBuf<double> dLetValues;
+    // The RBE model of a plain optimiser (section 23; rtd_optimizer_set_rbe in rtd_rbe_host.hpp allocates all of it): the objective is
+    // evaluated on R(dDose, dLetDose) instead of dDose. It shares dLetDose, dLetG and dLetGrad with the LET objective (one or the other)
+    // and adds R and g_R; rbeBox is the union of the fields' row boxes (bw == 0: no field has a row).
+    struct rtd_rbe_impl* rbe = nullptr;
+    DijBox rbeBox{0, 0, 0, 0, 0, 0};
+    DevBuf<float> dRbeDose, dRbeG;
     rtd_field_impl* sf(int s, size_t i) const { return sfields[(size_t)s * fields.size() + i]; }
     float* w() const { return dVec; }
     float* wPrev() const { return dVec + n; }
@@ -79,6 +85,9 @@ int letAdjoint(rtd_handle hh, rtd_optimizer_impl* p) {
     }
     return RTD_OK;
 }
+// R of the two volumes on rbeBox, and g_R back to dG and dLetG (rtd_rbe_host.hpp, included later).
+int rbeOptForward(rtd_handle_impl* h, rtd_optimizer_impl* p);
+int rbeOptBackward(rtd_handle_impl* h, rtd_optimizer_impl* p);
 int scenarioAdjoint(rtd_handle hh, rtd_optimizer_impl* p, int s, float* out) {   // out[offset[i] ..] = Dij_(s, i)^T g_s
     for (size_t i = 0; i < p->fields.size(); ++i) {
         const int st = rtd_field_dose_influence_apply_t(hh, reinterpret_cast<rtd_field>(p->sf(s, i)), p->gS[s], out + p->offset[i]);
@@ -358,7 +367,7 @@ int rtd_optimizer_run(rtd_handle hh, rtd_optimizer pp, uint32_t n_iterations) {
     if (!h) return RTD_ERR_INVALID_ARG;
     if (!p) return fail(h, RTD_ERR_INVALID_ARG, "rtd_optimizer_run: null pointer");
     if (p->obj->terms.empty()) return fail(h, RTD_ERR_INVALID_ARG, "rtd_optimizer_run: the objective has no terms");
-    if (p->letObj)                                                    // (in front of the first launch: a refused run launches nothing)
+    if (p->letObj || p->rbe)                                          // (in front of the first launch: a refused run launches nothing)
         for (const rtd_field_impl* f : p->fields)
             if (!(f->dijDone && f->letDone && h->dLetTable && f->letEpoch == h->letEpoch))
                 return fail(h, RTD_ERR_NOT_READY, "rtd_optimizer_run: a field's LET-weighted matrix is not that of its matrix and the handle's table (call rtd_field_let_influence again)");
@@ -366,7 +375,16 @@ int rtd_optimizer_run(rtd_handle hh, rtd_optimizer pp, uint32_t n_iterations) {
     hipStream_t s = h->stream;
     for (uint32_t k = 0; k < n_iterations; ++k) {
         int st = RTD_OK;
-        if (!p->robust) {
+        if (p->rbe) {                         // section 23: the objective sees R(dose, LET-weighted dose); its gradient goes back through both products
+            st = scenarioForward(hh, h, p, 0);
+            if (st == RTD_OK) st = letForward(hh, h, p);
+            if (st == RTD_OK) st = rbeOptForward(h, p);
+            if (st == RTD_OK) st = evalObjective(h, p->obj, p->dRbeDose, p->dValues, p->dRbeG);
+            if (st == RTD_OK) st = rbeOptBackward(h, p);
+            if (st == RTD_OK) st = scenarioAdjoint(hh, p, 0, p->grad());
+            if (st == RTD_OK) st = letAdjoint(hh, p);
+            if (st == RTD_OK) k_rbe_add<<<(unsigned)std::max((p->n + 255) / 256, 1), 256, 0, s>>>(p->grad(), (const float*)p->dLetGrad, p->n);
+        } else if (!p->robust) {
             st = scenarioForward(hh, h, p, 0);                                            // 1.
             if (st == RTD_OK) st = evalObjective(h, p->obj, p->dDose, p->dValues, p->dG); // 2.
             if (st == RTD_OK) st = scenarioAdjoint(hh, p, 0, p->grad());                  // 3.

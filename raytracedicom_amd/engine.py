@@ -142,6 +142,16 @@ def lib():
         L.rtd_optimizer_set_let_objective.argtypes = [vp, vp, vp]
         L.rtd_optimizer_let_dose.argtypes = [vp, vp, vpp]
         L.rtd_optimizer_let_values.argtypes = [vp, vp, C.POINTER(C.c_double)]
+        L.rtd_rbe_create.argtypes = [vp, u3, C.POINTER(abi.RtdRbeTissue), vpp]
+        L.rtd_rbe_add_tissue.argtypes = [vp, vp, C.POINTER(abi.RtdRbeTissue), C.POINTER(C.c_int32)]
+        L.rtd_rbe_assign_voxels.argtypes = [vp, vp, i3, C.c_size_t, C.c_int32]
+        L.rtd_rbe_assign_roi.argtypes = [vp, vp, vp, C.c_int32]
+        L.rtd_rbe_classes_device.argtypes = [vp, vp, vpp]
+        L.rtd_rbe_dose.argtypes = [vp, vp, vp, vp, i3, vp]
+        L.rtd_rbe_backward.argtypes = [vp, vp, vp, vp, vp, i3, vp, vp]
+        L.rtd_rbe_destroy.argtypes = [vp, vp]
+        L.rtd_optimizer_set_rbe.argtypes = [vp, vp, vp]
+        L.rtd_optimizer_rbe_dose.argtypes = [vp, vp, vpp]
         L.rtd_host_register.argtypes = [vp, C.c_size_t]
         L.rtd_host_unregister.argtypes = [vp]
         L.rtd_plan_create.argtypes = [C.POINTER(C.c_int), C.c_int, vpp]
@@ -700,6 +710,70 @@ class Roi:
             self._h = C.c_void_p()
 
 
+class Rbe:
+    """rtd_rbe_*: a variable-RBE model on a dose grid (Engine.create_rbe): one tissue class per voxel, class 0 (the default tissue)
+    everywhere until assign() says otherwise. Tissues are abi.RtdRbeTissue records; raytracedicom_amd.rbe.tissue makes the named ones."""
+
+    def __init__(self, eng, dims, tissue):
+        self.eng = eng
+        self._h = C.c_void_p()
+        self.dims = tuple(int(d) for d in dims)
+        self.n_voxels = self.dims[0] * self.dims[1] * self.dims[2]
+        eng._check(lib().rtd_rbe_create(eng._h, abi.uint3(self.dims), C.byref(tissue), C.byref(self._h)))
+
+    def add_tissue(self, tissue):
+        """rtd_rbe_add_tissue -> the new class (1 .. 255)."""
+        c = C.c_int32(-1)
+        self.eng._check(lib().rtd_rbe_add_tissue(self.eng._h, self._h, C.byref(tissue), C.byref(c)))
+        return int(c.value)
+
+    def assign(self, where, class_id):
+        """The class of a set of voxels: a Roi (its resident list, no copy to the host), a bool mask of the grid's size or an array of
+        linear voxel indices. A later assignment overwrites an earlier one."""
+        if isinstance(where, Roi):
+            self.eng._check(lib().rtd_rbe_assign_roi(self.eng._h, self._h, where._h, int(class_id)))
+            return
+        a = np.asarray(where)
+        idx = np.flatnonzero(a) if a.dtype == np.bool_ else a.reshape(-1)
+        idx = np.ascontiguousarray(idx, dtype=np.int32)
+        self.eng._check(lib().rtd_rbe_assign_voxels(self.eng._h, self._h, idx.ctypes.data_as(C.POINTER(C.c_int32)), idx.size, int(class_id)))
+
+    @staticmethod
+    def _box(box):
+        if box is None:
+            return None
+        lo, hi = box
+        return (C.c_int32 * 6)(*[int(v) for v in lo], *[int(v) for v in hi])
+
+    def dose(self, dev_dose, dev_let_dose, dev_out, box=None):
+        """rtd_rbe_dose: WRITES the RBE-weighted dose of the voxels of box ((min[3], max[3]) inclusive; None: the grid) into dev_out
+        (device pointers; dev_out may be one of the inputs). One launch on the engine's stream."""
+        self.eng._check(lib().rtd_rbe_dose(self.eng._h, self._h, C.c_void_p(int(dev_dose)), C.c_void_p(int(dev_let_dose)), self._box(box),
+                                           C.c_void_p(int(dev_out))))
+
+    def backward(self, dev_dose, dev_let_dose, dev_g_rbe, dev_g_dose, dev_g_let, box=None):
+        """rtd_rbe_backward: WRITES g_d = g_R * dR/dd and g_n = g_R * dR/dn of the voxels of box into two volumes."""
+        self.eng._check(lib().rtd_rbe_backward(self.eng._h, self._h, C.c_void_p(int(dev_dose)), C.c_void_p(int(dev_let_dose)), C.c_void_p(int(dev_g_rbe)),
+                                               self._box(box), C.c_void_p(int(dev_g_dose)), C.c_void_p(int(dev_g_let))))
+
+    def classes_device(self):
+        """Device pointer of the uint8 class volume (owned by the object)."""
+        p = C.c_void_p()
+        self.eng._check(lib().rtd_rbe_classes_device(self.eng._h, self._h, C.byref(p)))
+        return int(p.value or 0)
+
+    def classes(self):
+        """Waits; the class volume as a flat numpy uint8 array."""
+        out = np.empty(self.n_voxels, dtype=np.uint8)
+        self.eng.to_host(out, self.classes_device())
+        return out
+
+    def destroy(self):
+        if self._h:
+            lib().rtd_rbe_destroy(self.eng._h, self._h)
+            self._h = C.c_void_p()
+
+
 class Optimizer:
     """rtd_optimizer_*: the resident spectral projected gradient iteration on an Objective of the dose of `fields` (each with a
     dose_influence() matrix). Destroy it before its fields, its objective and its engine."""
@@ -795,6 +869,20 @@ class Optimizer:
         v = np.zeros(3, dtype=np.float64)
         self.eng._check(lib().rtd_optimizer_let_values(self.eng._h, self._h, v.ctypes.data_as(C.POINTER(C.c_double))))
         return v
+
+    def set_rbe(self, rbe):
+        """rtd_optimizer_set_rbe: the objective is then evaluated on the RBE-weighted dose R(dose, LET-weighted dose) of an Rbe object
+        (every field needs let_influence() first; not together with a LET objective); None removes it. Everything it needs is
+        allocated here, never in run(). The Rbe must outlive its use."""
+        self.eng._check(lib().rtd_optimizer_set_rbe(self.eng._h, self._h, rbe._h if rbe is not None else None))
+        self.rbe = rbe
+
+    def rbe_dose(self):
+        """Device pointer of the optimiser's RBE-weighted dose volume (of the iterate that entered the last iteration); dose() stays
+        the physical dose."""
+        p = C.c_void_p()
+        self.eng._check(lib().rtd_optimizer_rbe_dose(self.eng._h, self._h, C.byref(p)))
+        return int(p.value or 0)
 
     def scenario_values(self):
         """Waits; (values float64[S], lambdas float64[S], worst): every scenario's objective, its share of the combined gradient and
@@ -954,6 +1042,11 @@ class Engine:
         out = C.c_void_p()
         self._check(lib().rtd_roi_from_mask(self._h, abi.uint3(dims), C.c_void_p(ptr), C.byref(out)))
         return Roi._adopt(self, dims, out)
+
+    def create_rbe(self, dims, tissue):
+        """rtd_rbe_create: a variable-RBE model on the dose grid dims (x, y, z) with `tissue` (an abi.RtdRbeTissue, e.g. from
+        raytracedicom_amd.rbe.tissue) everywhere. Returns an Rbe."""
+        return Rbe(self, dims, tissue)
 
     def create_optimizer(self, fields, objective, options=None):
         return Optimizer(self, fields, objective, options)
