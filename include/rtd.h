@@ -1186,6 +1186,85 @@ int rtd_dose_quantize(rtd_handle h, const float* dev_dose, size_t n_voxels, int 
                       void* dev_out /* uint16 or uint32 [n_voxels] */, uint64_t* n_clamped /* host, may be NULL */);
 
 /*
+ * ---- Deformable dose warping: a dose through a displacement field, and the transposed operation ----
+ *
+ * Additive to the blocks above (RTD_ABI_VERSION stays 3; rtd_dose_resample and rtd_resample_options are untouched). A dose computed on
+ * one anatomy — a breathing phase, the CT of the day, a previous course — is pulled onto a reference anatomy through a deformation
+ * vector field (DVF): for every voxel of the destination (reference) grid the field gives the displacement that leads to the matching
+ * place of the source anatomy. rtd_dose_warp is rtd_dose_resample with that displacement added to the position; rtd_dose_warp_t is its
+ * transpose, which pushes a voxel gradient on the reference grid back to the source grid (where Dij^T lives). All volumes are x
+ * fastest, dims are (x, y, z), everything lives on the handle's device. Every operation is float32 in the stated order, each product,
+ * sum and difference rounded, nothing contracted (tests/warp_reference.py restates both rules in numpy).
+ *
+ * rtd_warp: dst_idx_to_src_idx as rtd_dose_resample takes it; dst_idx_to_dvf_idx, destination voxel index -> node index of the field's
+ * grid; disp_to_src_idx = k, row-major 3 x 3, displacement vector (for instance mm) -> source-index units; dev_dvf, component-major:
+ * three volumes of dvf_dims voxels, component 0, then 1, then 2; reserved words zero. raytracedicom_amd.grids.warp_maps makes the three
+ * maps from the index-to-world transforms of the three grids.
+ *
+ * Forward, rtd_dose_warp(h, dev_src, src_dims, warp, dev_dst, dst_dims, opt), opt as for rtd_dose_resample (src_type, scale, src_scale,
+ * accumulate mean what they mean there). For destination voxel (x, y, z):
+ * Field position. q_a = the Position formula of rtd_dose_resample with (m, v) = dst_idx_to_dvf_idx, a = 0, 1, 2. If a q_a is a NaN the
+ *     voxel is outside. Otherwise, with (n_0, n_1, n_2) = dvf_dims: qc_a = fminf(fmaxf(q_a, 0), float(n_a - 1)) — the field is held
+ *     constant beyond its grid —, i0_a = (int)floorf(qc_a), i1_a = min(i0_a + 1, n_a - 1), t_a = qc_a - floorf(qc_a). A dimension of 1
+ *     is legal.
+ * Displacement. For each component c, u_c = the trilinear blend of the 8 field nodes (i0 | i1 per axis) of volume c, each blend
+ *     a + t * (b - a), along x, then y, then z.
+ * Position. s_a = (k[3a] * u_0 + k[3a + 1] * u_1) + k[3a + 2] * u_2;  p_a = P_a + s_a, where P_a is rtd_dose_resample's p_a for
+ *     dst_idx_to_src_idx.
+ * From here on rtd_dose_resample's rule holds word for word: Outside, Nodes, Blend, Output. A displacement that is not finite makes
+ *     p_a a NaN (or infinite): the voxel is outside.
+ * With an all-zero field the result is bit for bit that of rtd_dose_resample with the same map (a position of -0.0 becomes +0.0, which
+ * changes no result). The call is asynchronous on the handle's stream and launches only (no allocation, no copy, no host
+ * synchronisation; it can be captured, and a captured call is not timed). rtd_dose_warp_kernel_ms: the time of the kernel of the
+ * handle's last rtd_dose_warp, as rtd_dose_resample_kernel_ms. RTD_ERR_INVALID_ARG, after which nothing has been written: everything
+ * rtd_dose_resample refuses (the dimensions of the field count as a third grid), a null warp or dev_dvf, an entry of k or of either
+ * affine that is not finite, a non-zero reserved word of the record.
+ *
+ * Transpose, rtd_dose_warp_t(h, dev_g_dst, dst_dims, warp, dev_g_src, src_dims, scale, accumulate, dev_workspace, workspace_bytes):
+ * float32 only. g_src = scale * W^T g_dst, where W is the forward operator of a float32 source at scale 1. A scatter: float sums
+ * would depend on the order in which the atomics arrive, so the sums are 64-bit integers of a quantum, which are associative.
+ * Per destination voxel. sg = scale * g_dst[voxel]; an sg that is not finite counts as zero everywhere below.
+ * Maximum. M = max |sg| over the destination (on the device: an integer atomicMax on the bit pattern). M == 0: the result is +0.0f in
+ *     every source voxel, or dev_g_src is left as it is when accumulate is set. Otherwise M = m * 2^E with m in [0.5, 1), and the
+ *     quantum is 2^(E - 30).
+ * Contribution. For a voxel the forward rule calls inside, with f_a, t_a of Nodes: w0_a = 1.0f - t_a, w1_a = t_a; its contribution to
+ *     node (dx, dy, dz) is c = ((sg * wx) * wy) * wz. A node outside [0, n_a - 1] receives nothing.
+ * Accumulation. S_j += llrint(double(c) * 2^(30 - E)), ties to even, into one int64 per source voxel (64-bit integer atomics on the
+ *     workspace). The scaling by a power of two is exact; |c| <= M < 2^E bounds every term by 2^30 and there are fewer than 2^31
+ *     terms, so no sum overflows; each contribution is off by at most half a quantum, which is at most M * 2^-30.
+ * Finish. out_j = float(double(S_j) * 2^(E - 30));  g_src[j] = out_j, or g_src[j] + out_j when accumulate is set — for every source
+ *     voxel j.
+ * rtd_dose_warp_t_workspace_bytes(src_dims, &bytes): 64 bytes of header plus one int64 per source voxel. The caller owns the workspace
+ * (8-byte aligned, its content on entry is irrelevant), so the call allocates nothing and can be captured: a memset of the workspace,
+ * then the maximum, scatter and finish kernels on the handle's stream. rtd_dose_warp_t_kernel_ms: the times of those four launches of
+ * the last call that was not captured. RTD_ERR_INVALID_ARG, after which nothing has been written: as for rtd_dose_warp, a scale that
+ * is not finite, accumulate > 1, a null or misaligned workspace, workspace_bytes below the size above.
+ *
+ * Kernels (rtd_warp.hpp): forward and scatter are one lane per destination voxel, lanes along x, the block of rtd_dose_resample. The
+ * scatter merges within a block before its atomics go out: a block takes 64 x 4 x 4 destination voxels, whose contributions under
+ * the near-identity maps of real registrations fall into a box of source nodes little larger than that; it sums them in an LDS tile
+ * of 72 x 7 x 8 int64 and sends one global atomic per tile node that is not zero (a voxel whose nodes leave the tile sends its own).
+ * The integers are summed exactly either way: the bits do not depend on it (RTD_WARP_T_PLAIN in the environment when the handle is
+ * created selects the scatter with eight global atomics per voxel, for measurements).
+ */
+typedef struct rtd_warp {
+    rtd_affine   dst_idx_to_src_idx;   /* offset   0 */
+    rtd_affine   dst_idx_to_dvf_idx;   /* offset  48 */
+    float        disp_to_src_idx[9];   /* offset  96: k, row-major */
+    uint32_t     reserved0;            /* offset 132: zero */
+    const float* dev_dvf;              /* offset 136: [3][dvf_dims z][y][x] on the device */
+    uint32_t     dvf_dims[3];          /* offset 144: (x, y, z) */
+    uint32_t     reserved[5];          /* offset 156: zero */
+} rtd_warp;    /* 176 bytes */
+int rtd_dose_warp(rtd_handle h, const void* dev_src, const uint32_t src_dims[3], const rtd_warp* warp, float* dev_dst,
+                  const uint32_t dst_dims[3], const rtd_resample_options* opt);
+int rtd_dose_warp_kernel_ms(rtd_handle h, float* ms);
+int rtd_dose_warp_t_workspace_bytes(const uint32_t src_dims[3], size_t* bytes);
+int rtd_dose_warp_t(rtd_handle h, const float* dev_g_dst, const uint32_t dst_dims[3], const rtd_warp* warp, float* dev_g_src,
+                    const uint32_t src_dims[3], float scale, uint32_t accumulate, void* dev_workspace, size_t workspace_bytes);
+int rtd_dose_warp_t_kernel_ms(rtd_handle h, float ms[4] /* memset, maximum, scatter, finish */);
+
+/*
  * ---- Dose-averaged LET: the LET-weighted influence matrix, LETd, a LET objective ----
  *
  * Additive to the blocks above (RTD_ABI_VERSION stays 3). The convention is the analytical one: the LET of spot j at voxel v is the

@@ -235,6 +235,28 @@ def default_resample_options():
     return o
 
 
+class RtdWarp(C.Structure):
+    """rtd_warp: the two index maps, k (displacement -> source-index units) and the field on the device (176 bytes)."""
+    _fields_ = [("dst_idx_to_src_idx", RtdAffine), ("dst_idx_to_dvf_idx", RtdAffine), ("disp_to_src_idx", C.c_float * 9),
+                ("reserved0", C.c_uint32), ("dev_dvf", C.c_void_p), ("dvf_dims", C.c_uint32 * 3), ("reserved", C.c_uint32 * 5)]
+
+
+def make_warp(dst_idx_to_src_idx, dst_idx_to_dvf_idx, disp_to_src_idx, dev_dvf, dvf_dims):
+    """rtd_warp from the pieces grids.warp_maps returns (each affine an RtdAffine or an (m, v) pair, k 3x3), the device pointer of
+    the field [3][Z][Y][X] and its dims (x, y, z)."""
+    w = RtdWarp()
+    for name, a in (("dst_idx_to_src_idx", dst_idx_to_src_idx), ("dst_idx_to_dvf_idx", dst_idx_to_dvf_idx)):
+        a = a if isinstance(a, RtdAffine) else make_affine(*a)
+        C.memmove(C.byref(w, getattr(RtdWarp, name).offset), C.byref(a), C.sizeof(RtdAffine))
+    k = np.asarray(disp_to_src_idx, dtype=np.float32).reshape(9)
+    for i in range(9):
+        w.disp_to_src_idx[i] = float(k[i])
+    w.dev_dvf = int(dev_dvf) if dev_dvf else None
+    for i in range(3):
+        w.dvf_dims[i] = int(dvf_dims[i])
+    return w
+
+
 class RtdRbeTissue(C.Structure):
     """rtd_rbe_tissue: photon alpha_x (1/Gy), beta_x (1/Gy^2) and the lines RBEmax / RBEmin = c[0] + c[1] * LETd (32 bytes)."""
     _fields_ = [("alpha_x", C.c_float), ("beta_x", C.c_float), ("rbe_max", C.c_float * 2), ("rbe_min", C.c_float * 2),

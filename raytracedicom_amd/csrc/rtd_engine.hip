@@ -49,6 +49,7 @@
 #include "rtd_target.hpp"
 #include "rtd_gamma.hpp"
 #include "rtd_resample.hpp"
+#include "rtd_warp.hpp"
 #include "rtd_let.hpp"
 #include "rtd_rbe.hpp"
 #include "rtd_field_memory.hpp"
@@ -156,6 +157,7 @@ int rtd_create(int device_id, rtd_handle* out) {
     h->stream = h->ownStream;
     h->gammaNaive = std::getenv("RTD_GAMMA_NAIVE") != nullptr;
     h->roiMarginNaive = std::getenv("RTD_ROI_MARGIN_NAIVE") != nullptr;
+    h->warpTPlain = std::getenv("RTD_WARP_T_PLAIN") != nullptr;
     if (hipDeviceGetAttribute(&h->numCUs, hipDeviceAttributeMultiprocessorCount, device_id) != hipSuccess || h->numCUs <= 0) h->numCUs = 256;
     *out = reinterpret_cast<rtd_handle>(h);
     return RTD_OK;
@@ -170,6 +172,8 @@ int rtd_destroy(rtd_handle hh) {
     h->clearCtBoxes();
     for (hipEvent_t e : h->gammaEv) if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : h->resampleEv) if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : h->warpEv) if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : h->warpTEv) if (e) (void)hipEventDestroy(e);
     if (h->dQuantScratch) (void)hipFree(h->dQuantScratch);
     if (h->dLetTable) (void)hipFree(h->dLetTable);
     if (h->dLutBlock) (void)hipFree(h->dLutBlock);
@@ -1432,5 +1436,6 @@ int rtd_compute(rtd_handle hh, const rtd_beam* beams, int n_beams, float* dose_i
 #include "rtd_target_host.hpp"
 #include "rtd_gamma_host.hpp"
 #include "rtd_resample_host.hpp"
+#include "rtd_warp_host.hpp"
 #include "rtd_let_host.hpp"
 #include "rtd_rbe_host.hpp"

@@ -44,6 +44,12 @@ struct rtd_handle_impl {
     hipEvent_t resampleEv[2] = {};                 // around the kernel of the last rtd_dose_resample that was not captured
     bool resampleTimed = false;
     void* dQuantScratch = nullptr;                 // 16 bytes: the bits of the largest dose, the count of clamped voxels (first rtd_dose_quantize)
+    // rtd_dose_warp, rtd_dose_warp_t (rtd_warp_host.hpp)
+    hipEvent_t warpEv[2] = {};                     // around the kernel of the last rtd_dose_warp that was not captured
+    bool warpTimed = false;
+    hipEvent_t warpTEv[5] = {};                    // before, between and behind the four launches of the last rtd_dose_warp_t that was not captured
+    bool warpTTimed = false;
+    bool warpTPlain = false;                       // RTD_WARP_T_PLAIN in the environment when the handle was made: the scatter without the LDS tile
     // rtd_set_let_table (rtd_let_host.hpp): an allocation of its own, [letEnergies][letSamples]; not an input of the dose (no epoch of
     // the above moves with it). letEpoch counts the tables set: a field's LET values belong to the table they were made from.
     float* dLetTable = nullptr;

@@ -132,6 +132,11 @@ def lib():
         L.rtd_dose_resample.argtypes = [vp, vp, u3, C.POINTER(abi.RtdAffine), vp, u3, C.POINTER(abi.RtdResampleOptions)]
         L.rtd_dose_resample_kernel_ms.argtypes = [vp, C.POINTER(C.c_float)]
         L.rtd_dose_quantize.argtypes = [vp, vp, C.c_size_t, C.c_int, C.POINTER(C.c_double), vp, C.POINTER(C.c_uint64)]
+        L.rtd_dose_warp.argtypes = [vp, vp, u3, C.POINTER(abi.RtdWarp), vp, u3, C.POINTER(abi.RtdResampleOptions)]
+        L.rtd_dose_warp_kernel_ms.argtypes = [vp, C.POINTER(C.c_float)]
+        L.rtd_dose_warp_t_workspace_bytes.argtypes = [u3, C.POINTER(C.c_size_t)]
+        L.rtd_dose_warp_t.argtypes = [vp, vp, u3, C.POINTER(abi.RtdWarp), vp, u3, C.c_float, C.c_uint32, vp, C.c_size_t]
+        L.rtd_dose_warp_t_kernel_ms.argtypes = [vp, C.POINTER(C.c_float)]
         L.rtd_set_let_table.argtypes = [vp, abi.c_float_p, C.c_int32, C.c_int32]
         L.rtd_field_water_depth.argtypes = [vp, vp, vp]
         L.rtd_field_let_influence.argtypes = [vp, vp]
@@ -1196,6 +1201,158 @@ class Engine:
         ms = C.c_float(0)
         self._check(lib().rtd_dose_resample_kernel_ms(self._h, C.byref(ms)))
         return float(ms.value)
+
+    # deformable dose warping (include/rtd.h "Deformable dose warping"). A host-side warp is (maps, dvf): maps the triple of
+    # grids.warp_maps (dst_idx_to_src_idx, dst_idx_to_dvf_idx, k), dvf the field as a host array [3][Z][Y][X] float32.
+    def warp_dose_device(self, src_ptr, src_dims, warp, dst_ptr, dst_dims, *, opt=None, **options):
+        """rtd_dose_warp: the device volume src_ptr (dims (x, y, z); the types of resample_dose_device) pulled through warp (an
+        abi.RtdWarp, abi.make_warp) onto the float32 device volume dst_ptr; asynchronous. options as for resample_dose_device."""
+        if opt is None:
+            opt = abi.RtdResampleOptions()
+            lib().rtd_default_resample_options(C.byref(opt))
+        for k, val in options.items():
+            if k not in ("src_type", "accumulate", "scale", "src_scale"):
+                raise TypeError("warp_dose_device: unknown option %r" % k)
+            setattr(opt, k, int(val) if k in ("src_type", "accumulate") else float(val))
+        self._check(lib().rtd_dose_warp(self._h, C.c_void_p(int(src_ptr)) if src_ptr else None, abi.uint3(src_dims), C.byref(warp) if warp is not None else None,
+                                        C.c_void_p(int(dst_ptr)) if dst_ptr else None, abi.uint3(dst_dims), C.byref(opt)))
+
+    def _upload_dvf(self, dvf):
+        """The host field [3][Z][Y][X] on the device -> (pointer, dims (x, y, z))."""
+        dvf = abi.f32(dvf)
+        assert dvf.ndim == 4 and dvf.shape[0] == 3
+        d = self.device_alloc(dvf.nbytes)
+        try:
+            self.to_device(d, dvf)
+        except Exception:
+            self.device_free(d)
+            raise
+        return d, (dvf.shape[3], dvf.shape[2], dvf.shape[1])
+
+    def warp_dose(self, src, maps, dvf, dst_dims, *, dst=None, **options):
+        """The host volume src ([Z][Y][X]; float32, uint16 or uint32 — the integer ones with src_scale) pulled through the field dvf
+        ([3][Z][Y][X] float32) and the maps of grids.warp_maps onto a grid of dst_dims (x, y, z) -> [Z][Y][X] float32. dst: the volume
+        to accumulate into with accumulate=1 (it is not modified)."""
+        src = np.ascontiguousarray(src)
+        if src.dtype not in self._DOSE_TYPES:
+            src = src.astype(np.float32)
+        assert src.ndim == 3
+        shape = (int(dst_dims[2]), int(dst_dims[1]), int(dst_dims[0]))
+        out = np.zeros(shape, dtype=np.float32) if dst is None else abi.f32(dst).copy()
+        assert out.shape == shape
+        bufs = []
+        try:
+            d_dvf, dvf_dims = self._upload_dvf(dvf)
+            bufs.append(d_dvf)
+            d_src = self.device_alloc(src.nbytes)
+            bufs.append(d_src)
+            d_dst = self.device_alloc(out.nbytes)
+            bufs.append(d_dst)
+            self.to_device(d_src, src)
+            self.to_device(d_dst, out)
+            self.warp_dose_device(d_src, (src.shape[2], src.shape[1], src.shape[0]), abi.make_warp(*maps, d_dvf, dvf_dims), d_dst, dst_dims,
+                                  src_type=self._DOSE_TYPES[src.dtype], **options)
+            self.to_host(out, d_dst)
+            return out
+        finally:
+            self.sync()
+            for p in bufs:
+                self.device_free(p)
+
+    def warp_kernel_ms(self):
+        """rtd_dose_warp_kernel_ms: the kernel of the last warp_dose / warp_dose_device call, in ms (waits for it)."""
+        ms = C.c_float(0)
+        self._check(lib().rtd_dose_warp_kernel_ms(self._h, C.byref(ms)))
+        return float(ms.value)
+
+    @staticmethod
+    def warp_t_workspace_bytes(src_dims):
+        """rtd_dose_warp_t_workspace_bytes: the workspace of warp_dose_t_device for a source grid of src_dims (x, y, z)."""
+        n = C.c_size_t(0)
+        if lib().rtd_dose_warp_t_workspace_bytes(abi.uint3(src_dims), C.byref(n)) != abi.RTD_OK:
+            raise RtdError(abi.RTD_ERR_INVALID_ARG, "warp_t_workspace_bytes: a zero dimension or more than 2^31 - 1 voxels")
+        return int(n.value)
+
+    def warp_dose_t_device(self, g_dst_ptr, dst_dims, warp, g_src_ptr, src_dims, workspace_ptr, workspace_bytes, *, scale=1.0, accumulate=0):
+        """rtd_dose_warp_t: the float32 device gradient g_dst_ptr on the destination grid pushed back through warp onto the float32
+        device volume g_src_ptr on the source grid (written, or added to with accumulate=1); asynchronous. workspace_ptr: device
+        memory of at least warp_t_workspace_bytes(src_dims) bytes, the caller's."""
+        self._check(lib().rtd_dose_warp_t(self._h, C.c_void_p(int(g_dst_ptr)) if g_dst_ptr else None, abi.uint3(dst_dims),
+                                          C.byref(warp) if warp is not None else None, C.c_void_p(int(g_src_ptr)) if g_src_ptr else None,
+                                          abi.uint3(src_dims), float(scale), int(accumulate),
+                                          C.c_void_p(int(workspace_ptr)) if workspace_ptr else None, int(workspace_bytes)))
+
+    def warp_dose_t(self, g, maps, dvf, src_dims, *, scale=1.0, accumulate=0, base=None):
+        """The host gradient g ([Z][Y][X] float32 on the destination grid) pushed back through the field and the maps of
+        grids.warp_maps -> [Z][Y][X] float32 on the source grid of src_dims (x, y, z). base: the volume added to with accumulate=1 (it
+        is not modified). The workspace is allocated here."""
+        g = abi.f32(g)
+        assert g.ndim == 3
+        shape = (int(src_dims[2]), int(src_dims[1]), int(src_dims[0]))
+        out = np.zeros(shape, dtype=np.float32) if base is None else abi.f32(base).copy()
+        assert out.shape == shape
+        bufs = []
+        try:
+            d_dvf, dvf_dims = self._upload_dvf(dvf)
+            bufs.append(d_dvf)
+            d_g = self.device_alloc(g.nbytes)
+            bufs.append(d_g)
+            d_out = self.device_alloc(out.nbytes)
+            bufs.append(d_out)
+            nws = self.warp_t_workspace_bytes(src_dims)
+            d_ws = self.device_alloc(nws)
+            bufs.append(d_ws)
+            self.to_device(d_g, g)
+            self.to_device(d_out, out)
+            self.warp_dose_t_device(d_g, (g.shape[2], g.shape[1], g.shape[0]), abi.make_warp(*maps, d_dvf, dvf_dims), d_out, src_dims, d_ws, nws,
+                                    scale=scale, accumulate=accumulate)
+            self.to_host(out, d_out)
+            return out
+        finally:
+            self.sync()
+            for p in bufs:
+                self.device_free(p)
+
+    def warp_t_kernel_ms(self):
+        """rtd_dose_warp_t_kernel_ms: the four launches of the last warp_dose_t / warp_dose_t_device call -> (memset, maximum,
+        scatter, finish) in ms (waits for them)."""
+        ms = (C.c_float * 4)()
+        self._check(lib().rtd_dose_warp_t_kernel_ms(self._h, ms))
+        return tuple(float(v) for v in ms)
+
+    def accumulate_phases(self, doses, warps, weights, dst_dims):
+        """The doses of several anatomies summed on a reference grid: sum_i weights[i] * warp_i(doses[i]) -> [Z][Y][X] float32 on
+        dst_dims (x, y, z). doses: host volumes as warp_dose takes them; warps: one (maps, dvf) per dose. Phase 0 is written with
+        scale weights[0], every later phase is accumulated with its weight in list order: a fixed sequence of float32 sums."""
+        if not (len(doses) == len(warps) == len(weights)) or not doses:
+            raise RtdError(abi.RTD_ERR_INVALID_ARG, "accumulate_phases: as many doses as warps and weights, and at least one")
+        shape = (int(dst_dims[2]), int(dst_dims[1]), int(dst_dims[0]))
+        out = np.empty(shape, dtype=np.float32)
+        d_dst = self.device_alloc(out.nbytes)
+        try:
+            for i, (dose, (maps, dvf), wgt) in enumerate(zip(doses, warps, weights)):
+                src = np.ascontiguousarray(dose)
+                if src.dtype not in self._DOSE_TYPES:
+                    src = src.astype(np.float32)
+                assert src.ndim == 3
+                bufs = []
+                try:
+                    d_dvf, dvf_dims = self._upload_dvf(dvf)
+                    bufs.append(d_dvf)
+                    d_src = self.device_alloc(src.nbytes)
+                    bufs.append(d_src)
+                    self.to_device(d_src, src)
+                    self.warp_dose_device(d_src, (src.shape[2], src.shape[1], src.shape[0]), abi.make_warp(*maps, d_dvf, dvf_dims), d_dst, dst_dims,
+                                          src_type=self._DOSE_TYPES[src.dtype], scale=wgt, accumulate=1 if i else 0)
+                finally:
+                    self.sync()
+                    for p in bufs:
+                        self.device_free(p)
+            self.to_host(out, d_dst)
+            return out
+        finally:
+            self.sync()
+            self.device_free(d_dst)
 
     def quantize_dose_device(self, dose_ptr, n_voxels, out_ptr, bits=16, scaling=0.0):
         """rtd_dose_quantize on device buffers -> (scaling used, n_clamped); synchronous."""
