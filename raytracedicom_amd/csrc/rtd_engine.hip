@@ -476,6 +476,8 @@ static int createField(rtd_handle hh, const rtd_beam* b, const uint32_t dose_dim
     auto* f = new rtd_field_impl();
     f->remote = remote;
     f->sw = readSwitches();
+    if (f->sw.fillSegSteps)   // (whole batches, at least one; large values: one segment, and no overflow in the kernel's step arithmetic)
+        f->fillSegSteps = (std::min(std::max(*f->sw.fillSegSteps, 1), 1 << 20) + kFillBatch - 1) / kFillBatch * kFillBatch;
     FieldConst& fc = f->fc;
     fc.W = W; fc.H = H; fc.L = L; fc.S = S; fc.bevW = W + 2 * kMaxSuperpR; fc.bevH = H + 2 * kMaxSuperpR;
     fc.tilesX = tilesX; fc.tilesY = tilesY;
@@ -610,7 +612,7 @@ static int createField(rtd_handle hh, const rtd_beam* b, const uint32_t dose_dim
     if (e == hipSuccess) e = hipMemset(f->dState, 0, sizeof(FieldState));
     // (k_fill's dead-store bytes describe what the dose and 1/sigma arrays hold: a workspace taken over starts, like a fresh one, with
     //  none set. Defensive: only a replaying fill reads them, and the walking compute in front of it, a field's first, clears them.)
-    const size_t nDeadBytes = (size_t)L * tilesX * tilesY * kFillSegs;
+    const size_t nDeadBytes = (size_t)L * tilesX * tilesY * f->fillSegMax() * kFillSegs;
     if (e == hipSuccess && !fresh) e = hipMemset(f->dFillDeadSig, 0, nDeadBytes);
     if (e == hipSuccess && !fresh) e = hipMemset(f->dFillDeadDose, 0, nDeadBytes);
     if (e == hipSuccess) {   // the sample positions at the segment boundaries of k_trace_sample: geometry only, walked once
@@ -858,10 +860,14 @@ static void launchFill(const ComputeJob& c) {
     // the record pass: the sigma walk of every (layer, tile) alone — with a dose record to fill, the dose walk of each as well — in front
     // of the fill that replays it (inside the fill's timing bucket)
     // (k_fill_dr: the kernel that holds the dose record's code; k_fill's builds are what they were without it)
-    if (c.is.sigma == 1 && c.is.dose) launchFillOn((k_fill_dr<false, false, kFillRecord>), fillGrid, (size_t)0, nullptr, recDose);
+    // STEP SEGMENTS (rtd_fill.hpp): the replaying launch is one group of fillGrid blocks per segment of the record's steps, counted here
+    // from what the host knows of the record; the recording launch keeps one block per walk and never looks at the argument
+    const size_t segExtent = std::min(f->memory.sigmaSteps, (size_t)fc.S);
+    const FillSegments segs{f->fillSegSteps, (int)std::max<size_t>((segExtent + (size_t)f->fillSegSteps - 1) / (size_t)f->fillSegSteps, 1), (int)f->fillSegMax()};
+    if (c.is.sigma == 1 && c.is.dose) launchFillOn((k_fill_dr<false, false, kFillRecord>), fillGrid, (size_t)0, nullptr, recDose, segs);
     else if (c.is.sigma == 1) launchFillOn((k_fill<false, false, kFillRecord>), dim3(fillGrid.x / 2), (size_t)0, nullptr);
     // (a replayed dose step looks nothing up: the block's dynamic LDS is the sigma role's exchange buffers and the step table)
-    if (c.is.dose) launchFillOn((k_fill_dr<false, false, kFillReplay>), fillGrid, (size_t)fillTabOffset(false, h->lut.nSamples) * sizeof(float) + tabLds, c.ev(kEvFill), recDose);
+    if (c.is.dose) launchFillOn((k_fill_dr<false, false, kFillReplay>), dim3(fillGrid.x * (unsigned)segs.count), (size_t)fillTabOffset(false, h->lut.nSamples) * sizeof(float) + tabLds, c.ev(kEvFill), recDose, segs);
     else if (c.is.sigma) { if (ldsLut) launchFill((k_fill<true, false, kFillReplay>), dynLds); else launchFill((k_fill<false, false, kFillReplay>), dynLds); }
     else if (fc.nuclearCorr) { if (ldsLut) launchFill((k_fill<true, true>), dynLds); else launchFill((k_fill<false, true>), dynLds); }
     else { if (ldsLut) launchFill((k_fill<true, false>), dynLds); else launchFill((k_fill<false, false>), dynLds); }
@@ -986,7 +992,7 @@ int rtd_field_compute_bev(rtd_handle hh, rtd_field ff) {
         f->dSigMin, f->dSigMax, (size_t)fc.L * fc.S, f->dScanDbg,
         // (a fill that walks stores every dead value and touches no dead-store byte: the reset in front of it leaves none set)
         reinterpret_cast<unsigned int*>(f->dFillDeadSig), reinterpret_cast<unsigned int*>(f->dFillDeadDose),
-        f->memory.flight.sigma == 0 && !f->sw.noDeadSkip ? (size_t)fc.L * fc.tilesX * fc.tilesY * kFillSegs / 4 : (size_t)0}};
+        f->memory.flight.sigma == 0 && !f->sw.noDeadSkip ? (size_t)fc.L * fc.tilesX * fc.tilesY * f->fillSegMax() * kFillSegs / 4 : (size_t)0}};
     if (!c.is.reuse) { const int st = launchTrace(c); if (st != RTD_OK) return st; }
     launchPlanConv(c);
     launchFill(c);

@@ -65,12 +65,14 @@ struct rtd_handle_impl {
 // RTD_NO_DOSE_REPLAY (no dose record: the dose role of every compute walks; RTD_NO_SIGMA_REUSE and RTD_NO_TRACE_REUSE leave it out too),
 // RTD_*_DEBUG (per-block clock stamps), and the overrides RTD_TRACE_MODE, RTD_TRACE_DIAG_B, RTD_KS_GROUPS, RTD_SW_GROUPS,
 // RTD_DOSE_REPLAY_BLOCKS (the number of k_fill blocks taken to be resident at once: a field with more keeps no dose record, doseReplayPays.
-// It exists for tests/test_gpu_dose_replay.py, which has no other way to a field whose fill does not fit; not a user-facing switch.)
+// It exists for tests/test_gpu_dose_replay.py, which has no other way to a field whose fill does not fit; not a user-facing switch.),
+// RTD_FILL_SEG_STEPS (steps of a walk per block of the dose-replaying k_fill, rounded up to whole batches of 8: rtd_fill.hpp, STEP
+// SEGMENTS; a value at or above the record's extent: one block per walk).
 struct Switches {
     bool noUniformPath = false, uniformV2 = false, noSweep = false, separatePlan = false, separateKsPlan = false, noTraceReuse = false, noFillCompact = false;
     bool noSigmaReuse = false, noDeadSkip = false, noDoseReplay = false;
     bool scanDebug = false, fillDebug = false, uniformDebug = false, sweepDebug = false;
-    std::optional<int> traceMode, traceDiagB, ksGroups, swGroups, doseReplayBlocks;
+    std::optional<int> traceMode, traceDiagB, ksGroups, swGroups, doseReplayBlocks, fillSegSteps;
 };
 
 Switches readSwitches() {
@@ -79,7 +81,8 @@ Switches readSwitches() {
     return Switches{on("RTD_NO_UNIFORM_PATH"), on("RTD_UNIFORM_V2"), on("RTD_NO_SWEEP"), on("RTD_SEPARATE_PLAN"), on("RTD_SEPARATE_KS_PLAN"),
                     on("RTD_NO_TRACE_REUSE"), on("RTD_NO_FILL_COMPACT"), on("RTD_NO_SIGMA_REUSE"), on("RTD_NO_DEAD_SKIP"), on("RTD_NO_DOSE_REPLAY"),
                     on("RTD_SCAN_DEBUG"), on("RTD_FILL_DEBUG"), on("RTD_UNIFORM_DEBUG"), on("RTD_SWEEP_DEBUG"),
-                    num("RTD_TRACE_MODE"), num("RTD_TRACE_DIAG_B"), num("RTD_KS_GROUPS"), num("RTD_SW_GROUPS"), num("RTD_DOSE_REPLAY_BLOCKS")};
+                    num("RTD_TRACE_MODE"), num("RTD_TRACE_DIAG_B"), num("RTD_KS_GROUPS"), num("RTD_SW_GROUPS"), num("RTD_DOSE_REPLAY_BLOCKS"),
+                    num("RTD_FILL_SEG_STEPS")};
 }
 
 // Classes of a field's device buffers: the workspace that a field of the same shape takes over (rtd_field_release), the NUCLEAR_CORR
@@ -119,7 +122,7 @@ struct rtd_field_impl {
     LayerPlan* dLayers = nullptr;
     float* dStepTab = nullptr;
     int* dActive = nullptr;      // [L][S][4] minima of (x, y, -x, -y) over rays with dose > 0
-    // k_fill's DEAD STORES (rtd_fill.hpp): per role [L][tiles][kFillSegs] "the segment's steps hold the dead value"; zero when allocated and when taken over
+    // k_fill's DEAD STORES (rtd_fill.hpp): per role [L][tiles][fillSegMax()][kFillSegs] "the segment's steps hold the dead value"; zero when allocated and when taken over
     unsigned char *dFillDeadSig = nullptr, *dFillDeadDose = nullptr;
     unsigned int *dSigMin = nullptr, *dSigMax = nullptr;   // [L][S] bits of the smallest / largest tile-uniform sigma^2 (uniform-sigma detection)
     bool uniformEligible = false; // the separable superposition may take the field (no nuclear halo, BEV height within its accumulators)
@@ -130,6 +133,10 @@ struct rtd_field_impl {
     unsigned int* dSigRec = nullptr; int* dSigRecLast = nullptr;
     unsigned int* dDoseRec = nullptr;   // the dose record, [L][memory.doseSteps][R] words: allocated and freed with the sigma record
     int fillResident = -1;              // blocks of the dose-replaying k_fill that the GPU holds at once (-1: not asked yet; doseReplayPays)
+    // STEP SEGMENTS of the dose-replaying k_fill (rtd_fill.hpp): steps per block (RTD_FILL_SEG_STEPS), and the most segments a walk of
+    // this field can have (S steps): the stride of the dead-store bytes and of the debug stamps
+    int fillSegSteps = kFillSegSteps;
+    size_t fillSegMax() const { return ((size_t)fc.S + (size_t)fillSegSteps - 1) / (size_t)fillSegSteps; }
     // NUCLEAR_CORR (default off): the halo on the spot-resolution grid
     int* dNucSpotIdx = nullptr; float *dNucRayWeights = nullptr, *dNucIdd = nullptr, *dNucRs = nullptr, *dNucBev = nullptr;
     int* dNucEffT = nullptr;
@@ -228,7 +235,7 @@ struct rtd_field_impl {
         visit(dTileRad, tileRadWords * 4, kShape, false, "tile_radius");
         visit(dLayers, L, kShape, false, nullptr); visit(dState, (size_t)1, kShape, false, nullptr); visit(dStepTab, 2 * S, kShape, false, nullptr);
         visit(dActive, 4 * L * S, kShape, false, "active"); visit(dSigMin, L * S, kShape, false, nullptr); visit(dSigMax, L * S, kShape, false, nullptr);
-        visit(dFillDeadSig, L * tiles * kFillSegs, kShape, true, nullptr); visit(dFillDeadDose, L * tiles * kFillSegs, kShape, true, nullptr);
+        visit(dFillDeadSig, L * tiles * fillSegMax() * kFillSegs, kShape, true, nullptr); visit(dFillDeadDose, L * tiles * fillSegMax() * kFillSegs, kShape, true, nullptr);
         visit(dNucSpotIdx, nuc * R, kNuclear, false, nullptr); visit(dNucRayWeights, nucR * L, kNuclear, false, nullptr);
         visit(dNucIdd, nucR * L, kNuclear, false, nullptr); visit(dNucRs, nucR * L, kNuclear, false, nullptr);
         visit(dNucBev, nuc * nucBev, kNuclear, false, nullptr); visit(dNucEffT, nucTiles * L, kNuclear, false, nullptr);
@@ -258,7 +265,8 @@ struct rtd_field_impl {
         visit(dSigRec, memory.sigmaSteps * R * L, kSigmaRec, false, nullptr); visit(dSigRecLast, memory.sigmaSteps ? R * L : (size_t)0, kSigmaRec, false, nullptr);
         visit(dDoseRec, memory.doseSteps * R * L, kSigmaRec, false, nullptr);
         visit(dScanDbg, sw.scanDebug ? 8 * (R / 64) : 0, kDiag, true, "scan_debug");
-        visit(dFillDbg, sw.fillDebug ? 4 * 2 * tiles * L : 0, kDiag, false, "fill_debug");
+        // (a stamp per block of the largest grid, STEP SEGMENTS; cleared: the rows of blocks that a launch does not have stay zero)
+        visit(dFillDbg, sw.fillDebug ? 4 * 2 * tiles * L * fillSegMax() : 0, kDiag, true, "fill_debug");
         visit(dUniDbg, sw.uniformDebug && uniformEligible && uniform4() ? 16 * S * nPartsU4 : 0, kDiag, true, "uniform_debug");
         visit(dSweepDbg, sw.sweepDebug ? sweep * (8 + 4 * 16) * (patches * swGroups + 1) : 0, kDiag, true, "sweep_debug");
         visit(dSweepBigDbg, sw.sweepDebug ? sweep * 48 * patches * bgGroups : 0, kDiag, true, "sweep_big_debug");

@@ -153,9 +153,33 @@ struct SigmaRec {
 //   classification or the rectangles stay). A walking fill stores everything and sets nothing: the reset in front of it
 //   (ResetJob, rtd_field_state.hpp) clears every byte, which claims nothing. Read when the kernel runs: a graph stays correct.
 // (RTD_NO_DEAD_SKIP: null pointers — every store as before, no bytes.)
-struct FillDead { unsigned char* sig; unsigned char* dose; };       // [L][tiles][kFillSegs] each
+struct FillDead { unsigned char* sig; unsigned char* dose; };       // [L][tiles][kFillSegs] each (k_fill_dr's replay: [L][tiles][FillSegments::stride][kFillSegs], STEP SEGMENTS)
 
-// NUC: NUCLEAR_CORR compiled in (its table lookups and IEEE divisions cost registers: the default build keeps 6 blocks per CU)
+// STEP SEGMENTS (k_fill_dr's kFillReplay alone). With both roles replayed no value of the sigma role crosses a step, and two of the
+// dose role do (res and, under dose to water, the stopping power of the step before); everything a block accumulates is an integer
+// minimum, maximum or sum. The kernel is a map over (layer, step, ray), so a block takes a SEGMENT of a walk's steps: segment s of a
+// layer is [pFirst + s * steps, min(pFirst + (s + 1) * steps, afterLast)), steps a multiple of the batch, so that every batch and every
+// (step, tile) reduction is the one the whole walk had. The grid is count groups of 2 * L * tiles blocks, count = ceil(record extent /
+// steps), known on the host; a block whose segment starts behind its layer's last step leaves in front of its first barrier.
+//   res         the dose block looks back from its first step (rtd_fill_body.hpp); nothing is handed from block to block.
+//   per walk    firstPassive, layerFirstPassive: every segment writes the same values.
+//   dead bytes  one per (layer, tile, STEP SEGMENT, segment of kFillSeg rays) and role, stride step segments to a tile (the field's
+//               largest count: S steps): "the steps of this step segment hold the dead value". One block reads and writes a byte.
+//   uniformity  tracked per block: a later segment of a field that is not uniform issues the sigMin / sigMax atomics again until
+//               it has seen two values in a tile; nonUniform is set by then, and nothing reads the extremes of such a field.
+// (count == 1: one block per walk, placed as k_fill places its walks — RTD_FILL_SEG_STEPS at or above the record's extent.)
+// LOOK BEFORE AN EXTREME (the same build). Every block of a field ends with atomic minima and maxima on a handful of words —
+// FieldState::actUnion, a layer's layerFirstPassive, classLo, classHi — and the L2 takes the atomics of one line one after the
+// other: measured, the launch grew by about 20 ns per block with them, whatever the number of blocks resident. The replaying build
+// reads the word (fillPeek) and sends only a value that would change what it read. The words move one way during a launch, so a
+// value that was read earlier errs on the side of sending; the sums (hist) are sent as before. The results are the same words.
+struct FillSegments { int steps; int count; int stride; };
+// (a plain read of a word that blocks of the running launch change with atomics: volatile, so that it is a load of its own)
+__device__ inline int fillPeek(const int* p) { return *reinterpret_cast<const volatile int*>(p); }
+constexpr int kFillSegSteps = 128;                    // the default (RTD_FILL_SEG_STEPS overrides; the values measured: DESIGN.md section 4 K5)
+static_assert(kFillSegSteps % kFillBatch == 0, "a segment is whole batches");
+
+// NUC: NUCLEAR_CORR compiled in(its table lookups and IEEE divisions cost registers: the default build keeps 6 blocks per CU)
 // k_fill: the body as it stands without the dose record.
 #define RTD_FILL_KERNEL k_fill
 #include "rtd_fill_body.hpp"

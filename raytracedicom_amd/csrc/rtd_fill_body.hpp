@@ -14,9 +14,9 @@ __global__ __launch_bounds__(256) void RTD_FILL_KERNEL(const float* __restrict__
 #ifndef RTD_FILL_DOSE_REC
                                                int compact, SigmaRec rec, FillDead dead) {
 #else
-                                               int compact, SigmaRec rec, FillDead dead, unsigned int* __restrict__ recDose) {
-    // (recDose: THE DOSE RECORD, [L][rec.steps][H][W], null: none. The last argument, so that the builds that never look at it read
-    //  their arguments from where they always were.)
+                                               int compact, SigmaRec rec, FillDead dead, unsigned int* __restrict__ recDose, FillSegments segs) {
+    // (recDose: THE DOSE RECORD, [L][rec.steps][H][W], null: none. segs: STEP SEGMENTS, looked at by kFillReplay alone. The last
+    //  arguments, so that the builds that never look at them read their arguments from where they always were.)
 #endif
     static_assert(!NUC || MODE == kFillWalk, "the halo's fields always walk");
     extern __shared__ float sLutF[];                                 // dose walk: the layer's two cumulative-IDD rows
@@ -50,6 +50,15 @@ __global__ __launch_bounds__(256) void RTD_FILL_KERNEL(const float* __restrict__
 #endif
     const int tid = threadIdx.y * 32 + threadIdx.x;                  // lane slot of the block (its ray: LANE PLACEMENT)
     int item = blockIdx.x;
+#ifdef RTD_FILL_DOSE_REC
+    // STEP SEGMENTS (rtd_fill.hpp): the grid is segs.count groups of nB blocks, the group of a walk's first steps in front. Nothing is
+    // resident from start to end any more, so the blocks are taken in the order of the grid: within a group the dose role, the dearer
+    // step, in front of the sigma role, the layers in their order. (One segment: the placement of the walks, as it was.)
+    const bool segmented = MODE == kFillReplay && segs.count > 1;
+    int seg = 0;
+    if (segmented) { seg = (int)blockIdx.x / nB; item = (int)blockIdx.x % nB; }
+    else
+#endif
     if (nB <= kFillSnakeRounds * nCU) {
         const int rr = blockIdx.x / nCU, c = blockIdx.x % nCU, nFull = nB / nCU;
         const bool reversed = rr < nFull && ((nFull - 1 - rr) & 1) == 0;       // the last full round: CU 0 gets its cheapest walk
@@ -60,7 +69,8 @@ __global__ __launch_bounds__(256) void RTD_FILL_KERNEL(const float* __restrict__
     const int pr = MODE == kFillRecord ? (item / nTiles) << 1 : (int)st->fillItems[item / nTiles];   // (record: sigma walks only, in layer order)
 #else
     // (record: the sigma walks in layer order, then — with a dose record to fill — the dose walks in layer order)
-    const int pr = MODE == kFillRecord ? (item / nTiles < fc.L ? (item / nTiles) << 1 : (item / nTiles - fc.L) << 1 | 1) : (int)st->fillItems[item / nTiles];
+    const int pr = MODE == kFillRecord ? (item / nTiles < fc.L ? (item / nTiles) << 1 : (item / nTiles - fc.L) << 1 | 1)
+                 : segmented ? (item / nTiles < fc.L ? (item / nTiles) << 1 | 1 : (item / nTiles - fc.L) << 1) : (int)st->fillItems[item / nTiles];
 #endif
     const int layer = pr >> 1;
     const int role = pr & 1;                                         // block-uniform: 0 sigma walk (or its replay), 1 dose walk
@@ -82,6 +92,19 @@ __global__ __launch_bounds__(256) void RTD_FILL_KERNEL(const float* __restrict__
     // many steps; a layer beyond them would be recorded short and replayed wrong, so it is an error flag (rtd_field_finish reports it).
     if (tid == 0 && pFirst < pAfterLast && (pAfterLast - pFirst > (unsigned int)rec.steps || pAfterLast > (unsigned int)fc.S))
         atomicOr(&st->errorFlags, kErrRecordExtent);
+    // STEP SEGMENTS: the steps [pBegin, pEnd) of the walk are this block's. A segment that starts behind the layer's last step has
+    // nothing to do (the first segment of a walk without steps still leaves what such a walk leaves).
+    const unsigned int pBegin = segmented ? pFirst + (unsigned int)seg * (unsigned int)segs.steps : pFirst;
+    const unsigned int pEnd = segmented && pBegin + (unsigned int)segs.steps < pAfterLast ? pBegin + (unsigned int)segs.steps : pAfterLast;
+    if (segmented && seg > 0 && pBegin >= pAfterLast) {
+        if (dbg && tid == 0) {
+            long long* q = dbg + 4 * (size_t)blockIdx.x;
+            q[0] = dbgT0; q[1] = dbgT0; q[2] = 0; q[3] = ((long long)seg << 40) | ((long long)item << 8) | (long long)(role << 4) | 1;
+        }
+        return;
+    }
+#else
+    const unsigned int pBegin = pFirst, pEnd = pAfterLast;           // (k_fill_dr's STEP SEGMENTS: a walk is one block here)
 #endif
 
     // liveness of a ray at the start of its walk (:236-243): a function of the ray weight and the cut-off steps
@@ -141,16 +164,22 @@ __global__ __launch_bounds__(256) void RTD_FILL_KERNEL(const float* __restrict__
     //  walks its first compute of a field measured 5 us slower, with the table in the sigma walk alone it needs 74 registers, a wave
     //  per SIMD less)
     if (MODE == kFillReplay) {
-        unsigned int nTab = pFirst < pAfterLast ? (pAfterLast - pFirst + (kFillBatch - 1)) & ~(unsigned int)(kFillBatch - 1) : 0u;
+        unsigned int nTab = pBegin < pEnd ? (pEnd - pBegin + (kFillBatch - 1)) & ~(unsigned int)(kFillBatch - 1) : 0u;
         nTab = nTab < (unsigned int)fillTabFloats(fc.S) ? nTab : (unsigned int)fillTabFloats(fc.S);
         for (unsigned int i = tid; i < nTab; i += 256) {
-            const unsigned int k = pFirst + i < (unsigned int)fc.S ? pFirst + i : (unsigned int)fc.S - 1u;
+            const unsigned int k = pBegin + i < (unsigned int)fc.S ? pBegin + i : (unsigned int)fc.S - 1u;
             sTab[i] = stepTab[2 * k + role];
         }
     }
     // DEAD STORES (the replaying build only): called once the wave knows whether it has a live ray at its start; wave-uniform throughout
+#ifndef RTD_FILL_DOSE_REC
     unsigned char* const deadBytes = MODE != kFillReplay || !dead.sig ? nullptr
                                      : (role == 0 ? dead.sig : dead.dose) + ((size_t)layer * nTiles + tileNo) * kFillSegs;
+#else
+    // (STEP SEGMENTS: the bytes of this block's steps — a byte has one writer and one reader per launch, as it always had)
+    unsigned char* const deadBytes = MODE != kFillReplay || !dead.sig ? nullptr
+                                     : (role == 0 ? dead.sig : dead.dose) + (((size_t)layer * nTiles + tileNo) * segs.stride + seg) * kFillSegs;
+#endif
     bool deadAtStart = false, deadSkip = false;
     unsigned int waveEnd = 0xffffffffu;                              // the tail of a walk: the last of the steps at which the wave's rays end
     auto deadOpen = [&]() {
@@ -177,7 +206,7 @@ __global__ __launch_bounds__(256) void RTD_FILL_KERNEL(const float* __restrict__
     auto loadTab = [&](unsigned int step0) {
 #pragma unroll
         for (int j = 0; j < kFillBatch; ++j)
-            tabB[j] = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(sTab[step0 - pFirst + j])));
+            tabB[j] = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(sTab[step0 - pBegin + j])));
     };
 
     if (role == 0) {
@@ -214,12 +243,12 @@ __global__ __launch_bounds__(256) void RTD_FILL_KERNEL(const float* __restrict__
         };
         if (MODE == kFillReplay) {
             afterLast = beamLive ? (unsigned int)rec.last[(size_t)layer * memStep + rayIdx] : 0u;
-            waveLive = __ballot(beamLive && pFirst < afterLast) != 0ull;   // a ray of the wave has a step that is not masked
+            waveLive = __ballot(beamLive && pBegin < afterLast) != 0ull;   // a ray of the wave has a step that is not masked
         }
         deadOpen();
 #pragma unroll
         for (int j = 0; j < kFillBatch; ++j) {
-            if (MODE == kFillReplay) fetchRec(j, pFirst + j);        // (NO BRANCH AROUND A PREFETCH: a wave without a live ray never looks at it)
+            if (MODE == kFillReplay) fetchRec(j, pBegin + j);        // (NO BRANCH AROUND A PREFETCH: a wave without a live ray never looks at it)
             else if (waveLive) fetch1(j, pFirst + j);
             else { spB[j] = 0.0f; denB[j] = 0.0f; rrlB[j] = 0.0f; }
         }
@@ -252,7 +281,7 @@ __global__ __launch_bounds__(256) void RTD_FILL_KERNEL(const float* __restrict__
             if (l == 31 && step0 + j < pAfterLast) {
                 // tile minimum of 1/sigma (= the reference's minVal, kernel_wrapper.cuh:282-297) from the tile maximum of
                 // sigmaSq with IEEE sqrt and division, then the class exactly as the reference computes it (:300-305)
-                const float minRs = m >= 0.0f ? (MODE == kFillReplay ? sTab[step0 + j - pFirst] : stepTab[2 * (step0 + j)]) / (sqrt2 * (sqrtf(m) + sigmaDeltaV)) : __int_as_float(0x7f800000);
+                const float minRs = m >= 0.0f ? (MODE == kFillReplay ? sTab[step0 + j - pBegin] : stepTab[2 * (step0 + j)]) / (sqrt2 * (sqrtf(m) + sigmaDeltaV)) : __int_as_float(0x7f800000);
                 int rad = f2iSat(fc.ksSigmaCutoff / (sqrtf(2.0f) * minRs) + 0.5f);
                 rad = rad > kMaxSuperpR + 1 ? kMaxSuperpR + 1 : rad;
                 rad = rad < 0 ? 0 : rad;
@@ -262,7 +291,7 @@ __global__ __launch_bounds__(256) void RTD_FILL_KERNEL(const float* __restrict__
                 atomicMax(&sClassHi[rad], (int)(step0 + j));
             }
         };
-        unsigned int step0 = pFirst;
+        unsigned int step0 = pBegin;
         int buf = 0;
         auto replayBatch = [&](auto kind) {
             loadTab(step0);
@@ -291,8 +320,8 @@ __global__ __launch_bounds__(256) void RTD_FILL_KERNEL(const float* __restrict__
         };
         // (ONE PATH THROUGH THE LOOP: the full batches, then the layer's last batch)
         if (MODE == kFillReplay) {
-            while (step0 + kFillBatch <= pAfterLast && waveLive) replayTrip(FillFullBatch{});
-            if (step0 < pAfterLast && waveLive) replayTrip(FillTailBatch{});
+            while (step0 + kFillBatch <= pEnd && waveLive) replayTrip(FillFullBatch{});
+            if (step0 < pEnd && waveLive) replayTrip(FillTailBatch{});
         }
         else for (; step0 < pAfterLast && waveLive; step0 += kFillBatch, buf ^= 1) {
 #pragma unroll
@@ -347,7 +376,7 @@ __global__ __launch_bounds__(256) void RTD_FILL_KERNEL(const float* __restrict__
         // -1 in the block's exchange buffers (those once per buffer) — without inputs and without arithmetic. The barriers and the
         // wave's share of the classification stay.
         // (record: "masked" into the record, and nothing else)
-        for (int deadBufs = 0; step0 < pAfterLast; step0 += kFillBatch, buf ^= 1) {
+        for (int deadBufs = 0; step0 < pEnd; step0 += kFillBatch, buf ^= 1) {
             if (MODE == kFillRecord) {
 #pragma nounroll
                 for (int j = 0; j < kFillBatch; ++j)
@@ -373,6 +402,18 @@ __global__ __launch_bounds__(256) void RTD_FILL_KERNEL(const float* __restrict__
         firstPassive[(size_t)layer * memStep + rayIdx] = (int)afterLast;
         if (NUC && nucIdx >= 0 && pFirst < pAfterLast) nuc.rs[(size_t)layer * fc.nucW * fc.nucH + nucIdx] = nucRSigmaEff;   // value of the last step (:367-373)
         int mx = waveMaxI((int)afterLast);
+#ifdef RTD_FILL_DOSE_REC
+        // STEP SEGMENTS: a minimum or maximum that the layer's record already holds is not sent (LOOK BEFORE AN EXTREME, rtd_fill.hpp)
+        if (MODE == kFillReplay) {
+            if ((tid & (kWave - 1)) == 0 && mx > fillPeek(&layers[layer].layerFirstPassive)) atomicMax(&layers[layer].layerFirstPassive, mx);
+            __syncthreads();
+            if (tid < kMaxSuperpR + 2 && sHist[tid] > 0) {
+                atomicAdd(&layers[layer].hist[tid], sHist[tid]);
+                if (sClassLo[tid] < fillPeek(&layers[layer].classLo[tid])) atomicMin(&layers[layer].classLo[tid], sClassLo[tid]);
+                if (sClassHi[tid] > fillPeek(&layers[layer].classHi[tid])) atomicMax(&layers[layer].classHi[tid], sClassHi[tid]);
+            }
+        } else {
+#endif
         if ((tid & (kWave - 1)) == 0) atomicMax(&layers[layer].layerFirstPassive, mx);
         __syncthreads();
         if (tid < kMaxSuperpR + 2 && sHist[tid] > 0) {
@@ -380,6 +421,9 @@ __global__ __launch_bounds__(256) void RTD_FILL_KERNEL(const float* __restrict__
             atomicMin(&layers[layer].classLo[tid], sClassLo[tid]);
             atomicMax(&layers[layer].classHi[tid], sClassHi[tid]);
         }
+#ifdef RTD_FILL_DOSE_REC
+        }
+#endif
     } else {
         // ================================ dose walk ================================
         // cumulative IDD: rows floor(energyIdx), floor(energyIdx)+1 (CLAMP) and the row weight are layer constants
@@ -449,15 +493,42 @@ __global__ __launch_bounds__(256) void RTD_FILL_KERNEL(const float* __restrict__
 #ifdef RTD_FILL_DOSE_REC
         if (MODE == kFillReplay) {                               // (as the sigma replay: the walk ends at the same step in both roles)
             afterLast = beamLive ? (unsigned int)rec.last[(size_t)layer * memStep + rayIdx] : 0u;
-            waveLive = __ballot(beamLive && pFirst < afterLast) != 0ull;   // a ray of the wave has a step that is not masked
+            waveLive = __ballot(beamLive && pBegin < afterLast) != 0ull;   // a ray of the wave has a step that is not masked
         }
 #endif
         deadOpen();
 #pragma unroll
         for (int j = 0; j < kFillBatch; ++j) {
-            if (MODE == kFillReplay || waveLive) fetch1(j, pFirst + j);   // (replay: NO BRANCH AROUND A PREFETCH, a wave without a live ray never looks at it)
+            if (MODE == kFillReplay || waveLive) fetch1(j, pBegin + j);   // (replay: NO BRANCH AROUND A PREFETCH, a wave without a live ray never looks at it)
             else { spB[j] = 0.0f; denB[j] = 0.0f; }
         }
+#ifdef RTD_FILL_DOSE_REC
+        // STEP SEGMENTS, what crosses a boundary: res in front of step pBegin, by looking back with the replayed step's own loads and
+        // expressions — +0 for a ray that is dead under this compute's weights or masked at the step before, the step's value where
+        // its mass is above 1e-2, else whatever the step before that leaves, back to the walk's first step (+0 in front of it): exact
+        // for a low-mass run of any length; and, under dose to water, the stopping power of step pBegin - 1. Behind the prefetches: the
+        // first look back lands with them. (A wave without a live ray at pBegin only stores and carries nothing.)
+        if (MODE == kFillReplay && pBegin > pFirst && waveLive) {
+            // (the loads clamped as the replayed step clamps its own, fetch1: every step of the layer lies within the limits)
+            auto clamped = [&](unsigned int step) { return step < lastFetch ? step : lastFetch; };
+            unsigned int k = pBegin - 1u;
+            float massIn = (denSrc + (size_t)clamped(k) * memStep32)[rayOff];
+            massInOld = massIn;
+            bool open = beamLive;
+            while (__ballot(open) != 0ull) {                         // (wave-uniform; k: the step looked at)
+                const unsigned int kc = clamped(k);
+                const unsigned int r = (recDose + recOff + (size_t)(kc - firstFetch) * memStep32)[rayOff];
+                const float below = fc.doseToWater && k > pFirst ? (denSrc + (size_t)clamped(k - 1u) * memStep32)[rayOff] : 0.0f;
+                const float tab = stepTab[2 * kc + 1];
+                const float mass = fc.doseToWater ? (massIn - below) * tab : massIn * tab;
+                const float val = rayWeight * __uint_as_float(r) * __builtin_amdgcn_rcpf(mass);
+                if (open && (r == kDoseMasked || mass > 1e-2f)) { res = r == kDoseMasked ? 0.0f : val; open = false; }
+                if (k == pFirst) break;
+                --k;
+                massIn = fc.doseToWater ? below : (denSrc + (size_t)clamped(k) * memStep32)[rayOff];
+            }
+        }
+#endif
         __syncthreads();
         // after a batch's barrier — rectangle of the tile's rays that carry dose at step j, as minima of (x, y, -x, -y): lanes 0..3 of
         // the step's group, one component each, from the four waves' rectangles
@@ -475,7 +546,7 @@ __global__ __launch_bounds__(256) void RTD_FILL_KERNEL(const float* __restrict__
                 }
             }
         };
-        unsigned int step0 = pFirst;
+        unsigned int step0 = pBegin;
         int buf = 0;
         auto doseTrip = [&](auto kind) {
             // lane kFillBatch - 1 - j: the wave's rectangle at step j of the batch (each step shifts the lanes up by one and enters at lane 0)
@@ -583,8 +654,8 @@ __global__ __launch_bounds__(256) void RTD_FILL_KERNEL(const float* __restrict__
         };
         // (replay: ONE PATH THROUGH THE LOOP)
         if (MODE == kFillReplay) {
-            while (step0 + kFillBatch <= pAfterLast && waveLive) doseTrip(FillFullBatch{});
-            if (step0 < pAfterLast && waveLive) doseTrip(FillTailBatch{});
+            while (step0 + kFillBatch <= pEnd && waveLive) doseTrip(FillFullBatch{});
+            if (step0 < pEnd && waveLive) doseTrip(FillTailBatch{});
         }
         else while (step0 < pAfterLast && waveLive) doseTrip(FillTailBatch{});
         // The rest of the walk when no ray of the wave is alive (any more): dose 0 in memory, no ray with dose in the block's exchange
@@ -592,7 +663,7 @@ __global__ __launch_bounds__(256) void RTD_FILL_KERNEL(const float* __restrict__
 #ifdef RTD_FILL_DOSE_REC
         // (record: "masked" into the record, and nothing else)
 #endif
-        for (int deadBufs = 0; step0 < pAfterLast; step0 += kFillBatch, buf ^= 1) {
+        for (int deadBufs = 0; step0 < pEnd; step0 += kFillBatch, buf ^= 1) {
 #ifdef RTD_FILL_DOSE_REC
             if (MODE == kFillRecord) {
 #pragma nounroll
@@ -618,14 +689,30 @@ __global__ __launch_bounds__(256) void RTD_FILL_KERNEL(const float* __restrict__
         if (MODE == kFillRecord) return;
 #endif
         deadClose();
+#ifdef RTD_FILL_DOSE_REC
+        // LOOK BEFORE AN EXTREME (rtd_fill.hpp; the replaying build): every dose block of the field sends its rectangle to the same four words,
+        // and the L2 takes the atomics of one line one after the other. The block reads the word first and sends only a value
+        // that is smaller than what it read: the word only ever falls during a launch, so a value read earlier (a line an L1 holds)
+        // is not below it, and what is left out could not have changed it.
+        if (MODE == kFillReplay) { if ((tid & 31) < 4 && actUni < fillPeek(&st->actUnion[tid & 3])) atomicMin(&st->actUnion[tid & 3], actUni); }
+        else
+#endif
         if ((tid & 31) < 4 && actUni != 0x7fffffff) atomicMin(&st->actUnion[tid & 3], actUni);
         if (NUC && nucIdx >= 0 && pFirst < pAfterLast) nuc.idd[(size_t)layer * fc.nucW * fc.nucH + nucIdx] = nucRes;   // value of the last step (:367-373)
     }
     if (dbg && tid == 0) {
+#ifndef RTD_FILL_DOSE_REC
         long long* q = dbg + 4 * (size_t)item;
+#else
+        long long* q = dbg + 4 * (size_t)(segmented ? (int)blockIdx.x : item);
+#endif
         q[0] = dbgT0; q[1] = (long long)__builtin_amdgcn_s_memtime();
         q[2] = ((long long)__builtin_amdgcn_s_getreg((20 << 0) | (0 << 6) | (3 << 11)) << 32) | (unsigned)__builtin_amdgcn_s_getreg((4 << 0) | (0 << 6) | (31 << 11));
+#ifndef RTD_FILL_DOSE_REC
         q[3] = ((long long)item << 8) | (long long)(role << 4) | 0;
+#else
+        q[3] = ((long long)seg << 40) | ((long long)item << 8) | (long long)(role << 4) | 0;   // (STEP SEGMENTS: the segment above the item)
+#endif
         (void)pAfterLast;
     }
 }

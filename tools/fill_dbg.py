@@ -23,8 +23,9 @@ for i in range(3):
 W, H, L = info["ray_dims"]
 nT = (W // 32) * (H // 8)
 dbg = f.fetch("fill_debug").reshape(-1, 4)
+dbg = dbg[(dbg[:, 1] != 0) & ((dbg[:, 3] & 1) == 0)]                 # (step segments: the blocks of the launch that had steps)
 dur = (dbg[:, 1] - dbg[:, 0]).astype(float)
-item = dbg[:, 3] >> 8; role = (dbg[:, 3] >> 4) & 1
+item = (dbg[:, 3] >> 8) & 0xffffffff; role = (dbg[:, 3] >> 4) & 1
 tile = item % nT
 hw = dbg[:, 2]; xcc = (hw >> 32) & 0xF; cu = (hw >> 8) & 0xF; sh = (hw >> 12) & 1; se = (hw >> 13) & 7
 key = (xcc << 16) | (se << 8) | (sh << 4) | cu
