@@ -28,6 +28,7 @@ RTD_OBJ_SQ_EUD, RTD_OBJ_SQ_MAX_EUD, RTD_OBJ_SQ_MIN_EUD = 6, 7, 8     # rtd_objec
 RTD_EUD_MAX_QUERIES = 64
 RTD_ROBUST_EXPECTED, RTD_ROBUST_WORST_CASE = 0, 1
 RTD_ROBUST_MAX_SCENARIOS = 32
+RTD_PLANSET_MAX_PLANS = 16     # plans of a plan set, and the largest plan_stride of the products with P right-hand sides
 
 c_float_p = C.POINTER(C.c_float)
 

@@ -57,6 +57,7 @@ int rtd_field_dose_influence(rtd_handle hh, rtd_field ff, float rel_threshold, s
     hipStream_t s = h->stream;
     const size_t nSpot = (size_t)fc.spotNx * fc.spotNy * fc.L;
     f->dijDone = false; f->letDone = false;                           // (the LET values belong to the matrix that is replaced)
+    ++f->dijEpoch;                                                    // (and so does whatever a plan set sized for it)
     if (!f->dDijSave) {
         f->dijCap = (size_t)1 << 20;
         const int st = allocBuffers(h, f, kDij);

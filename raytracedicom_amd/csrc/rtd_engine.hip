@@ -52,6 +52,7 @@
 #include "rtd_warp.hpp"
 #include "rtd_let.hpp"
 #include "rtd_rbe.hpp"
+#include "rtd_planset.hpp"
 #include "rtd_field_memory.hpp"
 #include "rtd_engine_impl.hpp"
 
@@ -176,6 +177,7 @@ int rtd_destroy(rtd_handle hh) {
     for (hipEvent_t e : h->warpTEv) if (e) (void)hipEventDestroy(e);
     if (h->dQuantScratch) (void)hipFree(h->dQuantScratch);
     if (h->dLetTable) (void)hipFree(h->dLetTable);
+    for (float* p : h->setScratch) (void)hipFree(p);
     if (h->dLutBlock) (void)hipFree(h->dLutBlock);
     if (h->dCtOwned) (void)hipFree(h->dCtOwned);
     if (h->ownStream) (void)hipStreamDestroy(h->ownStream);
@@ -1445,3 +1447,4 @@ int rtd_compute(rtd_handle hh, const rtd_beam* beams, int n_beams, float* dose_i
 #include "rtd_warp_host.hpp"
 #include "rtd_let_host.hpp"
 #include "rtd_rbe_host.hpp"
+#include "rtd_planset_host.hpp"

@@ -55,6 +55,10 @@ struct rtd_handle_impl {
     float* dLetTable = nullptr;
     int letEnergies = 0, letSamples = 0;
     unsigned letEpoch = 0;
+    // rtd_field_dose_influence_apply_t_set (rtd_planset_host.hpp): the chunk sums [chunk][accumulators] of the largest call so far; the
+    // blocks it outgrew stay until rtd_destroy (psHandleScratch)
+    std::vector<float*> setScratch;
+    size_t setScratchFloats = 0;
     void clearCtBoxes() { for (auto& b : ctBoxes) if (b.done) (void)hipEventDestroy(b.done); ctBoxes.clear(); }
 };
 
@@ -181,6 +185,7 @@ struct rtd_field_impl {
     long long *dDijColLen = nullptr, *dDijColSrc = nullptr, *dDijColPtr = nullptr;
     size_t dijCap = 0, dijNnz = 0;
     bool dijDone = false;          // the CSC buffers hold the last call's result
+    unsigned dijEpoch = 0;         // counts the rtd_field_dose_influence calls: what was sized for a matrix (a plan set) knows it by this number
     std::vector<int> dijBatchOf;   // per spot: its batch in the last call (-1: empty column); rtd_field_fetch "dij_batch"
     // products with the matrix (rtd_field_dose_influence_prepare / _apply / _apply_t, rtd_dij_apply.hpp): the row-major companion over the
     // voxels of dijBox (row pointers, columns ascending within a row, values) and the column chunks of the transposed product

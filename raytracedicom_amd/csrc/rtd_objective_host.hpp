@@ -14,6 +14,7 @@ struct rtd_objective_impl {
     std::vector<double> vfrac;    // per term: the volume fraction of a DVH term, 0 for the others
     std::vector<double> expo;     // per term: the exponent of an EUD term, 0 for the others
     bool built = false;           // the device tables belong to rois / terms as they are
+    unsigned epoch = 0;           // counts the ROIs and terms added: what was sized for the objective (a plan set) knows it by this number
     int nU = 0, nBlocks = 0;      // union voxels; blocks of k_obj_eval
     struct Tables { DevBuf<int> dUv, dTPtr; DevBuf<unsigned char> dTIdx; DevBuf<ObjTerm> dTerms; DevBuf<double> dPartial; } tab;   // (tab = {} frees them)
     // DVH (section 13): the ROI index lists concatenated on the device, the selection histograms and the thresholds eval reads. Built
@@ -252,7 +253,7 @@ int rtd_objective_add_roi(rtd_handle hh, rtd_objective oo, const int32_t* voxels
         if (voxels[i] < 0 || (size_t)voxels[i] >= o->nVox || (i && voxels[i] <= voxels[i - 1]))
             return fail(h, RTD_ERR_INVALID_ARG, "rtd_objective_add_roi: voxel indices must be strictly ascending and inside the dose grid");
     o->rois.emplace_back(voxels, voxels + n);
-    o->built = false;
+    o->built = false; ++o->epoch;
     o->dvhBuilt = false;
     o->eudBuilt = false;
     *roi_id = (int32_t)o->rois.size() - 1;
@@ -272,7 +273,7 @@ int rtd_objective_add_term(rtd_handle hh, rtd_objective oo, const rtd_objective_
     o->terms.push_back(*t);
     o->vfrac.push_back(0.0);
     o->expo.push_back(0.0);
-    o->built = false;
+    o->built = false; ++o->epoch;
     return RTD_OK;
 }
 
@@ -290,7 +291,7 @@ int rtd_objective_add_dvh_term(rtd_handle hh, rtd_objective oo, const rtd_object
     o->terms.push_back(rtd_objective_term{t->kind, t->roi, t->weight, t->dose_level});
     o->vfrac.push_back(t->volume_fraction);
     o->expo.push_back(0.0);
-    o->built = false;
+    o->built = false; ++o->epoch;
     return RTD_OK;
 }
 
@@ -338,7 +339,7 @@ int rtd_objective_add_eud_term(rtd_handle hh, rtd_objective oo, const rtd_object
     o->terms.push_back(rtd_objective_term{t->kind, t->roi, t->weight, t->dose_level});
     o->vfrac.push_back(0.0);
     o->expo.push_back(t->exponent);
-    o->built = false;
+    o->built = false; ++o->epoch;
     return RTD_OK;
 }
 

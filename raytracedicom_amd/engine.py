@@ -157,6 +157,17 @@ def lib():
         L.rtd_rbe_destroy.argtypes = [vp, vp]
         L.rtd_optimizer_set_rbe.argtypes = [vp, vp, vp]
         L.rtd_optimizer_rbe_dose.argtypes = [vp, vp, vpp]
+        L.rtd_field_dose_influence_apply_set.argtypes = [vp, vp, vp, vp, C.c_uint32, C.c_uint32, C.c_int]
+        L.rtd_field_dose_influence_apply_t_set.argtypes = [vp, vp, vp, vp, C.c_uint32, C.c_uint32]
+        L.rtd_planset_create.argtypes = [vp, vpp, C.c_uint32, vp, C.POINTER(abi.RtdObjectiveTerm), C.c_uint32, C.POINTER(abi.RtdOptimizerOptions), vpp]
+        L.rtd_planset_set_weights.argtypes = [vp, vp, C.c_uint32, C.c_uint32, vp]
+        L.rtd_planset_run.argtypes = [vp, vp, C.c_uint32]
+        L.rtd_planset_result.argtypes = [vp, vp, C.c_uint32, C.POINTER(abi.RtdOptimizerReport), C.POINTER(C.c_double), C.c_uint32]
+        L.rtd_planset_weights.argtypes = [vp, vp, C.c_uint32, C.c_uint32, C.c_int, vp]
+        L.rtd_planset_dose.argtypes = [vp, vp, C.c_uint32, vp]
+        L.rtd_planset_values.argtypes = [vp, vp, C.POINTER(C.c_double)]
+        L.rtd_planset_blend.argtypes = [vp, vp, C.POINTER(C.c_double), C.c_uint32, C.c_int, vp]
+        L.rtd_planset_destroy.argtypes = [vp, vp]
         L.rtd_host_register.argtypes = [vp, C.c_size_t]
         L.rtd_host_unregister.argtypes = [vp]
         L.rtd_plan_create.argtypes = [C.POINTER(C.c_int), C.c_int, vpp]
@@ -326,6 +337,20 @@ class Field:
         """rtd_field_dose_influence_apply_t: Dij^T g written to dev_out ([L][ny][nx] float32); dev_g: the voxel-weight volume (device
         pointers). Asynchronous once prepared."""
         self.eng._check(lib().rtd_field_dose_influence_apply_t(self.eng._h, self._h, C.c_void_p(int(dev_g)), C.c_void_p(int(dev_out))))
+
+    def dose_influence_apply_set(self, dev_w, dev_dose, n_plans, plan_stride=None, init=False):
+        """rtd_field_dose_influence_apply_set: Dij w for n_plans weight vectors in one pass over the matrix. Plan-minor: element i of
+        plan p at x[i * plan_stride + p] (pareto.interleave), for dev_w and dev_dose alike; plan_stride defaults to n_plans. Slot p
+        holds the bits dose_influence_apply gives for plan p alone; slots p >= n_plans are not written."""
+        stride = int(n_plans if plan_stride is None else plan_stride)
+        self.eng._check(lib().rtd_field_dose_influence_apply_set(self.eng._h, self._h, C.c_void_p(int(dev_w)), C.c_void_p(int(dev_dose)), int(n_plans), stride,
+                                                                 int(bool(init))))
+
+    def dose_influence_apply_t_set(self, dev_g, dev_out, n_plans, plan_stride=None):
+        """rtd_field_dose_influence_apply_t_set: Dij^T g for n_plans voxel-weight volumes in one pass over the matrix, plan-minor as
+        dose_influence_apply_set; dev_out[j * plan_stride + p] is written for p < n_plans."""
+        stride = int(n_plans if plan_stride is None else plan_stride)
+        self.eng._check(lib().rtd_field_dose_influence_apply_t_set(self.eng._h, self._h, C.c_void_p(int(dev_g)), C.c_void_p(int(dev_out)), int(n_plans), stride))
 
     def dose_influence_device(self):
         """rtd_field_dose_influence_device: (col_ptr, row_idx, values, nnz) — the device pointers of the resident CSC arrays as ints
@@ -910,6 +935,93 @@ class Optimizer:
             self._h = C.c_void_p()
 
 
+class PlanSet:
+    """rtd_planset_*: P plans optimised at once over the fields' resident matrices: P weight vectors under P variants of one
+    Objective, every step of the iteration one launch for all of them. Each plan has the bits of a plain Optimizer on a plain objective
+    with that plan's terms. `variants`: per plan one (kind, roi, weight, level) per term of `objective`, in term order (kind and roi
+    those of the objective's term; pareto.anchor_variants makes such tables). Destroy it before its fields, objective and engine."""
+
+    def __init__(self, eng, fields, objective, variants, options=None):
+        self.eng = eng
+        self.objective = objective
+        self.fields = list(fields)
+        self.n_plans = len(variants)
+        self.n_terms = int(objective.n_terms)
+        if any(len(v) != self.n_terms for v in variants):
+            raise ValueError("every plan needs one variant per term of the objective")
+        self._h = C.c_void_p()
+        flat = [t if isinstance(t, abi.RtdObjectiveTerm) else abi.RtdObjectiveTerm(int(t[0]), int(t[1]), float(t[2]), float(t[3]))
+                for v in variants for t in v]
+        tab = (abi.RtdObjectiveTerm * max(1, len(flat)))(*flat)
+        arr = (C.c_void_p * max(1, len(self.fields)))(*[f._h for f in self.fields])
+        po = C.byref(options) if options is not None else None
+        eng._check(lib().rtd_planset_create(eng._h, arr, len(self.fields), objective._h, tab, self.n_plans, po, C.byref(self._h)))
+
+    def set_weights(self, plan, field_index, dev_w):
+        """Plan `plan`'s weights of field field_index from dev_w ([L][ny][nx] float32, contiguous, device pointer)."""
+        self.eng._check(lib().rtd_planset_set_weights(self.eng._h, self._h, int(plan), int(field_index), C.c_void_p(int(dev_w))))
+
+    def run(self, n_iterations):
+        """Launches n_iterations iterations of every plan on the engine's stream; asynchronous, launches only."""
+        self.eng._check(lib().rtd_planset_run(self.eng._h, self._h, int(n_iterations)))
+
+    def result(self, plan, capacity=None):
+        """Waits; (report dict, history float64 array) of plan `plan`, as Optimizer.result."""
+        r = abi.RtdOptimizerReport()
+        self.eng._check(lib().rtd_planset_result(self.eng._h, self._h, int(plan), C.byref(r), None, 0))
+        n = r.history_len if capacity is None else min(int(capacity), r.history_len)
+        hist = np.empty(n, dtype=np.float64)
+        if n:
+            self.eng._check(lib().rtd_planset_result(self.eng._h, self._h, int(plan), C.byref(r), hist.ctypes.data_as(C.POINTER(C.c_double)), n))
+        return r.as_dict(), hist
+
+    def _fetch(self, call, shape, dev_out):
+        if dev_out is not None:
+            self.eng._check(call(C.c_void_p(int(dev_out))))
+            return None
+        out = np.empty(shape, dtype=np.float32)
+        d = self.eng.device_alloc(out.nbytes)
+        try:
+            self.eng._check(call(C.c_void_p(d)))
+            self.eng.to_host(out, d)
+        finally:
+            self.eng.device_free(d)
+        return out
+
+    def weights(self, plan, field_index, best=False, dev_w_out=None):
+        """Plan `plan`'s current (or best) weights of field field_index: de-interleaved to dev_w_out (device pointer, asynchronous),
+        or, without one, returned as a float32 array of the field's [L][ny][nx] shape."""
+        shape = np.asarray(self.fields[field_index]._beam.spotWeights).shape
+        return self._fetch(lambda p: lib().rtd_planset_weights(self.eng._h, self._h, int(plan), int(field_index), int(bool(best)), p), shape, dev_w_out)
+
+    def dose(self, plan, dev_out=None):
+        """Plan `plan`'s dose volume (of the iterate that entered the last iteration): copied out of the interleaved volume to dev_out
+        (device pointer, the whole grid), or, without one, returned as a float32 [Z][Y][X] array."""
+        dims = self.objective.dims
+        return self._fetch(lambda p: lib().rtd_planset_dose(self.eng._h, self._h, int(plan), p), (dims[2], dims[1], dims[0]), dev_out)
+
+    def values(self):
+        """Waits; float64 [n_plans][1 + n_terms]: per plan the objective and its terms of the iterate that entered the last iteration."""
+        v = np.zeros((self.n_plans, 1 + self.n_terms), dtype=np.float64)
+        self.eng._check(lib().rtd_planset_values(self.eng._h, self._h, v.ctypes.data_as(C.POINTER(C.c_double))))
+        return v
+
+    def blend(self, coeffs, field_index, best=True, dev_w_out=None):
+        """The navigated plan's weights of field field_index: float32(sum_p coeffs[p] * float64(w_p)), p ascending, of the plans' best
+        (or current) weights; coeffs finite and >= 0, one per plan. To dev_w_out, or returned as an array."""
+        c = np.ascontiguousarray(coeffs, dtype=np.float64).reshape(-1)
+        if c.size != self.n_plans:
+            raise ValueError("one coefficient per plan")
+        shape = np.asarray(self.fields[field_index]._beam.spotWeights).shape
+        cp = c.ctypes.data_as(C.POINTER(C.c_double))
+        return self._fetch(lambda p: lib().rtd_planset_blend(self.eng._h, self._h, cp, int(field_index), int(bool(best)), p), shape, dev_w_out)
+
+    def destroy(self):
+        if self._h:
+            lib().rtd_planset_destroy(self.eng._h, self._h)
+            self._h = C.c_void_p()
+
+
 class Engine:
     """One rtd_handle: one GPU, one stream, resident CT and LUTs."""
 
@@ -1055,6 +1167,10 @@ class Engine:
 
     def create_optimizer(self, fields, objective, options=None):
         return Optimizer(self, fields, objective, options)
+
+    def create_planset(self, fields, objective, variants, options=None):
+        """rtd_planset_create: len(variants) plans on `fields` under variants of `objective` (PlanSet)."""
+        return PlanSet(self, fields, objective, variants, options)
 
     def create_robust_optimizer(self, scenario_fields, objective, mode, probabilities=None, options=None):
         """rtd_optimizer_create_robust: scenario_fields is a list of per-scenario field lists (scenario 0 the nominal one, every field
