@@ -10,12 +10,32 @@
 //   k_dijap_fill          every entry to the next free slot of its row (a cursor; the order inside a row is that of arrival) ...
 //   k_dijap_sort          ... and every row ordered by column: a row holds a column at most once, so the result is the same whatever
 //                         the arrival order was.
-// The products:
-//   k_dijap_apply<INIT>   kDijApGroup lanes per box row: lane t adds the row's entries t, t + G, t + 2G, ... in that order, the G lane
-//                         sums are added in a butterfly (lane distances G/2, ..., 1);
-//   k_dijap_apply_t       one wave per chunk of kDijApChunk consecutive entries of a column: lane t adds the chunk's entries t, t + 64,
-//                         ... in that order, the 64 lane sums are added in a butterfly (32, ..., 1) -> one partial sum per chunk;
-//   k_dijap_reduce_t      one wave per column: lane t adds the column's chunk sums t, t + 64, ... in that order, butterfly as above.
+// The products. The forward product and the second pass of the transposed one each have ONE body (dijApplyBody, dijReduceTBody) with A
+// accumulators per lane: A right-hand sides that lie plan-minor (element i of plan p at x[i * stride + p]) share every read of the
+// matrix. The first pass of the transposed product has one body for one right-hand side (dijApplyTBody); its plan-set form keeps its
+// own text in rtd_planset.hpp with the same order of a lane's entries and the same butterfly. The kernels:
+//   k_dijap_apply<INIT>   the forward body at A = 1: kDijApGroup lanes per box row, lane t adds the row's entries t, t + G, t + 2G, ... in
+//                         that order, the G lane sums are added in a butterfly (lane distances G/2, ..., 1);
+//   k_dijap_apply_t       dijApplyTBody: one wave per chunk of kDijApChunk consecutive entries of a column, lane t adds the chunk's
+//                         entries t, t + 64, ... in that order, the 64 lane sums are added in a butterfly (32, ..., 1) -> one partial
+//                         sum per chunk;
+//   k_dijap_reduce_t      the second pass at A = 1: one wave per column, lane t adds the column's chunk sums t, t + 64, ... in that
+//                         order, butterfly as above;
+//   k_dijap_*_batch       (rtd_robust.hpp) the same three bodies with the operands picked by scenario;
+//   k_ps_apply<A, VEC, INIT>, k_ps_reduce_t<A>   (rtd_planset.hpp) the two templated bodies themselves; k_ps_apply_t<A, VEC>: its own text.
+// A: the stride rounded up to 1, 2, 4, 8 or 16. VEC: the stride is A and the arrays are aligned to min(16, 4 A) bytes, so a gather is
+// vector loads; else any stride, scalar loads of the slots p < n_plans alone.
+//
+// The bodies are __forceinline__: inlined before anything simplifies them, a kernel compiles as if it held the text itself (left to
+// the inliner, the instances at A = 8 and 16 took more registers and the 16-plan products measured 3 % slower: DESIGN.md section 11).
+//
+// THE TREES DO NOT DEPEND ON A. A lane's sequential sum per plan is the sum of A = 1. The butterfly over L lanes is done per plan for
+// the distances m >= A; below that every step halves what a lane carries: at distance m the lane whose bit m is set keeps the upper m
+// of its 2 m sums, its partner the lower, and each adds what the other sends for the sums it keeps. A plain butterfly gives every lane
+// the same bits (float addition is commutative: a + b and b + a are one result), so the lane that keeps plan p's sum holds what lane
+// 0 holds at A = 1: (l + l^m) at every level, the same pairs. The lane ends with the sum of plan `lane mod A`. 15 shuffles instead of
+// 64 for 16 plans over a row's 16 lanes, and the store of a row's A sums is one coalesced store. (NaN results are NaN in both forms;
+// which operand's payload a NaN + NaN keeps is the one thing that may differ.)
 // Every product is rounded to float32 before it is added (-ffp-contract=off), and every order above follows from the matrix and the
 // two constants alone: the same inputs give the same bits. No float atomics.
 #pragma once
@@ -25,6 +45,7 @@ namespace rtd {
 constexpr int kDijApGroup = 16;       // lanes per row of k_dijap_apply (4 rows per wave; measured against 8 and 64)
 constexpr int kDijApChunk = 2048;     // entries per chunk of k_dijap_apply_t (32 per lane)
 constexpr int kDijApScanItems = 4096; // rows per block of the scan (256 threads x 16)
+template <int A> constexpr int kDijApUnroll = A == 1 ? 4 : 2;   // entries in flight per lane of the forward product with A accumulators
 
 struct DijBox { int x0, y0, z0, bw, bh, bd; };   // the voxels that have a row in the companion (x fastest inside the box)
 
@@ -35,11 +56,6 @@ __device__ inline long long dijBoxRow(int v, int nx, int ny, const DijBox& b) {
 __device__ inline size_t dijBoxVoxel(long long r, int nx, int ny, const DijBox& b) {
     const int x = b.x0 + (int)(r % b.bw), y = b.y0 + (int)((r / b.bw) % b.bh), z = b.z0 + (int)(r / ((long long)b.bw * b.bh));
     return ((size_t)z * ny + y) * nx + x;
-}
-
-__device__ inline float dijWaveSum(float v, int lanes) {   // butterfly over `lanes` neighbouring lanes: every lane ends with the same sum
-    for (int m = lanes / 2; m >= 1; m >>= 1) v += __shfl_xor(v, m);
-    return v;
 }
 
 // mm[0..2] = min (x, y, z), mm[3..5] = max (x, y, z) over the rows of the matrix (preset to INT_MAX / -1).
@@ -135,56 +151,135 @@ __global__ __launch_bounds__(256) void k_dijap_sort(const long long* __restrict_
     }
 }
 
-// Dij w over the box rows. INIT: every voxel of the box is written (its sum, +0 for a row without entries); else the sum is added
-// to the voxels whose rows have entries and no other voxel is touched.
-template <bool INIT>
-__global__ __launch_bounds__(256) void k_dijap_apply(const long long* __restrict__ rowPtr, const int* __restrict__ cCols, const float* __restrict__ cVals,
-                                                     const float* __restrict__ w, float* __restrict__ dose, int nx, int ny, DijBox box, long long nRows) {
+// x[q] = plan q's element `idx` of a plan-minor array (q < A). VEC: stride == A, vector loads (the pad slots are loaded and take part
+// in nothing that is stored); else the slots q < nPlans alone, the others +0.
+template <int A, bool VEC>
+__device__ inline void psLoad(const float* __restrict__ base, size_t idx, int stride, int nPlans, float (&x)[A]) {
+    if constexpr (!VEC) {
+        const float* p = base + idx * (size_t)stride;
+#pragma unroll
+        for (int q = 0; q < A; ++q) x[q] = q < nPlans ? p[q] : 0.0f;
+    } else if constexpr (A >= 4) {
+        const float4* p = reinterpret_cast<const float4*>(base + idx * A);
+#pragma unroll
+        for (int q = 0; q < A / 4; ++q) { const float4 t = p[q]; x[4 * q] = t.x; x[4 * q + 1] = t.y; x[4 * q + 2] = t.z; x[4 * q + 3] = t.w; }
+    } else if constexpr (A == 2) {
+        const float2 t = *reinterpret_cast<const float2*>(base + idx * 2);
+        x[0] = t.x; x[1] = t.y;
+    } else {
+        x[0] = base[idx];
+    }
+}
+
+// The butterfly over LANES neighbouring lanes of A sums per lane (above): returns the sum of plan `lane % A`.
+template <int A, int M, typename T>
+__device__ inline void psReduceStep(T (&a)[A], int lane) {   // the distances M, M / 2, ..., 1 (a template, so that every index is a constant)
+    if constexpr (M >= 1) {
+        if constexpr (M >= A) {
+#pragma unroll
+            for (int p = 0; p < A; ++p) a[p] += __shfl_xor(a[p], M);
+        } else {
+            const bool up = (lane & M) != 0;
+#pragma unroll
+            for (int i = 0; i < M; ++i) {
+                const T send = up ? a[i] : a[i + M], keep = up ? a[i + M] : a[i];
+                a[i] = keep + __shfl_xor(send, M);
+            }
+        }
+        psReduceStep<A, M / 2>(a, lane);
+    }
+}
+template <int A, int LANES, typename T>
+__device__ inline T psReduce(T (&a)[A], int lane) {
+    psReduceStep<A, LANES / 2>(a, lane);
+    return a[0];
+}
+
+// Dij w over the box rows, for the A plans of a plan-minor w. INIT: every voxel of the box is written (its sum, +0 for a row without
+// entries); else the sum is added to the voxels whose rows have entries and no other voxel is touched. Slot p >= nPlans of dose is
+// never written.
+template <int A, bool VEC, bool INIT>
+__device__ __forceinline__ void dijApplyBody(const long long* __restrict__ rowPtr, const int* __restrict__ cCols, const float* __restrict__ cVals,
+                                    const float* __restrict__ w, float* __restrict__ dose, int nx, int ny, const DijBox& box, long long nRows,
+                                    int stride, int nPlans) {
     const long long r = ((long long)blockIdx.x * 256 + threadIdx.x) / kDijApGroup;
     const int t = threadIdx.x % kDijApGroup;
     long long a = 0, n = 0;
     if (r < nRows) { a = rowPtr[r]; n = rowPtr[r + 1] - a; }
-    float acc = 0.0f;
-#pragma unroll 4
-    for (long long i = t; i < n; i += kDijApGroup) acc += cVals[a + i] * w[cCols[a + i]];
-    acc = dijWaveSum(acc, kDijApGroup);
-    if (r < nRows && t == 0 && (INIT || n > 0)) {
-        const size_t v = dijBoxVoxel(r, nx, ny, box);
-        dose[v] = INIT ? acc : dose[v] + acc;
+    float acc[A];
+#pragma unroll
+    for (int p = 0; p < A; ++p) acc[p] = 0.0f;
+#pragma unroll kDijApUnroll<A>
+    for (long long i = t; i < n; i += kDijApGroup) {
+        const float v = cVals[a + i];
+        float x[A];
+        psLoad<A, VEC>(w, (size_t)cCols[a + i], stride, nPlans, x);
+#pragma unroll
+        for (int p = 0; p < A; ++p) acc[p] += v * x[p];
+    }
+    const float s = psReduce<A, kDijApGroup>(acc, t);
+    if (r < nRows && t < A && t < nPlans && (INIT || n > 0)) {
+        const size_t at = dijBoxVoxel(r, nx, ny, box) * (size_t)stride + t;
+        dose[at] = INIT ? s : dose[at] + s;
     }
 }
+template <bool INIT>
+__global__ __launch_bounds__(256) void k_dijap_apply(const long long* __restrict__ rowPtr, const int* __restrict__ cCols, const float* __restrict__ cVals,
+                                                     const float* __restrict__ w, float* __restrict__ dose, int nx, int ny, DijBox box, long long nRows) {
+    dijApplyBody<1, true, INIT>(rowPtr, cCols, cVals, w, dose, nx, ny, box, nRows, 1, 1);
+}
 
-// Dij^T g, first pass: chunk c belongs to column chunkCol[c] and is that column's (c - chunkFirst[column])-th.
-__global__ __launch_bounds__(256) void k_dijap_apply_t(const long long* __restrict__ colPtr, const int* __restrict__ rows, const float* __restrict__ vals,
-                                                       const int* __restrict__ chunkCol, const int* __restrict__ chunkFirst, const float* __restrict__ g,
-                                                       float* __restrict__ partial, int nChunks) {
+// Dij^T g, first pass, for one right-hand side: chunk c belongs to column chunkCol[c] and is that column's (c - chunkFirst[column])-th.
+// The body of k_dijap_apply_t and k_dijap_apply_t_batch (rtd_robust.hpp). k_ps_apply_t<A, VEC> (rtd_planset.hpp) keeps a text of
+// its own with A accumulators: as an instance of one body with this one its instances at A = 8 and 16 ran 1 % slower (there).
+__device__ __forceinline__ void dijApplyTBody(const long long* __restrict__ colPtr, const int* __restrict__ rows, const float* __restrict__ vals,
+                                     const int* __restrict__ chunkCol, const int* __restrict__ chunkFirst, const float* __restrict__ g,
+                                     float* __restrict__ partial, int nChunks) {
     const int c = blockIdx.x * 4 + threadIdx.x / 64, lane = threadIdx.x % 64;
     if (c >= nChunks) return;
     const int j = chunkCol[c];
     const long long a = colPtr[j] + (long long)(c - chunkFirst[j]) * kDijApChunk, b = min(a + (long long)kDijApChunk, colPtr[j + 1]);
-    float acc = 0.0f;
+    float acc[1] = {0.0f};
 #pragma unroll 4
-    for (long long e = a + lane; e < b; e += 64) acc += vals[e] * g[rows[e]];
-    acc = dijWaveSum(acc, 64);
-    if (lane == 0) partial[c] = acc;
+    for (long long e = a + lane; e < b; e += 64) acc[0] += vals[e] * g[rows[e]];
+    const float s = psReduce<1, 64>(acc, lane);
+    if (lane == 0) partial[c] = s;
+}
+__global__ __launch_bounds__(256) void k_dijap_apply_t(const long long* __restrict__ colPtr, const int* __restrict__ rows, const float* __restrict__ vals,
+                                                       const int* __restrict__ chunkCol, const int* __restrict__ chunkFirst, const float* __restrict__ g,
+                                                       float* __restrict__ partial, int nChunks) {
+    dijApplyTBody(colPtr, rows, vals, chunkCol, chunkFirst, g, partial, nChunks);
 }
 
-// Second pass: the chunk sums of column j in chunk order; a column without entries gives +0.
-__global__ __launch_bounds__(256) void k_dijap_reduce_t(const int* __restrict__ chunkFirst, const float* __restrict__ partial, float* __restrict__ out,
-                                                        int nSpots) {
+// Second pass: the chunk sums of column j in chunk order -> out[j * stride + p] for p < nPlans; a column without entries gives +0.
+template <int A>
+__device__ __forceinline__ void dijReduceTBody(const int* __restrict__ chunkFirst, const float* __restrict__ partial, float* __restrict__ out, int nSpots,
+                                      int stride, int nPlans) {
     const int j = blockIdx.x * 4 + threadIdx.x / 64, lane = threadIdx.x % 64;
     if (j >= nSpots) return;
     const int a = chunkFirst[j], b = chunkFirst[j + 1];
-    float acc = 0.0f;
-    for (int c = a + lane; c < b; c += 64) acc += partial[c];
-    acc = dijWaveSum(acc, 64);
-    if (lane == 0) out[j] = acc;
+    float acc[A];
+#pragma unroll
+    for (int p = 0; p < A; ++p) acc[p] = 0.0f;
+    for (int c = a + lane; c < b; c += 64) {
+        float x[A];
+        psLoad<A, true>(partial, (size_t)c, A, A, x);
+#pragma unroll
+        for (int p = 0; p < A; ++p) acc[p] += x[p];
+    }
+    const float s = psReduce<A, 64>(acc, lane);
+    if (lane < A && lane < nPlans) out[(size_t)j * stride + lane] = s;
+}
+__global__ __launch_bounds__(256) void k_dijap_reduce_t(const int* __restrict__ chunkFirst, const float* __restrict__ partial, float* __restrict__ out,
+                                                        int nSpots) {
+    dijReduceTBody<1>(chunkFirst, partial, out, nSpots, 1, 1);
 }
 
-// Zeroes this thread's voxel of a row box: the body of k_opt_clear_box (rtd_optimize.hpp) and k_robust_clear_box (rtd_robust.hpp).
-__device__ inline void dijClearBoxVoxel(float* __restrict__ vol, int nx, int ny, const DijBox& box, long long nRows) {
-    const long long r = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (r < nRows) vol[dijBoxVoxel(r, nx, ny, box)] = 0.0f;
+// Zeroes this thread's cell of a row box in a volume of S plan-minor slots: the body of k_opt_clear_box (rtd_optimize.hpp),
+// k_robust_clear_box (rtd_robust.hpp), both with the constant S = 1, and k_ps_clear_box (rtd_planset.hpp).
+__device__ __forceinline__ void dijClearBoxVoxel(float* __restrict__ vol, int nx, int ny, const DijBox& box, long long nRows, int S) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i < nRows * S) vol[dijBoxVoxel(i / S, nx, ny, box) * (size_t)S + (size_t)(i % S)] = 0.0f;
 }
 
 }  // namespace rtd

@@ -10,6 +10,8 @@
 //   k_opt_step      one wave: the chunk results, the objective value and the state record -> this iteration's decisions (improved?
 //                   guard? alpha), the history entry;
 //   k_opt_update    per entry: w_best, w_prev, grad_prev and the projected step, or w = w_best under the guard.
+// The bodies of the last three (optPartialsBody<S>, optStepBody, optUpdateEntry) and objReduce serve S plans that lie plan-minor; the
+// kernels here are their instances for one plan, k_ps_partials / _step / _update / _obj_reduce (rtd_planset.hpp) those for a plan set.
 // float64 wherever something is summed (full rate on this part), no contraction (-ffp-contract=off), no atomics: every order follows
 // from the shapes of the inputs alone.
 #pragma once
@@ -35,7 +37,7 @@ struct OptState {
     int pad;
 };
 
-__device__ inline double optWaveSum(double v) {   // the float64 sibling of dijWaveSum over a whole wave
+__device__ inline double optWaveSum(double v) {   // the float64 butterfly over a whole wave (distances 32, ..., 1)
     for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m);
     return v;
 }
@@ -98,19 +100,20 @@ __global__ __launch_bounds__(256) void k_obj_eval(const int* __restrict__ uv, co
 }
 
 // One block: wave w takes the terms w, w + 4, ...; values[1 + t] = wn_t * sum, values[0] = their sum in term order. kEud: the value of
-// an EUD term is eud[3 t + 2] (k_eud_finish) instead; the sum in term order is the same.
+// an EUD term is eud[3 t + 2] (k_eud_finish) instead; the sum in term order is the same. S, p: the block sums and the terms lie
+// plan-minor at stride S and this is plan p (k_ps_obj_reduce, rtd_planset.hpp); a plain objective is S = 1, p = 0, as constants.
 template <bool kEud>
-__device__ inline void objReduce(const double* __restrict__ partial, int nBlocks, const ObjTerm* __restrict__ terms, int nTerms,
-                                 double* __restrict__ values, const double* __restrict__ eud) {
+__device__ __forceinline__ void objReduce(const double* __restrict__ partial, int nBlocks, const ObjTerm* __restrict__ terms, int nTerms,
+                                 double* __restrict__ values, const double* __restrict__ eud, int S, int p) {
     __shared__ double sh[kObjMaxTerms];
     const int lane = threadIdx.x % 64, wave = threadIdx.x / 64;
     for (int t = wave; t < nTerms; t += 4) {
         double acc = 0.0;
-        for (int b = lane; b < nBlocks; b += 64) acc += partial[(size_t)t * nBlocks + b];
+        for (int b = lane; b < nBlocks; b += 64) acc += partial[((size_t)t * nBlocks + b) * S + p];
         acc = optWaveSum(acc);
         if (lane == 0) {
-            double val = terms[t].wn * acc;
-            if (kEud && terms[t].kind >= RTD_OBJ_SQ_EUD) val = eud[3 * t + 2];
+            double val = terms[(size_t)t * S + p].wn * acc;
+            if (kEud && terms[(size_t)t * S + p].kind >= RTD_OBJ_SQ_EUD) val = eud[3 * t + 2];
             sh[t] = val; values[1 + t] = val;
         }
     }
@@ -123,46 +126,67 @@ __device__ inline void objReduce(const double* __restrict__ partial, int nBlocks
 }
 __global__ __launch_bounds__(256) void k_obj_reduce(const double* __restrict__ partial, int nBlocks, const ObjTerm* __restrict__ terms, int nTerms,
                                                     double* __restrict__ values) {
-    objReduce<false>(partial, nBlocks, terms, nTerms, values, nullptr);
+    objReduce<false>(partial, nBlocks, terms, nTerms, values, nullptr, 1, 0);
 }
 __global__ __launch_bounds__(256) void k_obj_reduce_eud(const double* __restrict__ partial, int nBlocks, const ObjTerm* __restrict__ terms, int nTerms,
                                                         double* __restrict__ values, const double* __restrict__ eud) {
-    objReduce<true>(partial, nBlocks, terms, nTerms, values, eud);
+    objReduce<true>(partial, nBlocks, terms, nTerms, values, eud, 1, 0);
 }
 
 // Zeroes the box's voxels of a volume (the row box of a field other than the first, in front of the forward product).
 __global__ __launch_bounds__(256) void k_opt_clear_box(float* __restrict__ vol, int nx, int ny, DijBox box, long long nRows) {
-    dijClearBoxVoxel(vol, nx, ny, box, nRows);
+    dijClearBoxVoxel(vol, nx, ny, box, nRows, 1);
 }
 
-// part[c], part[nCh + c], part[2 nCh + c] = <s, s>, <s, y>, max |P(w - grad) - w| over chunk c.
-__global__ __launch_bounds__(256) void k_opt_partials(const float* __restrict__ w, const float* __restrict__ wPrev, const float* __restrict__ grad,
-                                                      const float* __restrict__ gradPrev, int n, int nCh, double* __restrict__ part) {
+// One wave per chunk c of kOptChunk entries, S plans per entry (plan-minor, stride S, aligned; a plain optimiser is S = 1):
+// part[(k * nCh + c) * S + p], k = 0, 1, 2 for <s, s>, <s, y>, max |P(w - grad) - w| over the chunk in plan p.
+template <int S>
+__device__ __forceinline__ void optPartialsBody(const float* __restrict__ w, const float* __restrict__ wPrev, const float* __restrict__ grad,
+                                       const float* __restrict__ gradPrev, int n, int nCh, double* __restrict__ part) {
     const int c = blockIdx.x * 4 + threadIdx.x / 64, lane = threadIdx.x % 64;
     if (c >= nCh) return;
     const int a = c * kOptChunk, b = min(a + kOptChunk, n);
-    double ss = 0.0, sy = 0.0, mx = 0.0;
+    double ss[S], sy[S], mx[S];
+#pragma unroll
+    for (int p = 0; p < S; ++p) { ss[p] = 0.0; sy[p] = 0.0; mx[p] = 0.0; }
     for (int j = a + lane; j < b; j += 64) {
-        const double wj = (double)w[j], gj = (double)grad[j];
-        const double s = wj - (double)wPrev[j], y = gj - (double)gradPrev[j];
-        ss += s * s;
-        sy += s * y;
-        mx = fmax(mx, wj - gj < 0.0 ? fabs(wj) : fabs(gj));           // |P(w - grad) - w| without the cancellation: grad may be 1e-15 of w
+        float xw[S], xp[S], xg[S], xq[S];
+        psLoad<S, true>(w, (size_t)j, S, S, xw); psLoad<S, true>(wPrev, (size_t)j, S, S, xp);
+        psLoad<S, true>(grad, (size_t)j, S, S, xg); psLoad<S, true>(gradPrev, (size_t)j, S, S, xq);
+#pragma unroll
+        for (int p = 0; p < S; ++p) {
+            const double wj = (double)xw[p], gj = (double)xg[p];
+            const double s = wj - (double)xp[p], y = gj - (double)xq[p];
+            ss[p] += s * s;
+            sy[p] += s * y;
+            mx[p] = fmax(mx[p], wj - gj < 0.0 ? fabs(wj) : fabs(gj));   // |P(w - grad) - w| without the cancellation: grad may be 1e-15 of w
+        }
     }
-    ss = optWaveSum(ss); sy = optWaveSum(sy); mx = optWaveMax(mx);
-    if (lane == 0) { part[c] = ss; part[nCh + c] = sy; part[2 * nCh + c] = mx; }
+#pragma unroll
+    for (int p = 0; p < S; ++p) { ss[p] = optWaveSum(ss[p]); sy[p] = optWaveSum(sy[p]); mx[p] = optWaveMax(mx[p]); }
+    if (lane == 0) {
+#pragma unroll
+        for (int p = 0; p < S; ++p) { part[((size_t)c) * S + p] = ss[p]; part[((size_t)nCh + c) * S + p] = sy[p]; part[((size_t)2 * nCh + c) * S + p] = mx[p]; }
+    }
+}
+__global__ __launch_bounds__(256) void k_opt_partials(const float* __restrict__ w, const float* __restrict__ wPrev, const float* __restrict__ grad,
+                                                      const float* __restrict__ gradPrev, int n, int nCh, double* __restrict__ part) {
+    optPartialsBody<1>(w, wPrev, grad, gradPrev, n, nCh, part);
 }
 
-// One wave. Steps 2 (history), 4, 5 and 7 of the iteration as far as they are scalar; k_opt_update carries them out per entry.
-__global__ __launch_bounds__(64) void k_opt_step(const double* __restrict__ part, int nCh, const double* __restrict__ values, OptState* __restrict__ st,
-                                                 double* __restrict__ history, unsigned cap, double stepMin, double stepMax) {
+// One wave. Steps 2 (history), 4, 5 and 7 of the iteration as far as they are scalar; optUpdateEntry carries them out per entry. The
+// chunk results of plan p of S (a plain optimiser: p = 0 of 1), the plan's objective value, its state record and its history row.
+__device__ __forceinline__ void optStepBody(const double* __restrict__ part, int nCh, int S, int p, const double* __restrict__ value, OptState* __restrict__ st,
+                                   double* __restrict__ history, unsigned cap, double stepMin, double stepMax) {
     const int lane = threadIdx.x;
     double ss = 0.0, sy = 0.0, mx = 0.0;
-    for (int c = lane; c < nCh; c += 64) { ss += part[c]; sy += part[nCh + c]; mx = fmax(mx, part[2 * nCh + c]); }
+    for (int c = lane; c < nCh; c += 64) {
+        ss += part[(size_t)c * S + p]; sy += part[((size_t)nCh + c) * S + p]; mx = fmax(mx, part[((size_t)2 * nCh + c) * S + p]);
+    }
     ss = optWaveSum(ss); sy = optWaveSum(sy); mx = optWaveMax(mx);
     if (lane != 0) return;
     OptState s = *st;
-    const double f = values[0];
+    const double f = *value;
     if (s.iter < (long long)cap) history[s.iter] = f;
     s.fLast = f;
     s.improved = 0;
@@ -183,18 +207,26 @@ __global__ __launch_bounds__(64) void k_opt_step(const double* __restrict__ part
     ++s.iter;
     *st = s;
 }
+__global__ __launch_bounds__(64) void k_opt_step(const double* __restrict__ part, int nCh, const double* __restrict__ values, OptState* __restrict__ st,
+                                                 double* __restrict__ history, unsigned cap, double stepMin, double stepMax) {
+    optStepBody(part, nCh, 1, 0, values, st, history, cap, stepMin, stepMax);
+}
 
+// Entry i under the decisions of its plan's record.
+__device__ __forceinline__ void optUpdateEntry(const OptState* __restrict__ st, float* __restrict__ w, float* __restrict__ wPrev, const float* __restrict__ grad,
+                                      float* __restrict__ gradPrev, float* __restrict__ wBest, long long i) {
+    if (st->guard) { w[i] = wBest[i]; return; }
+    const float wj = w[i], gj = grad[i];
+    if (st->improved) wBest[i] = wj;
+    wPrev[i] = wj; gradPrev[i] = gj;
+    const float step = (float)st->alpha * gj;                         // (rounded before the subtraction)
+    const float d = wj - step;
+    w[i] = d > 0.0f ? d : 0.0f;                                       // P: negative, -0 and NaN (0 * inf) give +0
+}
 __global__ __launch_bounds__(256) void k_opt_update(const OptState* __restrict__ st, float* __restrict__ w, float* __restrict__ wPrev,
                                                     const float* __restrict__ grad, float* __restrict__ gradPrev, float* __restrict__ wBest, int n) {
     const int j = blockIdx.x * 256 + threadIdx.x;
-    if (j >= n) return;
-    if (st->guard) { w[j] = wBest[j]; return; }
-    const float wj = w[j], gj = grad[j];
-    if (st->improved) wBest[j] = wj;
-    wPrev[j] = wj; gradPrev[j] = gj;
-    const float step = (float)st->alpha * gj;                         // (rounded before the subtraction)
-    const float d = wj - step;
-    w[j] = d > 0.0f ? d : 0.0f;                                       // P: negative, -0 and NaN (0 * inf) give +0
+    if (j < n) optUpdateEntry(st, w, wPrev, grad, gradPrev, wBest, j);
 }
 
 }  // namespace rtd

@@ -40,7 +40,8 @@ struct rtd_optimizer_impl {
     struct rtd_rbe_impl* rbe = nullptr;
     DijBox rbeBox{0, 0, 0, 0, 0, 0};
     DevBuf<float> dRbeDose, dRbeG;
-    rtd_field_impl* sf(int s, size_t i) const { return sfields[(size_t)s * fields.size() + i]; }
+    rtd_field_impl* const* row(int s) const { return sfields.data() + (size_t)s * fields.size(); }
+    rtd_field_impl* sf(int s, size_t i) const { return row(s)[i]; }
     float* w() const { return dVec; }
     float* wPrev() const { return dVec + n; }
     float* grad() const { return dVec + 2 * (size_t)n; }
@@ -48,39 +49,29 @@ struct rtd_optimizer_impl {
     float* wBest() const { return dVec + 4 * (size_t)n; }
 };
 
-// The two products of an iteration, for one scenario (a plain optimiser is scenario 0). A matrix-free route (rtd_field_compute +
-// rtd_field_spot_gradient) would replace these two.
-// dose = sum_f Dij_f w_f, bit for bit "zero the volume, apply(init = 0) per field in list order": the row boxes of the fields 1..
+// The two products of an iteration over one row of fields (a scenario's; a plain optimiser has the one row), with the product named
+// by the caller: rtd_field_dose_influence_apply / _apply_t on a scenario's dose and voxel gradient, rtd_field_let_influence_apply /
+// _apply_t on dLetDose and dLetG (sections 22 and 23). A matrix-free route (rtd_field_compute + rtd_field_spot_gradient) would
+// replace these two.
+// vol = sum_f M_f w_f, bit for bit "zero the volume, apply(init = 0) per field in list order": the row boxes of the fields 1..
 // are cleared, field 0 then WRITES its whole box (init = 1: s or +0, and 0 + s = s since a sum is never -0), the others accumulate.
-int scenarioForward(rtd_handle hh, rtd_handle_impl* h, rtd_optimizer_impl* p, int s) {
+using FieldApply = int (*)(rtd_handle, rtd_field, const float*, float*, int);
+using FieldApplyT = int (*)(rtd_handle, rtd_field, const float*, float*);
+int fieldsForward(rtd_handle hh, rtd_handle_impl* h, rtd_optimizer_impl* p, rtd_field_impl* const* row, float* vol, FieldApply apply) {
     for (size_t i = 1; i < p->fields.size(); ++i) {
-        const rtd_field_impl* f = p->sf(s, i);
+        const rtd_field_impl* f = row[i];
         const long long nRows = (long long)f->dijRowsN;
-        if (nRows) k_opt_clear_box<<<(unsigned)((nRows + 255) / 256), 256, 0, h->stream>>>(p->doseS[s], (int)f->doseDims[0], (int)f->doseDims[1], f->dijBox, nRows);
+        if (nRows) k_opt_clear_box<<<(unsigned)((nRows + 255) / 256), 256, 0, h->stream>>>(vol, (int)f->doseDims[0], (int)f->doseDims[1], f->dijBox, nRows);
     }
     for (size_t i = 0; i < p->fields.size(); ++i) {
-        const int st = rtd_field_dose_influence_apply(hh, reinterpret_cast<rtd_field>(p->sf(s, i)), p->w() + p->offset[i], p->doseS[s], i == 0 ? 1 : 0);
+        const int st = apply(hh, reinterpret_cast<rtd_field>(row[i]), p->w() + p->offset[i], vol, i == 0 ? 1 : 0);
         if (st != RTD_OK) return st;
     }
     return RTD_OK;
 }
-// The same two products with the LET-weighted values of the fields (a plain optimiser with a LET objective): dLetDose = sum_f N_f w_f
-// formed the way scenarioForward forms the dose, dLetGrad[offset[i] ..] = N_i^T g_let.
-int letForward(rtd_handle hh, rtd_handle_impl* h, rtd_optimizer_impl* p) {
-    for (size_t i = 1; i < p->fields.size(); ++i) {
-        const rtd_field_impl* f = p->fields[i];
-        const long long nRows = (long long)f->dijRowsN;
-        if (nRows) k_opt_clear_box<<<(unsigned)((nRows + 255) / 256), 256, 0, h->stream>>>(p->dLetDose, (int)f->doseDims[0], (int)f->doseDims[1], f->dijBox, nRows);
-    }
+int fieldsAdjoint(rtd_handle hh, rtd_optimizer_impl* p, rtd_field_impl* const* row, const float* g, float* out, FieldApplyT applyT) {   // out[offset[i] ..] = M_i^T g
     for (size_t i = 0; i < p->fields.size(); ++i) {
-        const int st = rtd_field_let_influence_apply(hh, reinterpret_cast<rtd_field>(p->fields[i]), p->w() + p->offset[i], p->dLetDose, i == 0 ? 1 : 0);
-        if (st != RTD_OK) return st;
-    }
-    return RTD_OK;
-}
-int letAdjoint(rtd_handle hh, rtd_optimizer_impl* p) {
-    for (size_t i = 0; i < p->fields.size(); ++i) {
-        const int st = rtd_field_let_influence_apply_t(hh, reinterpret_cast<rtd_field>(p->fields[i]), p->dLetG, p->dLetGrad + p->offset[i]);
+        const int st = applyT(hh, reinterpret_cast<rtd_field>(row[i]), g, out + p->offset[i]);
         if (st != RTD_OK) return st;
     }
     return RTD_OK;
@@ -88,22 +79,15 @@ int letAdjoint(rtd_handle hh, rtd_optimizer_impl* p) {
 // R of the two volumes on rbeBox, and g_R back to dG and dLetG (rtd_rbe_host.hpp, included later).
 int rbeOptForward(rtd_handle_impl* h, rtd_optimizer_impl* p);
 int rbeOptBackward(rtd_handle_impl* h, rtd_optimizer_impl* p);
-int scenarioAdjoint(rtd_handle hh, rtd_optimizer_impl* p, int s, float* out) {   // out[offset[i] ..] = Dij_(s, i)^T g_s
-    for (size_t i = 0; i < p->fields.size(); ++i) {
-        const int st = rtd_field_dose_influence_apply_t(hh, reinterpret_cast<rtd_field>(p->sf(s, i)), p->gS[s], out + p->offset[i]);
-        if (st != RTD_OK) return st;
-    }
-    return RTD_OK;
-}
 
 // The same two products over the scenario axis (section 14; kernels in rtd_robust.hpp). Batched: per field position one launch covers
 // every scenario. Unbatched (RTD_ROBUST_NO_BATCH): the single-matrix launches, scenario by scenario. Either way scenario s's volume
-// gets what scenarioForward gives it, and gradS[s] what scenarioAdjoint gives it.
+// gets what fieldsForward gives it, and gradS[s] what fieldsAdjoint gives it.
 int robustForward(rtd_handle hh, rtd_handle_impl* h, rtd_optimizer_impl* p) {
     const size_t F = p->fields.size();
     const int S = p->nScen, nx = (int)p->fields[0]->doseDims[0], ny = (int)p->fields[0]->doseDims[1];
     if (!p->batch) {
-        for (int s = 0; s < S; ++s) { const int st = scenarioForward(hh, h, p, s); if (st != RTD_OK) return st; }
+        for (int s = 0; s < S; ++s) { const int st = fieldsForward(hh, h, p, p->row(s), p->doseS[s], rtd_field_dose_influence_apply); if (st != RTD_OK) return st; }
         return RTD_OK;
     }
     for (size_t i = 1; i < F; ++i) {
@@ -138,7 +122,10 @@ int robustAdjoint(rtd_handle hh, rtd_handle_impl* h, rtd_optimizer_impl* p) {
     const size_t F = p->fields.size();
     const int S = p->nScen;
     if (!p->batch) {   // no decision on the host: every scenario's product is taken, the combine uses those with lambda != 0
-        for (int s = 0; s < S; ++s) { const int st = scenarioAdjoint(hh, p, s, p->dGradS + (size_t)s * p->n); if (st != RTD_OK) return st; }
+        for (int s = 0; s < S; ++s) {
+            const int st = fieldsAdjoint(hh, p, p->row(s), p->gS[s], p->dGradS + (size_t)s * p->n, rtd_field_dose_influence_apply_t);
+            if (st != RTD_OK) return st;
+        }
         return RTD_OK;
     }
     for (size_t i = 0; i < F; ++i) {
@@ -162,6 +149,67 @@ int robustAdjoint(rtd_handle hh, rtd_handle_impl* h, rtd_optimizer_impl* p) {
     return RTD_OK;
 }
 
+// What rtd_optimizer_create* and rtd_planset_create ask alike, in three plain steps between which each caller places its own checks.
+// `who` is the entry point the messages name.
+// 1. The field count and the option bounds; *op gets the options (the defaults without opt).
+int optCheckOptions(rtd_handle_impl* h, const std::string& who, uint32_t n_fields, const rtd_optimizer_options* opt, rtd_optimizer_options* op) {
+    if (n_fields < 1 || n_fields > RTD_OPT_MAX_FIELDS) return fail(h, RTD_ERR_INVALID_ARG, who + ": 1 to 16 fields");
+    rtd_default_optimizer_options(op);
+    if (opt) *op = *opt;
+    if (!(op->step_min > 0.0) || !(op->step_max >= op->step_min) || !std::isfinite(op->step_max))
+        return fail(h, RTD_ERR_INVALID_ARG, who + ": needs 0 < step_min <= step_max < inf");
+    return RTD_OK;
+}
+// 2. One field: not null, not remote, on the objective's dose grid.
+int optCheckField(rtd_handle_impl* h, const std::string& who, const rtd_field_impl* f, const rtd_objective_impl* o) {
+    if (!f) return fail(h, RTD_ERR_INVALID_ARG, who + ": null field");
+    if (f->remote) return fail(h, RTD_ERR_INVALID_ARG, who + ": a remote field has no matrix");
+    for (int a = 0; a < 3; ++a)
+        if (f->doseDims[a] != o->dims[a]) return fail(h, RTD_ERR_INVALID_ARG, who + ": the fields and the objective must share one dose grid");
+    return RTD_OK;
+}
+// 3. Every one of the n_all fields (rows of n_fields) has a matrix; their companions and the objective are built; *offset gets the
+// spot-offset table of the first row.
+int optPrepare(rtd_handle hh, const std::string& who, const rtd_field* fields, uint32_t n_fields, uint32_t n_all, rtd_objective_impl* o, std::vector<int>* offset) {
+    auto* h = reinterpret_cast<rtd_handle_impl*>(hh);
+    for (uint32_t i = 0; i < n_all; ++i)
+        if (!reinterpret_cast<rtd_field_impl*>(fields[i])->dijDone)
+            return fail(h, RTD_ERR_NOT_READY, who + ": a field has no dose-influence matrix (call rtd_field_dose_influence first)");
+    RTD_HIP(h, hipSetDevice(h->device));
+    for (uint32_t i = 0; i < n_all; ++i) { const int st = rtd_field_dose_influence_prepare(hh, fields[i]); if (st != RTD_OK) return st; }
+    if (!o->built) { const int st = buildObjective(h, o); if (st != RTD_OK) return st; }
+    offset->assign(1, 0);
+    long long total = 0;
+    for (uint32_t i = 0; i < n_fields; ++i) {
+        const auto* f = reinterpret_cast<rtd_field_impl*>(fields[i]);
+        total += (long long)f->fc.spotNx * f->fc.spotNy * f->fc.L;
+        if (total > 0x7fffffffLL) return fail(h, RTD_ERR_INVALID_ARG, who + ": more than 2^31 - 1 spots");
+        offset->push_back((int)total);
+    }
+    return RTD_OK;
+}
+
+// What rtd_optimizer_result and rtd_planset_result report: the state record at dState, and of its history row (historyCapacity
+// entries long) what fits capacity. `whose` start weights the last message speaks of.
+int optReport(rtd_handle_impl* h, const char* who, const char* whose, const OptState* dState, const double* dHistoryRow, uint32_t historyCapacity,
+              rtd_optimizer_report* r, double* history, uint32_t capacity) {
+    RTD_HIP(h, hipSetDevice(h->device));
+    OptState st{};
+    RTD_HIP(h, hipMemcpyAsync(&st, dState, sizeof st, hipMemcpyDeviceToHost, h->stream));
+    RTD_HIP(h, hipStreamSynchronize(h->stream));
+    std::memset(r, 0, sizeof *r);
+    r->f_last = st.fLast; r->f_best = st.fBest; r->step = st.alpha; r->best_iteration = st.bestIter;
+    r->iterations = (uint32_t)st.iter; r->history_len = (uint32_t)std::min<long long>(st.iter, (long long)historyCapacity);
+    r->guarded = st.guarded;
+    const uint32_t cnt = std::min(capacity, r->history_len);
+    if (cnt) {
+        RTD_HIP(h, hipMemcpyAsync(history, dHistoryRow, cnt * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+        RTD_HIP(h, hipStreamSynchronize(h->stream));
+    }
+    if (st.startBad) return fail(h, RTD_ERR_INVALID_ARG, std::string(who) + ": the objective of " + whose + " is not finite");
+    return RTD_OK;
+}
+
 // rtd_optimizer_create (robust == nullptr: one scenario, nothing of section 14 allocated or launched), rtd_optimizer_create_robust and
 // rtd_optimizer_create_voxelwise (voxelwise: what a robust optimiser owns plus the word of active scenarios; robust->mode is not read).
 int optCreate(rtd_handle hh, const rtd_field* fields, uint32_t n_fields, const rtd_robust_options* robust, rtd_objective oo,
@@ -180,19 +228,15 @@ int optCreate(rtd_handle hh, const rtd_field* fields, uint32_t n_fields, const r
                 if (!(robust->probabilities[sc] > 0.0) || !std::isfinite(robust->probabilities[sc]))
                     return fail(h, RTD_ERR_INVALID_ARG, "rtd_optimizer_create_robust: a probability must be positive and finite");
     }
-    if (n_fields < 1 || n_fields > RTD_OPT_MAX_FIELDS) return fail(h, RTD_ERR_INVALID_ARG, "rtd_optimizer_create: 1 to 16 fields");
+    const std::string who = "rtd_optimizer_create";
     rtd_optimizer_options op;
-    rtd_default_optimizer_options(&op);
-    if (opt) op = *opt;
-    if (!(op.step_min > 0.0) || !(op.step_max >= op.step_min) || !std::isfinite(op.step_max))
-        return fail(h, RTD_ERR_INVALID_ARG, "rtd_optimizer_create: needs 0 < step_min <= step_max < inf");
+    int st = optCheckOptions(h, who, n_fields, opt, &op);
+    if (st != RTD_OK) return st;
     const uint32_t nAll = nScen * n_fields;
     for (uint32_t i = 0; i < nAll; ++i) {
-        auto* f = reinterpret_cast<rtd_field_impl*>(fields[i]);
-        if (!f) return fail(h, RTD_ERR_INVALID_ARG, "rtd_optimizer_create: null field");
-        if (f->remote) return fail(h, RTD_ERR_INVALID_ARG, "rtd_optimizer_create: a remote field has no matrix");
-        for (int a = 0; a < 3; ++a)
-            if (f->doseDims[a] != o->dims[a]) return fail(h, RTD_ERR_INVALID_ARG, "rtd_optimizer_create: the fields and the objective must share one dose grid");
+        const auto* f = reinterpret_cast<rtd_field_impl*>(fields[i]);
+        st = optCheckField(h, who, f, o);
+        if (st != RTD_OK) return st;
         if (robust) {
             const auto* f0 = reinterpret_cast<rtd_field_impl*>(fields[i % n_fields]);
             if (f0 && (f->fc.spotNx != f0->fc.spotNx || f->fc.spotNy != f0->fc.spotNy || f->fc.L != f0->fc.L))
@@ -204,29 +248,18 @@ int optCreate(rtd_handle hh, const rtd_field* fields, uint32_t n_fields, const r
     if (o->terms.empty()) return fail(h, RTD_ERR_INVALID_ARG, "rtd_optimizer_create: the objective has no terms");
     if (voxelwise && o->hasDvhTerms()) return fail(h, RTD_ERR_INVALID_ARG, "rtd_optimizer_create_voxelwise: an objective with DVH terms has no voxel-wise worst case");
     if (voxelwise && o->hasEudTerms()) return fail(h, RTD_ERR_INVALID_ARG, "rtd_optimizer_create_voxelwise: an objective with EUD terms has no voxel-wise worst case");
-    for (uint32_t i = 0; i < nAll; ++i)
-        if (!reinterpret_cast<rtd_field_impl*>(fields[i])->dijDone)
-            return fail(h, RTD_ERR_NOT_READY, "rtd_optimizer_create: a field has no dose-influence matrix (call rtd_field_dose_influence first)");
-    RTD_HIP(h, hipSetDevice(h->device));
-    for (uint32_t i = 0; i < nAll; ++i) { const int st = rtd_field_dose_influence_prepare(hh, fields[i]); if (st != RTD_OK) return st; }
-    if (!o->built) { const int st = buildObjective(h, o); if (st != RTD_OK) return st; }
+    std::vector<int> offset;
+    st = optPrepare(hh, who, fields, n_fields, nAll, o, &offset);
+    if (st != RTD_OK) return st;
     auto* p = new rtd_optimizer_impl();
-    p->obj = o; p->opt = op; p->nVox = o->nVox;
+    p->obj = o; p->opt = op; p->nVox = o->nVox; p->offset = offset;
     if (robust) {
         p->robust = true; p->nScen = (int)nScen; p->mode = robust->mode; p->voxelwise = voxelwise;
         p->batch = std::getenv("RTD_ROBUST_NO_BATCH") == nullptr;      // read once, here (the convention of the engine switches)
     }
     for (uint32_t i = 0; i < nAll; ++i) p->sfields.push_back(reinterpret_cast<rtd_field_impl*>(fields[i]));
-    p->offset.push_back(0);
-    long long total = 0;
-    for (uint32_t i = 0; i < n_fields; ++i) {
-        auto* f = reinterpret_cast<rtd_field_impl*>(fields[i]);
-        p->fields.push_back(f);
-        total += (long long)f->fc.spotNx * f->fc.spotNy * f->fc.L;
-        if (total > 0x7fffffffLL) { delete p; return fail(h, RTD_ERR_INVALID_ARG, "rtd_optimizer_create: more than 2^31 - 1 spots"); }
-        p->offset.push_back((int)total);
-    }
-    p->n = (int)total;
+    p->fields.assign(p->sfields.begin(), p->sfields.begin() + n_fields);
+    p->n = offset.back();
     p->nCh = (p->n + kOptChunk - 1) / kOptChunk;
     const size_t n = (size_t)p->n, cap = std::max<size_t>(op.history_capacity, 1);
     hipStream_t s = h->stream;
@@ -373,25 +406,30 @@ int rtd_optimizer_run(rtd_handle hh, rtd_optimizer pp, uint32_t n_iterations) {
                 return fail(h, RTD_ERR_NOT_READY, "rtd_optimizer_run: a field's LET-weighted matrix is not that of its matrix and the handle's table (call rtd_field_let_influence again)");
     RTD_HIP(h, hipSetDevice(h->device));
     hipStream_t s = h->stream;
+    // the products of a plain optimiser: its one row of fields with the dose matrices and with the LET-weighted ones
+    auto doseForward = [&] { return fieldsForward(hh, h, p, p->row(0), p->dDose, rtd_field_dose_influence_apply); };
+    auto doseAdjoint = [&] { return fieldsAdjoint(hh, p, p->row(0), p->dG, p->grad(), rtd_field_dose_influence_apply_t); };
+    auto letForward = [&] { return fieldsForward(hh, h, p, p->row(0), p->dLetDose, rtd_field_let_influence_apply); };
+    auto letAdjoint = [&] { return fieldsAdjoint(hh, p, p->row(0), p->dLetG, p->dLetGrad, rtd_field_let_influence_apply_t); };
     for (uint32_t k = 0; k < n_iterations; ++k) {
         int st = RTD_OK;
         if (p->rbe) {                         // section 23: the objective sees R(dose, LET-weighted dose); its gradient goes back through both products
-            st = scenarioForward(hh, h, p, 0);
-            if (st == RTD_OK) st = letForward(hh, h, p);
+            st = doseForward();
+            if (st == RTD_OK) st = letForward();
             if (st == RTD_OK) st = rbeOptForward(h, p);
             if (st == RTD_OK) st = evalObjective(h, p->obj, p->dRbeDose, p->dValues, p->dRbeG);
             if (st == RTD_OK) st = rbeOptBackward(h, p);
-            if (st == RTD_OK) st = scenarioAdjoint(hh, p, 0, p->grad());
-            if (st == RTD_OK) st = letAdjoint(hh, p);
+            if (st == RTD_OK) st = doseAdjoint();
+            if (st == RTD_OK) st = letAdjoint();
             if (st == RTD_OK) k_rbe_add<<<(unsigned)std::max((p->n + 255) / 256, 1), 256, 0, s>>>(p->grad(), (const float*)p->dLetGrad, p->n);
         } else if (!p->robust) {
-            st = scenarioForward(hh, h, p, 0);                                            // 1.
+            st = doseForward();                                                           // 1.
             if (st == RTD_OK) st = evalObjective(h, p->obj, p->dDose, p->dValues, p->dG); // 2.
-            if (st == RTD_OK) st = scenarioAdjoint(hh, p, 0, p->grad());                  // 3.
+            if (st == RTD_OK) st = doseAdjoint();                                         // 3.
             if (st == RTD_OK && p->letObj) {                                              // the same three on the LET-weighted dose; then f and grad are the sums
-                st = letForward(hh, h, p);
+                st = letForward();
                 if (st == RTD_OK) st = evalObjective(h, p->letObj, p->dLetDose, p->dLetValues, p->dLetG);
-                if (st == RTD_OK) st = letAdjoint(hh, p);
+                if (st == RTD_OK) st = letAdjoint();
                 if (st == RTD_OK)
                     k_let_add<<<(unsigned)std::max((p->n + 255) / 256, 1), 256, 0, s>>>(p->grad(), (const float*)p->dLetGrad, p->n, p->dValues,
                                                                                        (const double*)p->dLetValues, p->dLetValues + 1 + kObjMaxTerms);
@@ -428,21 +466,7 @@ int rtd_optimizer_result(rtd_handle hh, rtd_optimizer pp, rtd_optimizer_report* 
     auto* p = reinterpret_cast<rtd_optimizer_impl*>(pp);
     if (!h) return RTD_ERR_INVALID_ARG;
     if (!p || !r || (capacity && !history)) return fail(h, RTD_ERR_INVALID_ARG, "rtd_optimizer_result: null pointer");
-    RTD_HIP(h, hipSetDevice(h->device));
-    OptState st{};
-    RTD_HIP(h, hipMemcpyAsync(&st, p->dState, sizeof st, hipMemcpyDeviceToHost, h->stream));
-    RTD_HIP(h, hipStreamSynchronize(h->stream));
-    std::memset(r, 0, sizeof *r);
-    r->f_last = st.fLast; r->f_best = st.fBest; r->step = st.alpha; r->best_iteration = st.bestIter;
-    r->iterations = (uint32_t)st.iter; r->history_len = (uint32_t)std::min<long long>(st.iter, (long long)p->opt.history_capacity);
-    r->guarded = st.guarded;
-    const uint32_t cnt = std::min(capacity, r->history_len);
-    if (cnt) {
-        RTD_HIP(h, hipMemcpyAsync(history, p->dHistory, cnt * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-        RTD_HIP(h, hipStreamSynchronize(h->stream));
-    }
-    if (st.startBad) return fail(h, RTD_ERR_INVALID_ARG, "rtd_optimizer_result: the objective of the start weights is not finite");
-    return RTD_OK;
+    return optReport(h, "rtd_optimizer_result", "the start weights", p->dState, p->dHistory, p->opt.history_capacity, r, history, capacity);
 }
 
 int rtd_optimizer_weights(rtd_handle hh, rtd_optimizer pp, uint32_t field_index, float* dev_w_out, int best) {

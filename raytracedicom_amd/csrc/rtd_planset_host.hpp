@@ -150,19 +150,11 @@ int rtd_planset_create(rtd_handle hh, const rtd_field* fields, uint32_t n_fields
     if (!fields || !o || !variants || !out) return fail(h, RTD_ERR_INVALID_ARG, "rtd_planset_create: null pointer");
     *out = nullptr;
     if (n_plans < 1 || n_plans > (uint32_t)kPlansetMaxPlans) return fail(h, RTD_ERR_INVALID_ARG, "rtd_planset_create: 1 to RTD_PLANSET_MAX_PLANS plans");
-    if (n_fields < 1 || n_fields > RTD_OPT_MAX_FIELDS) return fail(h, RTD_ERR_INVALID_ARG, "rtd_planset_create: 1 to 16 fields");
+    const std::string who = "rtd_planset_create";
     rtd_optimizer_options op;
-    rtd_default_optimizer_options(&op);
-    if (opt) op = *opt;
-    if (!(op.step_min > 0.0) || !(op.step_max >= op.step_min) || !std::isfinite(op.step_max))
-        return fail(h, RTD_ERR_INVALID_ARG, "rtd_planset_create: needs 0 < step_min <= step_max < inf");
-    for (uint32_t i = 0; i < n_fields; ++i) {
-        auto* f = reinterpret_cast<rtd_field_impl*>(fields[i]);
-        if (!f) return fail(h, RTD_ERR_INVALID_ARG, "rtd_planset_create: null field");
-        if (f->remote) return fail(h, RTD_ERR_INVALID_ARG, "rtd_planset_create: a remote field has no matrix");
-        for (int a = 0; a < 3; ++a)
-            if (f->doseDims[a] != o->dims[a]) return fail(h, RTD_ERR_INVALID_ARG, "rtd_planset_create: the fields and the objective must share one dose grid");
-    }
+    int st = optCheckOptions(h, who, n_fields, opt, &op);
+    for (uint32_t i = 0; i < n_fields && st == RTD_OK; ++i) st = optCheckField(h, who, reinterpret_cast<rtd_field_impl*>(fields[i]), o);
+    if (st != RTD_OK) return st;
     if (o->terms.empty()) return fail(h, RTD_ERR_INVALID_ARG, "rtd_planset_create: the objective has no terms");
     if (o->hasDvhTerms() || o->hasEudTerms()) return fail(h, RTD_ERR_INVALID_ARG, "rtd_planset_create: an objective with DVH or EUD terms cannot be varied in a plan set");
     const size_t nTerms = o->terms.size();
@@ -174,29 +166,21 @@ int rtd_planset_create(rtd_handle hh, const rtd_field* fields, uint32_t n_fields
             if (!(v.weight > 0.0) || !std::isfinite(v.weight)) return fail(h, RTD_ERR_INVALID_ARG, "rtd_planset_create: a variant's weight must be positive and finite");
             if (!std::isfinite(v.dose_level)) return fail(h, RTD_ERR_INVALID_ARG, "rtd_planset_create: a variant's dose level must be finite");
         }
-    for (uint32_t i = 0; i < n_fields; ++i)
-        if (!reinterpret_cast<rtd_field_impl*>(fields[i])->dijDone)
-            return fail(h, RTD_ERR_NOT_READY, "rtd_planset_create: a field has no dose-influence matrix (call rtd_field_dose_influence first)");
-    RTD_HIP(h, hipSetDevice(h->device));
-    for (uint32_t i = 0; i < n_fields; ++i) { const int st = rtd_field_dose_influence_prepare(hh, fields[i]); if (st != RTD_OK) return st; }
-    if (!o->built) { const int st = buildObjective(h, o); if (st != RTD_OK) return st; }
+    std::vector<int> offset;
+    st = optPrepare(hh, who, fields, n_fields, n_fields, o, &offset);
+    if (st != RTD_OK) return st;
     auto* p = new rtd_planset_impl();
     p->obj = o; p->opt = op; p->nVox = o->nVox; p->nPlans = (int)n_plans; p->S = psAccum(n_plans); p->nTerms = (int)nTerms;
-    p->objEpoch = o->epoch; p->objBlocks = o->nBlocks;
-    p->offset.push_back(0);
-    long long total = 0;
+    p->objEpoch = o->epoch; p->objBlocks = o->nBlocks; p->offset = offset;
     size_t mostChunks = 1;
     for (uint32_t i = 0; i < n_fields; ++i) {
         auto* f = reinterpret_cast<rtd_field_impl*>(fields[i]);
         p->fields.push_back(f);
         p->epoch.push_back(f->dijEpoch);
-        total += (long long)f->fc.spotNx * f->fc.spotNy * f->fc.L;
-        if (total > 0x7fffffffLL) { delete p; return fail(h, RTD_ERR_INVALID_ARG, "rtd_planset_create: more than 2^31 - 1 spots"); }
-        p->offset.push_back((int)total);
         mostChunks = std::max(mostChunks, f->dijChunks);
     }
     p->atChunks = mostChunks;
-    p->n = (int)total;
+    p->n = offset.back();
     p->nCh = (p->n + kOptChunk - 1) / kOptChunk;
     p->cap = std::max<size_t>(op.history_capacity, 1);
     const size_t S = (size_t)p->S, n = (size_t)p->n, nValues = S * (1 + kObjMaxTerms);
@@ -276,7 +260,7 @@ int rtd_planset_run(rtd_handle hh, rtd_planset pp, uint32_t n_iterations) {
     const int S = p->S, nx = (int)o->dims[0], ny = (int)o->dims[1];
     const long long nS = (long long)p->n * S;
     for (uint32_t k = 0; k < n_iterations; ++k) {
-        for (size_t i = 1; i < p->fields.size(); ++i) {               // 1. as scenarioForward, for every plan at once
+        for (size_t i = 1; i < p->fields.size(); ++i) {               // 1. as fieldsForward, for every plan at once
             const rtd_field_impl* f = p->fields[i];
             const long long cells = (long long)f->dijRowsN * S;
             if (cells) k_ps_clear_box<<<(unsigned)((cells + 255) / 256), 256, 0, s>>>(p->dDose, nx, ny, f->dijBox, (long long)f->dijRowsN, S);
@@ -321,21 +305,8 @@ int rtd_planset_result(rtd_handle hh, rtd_planset pp, uint32_t plan, rtd_optimiz
     if (!h) return RTD_ERR_INVALID_ARG;
     if (!p || !r || (capacity && !history)) return fail(h, RTD_ERR_INVALID_ARG, "rtd_planset_result: null pointer");
     if (plan >= (uint32_t)p->nPlans) return fail(h, RTD_ERR_INVALID_ARG, "rtd_planset_result: plan index out of range");
-    RTD_HIP(h, hipSetDevice(h->device));
-    OptState st{};
-    RTD_HIP(h, hipMemcpyAsync(&st, p->dState + plan, sizeof st, hipMemcpyDeviceToHost, h->stream));
-    RTD_HIP(h, hipStreamSynchronize(h->stream));
-    std::memset(r, 0, sizeof *r);
-    r->f_last = st.fLast; r->f_best = st.fBest; r->step = st.alpha; r->best_iteration = st.bestIter;
-    r->iterations = (uint32_t)st.iter; r->history_len = (uint32_t)std::min<long long>(st.iter, (long long)p->opt.history_capacity);
-    r->guarded = st.guarded;
-    const uint32_t cnt = std::min(capacity, r->history_len);
-    if (cnt) {
-        RTD_HIP(h, hipMemcpyAsync(history, p->dHistory + (size_t)plan * p->cap, cnt * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-        RTD_HIP(h, hipStreamSynchronize(h->stream));
-    }
-    if (st.startBad) return fail(h, RTD_ERR_INVALID_ARG, "rtd_planset_result: the objective of the plan's start weights is not finite");
-    return RTD_OK;
+    return optReport(h, "rtd_planset_result", "the plan's start weights", p->dState + plan, p->dHistory + (size_t)plan * p->cap, p->opt.history_capacity, r,
+                     history, capacity);
 }
 
 int rtd_planset_weights(rtd_handle hh, rtd_planset pp, uint32_t plan, uint32_t field_index, int best, float* dev_w_out) {

@@ -11,8 +11,9 @@
 //   k_dijap_apply_t_batch    k_dijap_apply_t of position f for the scenarios with lambda != 0 (read from the record: no decision
 //   k_dijap_reduce_t_batch   on the host); the same for k_dijap_reduce_t;
 //   k_robust_combine         grad[j] = float32(sum over the scenarios with lambda != 0, ascending, of lambda_s * double(grad_s[j])).
-// Per output element the lane assignment, the order of the additions and the butterflies are those of the single-matrix kernels
-// (the bodies below are theirs with the operands indexed by scenario): the batched launches give the bits of the per-scenario calls.
+// The three products pick their scenario's operands, leave where the scenario has no work, and then run the one body of the product
+// (dijApplyBody and dijReduceTBody of rtd_dij_apply.hpp at A = 1, dijApplyTBody): the batched launches give the bits of the
+// per-scenario calls because they are the same code.
 #pragma once
 
 namespace rtd {
@@ -60,10 +61,10 @@ static_assert(sizeof(RobustFwd) + 64 <= 4096 && sizeof(RobustAdj) + 64 <= 4096, 
 
 __global__ __launch_bounds__(256) void k_robust_clear_box(RobustClear a, int nx, int ny) {
     const int s = blockIdx.y;
-    dijClearBoxVoxel(a.dose[s], nx, ny, a.box[s], a.nRows[s]);
+    dijClearBoxVoxel(a.dose[s], nx, ny, a.box[s], a.nRows[s], 1);
 }
 
-// k_dijap_apply<INIT> with blockIdx.y the scenario. A block past the scenario's rows leaves (uniform: its first row decides).
+// The forward body with blockIdx.y the scenario. A block past the scenario's rows leaves (uniform: its first row decides).
 template <bool INIT>
 __global__ __launch_bounds__(256) void k_dijap_apply_batch(RobustFwd a, const float* __restrict__ w, int nx, int ny) {
     const int s = blockIdx.y;
@@ -73,18 +74,7 @@ __global__ __launch_bounds__(256) void k_dijap_apply_batch(RobustFwd a, const fl
     const int* __restrict__ cCols = a.cCols[s];
     const float* __restrict__ cVals = a.cVals[s];
     float* __restrict__ dose = a.dose[s];
-    const long long r = ((long long)blockIdx.x * 256 + threadIdx.x) / kDijApGroup;
-    const int t = threadIdx.x % kDijApGroup;
-    long long e = 0, n = 0;
-    if (r < nRows) { e = rowPtr[r]; n = rowPtr[r + 1] - e; }
-    float acc = 0.0f;
-#pragma unroll 4
-    for (long long i = t; i < n; i += kDijApGroup) acc += cVals[e + i] * w[cCols[e + i]];
-    acc = dijWaveSum(acc, kDijApGroup);
-    if (r < nRows && t == 0 && (INIT || n > 0)) {
-        const size_t v = dijBoxVoxel(r, nx, ny, a.box[s]);
-        dose[v] = INIT ? acc : dose[v] + acc;
-    }
+    dijApplyBody<1, true, INIT>(rowPtr, cCols, cVals, w, dose, nx, ny, a.box[s], nRows, 1, 1);
 }
 
 // Step 3. mode 0 (EXPECTED): lambda_s = p_s, F = sum_s p_s f_s from 0.0 in ascending s. mode 1 (WORST_CASE): s* the lowest index that
@@ -110,38 +100,18 @@ __global__ __launch_bounds__(64) void k_robust_decide(const double* __restrict__
     values[0] = F;
 }
 
-// k_dijap_apply_t with blockIdx.y the scenario; a scenario without a share in the gradient does no work.
+// The transposed bodies with blockIdx.y the scenario; a scenario without a share in the gradient does no work.
 __global__ __launch_bounds__(256) void k_dijap_apply_t_batch(RobustAdj a, const RobustState* __restrict__ rs) {
     const int s = blockIdx.y;
     const int nChunks = a.nChunks[s];
     if ((int)blockIdx.x * 4 >= nChunks || rs->lambda[s] == 0.0) return;
-    const int c = blockIdx.x * 4 + threadIdx.x / 64, lane = threadIdx.x % 64;
-    if (c >= nChunks) return;
-    const long long* __restrict__ colPtr = a.colPtr[s];
-    const int* __restrict__ rows = a.rows[s];
-    const float* __restrict__ vals = a.vals[s];
-    const float* __restrict__ g = a.g[s];
-    const int j = a.chunkCol[s][c];
-    const long long e0 = colPtr[j] + (long long)(c - a.chunkFirst[s][j]) * kDijApChunk, e1 = min(e0 + (long long)kDijApChunk, colPtr[j + 1]);
-    float acc = 0.0f;
-#pragma unroll 4
-    for (long long e = e0 + lane; e < e1; e += 64) acc += vals[e] * g[rows[e]];
-    acc = dijWaveSum(acc, 64);
-    if (lane == 0) a.partial[s][c] = acc;
+    dijApplyTBody(a.colPtr[s], a.rows[s], a.vals[s], a.chunkCol[s], a.chunkFirst[s], a.g[s], a.partial[s], nChunks);
 }
 
 __global__ __launch_bounds__(256) void k_dijap_reduce_t_batch(RobustRed a, const RobustState* __restrict__ rs, int nSpots) {
     const int s = blockIdx.y;
     if (rs->lambda[s] == 0.0) return;
-    const int j = blockIdx.x * 4 + threadIdx.x / 64, lane = threadIdx.x % 64;
-    if (j >= nSpots) return;
-    const int* __restrict__ chunkFirst = a.chunkFirst[s];
-    const float* __restrict__ partial = a.partial[s];
-    const int c0 = chunkFirst[j], c1 = chunkFirst[j + 1];
-    float acc = 0.0f;
-    for (int c = c0 + lane; c < c1; c += 64) acc += partial[c];
-    acc = dijWaveSum(acc, 64);
-    if (lane == 0) a.out[s][j] = acc;
+    dijReduceTBody<1>(a.chunkFirst[s], a.partial[s], a.out[s], nSpots, 1, 1);
 }
 
 // Step 5. gradS: [nScen][n]. The sum starts from the first product (one scenario with lambda 1.0 hands its bits through, -0 included).
