@@ -40,14 +40,14 @@
 // two constants alone: the same inputs give the same bits. No float atomics.
 #pragma once
 
+#include "rtd_field_matrix.hpp"   // DijBox
+
 namespace rtd {
 
 constexpr int kDijApGroup = 16;       // lanes per row of k_dijap_apply (4 rows per wave; measured against 8 and 64)
 constexpr int kDijApChunk = 2048;     // entries per chunk of k_dijap_apply_t (32 per lane)
 constexpr int kDijApScanItems = 4096; // rows per block of the scan (256 threads x 16)
 template <int A> constexpr int kDijApUnroll = A == 1 ? 4 : 2;   // entries in flight per lane of the forward product with A accumulators
-
-struct DijBox { int x0, y0, z0, bw, bh, bd; };   // the voxels that have a row in the companion (x fastest inside the box)
 
 __device__ inline long long dijBoxRow(int v, int nx, int ny, const DijBox& b) {
     const int x = v % nx, y = (v / nx) % ny, z = v / (nx * ny);

@@ -1,26 +1,57 @@
 // rtd_dij_host.hpp — host side of a field's dose-influence matrix and of the products with it (include/rtd.h, DESIGN.md sections 10
 // and 11; kernels in rtd_dij.hpp and rtd_dij_apply.hpp). Part of rtd_engine.hip's translation unit, included at its end: the batches
-// run through its rtd_field_compute_bev and transferImpl. The matrix's buffers are the field's (classes kDij, kDijOut of its table).
+// run through its rtd_field_compute_bev and transferImpl. The matrix's buffers are the field's (classes kDij, kDijCsc, kDijCompanion
+// and kDijLet of its table); what exists of it and what it is valid for is f->matrix (rtd_field_matrix.hpp), which these files
+// tell what happened and ask what holds.
 #pragma once
 
 namespace {
 
+// The field's LET values are those of its matrix and of the handle's table as it stands.
+bool letReady(const rtd_handle_impl* h, const rtd_field_impl* f) { return f->matrix.letValid(h->dLetTable != nullptr, h->letTableNo); }
+
+// The opening of the matrix entry points, behind the handle and pointer tests of each: what the call needs of the field.
+//   kWorkspace   a field that is not remote                         (rtd_field_dose_influence)
+//   kMatrix      ... with a matrix
+//   kPrepared    ... with a matrix, prepared on demand (the first product of a matrix is synchronous that once)
+//   kLetValues   ... with LET values of the matrix and of the handle's table
+enum class MatrixStage { kWorkspace, kMatrix, kPrepared, kLetValues };
+// The refusals alone, `who` being the entry point the messages name: all that an entry point without launches asks.
+int matrixRefusal(rtd_handle_impl* h, const rtd_field_impl* f, const char* who_, MatrixStage need) {
+    auto who = [&] { return std::string(who_); };                      // (composed only for a refusal)
+    if (f->remote) return fail(h, RTD_ERR_INVALID_ARG, who() + ": a remote field has no workspace");
+    if (need == MatrixStage::kLetValues) {
+        if (!letReady(h, f)) return fail(h, RTD_ERR_NOT_READY, who() + ": no LET-weighted matrix of the current matrix and table (call rtd_field_let_influence first)");
+    } else if (need != MatrixStage::kWorkspace && !f->matrix.hasMatrix())
+        return fail(h, RTD_ERR_NOT_READY, who() + ": no dose-influence matrix (call rtd_field_dose_influence first)");
+    return RTD_OK;
+}
+// The refusals, the preparation, and the handle's device made current: a launch may follow.
+int matrixOpen(rtd_handle hh, rtd_field ff, const char* who, MatrixStage need) {
+    auto* h = reinterpret_cast<rtd_handle_impl*>(hh);
+    auto* f = reinterpret_cast<rtd_field_impl*>(ff);
+    { const int st = matrixRefusal(h, f, who, need); if (st != RTD_OK) return st; }
+    if (need == MatrixStage::kPrepared && !f->matrix.prepared()) { const int st = rtd_field_dose_influence_prepare(hh, ff); if (st != RTD_OK) return st; }
+    RTD_HIP(h, hipSetDevice(h->device));
+    return RTD_OK;
+}
+
 // The two products' launches with a values array of the matrix's structure: the dose's (rtd_field_dose_influence_apply / _apply_t) or
 // the LET-weighted one (rtd_let_host.hpp). cVals: the row-major companion's values; vals: the CSC's.
 int dijApplyLaunch(rtd_handle_impl* h, rtd_field_impl* f, const float* cVals, const float* dev_spot_weights, float* dev_dose, int init) {
-    const long long nRows = (long long)f->dijRowsN;
-    if (nRows == 0 || (!init && f->dijNnz == 0)) return RTD_OK;       // nothing to write: no launch
+    const long long nRows = (long long)f->matrix.rows();
+    if (nRows == 0 || (!init && f->matrix.nnz() == 0)) return RTD_OK; // nothing to write: no launch
     const unsigned g = (unsigned)((nRows * kDijApGroup + 255) / 256);
     auto launch = [&](auto kern) {
         kern<<<g, 256, 0, h->stream>>>((const long long*)f->dDijRowPtr, (const int*)f->dDijCCols, cVals, dev_spot_weights, dev_dose,
-                                       (int)f->doseDims[0], (int)f->doseDims[1], f->dijBox, nRows);
+                                       (int)f->doseDims[0], (int)f->doseDims[1], f->matrix.box(), nRows);
     };
     if (init) launch(k_dijap_apply<true>); else launch(k_dijap_apply<false>);
     RTD_HIP(h, hipGetLastError());
     return RTD_OK;
 }
 int dijApplyTLaunch(rtd_handle_impl* h, rtd_field_impl* f, const float* vals, const float* dev_voxel_weights, float* dev_spot_grad) {
-    const int nSpot = f->fc.spotNx * f->fc.spotNy * f->fc.L, nChunks = (int)f->dijChunks;
+    const int nSpot = f->fc.spotNx * f->fc.spotNy * f->fc.L, nChunks = (int)f->matrix.chunks();
     if (nChunks)
         k_dijap_apply_t<<<(unsigned)((nChunks + 3) / 4), 256, 0, h->stream>>>((const long long*)f->dDijColPtr, (const int*)f->dDijRows, vals,
                                                                             (const int*)f->dDijChunkCol, (const int*)f->dDijChunkFirst, dev_voxel_weights,
@@ -45,7 +76,7 @@ int rtd_field_dose_influence(rtd_handle hh, rtd_field ff, float rel_threshold, s
     if (!h || !f) return RTD_ERR_INVALID_ARG;
     if (!nnz) return fail(h, RTD_ERR_INVALID_ARG, "rtd_field_dose_influence: null nnz pointer");
     if (!(rel_threshold >= 0.0f && rel_threshold < 1.0f)) return fail(h, RTD_ERR_INVALID_ARG, "rtd_field_dose_influence: rel_threshold must lie in [0, 1)");
-    if (f->remote) return fail(h, RTD_ERR_INVALID_ARG, "rtd_field_dose_influence: a remote field has no workspace");
+    { const int st = matrixRefusal(h, f, "rtd_field_dose_influence", MatrixStage::kWorkspace); if (st != RTD_OK) return st; }
     if (f->fc.nuclearCorr) return fail(h, RTD_ERR_INVALID_ARG, "rtd_field_dose_influence: not available with nuclear_corr");
     if (f->fc.rayWeightCutoff != 0.0f)
         return fail(h, RTD_ERR_INVALID_ARG, "rtd_field_dose_influence: needs options.ray_weight_cutoff = 0 when the field is created (only then is the dose linear in the spot weights)");
@@ -56,12 +87,12 @@ int rtd_field_dose_influence(rtd_handle hh, rtd_field ff, float rel_threshold, s
     RTD_HIP(h, hipSetDevice(h->device));
     hipStream_t s = h->stream;
     const size_t nSpot = (size_t)fc.spotNx * fc.spotNy * fc.L;
-    f->dijDone = false; f->letDone = false;                           // (the LET values belong to the matrix that is replaced)
-    ++f->dijEpoch;                                                    // (and so does whatever a plan set sized for it)
+    FieldMatrix& m = f->matrix;
+    m.computeBegins();                                                // (the LET values and whatever a plan set sized belong to the matrix that is replaced)
     if (!f->dDijSave) {
-        f->dijCap = (size_t)1 << 20;
+        m.stagingSized((size_t)1 << 20);
         const int st = allocBuffers(h, f, kDij);
-        if (st != RTD_OK) { freeBuffers(f, kDij); f->dijCap = 0; return st; }
+        if (st != RTD_OK) { freeBuffers(f, kDij); m.stagingSized(0); return st; }
     }
     // 1. the forward at the field's own weights: Rmax, the entry plane, the field's findings
     { const int st = rtd_field_compute_bev(hh, ff); if (st != RTD_OK) return st; }
@@ -87,7 +118,7 @@ int rtd_field_dose_influence(rtd_handle hh, rtd_field ff, float rel_threshold, s
     std::vector<std::array<int, 4>> box(nSpot);
     std::vector<std::vector<uint64_t>> occ;
     std::vector<std::vector<int>> members;
-    f->dijBatchOf.assign(nSpot, -1);
+    std::vector<int> batchOf(nSpot, -1);                               // per spot: its batch (-1: empty column); the matrix's once it is finished
     auto meets = [&](const std::vector<uint64_t>& bm, const std::array<int, 4>& b) {
         for (int y = b[1]; y <= b[3]; ++y)
             for (int w = b[0] / 64; w <= b[2] / 64; ++w) {
@@ -110,7 +141,7 @@ int rtd_field_dose_influence(rtd_handle hh, rtd_field ff, float rel_threshold, s
         if (k == occ.size()) { occ.emplace_back((size_t)bevH * words, 0ull); members.emplace_back(); }
         for (int y = b[1]; y <= b[3]; ++y) for (int x = b[0]; x <= b[2]; ++x) occ[k][(size_t)y * words + x / 64] |= 1ull << (x % 64);
         members[k].push_back((int)j);
-        f->dijBatchOf[j] = (int)k;
+        batchOf[j] = (int)k;
     }
     occ.clear();
     std::vector<int> list, boxes;
@@ -175,8 +206,8 @@ int rtd_field_dose_influence(rtd_handle hh, rtd_field ff, float rel_threshold, s
         if (f->hState->errorFlags & kErrRecordExtent) {               // (reported as takeFindings reports it)
             h->error = "a layer's steps exceed the field's sigma and dose records (inputs modified in place?): the records and the trace are dropped, recompute"; st = RTD_ERR_NOT_READY; break;
         }
-        if ((size_t)(total + count) > f->dijCap) {                   // grow the batch-major staging geometrically (the stream is idle)
-            size_t cap = f->dijCap;
+        if ((size_t)(total + count) > m.stagingEntries()) {          // grow the batch-major staging geometrically (the stream is idle)
+            size_t cap = m.stagingEntries();
             while (cap < (size_t)(total + count)) cap *= 2;
             DevBuf<int> r; DevBuf<float> v;
             e = r.alloc(cap);
@@ -184,7 +215,7 @@ int rtd_field_dose_influence(rtd_handle hh, rtd_field ff, float rel_threshold, s
             if (e == hipSuccess) e = hipMemcpy(r, f->dDijRowsB, (size_t)total * sizeof(int), hipMemcpyDeviceToDevice);
             if (e == hipSuccess) e = hipMemcpy(v, f->dDijValsB, (size_t)total * sizeof(float), hipMemcpyDeviceToDevice);
             if (e != hipSuccess) { hipFail(e); break; }
-            std::swap(f->dDijRowsB, r.p); std::swap(f->dDijValsB, v.p); f->dijCap = cap;   // (r and v free the old staging)
+            std::swap(f->dDijRowsB, r.p); std::swap(f->dDijValsB, v.p); m.stagingSized(cap);   // (r and v free the old staging)
         }
         split(k_dij_split<2>);
         if ((e = hipGetLastError()) != hipSuccess) { hipFail(e); break; }
@@ -214,19 +245,19 @@ int rtd_field_dose_influence(rtd_handle hh, rtd_field ff, float rel_threshold, s
     // 6. CSC: column pointers on the host, the batch-major columns gathered into column order on the device
     std::vector<long long> colPtr(nSpot + 1, 0);
     for (size_t j = 0; j < nSpot; ++j) colPtr[j + 1] = colPtr[j] + colLen[j];
-    freeBuffers(f, kDijOut);                                          // (with it what rtd_field_dose_influence_prepare built)
-    f->dijPrepared = false; f->letAlloc = false;
-    { const FieldState& fin = *f->hState; for (int i = 0; i < 3; ++i) { f->dijOwnBox[i] = fin.tboxMin[i]; f->dijOwnBox[3 + i] = fin.tboxMax[i]; } }
-    f->dijNnz = (size_t)colPtr[nSpot];
-    { const int ast = allocBuffers(h, f, kDijOut); if (ast != RTD_OK) { freeBuffers(f, kDijOut); f->dijNnz = 0; return ast; } }
+    freeBuffers(f, kDijCsc | kDijCompanion | kDijLet);               // (with the old result what was built and computed from it)
+    const FieldState& fin = *f->hState;
+    const int ownBox[6] = {fin.tboxMin[0], fin.tboxMin[1], fin.tboxMin[2], fin.tboxMax[0], fin.tboxMax[1], fin.tboxMax[2]};
+    m.resultSized((size_t)colPtr[nSpot], ownBox);
+    { const int ast = allocBuffers(h, f, kDijCsc); if (ast != RTD_OK) { freeBuffers(f, kDijCsc); m.resultAllocationFailed(); return ast; } }
     RTD_HIP(h, hipMemcpyAsync(f->dDijColPtr, colPtr.data(), colPtr.size() * sizeof(long long), hipMemcpyHostToDevice, s));
-    if (f->dijNnz)
+    if (m.nnz())
         k_dij_gather<<<(unsigned)nSpot, 256, 0, s>>>((const long long*)f->dDijColPtr, (const long long*)f->dDijColSrc, (const int*)f->dDijRowsB,
                                                      (const float*)f->dDijValsB, f->dDijRows, f->dDijVals);
     RTD_HIP(h, hipGetLastError());
     RTD_HIP(h, hipStreamSynchronize(s));
-    f->dijDone = true;
-    *nnz = f->dijNnz;
+    m.computeFinished(std::move(batchOf));
+    *nnz = m.nnz();
     return RTD_OK;
 }
 
@@ -235,15 +266,17 @@ int rtd_field_dose_influence_copy(rtd_handle hh, rtd_field ff, int64_t* col_ptr,
     auto* h = reinterpret_cast<rtd_handle_impl*>(hh);
     auto* f = reinterpret_cast<rtd_field_impl*>(ff);
     if (!h || !f) return RTD_ERR_INVALID_ARG;
-    if (!f->dijDone) return fail(h, RTD_ERR_NOT_READY, "rtd_field_dose_influence_copy: no dose-influence matrix (call rtd_field_dose_influence first)");
-    if (!col_ptr || (f->dijNnz && (!row_idx || !values))) return fail(h, RTD_ERR_INVALID_ARG, "rtd_field_dose_influence_copy: null pointer");
+    // (its own opening: the matrix in front of the pointers, and a remote field is answered like any field without a matrix)
+    const size_t nnz = f->matrix.nnz();
+    if (!f->matrix.hasMatrix()) return fail(h, RTD_ERR_NOT_READY, "rtd_field_dose_influence_copy: no dose-influence matrix (call rtd_field_dose_influence first)");
+    if (!col_ptr || (nnz && (!row_idx || !values))) return fail(h, RTD_ERR_INVALID_ARG, "rtd_field_dose_influence_copy: null pointer");
     RTD_HIP(h, hipSetDevice(h->device));
     const size_t nSpot = (size_t)f->fc.spotNx * f->fc.spotNy * f->fc.L;
     hipStream_t s = h->stream;
     RTD_HIP(h, hipMemcpyAsync(col_ptr, f->dDijColPtr, (nSpot + 1) * sizeof(int64_t), hipMemcpyDefault, s));
-    if (f->dijNnz) {
-        RTD_HIP(h, hipMemcpyAsync(row_idx, f->dDijRows, f->dijNnz * sizeof(int32_t), hipMemcpyDefault, s));
-        RTD_HIP(h, hipMemcpyAsync(values, f->dDijVals, f->dijNnz * sizeof(float), hipMemcpyDefault, s));
+    if (nnz) {
+        RTD_HIP(h, hipMemcpyAsync(row_idx, f->dDijRows, nnz * sizeof(int32_t), hipMemcpyDefault, s));
+        RTD_HIP(h, hipMemcpyAsync(values, f->dDijVals, nnz * sizeof(float), hipMemcpyDefault, s));
     }
     RTD_HIP(h, hipStreamSynchronize(s));
     return RTD_OK;
@@ -255,9 +288,8 @@ int rtd_field_dose_influence_device(rtd_handle hh, rtd_field ff, const int64_t**
     auto* f = reinterpret_cast<rtd_field_impl*>(ff);
     if (!h || !f) return RTD_ERR_INVALID_ARG;
     if (!col_ptr || !row_idx || !values || !nnz) return fail(h, RTD_ERR_INVALID_ARG, "rtd_field_dose_influence_device: null pointer");
-    if (f->remote) return fail(h, RTD_ERR_INVALID_ARG, "rtd_field_dose_influence_device: a remote field has no workspace");
-    if (!f->dijDone) return fail(h, RTD_ERR_NOT_READY, "rtd_field_dose_influence_device: no dose-influence matrix (call rtd_field_dose_influence first)");
-    *col_ptr = reinterpret_cast<const int64_t*>(f->dDijColPtr); *row_idx = f->dDijRows; *values = f->dDijVals; *nnz = f->dijNnz;
+    { const int st = matrixRefusal(h, f, "rtd_field_dose_influence_device", MatrixStage::kMatrix); if (st != RTD_OK) return st; }
+    *col_ptr = reinterpret_cast<const int64_t*>(f->dDijColPtr); *row_idx = f->dDijRows; *values = f->dDijVals; *nnz = f->matrix.nnz();
     return RTD_OK;
 }
 
@@ -269,15 +301,15 @@ int rtd_field_dose_influence_prepare(rtd_handle hh, rtd_field ff) {
     auto* h = reinterpret_cast<rtd_handle_impl*>(hh);
     auto* f = reinterpret_cast<rtd_field_impl*>(ff);
     if (!h || !f) return RTD_ERR_INVALID_ARG;
-    if (f->remote) return fail(h, RTD_ERR_INVALID_ARG, "rtd_field_dose_influence_prepare: a remote field has no workspace");
-    if (!f->dijDone) return fail(h, RTD_ERR_NOT_READY, "rtd_field_dose_influence_prepare: no dose-influence matrix (call rtd_field_dose_influence first)");
-    if (f->dijPrepared) return RTD_OK;
+    { const int st = matrixRefusal(h, f, "rtd_field_dose_influence_prepare", MatrixStage::kMatrix); if (st != RTD_OK) return st; }
+    FieldMatrix& m = f->matrix;
+    if (m.prepared()) return RTD_OK;
     RTD_HIP(h, hipSetDevice(h->device));
     hipStream_t s = h->stream;
     const size_t nSpot = (size_t)f->fc.spotNx * f->fc.spotNy * f->fc.L;
-    const long long nnz = (long long)f->dijNnz;
+    const long long nnz = (long long)m.nnz();
     const int nx = (int)f->doseDims[0], ny = (int)f->doseDims[1];
-    if (nnz && (f->dijCap < f->dijNnz || !f->dDijRowsB || !f->dDijValsB))
+    if (nnz && (m.stagingEntries() < m.nnz() || !f->dDijRowsB || !f->dDijValsB))
         return fail(h, RTD_ERR_HIP, "rtd_field_dose_influence_prepare: internal error: the staging buffers are smaller than the matrix");
     // column pointers -> the chunks of the transposed product
     std::vector<long long> colPtr(nSpot + 1);
@@ -292,7 +324,7 @@ int rtd_field_dose_influence_prepare(rtd_handle hh, rtd_field ff) {
     }
     // the voxels that get a row: the field's dose box, grown (if need be) to hold every row of the matrix
     int lo[3], hi[3];
-    for (int i = 0; i < 3; ++i) { lo[i] = f->dijOwnBox[i]; hi[i] = f->dijOwnBox[3 + i]; }
+    for (int i = 0; i < 3; ++i) { lo[i] = m.ownBox()[i]; hi[i] = m.ownBox()[3 + i]; }
     if (hi[0] < lo[0] || hi[1] < lo[1] || hi[2] < lo[2]) for (int i = 0; i < 3; ++i) { lo[i] = 0x7fffffff; hi[i] = -1; }
     DevBuf<int> dTmp; DevBuf<long long> dBlockSum;                    // scratch: freed when this call returns, after done's synchronise
     hipError_t e = hipSuccess;
@@ -316,17 +348,9 @@ int rtd_field_dose_influence_prepare(rtd_handle hh, rtd_field ff) {
     DijBox box{0, 0, 0, 0, 0, 0};
     if (hi[0] >= lo[0]) box = DijBox{lo[0], lo[1], lo[2], hi[0] - lo[0] + 1, hi[1] - lo[1] + 1, hi[2] - lo[2] + 1};
     const long long nRows = (long long)box.bw * box.bh * box.bd;
-    f->dijBox = box; f->dijRowsN = (size_t)nRows; f->dijChunks = chunkCol.size();
-    f->dijPrepared = true;                                            // (the buffer table lists the companion from here on)
-    f->forEachBuffer([&](auto*& p, size_t n, BufClass c, bool, const char*) {
-        if (e == hipSuccess && c == kDijOut && n && !p) e = hipMalloc((void**)&p, n * sizeof *p);
-    });
-    auto undo = [&]() {   // the CSC stays; the companion goes
-        f->dijPrepared = false;
-        for (void** p : {(void**)&f->dDijRowPtr, (void**)&f->dDijCCols, (void**)&f->dDijCVals, (void**)&f->dDijChunkFirst, (void**)&f->dDijChunkCol,
-                         (void**)&f->dDijPartial})
-            if (*p) { (void)hipFree(*p); *p = nullptr; }
-    };
+    m.companionSized(box, (size_t)nRows, chunkCol.size());            // (the buffer table lists the companion from here on)
+    e = tryAllocBuffers(f, kDijCompanion);
+    auto undo = [&]() { m.companionFailed(); freeBuffers(f, kDijCompanion); };   // the CSC stays; the companion goes
     if (e == hipSuccess) e = hipMemcpyAsync(f->dDijChunkFirst, chunkFirst.data(), chunkFirst.size() * sizeof(int), hipMemcpyHostToDevice, s);
     if (e == hipSuccess && !chunkCol.empty()) e = hipMemcpyAsync(f->dDijChunkCol, chunkCol.data(), chunkCol.size() * sizeof(int), hipMemcpyHostToDevice, s);
     if (e == hipSuccess && !nnz) e = hipMemsetAsync(f->dDijRowPtr, 0, (size_t)(nRows + 1) * sizeof(long long), s);
@@ -363,10 +387,7 @@ int rtd_field_dose_influence_apply(rtd_handle hh, rtd_field ff, const float* dev
     auto* f = reinterpret_cast<rtd_field_impl*>(ff);
     if (!h || !f) return RTD_ERR_INVALID_ARG;
     if (!dev_spot_weights || !dev_dose) return fail(h, RTD_ERR_INVALID_ARG, "rtd_field_dose_influence_apply: null device pointer");
-    if (f->remote) return fail(h, RTD_ERR_INVALID_ARG, "rtd_field_dose_influence_apply: a remote field has no workspace");
-    if (!f->dijDone) return fail(h, RTD_ERR_NOT_READY, "rtd_field_dose_influence_apply: no dose-influence matrix (call rtd_field_dose_influence first)");
-    if (!f->dijPrepared) { const int st = rtd_field_dose_influence_prepare(hh, ff); if (st != RTD_OK) return st; }
-    RTD_HIP(h, hipSetDevice(h->device));
+    { const int st = matrixOpen(hh, ff, "rtd_field_dose_influence_apply", MatrixStage::kPrepared); if (st != RTD_OK) return st; }
     return dijApplyLaunch(h, f, f->dDijCVals, dev_spot_weights, dev_dose, init);
 }
 
@@ -376,10 +397,7 @@ int rtd_field_dose_influence_apply_t(rtd_handle hh, rtd_field ff, const float* d
     auto* f = reinterpret_cast<rtd_field_impl*>(ff);
     if (!h || !f) return RTD_ERR_INVALID_ARG;
     if (!dev_voxel_weights || !dev_spot_grad) return fail(h, RTD_ERR_INVALID_ARG, "rtd_field_dose_influence_apply_t: null device pointer");
-    if (f->remote) return fail(h, RTD_ERR_INVALID_ARG, "rtd_field_dose_influence_apply_t: a remote field has no workspace");
-    if (!f->dijDone) return fail(h, RTD_ERR_NOT_READY, "rtd_field_dose_influence_apply_t: no dose-influence matrix (call rtd_field_dose_influence first)");
-    if (!f->dijPrepared) { const int st = rtd_field_dose_influence_prepare(hh, ff); if (st != RTD_OK) return st; }
-    RTD_HIP(h, hipSetDevice(h->device));
+    { const int st = matrixOpen(hh, ff, "rtd_field_dose_influence_apply_t", MatrixStage::kPrepared); if (st != RTD_OK) return st; }
     return dijApplyTLaunch(h, f, f->dDijVals, dev_voxel_weights, dev_spot_grad);
 }
 

@@ -54,6 +54,7 @@
 #include "rtd_rbe.hpp"
 #include "rtd_planset.hpp"
 #include "rtd_field_memory.hpp"
+#include "rtd_field_matrix.hpp"
 #include "rtd_engine_impl.hpp"
 
 namespace {
@@ -431,11 +432,10 @@ int rtd_field_release(rtd_handle hh, rtd_field ff) {
     // The next owner of the workspace is a new field object, and this one is deleted when it takes over: nothing carries over, and
     // nothing in between reads these. They make a call on the stale field handle answer "not computed" instead of using freed buffers.
     f->computed = false; f->transferred = false;
-    freeBuffers(f, kGradient | kDiag | kDij | kDijOut | kTarget | kSigmaRec);   // (not part of the shape's workspace)
+    freeBuffers(f, kGradient | kDiag | kDij | kDijCsc | kDijCompanion | kDijLet | kTarget | kSigmaRec);   // (not part of the shape's workspace)
     f->memory = FieldMemory{};
     f->gradDone = false; f->targetProjected = false; f->targetSelected = false;
-    f->dijDone = false; f->dijPrepared = false; f->dijCap = 0; f->dijNnz = 0; f->dijBatchOf.clear();
-    f->letAlloc = false; f->letDone = false;
+    f->matrix.released();
     f->released = shapeCounts(f);
     h->fieldCache.push_back(f);
     return RTD_OK;
@@ -1341,9 +1341,9 @@ int rtd_field_fetch(rtd_handle hh, rtd_field ff, const char* name, void* host_ou
     if (found) {
         if (nm == "tile_radius") n = L * S * tiles;   // (the allocation is rounded up to whole 32-bit words)
     } else if (nm == "dij_batch") {
-        if (!f->dijDone) return fail(h, RTD_ERR_NOT_READY, "rtd_field_fetch: no dose-influence matrix");
-        n = f->dijBatchOf.size() * sizeof(int); staging.resize(std::max<size_t>(n, 1));
-        std::memcpy(staging.data(), f->dijBatchOf.data(), n);
+        if (!f->matrix.hasMatrix()) return fail(h, RTD_ERR_NOT_READY, "rtd_field_fetch: no dose-influence matrix");
+        n = f->matrix.batchOf().size() * sizeof(int); staging.resize(std::max<size_t>(n, 1));
+        std::memcpy(staging.data(), f->matrix.batchOf().data(), n);
     } else if (nm == "trace_reused") {
         const int32_t v = f->computed && f->memory.flight.reuse ? 1 : 0;   // the last launched compute left out the tracer, the scan and the plan
         n = sizeof v; staging.resize(n);

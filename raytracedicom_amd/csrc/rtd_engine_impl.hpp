@@ -51,10 +51,10 @@ struct rtd_handle_impl {
     bool warpTTimed = false;
     bool warpTPlain = false;                       // RTD_WARP_T_PLAIN in the environment when the handle was made: the scatter without the LDS tile
     // rtd_set_let_table (rtd_let_host.hpp): an allocation of its own, [letEnergies][letSamples]; not an input of the dose (no epoch of
-    // the above moves with it). letEpoch counts the tables set: a field's LET values belong to the table they were made from.
+    // the above moves with it). letTableNo counts the tables set: a field's LET values belong to the table they were made from.
     float* dLetTable = nullptr;
     int letEnergies = 0, letSamples = 0;
-    unsigned letEpoch = 0;
+    unsigned letTableNo = 0;
     // rtd_field_dose_influence_apply_t_set (rtd_planset_host.hpp): the chunk sums [chunk][accumulators] of the largest call so far; the
     // blocks it outgrew stay until rtd_destroy (psHandleScratch)
     std::vector<float*> setScratch;
@@ -91,10 +91,12 @@ Switches readSwitches() {
 
 // Classes of a field's device buffers: the workspace that a field of the same shape takes over (rtd_field_release), the NUCLEAR_CORR
 // halo, the spot-weight gradient's (allocated by its first call), the RTD_*_DEBUG clock stamps, the dose-influence matrix's workspace
-// and its result (rtd_field_dose_influence: allocated by its first call, the result replaced by every call; the result's class also
-// holds what rtd_field_dose_influence_prepare builds from it, so that the two are freed together), the target in beam's-eye view
-// (rtd_field_project_target: allocated by its first call), the sigma record (allocated by the first compute that reuses the trace).
-enum BufClass : unsigned { kShape = 1, kNuclear = 2, kGradient = 4, kDiag = 8, kDij = 16, kDijOut = 32, kTarget = 64, kSigmaRec = 128, kAllBufs = 255 };
+// (rtd_field_dose_influence: allocated by its first call) and its CSC result (replaced by every call), the target in beam's-eye view
+// (rtd_field_project_target: allocated by its first call), the sigma record (allocated by the first compute that reuses the trace),
+// and what hangs on the CSC result, each with a life of its own: the companion (rtd_field_dose_influence_prepare) and the LET values
+// (rtd_field_let_influence). A class is what is allocated together and dies together; the three of the result go when it is replaced.
+enum BufClass : unsigned { kShape = 1, kNuclear = 2, kGradient = 4, kDiag = 8, kDij = 16, kDijCsc = 32, kTarget = 64, kSigmaRec = 128,
+                           kDijCompanion = 256, kDijLet = 512, kAllBufs = 1023 };
 
 // A field's events: the start of a compute's first launch, the ends of its stages, the end of the transfer, and the start of the
 // superposition's first launch. kEvTrace is not recorded by a compute that reused the trace, kEvKsPlan not by one whose sweep launch
@@ -177,30 +179,21 @@ struct rtd_field_impl {
     float4* dAdjWalk = nullptr;   // [chunk][L][H][W] the dose walk's state in front of every chunk of k_adj_superpose
     bool gradDone = false;        // a gradient has been launched: grad_bev / grad_ray_weights hold the last one's intermediates
     // dose-influence matrix (rtd_field_dose_influence, rtd_dij.hpp): workspace allocated by the first call; the batch-major staging
-    // (dijCap entries) grows geometrically; the CSC result (dijNnz entries) is replaced by every call
+    // grows geometrically; the CSC result is replaced by every call. What exists of it, what it is valid for and every element count
+    // below: rtd_field_matrix.hpp.
+    FieldMatrix matrix;
     float *dDijSave = nullptr, *dDijDose = nullptr, *dDijValsB = nullptr, *dDijVals = nullptr;
     unsigned short* dDijOwner = nullptr;
     int *dDijFoot = nullptr, *dDijList = nullptr, *dDijBoxes = nullptr, *dDijCnt = nullptr, *dDijMisc = nullptr, *dDijRowsB = nullptr, *dDijRows = nullptr;
     unsigned int* dDijColMax = nullptr;
     long long *dDijColLen = nullptr, *dDijColSrc = nullptr, *dDijColPtr = nullptr;
-    size_t dijCap = 0, dijNnz = 0;
-    bool dijDone = false;          // the CSC buffers hold the last call's result
-    unsigned dijEpoch = 0;         // counts the rtd_field_dose_influence calls: what was sized for a matrix (a plan set) knows it by this number
-    std::vector<int> dijBatchOf;   // per spot: its batch in the last call (-1: empty column); rtd_field_fetch "dij_batch"
     // products with the matrix (rtd_field_dose_influence_prepare / _apply / _apply_t, rtd_dij_apply.hpp): the row-major companion over the
-    // voxels of dijBox (row pointers, columns ascending within a row, values) and the column chunks of the transposed product
+    // voxels of matrix.box() (row pointers, columns ascending within a row, values) and the column chunks of the transposed product
     long long* dDijRowPtr = nullptr; int* dDijCCols = nullptr; float* dDijCVals = nullptr;
     int *dDijChunkFirst = nullptr, *dDijChunkCol = nullptr; float* dDijPartial = nullptr;
-    bool dijPrepared = false;      // the buffers above exist and belong to the CSC result
-    int dijOwnBox[6] = {0, 0, 0, -1, -1, -1};   // the field's dose box (min, max) when the matrix was computed
-    DijBox dijBox{};               // ... united with the bounding box of the matrix's rows: the voxels that have a row
-    size_t dijRowsN = 0, dijChunks = 0;
     // the LET-weighted values on the matrix's structure (rtd_field_let_influence, rtd_let.hpp): a second values array for the CSC, one
-    // for the row-major companion, and the water-equivalent depth of the voxels of dijBox. With the matrix's result (class kDijOut).
+    // for the row-major companion, and the water-equivalent depth of the voxels of matrix.box()
     float *dLetVals = nullptr, *dLetCVals = nullptr, *dLetDepth = nullptr;
-    bool letAlloc = false;         // the buffer table lists the three
-    bool letDone = false;          // ... and they hold the values of the CSC result under the handle's table number letEpoch
-    unsigned letEpoch = 0;
     // the target in beam's-eye view (rtd_field_project_target / rtd_field_select_spots, rtd_target.hpp): allocated by the first projection
     unsigned int* dTargetBev = nullptr;      // [ceil(S / 32)][H][W] bit k & 31 of word k >> 5: sample (ray, step k) lies in the target
     unsigned char* dTargetHit = nullptr;     // [L][H][W] the layer hits of the last selection
@@ -254,17 +247,15 @@ struct rtd_field_impl {
         visit(dDijList, nSpot, kDij, false, nullptr); visit(dDijBoxes, 4 * nSpot, kDij, false, nullptr);
         visit(dDijCnt, (size_t)kDijBlocks * dijSpots, kDij, false, nullptr); visit(dDijColMax, dijSpots, kDij, false, nullptr);
         visit(dDijMisc, (size_t)4, kDij, true, nullptr); visit(dDijColLen, nSpot, kDij, false, nullptr); visit(dDijColSrc, nSpot, kDij, false, nullptr);
-        visit(dDijRowsB, dijCap, kDij, false, nullptr); visit(dDijValsB, dijCap, kDij, false, nullptr);
-        visit(dDijColPtr, nSpot + 1, kDijOut, false, nullptr); visit(dDijRows, std::max<size_t>(dijNnz, 1), kDijOut, false, nullptr);
-        visit(dDijVals, std::max<size_t>(dijNnz, 1), kDijOut, false, nullptr);
-        const size_t ap = dijPrepared ? 1 : 0;   // (only after rtd_field_dose_influence_prepare)
-        visit(dDijRowPtr, ap * (dijRowsN + 1), kDijOut, false, nullptr); visit(dDijCCols, ap * std::max<size_t>(dijNnz, 1), kDijOut, false, nullptr);
-        visit(dDijCVals, ap * std::max<size_t>(dijNnz, 1), kDijOut, false, nullptr); visit(dDijChunkFirst, ap * (nSpot + 1), kDijOut, false, nullptr);
-        visit(dDijChunkCol, ap * std::max<size_t>(dijChunks, 1), kDijOut, false, nullptr);
-        visit(dDijPartial, ap * std::max<size_t>(dijChunks, 1), kDijOut, false, nullptr);
-        const size_t lt = letAlloc ? 1 : 0;      // (only after rtd_field_let_influence)
-        visit(dLetVals, lt * std::max<size_t>(dijNnz, 1), kDijOut, false, nullptr); visit(dLetCVals, lt * std::max<size_t>(dijNnz, 1), kDijOut, false, nullptr);
-        visit(dLetDepth, lt * std::max<size_t>(dijRowsN, 1), kDijOut, false, nullptr);
+        visit(dDijRowsB, matrix.stagingEntries(), kDij, false, nullptr); visit(dDijValsB, matrix.stagingEntries(), kDij, false, nullptr);
+        visit(dDijColPtr, nSpot + 1, kDijCsc, false, nullptr); visit(dDijRows, matrix.resultEntries(), kDijCsc, false, nullptr);
+        visit(dDijVals, matrix.resultEntries(), kDijCsc, false, nullptr);
+        visit(dDijRowPtr, matrix.companionRowPtrs(), kDijCompanion, false, nullptr); visit(dDijCCols, matrix.companionEntries(), kDijCompanion, false, nullptr);
+        visit(dDijCVals, matrix.companionEntries(), kDijCompanion, false, nullptr);
+        visit(dDijChunkFirst, matrix.companionChunkFirsts(nSpot), kDijCompanion, false, nullptr);
+        visit(dDijChunkCol, matrix.companionChunks(), kDijCompanion, false, nullptr); visit(dDijPartial, matrix.companionChunks(), kDijCompanion, false, nullptr);
+        visit(dLetVals, matrix.letEntries(), kDijLet, false, nullptr); visit(dLetCVals, matrix.letEntries(), kDijLet, false, nullptr);
+        visit(dLetDepth, matrix.letDepths(), kDijLet, false, nullptr);
         visit(dTargetBev, ((S + 31) / 32) * R, kTarget, false, "target_bev"); visit(dTargetHit, L * R, kTarget, false, "target_hit");
         visit(dTargetSum, (size_t)1, kTarget, false, nullptr); visit(dTargetCount, (size_t)1, kTarget, false, nullptr);
         visit(dSigRec, memory.sigmaSteps * R * L, kSigmaRec, false, nullptr); visit(dSigRecLast, memory.sigmaSteps ? R * L : (size_t)0, kSigmaRec, false, nullptr);
@@ -306,14 +297,18 @@ struct DevBuf {
 };
 
 // Allocates the field's buffers of the given classes (clearing those marked so); after a failure the caller frees them.
-int allocBuffers(rtd_handle_impl* h, rtd_field_impl* f, unsigned classes) {
+// tryAllocBuffers: the HIP error itself, for a caller that words its own message.
+hipError_t tryAllocBuffers(rtd_field_impl* f, unsigned classes) {
     hipError_t e = hipSuccess;
     f->forEachBuffer([&](auto*& p, size_t n, BufClass c, bool clear, const char*) {
         if (e != hipSuccess || !(classes & c) || n == 0) return;
         e = hipMalloc((void**)&p, n * sizeof *p);
         if (e == hipSuccess && clear) e = hipMemset(p, 0, n * sizeof *p);
     });
-    RTD_HIP(h, e);
+    return e;
+}
+int allocBuffers(rtd_handle_impl* h, rtd_field_impl* f, unsigned classes) {
+    RTD_HIP(h, tryAllocBuffers(f, classes));
     return RTD_OK;
 }
 

@@ -1,13 +1,10 @@
 // rtd_let_host.hpp — host side of the dose-averaged LET (include/rtd.h; kernels in rtd_let.hpp). Part of
 // rtd_engine.hip's translation unit, included at its end: the products are the launches of rtd_dij_host.hpp with the LET values, the
-// optimiser's LET objective lives in the object of rtd_optimizer_host.hpp. The field's buffers are in its table (class kDijOut: they
-// go when the matrix goes); the table of the handle is an allocation of its own.
+// optimiser's LET objective lives in the object of rtd_optimizer_host.hpp. The field's buffers are in its table (class kDijLet: they
+// go when the matrix goes); the table of the handle is an allocation of its own. letReady and the entry points' opening: rtd_dij_host.hpp.
 #pragma once
 
 namespace {
-
-// The LET values of the field belong to its matrix and to the handle's table as it stands.
-bool letReady(const rtd_handle_impl* h, const rtd_field_impl* f) { return f->dijDone && f->letDone && h->dLetTable && f->letEpoch == h->letEpoch; }
 
 void launchLetDepth(rtd_handle_impl* h, rtd_field_impl* f, const DijBox& box, bool stateBox, bool compact, float* out) {
     // a wave per (y, z) line of the box; the state's box is known on the device only: a fixed grid strides over it
@@ -28,7 +25,7 @@ int rtd_set_let_table(rtd_handle hh, const float* let_matrix, int32_t n_energies
     if (!let_matrix) {                                                // removes the table
         RTD_HIP(h, hipStreamSynchronize(h->stream));
         if (h->dLetTable) { (void)hipFree(h->dLetTable); h->dLetTable = nullptr; }
-        h->letEnergies = 0; h->letSamples = 0; ++h->letEpoch;
+        h->letEnergies = 0; h->letSamples = 0; ++h->letTableNo;
         return RTD_OK;
     }
     if (!h->haveLuts) return fail(h, RTD_ERR_INVALID_ARG, "rtd_set_let_table: set the LUTs first (the table has their rows and their depth sampling)");
@@ -43,7 +40,7 @@ int rtd_set_let_table(rtd_handle hh, const float* let_matrix, int32_t n_energies
         h->letEnergies = 0; h->letSamples = 0;
         RTD_HIP(h, hipMalloc((void**)&h->dLetTable, n * sizeof(float)));
     }
-    h->letEnergies = n_energies; h->letSamples = n_energy_samples; ++h->letEpoch;
+    h->letEnergies = n_energies; h->letSamples = n_energy_samples; ++h->letTableNo;
     RTD_HIP(h, hipMemcpy(h->dLetTable, let_matrix, n * sizeof(float), hipMemcpyHostToDevice));
     return RTD_OK;
 }
@@ -66,34 +63,31 @@ int rtd_field_let_influence(rtd_handle hh, rtd_field ff) {
     auto* h = reinterpret_cast<rtd_handle_impl*>(hh);
     auto* f = reinterpret_cast<rtd_field_impl*>(ff);
     if (!h || !f) return RTD_ERR_INVALID_ARG;
-    if (f->remote) return fail(h, RTD_ERR_INVALID_ARG, "rtd_field_let_influence: a remote field has no workspace");
-    if (!f->dijDone) return fail(h, RTD_ERR_NOT_READY, "rtd_field_let_influence: no dose-influence matrix (call rtd_field_dose_influence first)");
+    { const int st = matrixRefusal(h, f, "rtd_field_let_influence", MatrixStage::kMatrix); if (st != RTD_OK) return st; }
     if (!h->dLetTable) return fail(h, RTD_ERR_NOT_READY, "rtd_field_let_influence: no LET table (call rtd_set_let_table first)");
     if (h->letEnergies != h->lut.nEnergies || h->letSamples != h->lut.nSamples)
         return fail(h, RTD_ERR_NOT_READY, "rtd_field_let_influence: the LUTs were replaced by ones of other dimensions; set the LET table again");
-    if (!f->dijPrepared) { const int st = rtd_field_dose_influence_prepare(hh, ff); if (st != RTD_OK) return st; }
-    RTD_HIP(h, hipSetDevice(h->device));
+    // (the table's tests stand between the refusals above and the preparation: the opening again, which now only prepares)
+    { const int st = matrixOpen(hh, ff, "rtd_field_let_influence", MatrixStage::kPrepared); if (st != RTD_OK) return st; }
     hipStream_t s = h->stream;
-    f->letDone = false;
-    if (!f->letAlloc) {
-        f->letAlloc = true;                                           // (the buffer table lists the three from here on)
-        hipError_t e = hipSuccess;
-        f->forEachBuffer([&](auto*& p, size_t n, BufClass c, bool, const char*) {
-            if (e == hipSuccess && c == kDijOut && n && !p) e = hipMalloc((void**)&p, n * sizeof *p);
-        });
+    FieldMatrix& m = f->matrix;
+    m.letBegins();
+    if (!m.letListed()) {
+        m.letSized();                                                 // (the buffer table lists the three from here on)
+        const hipError_t e = tryAllocBuffers(f, kDijLet);
         if (e != hipSuccess) {                                        // the matrix and its companion stay; the three go
             (void)hipGetLastError();
-            for (float** p : {&f->dLetVals, &f->dLetCVals, &f->dLetDepth}) if (*p) { (void)hipFree(*p); *p = nullptr; }
-            f->letAlloc = false;
+            freeBuffers(f, kDijLet);
+            m.letFailed();
             return fail(h, e == hipErrorOutOfMemory ? RTD_ERR_OUT_OF_MEMORY : RTD_ERR_HIP, std::string("rtd_field_let_influence: ") + hipGetErrorString(e));
         }
     }
-    const long long nRows = (long long)f->dijRowsN, nnz = (long long)f->dijNnz;
+    const long long nRows = (long long)m.rows(), nnz = (long long)m.nnz();
     const int nSpot = f->fc.spotNx * f->fc.spotNy * f->fc.L, perLayer = f->fc.spotNx * f->fc.spotNy;
-    if (nRows) launchLetDepth(h, f, f->dijBox, false, true, f->dLetDepth);
+    if (nRows) launchLetDepth(h, f, m.box(), false, true, f->dLetDepth);
     if (nnz) {
         k_let_values_csc<<<(unsigned)nSpot, 256, 0, s>>>((const long long*)f->dDijColPtr, (const int*)f->dDijRows, (const float*)f->dDijVals,
-                                                         (const float*)f->dLetDepth, (int)f->doseDims[0], (int)f->doseDims[1], f->dijBox,
+                                                         (const float*)f->dLetDepth, (int)f->doseDims[0], (int)f->doseDims[1], m.box(),
                                                          (const LayerPlan*)f->dLayers, f->fc.L, perLayer, (const float*)h->dLetTable, h->letEnergies,
                                                          h->letSamples, f->dLetVals);
         k_let_values_rows<<<(unsigned)((nRows * kDijApGroup + 255) / 256), 256, 0, s>>>((const long long*)f->dDijRowPtr, (const int*)f->dDijCCols,
@@ -102,7 +96,7 @@ int rtd_field_let_influence(rtd_handle hh, rtd_field ff) {
                                                                                       (const float*)h->dLetTable, h->letEnergies, h->letSamples, f->dLetCVals);
     }
     RTD_HIP(h, hipGetLastError());
-    f->letDone = true; f->letEpoch = h->letEpoch;
+    m.letComputed(h->letTableNo);
     return RTD_OK;
 }
 
@@ -111,9 +105,7 @@ int rtd_field_let_influence_apply(rtd_handle hh, rtd_field ff, const float* dev_
     auto* f = reinterpret_cast<rtd_field_impl*>(ff);
     if (!h || !f) return RTD_ERR_INVALID_ARG;
     if (!dev_spot_weights || !dev_out) return fail(h, RTD_ERR_INVALID_ARG, "rtd_field_let_influence_apply: null device pointer");
-    if (f->remote) return fail(h, RTD_ERR_INVALID_ARG, "rtd_field_let_influence_apply: a remote field has no workspace");
-    if (!letReady(h, f)) return fail(h, RTD_ERR_NOT_READY, "rtd_field_let_influence_apply: no LET-weighted matrix of the current matrix and table (call rtd_field_let_influence first)");
-    RTD_HIP(h, hipSetDevice(h->device));
+    { const int st = matrixOpen(hh, ff, "rtd_field_let_influence_apply", MatrixStage::kLetValues); if (st != RTD_OK) return st; }
     return dijApplyLaunch(h, f, f->dLetCVals, dev_spot_weights, dev_out, init);
 }
 
@@ -122,9 +114,7 @@ int rtd_field_let_influence_apply_t(rtd_handle hh, rtd_field ff, const float* de
     auto* f = reinterpret_cast<rtd_field_impl*>(ff);
     if (!h || !f) return RTD_ERR_INVALID_ARG;
     if (!dev_voxel_weights || !dev_spot_grad) return fail(h, RTD_ERR_INVALID_ARG, "rtd_field_let_influence_apply_t: null device pointer");
-    if (f->remote) return fail(h, RTD_ERR_INVALID_ARG, "rtd_field_let_influence_apply_t: a remote field has no workspace");
-    if (!letReady(h, f)) return fail(h, RTD_ERR_NOT_READY, "rtd_field_let_influence_apply_t: no LET-weighted matrix of the current matrix and table (call rtd_field_let_influence first)");
-    RTD_HIP(h, hipSetDevice(h->device));
+    { const int st = matrixOpen(hh, ff, "rtd_field_let_influence_apply_t", MatrixStage::kLetValues); if (st != RTD_OK) return st; }
     return dijApplyTLaunch(h, f, f->dLetVals, dev_voxel_weights, dev_spot_grad);
 }
 
@@ -133,9 +123,8 @@ int rtd_field_let_influence_device(rtd_handle hh, rtd_field ff, const float** va
     auto* f = reinterpret_cast<rtd_field_impl*>(ff);
     if (!h || !f) return RTD_ERR_INVALID_ARG;
     if (!values || !nnz) return fail(h, RTD_ERR_INVALID_ARG, "rtd_field_let_influence_device: null pointer");
-    if (f->remote) return fail(h, RTD_ERR_INVALID_ARG, "rtd_field_let_influence_device: a remote field has no workspace");
-    if (!letReady(h, f)) return fail(h, RTD_ERR_NOT_READY, "rtd_field_let_influence_device: no LET-weighted matrix of the current matrix and table (call rtd_field_let_influence first)");
-    *values = f->dLetVals; *nnz = f->dijNnz;
+    { const int st = matrixRefusal(h, f, "rtd_field_let_influence_device", MatrixStage::kLetValues); if (st != RTD_OK) return st; }
+    *values = f->dLetVals; *nnz = f->matrix.nnz();
     return RTD_OK;
 }
 

@@ -60,8 +60,8 @@ using FieldApplyT = int (*)(rtd_handle, rtd_field, const float*, float*);
 int fieldsForward(rtd_handle hh, rtd_handle_impl* h, rtd_optimizer_impl* p, rtd_field_impl* const* row, float* vol, FieldApply apply) {
     for (size_t i = 1; i < p->fields.size(); ++i) {
         const rtd_field_impl* f = row[i];
-        const long long nRows = (long long)f->dijRowsN;
-        if (nRows) k_opt_clear_box<<<(unsigned)((nRows + 255) / 256), 256, 0, h->stream>>>(vol, (int)f->doseDims[0], (int)f->doseDims[1], f->dijBox, nRows);
+        const long long nRows = (long long)f->matrix.rows();
+        if (nRows) k_opt_clear_box<<<(unsigned)((nRows + 255) / 256), 256, 0, h->stream>>>(vol, (int)f->doseDims[0], (int)f->doseDims[1], f->matrix.box(), nRows);
     }
     for (size_t i = 0; i < p->fields.size(); ++i) {
         const int st = apply(hh, reinterpret_cast<rtd_field>(row[i]), p->w() + p->offset[i], vol, i == 0 ? 1 : 0);
@@ -95,7 +95,7 @@ int robustForward(rtd_handle hh, rtd_handle_impl* h, rtd_optimizer_impl* p) {
         long long most = 0;
         for (int s = 0; s < S; ++s) {
             const rtd_field_impl* f = p->sf(s, i);
-            a.dose[s] = p->doseS[s]; a.nRows[s] = (long long)f->dijRowsN; a.box[s] = f->dijBox;
+            a.dose[s] = p->doseS[s]; a.nRows[s] = (long long)f->matrix.rows(); a.box[s] = f->matrix.box();
             most = std::max(most, a.nRows[s]);
         }
         if (most) k_robust_clear_box<<<dim3((unsigned)((most + 255) / 256), (unsigned)S), 256, 0, h->stream>>>(a, nx, ny);
@@ -106,8 +106,8 @@ int robustForward(rtd_handle hh, rtd_handle_impl* h, rtd_optimizer_impl* p) {
         for (int s = 0; s < S; ++s) {
             const rtd_field_impl* f = p->sf(s, i);
             a.rowPtr[s] = (const long long*)f->dDijRowPtr; a.cCols[s] = f->dDijCCols; a.cVals[s] = f->dDijCVals; a.dose[s] = p->doseS[s];
-            a.nRows[s] = (i != 0 && f->dijNnz == 0) ? 0 : (long long)f->dijRowsN;   // (an empty matrix adds nothing: no work, as the single call)
-            a.box[s] = f->dijBox;
+            a.nRows[s] = (i != 0 && f->matrix.nnz() == 0) ? 0 : (long long)f->matrix.rows();   // (an empty matrix adds nothing: no work, as the single call)
+            a.box[s] = f->matrix.box();
             most = std::max(most, a.nRows[s]);
         }
         if (!most) continue;
@@ -136,7 +136,7 @@ int robustAdjoint(rtd_handle hh, rtd_handle_impl* h, rtd_optimizer_impl* p) {
             const rtd_field_impl* f = p->sf(s, i);
             a.colPtr[s] = (const long long*)f->dDijColPtr; a.rows[s] = (const int*)f->dDijRows; a.vals[s] = (const float*)f->dDijVals;
             a.chunkCol[s] = (const int*)f->dDijChunkCol; a.chunkFirst[s] = (const int*)f->dDijChunkFirst; a.g[s] = p->gS[s];
-            a.partial[s] = f->dDijPartial; a.nChunks[s] = (int)f->dijChunks;
+            a.partial[s] = f->dDijPartial; a.nChunks[s] = (int)f->matrix.chunks();
             r.chunkFirst[s] = (const int*)f->dDijChunkFirst; r.partial[s] = (const float*)f->dDijPartial;
             r.out[s] = p->dGradS + (size_t)s * p->n + p->offset[i];
             most = std::max(most, a.nChunks[s]);
@@ -173,7 +173,7 @@ int optCheckField(rtd_handle_impl* h, const std::string& who, const rtd_field_im
 int optPrepare(rtd_handle hh, const std::string& who, const rtd_field* fields, uint32_t n_fields, uint32_t n_all, rtd_objective_impl* o, std::vector<int>* offset) {
     auto* h = reinterpret_cast<rtd_handle_impl*>(hh);
     for (uint32_t i = 0; i < n_all; ++i)
-        if (!reinterpret_cast<rtd_field_impl*>(fields[i])->dijDone)
+        if (!reinterpret_cast<rtd_field_impl*>(fields[i])->matrix.hasMatrix())
             return fail(h, RTD_ERR_NOT_READY, who + ": a field has no dose-influence matrix (call rtd_field_dose_influence first)");
     RTD_HIP(h, hipSetDevice(h->device));
     for (uint32_t i = 0; i < n_all; ++i) { const int st = rtd_field_dose_influence_prepare(hh, fields[i]); if (st != RTD_OK) return st; }
@@ -402,7 +402,7 @@ int rtd_optimizer_run(rtd_handle hh, rtd_optimizer pp, uint32_t n_iterations) {
     if (p->obj->terms.empty()) return fail(h, RTD_ERR_INVALID_ARG, "rtd_optimizer_run: the objective has no terms");
     if (p->letObj || p->rbe)                                          // (in front of the first launch: a refused run launches nothing)
         for (const rtd_field_impl* f : p->fields)
-            if (!(f->dijDone && f->letDone && h->dLetTable && f->letEpoch == h->letEpoch))
+            if (!letReady(h, f))
                 return fail(h, RTD_ERR_NOT_READY, "rtd_optimizer_run: a field's LET-weighted matrix is not that of its matrix and the handle's table (call rtd_field_let_influence again)");
     RTD_HIP(h, hipSetDevice(h->device));
     hipStream_t s = h->stream;

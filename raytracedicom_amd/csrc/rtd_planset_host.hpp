@@ -26,10 +26,10 @@ const char* psCountError(uint32_t n_plans, uint32_t plan_stride) {
 }
 
 // The launches of the two products for every plan (dijApplyLaunch / dijApplyTLaunch of rtd_dij_host.hpp with A accumulators): the
-// same grids, the same cases without a launch. scratch: dijChunks * A floats of the caller.
+// same grids, the same cases without a launch. scratch: the matrix's chunks * A floats of the caller.
 int psApplyLaunch(rtd_handle_impl* h, rtd_field_impl* f, const float* w, float* dose, int nPlans, int stride, int init) {
-    const long long nRows = (long long)f->dijRowsN;
-    if (nRows == 0 || (!init && f->dijNnz == 0)) return RTD_OK;
+    const long long nRows = (long long)f->matrix.rows();
+    if (nRows == 0 || (!init && f->matrix.nnz() == 0)) return RTD_OK;
     const unsigned g = (unsigned)((nRows * kDijApGroup + 255) / 256);
     const int A = psAccum((uint32_t)stride);
     const bool vec = stride == A && psAligned(w, A);
@@ -37,7 +37,7 @@ int psApplyLaunch(rtd_handle_impl* h, rtd_field_impl* f, const float* w, float* 
         constexpr int kA = decltype(tag)::value;
         auto launch = [&](auto kern) {
             kern<<<g, 256, 0, h->stream>>>((const long long*)f->dDijRowPtr, (const int*)f->dDijCCols, (const float*)f->dDijCVals, w, dose,
-                                           (int)f->doseDims[0], (int)f->doseDims[1], f->dijBox, nRows, stride, nPlans);
+                                           (int)f->doseDims[0], (int)f->doseDims[1], f->matrix.box(), nRows, stride, nPlans);
         };
         if (vec) { if (init) launch(k_ps_apply<kA, true, true>); else launch(k_ps_apply<kA, true, false>); }
         else { if (init) launch(k_ps_apply<kA, false, true>); else launch(k_ps_apply<kA, false, false>); }
@@ -46,7 +46,7 @@ int psApplyLaunch(rtd_handle_impl* h, rtd_field_impl* f, const float* w, float* 
     return RTD_OK;
 }
 int psApplyTLaunch(rtd_handle_impl* h, rtd_field_impl* f, const float* g, float* out, int nPlans, int stride, float* scratch) {
-    const int nSpot = f->fc.spotNx * f->fc.spotNy * f->fc.L, nChunks = (int)f->dijChunks;
+    const int nSpot = f->fc.spotNx * f->fc.spotNy * f->fc.L, nChunks = (int)f->matrix.chunks();
     const int A = psAccum((uint32_t)stride);
     const bool vec = stride == A && psAligned(g, A);
     psDispatch(A, [&](auto tag) {
@@ -79,7 +79,7 @@ int psHandleScratch(rtd_handle_impl* h, size_t floats, float** out) {
 
 struct rtd_planset_impl {
     std::vector<rtd_field_impl*> fields;
-    std::vector<unsigned> epoch;  // per field: its dijEpoch when the set was made (dAtPartial and the vectors are sized for that matrix)
+    std::vector<unsigned> epoch;  // per field: its matrix's epoch when the set was made (dAtPartial and the vectors are sized for that matrix)
     size_t atChunks = 0;          // chunks dAtPartial holds per accumulator
     unsigned objEpoch = 0;        // the objective's epoch when the set was made (dTerms and dObjPartial are sized for its terms and blocks)
     int objBlocks = 0;            // blocks of k_ps_obj_eval dObjPartial holds per (term, plan)
@@ -119,10 +119,7 @@ int rtd_field_dose_influence_apply_set(rtd_handle hh, rtd_field ff, const float*
     if (!h || !f) return RTD_ERR_INVALID_ARG;
     if (!dev_w || !dev_dose) return fail(h, RTD_ERR_INVALID_ARG, "rtd_field_dose_influence_apply_set: null device pointer");
     if (const char* why = psCountError(n_plans, plan_stride)) return fail(h, RTD_ERR_INVALID_ARG, std::string("rtd_field_dose_influence_apply_set: ") + why);
-    if (f->remote) return fail(h, RTD_ERR_INVALID_ARG, "rtd_field_dose_influence_apply_set: a remote field has no workspace");
-    if (!f->dijDone) return fail(h, RTD_ERR_NOT_READY, "rtd_field_dose_influence_apply_set: no dose-influence matrix (call rtd_field_dose_influence first)");
-    if (!f->dijPrepared) { const int st = rtd_field_dose_influence_prepare(hh, ff); if (st != RTD_OK) return st; }
-    RTD_HIP(h, hipSetDevice(h->device));
+    { const int st = matrixOpen(hh, ff, "rtd_field_dose_influence_apply_set", MatrixStage::kPrepared); if (st != RTD_OK) return st; }
     return psApplyLaunch(h, f, dev_w, dev_dose, (int)n_plans, (int)plan_stride, init);
 }
 
@@ -132,12 +129,9 @@ int rtd_field_dose_influence_apply_t_set(rtd_handle hh, rtd_field ff, const floa
     if (!h || !f) return RTD_ERR_INVALID_ARG;
     if (!dev_g || !dev_spot_grad) return fail(h, RTD_ERR_INVALID_ARG, "rtd_field_dose_influence_apply_t_set: null device pointer");
     if (const char* why = psCountError(n_plans, plan_stride)) return fail(h, RTD_ERR_INVALID_ARG, std::string("rtd_field_dose_influence_apply_t_set: ") + why);
-    if (f->remote) return fail(h, RTD_ERR_INVALID_ARG, "rtd_field_dose_influence_apply_t_set: a remote field has no workspace");
-    if (!f->dijDone) return fail(h, RTD_ERR_NOT_READY, "rtd_field_dose_influence_apply_t_set: no dose-influence matrix (call rtd_field_dose_influence first)");
-    if (!f->dijPrepared) { const int st = rtd_field_dose_influence_prepare(hh, ff); if (st != RTD_OK) return st; }
-    RTD_HIP(h, hipSetDevice(h->device));
+    { const int st = matrixOpen(hh, ff, "rtd_field_dose_influence_apply_t_set", MatrixStage::kPrepared); if (st != RTD_OK) return st; }
     float* scratch = nullptr;
-    const int st = psHandleScratch(h, std::max<size_t>(f->dijChunks, 1) * (size_t)psAccum(plan_stride), &scratch);
+    const int st = psHandleScratch(h, std::max<size_t>(f->matrix.chunks(), 1) * (size_t)psAccum(plan_stride), &scratch);
     if (st != RTD_OK) return st;
     return psApplyTLaunch(h, f, dev_g, dev_spot_grad, (int)n_plans, (int)plan_stride, scratch);
 }
@@ -176,8 +170,8 @@ int rtd_planset_create(rtd_handle hh, const rtd_field* fields, uint32_t n_fields
     for (uint32_t i = 0; i < n_fields; ++i) {
         auto* f = reinterpret_cast<rtd_field_impl*>(fields[i]);
         p->fields.push_back(f);
-        p->epoch.push_back(f->dijEpoch);
-        mostChunks = std::max(mostChunks, f->dijChunks);
+        p->epoch.push_back(f->matrix.epoch());
+        mostChunks = std::max(mostChunks, f->matrix.chunks());
     }
     p->atChunks = mostChunks;
     p->n = offset.back();
@@ -250,11 +244,9 @@ int rtd_planset_run(rtd_handle hh, rtd_planset pp, uint32_t n_iterations) {
     //  set's term table and block sums are sized for the objective it was created on)
     if (!o->built || o->epoch != p->objEpoch || (int)o->terms.size() != p->nTerms || o->nBlocks > p->objBlocks)
         return fail(h, RTD_ERR_NOT_READY, "rtd_planset_run: the objective is not the one the plan set was created on (create a new set)");
-    for (size_t i = 0; i < p->fields.size(); ++i) {                   // the set's scratch is sized for the matrices it was created on
-        const rtd_field_impl* f = p->fields[i];
-        if (!f->dijDone || !f->dijPrepared || f->dijEpoch != p->epoch[i] || f->dijChunks > p->atChunks)
+    for (size_t i = 0; i < p->fields.size(); ++i)                     // the set's scratch is sized for the matrices it was created on
+        if (!p->fields[i]->matrix.isMatrixOf(p->epoch[i], p->atChunks))
             return fail(h, RTD_ERR_NOT_READY, "rtd_planset_run: a field's matrix is not the one the plan set was created on (create a new set)");
-    }
     RTD_HIP(h, hipSetDevice(h->device));
     hipStream_t s = h->stream;
     const int S = p->S, nx = (int)o->dims[0], ny = (int)o->dims[1];
@@ -262,8 +254,8 @@ int rtd_planset_run(rtd_handle hh, rtd_planset pp, uint32_t n_iterations) {
     for (uint32_t k = 0; k < n_iterations; ++k) {
         for (size_t i = 1; i < p->fields.size(); ++i) {               // 1. as fieldsForward, for every plan at once
             const rtd_field_impl* f = p->fields[i];
-            const long long cells = (long long)f->dijRowsN * S;
-            if (cells) k_ps_clear_box<<<(unsigned)((cells + 255) / 256), 256, 0, s>>>(p->dDose, nx, ny, f->dijBox, (long long)f->dijRowsN, S);
+            const long long cells = (long long)f->matrix.rows() * S;
+            if (cells) k_ps_clear_box<<<(unsigned)((cells + 255) / 256), 256, 0, s>>>(p->dDose, nx, ny, f->matrix.box(), (long long)f->matrix.rows(), S);
         }
         for (size_t i = 0; i < p->fields.size(); ++i) {
             const int st = psApplyLaunch(h, p->fields[i], p->w() + (size_t)p->offset[i] * S, p->dDose, p->nPlans, S, i == 0 ? 1 : 0);

@@ -252,8 +252,8 @@ int rtd_optimizer_set_rbe(rtd_handle hh, rtd_optimizer pp, rtd_rbe rr) {
     int lo[3] = {0, 0, 0}, hi[3] = {-1, -1, -1};
     bool any = false;
     for (const rtd_field_impl* f : p->fields) {
-        if (!f->dijRowsN) continue;
-        const DijBox& b = f->dijBox;
+        if (!f->matrix.rows()) continue;
+        const DijBox& b = f->matrix.box();
         const int fl[3] = {b.x0, b.y0, b.z0}, fh[3] = {b.x0 + b.bw - 1, b.y0 + b.bh - 1, b.z0 + b.bd - 1};
         for (int a = 0; a < 3; ++a) { lo[a] = any ? std::min(lo[a], fl[a]) : fl[a]; hi[a] = any ? std::max(hi[a], fh[a]) : fh[a]; }
         any = true;
