@@ -1307,6 +1307,84 @@ int rtd_dose_warp_t(rtd_handle h, const float* dev_g_dst, const uint32_t dst_dim
 int rtd_dose_warp_t_kernel_ms(rtd_handle h, float ms[4] /* memset, maximum, scatter, finish */);
 
 /*
+ * ---- 4D dose: phases warped and summed, and an optimiser on the accumulated dose ----
+ *
+ * Additive to the blocks above (RTD_ABI_VERSION stays 3; no entry point, kernel result or structure above changes). A 4D plan is
+ * judged on the dose accumulated over the breathing phases of a 4DCT: every phase's dose pulled onto one reference anatomy through
+ * that phase's deformation field and summed with the time spent in the phase as its weight. The two calls below are the warps of the
+ * block above over a phase axis; rtd_optimizer_create_4d puts them into the resident iteration. All phases share one source grid,
+ * src_dims (the phases of a 4DCT do); sources are float32; 1 <= n <= RTD_4D_MAX_PHASES.
+ *
+ * rtd_dose_warp_sum(h, dev_srcs, src_dims, warps, weights, n, dev_dst, dst_dims): dev_srcs a HOST array of n device pointers, warps host
+ * rtd_warp[n], weights host float[n], each finite. The result is bit for bit what these calls give in order:
+ * rtd_dose_warp(src_0, warp_0, dst, scale = weights[0], accumulate = 0), then rtd_dose_warp(src_p, warp_p, dst, scale = weights[p],
+ * accumulate = 1) for p = 1 .. n - 1. Per destination voxel: d = inside_0 ? weights[0] * e_0 : 0.0f, then for ascending p,
+ * if (inside_p) d = d + weights[p] * e_p, with inside_p and e_p the forward rule's for phase p; every product and sum is rounded on
+ * its own. One launch writes the destination once (non-temporal); nothing is read back. It launches only and can be captured.
+ * RTD_ERR_INVALID_ARG, after which nothing has been written: whatever rtd_dose_warp refuses of a phase, n of 0 or above 16, a null
+ * array or a null entry of dev_srcs, a weight that is not finite.
+ *
+ * rtd_dose_warp_t_phases(h, dev_g_dst, dst_dims, warps, weights, n, dev_g_srcs, src_dims, dev_workspace, workspace_bytes):
+ * dev_g_srcs[p] (a HOST array of n device pointers) gets, bit for bit, what rtd_dose_warp_t(g, warp_p, scale = weights[p],
+ * accumulate = 0) writes. rtd_dose_warp_t_phases_workspace_bytes(src_dims, n, &bytes): n times rtd_dose_warp_t_workspace_bytes; slice p
+ * begins at p times the single call's size and keeps its own 64-byte header. Four operations in all on the handle's stream: one
+ * memset of the whole workspace, one maximum kernel that reads g once and keeps n maxima M_p = max |weights[p] * g| (each phase's own
+ * products: a product that overflows counts as zero, as the rule above says, so M_p is NOT weights[p] times one max |g|), one scatter
+ * kernel and one finish kernel with the phase on the grid. RTD_WARP_T_PLAIN keeps its meaning; the bits are the same. Refusals as
+ * rtd_dose_warp_t's per phase, and those of the arrays as above. It launches only and can be captured.
+ *
+ * rtd_optimizer_create_4d(h, fields, n_fields, fourd, obj, options, &opt): fields is [n_phases][n_fields], phase-major: a phase is a
+ * row of fields, the same beams computed on that phase's CT, each with its matrix. All phases carry ONE weight vector; the spot-map
+ * shape of field f must equal that of phase 0's field f; all fields share one dose grid, the phase grid. The objective lives on the
+ * reference grid, whose dims may differ from the phase grid's. warps[p] leads from a reference voxel to phase p's dose grid (what
+ * rtd_dose_warp takes with src_dims = the phase grid and dst_dims = the objective's dims); the records are copied, dev_dvf stays the
+ * caller's: THE FIELDS MUST OUTLIVE THE OPTIMISER. weights[p] (finite, > 0: the time spent in the phase) is used as given; NULL:
+ * float(1.0 / n_phases) each. The call returns an ordinary rtd_optimizer: rtd_optimizer_set_weights, _run, _result, _weights and
+ * _destroy work on it unchanged; the start weights are phase 0's.
+ * One iteration, launches on the handle's stream only, no decision on the host, capturable:
+ *   1. dose_p = sum_f Dij_{p,f} w_f into P volumes on the phase grid (the batched products of the robust optimiser);
+ *   2. acc = sum_p a_p W_p dose_p on the reference grid: rtd_dose_warp_sum's launch;
+ *   3. rtd_objective_eval(acc): f, the term values and g on the reference grid (every term kind of the plain optimiser, DVH and EUD
+ *      terms included);
+ *   4. g_p = a_p W_p^T g: rtd_dose_warp_t_phases's four operations on a workspace the optimiser owns;
+ *   5. grad_p = Dij_{p,f}^T g_p per field (the batched transposed products, every phase taken);
+ *   6. grad[j] = float32(sum_p double(grad_p[j])), p ascending, the sum starting from the first term, rounded once (the phase
+ *      weights already act through the warps' scale);
+ *   7. steps 4 to 7 of the plain iteration, word for word.
+ * rtd_optimizer_dose answers acc of the iterate that entered the last iteration, rtd_optimizer_scenario_dose(p) dose_p;
+ * rtd_optimizer_scenario_values answers as for a composite: f_p = f_last for every p, lambda 1.0, worst 0.
+ * Memory: per phase a dose volume, a g volume and a workspace slice, 16 bytes per phase-grid voxel per phase (4.3 GB at 256^3 and 16
+ * phases), plus acc and g on the reference grid. A failed allocation is RTD_ERR_OUT_OF_MEMORY with everything freed.
+ * RTD_4D_NO_BATCH in the environment at creation makes the optimiser issue the per-phase public sequences instead (rtd_dose_warp P
+ * times, rtd_dose_warp_t P times each on its slice, the unbatched products): the same bits, for tests and measurements.
+ * The optimiser notes every field's matrix at creation; rtd_optimizer_run refuses with RTD_ERR_NOT_READY, before its first launch,
+ * once rtd_field_dose_influence has been called again on one of the fields: destroy the optimiser and create a new one.
+ * RTD_ERR_INVALID_ARG: whatever rtd_optimizer_create_robust refuses of a field list; n_phases of 0 or above 16; a null warps; a warp
+ * that rtd_dose_warp would refuse between the phase grid and the objective's dims; a weight that is not finite and positive; a
+ * non-zero reserved word. RTD_ERR_NOT_READY: a field without a matrix. rtd_optimizer_set_let_objective and rtd_optimizer_set_rbe
+ * refuse a 4D optimiser as they refuse a robust one. After a refusal every object stays usable.
+ *
+ * Out of scope: phases combined with set-up or range scenarios; the voxel-wise worst case over phases; LET and RBE; phases on
+ * different dose grids; a forward sum restricted to the ROI union; energy- or mass-conserving warps; a registration reader;
+ * nuclear_corr, remote fields and the rtd_plan_* path; interplay with the delivery time structure.
+ */
+enum { RTD_4D_MAX_PHASES = 16 };
+int rtd_dose_warp_sum(rtd_handle h, const float* const* dev_srcs, const uint32_t src_dims[3], const rtd_warp* warps, const float* weights,
+                      uint32_t n, float* dev_dst, const uint32_t dst_dims[3]);
+int rtd_dose_warp_t_phases_workspace_bytes(const uint32_t src_dims[3], uint32_t n, size_t* bytes);
+int rtd_dose_warp_t_phases(rtd_handle h, const float* dev_g_dst, const uint32_t dst_dims[3], const rtd_warp* warps, const float* weights,
+                           uint32_t n, float* const* dev_g_srcs, const uint32_t src_dims[3], void* dev_workspace, size_t workspace_bytes);
+typedef struct rtd_4d_options {
+    uint32_t n_phases;          /* 1 .. RTD_4D_MAX_PHASES */
+    uint32_t reserved0;
+    const rtd_warp* warps;      /* [n_phases]: reference voxel -> phase p's dose grid; the records are copied, dev_dvf stays the caller's */
+    const float* weights;       /* [n_phases], finite and > 0 (time spent in the phase), used as given; NULL: float(1.0 / n_phases) each */
+    int32_t reserved[4];
+} rtd_4d_options;               /* 40 bytes */
+int rtd_optimizer_create_4d(rtd_handle h, const rtd_field* fields /* [n_phases][n_fields], phase-major */, uint32_t n_fields,
+                            const rtd_4d_options* fourd, rtd_objective obj, const rtd_optimizer_options* o, rtd_optimizer* out);
+
+/*
  * ---- Dose-averaged LET: the LET-weighted influence matrix, LETd, a LET objective ----
  *
  * Additive to the blocks above (RTD_ABI_VERSION stays 3). The convention is the analytical one: the LET of spot j at voxel v is the

@@ -258,6 +258,16 @@ def make_warp(dst_idx_to_src_idx, dst_idx_to_dvf_idx, disp_to_src_idx, dev_dvf, 
     return w
 
 
+RTD_4D_MAX_PHASES = 16
+
+
+class Rtd4dOptions(C.Structure):
+    """rtd_4d_options: the phases of rtd_optimizer_create_4d — their warps (host rtd_warp[n_phases]) and weights (host float[n_phases]
+    or NULL) (40 bytes)."""
+    _fields_ = [("n_phases", C.c_uint32), ("reserved0", C.c_uint32), ("warps", C.POINTER(RtdWarp)), ("weights", c_float_p),
+                ("reserved", C.c_int32 * 4)]
+
+
 class RtdRbeTissue(C.Structure):
     """rtd_rbe_tissue: photon alpha_x (1/Gy), beta_x (1/Gy^2) and the lines RBEmax / RBEmin = c[0] + c[1] * LETd (32 bytes)."""
     _fields_ = [("alpha_x", C.c_float), ("beta_x", C.c_float), ("rbe_max", C.c_float * 2), ("rbe_min", C.c_float * 2),

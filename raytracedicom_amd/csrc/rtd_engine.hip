@@ -50,6 +50,7 @@
 #include "rtd_gamma.hpp"
 #include "rtd_resample.hpp"
 #include "rtd_warp.hpp"
+#include "rtd_warp_phases.hpp"
 #include "rtd_let.hpp"
 #include "rtd_rbe.hpp"
 #include "rtd_planset.hpp"
@@ -1448,3 +1449,4 @@ int rtd_compute(rtd_handle hh, const rtd_beam* beams, int n_beams, float* dose_i
 #include "rtd_let_host.hpp"
 #include "rtd_rbe_host.hpp"
 #include "rtd_planset_host.hpp"
+#include "rtd_fourd_host.hpp"

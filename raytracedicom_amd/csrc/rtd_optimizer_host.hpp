@@ -1,6 +1,7 @@
 // rtd_optimizer_host.hpp — host side of the resident spot-weight optimiser, plain, robust and voxel-wise worst case (include/rtd.h,
 // DESIGN.md sections 12, 14 and 15; kernels in rtd_optimize.hpp, rtd_robust.hpp and rtd_voxelwise.hpp). Part of rtd_engine.hip's
 // translation unit, included after rtd_dij_host.hpp and rtd_objective_host.hpp, whose products and evaluations an iteration launches.
+// A 4D optimiser (section 26) is created in rtd_fourd_host.hpp and runs through the branch of rtd_optimizer_run beside the robust one.
 #pragma once
 
 namespace {
@@ -40,6 +41,18 @@ struct rtd_optimizer_impl {
     struct rtd_rbe_impl* rbe = nullptr;
     DijBox rbeBox{0, 0, 0, 0, 0, 0};
     DevBuf<float> dRbeDose, dRbeG;
+    // A 4D optimiser (section 26; rtd_optimizer_create_4d in rtd_fourd_host.hpp allocates all of it): a robust one whose scenarios are
+    // breathing phases on the phase grid (every doseS / gS volume is owned, nPhaseVox voxels each), joined on the reference grid, where
+    // dDose is the accumulated dose and dG the objective's voxel gradient. `batch` also chooses between the fused warps and the
+    // per-phase sequences (RTD_4D_NO_BATCH). matEpoch / matChunks: per field of sfields, what its matrix was at creation.
+    bool fourd = false;
+    uint32_t phaseDims[3] = {0, 0, 0}, refDims[3] = {0, 0, 0};
+    size_t nPhaseVox = 0, warpSliceBytes = 0;
+    std::vector<rtd_warp> warps;
+    std::vector<float> phaseWeights;
+    DevBuf<unsigned char> dWarpWs;          // nScen slices of rtd_dose_warp_t_workspace_bytes(phaseDims)
+    std::vector<unsigned> matEpoch;
+    std::vector<size_t> matChunks;
     rtd_field_impl* const* row(int s) const { return sfields.data() + (size_t)s * fields.size(); }
     rtd_field_impl* sf(int s, size_t i) const { return row(s)[i]; }
     float* w() const { return dVec; }
@@ -79,6 +92,11 @@ int fieldsAdjoint(rtd_handle hh, rtd_optimizer_impl* p, rtd_field_impl* const* r
 // R of the two volumes on rbeBox, and g_R back to dG and dLetG (rtd_rbe_host.hpp, included later).
 int rbeOptForward(rtd_handle_impl* h, rtd_optimizer_impl* p);
 int rbeOptBackward(rtd_handle_impl* h, rtd_optimizer_impl* p);
+// Section 26 (rtd_fourd_host.hpp, included later): whether every matrix is still the one the optimiser was created on, the phase
+// doses joined into dDose, and dG pushed back into every phase's g volume.
+bool fourdMatricesStand(const rtd_optimizer_impl* p);
+int fourdJoin(rtd_handle hh, rtd_optimizer_impl* p);
+int fourdSplit(rtd_handle hh, rtd_optimizer_impl* p);
 
 // The same two products over the scenario axis (section 14; kernels in rtd_robust.hpp). Batched: per field position one launch covers
 // every scenario. Unbatched (RTD_ROBUST_NO_BATCH): the single-matrix launches, scenario by scenario. Either way scenario s's volume
@@ -354,12 +372,11 @@ int rtd_optimizer_scenario_values(rtd_handle hh, rtd_optimizer pp, double* value
     if (!h) return RTD_ERR_INVALID_ARG;
     if (!p || !values) return fail(h, RTD_ERR_INVALID_ARG, "rtd_optimizer_scenario_values: null pointer");
     RTD_HIP(h, hipSetDevice(h->device));
-    if (!p->robust) {
+    if (!p->robust || p->fourd) {             // (a 4D optimiser answers as a composite: f_p = f_last, lambda 1.0, worst 0)
         OptState st{};
         RTD_HIP(h, hipMemcpyAsync(&st, p->dState, sizeof st, hipMemcpyDeviceToHost, h->stream));
         RTD_HIP(h, hipStreamSynchronize(h->stream));
-        values[0] = st.fLast;
-        if (lambdas) lambdas[0] = 1.0;
+        for (int sc = 0; sc < p->nScen; ++sc) { values[sc] = st.fLast; if (lambdas) lambdas[sc] = 1.0; }
         if (worst) *worst = 0;
         return RTD_OK;
     }
@@ -404,6 +421,8 @@ int rtd_optimizer_run(rtd_handle hh, rtd_optimizer pp, uint32_t n_iterations) {
         for (const rtd_field_impl* f : p->fields)
             if (!letReady(h, f))
                 return fail(h, RTD_ERR_NOT_READY, "rtd_optimizer_run: a field's LET-weighted matrix is not that of its matrix and the handle's table (call rtd_field_let_influence again)");
+    if (p->fourd && !fourdMatricesStand(p))
+        return fail(h, RTD_ERR_NOT_READY, "rtd_optimizer_run: a field's dose-influence matrix has been computed again since rtd_optimizer_create_4d (destroy the optimiser and create a new one)");
     RTD_HIP(h, hipSetDevice(h->device));
     hipStream_t s = h->stream;
     // the products of a plain optimiser: its one row of fields with the dose matrices and with the LET-weighted ones
@@ -434,6 +453,14 @@ int rtd_optimizer_run(rtd_handle hh, rtd_optimizer pp, uint32_t n_iterations) {
                     k_let_add<<<(unsigned)std::max((p->n + 255) / 256, 1), 256, 0, s>>>(p->grad(), (const float*)p->dLetGrad, p->n, p->dValues,
                                                                                        (const double*)p->dLetValues, p->dLetValues + 1 + kObjMaxTerms);
             }
+        } else if (p->fourd) {                // section 26: the phases' doses joined on the reference grid, the objective there, its gradient back to every phase
+            st = robustForward(hh, h, p);
+            if (st == RTD_OK) st = fourdJoin(hh, p);
+            if (st == RTD_OK) st = evalObjective(h, p->obj, p->dDose, p->dValues, p->dG);
+            if (st == RTD_OK) st = fourdSplit(hh, p);
+            if (st == RTD_OK) st = robustAdjoint(hh, h, p);
+            if (st == RTD_OK)
+                k_robust_combine<<<(unsigned)((p->n + 255) / 256), 256, 0, s>>>((const float*)p->dGradS, (const RobustState*)p->dRobust, p->nScen, p->n, p->grad());
         } else {                              // sections 14 and 15, steps 1.-5.: they differ in the evaluation and in who decides on it
             st = robustForward(hh, h, p);
             if (p->voxelwise) {

@@ -1,7 +1,8 @@
 // rtd_warp_host.hpp — rtd_dose_warp, rtd_dose_warp_t and their companions (include/rtd.h "Deformable dose warping", DESIGN.md
 // section 24; kernels in rtd_warp.hpp). Part of rtd_engine.hip's translation unit. Neither call owns device memory: the forward call
 // only launches its kernel, the transposed one zeroes the caller's workspace and launches three kernels. The handle keeps the events
-// around them.
+// around them. Behind them the same two over a phase axis, rtd_dose_warp_sum and rtd_dose_warp_t_phases ("4D dose: phases warped and
+// summed", section 26; kernels in rtd_warp_phases.hpp), which are not timed.
 #pragma once
 
 namespace {
@@ -158,6 +159,97 @@ int rtd_dose_warp_t_kernel_ms(rtd_handle hh, float ms[4]) {
     if (!h->warpTTimed) return fail(h, RTD_ERR_NOT_READY, "rtd_dose_warp_t_kernel_ms: no rtd_dose_warp_t call has been timed");
     RTD_HIP(h, hipEventSynchronize(h->warpTEv[4]));
     for (int i = 0; i < 4; ++i) RTD_HIP(h, hipEventElapsedTime(&ms[i], h->warpTEv[i], h->warpTEv[i + 1]));
+    return RTD_OK;
+}
+
+// ---- the two warps over a phase axis (include/rtd.h "4D dose: phases warped and summed"; kernels in rtd_warp_phases.hpp) ----
+
+}  // extern "C"
+
+namespace {
+
+// What both phase calls refuse about their host arrays; on success a holds every phase's operands with its weight as the scale.
+int warpPhaseParams(rtd_handle_impl* h, const std::string& who, const uint32_t src_dims[3], const uint32_t dst_dims[3], const rtd_warp* warps, const float* weights,
+                    uint32_t n, WarpPhases& a) {
+    if (n < 1 || n > RTD_4D_MAX_PHASES) return fail(h, RTD_ERR_INVALID_ARG, who + ": 1 to 16 phases");
+    if (!warps || !weights) return fail(h, RTD_ERR_INVALID_ARG, who + ": null pointer");
+    a.n = (int)n;
+    for (uint32_t p = 0; p < n; ++p) {
+        if (const char* why = warpParams(src_dims, dst_dims, &warps[p], a.w[p])) return fail(h, RTD_ERR_INVALID_ARG, who + ": " + why);
+        if (!std::isfinite(weights[p])) return fail(h, RTD_ERR_INVALID_ARG, who + ": a weight is not finite");
+        a.w[p].r.scale = weights[p];
+    }
+    return RTD_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int rtd_dose_warp_sum(rtd_handle hh, const float* const* dev_srcs, const uint32_t src_dims[3], const rtd_warp* warps, const float* weights, uint32_t n,
+                      float* dev_dst, const uint32_t dst_dims[3]) {
+    auto* h = reinterpret_cast<rtd_handle_impl*>(hh);
+    if (!h) return RTD_ERR_INVALID_ARG;
+    if (!dev_srcs || !dev_dst) return fail(h, RTD_ERR_INVALID_ARG, "rtd_dose_warp_sum: null pointer");
+    WarpPhases a{};
+    const int st = warpPhaseParams(h, "rtd_dose_warp_sum", src_dims, dst_dims, warps, weights, n, a);
+    if (st != RTD_OK) return st;
+    WarpVols src{};
+    for (uint32_t p = 0; p < n; ++p) {
+        if (!dev_srcs[p]) return fail(h, RTD_ERR_INVALID_ARG, "rtd_dose_warp_sum: a null source");
+        src.p[p] = const_cast<float*>(dev_srcs[p]);
+    }
+    RTD_HIP(h, hipSetDevice(h->device));
+    k_dose_warp_sum<<<warpGrid(dst_dims), dim3(kResampleBX, kResampleBY), 0, h->stream>>>(a, src, dev_dst);
+    RTD_HIP(h, hipGetLastError());
+    return RTD_OK;
+}
+
+int rtd_dose_warp_t_phases_workspace_bytes(const uint32_t src_dims[3], uint32_t n, size_t* bytes) {
+    if (!bytes || n < 1 || n > RTD_4D_MAX_PHASES) return RTD_ERR_INVALID_ARG;
+    size_t one = 0;
+    const int st = rtd_dose_warp_t_workspace_bytes(src_dims, &one);
+    if (st != RTD_OK) return st;
+    *bytes = one * n;
+    return RTD_OK;
+}
+
+int rtd_dose_warp_t_phases(rtd_handle hh, const float* dev_g_dst, const uint32_t dst_dims[3], const rtd_warp* warps, const float* weights, uint32_t n,
+                           float* const* dev_g_srcs, const uint32_t src_dims[3], void* dev_workspace, size_t workspace_bytes) {
+    auto* h = reinterpret_cast<rtd_handle_impl*>(hh);
+    if (!h) return RTD_ERR_INVALID_ARG;
+    if (!dev_g_dst || !dev_g_srcs || !dev_workspace) return fail(h, RTD_ERR_INVALID_ARG, "rtd_dose_warp_t_phases: null pointer");
+    WarpPhases a{};
+    const int st = warpPhaseParams(h, "rtd_dose_warp_t_phases", src_dims, dst_dims, warps, weights, n, a);
+    if (st != RTD_OK) return st;
+    WarpVols out{};
+    WarpScales sc{};
+    sc.n = (int)n;
+    for (uint32_t p = 0; p < n; ++p) {
+        if (!dev_g_srcs[p]) return fail(h, RTD_ERR_INVALID_ARG, "rtd_dose_warp_t_phases: a null output");
+        out.p[p] = dev_g_srcs[p];
+        sc.s[p] = weights[p];
+    }
+    size_t slice = 0;
+    (void)rtd_dose_warp_t_workspace_bytes(src_dims, &slice);         // (the dimensions have passed the same checks)
+    if (workspace_bytes < slice * n) return fail(h, RTD_ERR_INVALID_ARG, "rtd_dose_warp_t_phases: the workspace is smaller than rtd_dose_warp_t_phases_workspace_bytes");
+    if (reinterpret_cast<uintptr_t>(dev_workspace) % 8) return fail(h, RTD_ERR_INVALID_ARG, "rtd_dose_warp_t_phases: the workspace is not aligned to 8 bytes");
+
+    RTD_HIP(h, hipSetDevice(h->device));
+    const size_t nSrc = (size_t)src_dims[0] * src_dims[1] * src_dims[2], nDst = (size_t)dst_dims[0] * dst_dims[1] * dst_dims[2];
+    auto* ws = static_cast<unsigned char*>(dev_workspace);
+    const auto flat = [&](size_t cnt) { return (unsigned)std::min<size_t>((cnt + 255) / 256, (size_t)h->numCUs * 8); };
+    RTD_HIP(h, hipMemsetAsync(dev_workspace, 0, slice * n, h->stream));
+    k_warp_t_max_phases<<<flat(nDst), 256, 0, h->stream>>>(dev_g_dst, nDst, sc, ws, slice);
+    const dim3 block(kResampleBX, kResampleBY), grid = warpGrid(dst_dims);
+    // (grid.x * n stays below 2^29: a dimension is below 2^31 and a block takes 64 voxels of it)
+    if (h->warpTPlain) k_warp_t_scatter_phases<false><<<dim3(grid.x * n, grid.y, grid.z), block, 0, h->stream>>>(dev_g_dst, a, ws, slice, grid.x);
+    else {                                                           // a block per 64 x 4 x kWarpChunkZ voxels of a phase
+        const dim3 chunked(grid.x * n, grid.y, std::min<uint32_t>((dst_dims[2] + kWarpChunkZ - 1) / kWarpChunkZ, 65535u));
+        k_warp_t_scatter_phases<true><<<chunked, block, 0, h->stream>>>(dev_g_dst, a, ws, slice, grid.x);
+    }
+    k_warp_t_finish_phases<<<dim3(flat(nSrc), n), 256, 0, h->stream>>>(ws, slice, nSrc, out);
+    RTD_HIP(h, hipGetLastError());
     return RTD_OK;
 }
 

@@ -137,6 +137,10 @@ def lib():
         L.rtd_dose_warp_t_workspace_bytes.argtypes = [u3, C.POINTER(C.c_size_t)]
         L.rtd_dose_warp_t.argtypes = [vp, vp, u3, C.POINTER(abi.RtdWarp), vp, u3, C.c_float, C.c_uint32, vp, C.c_size_t]
         L.rtd_dose_warp_t_kernel_ms.argtypes = [vp, C.POINTER(C.c_float)]
+        L.rtd_dose_warp_sum.argtypes = [vp, vpp, u3, C.POINTER(abi.RtdWarp), abi.c_float_p, C.c_uint32, vp, u3]
+        L.rtd_dose_warp_t_phases_workspace_bytes.argtypes = [u3, C.c_uint32, C.POINTER(C.c_size_t)]
+        L.rtd_dose_warp_t_phases.argtypes = [vp, vp, u3, C.POINTER(abi.RtdWarp), abi.c_float_p, C.c_uint32, vpp, u3, vp, C.c_size_t]
+        L.rtd_optimizer_create_4d.argtypes = [vp, vpp, C.c_uint32, C.POINTER(abi.Rtd4dOptions), vp, C.POINTER(abi.RtdOptimizerOptions), vpp]
         L.rtd_set_let_table.argtypes = [vp, abi.c_float_p, C.c_int32, C.c_int32]
         L.rtd_field_water_depth.argtypes = [vp, vp, vp]
         L.rtd_field_let_influence.argtypes = [vp, vp]
@@ -808,10 +812,13 @@ class Optimizer:
     """rtd_optimizer_*: the resident spectral projected gradient iteration on an Objective of the dose of `fields` (each with a
     dose_influence() matrix). Destroy it before its fields, its objective and its engine."""
 
-    def __init__(self, eng, fields, objective, options=None, scenario_fields=None, mode=None, probabilities=None, voxelwise=False):
+    def __init__(self, eng, fields, objective, options=None, scenario_fields=None, mode=None, probabilities=None, voxelwise=False, phase_warps=None,
+                 phase_weights=None):
         """scenario_fields (a list of per-scenario field lists, scenario 0 the nominal one) makes it a robust optimiser
         (rtd_optimizer_create_robust) in mode abi.RTD_ROBUST_EXPECTED / _WORST_CASE, or with voxelwise=True the voxel-wise worst case
-        (rtd_optimizer_create_voxelwise; mode and probabilities are then not used); `fields` is then ignored."""
+        (rtd_optimizer_create_voxelwise; mode and probabilities are then not used); `fields` is then ignored. With phase_warps (a list
+        of abi.RtdWarp, one per row of scenario_fields) the rows are breathing phases and it is a 4D optimiser
+        (rtd_optimizer_create_4d; phase_weights: one positive weight per phase, None for equal ones)."""
         self.eng = eng
         self.objective = objective
         self._h = C.c_void_p()
@@ -829,6 +836,20 @@ class Optimizer:
             raise ValueError("every scenario needs the same number of fields")
         flat = [f._h for fs in self.scenario_fields for f in fs]
         arr = (C.c_void_p * max(1, len(flat)))(*flat)
+        if phase_warps is not None:
+            fo = abi.Rtd4dOptions()
+            fo.n_phases = len(self.scenario_fields)
+            if len(phase_warps) != len(self.scenario_fields):
+                raise ValueError("one warp per phase")
+            self._warps = (abi.RtdWarp * max(1, len(phase_warps)))(*phase_warps)
+            fo.warps = self._warps
+            if phase_weights is not None:
+                pw = np.ascontiguousarray(phase_weights, dtype=np.float32).reshape(-1)
+                if pw.size != len(self.scenario_fields):
+                    raise ValueError("one weight per phase")
+                fo.weights = abi.fptr(pw)
+            eng._check(lib().rtd_optimizer_create_4d(eng._h, arr, n_fields, C.byref(fo), objective._h, po, C.byref(self._h)))
+            return
         if voxelwise:
             eng._check(lib().rtd_optimizer_create_voxelwise(eng._h, arr, n_fields, len(self.scenario_fields), objective._h, po, C.byref(self._h)))
             return
@@ -1182,6 +1203,13 @@ class Engine:
         dose that is worst for it). scenario_fields as create_robust_optimizer; the objective must not have DVH or EUD terms."""
         return Optimizer(self, None, objective, options, scenario_fields=scenario_fields, voxelwise=True)
 
+    def create_4d_optimizer(self, phase_fields, warps, objective, weights=None, options=None):
+        """rtd_optimizer_create_4d: phase_fields is a list of per-phase field lists (the same beams computed on every phase's CT, each
+        with a dose_influence() matrix, all on one dose grid); warps one abi.RtdWarp per phase, reference voxel -> that phase's dose
+        grid, its field already on the device (raytracedicom_amd.fourd.phase_warps) and alive as long as the optimiser; the objective
+        lives on the reference grid; weights: the time spent in each phase (None: equal)."""
+        return Optimizer(self, None, objective, options, scenario_fields=phase_fields, phase_warps=list(warps), phase_weights=weights)
+
     def dose_extremes(self, dose_ptrs, n_voxels, d_min=None, d_max=None):
         """rtd_scenario_dose_extremes: d_min[v] / d_max[v] (device pointers of float32[n_voxels], either may be None) = the smallest /
         largest of the scenario volumes dose_ptrs at v; asynchronous. Point Objective.dvh and .dose_at_volume at them for worst-case
@@ -1469,6 +1497,101 @@ class Engine:
         finally:
             self.sync()
             self.device_free(d_dst)
+
+    # the warps over a phase axis (include/rtd.h "4D dose: phases warped and summed")
+    @staticmethod
+    def _phase_arrays(ptrs, warps, weights):
+        n = len(warps)
+        if not (len(ptrs) == len(weights) == n):
+            raise ValueError("as many volumes as warps and weights")
+        arr = (C.c_void_p * max(1, n))(*[int(p) if p else None for p in ptrs])
+        wa = (abi.RtdWarp * max(1, n))(*warps)
+        wt = np.ascontiguousarray(weights, dtype=np.float32).reshape(-1)
+        return arr, wa, wt, n
+
+    def warp_sum_device(self, src_ptrs, src_dims, warps, weights, dst_ptr, dst_dims):
+        """rtd_dose_warp_sum: dst = sum_p weights[p] * warp_p(src_p) in one launch, bit for bit the sequence of warp_dose_device calls
+        (phase 0 written, the others accumulated). src_ptrs: float32 device volumes on src_dims; warps: abi.RtdWarp records."""
+        arr, wa, wt, n = self._phase_arrays(src_ptrs, warps, weights)
+        self._check(lib().rtd_dose_warp_sum(self._h, arr, abi.uint3(src_dims), wa, abi.fptr(wt) if wt.size else None, n,
+                                            C.c_void_p(int(dst_ptr)) if dst_ptr else None, abi.uint3(dst_dims)))
+
+    def warp_sum(self, doses, warps, weights, dst_dims):
+        """The host float32 volumes `doses` ([Z][Y][X], one grid) summed on dst_dims (x, y, z) through warps, one (maps, dvf) per dose as
+        accumulate_phases takes them -> [Z][Y][X] float32: accumulate_phases's bits from one launch."""
+        if not (len(doses) == len(warps) == len(weights)) or not doses:
+            raise RtdError(abi.RTD_ERR_INVALID_ARG, "warp_sum: as many doses as warps and weights, and at least one")
+        srcs = [abi.f32(d) for d in doses]
+        assert all(s.ndim == 3 and s.shape == srcs[0].shape for s in srcs)
+        out = np.empty((int(dst_dims[2]), int(dst_dims[1]), int(dst_dims[0])), dtype=np.float32)
+        bufs, recs, ptrs = [], [], []
+        try:
+            for src, (maps, dvf) in zip(srcs, warps):
+                d_dvf, dvf_dims = self._upload_dvf(dvf)
+                bufs.append(d_dvf)
+                d_src = self.device_alloc(src.nbytes)
+                bufs.append(d_src)
+                self.to_device(d_src, src)
+                recs.append(abi.make_warp(*maps, d_dvf, dvf_dims))
+                ptrs.append(d_src)
+            d_dst = self.device_alloc(out.nbytes)
+            bufs.append(d_dst)
+            self.warp_sum_device(ptrs, (srcs[0].shape[2], srcs[0].shape[1], srcs[0].shape[0]), recs, weights, d_dst, dst_dims)
+            self.to_host(out, d_dst)
+            return out
+        finally:
+            self.sync()
+            for p in bufs:
+                self.device_free(p)
+
+    @staticmethod
+    def warp_t_phases_workspace_bytes(src_dims, n):
+        """rtd_dose_warp_t_phases_workspace_bytes: n slices of warp_t_workspace_bytes(src_dims)."""
+        b = C.c_size_t(0)
+        if lib().rtd_dose_warp_t_phases_workspace_bytes(abi.uint3(src_dims), int(n), C.byref(b)) != abi.RTD_OK:
+            raise RtdError(abi.RTD_ERR_INVALID_ARG, "warp_t_phases_workspace_bytes: a zero dimension, more than 2^31 - 1 voxels, or not 1 to 16 phases")
+        return int(b.value)
+
+    def warp_dose_t_phases_device(self, g_dst_ptr, dst_dims, warps, weights, g_src_ptrs, src_dims, workspace_ptr, workspace_bytes):
+        """rtd_dose_warp_t_phases: g_src_ptrs[p] = weights[p] * W_p^T g, bit for bit warp_dose_t_device per phase, in four operations.
+        workspace_ptr: device memory of at least warp_t_phases_workspace_bytes(src_dims, len(warps)) bytes, the caller's."""
+        arr, wa, wt, n = self._phase_arrays(g_src_ptrs, warps, weights)
+        self._check(lib().rtd_dose_warp_t_phases(self._h, C.c_void_p(int(g_dst_ptr)) if g_dst_ptr else None, abi.uint3(dst_dims), wa,
+                                                 abi.fptr(wt) if wt.size else None, n, arr, abi.uint3(src_dims),
+                                                 C.c_void_p(int(workspace_ptr)) if workspace_ptr else None, int(workspace_bytes)))
+
+    def warp_dose_t_phases(self, g, warps, weights, src_dims):
+        """The host gradient g ([Z][Y][X] float32 on the destination grid) pushed back through every (maps, dvf) of warps -> a list of
+        [Z][Y][X] float32 volumes on src_dims (x, y, z), one per phase. The workspace is allocated here."""
+        if len(warps) != len(weights) or not warps:
+            raise RtdError(abi.RTD_ERR_INVALID_ARG, "warp_dose_t_phases: as many warps as weights, and at least one")
+        g = abi.f32(g)
+        assert g.ndim == 3
+        shape = (int(src_dims[2]), int(src_dims[1]), int(src_dims[0]))
+        outs = [np.empty(shape, dtype=np.float32) for _ in warps]
+        bufs, recs, ptrs = [], [], []
+        try:
+            for out, (maps, dvf) in zip(outs, warps):
+                d_dvf, dvf_dims = self._upload_dvf(dvf)
+                bufs.append(d_dvf)
+                d_out = self.device_alloc(out.nbytes)
+                bufs.append(d_out)
+                recs.append(abi.make_warp(*maps, d_dvf, dvf_dims))
+                ptrs.append(d_out)
+            d_g = self.device_alloc(g.nbytes)
+            bufs.append(d_g)
+            self.to_device(d_g, g)
+            nws = self.warp_t_phases_workspace_bytes(src_dims, len(warps))
+            d_ws = self.device_alloc(nws)
+            bufs.append(d_ws)
+            self.warp_dose_t_phases_device(d_g, (g.shape[2], g.shape[1], g.shape[0]), recs, weights, ptrs, src_dims, d_ws, nws)
+            for out, d_out in zip(outs, ptrs):
+                self.to_host(out, d_out)
+            return outs
+        finally:
+            self.sync()
+            for p in bufs:
+                self.device_free(p)
 
     def quantize_dose_device(self, dose_ptr, n_voxels, out_ptr, bits=16, scaling=0.0):
         """rtd_dose_quantize on device buffers -> (scaling used, n_clamped); synchronous."""
