@@ -330,6 +330,11 @@ int rtd_set_stream(rtd_handle h, void* hip_stream);
  * "trace_reused" int32[1]: 1 if the last launched compute reused the field's trace and plan (see rtd_field_compute).
  * "sigma_reused" int32[1]: the sigma recurrence of the last launched compute: 0 walked, 1 recorded and replayed, 2 replayed.
  * "dose_reused" int32[1]: the dose walk of the last launched compute, likewise (never ahead of "sigma_reused").
+ * "launch_builds" int32[4]: which kernel builds the field's last launched tracer and fill were (a host record; -1 before the first):
+ *   [0] the tracer's sampling kernel after the LDS fallbacks: 0 plain, 1 along-beam, 2 diagonal;
+ *   [1] 1 if the fill staged the layer's cumulative-IDD rows in LDS, 0 if it read them from global memory (or looked none up);
+ *   [2] the fill's mode: 0 walked, 1 sigma replayed and dose walked, 2 both replayed;
+ *   [3] 1 for the NUCLEAR_CORR build of the fill.
  * "target_bev" and "target_hit": see rtd_field_project_target below.
  * Returns the number of bytes the buffer holds via *bytes_needed when host_out is NULL.
  */

@@ -264,6 +264,8 @@ int rtd_copy_to_host(rtd_handle hh, void* d, const void* s, size_t bytes) {
     return RTD_OK;
 }
 
+constexpr size_t kTraceLutLdsMax = 160 * 1024;   // a block's LDS on gfx950: what k_trace_sample's staged tables may take (launchTrace)
+
 int rtd_set_luts(rtd_handle hh, const rtd_luts* l) {   // kernel_wrapper.cu:453-537
     auto* h = reinterpret_cast<rtd_handle_impl*>(hh);
     if (h) ++h->inputEpoch;
@@ -272,6 +274,12 @@ int rtd_set_luts(rtd_handle hh, const rtd_luts* l) {   // kernel_wrapper.cu:453-
         l->n_rrl_samples <= 0 || !l->energies_per_u || !l->peak_depths || !l->scale_facts || !l->cidd_matrix ||
         !l->density_vector || !l->sp_vector || !l->rrl_vector)
         return fail(h, RTD_ERR_INVALID_ARG, "rtd_set_luts: empty or null table");
+    // every tracer kernel stages the density and stopping-power tables in its block's LDS (rtd_trace.hpp): tables beyond a block's
+    // 160 KiB have no kernel that could be launched. Refused here, where the sizes are first known; the handle keeps the tables it has.
+    if (((size_t)l->n_density_samples + (size_t)l->n_sp_samples) * sizeof(float) > kTraceLutLdsMax)
+        return fail(h, RTD_ERR_INVALID_ARG, "rtd_set_luts: the density and stopping-power tables have " +
+                    std::to_string((size_t)l->n_density_samples + (size_t)l->n_sp_samples) + " entries together; the tracer stages them in LDS and takes at most " +
+                    std::to_string(kTraceLutLdsMax / sizeof(float)) + " (160 KiB)");
     RTD_HIP(h, hipSetDevice(h->device));
     const size_t nC = (size_t)l->n_energies * l->n_energy_samples, nD = l->n_density_samples, nS = l->n_sp_samples, nR = l->n_rrl_samples;
     const bool nuc = l->nuc_weight_matrix && l->nuc_sq_sigma_matrix;    // NUCLEAR_CORR tables (energy_struct.h:33-36), optional
@@ -746,6 +754,7 @@ static int launchTrace(const ComputeJob& c) {
     const size_t dLds = lutLds + (size_t)3 * kTdSteps * kTdPitch * sizeof(float);
     if (f->traceMode == 2 && dLds <= 150 * 1024) {
         RTD_HIP(h, raiseLdsCap(h, k_trace_sample_d, dLds));
+        f->launchBuilds[0] = 2;
         launchK(k_trace_sample_d, dim3((unsigned)(fc.W / kTdRays), (unsigned)fc.H, (unsigned)((fc.S + kTdSteps - 1) / kTdSteps)), dim3(kTdThreads), dLds, s, f->ev[kEvStart], nullptr,
                 (const float*)h->dCt, (int)h->ctDims[0], (int)h->ctDims[1], (int)h->ctDims[2], h->lut, f->tracer, fc.W, fc.H, f->dDensity, f->dWepl, f->dIdd,
                 f->dRrl, h->rrlScale, f->dState, (const float*)f->dSegPos, f->traceDiagB);
@@ -753,10 +762,15 @@ static int launchTrace(const ComputeJob& c) {
         // the beam runs along the CT x axis: lanes on consecutive steps of one ray (see k_trace_sample_t); 16 rays per block
         // measured best (4 .. 12 rays: 0.107 - 0.133 ms for the stage, 16: 0.100 ms)
         RTD_HIP(h, raiseLdsCap(h, k_trace_sample_t, tLds));
+        f->launchBuilds[0] = 1;
         launchK(k_trace_sample_t, dim3((unsigned)((f->R + kTrRays - 1) / kTrRays)), dim3(64, kTrRays), tLds, s, f->ev[kEvStart], nullptr,
                 (const float*)h->dCt, (int)h->ctDims[0], (int)h->ctDims[1], (int)h->ctDims[2], h->lut, f->tracer, fc.W, fc.H, f->dDensity, f->dWepl, f->dIdd,
                 f->dRrl, h->rrlScale, f->dState);
     } else {
+        // (also the fallback of the two kernels above when the tables and their tile exceed a block's LDS; the tables alone fit:
+        //  rtd_set_luts refuses those that do not)
+        if (lutLds > 64 * 1024) RTD_HIP(h, raiseLdsCap(h, k_trace_sample, lutLds));   // (above the default cap of dynamic LDS only)
+        f->launchBuilds[0] = 0;
         launchK(k_trace_sample, dim3((unsigned)(f->R / 256), (fc.S + kTraceSeg * kTraceSegsPerBlock - 1) / (kTraceSeg * kTraceSegsPerBlock)), dim3(256, kTraceSegsPerBlock), lutLds, s, f->ev[kEvStart], nullptr,
                 (const float*)h->dCt, (int)h->ctDims[0], (int)h->ctDims[1], (int)h->ctDims[2], h->lut, f->tracer, fc.W, fc.H, f->dDensity, f->dWepl, f->dIdd,
                 f->dRrl, h->rrlScale, f->dState, (const float*)f->dSegPos);
@@ -860,6 +874,9 @@ static void launchFill(const ComputeJob& c) {
     const bool ldsLut = fillLds + tabLds <= 56 * 1024;   // (+ ~1 KiB of static arrays: stays under the 64 KiB default cap of a block's LDS)
     // the sigma walk's exchange buffers share the dynamic LDS with the dose walk's LUT rows (fillTabOffset: the kernel's view of the same layout)
     const size_t dynLds = (size_t)fillTabOffset(ldsLut, h->lut.nSamples) * sizeof(float) + tabLds;
+    // (what rtd_field_fetch "launch_builds" reads: a replayed dose step looks nothing up, so that build stages no rows)
+    f->launchBuilds[1] = !c.is.dose && ldsLut ? 1 : 0; f->launchBuilds[2] = c.is.dose ? 2 : (c.is.sigma ? 1 : 0);
+    f->launchBuilds[3] = !c.is.sigma && fc.nuclearCorr ? 1 : 0;
     // the record pass: the sigma walk of every (layer, tile) alone — with a dose record to fill, the dose walk of each as well — in front
     // of the fill that replays it (inside the fill's timing bucket)
     // (k_fill_dr: the kernel that holds the dose record's code; k_fill's builds are what they were without it)
@@ -1357,6 +1374,9 @@ int rtd_field_fetch(rtd_handle hh, rtd_field ff, const char* name, void* host_ou
         const int32_t v = f->computed ? f->memory.flight.dose : 0;        // ... its dose walk likewise
         n = sizeof v; staging.resize(n);
         std::memcpy(staging.data(), &v, n);
+    } else if (nm == "launch_builds") {
+        n = sizeof f->launchBuilds; staging.resize(n);                     // the builds of the last launched tracer and fill (host record)
+        std::memcpy(staging.data(), f->launchBuilds, n);
     } else if (nm == "eff_radius" || nm == "layer_plan") {
         std::vector<LayerPlan> lp(L);
         RTD_HIP(h, hipMemcpy(lp.data(), f->dLayers, L * sizeof(LayerPlan), hipMemcpyDeviceToHost));

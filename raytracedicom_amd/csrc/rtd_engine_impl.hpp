@@ -112,6 +112,10 @@ struct rtd_field_impl {
     TransferParams transfer0{};
     int traceMode = 0;              // tracer: 0 lanes across the rays, 1 along the beam (CT x runs along it), 2 along diagonals of (ray, step) (oblique beams)
     int traceDiagB = 0;             // ... mode 2: steps per ray along a diagonal
+    // Which builds the field's last launchTrace / launchFill chose (rtd_field_fetch "launch_builds"; -1: none launched yet): the tracer
+    // kernel after the LDS fallbacks (0 plain, 1 along-beam, 2 diagonal), 1 if the fill's LUT rows were staged in LDS, the fill's mode
+    // (0 walked, 1 sigma replayed and dose walked, 2 both replayed), 1 for NUCLEAR_CORR. Host only: no kernel reads it.
+    int32_t launchBuilds[4] = {-1, -1, -1, -1};
     int transferMode = 0;           // transfer kernel: lanes of the BEV gathers along dose x (0), y (1) or z (2)
     uint32_t doseDims[3] = {0, 0, 0};
     size_t R = 0;

@@ -21,7 +21,7 @@ _LIB = None
 
 _FETCH_DTYPES = {"first_inside": np.int32, "first_outside": np.int32, "first_passive": np.int32,
                  "eff_radius": np.int32, "tile_radius": np.uint8, "fill_debug": np.int64, "sweep_debug": np.int64, "uniform_debug": np.int64, "sweep_big_debug": np.int64, "scan_debug": np.int64,
-                 "dij_batch": np.int32, "trace_reused": np.int32, "sigma_reused": np.int32, "dose_reused": np.int32, "active": np.int32, "target_bev": np.uint32, "target_hit": np.uint8}
+                 "dij_batch": np.int32, "trace_reused": np.int32, "sigma_reused": np.int32, "dose_reused": np.int32, "launch_builds": np.int32, "active": np.int32, "target_bev": np.uint32, "target_hit": np.uint8}
 
 
 class RtdError(RuntimeError):

@@ -244,9 +244,10 @@ def box_mask(rig, info):
     return m
 
 
-def compare_field(orc, engine, scn, beam, options=None, dose_dims=None, dose_spacing=None):
+def compare_field(orc, engine, scn, beam, options=None, dose_dims=None, dose_spacing=None, inspect=None):
     """One field of the engine against the CPU oracle, stage by stage (the tolerances: tests/test_gpu_parity.py) -> (dose, the
-    oracle's dose, timing, info). dose_dims, dose_spacing: the dose grid of the beam's gantryToDoseIdx when it is not the CT's."""
+    oracle's dose, timing, info). dose_dims, dose_spacing: the dose grid of the beam's gantryToDoseIdx when it is not the CT's.
+    inspect: called with the computed field in front of the comparisons (what a test fetches beyond them, "launch_builds" say)."""
     dose_dims = tuple(scn.dims if dose_dims is None else dose_dims)
     dose_spacing = scn.spacing if dose_spacing is None else dose_spacing
     dose_ref = np.zeros((dose_dims[2], dose_dims[1], dose_dims[0]), dtype=np.float32)
@@ -256,6 +257,8 @@ def compare_field(orc, engine, scn, beam, options=None, dose_dims=None, dose_spa
     try:
         fld = rig.field(beam)
         dose, info, timing = rig.compute(fld)
+        if inspect is not None:
+            inspect(fld)
         oi = of.info
         for k in ("ray_dims", "beam_first_inside", "beam_first_outside", "beam_first_guaranteed_passive",
                   "beam_first_calculated_passive", "bbox_min", "bbox_max", "live_steps", "max_radius"):
@@ -307,9 +310,10 @@ def compare_field(orc, engine, scn, beam, options=None, dose_dims=None, dose_spa
         rig.close()
 
 
-def compare_nuclear_field(orc, engine, scn, opt, dose_dims=None, dose_spacing=None):
+def compare_nuclear_field(orc, engine, scn, opt, dose_dims=None, dose_spacing=None, inspect=None):
     """The scenario's first beam under a nuclear correction against the oracle -> (dose, the oracle's dose, the oracle's info).
-    dose_dims, dose_spacing: the dose grid of the beam's gantryToDoseIdx when it is not the CT's (default)."""
+    dose_dims, dose_spacing: the dose grid of the beam's gantryToDoseIdx when it is not the CT's (default). inspect: as in
+    compare_field."""
     dose_dims = tuple(scn.dims if dose_dims is None else dose_dims)
     dose_spacing = scn.spacing if dose_spacing is None else dose_spacing
     ref = np.zeros((dose_dims[2], dose_dims[1], dose_dims[0]), dtype=np.float32)
@@ -319,6 +323,8 @@ def compare_nuclear_field(orc, engine, scn, opt, dose_dims=None, dose_spacing=No
     try:
         f = rig.field(scn.beams[0])
         dose, info, _ = rig.compute(f)
+        if inspect is not None:
+            inspect(f)
         W, H, L = of.info["ray_dims"]
         S = scn.beams[0].tracerSteps
         # the sigma chain with the variant's constants: radius classes stay bit-exact (over the steps the reference classifies)

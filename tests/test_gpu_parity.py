@@ -362,13 +362,19 @@ def test_seeded_random_scenarios(orc, engine, synth, seed):
 
 @pytest.mark.parametrize("n_samples,n_hu", [(6144, 3072), (2048, 9000)])
 def test_lookup_tables_too_large_for_lds(orc, engine, n_samples, n_hu):
-    """Tables beyond the LDS staging limits take the global-memory paths: k_fill<false> (two cIDD rows + 1/X0 above 48 KiB) and the
-    tail loop of the tracer's LUT staging (density + SP beyond the 4096 entries held in registers)."""
+    """Tables larger than the default ones. (6144, 3072): two cIDD rows of 24 KiB each; with the step table they are 51 200 B, within
+    the 56 KiB that k_fill stages in LDS, so the rows are still in LDS (the case was written when the limit was 40 KiB; the builds that
+    read the rows from global memory are reached by tests/test_gpu_lut_shapes.py, which asks the engine which build ran).
+    (2048, 9000): density + SP of 18 000 entries, beyond the 6144 that k_trace_sample holds in registers: the tail loop of its LUT
+    staging, with 72 000 B of dynamic LDS."""
     from raytracedicom_amd import luts
     big = luts.synth_luts(n_energies=40, n_samples=n_samples, n_hu=n_hu)
     ct, _ = scenarios.hetero_phantom(64)
     scn = scenarios.hetero_ct(big, n=64, spots=5, pitch=7.0, n_layers=3, angles=[15.0], ct=ct)
-    compare_field(orc, engine, scn, scn.beams[0])
+    got = []
+    compare_field(orc, engine, scn, scn.beams[0], inspect=lambda f: got.append([int(v) for v in f.fetch("launch_builds")]))
+    print("(%d, %d): launch_builds %s" % (n_samples, n_hu, got[0]))
+    assert got[0] == [0, 1, 0, 0], got                                # the plain tracer kernel, rows in LDS, a walked fill without the halo
 
 
 def test_c1_bev_dose_against_the_reference_cpu_convolution(orc, rig_of, synth):
