@@ -1624,6 +1624,133 @@ int rtd_planset_blend(rtd_handle h, rtd_planset ps, const double* coeffs, uint32
 int rtd_planset_destroy(rtd_handle h, rtd_planset ps);
 
 /*
+ * ---- L-BFGS with a line search on the device ----
+ *
+ * Additive to the blocks above (RTD_ABI_VERSION stays 3; no entry point, kernel or structure above changes). The spectral iteration
+ * of rtd_optimizer_create has no line search and is not monotone. rtd_optimizer_create_lbfgs returns an ordinary rtd_optimizer whose
+ * iteration is a projected limited-memory quasi-Newton step with a backtracking line search that needs no further matrix product:
+ * between two feasible weight vectors the dose is linear, D (w + a (w_full - w)) = d0 + a (d1 - d0), so after ONE forward product for
+ * the full step the objective at every trial step length is an evaluation of a mixed volume. rtd_optimizer_set_weights, _run, _result,
+ * _weights, _dose and _destroy work on it; an iteration costs the two matrix products of the spectral one (one apply and one apply_t
+ * per field).
+ *
+ * State on the device, owned by the optimiser: w, w_prev, grad, grad_prev, w_best, w_full (float32, n entries, the fields'
+ * [L][ny][nx] maps concatenated in list order); a ring of m pairs s_i, y_i (each the float64 difference of float32 values, rounded
+ * once to float32); the symmetric Gram matrix G (float64, (2m+1)^2) of the basis B = [s_0 .. s_{m-1}, y_0 .. y_{m-1}, ghat], a
+ * pair's place in B being its ring slot; two dose volumes d0 (the tracked dose of w: rtd_optimizer_dose) and d1 and one g volume; a
+ * record of scalars and the history.
+ *
+ * rtd_optimizer_run starts with d0 = sum_f Dij_f w_f when the dose is stale: after creation and after rtd_optimizer_set_weights (host
+ * state known at launch time, not a device decision), by the spectral iteration's rule (step 1 of the block "Dose objectives and the
+ * resident optimiser": the boxes of the fields 1.. cleared, field 0 with init = 1, the others accumulate). Then iteration k, launches
+ * only, no decision on the host:
+ *   1. rtd_objective_eval(d0) -> f_k, g; grad_f = Dij_f^T g per field; history[k] = f_k while k < history_capacity; if f_k < f_best:
+ *      w_best = w, f_best = f_k, best_iteration = k (as the spectral iteration keeps them).
+ *   2. Pair. If the previous iteration moved (a > 0): s = w - w_prev, y = grad - grad_prev. The pair enters the ring iff <s, y> > 0
+ *      and <y, y> > 0 and both are finite; it takes the slot after the newest pair's (mod m), where the oldest pair leaves when the
+ *      ring is full.
+ *   3. Active set. ghat_j = (w_j == 0 && grad_j > 0) ? 0 : grad_j.
+ *   4. One wide reduction: the products of s, y and ghat with every live vector of B, with ghat, s and y themselves: 3 (2m + 3)
+ *      float64 sums (the pair's admission is decided from two of them, so the products with the pair it may replace are taken too),
+ *      and max_j |P(w - grad)_j - w_j| in the cancellation-free form of the spectral iteration. Every sum by the optimiser's fixed
+ *      tree: chunks of 2048 entries, one wave each, lane t adds the products of the entries t, t + 64, ... in order from +0.0
+ *      (entries past n count as +0.0), butterfly (32, ..., 1); the chunk sums are added the same way. G takes the admitted pair's rows
+ *      and columns and the row of ghat.
+ *   5. The two-loop recursion on coefficients over B, every scalar in float64. q = ghat (coefficient 1 on ghat). For the pairs newest
+ *      to oldest: alpha_i = <s_i, q> / <s_i, y_i>, then q -= alpha_i y_i. r = gamma q with gamma = <s, y> / <y, y> of the newest
+ *      pair. For the pairs oldest to newest: beta = <y_i, r> / <s_i, y_i>, then r += (alpha_i - beta) s_i. An inner product <B_i, q>
+ *      is the sum from 0.0 over the live indices j of B ascending of c_j * G[i][j], c the coefficients of q. The result is the
+ *      coefficients delta of r (2m + 1 of them, 0 where a slot is not live). Without pairs delta is gamma0 on ghat alone, gamma0 =
+ *      (initial_step > 0 ? initial_step : (mx > 0 ? 1 / mx : 0) with mx the max of step 4) times the stall factor of step 7.
+ *   6. Direction and full step: dir_j = -(sum over the live i ascending, from 0.0, of delta_i * double(B_i[j])), 0 where j is active
+ *      (w_j == 0 && grad_j > 0); w_full_j = float32(P(double(w_j) + dir_j)), P(x) = x > 0 ? x : +0. The same launch leaves the chunk
+ *      sums of gp = <grad, w_full - w> = sum_j double(grad_j) * (double(w_full_j) - double(w_j)), by the tree of step 4. Then
+ *      d1 = sum_f Dij_f w_full_f, the forward products by the rule above.
+ *   7. Line search over K = 1 + max_halvings trial steps a_k = 2^-k. The trial dose of voxel v: t_0 = double(d1[v]), t_k = double(d0[v])
+ *      + a_k * (double(d1[v]) - double(d0[v])) for k >= 1, no contraction. F_k is the objective of trial k: phi and every sum follow
+ *      rtd_objective_eval's text exactly, so F_0 has the bits of rtd_objective_eval(d1). The first k with F_k <= f_k + (armijo_c1 *
+ *      a_k) * gp is accepted (comparisons with a NaN are false: a trial that is not finite is never accepted). Then w_prev = w,
+ *      grad_prev = grad and, k = 0: w = w_full and d0 = d1, copies of the bits; k >= 1: w_j = float32(double(w_j) + a_k *
+ *      (double(w_full_j) - double(w_j))) and d0[v] = float32(t_k), over the bounding box of the fields' row boxes (outside the row
+ *      boxes both volumes hold +0). After every unit step the tracked dose is the product's own bits; drift can accumulate only over
+ *      consecutive backtracked steps.
+ *      Not (gp < 0): a = 0 and nothing moves. With pairs held the ring is emptied and a reset is counted: the next iteration is a
+ *      projected steepest-descent step. Without pairs the iterate is stationary for that step (gp = 0) and nothing is counted.
+ *      No k accepted: a = 0, a stall is counted. With pairs held the ring is emptied; without pairs the stall factor (1 at the start)
+ *      is multiplied by 2^-K. It returns to 1 at the next accepted step.
+ *      f_k not finite: a = 0, nothing moves, counted in `guarded`; if no finite objective had been seen rtd_optimizer_result answers
+ *      RTD_ERR_INVALID_ARG as it does for the spectral iteration. (w is NOT set back to w_best: no accepted step leads to such an f.)
+ * Fixed summation trees and no float atomics: the same inputs give the same bits across calls, handles, processes and graph replays.
+ *
+ * rtd_optimizer_create_lbfgs  1 .. RTD_OPT_MAX_FIELDS local fields on the objective's dose grid, each with a matrix; options may be
+ *                          NULL (rtd_default_lbfgs_options: memory 8, max_halvings 5, armijo_c1 1e-4, initial_step 0,
+ *                          history_capacity 4096). Runs rtd_field_dose_influence_prepare where it has not run. Synchronous. It notes
+ *                          every field's matrix and the objective: rtd_optimizer_run refuses with RTD_ERR_NOT_READY, before its
+ *                          first launch, once rtd_field_dose_influence has been called again on a field or an ROI or a term has been
+ *                          added to the objective. Such an optimiser can only be destroyed.
+ * rtd_optimizer_set_weights   as before; in addition the ring is emptied and the next run recomputes d0.
+ * rtd_optimizer_result     f_last, f_best, best_iteration, iterations, history_len with their meaning above; step is the accepted a
+ *                          of the last iteration (0: none); guarded counts the iterations whose objective was not finite.
+ * rtd_optimizer_dose       d0: THE TRACKED DOSE OF THE CURRENT w, updated by the last iteration. This differs from the spectral
+ *                          optimiser, whose volume holds the dose of the iterate that entered the last iteration.
+ * rtd_optimizer_lbfgs_report  waits for the stream, like rtd_optimizer_result. RTD_ERR_INVALID_ARG on any other optimiser.
+ * rtd_optimizer_lbfgs_buffers the optimiser's own device arrays, for inspection (read-only; they change with every iteration): no
+ *                          synchronisation. delta: the 2m + 1 coefficients of step 5. gram: row-major (2m+1)^2. ring: [2m][n], the s
+ *                          slots then the y slots. RTD_ERR_INVALID_ARG on any other optimiser.
+ * RTD_ERR_INVALID_ARG: what rtd_optimizer_create refuses of a field list and an objective; an objective with DVH or EUD terms (D_v
+ * and E couple the voxels of a structure, so the K-wide evaluation of step 7 does not apply); memory outside 1 .. 16, max_halvings
+ * above 7, armijo_c1 outside (0, 0.5), an initial_step that is negative or not finite, a non-zero reserved word.
+ * rtd_optimizer_set_let_objective, rtd_optimizer_set_rbe, rtd_optimizer_scenario_values and _scenario_dose refuse such an optimiser
+ * with RTD_ERR_INVALID_ARG. RTD_ERR_NOT_READY: a field without a matrix.
+ *
+ * Out of scope: DVH and EUD terms in the line search; L-BFGS behind the robust, voxel-wise, plan-set, 4D, LET and RBE optimisers;
+ * the Cauchy-point / subspace step of full L-BFGS-B; nuclear_corr and the rtd_plan_* path (as the matrix itself).
+ */
+enum { RTD_LBFGS_MAX_MEMORY = 16, RTD_LBFGS_MAX_HALVINGS = 7 };
+typedef struct rtd_lbfgs_options {
+    uint32_t memory;            /* m: pairs kept, 1 .. RTD_LBFGS_MAX_MEMORY */
+    uint32_t max_halvings;      /* the line search tries K = 1 + max_halvings steps 2^-k; 0 .. RTD_LBFGS_MAX_HALVINGS */
+    double armijo_c1;           /* sufficient decrease, in (0, 0.5) */
+    double initial_step;        /* 0: the first rule of the spectral iteration, 1 / max_j |P(w - grad)_j - w_j|; else that scale */
+    uint32_t history_capacity;  /* objective values kept on the device */
+    int32_t reserved[5];        /* must be 0 */
+} rtd_lbfgs_options;            /* 48 bytes */
+typedef struct rtd_lbfgs_report {
+    uint32_t pairs;             /* pairs held */
+    uint32_t unit_steps;        /* iterations that accepted a = 1 */
+    uint32_t backtracked_steps; /* iterations that accepted a < 1 */
+    uint32_t halvings;          /* sum of k over the backtracked steps */
+    uint32_t resets;            /* gp >= 0 with pairs held: the memory was dropped */
+    uint32_t stalls;            /* no trial step accepted */
+    int32_t last_trial;         /* k of the last iteration, -1: none accepted */
+    int32_t pair_admitted;      /* the last iteration's pair entered the ring ... */
+    int32_t pair_slot;          /* ... at this slot */
+    int32_t ring_head;          /* the slot the next pair takes */
+    double last_step;           /* the last accepted a (0: the last iteration accepted none) */
+    double last_gp;             /* the last directional derivative <grad, w_full - w> */
+    double stall_factor;        /* the factor on gamma0 */
+    double trial_values[8];     /* F_k of the last line search, k < K */
+    int32_t reserved[4];
+} rtd_lbfgs_report;             /* 144 bytes */
+typedef struct rtd_lbfgs_buffers {
+    const float* w;
+    const float* w_prev;
+    const float* grad;
+    const float* grad_prev;
+    const float* w_full;
+    const float* ring;
+    const float* trial_dose;    /* d1 */
+    const double* gram;
+    const double* delta;
+    uint32_t n, memory, n_chunks, n_trials;
+} rtd_lbfgs_buffers;            /* 88 bytes */
+void rtd_default_lbfgs_options(rtd_lbfgs_options* out);
+int rtd_optimizer_create_lbfgs(rtd_handle h, const rtd_field* fields, uint32_t n_fields, rtd_objective obj, const rtd_lbfgs_options* o,
+                               rtd_optimizer* out);
+int rtd_optimizer_lbfgs_report(rtd_handle h, rtd_optimizer opt, rtd_lbfgs_report* r);
+int rtd_optimizer_lbfgs_buffers(rtd_handle h, rtd_optimizer opt, rtd_lbfgs_buffers* b);
+
+/*
  * ---- Multi-GPU plans behind the boundary (SURVEY.md 8(b) "Threading": one handle and one host thread per device) ----
  *
  * rtd_plan is the reference-shaped call on several GPUs of one process: the 4-beam cudaWrapperProtons of the C++ shim uses

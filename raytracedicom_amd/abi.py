@@ -268,6 +268,47 @@ class Rtd4dOptions(C.Structure):
                 ("reserved", C.c_int32 * 4)]
 
 
+RTD_LBFGS_MAX_MEMORY, RTD_LBFGS_MAX_HALVINGS = 16, 7
+
+
+class RtdLbfgsOptions(C.Structure):
+    """rtd_lbfgs_options: memory m, max_halvings (K = 1 + max_halvings trial steps 2^-k), armijo_c1, initial_step (0: the spectral
+    iteration's first rule), history_capacity (48 bytes)."""
+    _fields_ = [("memory", C.c_uint32), ("max_halvings", C.c_uint32), ("armijo_c1", C.c_double), ("initial_step", C.c_double),
+                ("history_capacity", C.c_uint32), ("reserved", C.c_int32 * 5)]
+
+
+class RtdLbfgsReport(C.Structure):
+    """rtd_lbfgs_report: what the line search and the memory of an L-BFGS optimiser did so far (144 bytes)."""
+    _fields_ = [("pairs", C.c_uint32), ("unit_steps", C.c_uint32), ("backtracked_steps", C.c_uint32), ("halvings", C.c_uint32),
+                ("resets", C.c_uint32), ("stalls", C.c_uint32), ("last_trial", C.c_int32), ("pair_admitted", C.c_int32),
+                ("pair_slot", C.c_int32), ("ring_head", C.c_int32), ("last_step", C.c_double), ("last_gp", C.c_double),
+                ("stall_factor", C.c_double), ("trial_values", C.c_double * 8), ("reserved", C.c_int32 * 4)]
+
+    def as_dict(self):
+        d = {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
+        d["trial_values"] = list(d["trial_values"])
+        return d
+
+
+class RtdLbfgsBuffers(C.Structure):
+    """rtd_lbfgs_buffers: the device arrays of an L-BFGS optimiser, for inspection (88 bytes)."""
+    _fields_ = [("w", C.c_void_p), ("w_prev", C.c_void_p), ("grad", C.c_void_p), ("grad_prev", C.c_void_p), ("w_full", C.c_void_p),
+                ("ring", C.c_void_p), ("trial_dose", C.c_void_p), ("gram", C.c_void_p), ("delta", C.c_void_p),
+                ("n", C.c_uint32), ("memory", C.c_uint32), ("n_chunks", C.c_uint32), ("n_trials", C.c_uint32)]
+
+
+def default_lbfgs_options():
+    """rtd_default_lbfgs_options: 8 pairs, 5 halvings (K = 6), c1 = 1e-4, the spectral iteration's first step rule."""
+    o = RtdLbfgsOptions()
+    o.memory = 8
+    o.max_halvings = 5
+    o.armijo_c1 = 1e-4
+    o.initial_step = 0.0
+    o.history_capacity = 4096
+    return o
+
+
 class RtdRbeTissue(C.Structure):
     """rtd_rbe_tissue: photon alpha_x (1/Gy), beta_x (1/Gy^2) and the lines RBEmax / RBEmin = c[0] + c[1] * LETd (32 bytes)."""
     _fields_ = [("alpha_x", C.c_float), ("beta_x", C.c_float), ("rbe_max", C.c_float * 2), ("rbe_min", C.c_float * 2),

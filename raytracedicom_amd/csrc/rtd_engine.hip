@@ -54,6 +54,7 @@
 #include "rtd_let.hpp"
 #include "rtd_rbe.hpp"
 #include "rtd_planset.hpp"
+#include "rtd_lbfgs.hpp"
 #include "rtd_field_memory.hpp"
 #include "rtd_field_matrix.hpp"
 #include "rtd_engine_impl.hpp"
@@ -1470,3 +1471,4 @@ int rtd_compute(rtd_handle hh, const rtd_beam* beams, int n_beams, float* dose_i
 #include "rtd_rbe_host.hpp"
 #include "rtd_planset_host.hpp"
 #include "rtd_fourd_host.hpp"
+#include "rtd_lbfgs_host.hpp"

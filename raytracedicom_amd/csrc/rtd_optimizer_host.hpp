@@ -53,6 +53,16 @@ struct rtd_optimizer_impl {
     DevBuf<unsigned char> dWarpWs;          // nScen slices of rtd_dose_warp_t_workspace_bytes(phaseDims)
     std::vector<unsigned> matEpoch;
     std::vector<size_t> matChunks;
+    // An L-BFGS optimiser (section 27; rtd_optimizer_create_lbfgs in rtd_lbfgs_host.hpp allocates all of it): a plain optimiser whose
+    // iteration is lbfgsRun. dDose is the tracked dose d0 of w, dLbTrialDose the dose d1 of the full step. dLbVec: the ring of m pairs
+    // (s slots, then y slots) | s | y | ghat | w_full, n each. lbBox: the union of the fields' row boxes. matEpoch / matChunks as above.
+    bool lbfgs = false, lbDoseStale = false;
+    rtd_lbfgs_options lbOpt{};
+    unsigned lbObjEpoch = 0;
+    DijBox lbBox{0, 0, 0, 0, 0, 0};
+    DevBuf<float> dLbTrialDose, dLbVec;
+    DevBuf<double> dLbGram, dLbPart, dLbGp, dLbLine;
+    DevBuf<LbState> dLbState;
     rtd_field_impl* const* row(int s) const { return sfields.data() + (size_t)s * fields.size(); }
     rtd_field_impl* sf(int s, size_t i) const { return row(s)[i]; }
     float* w() const { return dVec; }
@@ -97,6 +107,9 @@ int rbeOptBackward(rtd_handle_impl* h, rtd_optimizer_impl* p);
 bool fourdMatricesStand(const rtd_optimizer_impl* p);
 int fourdJoin(rtd_handle hh, rtd_optimizer_impl* p);
 int fourdSplit(rtd_handle hh, rtd_optimizer_impl* p);
+// Section 27 (rtd_lbfgs_host.hpp, included later): the iteration of an L-BFGS optimiser, and what rtd_optimizer_set_weights means to it.
+int lbfgsRun(rtd_handle hh, rtd_optimizer_impl* p, uint32_t n_iterations);
+int lbfgsWeightsSet(rtd_handle_impl* h, rtd_optimizer_impl* p);
 
 // The same two products over the scenario axis (section 14; kernels in rtd_robust.hpp). Batched: per field position one launch covers
 // every scenario. Unbatched (RTD_ROBUST_NO_BATCH): the single-matrix launches, scenario by scenario. Either way scenario s's volume
@@ -371,6 +384,7 @@ int rtd_optimizer_scenario_values(rtd_handle hh, rtd_optimizer pp, double* value
     auto* p = reinterpret_cast<rtd_optimizer_impl*>(pp);
     if (!h) return RTD_ERR_INVALID_ARG;
     if (!p || !values) return fail(h, RTD_ERR_INVALID_ARG, "rtd_optimizer_scenario_values: null pointer");
+    if (p->lbfgs) return fail(h, RTD_ERR_INVALID_ARG, "rtd_optimizer_scenario_values: not available for an L-BFGS optimiser");
     RTD_HIP(h, hipSetDevice(h->device));
     if (!p->robust || p->fourd) {             // (a 4D optimiser answers as a composite: f_p = f_last, lambda 1.0, worst 0)
         OptState st{};
@@ -393,6 +407,7 @@ int rtd_optimizer_scenario_dose(rtd_handle hh, rtd_optimizer pp, uint32_t scenar
     auto* p = reinterpret_cast<rtd_optimizer_impl*>(pp);
     if (!h) return RTD_ERR_INVALID_ARG;
     if (!p || !dev_dose) return fail(h, RTD_ERR_INVALID_ARG, "rtd_optimizer_scenario_dose: null pointer");
+    if (p->lbfgs) return fail(h, RTD_ERR_INVALID_ARG, "rtd_optimizer_scenario_dose: not available for an L-BFGS optimiser");
     if (scenario >= (uint32_t)p->nScen) return fail(h, RTD_ERR_INVALID_ARG, "rtd_optimizer_scenario_dose: scenario index out of range");
     *dev_dose = p->doseS[scenario];
     return RTD_OK;
@@ -408,6 +423,7 @@ int rtd_optimizer_set_weights(rtd_handle hh, rtd_optimizer pp, uint32_t field_in
     const size_t cnt = (size_t)(p->offset[field_index + 1] - p->offset[field_index]) * sizeof(float);
     RTD_HIP(h, hipMemcpyAsync(p->w() + p->offset[field_index], dev_w, cnt, hipMemcpyDeviceToDevice, h->stream));
     if (!p->launched) RTD_HIP(h, hipMemcpyAsync(p->wBest() + p->offset[field_index], dev_w, cnt, hipMemcpyDeviceToDevice, h->stream));
+    if (p->lbfgs) return lbfgsWeightsSet(h, p);
     return RTD_OK;
 }
 
@@ -417,6 +433,7 @@ int rtd_optimizer_run(rtd_handle hh, rtd_optimizer pp, uint32_t n_iterations) {
     if (!h) return RTD_ERR_INVALID_ARG;
     if (!p) return fail(h, RTD_ERR_INVALID_ARG, "rtd_optimizer_run: null pointer");
     if (p->obj->terms.empty()) return fail(h, RTD_ERR_INVALID_ARG, "rtd_optimizer_run: the objective has no terms");
+    if (p->lbfgs) return lbfgsRun(hh, p, n_iterations);
     if (p->letObj || p->rbe)                                          // (in front of the first launch: a refused run launches nothing)
         for (const rtd_field_impl* f : p->fields)
             if (!letReady(h, f))

@@ -172,6 +172,11 @@ def lib():
         L.rtd_planset_values.argtypes = [vp, vp, C.POINTER(C.c_double)]
         L.rtd_planset_blend.argtypes = [vp, vp, C.POINTER(C.c_double), C.c_uint32, C.c_int, vp]
         L.rtd_planset_destroy.argtypes = [vp, vp]
+        L.rtd_default_lbfgs_options.argtypes = [C.POINTER(abi.RtdLbfgsOptions)]
+        L.rtd_default_lbfgs_options.restype = None
+        L.rtd_optimizer_create_lbfgs.argtypes = [vp, vpp, C.c_uint32, vp, C.POINTER(abi.RtdLbfgsOptions), vpp]
+        L.rtd_optimizer_lbfgs_report.argtypes = [vp, vp, C.POINTER(abi.RtdLbfgsReport)]
+        L.rtd_optimizer_lbfgs_buffers.argtypes = [vp, vp, C.POINTER(abi.RtdLbfgsBuffers)]
         L.rtd_host_register.argtypes = [vp, C.c_size_t]
         L.rtd_host_unregister.argtypes = [vp]
         L.rtd_plan_create.argtypes = [C.POINTER(C.c_int), C.c_int, vpp]
@@ -813,20 +818,25 @@ class Optimizer:
     dose_influence() matrix). Destroy it before its fields, its objective and its engine."""
 
     def __init__(self, eng, fields, objective, options=None, scenario_fields=None, mode=None, probabilities=None, voxelwise=False, phase_warps=None,
-                 phase_weights=None):
+                 phase_weights=None, lbfgs=False):
         """scenario_fields (a list of per-scenario field lists, scenario 0 the nominal one) makes it a robust optimiser
         (rtd_optimizer_create_robust) in mode abi.RTD_ROBUST_EXPECTED / _WORST_CASE, or with voxelwise=True the voxel-wise worst case
         (rtd_optimizer_create_voxelwise; mode and probabilities are then not used); `fields` is then ignored. With phase_warps (a list
         of abi.RtdWarp, one per row of scenario_fields) the rows are breathing phases and it is a 4D optimiser
-        (rtd_optimizer_create_4d; phase_weights: one positive weight per phase, None for equal ones)."""
+        (rtd_optimizer_create_4d; phase_weights: one positive weight per phase, None for equal ones). With lbfgs=True it is the
+        L-BFGS iteration with its line search on the device (rtd_optimizer_create_lbfgs; options: an abi.RtdLbfgsOptions or None)."""
         self.eng = eng
         self.objective = objective
         self._h = C.c_void_p()
+        self.is_lbfgs = bool(lbfgs)
         po = C.byref(options) if options is not None else None
         if scenario_fields is None:
             self.fields = list(fields)
             self.scenario_fields = [self.fields]
             arr = (C.c_void_p * max(1, len(self.fields)))(*[f._h for f in self.fields])
+            if lbfgs:
+                eng._check(lib().rtd_optimizer_create_lbfgs(eng._h, arr, len(self.fields), objective._h, po, C.byref(self._h)))
+                return
             eng._check(lib().rtd_optimizer_create(eng._h, arr, len(self.fields), objective._h, po, C.byref(self._h)))
             return
         self.scenario_fields = [list(fs) for fs in scenario_fields]
@@ -897,10 +907,26 @@ class Optimizer:
         return out
 
     def dose(self):
-        """Device pointer of the optimiser's dose volume: the dose of the iterate that entered the last iteration."""
+        """Device pointer of the optimiser's dose volume: the dose of the iterate that entered the last iteration (an L-BFGS
+        optimiser: the tracked dose of the current weights)."""
         p = C.c_void_p()
         self.eng._check(lib().rtd_optimizer_dose(self.eng._h, self._h, C.byref(p)))
         return int(p.value or 0)
+
+    def lbfgs_report(self):
+        """rtd_optimizer_lbfgs_report: waits; a dict of the pairs held, the unit and backtracked steps, halvings, resets, stalls, the
+        last accepted step, the last directional derivative and the trial values of the last line search. Only on an optimiser from
+        Engine.create_lbfgs_optimizer (RtdError INVALID_ARG otherwise)."""
+        r = abi.RtdLbfgsReport()
+        self.eng._check(lib().rtd_optimizer_lbfgs_report(self.eng._h, self._h, C.byref(r)))
+        return r.as_dict()
+
+    def lbfgs_buffers(self):
+        """rtd_optimizer_lbfgs_buffers: the device pointers and sizes of an L-BFGS optimiser's own arrays (abi.RtdLbfgsBuffers), for
+        inspection."""
+        b = abi.RtdLbfgsBuffers()
+        self.eng._check(lib().rtd_optimizer_lbfgs_buffers(self.eng._h, self._h, C.byref(b)))
+        return b
 
     def set_let_objective(self, let_objective):
         """rtd_optimizer_set_let_objective: a second Objective, evaluated on the LET-weighted dose sum_f N_f w_f (every field needs
@@ -1188,6 +1214,12 @@ class Engine:
 
     def create_optimizer(self, fields, objective, options=None):
         return Optimizer(self, fields, objective, options)
+
+    def create_lbfgs_optimizer(self, fields, objective, options=None):
+        """rtd_optimizer_create_lbfgs: an Optimizer whose iteration is L-BFGS with a backtracking line search on the device (the
+        objective must not have DVH or EUD terms); options: an abi.RtdLbfgsOptions (abi.default_lbfgs_options) or None. It also has
+        .lbfgs_report()."""
+        return Optimizer(self, fields, objective, options, lbfgs=True)
 
     def create_planset(self, fields, objective, variants, options=None):
         """rtd_planset_create: len(variants) plans on `fields` under variants of `objective` (PlanSet)."""
