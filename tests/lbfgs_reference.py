@@ -79,12 +79,22 @@ def trial_doses(d0, d1, K):
 
 def objective_tree_value(obj, t):
     """The objective of the float64 trial dose t by the evaluation's tree -> float (the bits of values[0])."""
+    f = 0.0
+    with np.errstate(over="ignore", invalid="ignore"):
+        for v in objective_tree_terms(obj, t):
+            f = f + v
+    return float(f)
+
+
+def objective_tree_terms(obj, t):
+    """The terms of the objective of the float64 trial dose t by the evaluation's tree -> [wn_t * sum phi_t, ...] (the bits of
+    values[1:]); the objective is their sum in term order from +0.0."""
     t = np.asarray(t, dtype=np.float64).reshape(-1)
     u = np.flatnonzero(obj.union())
     n_blocks = -(-u.size // 256)
     pos = np.full(obj.n_voxels, -1, dtype=np.int64)
     pos[u] = np.arange(u.size)
-    f = 0.0
+    out = []
     with np.errstate(over="ignore", invalid="ignore"):
         for kind, roi, weight, level in obj.terms:
             idx = obj.rois[roi]
@@ -104,8 +114,8 @@ def objective_tree_value(obj, t):
             w = _butterfly(phi.reshape(-1, 64)).reshape(n_blocks, 4)
             blocks = (w[:, 0] + w[:, 1]) + (w[:, 2] + w[:, 3])
             acc = float(_butterfly(_lane_sums(_pad(blocks, 64).reshape(1, -1)))[0])
-            f = f + wn * acc
-    return float(f)
+            out.append(float(wn * acc))
+    return out
 
 
 def rounding_rise_bound(obj, d):
@@ -132,6 +142,12 @@ def two_loop_vectors(pairs, ghat, dot=plain_dot):
         b = dot(y, r) / dot(s, y)
         r = r + (a - b) * np.asarray(s, dtype=np.float64)
     return r
+
+
+def event_letter(r):
+    """The one-letter record of a step() result: R the memory was dropped (no descent with pairs held), S no trial was accepted, . nothing
+    moved without a stall (no descent without pairs, or the guard), else the accepted trial index."""
+    return "R" if r.get("reset") else "S" if r.get("stall") else "." if r["k"] < 0 else str(r["k"])
 
 
 class LbfgsReference:
@@ -211,6 +227,19 @@ class LbfgsReference:
         for j in live:
             delta[j] = cq[j]
         return delta
+
+    def set_weights(self, w):
+        """rtd_optimizer_set_weights on an L-BFGS optimiser (k_lb_forget and lbDoseStale): w - w_prev is no pair and the pairs held
+        are dropped, the tracked dose is stale (the next step takes d0 from outside or forms the product itself). The ring head, the
+        stall factor, the history, f_best with its iterate and the counters stay."""
+        w = np.asarray(w).reshape(-1).astype(self.ft)
+        assert w.size == self.n
+        self.w = w
+        if not self.history:                                           # (before the first iteration the start is also the best iterate)
+            self.w_best = w.copy()
+        self.moved = False
+        self.count = 0
+        self.d0 = None
 
     # -- one iteration ----------------------------------------------------------------------------------------------------------
     def step(self, d0=None, d1=None, grad=None, f=None):

@@ -3,6 +3,7 @@ their device arrays, the restatement beside them, and the step-by-step compariso
 import numpy as np
 
 import lbfgs_reference as LB
+import optimizer_reference as R
 import tree_reference as T
 from gpu_plan_rigs import OptimizerRig
 from gpu_support import bits, row_bound
@@ -33,6 +34,23 @@ class LbfgsRig(OptimizerRig):
         self.n = sum(self.sizes)
         self.dScratch = self.alloc(4 * self.nvox)
         self.dG = self.alloc(4 * self.nvox)
+
+    def set_objective(self, terms, rois):
+        """Another objective in place of the rig's: terms [(kind, roi, weight, level), ...] over the ROI masks (or index lists) `rois`,
+        built as the engine's objective (self.obj) and as the ReferenceObjective (self.ref). The optimisers made on the objective it
+        replaces are destroyed with it."""
+        for o in self.opts:
+            o.destroy()
+        self.opts = []
+        self.obj.destroy()
+        self.obj = self.eng.create_objective(self.dims)
+        self.ref = R.ReferenceObjective(self.nvox)
+        for m in rois:
+            self.obj.add_roi(m)
+            self.ref.add_roi(m)
+        for t in terms:
+            self.obj.add_term(*t)
+            self.ref.add_term(*t)
 
     def lbfgs(self, start=None, **kw):
         o = self.eng.create_lbfgs_optimizer(self.fields, self.obj, lbfgs_options(**kw) if kw else None)
@@ -137,3 +155,25 @@ def step_and_compare(rig, opt, ref, k, d0):
         assert np.array_equal(bits(dev["ring"][h]), bits(s)) and np.array_equal(bits(dev["ring"][m + h]), bits(y))
     assert dev["gram"][2 * m, 2 * m] == out["dots"]["gg"]
     return out, dose
+
+
+def drive(rig, opt, ref, n):
+    """The next n iterations of opt and ref (both have done the same number so far) through step_and_compare, the tracked dose threaded
+    from one to the next; the first takes the restatement's tracked dose, or, where that is stale (a fresh run, after set_weights),
+    the device's product of the weights. Every record also gets what the device reported after its iteration ("lb":
+    rtd_optimizer_lbfgs_report, "delta_dev": the device's coefficients, "hist": its history value, "w" and "dose": the weights and
+    the tracked dose it left) and the pairs held entering it ("pairs_in"). -> (the event letters, the records)."""
+    marks, records = "", []
+    d0 = ref.d0 if ref.d0 is not None else rig.product(ref.w)
+    k0 = len(ref.history)
+    for k in range(k0, k0 + n):
+        pairs_in = ref.count
+        out, d0 = step_and_compare(rig, opt, ref, k, d0)
+        out["pairs_in"] = pairs_in
+        out["lb"] = opt.lbfgs_report()
+        out["delta_dev"] = rig.peek(opt)["delta"]
+        out["hist"] = float(opt.result()[1][k])
+        out["w"], out["dose"] = ref.w.copy(), d0                       # (after the iteration; the device's, bit for bit)
+        marks += LB.event_letter(out)
+        records.append(out)
+    return marks, records

@@ -60,8 +60,12 @@ def events(o, n):
     out = []
     for _ in range(n):
         r = o.step()
-        out.append((r, "R" if r.get("reset") else "S" if r.get("stall") else "." if r["k"] < 0 else str(r["k"])))
+        out.append((r, LB.event_letter(r)))
     return out
+
+
+def letters(o, n):
+    return "".join(e for _, e in events(o, n))
 
 
 def two_loop_bound(pairs, ghat, m):
@@ -229,3 +233,140 @@ def test_reset_path():
     assert nxt["pairs"] == 0 and not nxt["admitted"] and np.all(nxt["delta"][:6] == 0.0) and nxt["delta"][6] > 0.0
     assert o.history[k + 1] == o.history[k]
     assert nxt["k"] >= 0 and o.history[k + 2] < o.history[k + 1], marks
+
+
+def test_event_letters(plan):
+    assert LB.event_letter({"k": -1, "reset": True}) == "R" and LB.event_letter({"k": -1, "stall": True}) == "S"
+    assert LB.event_letter({"k": -1}) == "." and LB.event_letter({"k": -1, "guard": True}) == "."
+    assert [LB.event_letter({"k": k}) for k in range(8)] == list("01234567")
+    # ... and on records of step(): a stall, then a backtracked step (test_backtrack_and_stall_paths' run); a guarded start
+    o = plan.lbfgs(np.full(COLS, 100.0), memory=8, initial_step=1e3, tree=True)
+    r0, r1 = o.step(), o.step()
+    assert LB.event_letter(r0) == "S" and LB.event_letter(r1) == str(r1["k"]) and r1["k"] >= 1
+    g = plan.lbfgs(np.full(COLS, np.inf), tree=True)
+    assert LB.event_letter(g.step()) == "." and g.guarded == 1
+
+
+def test_set_weights(plan):
+    """set_weights is k_lb_forget plus a stale dose: the pairs are dropped and w - w_prev is no pair; the ring head, the stall factor,
+    the history, f_best with its iterate and the counters stay. The next iteration is a first-rule step from the new weights'
+    product, and the one after it admits a pair at the slot the head pointed to."""
+    m = 3
+    o = plan.lbfgs(np.zeros(COLS), memory=m, tree=True)
+    fresh = np.full(COLS, 3.0)
+    o.set_weights(fresh)                                               # before the first iteration: also the best iterate
+    assert np.array_equal(o.w, fresh.astype(np.float32)) and np.array_equal(o.w_best, o.w) and o.d0 is None
+    o.set_weights(np.zeros(COLS))
+    o.run(4)
+    assert o.count == 3 and o.moved and o.head == 0
+    o.run(1)
+    assert o.count == 3 and o.head == 1
+    kept = (o.head, o.stall, list(o.history), o.f_best, o.best_iteration, o.w_best.copy(), o.ring.copy(), o.G.copy(),
+            (o.guarded, o.unit, o.backtracked, o.halvings, o.resets, o.stalls))
+    w_new = (5.0 + 20.0 * np.random.default_rng(3).random(COLS)).astype(np.float32)
+    o.set_weights(w_new)
+    assert not o.moved and o.count == 0 and o.d0 is None and np.array_equal(o.w, w_new)
+    now = (o.head, o.stall, list(o.history), o.f_best, o.best_iteration, o.w_best, o.ring, o.G,
+           (o.guarded, o.unit, o.backtracked, o.halvings, o.resets, o.stalls))
+    for a, b in zip(kept, now):
+        assert np.array_equal(a, b), (a, b)
+    r = o.step()
+    assert r["f"] == o.value(o.forward(w_new).astype(np.float64)) == o.history[5]
+    assert r["pairs"] == 0 and not r["admitted"] and np.all(r["delta"][:2 * m] == 0.0) and r["delta"][2 * m] > 0.0 and o.head == 1
+    assert r["k"] >= 0
+    r = o.step()
+    assert r["admitted"] and r["slot"] == 1 and r["pairs"] == 1 and o.head == 2
+    # the stall factor survives it
+    s = plan.lbfgs(np.full(COLS, 100.0), memory=8, initial_step=1e3, tree=True)
+    assert s.step().get("stall") and s.stall == 2.0 ** -6
+    s.set_weights(np.full(COLS, 90.0))
+    assert s.stall == 2.0 ** -6 and s.stalls == 1
+    assert s.step()["delta"][16] == 1e3 * 2.0 ** -6
+
+
+def mean_only(plan):
+    """A MEAN term over the rows of the matrix, weight 1: the gradient g = A^T (1 / N) does not depend on w. The start is r_j g_j with
+    r_j in (0.5, 3.5) and the first scale 1: every accepted step takes g off, so entry j reaches 0 after ceil(r_j) steps."""
+    rows = np.flatnonzero(plan.A.any(axis=1))
+    p = Problem(plan.A, [(R.MEAN, 0, 1.0, 0.0)], [rows])
+    g = p.rmatvec(p.obj.eval(np.zeros(ROWS))[1])
+    assert np.all(g > 0.0)
+    w0 = ((0.5 + 3.0 * np.random.default_rng(11).random(COLS)) * g).astype(np.float32)
+    return p, w0
+
+
+def test_a_pair_with_y_zero_is_never_admitted(plan):
+    p, w0 = mean_only(plan)
+    for m in (1, 3):
+        o = p.lbfgs(w0, memory=m, initial_step=1.0, tree=True)
+        ev = events(o, 8)
+        marks = "".join(e for _, e in ev)
+        print("MEAN only, m = %d: %s" % (m, marks))
+        assert marks == "0000....", marks
+        for k, (r, e) in enumerate(ev):
+            assert not r["admitted"] and r["pairs"] == 0 and np.all(r["delta"][:2 * m] == 0.0), k
+            if k > 0:
+                assert not np.any(r["y"]) and r["dots"]["yy"] == 0.0 and (k > 4 or r["dots"]["ss"] > 0.0), k
+        assert np.all(o.w == 0.0) and o.resets == 0 and o.stalls == 0 and o.unit == 4
+        assert all(r["gp"] == 0.0 and np.array_equal(r["w_full"], np.zeros(COLS, np.float32)) for r, e in ev[4:])
+
+
+def test_a_zero_gradient_moves_nothing(plan):
+    """SQ_OVERDOSE at a level above any dose the start gives: g is +0 everywhere, so grad is +0, the first rule's mx is 0 and its
+    scale 1 / mx is taken as 0: w_full is w bit for bit, gp is 0, no counter moves."""
+    w0 = (1.0 + np.random.default_rng(13).random(COLS)).astype(np.float32)
+    top = float((plan.A.astype(np.float64) @ w0).max())
+    p = Problem(plan.A, [(R.SQ_OVERDOSE, 0, 1.0, 2.0 * top)], [np.ones(ROWS, dtype=bool)])
+    m = 4
+    o = p.lbfgs(w0, memory=m, tree=True)
+    for k in range(3):
+        r = o.step()
+        assert LB.event_letter(r) == "." and r["f"] == 0.0 and r["mx"] == 0.0 and not np.any(r["grad"]) and not np.signbit(r["grad"]).any()
+        assert np.all(r["delta"] == 0.0) and r["gp"] == 0.0 and not r["admitted"] and r["pairs"] == 0
+        assert np.array_equal(r["w_full"].view(np.uint32), w0.view(np.uint32)) and np.array_equal(o.w.view(np.uint32), w0.view(np.uint32))
+    assert (o.guarded, o.unit, o.backtracked, o.halvings, o.resets, o.stalls) == (0,) * 6 and o.stall == 1.0 and not o.moved
+    assert o.best_iteration == 0 and o.history == [0.0, 0.0, 0.0]
+
+
+def test_one_trial_stalls_with_and_without_pairs(plan):
+    """max_halvings = 0 (K = 1: the full step or nothing). A stall with pairs held drops them and leaves the stall factor alone; a
+    stall without pairs halves it (2^-K). m = 3 from w = 0 stalls at iterations 25 (3 pairs) and 26 (none); m = 16 from w = 100 at
+    iteration 2 (one pair)."""
+    o = plan.lbfgs(np.zeros(COLS), memory=3, max_halvings=0, tree=True)
+    ev, ws = [], []
+    for _ in range(28):
+        ws.append(o.w.copy())
+        ev += events(o, 1)
+    marks = "".join(e for _, e in ev)
+    assert marks == "0" * 25 + "SS0", marks
+    a, b = ev[25][0], ev[26][0]
+    assert a["pairs"] == 3 and a["stall_factor"] == 1.0 and len(a["F"]) == 1
+    assert b["pairs"] == 0 and not b["admitted"] and b["stall_factor"] == 1.0 and np.all(b["delta"][:6] == 0.0)
+    assert ev[27][0]["stall_factor"] == 0.5 and ev[27][0]["pairs"] == 0 and o.stalls == 2 and o.stall == 1.0
+    assert o.history[25] == o.history[26] == o.history[27] and np.array_equal(ws[25], ws[26]) and np.array_equal(ws[26], ws[27])
+    assert not np.array_equal(ws[24], ws[25]) and not np.array_equal(ws[27], o.w)
+    assert o.halvings == 0 and o.backtracked == 0 and o.unit == 26
+    o = plan.lbfgs(np.full(COLS, 100.0), memory=16, max_halvings=0, tree=True)
+    ev = events(o, 4)
+    marks = "".join(e for _, e in ev)
+    assert marks == "00S0", marks
+    assert ev[2][0]["pairs"] == 2 and ev[2][0]["admitted"] and o.stalls == 1 and ev[3][0]["pairs"] == 0 and ev[3][0]["stall_factor"] == 1.0
+
+
+def test_the_last_trial_is_reached_for_every_trial_count(plan):
+    """From w = 0 the first scale is the first rule's times 2^j, j = 0, 1, ... until the first iteration accepts its last trial K - 1:
+    one more doubling per halving, j = 9 + (K - 2) on this problem for K = 2 .. 8."""
+    first = plan.lbfgs(np.zeros(COLS), tree=True).step()["delta"][-1]
+    for K in range(2, 9):
+        found = None
+        for j in range(40):
+            o = plan.lbfgs(np.zeros(COLS), memory=3, max_halvings=K - 1, initial_step=first * 2.0 ** j, tree=True)
+            r = o.step()
+            if r["k"] == K - 1:
+                found = j
+                break
+        assert found == 9 + (K - 2), (K, found)
+        assert len(r["F"]) == K and r["a"] == 2.0 ** -(K - 1) and o.halvings == K - 1 and o.backtracked == 1
+        assert all(not f <= r["f"] + (o.c1 * 2.0 ** -k) * r["gp"] for k, f in enumerate(r["F"][:K - 1]))
+        marks = LB.event_letter(r) + letters(o, 4)
+        assert marks[0] == str(K - 1) and "S" not in marks and "R" not in marks, marks
