@@ -1751,6 +1751,107 @@ int rtd_optimizer_lbfgs_report(rtd_handle h, rtd_optimizer opt, rtd_lbfgs_report
 int rtd_optimizer_lbfgs_buffers(rtd_handle h, rtd_optimizer opt, rtd_lbfgs_buffers* b);
 
 /*
+ * ---- Compact dose-influence matrix: fp16 values, 16-bit indices, products of its own ----
+ *
+ * Additive to the blocks above (RTD_ABI_VERSION stays 3; no entry point, kernel or structure above changes). The plain form of a
+ * field's matrix keeps 16 bytes per entry: 4 B row + 4 B value in the CSC, 4 B column + 4 B value in the row-major companion. The two
+ * products are bound by those bytes. The compact form is opt-in and keeps 4 B per entry on each side where the shapes allow.
+ *
+ * VALUES. The two sides share one scale s_j (float32) per column j (spot):
+ *   m_j is the largest |v| of column j; e_j is the exponent of frexp(m_j), so m_j = f 2^e_j with f in [0.5, 1); s_j = 2^(e_j - 15).
+ *   The code of an entry is half_rne(v * 2^(15 - e_j)): an IEEE binary16, round to nearest even. The product by a power of two is
+ *   exact. A column that is empty or all zero gets s_j = 1 and zero codes.
+ * The dequantised value is v^ = float(code) * s_j, exact in float32, and |v^ - v| <= max(2^-11 |v|, 2^-25 s_j).
+ * The build is refused with RTD_ERR_INVALID_ARG, and leaves the field as it was, if a value is not finite or a column has
+ * 0 < m_j < 2^-100 (decided on the device, read once by the synchronous build), or if the field has more than 65 536 spots.
+ *
+ * COMPANION SIDE (forward product). Per entry a binary16 code and a uint16 column, rows in the plain companion's order (the voxels
+ * of the row box, x fastest), columns ascending. The forward tree has G lanes per row (lanes_per_row, 16 or 32), each taking E
+ * consecutive entries per trip (entries_per_lane, 1, 2 or 4). With E == 1 the row pointers are the plain companion's. With E > 1
+ * every row is padded to a multiple of E (pads at its end: code +0, column 0) and the side has row pointers of its own: row r's
+ * entries start at row_ptr[r] & ~(E - 1), its pads number row_ptr[r] & (E - 1), row_ptr[n_rows] is the number of entries, pads included.
+ *
+ * CSC SIDE (transposed product). Per entry a binary16 code and a uint16 offset; per group of 64 consecutive entries of a column one
+ * int32 base, the voxel of the group's first entry. Groups restart at every chunk of 2048 entries of a column (the chunks of
+ * rtd_field_dose_influence_apply_t): group g of the field's chunk c is csc_base[32 c + g] (0 where a short chunk has no such group).
+ * Rows ascend within a column: voxel = base + offset. If any group of the field spans more than 65 535 voxels (a dose-grid slice
+ * nx * ny that large), the side keeps the plain 32-bit rows instead of the offsets: row_bits = 32, 6 B per entry.
+ *
+ * THE PRODUCTS. Every product is rounded to float32 before it is added, every sum starts from +0, no float atomics: the same inputs
+ * give the same bits across calls, handles, processes and graph replays.
+ *   rtd_field_dose_influence_apply_compact    ws[j] = fl(w[j] * s_j); then per voxel of the row box lane t of G adds the products
+ *                                             fl(float(code) * ws[col]) of the row's entries (k G + t) E + e, e = 0 .. E - 1, then
+ *                                             k = 0, 1, ..., in that order; the G lane sums in a butterfly at distances G / 2 .. 1. A pad
+ *                                             is never multiplied. init, the row box and an empty matrix as rtd_field_dose_influence_apply.
+ *   rtd_field_dose_influence_apply_t_compact  the chunks and both trees of rtd_field_dose_influence_apply_t on the products
+ *                                             fl(float(code) * g[voxel]); dev_spot_grad[j] = fl(s_j * sum). Empty columns give +0.
+ * Both are launches only on the handle's stream, allocate nothing and can be captured into a graph.
+ *
+ * rtd_field_dose_influence_compact      synchronous. Runs rtd_field_dose_influence_prepare where it has not run, builds the scales and
+ *                          both sides. options may be NULL. With release_plain = 1 it then frees the CSC's rows (unless row_bits = 32)
+ *                          and values, the plain companion's columns and values and any LET values. From there until the next
+ *                          rtd_field_dose_influence every consumer of the plain form answers RTD_ERR_NOT_READY with a message that
+ *                          names release_plain: rtd_field_dose_influence_copy, _device, _apply, _apply_t, _apply_set, _apply_t_set,
+ *                          rtd_field_let_*, every optimiser and plan-set creator but rtd_optimizer_create_compact, and the run of an
+ *                          optimiser or plan set created before. The next rtd_field_dose_influence frees the compact form with the
+ *                          matrix it belonged to. A second call keeps the form that stands (and releases, if asked).
+ *                          RTD_ERR_NOT_READY: no matrix. RTD_ERR_INVALID_ARG: a remote or nuclear_corr field, a non-zero reserved
+ *                          word, release_plain above 1, the refusals of the format above.
+ *                          Environment (read by the build; for the profiles): RTD_DIJC_LANES (16 or 32) and RTD_DIJC_PER (1, 2 or 4)
+ *                          choose the forward tree; the default is 16 lanes, 4 entries.
+ * rtd_field_dose_influence_compact_info     what was built, the bytes it keeps, and the bytes the plain form's bulk keeps or kept.
+ * rtd_field_dose_influence_compact_device   the device pointers (owned by the field), for inspection.
+ * rtd_optimizer_create_compact  rtd_optimizer_create's spectral optimiser, every term kind, with the two compact products in place of
+ *                          the plain ones. Every field needs a compact form (RTD_ERR_NOT_READY). It notes every field's matrix:
+ *                          rtd_optimizer_run refuses with RTD_ERR_NOT_READY, before its first launch, once rtd_field_dose_influence
+ *                          has been called again on a field. rtd_optimizer_set_let_objective and rtd_optimizer_set_rbe refuse it
+ *                          with RTD_ERR_INVALID_ARG.
+ *
+ * Out of scope: L-BFGS, robust, voxel-wise, plan-set and 4D optimisers on the compact form; compact LET values; plan-minor products
+ * with several right-hand sides; nuclear_corr and the rtd_plan_* path (as the matrix itself).
+ */
+typedef struct rtd_dij_compact_options {
+    uint32_t release_plain;     /* 1: free the plain form's bulk once the compact form stands */
+    int32_t reserved[7];        /* must be 0 */
+} rtd_dij_compact_options;      /* 32 bytes */
+typedef struct rtd_dij_compact_info {
+    uint32_t value_bits;        /* 16 */
+    uint32_t col_bits;          /* 16 */
+    uint32_t row_bits;          /* 16: offsets from group bases; 32: the plain rows */
+    uint32_t lanes_per_row;     /* G */
+    uint32_t entries_per_lane;  /* E */
+    uint32_t plain_released;
+    uint64_t nnz;
+    uint64_t row_entries;       /* entries of the companion side, pads included */
+    uint64_t compact_bytes;     /* kept by the compact form's own buffers */
+    uint64_t plain_bytes;       /* the plain form's bulk (CSC rows and values, companion columns and values, LET values): kept, or as
+                                   it was when it was released */
+    uint64_t released_bytes;    /* of those, freed by release_plain (0: not released) */
+    int32_t reserved[4];
+} rtd_dij_compact_info;         /* 80 bytes */
+typedef struct rtd_dij_compact_device {
+    const float* scale;         /* [n_spots] */
+    const int64_t* col_ptr;     /* [n_spots + 1], the plain CSC's */
+    const uint16_t* csc_code;   /* [nnz] */
+    const uint16_t* csc_offset; /* [nnz]; NULL when row_bits = 32 */
+    const int32_t* csc_base;    /* [n_groups] */
+    const int32_t* csc_rows;    /* [nnz] when row_bits = 32, else NULL */
+    const int64_t* row_ptr;     /* [n_rows + 1] */
+    const uint16_t* row_code;   /* [row_entries] */
+    const uint16_t* row_col;    /* [row_entries] */
+    uint64_t nnz, n_groups, n_rows, row_entries;
+    int32_t box[6];             /* the row box: x0, y0, z0, width, height, depth */
+} rtd_dij_compact_device;       /* 128 bytes */
+void rtd_default_dij_compact_options(rtd_dij_compact_options* out);
+int rtd_field_dose_influence_compact(rtd_handle h, rtd_field f, const rtd_dij_compact_options* o);
+int rtd_field_dose_influence_compact_info(rtd_handle h, rtd_field f, rtd_dij_compact_info* info);
+int rtd_field_dose_influence_compact_device(rtd_handle h, rtd_field f, rtd_dij_compact_device* d);
+int rtd_field_dose_influence_apply_compact(rtd_handle h, rtd_field f, const float* dev_spot_weights, float* dev_dose, int init);
+int rtd_field_dose_influence_apply_t_compact(rtd_handle h, rtd_field f, const float* dev_voxel_weights, float* dev_spot_grad);
+int rtd_optimizer_create_compact(rtd_handle h, const rtd_field* fields, uint32_t n_fields, rtd_objective obj, const rtd_optimizer_options* o,
+                                 rtd_optimizer* out);
+
+/*
  * ---- Multi-GPU plans behind the boundary (SURVEY.md 8(b) "Threading": one handle and one host thread per device) ----
  *
  * rtd_plan is the reference-shaped call on several GPUs of one process: the 4-beam cudaWrapperProtons of the C++ shim uses

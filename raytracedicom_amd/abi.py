@@ -309,6 +309,33 @@ def default_lbfgs_options():
     return o
 
 
+class RtdDijCompactOptions(C.Structure):
+    """rtd_dij_compact_options: release_plain (1: free the plain form's bulk once the compact form stands) (32 bytes)."""
+    _fields_ = [("release_plain", C.c_uint32), ("reserved", C.c_int32 * 7)]
+
+
+class RtdDijCompactInfo(C.Structure):
+    """rtd_dij_compact_info: what rtd_field_dose_influence_compact built and the bytes the two forms keep (80 bytes)."""
+    _fields_ = [("value_bits", C.c_uint32), ("col_bits", C.c_uint32), ("row_bits", C.c_uint32), ("lanes_per_row", C.c_uint32),
+                ("entries_per_lane", C.c_uint32), ("plain_released", C.c_uint32), ("nnz", C.c_uint64), ("row_entries", C.c_uint64),
+                ("compact_bytes", C.c_uint64), ("plain_bytes", C.c_uint64), ("released_bytes", C.c_uint64), ("reserved", C.c_int32 * 4)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_ if k != "reserved"}
+
+
+class RtdDijCompactDevice(C.Structure):
+    """rtd_dij_compact_device: the device arrays of a field's compact matrix, for inspection (128 bytes)."""
+    _fields_ = [("scale", C.c_void_p), ("col_ptr", C.c_void_p), ("csc_code", C.c_void_p), ("csc_offset", C.c_void_p), ("csc_base", C.c_void_p),
+                ("csc_rows", C.c_void_p), ("row_ptr", C.c_void_p), ("row_code", C.c_void_p), ("row_col", C.c_void_p),
+                ("nnz", C.c_uint64), ("n_groups", C.c_uint64), ("n_rows", C.c_uint64), ("row_entries", C.c_uint64), ("box", C.c_int32 * 6)]
+
+
+def default_dij_compact_options():
+    """rtd_default_dij_compact_options: the plain form is kept."""
+    return RtdDijCompactOptions()
+
+
 class RtdRbeTissue(C.Structure):
     """rtd_rbe_tissue: photon alpha_x (1/Gy), beta_x (1/Gy^2) and the lines RBEmax / RBEmin = c[0] + c[1] * LETd (32 bytes)."""
     _fields_ = [("alpha_x", C.c_float), ("beta_x", C.c_float), ("rbe_max", C.c_float * 2), ("rbe_min", C.c_float * 2),

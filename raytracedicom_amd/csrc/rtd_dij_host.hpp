@@ -16,10 +16,13 @@ bool letReady(const rtd_handle_impl* h, const rtd_field_impl* f) { return f->mat
 //   kPrepared    ... with a matrix, prepared on demand (the first product of a matrix is synchronous that once)
 //   kLetValues   ... with LET values of the matrix and of the handle's table
 enum class MatrixStage { kWorkspace, kMatrix, kPrepared, kLetValues };
+// What every consumer of the plain form answers (RTD_ERR_NOT_READY) between a release and the next rtd_field_dose_influence.
+const char* const kPlainReleasedMsg = ": the plain form of the matrix was freed (rtd_field_dose_influence_compact with release_plain = 1); call rtd_field_dose_influence again";
 // The refusals alone, `who` being the entry point the messages name: all that an entry point without launches asks.
 int matrixRefusal(rtd_handle_impl* h, const rtd_field_impl* f, const char* who_, MatrixStage need) {
     auto who = [&] { return std::string(who_); };                      // (composed only for a refusal)
     if (f->remote) return fail(h, RTD_ERR_INVALID_ARG, who() + ": a remote field has no workspace");
+    if (need != MatrixStage::kWorkspace && f->matrix.hasMatrix() && f->matrix.plainReleased()) return fail(h, RTD_ERR_NOT_READY, who() + kPlainReleasedMsg);
     if (need == MatrixStage::kLetValues) {
         if (!letReady(h, f)) return fail(h, RTD_ERR_NOT_READY, who() + ": no LET-weighted matrix of the current matrix and table (call rtd_field_let_influence first)");
     } else if (need != MatrixStage::kWorkspace && !f->matrix.hasMatrix())
@@ -245,7 +248,7 @@ int rtd_field_dose_influence(rtd_handle hh, rtd_field ff, float rel_threshold, s
     // 6. CSC: column pointers on the host, the batch-major columns gathered into column order on the device
     std::vector<long long> colPtr(nSpot + 1, 0);
     for (size_t j = 0; j < nSpot; ++j) colPtr[j + 1] = colPtr[j] + colLen[j];
-    freeBuffers(f, kDijCsc | kDijCompanion | kDijLet);               // (with the old result what was built and computed from it)
+    freeBuffers(f, kDijCsc | kDijCompanion | kDijLet | kDijCompact | kDijCompactRows);   // (with the old result what was built and computed from it)
     const FieldState& fin = *f->hState;
     const int ownBox[6] = {fin.tboxMin[0], fin.tboxMin[1], fin.tboxMin[2], fin.tboxMax[0], fin.tboxMax[1], fin.tboxMax[2]};
     m.resultSized((size_t)colPtr[nSpot], ownBox);
@@ -269,6 +272,7 @@ int rtd_field_dose_influence_copy(rtd_handle hh, rtd_field ff, int64_t* col_ptr,
     // (its own opening: the matrix in front of the pointers, and a remote field is answered like any field without a matrix)
     const size_t nnz = f->matrix.nnz();
     if (!f->matrix.hasMatrix()) return fail(h, RTD_ERR_NOT_READY, "rtd_field_dose_influence_copy: no dose-influence matrix (call rtd_field_dose_influence first)");
+    if (f->matrix.plainReleased()) return fail(h, RTD_ERR_NOT_READY, std::string("rtd_field_dose_influence_copy") + kPlainReleasedMsg);
     if (!col_ptr || (nnz && (!row_idx || !values))) return fail(h, RTD_ERR_INVALID_ARG, "rtd_field_dose_influence_copy: null pointer");
     RTD_HIP(h, hipSetDevice(h->device));
     const size_t nSpot = (size_t)f->fc.spotNx * f->fc.spotNy * f->fc.L;

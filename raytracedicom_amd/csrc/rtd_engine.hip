@@ -39,6 +39,7 @@
 #include "rtd_adjoint.hpp"
 #include "rtd_dij.hpp"
 #include "rtd_dij_apply.hpp"
+#include "rtd_dij_compact.hpp"
 #include "rtd_optimize.hpp"
 #include "rtd_dvh.hpp"
 #include "rtd_eud.hpp"
@@ -442,7 +443,7 @@ int rtd_field_release(rtd_handle hh, rtd_field ff) {
     // The next owner of the workspace is a new field object, and this one is deleted when it takes over: nothing carries over, and
     // nothing in between reads these. They make a call on the stale field handle answer "not computed" instead of using freed buffers.
     f->computed = false; f->transferred = false;
-    freeBuffers(f, kGradient | kDiag | kDij | kDijCsc | kDijCompanion | kDijLet | kTarget | kSigmaRec);   // (not part of the shape's workspace)
+    freeBuffers(f, kGradient | kDiag | kDij | kDijCsc | kDijCompanion | kDijLet | kDijCompact | kDijCompactRows | kTarget | kSigmaRec);   // (not part of the shape's workspace)
     f->memory = FieldMemory{};
     f->gradDone = false; f->targetProjected = false; f->targetSelected = false;
     f->matrix.released();
@@ -1472,3 +1473,4 @@ int rtd_compute(rtd_handle hh, const rtd_beam* beams, int n_beams, float* dose_i
 #include "rtd_planset_host.hpp"
 #include "rtd_fourd_host.hpp"
 #include "rtd_lbfgs_host.hpp"
+#include "rtd_dij_compact_host.hpp"

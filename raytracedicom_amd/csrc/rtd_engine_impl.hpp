@@ -95,8 +95,10 @@ Switches readSwitches() {
 // (rtd_field_project_target: allocated by its first call), the sigma record (allocated by the first compute that reuses the trace),
 // and what hangs on the CSC result, each with a life of its own: the companion (rtd_field_dose_influence_prepare) and the LET values
 // (rtd_field_let_influence). A class is what is allocated together and dies together; the three of the result go when it is replaced.
+// The compact form (rtd_field_dose_influence_compact) hangs on the result likewise: kDijCompact, and kDijCompactRows for its companion
+// side, whose size is known only once the padded rows have been scanned.
 enum BufClass : unsigned { kShape = 1, kNuclear = 2, kGradient = 4, kDiag = 8, kDij = 16, kDijCsc = 32, kTarget = 64, kSigmaRec = 128,
-                           kDijCompanion = 256, kDijLet = 512, kAllBufs = 1023 };
+                           kDijCompanion = 256, kDijLet = 512, kDijCompact = 1024, kDijCompactRows = 2048, kAllBufs = 4095 };
 
 // A field's events: the start of a compute's first launch, the ends of its stages, the end of the transfer, and the start of the
 // superposition's first launch. kEvTrace is not recorded by a compute that reused the trace, kEvKsPlan not by one whose sweep launch
@@ -198,6 +200,13 @@ struct rtd_field_impl {
     // the LET-weighted values on the matrix's structure (rtd_field_let_influence, rtd_let.hpp): a second values array for the CSC, one
     // for the row-major companion, and the water-equivalent depth of the voxels of matrix.box()
     float *dLetVals = nullptr, *dLetCVals = nullptr, *dLetDepth = nullptr;
+    // the compact form (rtd_field_dose_influence_compact, rtd_dij_compact.hpp): one scale per spot and the scaled weights of the last
+    // forward product; the CSC side (binary16 codes, 16-bit offsets from the base of their 64-entry group); the companion side
+    // (binary16 codes, 16-bit columns, and row pointers of its own where rows are padded)
+    float *dDijcScale = nullptr, *dDijcWs = nullptr;
+    unsigned short *dDijcCode = nullptr, *dDijcOff = nullptr, *dDijcCCode = nullptr, *dDijcCCol = nullptr;
+    int* dDijcBase = nullptr;
+    long long* dDijcRowPtr = nullptr;
     // the target in beam's-eye view (rtd_field_project_target / rtd_field_select_spots, rtd_target.hpp): allocated by the first projection
     unsigned int* dTargetBev = nullptr;      // [ceil(S / 32)][H][W] bit k & 31 of word k >> 5: sample (ray, step k) lies in the target
     unsigned char* dTargetHit = nullptr;     // [L][H][W] the layer hits of the last selection
@@ -252,14 +261,19 @@ struct rtd_field_impl {
         visit(dDijCnt, (size_t)kDijBlocks * dijSpots, kDij, false, nullptr); visit(dDijColMax, dijSpots, kDij, false, nullptr);
         visit(dDijMisc, (size_t)4, kDij, true, nullptr); visit(dDijColLen, nSpot, kDij, false, nullptr); visit(dDijColSrc, nSpot, kDij, false, nullptr);
         visit(dDijRowsB, matrix.stagingEntries(), kDij, false, nullptr); visit(dDijValsB, matrix.stagingEntries(), kDij, false, nullptr);
-        visit(dDijColPtr, nSpot + 1, kDijCsc, false, nullptr); visit(dDijRows, matrix.resultEntries(), kDijCsc, false, nullptr);
-        visit(dDijVals, matrix.resultEntries(), kDijCsc, false, nullptr);
+        visit(dDijColPtr, nSpot + 1, kDijCsc, false, nullptr); visit(dDijRows, matrix.resultRows(), kDijCsc, false, nullptr);
+        visit(dDijVals, matrix.resultValues(), kDijCsc, false, nullptr);
         visit(dDijRowPtr, matrix.companionRowPtrs(), kDijCompanion, false, nullptr); visit(dDijCCols, matrix.companionEntries(), kDijCompanion, false, nullptr);
         visit(dDijCVals, matrix.companionEntries(), kDijCompanion, false, nullptr);
         visit(dDijChunkFirst, matrix.companionChunkFirsts(nSpot), kDijCompanion, false, nullptr);
         visit(dDijChunkCol, matrix.companionChunks(), kDijCompanion, false, nullptr); visit(dDijPartial, matrix.companionChunks(), kDijCompanion, false, nullptr);
         visit(dLetVals, matrix.letEntries(), kDijLet, false, nullptr); visit(dLetCVals, matrix.letEntries(), kDijLet, false, nullptr);
         visit(dLetDepth, matrix.letDepths(), kDijLet, false, nullptr);
+        visit(dDijcScale, matrix.compactSpots(nSpot), kDijCompact, false, nullptr); visit(dDijcWs, matrix.compactSpots(nSpot), kDijCompact, false, nullptr);
+        visit(dDijcCode, matrix.compactCscEntries(), kDijCompact, false, nullptr); visit(dDijcOff, matrix.compactCscOffsets(), kDijCompact, false, nullptr);
+        visit(dDijcBase, matrix.compactCscGroups(), kDijCompact, false, nullptr); visit(dDijcRowPtr, matrix.compactRowPtrs(), kDijCompact, false, nullptr);
+        visit(dDijcCCode, matrix.compactCompanionEntries(), kDijCompactRows, false, nullptr);
+        visit(dDijcCCol, matrix.compactCompanionEntries(), kDijCompactRows, false, nullptr);
         visit(dTargetBev, ((S + 31) / 32) * R, kTarget, false, "target_bev"); visit(dTargetHit, L * R, kTarget, false, "target_hit");
         visit(dTargetSum, (size_t)1, kTarget, false, nullptr); visit(dTargetCount, (size_t)1, kTarget, false, nullptr);
         visit(dSigRec, memory.sigmaSteps * R * L, kSigmaRec, false, nullptr); visit(dSigRecLast, memory.sigmaSteps ? R * L : (size_t)0, kSigmaRec, false, nullptr);

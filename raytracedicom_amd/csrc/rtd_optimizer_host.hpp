@@ -63,6 +63,9 @@ struct rtd_optimizer_impl {
     DevBuf<float> dLbTrialDose, dLbVec;
     DevBuf<double> dLbGram, dLbPart, dLbGp, dLbLine;
     DevBuf<LbState> dLbState;
+    // A compact optimiser (section 28; rtd_optimizer_create_compact in rtd_dij_compact_host.hpp): a plain optimiser whose two products
+    // are rtd_field_dose_influence_apply_compact / _apply_t_compact. matEpoch: per field, what its matrix was at creation.
+    bool compact = false;
     rtd_field_impl* const* row(int s) const { return sfields.data() + (size_t)s * fields.size(); }
     rtd_field_impl* sf(int s, size_t i) const { return row(s)[i]; }
     float* w() const { return dVec; }
@@ -201,13 +204,18 @@ int optCheckField(rtd_handle_impl* h, const std::string& who, const rtd_field_im
 }
 // 3. Every one of the n_all fields (rows of n_fields) has a matrix; their companions and the objective are built; *offset gets the
 // spot-offset table of the first row.
-int optPrepare(rtd_handle hh, const std::string& who, const rtd_field* fields, uint32_t n_fields, uint32_t n_all, rtd_objective_impl* o, std::vector<int>* offset) {
+// compact: the fields' compact forms are asked for instead of their plain ones (rtd_optimizer_create_compact).
+int optPrepare(rtd_handle hh, const std::string& who, const rtd_field* fields, uint32_t n_fields, uint32_t n_all, rtd_objective_impl* o, std::vector<int>* offset,
+               bool compact = false) {
     auto* h = reinterpret_cast<rtd_handle_impl*>(hh);
-    for (uint32_t i = 0; i < n_all; ++i)
-        if (!reinterpret_cast<rtd_field_impl*>(fields[i])->matrix.hasMatrix())
-            return fail(h, RTD_ERR_NOT_READY, who + ": a field has no dose-influence matrix (call rtd_field_dose_influence first)");
+    for (uint32_t i = 0; i < n_all; ++i) {
+        const FieldMatrix& m = reinterpret_cast<rtd_field_impl*>(fields[i])->matrix;
+        if (!m.hasMatrix()) return fail(h, RTD_ERR_NOT_READY, who + ": a field has no dose-influence matrix (call rtd_field_dose_influence first)");
+        if (compact && !m.compact()) return fail(h, RTD_ERR_NOT_READY, who + ": a field has no compact form of its matrix (call rtd_field_dose_influence_compact first)");
+        if (!compact && m.plainReleased()) return fail(h, RTD_ERR_NOT_READY, who + kPlainReleasedMsg);
+    }
     RTD_HIP(h, hipSetDevice(h->device));
-    for (uint32_t i = 0; i < n_all; ++i) { const int st = rtd_field_dose_influence_prepare(hh, fields[i]); if (st != RTD_OK) return st; }
+    for (uint32_t i = 0; i < n_all && !compact; ++i) { const int st = rtd_field_dose_influence_prepare(hh, fields[i]); if (st != RTD_OK) return st; }
     if (!o->built) { const int st = buildObjective(h, o); if (st != RTD_OK) return st; }
     offset->assign(1, 0);
     long long total = 0;
@@ -244,7 +252,7 @@ int optReport(rtd_handle_impl* h, const char* who, const char* whose, const OptS
 // rtd_optimizer_create (robust == nullptr: one scenario, nothing of section 14 allocated or launched), rtd_optimizer_create_robust and
 // rtd_optimizer_create_voxelwise (voxelwise: what a robust optimiser owns plus the word of active scenarios; robust->mode is not read).
 int optCreate(rtd_handle hh, const rtd_field* fields, uint32_t n_fields, const rtd_robust_options* robust, rtd_objective oo,
-              const rtd_optimizer_options* opt, rtd_optimizer* out, bool voxelwise = false) {
+              const rtd_optimizer_options* opt, rtd_optimizer* out, bool voxelwise = false, bool compact = false) {
     auto* h = reinterpret_cast<rtd_handle_impl*>(hh);
     auto* o = reinterpret_cast<rtd_objective_impl*>(oo);
     if (!h) return RTD_ERR_INVALID_ARG;
@@ -259,7 +267,7 @@ int optCreate(rtd_handle hh, const rtd_field* fields, uint32_t n_fields, const r
                 if (!(robust->probabilities[sc] > 0.0) || !std::isfinite(robust->probabilities[sc]))
                     return fail(h, RTD_ERR_INVALID_ARG, "rtd_optimizer_create_robust: a probability must be positive and finite");
     }
-    const std::string who = "rtd_optimizer_create";
+    const std::string who = compact ? "rtd_optimizer_create_compact" : "rtd_optimizer_create";
     rtd_optimizer_options op;
     int st = optCheckOptions(h, who, n_fields, opt, &op);
     if (st != RTD_OK) return st;
@@ -280,10 +288,12 @@ int optCreate(rtd_handle hh, const rtd_field* fields, uint32_t n_fields, const r
     if (voxelwise && o->hasDvhTerms()) return fail(h, RTD_ERR_INVALID_ARG, "rtd_optimizer_create_voxelwise: an objective with DVH terms has no voxel-wise worst case");
     if (voxelwise && o->hasEudTerms()) return fail(h, RTD_ERR_INVALID_ARG, "rtd_optimizer_create_voxelwise: an objective with EUD terms has no voxel-wise worst case");
     std::vector<int> offset;
-    st = optPrepare(hh, who, fields, n_fields, nAll, o, &offset);
+    st = optPrepare(hh, who, fields, n_fields, nAll, o, &offset, compact);
     if (st != RTD_OK) return st;
     auto* p = new rtd_optimizer_impl();
     p->obj = o; p->opt = op; p->nVox = o->nVox; p->offset = offset;
+    p->compact = compact;
+    if (compact) for (uint32_t i = 0; i < nAll; ++i) p->matEpoch.push_back(reinterpret_cast<rtd_field_impl*>(fields[i])->matrix.epoch());
     if (robust) {
         p->robust = true; p->nScen = (int)nScen; p->mode = robust->mode; p->voxelwise = voxelwise;
         p->batch = std::getenv("RTD_ROBUST_NO_BATCH") == nullptr;      // read once, here (the convention of the engine switches)
@@ -440,11 +450,19 @@ int rtd_optimizer_run(rtd_handle hh, rtd_optimizer pp, uint32_t n_iterations) {
                 return fail(h, RTD_ERR_NOT_READY, "rtd_optimizer_run: a field's LET-weighted matrix is not that of its matrix and the handle's table (call rtd_field_let_influence again)");
     if (p->fourd && !fourdMatricesStand(p))
         return fail(h, RTD_ERR_NOT_READY, "rtd_optimizer_run: a field's dose-influence matrix has been computed again since rtd_optimizer_create_4d (destroy the optimiser and create a new one)");
+    for (size_t i = 0; i < p->sfields.size(); ++i) {                  // (likewise in front of the first launch)
+        const FieldMatrix& m = p->sfields[i]->matrix;
+        if (p->compact && !m.isCompactOf(p->matEpoch[i]))
+            return fail(h, RTD_ERR_NOT_READY, "rtd_optimizer_run: a field's dose-influence matrix has been computed again since rtd_optimizer_create_compact (destroy the optimiser and create a new one)");
+        if (!p->compact && m.hasMatrix() && m.plainReleased()) return fail(h, RTD_ERR_NOT_READY, std::string("rtd_optimizer_run") + kPlainReleasedMsg);
+    }
     RTD_HIP(h, hipSetDevice(h->device));
     hipStream_t s = h->stream;
-    // the products of a plain optimiser: its one row of fields with the dose matrices and with the LET-weighted ones
-    auto doseForward = [&] { return fieldsForward(hh, h, p, p->row(0), p->dDose, rtd_field_dose_influence_apply); };
-    auto doseAdjoint = [&] { return fieldsAdjoint(hh, p, p->row(0), p->dG, p->grad(), rtd_field_dose_influence_apply_t); };
+    // the products of a plain optimiser: its one row of fields with the dose matrices (plain or compact) and with the LET-weighted ones
+    const FieldApply apply = p->compact ? rtd_field_dose_influence_apply_compact : rtd_field_dose_influence_apply;
+    const FieldApplyT applyT = p->compact ? rtd_field_dose_influence_apply_t_compact : rtd_field_dose_influence_apply_t;
+    auto doseForward = [&] { return fieldsForward(hh, h, p, p->row(0), p->dDose, apply); };
+    auto doseAdjoint = [&] { return fieldsAdjoint(hh, p, p->row(0), p->dG, p->grad(), applyT); };
     auto letForward = [&] { return fieldsForward(hh, h, p, p->row(0), p->dLetDose, rtd_field_let_influence_apply); };
     auto letAdjoint = [&] { return fieldsAdjoint(hh, p, p->row(0), p->dLetG, p->dLetGrad, rtd_field_let_influence_apply_t); };
     for (uint32_t k = 0; k < n_iterations; ++k) {

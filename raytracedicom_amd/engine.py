@@ -177,6 +177,14 @@ def lib():
         L.rtd_optimizer_create_lbfgs.argtypes = [vp, vpp, C.c_uint32, vp, C.POINTER(abi.RtdLbfgsOptions), vpp]
         L.rtd_optimizer_lbfgs_report.argtypes = [vp, vp, C.POINTER(abi.RtdLbfgsReport)]
         L.rtd_optimizer_lbfgs_buffers.argtypes = [vp, vp, C.POINTER(abi.RtdLbfgsBuffers)]
+        L.rtd_default_dij_compact_options.argtypes = [C.POINTER(abi.RtdDijCompactOptions)]
+        L.rtd_default_dij_compact_options.restype = None
+        L.rtd_field_dose_influence_compact.argtypes = [vp, vp, C.POINTER(abi.RtdDijCompactOptions)]
+        L.rtd_field_dose_influence_compact_info.argtypes = [vp, vp, C.POINTER(abi.RtdDijCompactInfo)]
+        L.rtd_field_dose_influence_compact_device.argtypes = [vp, vp, C.POINTER(abi.RtdDijCompactDevice)]
+        L.rtd_field_dose_influence_apply_compact.argtypes = [vp, vp, vp, vp, C.c_int]
+        L.rtd_field_dose_influence_apply_t_compact.argtypes = [vp, vp, vp, vp]
+        L.rtd_optimizer_create_compact.argtypes = [vp, vpp, C.c_uint32, vp, C.POINTER(abi.RtdOptimizerOptions), vpp]
         L.rtd_host_register.argtypes = [vp, C.c_size_t]
         L.rtd_host_unregister.argtypes = [vp]
         L.rtd_plan_create.argtypes = [C.POINTER(C.c_int), C.c_int, vpp]
@@ -367,6 +375,38 @@ class Field:
         cp, ri, va, n = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_size_t(0)
         self.eng._check(lib().rtd_field_dose_influence_device(self.eng._h, self._h, C.byref(cp), C.byref(ri), C.byref(va), C.byref(n)))
         return int(cp.value or 0), int(ri.value or 0), int(va.value or 0), int(n.value)
+
+    def dose_influence_compact(self, release_plain=False, options=None):
+        """rtd_field_dose_influence_compact: builds the compact form of the matrix of the last dose_influence() (binary16 codes under
+        one scale per spot, 16-bit indices; synchronous). release_plain=True then frees the plain form's bulk: until the next
+        dose_influence() only the compact calls and Engine.create_compact_optimizer work on the field. options: an
+        abi.RtdDijCompactOptions instead of the keyword."""
+        o = options if options is not None else abi.default_dij_compact_options()
+        if options is None:
+            o.release_plain = int(bool(release_plain))
+        self.eng._check(lib().rtd_field_dose_influence_compact(self.eng._h, self._h, C.byref(o)))
+
+    def dose_influence_compact_info(self):
+        """rtd_field_dose_influence_compact_info: a dict of value_bits, col_bits, row_bits, lanes_per_row (G), entries_per_lane (E),
+        plain_released, nnz, row_entries, compact_bytes, plain_bytes and released_bytes."""
+        i = abi.RtdDijCompactInfo()
+        self.eng._check(lib().rtd_field_dose_influence_compact_info(self.eng._h, self._h, C.byref(i)))
+        return i.as_dict()
+
+    def dose_influence_compact_device(self):
+        """rtd_field_dose_influence_compact_device: the device pointers and sizes of the compact form (abi.RtdDijCompactDevice; owned
+        by the field, valid until its next dose_influence(), release or destroy)."""
+        d = abi.RtdDijCompactDevice()
+        self.eng._check(lib().rtd_field_dose_influence_compact_device(self.eng._h, self._h, C.byref(d)))
+        return d
+
+    def dose_influence_apply_compact(self, dev_w, dev_dose, init=False):
+        """rtd_field_dose_influence_apply_compact: Dij w with the compact form; arguments as dose_influence_apply. Launches only."""
+        self.eng._check(lib().rtd_field_dose_influence_apply_compact(self.eng._h, self._h, C.c_void_p(int(dev_w)), C.c_void_p(int(dev_dose)), int(bool(init))))
+
+    def dose_influence_apply_t_compact(self, dev_g, dev_out):
+        """rtd_field_dose_influence_apply_t_compact: Dij^T g with the compact form; arguments as dose_influence_apply_t. Launches only."""
+        self.eng._check(lib().rtd_field_dose_influence_apply_t_compact(self.eng._h, self._h, C.c_void_p(int(dev_g)), C.c_void_p(int(dev_out))))
 
     def water_depth(self, dev_depth):
         """rtd_field_water_depth: WRITES the field's water-equivalent depth (mm) of every voxel of its dose box into dev_depth (a
@@ -818,13 +858,14 @@ class Optimizer:
     dose_influence() matrix). Destroy it before its fields, its objective and its engine."""
 
     def __init__(self, eng, fields, objective, options=None, scenario_fields=None, mode=None, probabilities=None, voxelwise=False, phase_warps=None,
-                 phase_weights=None, lbfgs=False):
+                 phase_weights=None, lbfgs=False, compact=False):
         """scenario_fields (a list of per-scenario field lists, scenario 0 the nominal one) makes it a robust optimiser
         (rtd_optimizer_create_robust) in mode abi.RTD_ROBUST_EXPECTED / _WORST_CASE, or with voxelwise=True the voxel-wise worst case
         (rtd_optimizer_create_voxelwise; mode and probabilities are then not used); `fields` is then ignored. With phase_warps (a list
         of abi.RtdWarp, one per row of scenario_fields) the rows are breathing phases and it is a 4D optimiser
         (rtd_optimizer_create_4d; phase_weights: one positive weight per phase, None for equal ones). With lbfgs=True it is the
-        L-BFGS iteration with its line search on the device (rtd_optimizer_create_lbfgs; options: an abi.RtdLbfgsOptions or None)."""
+        L-BFGS iteration with its line search on the device (rtd_optimizer_create_lbfgs; options: an abi.RtdLbfgsOptions or None). With
+        compact=True it is the spectral iteration on the fields' compact matrices (rtd_optimizer_create_compact)."""
         self.eng = eng
         self.objective = objective
         self._h = C.c_void_p()
@@ -836,6 +877,9 @@ class Optimizer:
             arr = (C.c_void_p * max(1, len(self.fields)))(*[f._h for f in self.fields])
             if lbfgs:
                 eng._check(lib().rtd_optimizer_create_lbfgs(eng._h, arr, len(self.fields), objective._h, po, C.byref(self._h)))
+                return
+            if compact:
+                eng._check(lib().rtd_optimizer_create_compact(eng._h, arr, len(self.fields), objective._h, po, C.byref(self._h)))
                 return
             eng._check(lib().rtd_optimizer_create(eng._h, arr, len(self.fields), objective._h, po, C.byref(self._h)))
             return
@@ -1220,6 +1264,11 @@ class Engine:
         objective must not have DVH or EUD terms); options: an abi.RtdLbfgsOptions (abi.default_lbfgs_options) or None. It also has
         .lbfgs_report()."""
         return Optimizer(self, fields, objective, options, lbfgs=True)
+
+    def create_compact_optimizer(self, fields, objective, options=None):
+        """rtd_optimizer_create_compact: the spectral optimiser of create_optimizer whose two products read the fields' compact
+        matrices (every field needs dose_influence_compact() first)."""
+        return Optimizer(self, fields, objective, options, compact=True)
 
     def create_planset(self, fields, objective, variants, options=None):
         """rtd_planset_create: len(variants) plans on `fields` under variants of `objective` (PlanSet)."""
