@@ -1852,6 +1852,44 @@ int rtd_optimizer_create_compact(rtd_handle h, const rtd_field* fields, uint32_t
                                  rtd_optimizer* out);
 
 /*
+ * ---- Robust and voxel-wise optimisation on the compact matrix ----
+ *
+ * Additive to the blocks above (RTD_ABI_VERSION stays 3; no entry point or structure above changes what it answers). A robust plan
+ * holds S x F matrices and reads each of them in every iteration, so it is where the bytes of the compact form count most; with
+ * release_plain it is also the only way such a plan fits the card once the plain forms would not. The two creators below lift the
+ * restriction of the block above for the scenario-wise robust optimiser and the voxel-wise worst case.
+ *
+ * rtd_optimizer_create_robust_compact     rtd_optimizer_create_robust (same arguments, same checks, every term kind it accepts) on
+ *                          the compact forms of the S x F fields. The iteration is that optimiser's; only its two products change:
+ *                          step 1 is rtd_field_dose_influence_apply_compact(init = 0) per field into a zeroed volume, step 4 is
+ *                          rtd_field_dose_influence_apply_t_compact, bit for bit. Per field position one launch covers every scenario
+ *                          (the single-matrix kernels' bodies with the scenario as the grid's y; the scaled weights
+ *                          ws_s[j] = fl(w[j] * s_{s,j}) go into each field's own workspace; scenarios with lambda_s = 0 do no
+ *                          transposed work). RTD_ROBUST_NO_BATCH (read at creation) issues the single-matrix compact products
+ *                          scenario by scenario instead: the same bits.
+ *                          The width of the CSC side's rows (row_bits) may differ between the scenarios of one position. The forward
+ *                          tree may not: field f of every scenario must have the lanes_per_row and entries_per_lane of field f of
+ *                          scenario 0 (RTD_ERR_INVALID_ARG).
+ *                          Every field needs a compact form (RTD_ERR_NOT_READY); no rtd_field_dose_influence_prepare runs, so creation
+ *                          works after release_plain. It notes every field's matrix: rtd_optimizer_run refuses with
+ *                          RTD_ERR_NOT_READY, before its first launch, once rtd_field_dose_influence has been called again on any of
+ *                          the S x F fields.
+ * rtd_optimizer_create_voxelwise_compact  rtd_optimizer_create_voxelwise likewise (it refuses DVH and EUD terms as that one does).
+ * Both return an ordinary rtd_optimizer: rtd_optimizer_set_weights, _run, _result, _weights, _dose, _scenario_values, _scenario_dose
+ * and _destroy work as on their plain siblings; rtd_optimizer_set_let_objective and rtd_optimizer_set_rbe refuse them with
+ * RTD_ERR_INVALID_ARG. rtd_optimizer_create_robust and rtd_optimizer_create_voxelwise themselves still answer RTD_ERR_NOT_READY on
+ * a field whose plain form has been released.
+ * Environment (read by rtd_field_dose_influence_compact; for tests and profiles): RTD_DIJC_ROWS32=1 makes the build keep the 32-bit
+ * rows whatever the spans are, so that one plan can mix the two widths.
+ *
+ * Out of scope: L-BFGS, plan-set and 4D optimisers on the compact form; compact LET values; RBE and LET objectives in robust optimisers.
+ */
+int rtd_optimizer_create_robust_compact(rtd_handle h, const rtd_field* fields /* [S][F] scenario-major */, uint32_t n_fields,
+                                        const rtd_robust_options* robust, rtd_objective obj, const rtd_optimizer_options* o, rtd_optimizer* out);
+int rtd_optimizer_create_voxelwise_compact(rtd_handle h, const rtd_field* fields, uint32_t n_fields, uint32_t n_scenarios,
+                                           rtd_objective obj, const rtd_optimizer_options* o, rtd_optimizer* out);
+
+/*
  * ---- Multi-GPU plans behind the boundary (SURVEY.md 8(b) "Threading": one handle and one host thread per device) ----
  *
  * rtd_plan is the reference-shaped call on several GPUs of one process: the 4-beam cudaWrapperProtons of the C++ shim uses

@@ -121,9 +121,14 @@ __global__ __launch_bounds__(256) void k_dijc_tag_pads(const long long* __restri
 }
 
 // ---- the forward product ----
-__global__ __launch_bounds__(256) void k_dijc_scale_w(const float* __restrict__ w, const float* __restrict__ scale, float* __restrict__ ws, int n) {
+// The bodies of the four product kernels are shared with the launches over a scenario axis (rtd_robust_compact.hpp), as dijApplyBody is
+// in the plain case: one body per product, so a batched launch gives the bits of the per-scenario calls.
+__device__ __forceinline__ void dijcScaleWBody(const float* __restrict__ w, const float* __restrict__ scale, float* __restrict__ ws, int n) {
     const int j = blockIdx.x * 256 + threadIdx.x;
     if (j < n) ws[j] = w[j] * scale[j];
+}
+__global__ __launch_bounds__(256) void k_dijc_scale_w(const float* __restrict__ w, const float* __restrict__ scale, float* __restrict__ ws, int n) {
+    dijcScaleWBody(w, scale, ws, n);
 }
 
 // E consecutive 16-bit elements at p[i], i a multiple of E, as one load.
@@ -142,9 +147,9 @@ __device__ __forceinline__ void dijcLoad(const unsigned short* __restrict__ p, l
 
 // Dij w over the box rows: INIT as in k_dijap_apply (every voxel of the box written; else added to the voxels whose rows have entries).
 template <int G, int E, bool INIT>
-__global__ __launch_bounds__(256) void k_dijc_apply(const long long* __restrict__ rowPtr, const unsigned short* __restrict__ cCode,
-                                                    const unsigned short* __restrict__ cCol, const float* __restrict__ ws, float* __restrict__ dose,
-                                                    int nx, int ny, DijBox box, long long nRows) {
+__device__ __forceinline__ void dijcApplyBody(const long long* __restrict__ rowPtr, const unsigned short* __restrict__ cCode,
+                                              const unsigned short* __restrict__ cCol, const float* __restrict__ ws, float* __restrict__ dose,
+                                              int nx, int ny, DijBox box, long long nRows) {
     const long long r = ((long long)blockIdx.x * 256 + threadIdx.x) / G;
     const int t = threadIdx.x % G;
     long long a = 0, nPad = 0, n = 0;
@@ -171,14 +176,20 @@ __global__ __launch_bounds__(256) void k_dijc_apply(const long long* __restrict_
         dose[at] = INIT ? sum : dose[at] + sum;
     }
 }
+template <int G, int E, bool INIT>
+__global__ __launch_bounds__(256) void k_dijc_apply(const long long* __restrict__ rowPtr, const unsigned short* __restrict__ cCode,
+                                                    const unsigned short* __restrict__ cCol, const float* __restrict__ ws, float* __restrict__ dose,
+                                                    int nx, int ny, DijBox box, long long nRows) {
+    dijcApplyBody<G, E, INIT>(rowPtr, cCode, cCol, ws, dose, nx, ny, box, nRows);
+}
 
 // ---- the transposed product ----
 // First pass: k_dijap_apply_t's chunks and tree on fl(float(code) * g[voxel]). ROWS32: voxel = rows[e]; else base + offset.
 template <bool ROWS32>
-__global__ __launch_bounds__(256) void k_dijc_apply_t(const long long* __restrict__ colPtr, const unsigned short* __restrict__ code,
-                                                      const unsigned short* __restrict__ off, const int* __restrict__ base, const int* __restrict__ rows,
-                                                      const int* __restrict__ chunkCol, const int* __restrict__ chunkFirst, const float* __restrict__ g,
-                                                      float* __restrict__ partial, int nChunks) {
+__device__ __forceinline__ void dijcApplyTBody(const long long* __restrict__ colPtr, const unsigned short* __restrict__ code,
+                                               const unsigned short* __restrict__ off, const int* __restrict__ base, const int* __restrict__ rows,
+                                               const int* __restrict__ chunkCol, const int* __restrict__ chunkFirst, const float* __restrict__ g,
+                                               float* __restrict__ partial, int nChunks) {
     const int c = blockIdx.x * 4 + threadIdx.x / 64, lane = threadIdx.x % 64;
     if (c >= nChunks) return;
     const int j = chunkCol[c];
@@ -194,15 +205,26 @@ __global__ __launch_bounds__(256) void k_dijc_apply_t(const long long* __restric
     const float s = psReduce<1, 64>(acc, lane);
     if (lane == 0) partial[c] = s;
 }
+template <bool ROWS32>
+__global__ __launch_bounds__(256) void k_dijc_apply_t(const long long* __restrict__ colPtr, const unsigned short* __restrict__ code,
+                                                      const unsigned short* __restrict__ off, const int* __restrict__ base, const int* __restrict__ rows,
+                                                      const int* __restrict__ chunkCol, const int* __restrict__ chunkFirst, const float* __restrict__ g,
+                                                      float* __restrict__ partial, int nChunks) {
+    dijcApplyTBody<ROWS32>(colPtr, code, off, base, rows, chunkCol, chunkFirst, g, partial, nChunks);
+}
 // Second pass: the chunk sums of column j in dijReduceTBody's tree, then the column's scale once.
-__global__ __launch_bounds__(256) void k_dijc_reduce_t(const int* __restrict__ chunkFirst, const float* __restrict__ partial, const float* __restrict__ scale,
-                                                       float* __restrict__ out, int nSpots) {
+__device__ __forceinline__ void dijcReduceTBody(const int* __restrict__ chunkFirst, const float* __restrict__ partial, const float* __restrict__ scale,
+                                                float* __restrict__ out, int nSpots) {
     const int j = blockIdx.x * 4 + threadIdx.x / 64, lane = threadIdx.x % 64;
     if (j >= nSpots) return;
     float acc[1] = {0.0f};
     for (int c = chunkFirst[j] + lane; c < chunkFirst[j + 1]; c += 64) acc[0] += partial[c];
     const float s = psReduce<1, 64>(acc, lane);
     if (lane == 0) out[j] = scale[j] * s;
+}
+__global__ __launch_bounds__(256) void k_dijc_reduce_t(const int* __restrict__ chunkFirst, const float* __restrict__ partial, const float* __restrict__ scale,
+                                                       float* __restrict__ out, int nSpots) {
+    dijcReduceTBody(chunkFirst, partial, scale, out, nSpots);
 }
 
 }  // namespace rtd

@@ -61,9 +61,11 @@ int rtd_field_dose_influence_compact(rtd_handle hh, rtd_field ff, const rtd_dij_
     if (const char* v = std::getenv("RTD_DIJC_LANES")) G = std::atoi(v);
     if (const char* v = std::getenv("RTD_DIJC_PER")) E = std::atoi(v);
     if (!dijcTreeAllowed(G, E)) return fail(h, RTD_ERR_INVALID_ARG, who + ": RTD_DIJC_LANES must be 16 or 32 and RTD_DIJC_PER 1, 2 or 4");
+    bool wide = false;                                                // RTD_DIJC_ROWS32=1: the CSC side keeps the 32-bit rows whatever the spans are
+    if (const char* v = std::getenv("RTD_DIJC_ROWS32")) wide = std::atoi(v) != 0;
     RTD_HIP(h, hipSetDevice(h->device));
     hipStream_t s = h->stream;
-    const bool stands = m.compact() && (m.plainReleased() || (m.compactLanes() == G && m.compactPer() == E));
+    const bool stands = m.compact() && (m.plainReleased() || (m.compactLanes() == G && m.compactPer() == E && (!wide || m.compactRowBits() == 32)));
     if (!stands) {
         if (!m.prepared()) { const int st = rtd_field_dose_influence_prepare(hh, ff); if (st != RTD_OK) return st; }
         RTD_HIP(h, hipStreamSynchronize(s));
@@ -118,7 +120,7 @@ int rtd_field_dose_influence_compact(rtd_handle hh, rtd_field ff, const rtd_dij_
         if (e == hipSuccess) e = hipStreamSynchronize(s);             // the one read of the device's decisions
         if (e != hipSuccess) return hipFailed();
         if (const char* why = dijcRefusal(flags[0])) { undo(); return fail(h, RTD_ERR_INVALID_ARG, who + ": " + why); }
-        if (!dijcOffsetsFit(flags[1])) {                               // a group spans more than 65 535 voxels: the side keeps the 32-bit rows
+        if (wide || !dijcOffsetsFit(flags[1])) {                       // a group spans more than 65 535 voxels: the side keeps the 32-bit rows
             (void)hipFree(f->dDijcOff); f->dDijcOff = nullptr;
             m.compactRowsStayWide();
         }
@@ -236,13 +238,33 @@ int rtd_field_dose_influence_apply_t_compact(rtd_handle hh, rtd_field ff, const 
     return RTD_OK;
 }
 
-// The plain spectral optimiser of rtd_optimizer_create whose two products are the compact ones.
+// The spectral optimisers of rtd_optimizer_create, _create_robust and _create_voxelwise whose two products are the compact ones
+// (the last two: DESIGN.md section 29; the checks and the iteration are optCreate's and rtd_optimizer_run's).
 int rtd_optimizer_create_compact(rtd_handle hh, const rtd_field* fields, uint32_t n_fields, rtd_objective oo, const rtd_optimizer_options* opt,
                                  rtd_optimizer* out) {
     auto* h = reinterpret_cast<rtd_handle_impl*>(hh);
     if (!h) return RTD_ERR_INVALID_ARG;
     if (out) *out = nullptr;
     return optCreate(hh, fields, n_fields, nullptr, oo, opt, out, false, true);
+}
+
+int rtd_optimizer_create_robust_compact(rtd_handle hh, const rtd_field* fields, uint32_t n_fields, const rtd_robust_options* robust, rtd_objective oo,
+                                        const rtd_optimizer_options* opt, rtd_optimizer* out) {
+    auto* h = reinterpret_cast<rtd_handle_impl*>(hh);
+    if (!h) return RTD_ERR_INVALID_ARG;
+    if (!robust) return fail(h, RTD_ERR_INVALID_ARG, "rtd_optimizer_create_robust_compact: null pointer");
+    if (out) *out = nullptr;
+    return optCreate(hh, fields, n_fields, robust, oo, opt, out, false, true);
+}
+
+int rtd_optimizer_create_voxelwise_compact(rtd_handle hh, const rtd_field* fields, uint32_t n_fields, uint32_t n_scenarios, rtd_objective oo,
+                                           const rtd_optimizer_options* opt, rtd_optimizer* out) {
+    auto* h = reinterpret_cast<rtd_handle_impl*>(hh);
+    if (!h) return RTD_ERR_INVALID_ARG;
+    if (out) *out = nullptr;
+    rtd_robust_options ro{};
+    ro.mode = RTD_ROBUST_EXPECTED; ro.n_scenarios = n_scenarios;
+    return optCreate(hh, fields, n_fields, &ro, oo, opt, out, true, true);
 }
 
 }  // extern "C"

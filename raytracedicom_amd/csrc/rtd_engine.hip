@@ -44,6 +44,7 @@
 #include "rtd_dvh.hpp"
 #include "rtd_eud.hpp"
 #include "rtd_robust.hpp"
+#include "rtd_robust_compact.hpp"
 #include "rtd_voxelwise.hpp"
 #include "rtd_roi.hpp"
 #include "rtd_roi_ops.hpp"

@@ -1,5 +1,5 @@
 // rtd_optimizer_host.hpp — host side of the resident spot-weight optimiser, plain, robust and voxel-wise worst case (include/rtd.h,
-// DESIGN.md sections 12, 14 and 15; kernels in rtd_optimize.hpp, rtd_robust.hpp and rtd_voxelwise.hpp). Part of rtd_engine.hip's
+// DESIGN.md sections 12, 14, 15 and 29; kernels in rtd_optimize.hpp, rtd_robust.hpp, rtd_robust_compact.hpp and rtd_voxelwise.hpp). Part of rtd_engine.hip's
 // translation unit, included after rtd_dij_host.hpp and rtd_objective_host.hpp, whose products and evaluations an iteration launches.
 // A 4D optimiser (section 26) is created in rtd_fourd_host.hpp and runs through the branch of rtd_optimizer_run beside the robust one.
 #pragma once
@@ -63,8 +63,9 @@ struct rtd_optimizer_impl {
     DevBuf<float> dLbTrialDose, dLbVec;
     DevBuf<double> dLbGram, dLbPart, dLbGp, dLbLine;
     DevBuf<LbState> dLbState;
-    // A compact optimiser (section 28; rtd_optimizer_create_compact in rtd_dij_compact_host.hpp): a plain optimiser whose two products
-    // are rtd_field_dose_influence_apply_compact / _apply_t_compact. matEpoch: per field, what its matrix was at creation.
+    // A compact optimiser (sections 28 and 29; rtd_optimizer_create_compact, _create_robust_compact and _create_voxelwise_compact in
+    // rtd_dij_compact_host.hpp): a plain, robust or voxel-wise optimiser whose two products are rtd_field_dose_influence_apply_compact /
+    // _apply_t_compact, or their launches over the scenario axis. matEpoch: per field of sfields, what its matrix was at creation.
     bool compact = false;
     rtd_field_impl* const* row(int s) const { return sfields.data() + (size_t)s * fields.size(); }
     rtd_field_impl* sf(int s, size_t i) const { return row(s)[i]; }
@@ -113,15 +114,72 @@ int fourdSplit(rtd_handle hh, rtd_optimizer_impl* p);
 // Section 27 (rtd_lbfgs_host.hpp, included later): the iteration of an L-BFGS optimiser, and what rtd_optimizer_set_weights means to it.
 int lbfgsRun(rtd_handle hh, rtd_optimizer_impl* p, uint32_t n_iterations);
 int lbfgsWeightsSet(rtd_handle_impl* h, rtd_optimizer_impl* p);
+// Section 28 (rtd_dij_compact_host.hpp, included later): the row pointers the compact companion side reads.
+const long long* compactRowPtr(const rtd_field_impl* f);
+
+// The compact products of field position i over the scenario axis (section 29; kernels in rtd_robust_compact.hpp).
+template <int G, int E>
+void robustCompactLaunchApply(hipStream_t s, const RobustCFwd& a, long long most, int S, bool init, int nx, int ny) {
+    const dim3 grid((unsigned)((most * G + 255) / 256), (unsigned)S);
+    if (init) k_dijc_apply_batch<G, E, true><<<grid, 256, 0, s>>>(a, nx, ny);
+    else k_dijc_apply_batch<G, E, false><<<grid, 256, 0, s>>>(a, nx, ny);
+}
+void robustCompactForward(rtd_handle_impl* h, rtd_optimizer_impl* p, size_t i, int nx, int ny) {
+    const int S = p->nScen;
+    RobustCScale c{};
+    RobustCFwd a{};
+    long long most = 0;
+    for (int s = 0; s < S; ++s) {
+        const rtd_field_impl* f = p->sf(s, i);
+        c.scale[s] = f->dDijcScale; c.ws[s] = f->dDijcWs;
+        a.rowPtr[s] = compactRowPtr(f); a.cCode[s] = f->dDijcCCode; a.cCol[s] = f->dDijcCCol; a.ws[s] = f->dDijcWs; a.dose[s] = p->doseS[s];
+        a.nRows[s] = (i != 0 && f->matrix.nnz() == 0) ? 0 : (long long)f->matrix.rows();   // (as the single call: an empty matrix adds nothing)
+        a.box[s] = f->matrix.box();
+        most = std::max(most, a.nRows[s]);
+    }
+    if (!most) return;
+    const int nSpot = p->offset[i + 1] - p->offset[i];
+    k_dijc_scale_w_batch<<<dim3((unsigned)((nSpot + 255) / 256), (unsigned)S), 256, 0, h->stream>>>(c, (const float*)(p->w() + p->offset[i]), nSpot);
+    const FieldMatrix& m = p->sf(0, i)->matrix;                        // (creation saw to it: one tree per position)
+    switch (m.compactLanes() * 8 + m.compactPer()) {
+        case 16 * 8 + 1: robustCompactLaunchApply<16, 1>(h->stream, a, most, S, i == 0, nx, ny); break;
+        case 16 * 8 + 2: robustCompactLaunchApply<16, 2>(h->stream, a, most, S, i == 0, nx, ny); break;
+        case 16 * 8 + 4: robustCompactLaunchApply<16, 4>(h->stream, a, most, S, i == 0, nx, ny); break;
+        case 32 * 8 + 1: robustCompactLaunchApply<32, 1>(h->stream, a, most, S, i == 0, nx, ny); break;
+        case 32 * 8 + 2: robustCompactLaunchApply<32, 2>(h->stream, a, most, S, i == 0, nx, ny); break;
+        default: robustCompactLaunchApply<32, 4>(h->stream, a, most, S, i == 0, nx, ny); break;
+    }
+}
+void robustCompactAdjoint(rtd_handle_impl* h, rtd_optimizer_impl* p, size_t i) {
+    const int S = p->nScen;
+    RobustCAdj a{};
+    RobustCRed r{};
+    int most = 0;
+    for (int s = 0; s < S; ++s) {
+        const rtd_field_impl* f = p->sf(s, i);
+        a.colPtr[s] = (const long long*)f->dDijColPtr; a.code[s] = f->dDijcCode; a.off[s] = f->dDijcOff; a.base[s] = f->dDijcBase;
+        a.rows[s] = (const int*)f->dDijRows; a.chunkCol[s] = (const int*)f->dDijChunkCol; a.chunkFirst[s] = (const int*)f->dDijChunkFirst;
+        a.g[s] = p->gS[s]; a.partial[s] = f->dDijPartial; a.nChunks[s] = (int)f->matrix.chunks();
+        a.rows32[s] = f->matrix.compactRowBits() == 32;
+        r.chunkFirst[s] = (const int*)f->dDijChunkFirst; r.partial[s] = (const float*)f->dDijPartial; r.scale[s] = f->dDijcScale;
+        r.out[s] = p->dGradS + (size_t)s * p->n + p->offset[i];
+        most = std::max(most, a.nChunks[s]);
+    }
+    const int nSpot = p->offset[i + 1] - p->offset[i];
+    if (most) k_dijc_apply_t_batch<<<dim3((unsigned)((most + 3) / 4), (unsigned)S), 256, 0, h->stream>>>(a, (const RobustState*)p->dRobust);
+    k_dijc_reduce_t_batch<<<dim3((unsigned)((nSpot + 3) / 4), (unsigned)S), 256, 0, h->stream>>>(r, (const RobustState*)p->dRobust, nSpot);
+}
 
 // The same two products over the scenario axis (section 14; kernels in rtd_robust.hpp). Batched: per field position one launch covers
 // every scenario. Unbatched (RTD_ROBUST_NO_BATCH): the single-matrix launches, scenario by scenario. Either way scenario s's volume
-// gets what fieldsForward gives it, and gradS[s] what fieldsAdjoint gives it.
+// gets what fieldsForward gives it, and gradS[s] what fieldsAdjoint gives it. A compact optimiser (section 29) takes the same two
+// routes with the compact products.
 int robustForward(rtd_handle hh, rtd_handle_impl* h, rtd_optimizer_impl* p) {
     const size_t F = p->fields.size();
     const int S = p->nScen, nx = (int)p->fields[0]->doseDims[0], ny = (int)p->fields[0]->doseDims[1];
     if (!p->batch) {
-        for (int s = 0; s < S; ++s) { const int st = fieldsForward(hh, h, p, p->row(s), p->doseS[s], rtd_field_dose_influence_apply); if (st != RTD_OK) return st; }
+        const FieldApply apply = p->compact ? rtd_field_dose_influence_apply_compact : rtd_field_dose_influence_apply;
+        for (int s = 0; s < S; ++s) { const int st = fieldsForward(hh, h, p, p->row(s), p->doseS[s], apply); if (st != RTD_OK) return st; }
         return RTD_OK;
     }
     for (size_t i = 1; i < F; ++i) {
@@ -135,6 +193,7 @@ int robustForward(rtd_handle hh, rtd_handle_impl* h, rtd_optimizer_impl* p) {
         if (most) k_robust_clear_box<<<dim3((unsigned)((most + 255) / 256), (unsigned)S), 256, 0, h->stream>>>(a, nx, ny);
     }
     for (size_t i = 0; i < F; ++i) {
+        if (p->compact) { robustCompactForward(h, p, i, nx, ny); continue; }
         RobustFwd a{};
         long long most = 0;
         for (int s = 0; s < S; ++s) {
@@ -157,12 +216,14 @@ int robustAdjoint(rtd_handle hh, rtd_handle_impl* h, rtd_optimizer_impl* p) {
     const int S = p->nScen;
     if (!p->batch) {   // no decision on the host: every scenario's product is taken, the combine uses those with lambda != 0
         for (int s = 0; s < S; ++s) {
-            const int st = fieldsAdjoint(hh, p, p->row(s), p->gS[s], p->dGradS + (size_t)s * p->n, rtd_field_dose_influence_apply_t);
+            const int st = fieldsAdjoint(hh, p, p->row(s), p->gS[s], p->dGradS + (size_t)s * p->n,
+                                         p->compact ? rtd_field_dose_influence_apply_t_compact : rtd_field_dose_influence_apply_t);
             if (st != RTD_OK) return st;
         }
         return RTD_OK;
     }
     for (size_t i = 0; i < F; ++i) {
+        if (p->compact) { robustCompactAdjoint(h, p, i); continue; }
         RobustAdj a{};
         RobustRed r{};
         int most = 0;
@@ -251,6 +312,7 @@ int optReport(rtd_handle_impl* h, const char* who, const char* whose, const OptS
 
 // rtd_optimizer_create (robust == nullptr: one scenario, nothing of section 14 allocated or launched), rtd_optimizer_create_robust and
 // rtd_optimizer_create_voxelwise (voxelwise: what a robust optimiser owns plus the word of active scenarios; robust->mode is not read).
+// compact: the same three on the fields' compact forms (rtd_optimizer_create_compact, _create_robust_compact, _create_voxelwise_compact).
 int optCreate(rtd_handle hh, const rtd_field* fields, uint32_t n_fields, const rtd_robust_options* robust, rtd_objective oo,
               const rtd_optimizer_options* opt, rtd_optimizer* out, bool voxelwise = false, bool compact = false) {
     auto* h = reinterpret_cast<rtd_handle_impl*>(hh);
@@ -267,7 +329,8 @@ int optCreate(rtd_handle hh, const rtd_field* fields, uint32_t n_fields, const r
                 if (!(robust->probabilities[sc] > 0.0) || !std::isfinite(robust->probabilities[sc]))
                     return fail(h, RTD_ERR_INVALID_ARG, "rtd_optimizer_create_robust: a probability must be positive and finite");
     }
-    const std::string who = compact ? "rtd_optimizer_create_compact" : "rtd_optimizer_create";
+    const std::string who = !compact ? "rtd_optimizer_create" : !robust ? "rtd_optimizer_create_compact"
+                            : voxelwise ? "rtd_optimizer_create_voxelwise_compact" : "rtd_optimizer_create_robust_compact";
     rtd_optimizer_options op;
     int st = optCheckOptions(h, who, n_fields, opt, &op);
     if (st != RTD_OK) return st;
@@ -290,6 +353,13 @@ int optCreate(rtd_handle hh, const rtd_field* fields, uint32_t n_fields, const r
     std::vector<int> offset;
     st = optPrepare(hh, who, fields, n_fields, nAll, o, &offset, compact);
     if (st != RTD_OK) return st;
+    if (compact && robust)                                            // (G, E) is a launch template of the batched forward product
+        for (uint32_t i = n_fields; i < nAll; ++i) {
+            const FieldMatrix& m = reinterpret_cast<rtd_field_impl*>(fields[i])->matrix;
+            const FieldMatrix& m0 = reinterpret_cast<rtd_field_impl*>(fields[i % n_fields])->matrix;
+            if (m.compactLanes() != m0.compactLanes() || m.compactPer() != m0.compactPer())
+                return fail(h, RTD_ERR_INVALID_ARG, who + ": field f of every scenario must have the forward tree (lanes_per_row, entries_per_lane) of field f of scenario 0");
+        }
     auto* p = new rtd_optimizer_impl();
     p->obj = o; p->opt = op; p->nVox = o->nVox; p->offset = offset;
     p->compact = compact;

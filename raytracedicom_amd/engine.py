@@ -185,6 +185,8 @@ def lib():
         L.rtd_field_dose_influence_apply_compact.argtypes = [vp, vp, vp, vp, C.c_int]
         L.rtd_field_dose_influence_apply_t_compact.argtypes = [vp, vp, vp, vp]
         L.rtd_optimizer_create_compact.argtypes = [vp, vpp, C.c_uint32, vp, C.POINTER(abi.RtdOptimizerOptions), vpp]
+        L.rtd_optimizer_create_robust_compact.argtypes = L.rtd_optimizer_create_robust.argtypes
+        L.rtd_optimizer_create_voxelwise_compact.argtypes = L.rtd_optimizer_create_voxelwise.argtypes
         L.rtd_host_register.argtypes = [vp, C.c_size_t]
         L.rtd_host_unregister.argtypes = [vp]
         L.rtd_plan_create.argtypes = [C.POINTER(C.c_int), C.c_int, vpp]
@@ -379,7 +381,8 @@ class Field:
     def dose_influence_compact(self, release_plain=False, options=None):
         """rtd_field_dose_influence_compact: builds the compact form of the matrix of the last dose_influence() (binary16 codes under
         one scale per spot, 16-bit indices; synchronous). release_plain=True then frees the plain form's bulk: until the next
-        dose_influence() only the compact calls and Engine.create_compact_optimizer work on the field. options: an
+        dose_influence() only the compact calls and Engine.create_compact_optimizer, create_robust_compact_optimizer and
+        create_voxelwise_compact_optimizer work on the field. options: an
         abi.RtdDijCompactOptions instead of the keyword."""
         o = options if options is not None else abi.default_dij_compact_options()
         if options is None:
@@ -865,7 +868,8 @@ class Optimizer:
         of abi.RtdWarp, one per row of scenario_fields) the rows are breathing phases and it is a 4D optimiser
         (rtd_optimizer_create_4d; phase_weights: one positive weight per phase, None for equal ones). With lbfgs=True it is the
         L-BFGS iteration with its line search on the device (rtd_optimizer_create_lbfgs; options: an abi.RtdLbfgsOptions or None). With
-        compact=True it is the spectral iteration on the fields' compact matrices (rtd_optimizer_create_compact)."""
+        compact=True it is the spectral iteration on the fields' compact matrices (rtd_optimizer_create_compact), and with
+        scenario_fields the robust or voxel-wise one on them (rtd_optimizer_create_robust_compact, _create_voxelwise_compact)."""
         self.eng = eng
         self.objective = objective
         self._h = C.c_void_p()
@@ -905,7 +909,8 @@ class Optimizer:
             eng._check(lib().rtd_optimizer_create_4d(eng._h, arr, n_fields, C.byref(fo), objective._h, po, C.byref(self._h)))
             return
         if voxelwise:
-            eng._check(lib().rtd_optimizer_create_voxelwise(eng._h, arr, n_fields, len(self.scenario_fields), objective._h, po, C.byref(self._h)))
+            create = lib().rtd_optimizer_create_voxelwise_compact if compact else lib().rtd_optimizer_create_voxelwise
+            eng._check(create(eng._h, arr, n_fields, len(self.scenario_fields), objective._h, po, C.byref(self._h)))
             return
         ro = abi.RtdRobustOptions()
         ro.mode = int(abi.RTD_ROBUST_EXPECTED if mode is None else mode)
@@ -915,7 +920,8 @@ class Optimizer:
             if pr.size != len(self.scenario_fields):
                 raise ValueError("one probability per scenario")
             ro.probabilities = pr.ctypes.data_as(C.POINTER(C.c_double))
-        eng._check(lib().rtd_optimizer_create_robust(eng._h, arr, n_fields, C.byref(ro), objective._h, po, C.byref(self._h)))
+        create = lib().rtd_optimizer_create_robust_compact if compact else lib().rtd_optimizer_create_robust
+        eng._check(create(eng._h, arr, n_fields, C.byref(ro), objective._h, po, C.byref(self._h)))
 
     def set_weights(self, field_index, dev_w):
         self.eng._check(lib().rtd_optimizer_set_weights(self.eng._h, self._h, int(field_index), C.c_void_p(int(dev_w))))
@@ -1283,6 +1289,17 @@ class Engine:
         """rtd_optimizer_create_voxelwise: the voxel-wise worst case over the scenarios (every voxel takes, per term, the scenario
         dose that is worst for it). scenario_fields as create_robust_optimizer; the objective must not have DVH or EUD terms."""
         return Optimizer(self, None, objective, options, scenario_fields=scenario_fields, voxelwise=True)
+
+    def create_robust_compact_optimizer(self, sfields, obj, mode, probabilities=None, options=None):
+        """rtd_optimizer_create_robust_compact: create_robust_optimizer on the fields' compact matrices (every field of sfields, a list
+        of per-scenario field lists, needs dose_influence_compact() first; it works after release_plain). Field f of every scenario
+        must have been built with the forward tree of field f of scenario 0."""
+        return Optimizer(self, None, obj, options, scenario_fields=sfields, mode=mode, probabilities=probabilities, compact=True)
+
+    def create_voxelwise_compact_optimizer(self, sfields, obj, options=None):
+        """rtd_optimizer_create_voxelwise_compact: create_voxelwise_optimizer on the fields' compact matrices; sfields as
+        create_robust_compact_optimizer."""
+        return Optimizer(self, None, obj, options, scenario_fields=sfields, voxelwise=True, compact=True)
 
     def create_4d_optimizer(self, phase_fields, warps, objective, weights=None, options=None):
         """rtd_optimizer_create_4d: phase_fields is a list of per-phase field lists (the same beams computed on every phase's CT, each
