@@ -1703,7 +1703,8 @@ int rtd_planset_destroy(rtd_handle h, rtd_planset ps);
  * rtd_optimizer_set_let_objective, rtd_optimizer_set_rbe, rtd_optimizer_scenario_values and _scenario_dose refuse such an optimiser
  * with RTD_ERR_INVALID_ARG. RTD_ERR_NOT_READY: a field without a matrix.
  *
- * Out of scope: DVH and EUD terms in the line search; L-BFGS behind the robust, voxel-wise, plan-set, 4D, LET and RBE optimisers;
+ * DVH and EUD terms in the line search and the compact matrix: rtd_optimizer_create_lbfgs_ex, the next block.
+ * Out of scope: L-BFGS behind the robust, voxel-wise, plan-set, 4D, LET and RBE optimisers;
  * the Cauchy-point / subspace step of full L-BFGS-B; nuclear_corr and the rtd_plan_* path (as the matrix itself).
  */
 enum { RTD_LBFGS_MAX_MEMORY = 16, RTD_LBFGS_MAX_HALVINGS = 7 };
@@ -1749,6 +1750,62 @@ int rtd_optimizer_create_lbfgs(rtd_handle h, const rtd_field* fields, uint32_t n
                                rtd_optimizer* out);
 int rtd_optimizer_lbfgs_report(rtd_handle h, rtd_optimizer opt, rtd_lbfgs_report* r);
 int rtd_optimizer_lbfgs_buffers(rtd_handle h, rtd_optimizer opt, rtd_lbfgs_buffers* b);
+
+/*
+ * ---- L-BFGS with DVH and EUD terms, and on the compact matrix ----
+ *
+ * Additive to the blocks above (RTD_ABI_VERSION stays 3; no entry point or structure above changes; rtd_optimizer_create_lbfgs keeps
+ * its behaviour, its refusals and its bits). rtd_optimizer_create_lbfgs_ex returns an ordinary L-BFGS optimiser: rtd_optimizer_run,
+ * _result, _weights, _set_weights, _dose, _lbfgs_report and _lbfgs_buffers work on it as on one of rtd_optimizer_create_lbfgs, and
+ * rtd_optimizer_set_let_objective, _set_rbe, _scenario_values and _scenario_dose refuse it with the same codes. It accepts every term
+ * kind of rtd_objective_eval, and with RTD_LBFGS_COMPACT its two products are rtd_field_dose_influence_apply_compact /
+ * _apply_t_compact of the block below.
+ *
+ * THE LINE SEARCH WITH COUPLED TERMS. D_v (a DVH term) and E (an EUD term) couple all voxels of a structure, so every trial of step 7
+ * needs a selection and a power sum of its own.
+ *   If the objective has NO DVH or EUD term, the iteration is the one above, bit for bit: trials are evaluated on the float64 t_k, and
+ *   rtd_optimizer_create_lbfgs_ex with flags 0 reproduces rtd_optimizer_create_lbfgs exactly.
+ *   If it has one, every term of every trial is evaluated on the float32-rounded trial volume r_k[v] = float(t_k[v]), with t_0 =
+ *   double(d1[v]) and t_k = double(d0[v]) + 2^-k * (double(d1[v]) - double(d0[v])), no contraction: exactly the expression step 7
+ *   writes back as the new d0. (D_v is an order statistic of a float32 volume, selected on 32-bit keys, and the accepted trial
+ *   becomes the tracked dose by that same rounding.) Two properties follow:
+ *     1. F_k has the bits of rtd_objective_eval(r_k).values[0]: the same trees, the same selection, the same power sums. The DVH
+ *        thresholds of trial k are rtd_objective_dose_at_volume(r_k), the E of an EUD term is rtd_objective_eud(r_k).
+ *     2. After an accepted trial k the next iteration's f (its history entry) equals trial_values[k] bit for bit: no accepted step
+ *        raises the objective, with no rounding allowance.
+ *   Step 1 (value and gradient with D_v and K held fixed) is rtd_objective_eval as before. Per line search, whatever K is: three
+ *   counting passes and one finish over (chunk, selection, trial) for the DVH terms, one sum and one finish for the EUD terms, the
+ *   line kernel and the decision; launches only, no host read, integer counting and fixed float64 trees, so the iteration can be
+ *   captured into a graph and gives the same bits across calls, handles, processes and replays.
+ *
+ * rtd_optimizer_create_lbfgs_ex  as rtd_optimizer_create_lbfgs, except that DVH and EUD terms are accepted.
+ *                          flags: an unknown bit is RTD_ERR_INVALID_ARG.
+ *                          Without RTD_LBFGS_COMPACT the refusals are those of rtd_optimizer_create_lbfgs,
+ *                          RTD_ERR_NOT_READY for a field whose plain form has been released among them. With RTD_LBFGS_COMPACT every
+ *                          field needs its compact form (RTD_ERR_NOT_READY otherwise, as rtd_optimizer_create_compact); creation
+ *                          prepares nothing, so it works after release_plain; rtd_optimizer_run refuses with RTD_ERR_NOT_READY, before
+ *                          its first launch, once a field's matrix has been computed again. The per-trial arrays are allocated here
+ *                          from the objective's own counts (at most 12.6 MB of histograms); RTD_ERR_OUT_OF_MEMORY keeps nothing.
+ * rtd_optimizer_lbfgs_line_buffers  what the line search reads and leaves, for inspection (read-only; no synchronisation): d0, d1, and
+ *                          of the last line search thresholds[k][t] = D_v of DVH term t at trial k and eud[k][t] = {E, K, value} of EUD
+ *                          term t at trial k (entries of other terms are 0). Both are NULL when the objective has no DVH or EUD
+ *                          term. RTD_ERR_INVALID_ARG on anything that is not an L-BFGS optimiser.
+ *
+ * Out of scope: L-BFGS behind the robust, voxel-wise, plan-set, 4D, LET and RBE optimisers; the Cauchy point of L-BFGS-B; any change
+ * to the forward tree of the compact product.
+ */
+enum { RTD_LBFGS_COMPACT = 1u };   /* products read the fields' compact matrices */
+typedef struct rtd_lbfgs_line_buffers {
+    const float* d0;            /* the tracked dose of w */
+    const float* d1;            /* the dose of w_full (rtd_lbfgs_buffers.trial_dose) */
+    const float* thresholds;    /* float[n_trials][RTD_OBJ_MAX_TERMS], indexed by term; NULL without DVH or EUD terms */
+    const double* eud;          /* double[n_trials][RTD_OBJ_MAX_TERMS][3]: E, K, value; NULL without DVH or EUD terms */
+    uint32_t n_trials, n_terms;
+    uint32_t reserved[6];
+} rtd_lbfgs_line_buffers;       /* 64 bytes */
+int rtd_optimizer_create_lbfgs_ex(rtd_handle h, const rtd_field* fields, uint32_t n_fields, rtd_objective obj, const rtd_lbfgs_options* o,
+                                  uint32_t flags, rtd_optimizer* out);
+int rtd_optimizer_lbfgs_line_buffers(rtd_handle h, rtd_optimizer opt, rtd_lbfgs_line_buffers* b);
 
 /*
  * ---- Compact dose-influence matrix: fp16 values, 16-bit indices, products of its own ----

@@ -298,6 +298,16 @@ class RtdLbfgsBuffers(C.Structure):
                 ("n", C.c_uint32), ("memory", C.c_uint32), ("n_chunks", C.c_uint32), ("n_trials", C.c_uint32)]
 
 
+RTD_LBFGS_COMPACT = 1
+
+
+class RtdLbfgsLineBuffers(C.Structure):
+    """rtd_lbfgs_line_buffers: what the line search of an L-BFGS optimiser reads and leaves, for inspection: d0, d1, the per-trial DVH
+    thresholds float[n_trials][RTD_OBJ_MAX_TERMS] and EUD triples double[n_trials][RTD_OBJ_MAX_TERMS][3] (64 bytes)."""
+    _fields_ = [("d0", C.c_void_p), ("d1", C.c_void_p), ("thresholds", C.c_void_p), ("eud", C.c_void_p),
+                ("n_trials", C.c_uint32), ("n_terms", C.c_uint32), ("reserved", C.c_uint32 * 6)]
+
+
 def default_lbfgs_options():
     """rtd_default_lbfgs_options: 8 pairs, 5 halvings (K = 6), c1 = 1e-4, the spectral iteration's first step rule."""
     o = RtdLbfgsOptions()

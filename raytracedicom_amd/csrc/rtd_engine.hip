@@ -57,6 +57,7 @@
 #include "rtd_rbe.hpp"
 #include "rtd_planset.hpp"
 #include "rtd_lbfgs.hpp"
+#include "rtd_lbfgs_terms.hpp"
 #include "rtd_field_memory.hpp"
 #include "rtd_field_matrix.hpp"
 #include "rtd_engine_impl.hpp"

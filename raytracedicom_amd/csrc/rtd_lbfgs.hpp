@@ -328,9 +328,13 @@ __global__ __launch_bounds__(256) void k_lb_line(const int* __restrict__ uv, con
 }
 
 // One block of kLbScalarThreads (a wave per (term, trial) at a time). F_k by objReduce's tree per trial (block b to lane b mod 64, ascending, butterfly, times wn_t, the terms in term order),
-// gp from its chunk sums, then the decision.
-__global__ __launch_bounds__(kLbScalarThreads) void k_lb_decide(const double* __restrict__ partial, int nBlocks, const ObjTerm* __restrict__ terms, int nTerms,
-                                                   const double* __restrict__ gpPart, int nCh, OptState* __restrict__ st, LbState* __restrict__ lb, LbParams P) {
+// gp from its chunk sums, then the decision. kEud: the share of an EUD term in F_k is eud[(k * kObjMaxTerms + t) * 3 + 2], the value
+// k_lb_eud_finish left for trial k (rtd_lbfgs_terms.hpp), as in objReduce<true>; without it nothing of this is compiled in, and eud is
+// not read. k_lb_decide is the kernel as it was; k_lb_decide_terms (rtd_lbfgs_terms.hpp) is the same body with kEud.
+template <bool kEud>
+__device__ __forceinline__ void lbDecide(const double* __restrict__ partial, int nBlocks, const ObjTerm* __restrict__ terms, int nTerms,
+                                         const double* __restrict__ gpPart, int nCh, OptState* __restrict__ st, LbState* __restrict__ lb, LbParams P,
+                                         const double* __restrict__ eud) {
     __shared__ double sh[kObjMaxTerms * kLbMaxTrials];
     __shared__ double F[kLbMaxTrials];
     __shared__ double shGp;
@@ -340,7 +344,11 @@ __global__ __launch_bounds__(kLbScalarThreads) void k_lb_decide(const double* __
         double acc = 0.0;
         for (int b = lane; b < nBlocks; b += 64) acc += partial[((size_t)t * nBlocks + b) * K + k];
         acc = optWaveSum(acc);
-        if (lane == 0) sh[q] = terms[t].wn * acc;
+        if (lane == 0) {
+            double val = terms[t].wn * acc;
+            if (kEud && terms[t].kind >= RTD_OBJ_SQ_EUD) val = eud[((size_t)k * kObjMaxTerms + t) * 3 + 2];
+            sh[q] = val;
+        }
     }
     if (wave == nW - 1) {
         double acc = 0.0;
@@ -382,6 +390,10 @@ __global__ __launch_bounds__(kLbScalarThreads) void k_lb_decide(const double* __
     }
     s.alpha = L.a;
     *st = s; *lb = L;
+}
+__global__ __launch_bounds__(kLbScalarThreads) void k_lb_decide(const double* __restrict__ partial, int nBlocks, const ObjTerm* __restrict__ terms, int nTerms,
+                                                   const double* __restrict__ gpPart, int nCh, OptState* __restrict__ st, LbState* __restrict__ lb, LbParams P) {
+    lbDecide<false>(partial, nBlocks, terms, nTerms, gpPart, nCh, st, lb, P, nullptr);
 }
 
 __global__ __launch_bounds__(256) void k_lb_update(const LbState* __restrict__ lb, float* __restrict__ w, float* __restrict__ wPrev,

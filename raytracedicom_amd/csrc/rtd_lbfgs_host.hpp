@@ -1,21 +1,23 @@
-// rtd_lbfgs_host.hpp — rtd_optimizer_create_lbfgs, the iteration rtd_optimizer_run launches on such an optimiser, and
-// rtd_optimizer_lbfgs_report / _lbfgs_buffers (include/rtd.h "L-BFGS with a line search on the device"; kernels
-// in rtd_lbfgs.hpp). Part of rtd_engine.hip's translation unit, included after rtd_fourd_host.hpp: an L-BFGS optimiser is a plain
+// rtd_lbfgs_host.hpp — rtd_optimizer_create_lbfgs and _create_lbfgs_ex, the iteration rtd_optimizer_run launches on such an optimiser,
+// and rtd_optimizer_lbfgs_report / _lbfgs_buffers / _lbfgs_line_buffers (include/rtd.h "L-BFGS with a line search on the device" and
+// "L-BFGS with DVH and EUD terms, and on the compact matrix", DESIGN.md sections 27 and 30; kernels in rtd_lbfgs.hpp and
+// rtd_lbfgs_terms.hpp). Part of rtd_engine.hip's translation unit, included after rtd_fourd_host.hpp: an L-BFGS optimiser is a plain
 // rtd_optimizer_impl (one row of fields, dDose the tracked dose d0, dG, the five vectors, dState, dHistory) with `lbfgs` set and the
 // buffers below; it notes its matrices as a 4D optimiser does (matEpoch / matChunks, fourdMatricesStand).
 #pragma once
 
 namespace {
 
-// vol = sum_f Dij_f x_f for any concatenated vector x, by fieldsForward's rule.
+// vol = sum_f Dij_f x_f for any concatenated vector x, by fieldsForward's rule; the compact product on a compact optimiser.
 int lbForward(rtd_handle hh, rtd_handle_impl* h, rtd_optimizer_impl* p, const float* x, float* vol) {
     for (size_t i = 1; i < p->fields.size(); ++i) {
         const rtd_field_impl* f = p->fields[i];
         const long long nRows = (long long)f->matrix.rows();
         if (nRows) k_opt_clear_box<<<(unsigned)((nRows + 255) / 256), 256, 0, h->stream>>>(vol, (int)f->doseDims[0], (int)f->doseDims[1], f->matrix.box(), nRows);
     }
+    const FieldApply apply = p->compact ? rtd_field_dose_influence_apply_compact : rtd_field_dose_influence_apply;
     for (size_t i = 0; i < p->fields.size(); ++i) {
-        const int st = rtd_field_dose_influence_apply(hh, reinterpret_cast<rtd_field>(p->fields[i]), x + p->offset[i], vol, i == 0 ? 1 : 0);
+        const int st = apply(hh, reinterpret_cast<rtd_field>(p->fields[i]), x + p->offset[i], vol, i == 0 ? 1 : 0);
         if (st != RTD_OK) return st;
     }
     return RTD_OK;
@@ -29,11 +31,61 @@ template <int K> void lbLaunchLine(rtd_handle_impl* h, rtd_optimizer_impl* p) {
         (const float*)p->dDose, (const float*)p->dLbTrialDose, p->dLbLine, o->nBlocks);
 }
 
+template <int K> void lbLaunchLineTerms(rtd_handle_impl* h, rtd_optimizer_impl* p) {
+    rtd_objective_impl* o = p->obj;
+    const int nTerms = (int)o->terms.size();
+    k_lb_line_terms<K><<<(unsigned)o->nBlocks, 256, (size_t)4 * nTerms * K * sizeof(double), h->stream>>>(
+        (const int*)o->tab.dUv, (const int*)o->tab.dTPtr, (const unsigned char*)o->tab.dTIdx, (const ObjTerm*)o->tab.dTerms, nTerms, o->nU,
+        (const float*)p->dDose, (const float*)p->dLbTrialDose, p->dLbLine, o->nBlocks, (const float*)p->dLbThr);
+}
+template <int K> void lbLaunchEudSum(rtd_handle_impl* h, rtd_optimizer_impl* p, dim3 grid) {
+    rtd_objective_impl* o = p->obj;
+    k_lb_eud_sum<K><<<grid, 256, 0, h->stream>>>((const int*)o->dvh.dRoiIdx, (const float*)p->dDose, (const float*)p->dLbTrialDose, o->eudSel, o->nChMax,
+                                                 p->dLbEudPart);
+}
+#define RTD_LB_PER_K(K, call) \
+    switch (K) { case 1: call(1); break; case 2: call(2); break; case 3: call(3); break; case 4: call(4); break; \
+                 case 5: call(5); break; case 6: call(6); break; case 7: call(7); break; default: call(8); break; }
+
+// The K-wide selections (four launches) and power sums (two) of the trial volumes r_k formed from d0 and d1, then the line kernel.
+void lbLineCoupled(rtd_handle_impl* h, rtd_optimizer_impl* p, int K) {
+    rtd_objective_impl* o = p->obj;
+    hipStream_t s = h->stream;
+    const int* roiIdx = (const int*)o->dvh.dRoiIdx;
+    const float* d0 = p->dDose;
+    const float* d1 = p->dLbTrialDose;
+    if (o->nEvalSel) {
+        int nMax = 0;
+        for (int i = 0; i < o->nEvalSel; ++i) nMax = std::max(nMax, o->evalSel.n[i]);
+        const dim3 grid((unsigned)((nMax + kDvhChunk - 1) / kDvhChunk), (unsigned)o->nEvalSel, (unsigned)K);
+        k_lb_dvh_pass<0><<<grid, 256, 0, s>>>(roiIdx, d0, d1, o->evalSel, p->dLbHist);
+        k_lb_dvh_pass<1><<<grid, 256, 0, s>>>(roiIdx, d0, d1, o->evalSel, p->dLbHist);
+        k_lb_dvh_pass<2><<<grid, 256, 0, s>>>(roiIdx, d0, d1, o->evalSel, p->dLbHist);
+        k_lb_dvh_finish<<<dim3((unsigned)o->nEvalSel, (unsigned)K), 256, 0, s>>>(o->evalSel, p->dLbHist, p->dLbThr);
+    }
+    if (o->nEudSel) {
+        int nMax = 0;
+        for (int i = 0; i < o->nEudSel; ++i) nMax = std::max(nMax, o->eudSel.n[i]);
+        const dim3 grid((unsigned)((nMax + kEudChunk - 1) / kEudChunk), (unsigned)o->nEudSel);
+#define RTD_LB_CALL(k) lbLaunchEudSum<k>(h, p, grid)
+        RTD_LB_PER_K(K, RTD_LB_CALL)
+#undef RTD_LB_CALL
+        k_lb_eud_finish<<<dim3((unsigned)o->nEudSel, (unsigned)K), 256, 0, s>>>(o->eudSel, (const double*)p->dLbEudPart, o->nChMax, p->dLbEud);
+    }
+#define RTD_LB_CALL(k) lbLaunchLineTerms<k>(h, p)
+    RTD_LB_PER_K(K, RTD_LB_CALL)
+#undef RTD_LB_CALL
+}
+
 int lbfgsRun(rtd_handle hh, rtd_optimizer_impl* p, uint32_t n_iterations) {
     auto* h = reinterpret_cast<rtd_handle_impl*>(hh);
     rtd_objective_impl* o = p->obj;
     const std::string who = "rtd_optimizer_run";
-    if (!fourdMatricesStand(p))                                       // (in front of the first launch: a refused run launches nothing)
+    if (p->compact) {                                                 // (in front of the first launch: a refused run launches nothing)
+        for (size_t i = 0; i < p->sfields.size(); ++i)
+            if (!p->sfields[i]->matrix.isCompactOf(p->matEpoch[i]))
+                return fail(h, RTD_ERR_NOT_READY, who + ": a field's dose-influence matrix has been computed again since rtd_optimizer_create_lbfgs_ex (destroy the optimiser and create a new one)");
+    } else if (!fourdMatricesStand(p))
         return fail(h, RTD_ERR_NOT_READY, who + ": a field's dose-influence matrix has been computed again since rtd_optimizer_create_lbfgs (destroy the optimiser and create a new one)");
     if (!o->built || o->epoch != p->lbObjEpoch)
         return fail(h, RTD_ERR_NOT_READY, who + ": the objective has changed since rtd_optimizer_create_lbfgs (destroy the optimiser and create a new one)");
@@ -56,7 +108,7 @@ int lbfgsRun(rtd_handle hh, rtd_optimizer_impl* p, uint32_t n_iterations) {
     }
     for (uint32_t it = 0; it < n_iterations; ++it) {
         int st = evalObjective(h, o, p->dDose, p->dValues, p->dG);                                          // 1.
-        if (st == RTD_OK) st = fieldsAdjoint(hh, p, p->row(0), p->dG, p->grad(), rtd_field_dose_influence_apply_t);
+        if (st == RTD_OK) st = fieldsAdjoint(hh, p, p->row(0), p->dG, p->grad(), p->compact ? rtd_field_dose_influence_apply_t_compact : rtd_field_dose_influence_apply_t);
         if (st != RTD_OK) return st;
         k_lb_gram<<<dim3((unsigned)((nCh + 3) / 4), (unsigned)(2 * m + 3)), 256, 0, s>>>((const float*)p->w(), (const float*)p->wPrev(), (const float*)p->grad(), (const float*)p->gradPrev(),
                                                             (const float*)ring, sNew, yNew, ghat, n, nCh, m, (const LbState*)p->dLbState, p->dLbPart);   // 2., 3., 4.
@@ -66,18 +118,17 @@ int lbfgsRun(rtd_handle hh, rtd_optimizer_impl* p, uint32_t n_iterations) {
                                                                  (const LbState*)p->dLbState, p->dLbGp);                                               // 6.
         st = lbForward(hh, h, p, wFull, p->dLbTrialDose);
         if (st != RTD_OK) return st;
-        switch (K) {                                                                                        // 7.
-            case 1: lbLaunchLine<1>(h, p); break;
-            case 2: lbLaunchLine<2>(h, p); break;
-            case 3: lbLaunchLine<3>(h, p); break;
-            case 4: lbLaunchLine<4>(h, p); break;
-            case 5: lbLaunchLine<5>(h, p); break;
-            case 6: lbLaunchLine<6>(h, p); break;
-            case 7: lbLaunchLine<7>(h, p); break;
-            default: lbLaunchLine<8>(h, p); break;
+        if (p->lbCoupled) {                                                                                 // 7. with DVH or EUD terms
+            lbLineCoupled(h, p, K);
+            k_lb_decide_terms<<<1, kLbScalarThreads, 0, s>>>((const double*)p->dLbLine, o->nBlocks, (const ObjTerm*)o->tab.dTerms, nTerms, (const double*)p->dLbGp, nCh,
+                                                            p->dState, p->dLbState, P, (const double*)p->dLbEud);
+        } else {                                                                                            // 7.
+#define RTD_LB_CALL(k) lbLaunchLine<k>(h, p)
+            RTD_LB_PER_K(K, RTD_LB_CALL)
+#undef RTD_LB_CALL
+            k_lb_decide<<<1, kLbScalarThreads, 0, s>>>((const double*)p->dLbLine, o->nBlocks, (const ObjTerm*)o->tab.dTerms, nTerms, (const double*)p->dLbGp, nCh,
+                                                      p->dState, p->dLbState, P);
         }
-        k_lb_decide<<<1, kLbScalarThreads, 0, s>>>((const double*)p->dLbLine, o->nBlocks, (const ObjTerm*)o->tab.dTerms, nTerms, (const double*)p->dLbGp, nCh, p->dState,
-                                      p->dLbState, P);
         k_lb_update<<<(unsigned)std::max((n + 255) / 256, 1), 256, 0, s>>>((const LbState*)p->dLbState, p->w(), p->wPrev(), (const float*)p->grad(), p->gradPrev(),
                                                                           (const float*)wFull, n);
         if (boxRows)
@@ -106,14 +157,16 @@ void rtd_default_lbfgs_options(rtd_lbfgs_options* o) {
     o->memory = 8; o->max_halvings = 5; o->armijo_c1 = 1e-4; o->initial_step = 0.0; o->history_capacity = 4096;
 }
 
-int rtd_optimizer_create_lbfgs(rtd_handle hh, const rtd_field* fields, uint32_t n_fields, rtd_objective oo, const rtd_lbfgs_options* opt,
-                               rtd_optimizer* out) {
+// rtd_optimizer_create_lbfgs (ex == false: flags is 0, and an objective with DVH or EUD terms is refused) and _create_lbfgs_ex.
+static int lbfgsCreate(rtd_handle hh, const std::string& who, bool ex, const rtd_field* fields, uint32_t n_fields, rtd_objective oo,
+                       const rtd_lbfgs_options* opt, uint32_t flags, rtd_optimizer* out) {
     auto* h = reinterpret_cast<rtd_handle_impl*>(hh);
     auto* o = reinterpret_cast<rtd_objective_impl*>(oo);
     if (!h) return RTD_ERR_INVALID_ARG;
     if (out) *out = nullptr;
-    const std::string who = "rtd_optimizer_create_lbfgs";
     if (!fields || !o || !out) return fail(h, RTD_ERR_INVALID_ARG, who + ": null pointer");
+    if (flags & ~(uint32_t)RTD_LBFGS_COMPACT) return fail(h, RTD_ERR_INVALID_ARG, who + ": unknown bits in flags");
+    const bool compact = (flags & RTD_LBFGS_COMPACT) != 0;
     rtd_lbfgs_options lo;
     rtd_default_lbfgs_options(&lo);
     if (opt) lo = *opt;
@@ -132,14 +185,15 @@ int rtd_optimizer_create_lbfgs(rtd_handle hh, const rtd_field* fields, uint32_t 
         if (st != RTD_OK) return st;
     }
     if (o->terms.empty()) return fail(h, RTD_ERR_INVALID_ARG, who + ": the objective has no terms");
-    if (o->hasDvhTerms()) return fail(h, RTD_ERR_INVALID_ARG, who + ": an objective with DVH terms has no K-wide line evaluation (D_v couples the voxels of a structure)");
-    if (o->hasEudTerms()) return fail(h, RTD_ERR_INVALID_ARG, who + ": an objective with EUD terms has no K-wide line evaluation (E couples the voxels of a structure)");
+    if (!ex && o->hasDvhTerms()) return fail(h, RTD_ERR_INVALID_ARG, who + ": an objective with DVH terms has no K-wide line evaluation (D_v couples the voxels of a structure)");
+    if (!ex && o->hasEudTerms()) return fail(h, RTD_ERR_INVALID_ARG, who + ": an objective with EUD terms has no K-wide line evaluation (E couples the voxels of a structure)");
     std::vector<int> offset;
-    st = optPrepare(hh, who, fields, n_fields, n_fields, o, &offset);
+    st = optPrepare(hh, who, fields, n_fields, n_fields, o, &offset, compact);
     if (st != RTD_OK) return st;
 
     auto* p = new rtd_optimizer_impl();
     p->obj = o; p->opt = op; p->nVox = o->nVox; p->offset = offset;
+    p->compact = compact; p->lbCoupled = o->nEvalSel > 0 || o->nEudSel > 0;
     p->lbfgs = true; p->lbOpt = lo; p->lbObjEpoch = o->epoch; p->lbDoseStale = true;
     int lo3[3] = {0, 0, 0}, hi3[3] = {-1, -1, -1};
     bool any = false;
@@ -175,6 +229,17 @@ int rtd_optimizer_create_lbfgs(rtd_handle hh, const rtd_field* fields, uint32_t 
     if (e == hipSuccess) e = p->dLbPart.alloc(nPart);
     if (e == hipSuccess) e = p->dLbGp.alloc(nGp);
     if (e == hipSuccess) e = p->dLbLine.alloc(nLine);
+    // per trial of the line search, from the objective's own counts (the histograms: at most 8 x 64 x 3 x 2048 x 4 B = 12.6 MB)
+    const size_t nHist = (size_t)K * o->nEvalSel * 3 * kDvhBins, nThr = p->lbCoupled ? (size_t)K * kObjMaxTerms : 0;
+    const size_t nEudPart = (size_t)K * o->nEudSel * std::max(o->nChMax, 1);
+    if (e == hipSuccess && nHist) e = p->dLbHist.alloc(nHist);
+    if (e == hipSuccess && nThr) e = p->dLbThr.alloc(nThr);
+    if (e == hipSuccess && nThr) e = p->dLbEud.alloc(3 * nThr);
+    if (e == hipSuccess && nEudPart) e = p->dLbEudPart.alloc(nEudPart);
+    if (e == hipSuccess && nHist) e = hipMemsetAsync(p->dLbHist, 0, nHist * sizeof(unsigned), s);
+    if (e == hipSuccess && nThr) e = hipMemsetAsync(p->dLbThr, 0, nThr * sizeof(float), s);
+    if (e == hipSuccess && nThr) e = hipMemsetAsync(p->dLbEud, 0, 3 * nThr * sizeof(double), s);
+    if (e == hipSuccess && nEudPart) e = hipMemsetAsync(p->dLbEudPart, 0, nEudPart * sizeof(double), s);
     if (e == hipSuccess) e = hipMemsetAsync(p->dDose, 0, p->nVox * sizeof(float), s);
     if (e == hipSuccess) e = hipMemsetAsync(p->dG, 0, p->nVox * sizeof(float), s);
     if (e == hipSuccess) e = hipMemsetAsync(p->dLbTrialDose, 0, p->nVox * sizeof(float), s);
@@ -209,6 +274,16 @@ int rtd_optimizer_create_lbfgs(rtd_handle hh, const rtd_field* fields, uint32_t 
     return RTD_OK;
 }
 
+int rtd_optimizer_create_lbfgs(rtd_handle hh, const rtd_field* fields, uint32_t n_fields, rtd_objective oo, const rtd_lbfgs_options* opt,
+                               rtd_optimizer* out) {
+    return lbfgsCreate(hh, "rtd_optimizer_create_lbfgs", false, fields, n_fields, oo, opt, 0u, out);
+}
+
+int rtd_optimizer_create_lbfgs_ex(rtd_handle hh, const rtd_field* fields, uint32_t n_fields, rtd_objective oo, const rtd_lbfgs_options* opt,
+                                  uint32_t flags, rtd_optimizer* out) {
+    return lbfgsCreate(hh, "rtd_optimizer_create_lbfgs_ex", true, fields, n_fields, oo, opt, flags, out);
+}
+
 int rtd_optimizer_lbfgs_report(rtd_handle hh, rtd_optimizer pp, rtd_lbfgs_report* r) {
     auto* h = reinterpret_cast<rtd_handle_impl*>(hh);
     auto* p = reinterpret_cast<rtd_optimizer_impl*>(pp);
@@ -240,6 +315,19 @@ int rtd_optimizer_lbfgs_buffers(rtd_handle hh, rtd_optimizer pp, rtd_lbfgs_buffe
     b->ring = p->dLbVec; b->w_full = p->dLbVec + (2 * m + 3) * n; b->trial_dose = p->dLbTrialDose;
     b->gram = p->dLbGram; b->delta = reinterpret_cast<const double*>(p->dLbState.p);
     b->n = (uint32_t)p->n; b->memory = (uint32_t)m; b->n_chunks = (uint32_t)p->nCh; b->n_trials = 1 + p->lbOpt.max_halvings;
+    return RTD_OK;
+}
+
+int rtd_optimizer_lbfgs_line_buffers(rtd_handle hh, rtd_optimizer pp, rtd_lbfgs_line_buffers* b) {
+    auto* h = reinterpret_cast<rtd_handle_impl*>(hh);
+    auto* p = reinterpret_cast<rtd_optimizer_impl*>(pp);
+    if (!h) return RTD_ERR_INVALID_ARG;
+    if (!p || !b) return fail(h, RTD_ERR_INVALID_ARG, "rtd_optimizer_lbfgs_line_buffers: null pointer");
+    if (!p->lbfgs) return fail(h, RTD_ERR_INVALID_ARG, "rtd_optimizer_lbfgs_line_buffers: not an L-BFGS optimiser (rtd_optimizer_create_lbfgs, _create_lbfgs_ex)");
+    std::memset(b, 0, sizeof *b);
+    b->d0 = p->dDose; b->d1 = p->dLbTrialDose;
+    if (p->lbCoupled) { b->thresholds = p->dLbThr; b->eud = p->dLbEud; }
+    b->n_trials = 1 + p->lbOpt.max_halvings; b->n_terms = (uint32_t)p->obj->terms.size();
     return RTD_OK;
 }
 

@@ -63,6 +63,13 @@ struct rtd_optimizer_impl {
     DevBuf<float> dLbTrialDose, dLbVec;
     DevBuf<double> dLbGram, dLbPart, dLbGp, dLbLine;
     DevBuf<LbState> dLbState;
+    // ... whose objective has DVH or EUD terms (section 30; rtd_optimizer_create_lbfgs_ex): per trial of the line search the selection
+    // histograms [K][nEvalSel][3][kDvhBins], the thresholds [K][kObjMaxTerms], the chunk sums [K][nEudSel][nChMax] and {E, K, value}
+    // [K][kObjMaxTerms][3]. With `compact` set beside `lbfgs` the two products are the compact ones.
+    bool lbCoupled = false;
+    DevBuf<unsigned> dLbHist;
+    DevBuf<float> dLbThr;
+    DevBuf<double> dLbEudPart, dLbEud;
     // A compact optimiser (sections 28 and 29; rtd_optimizer_create_compact, _create_robust_compact and _create_voxelwise_compact in
     // rtd_dij_compact_host.hpp): a plain, robust or voxel-wise optimiser whose two products are rtd_field_dose_influence_apply_compact /
     // _apply_t_compact, or their launches over the scenario axis. matEpoch: per field of sfields, what its matrix was at creation.

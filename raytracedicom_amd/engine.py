@@ -177,6 +177,8 @@ def lib():
         L.rtd_optimizer_create_lbfgs.argtypes = [vp, vpp, C.c_uint32, vp, C.POINTER(abi.RtdLbfgsOptions), vpp]
         L.rtd_optimizer_lbfgs_report.argtypes = [vp, vp, C.POINTER(abi.RtdLbfgsReport)]
         L.rtd_optimizer_lbfgs_buffers.argtypes = [vp, vp, C.POINTER(abi.RtdLbfgsBuffers)]
+        L.rtd_optimizer_create_lbfgs_ex.argtypes = [vp, vpp, C.c_uint32, vp, C.POINTER(abi.RtdLbfgsOptions), C.c_uint32, vpp]
+        L.rtd_optimizer_lbfgs_line_buffers.argtypes = [vp, vp, C.POINTER(abi.RtdLbfgsLineBuffers)]
         L.rtd_default_dij_compact_options.argtypes = [C.POINTER(abi.RtdDijCompactOptions)]
         L.rtd_default_dij_compact_options.restype = None
         L.rtd_field_dose_influence_compact.argtypes = [vp, vp, C.POINTER(abi.RtdDijCompactOptions)]
@@ -861,7 +863,7 @@ class Optimizer:
     dose_influence() matrix). Destroy it before its fields, its objective and its engine."""
 
     def __init__(self, eng, fields, objective, options=None, scenario_fields=None, mode=None, probabilities=None, voxelwise=False, phase_warps=None,
-                 phase_weights=None, lbfgs=False, compact=False):
+                 phase_weights=None, lbfgs=False, compact=False, lbfgs_flags=None):
         """scenario_fields (a list of per-scenario field lists, scenario 0 the nominal one) makes it a robust optimiser
         (rtd_optimizer_create_robust) in mode abi.RTD_ROBUST_EXPECTED / _WORST_CASE, or with voxelwise=True the voxel-wise worst case
         (rtd_optimizer_create_voxelwise; mode and probabilities are then not used); `fields` is then ignored. With phase_warps (a list
@@ -869,7 +871,9 @@ class Optimizer:
         (rtd_optimizer_create_4d; phase_weights: one positive weight per phase, None for equal ones). With lbfgs=True it is the
         L-BFGS iteration with its line search on the device (rtd_optimizer_create_lbfgs; options: an abi.RtdLbfgsOptions or None). With
         compact=True it is the spectral iteration on the fields' compact matrices (rtd_optimizer_create_compact), and with
-        scenario_fields the robust or voxel-wise one on them (rtd_optimizer_create_robust_compact, _create_voxelwise_compact)."""
+        scenario_fields the robust or voxel-wise one on them (rtd_optimizer_create_robust_compact, _create_voxelwise_compact). With
+        lbfgs=True and lbfgs_flags (an int, abi.RTD_LBFGS_COMPACT or 0) it is rtd_optimizer_create_lbfgs_ex: L-BFGS on an objective
+        of any term kind, on the compact matrices with the flag."""
         self.eng = eng
         self.objective = objective
         self._h = C.c_void_p()
@@ -879,6 +883,9 @@ class Optimizer:
             self.fields = list(fields)
             self.scenario_fields = [self.fields]
             arr = (C.c_void_p * max(1, len(self.fields)))(*[f._h for f in self.fields])
+            if lbfgs and lbfgs_flags is not None:
+                eng._check(lib().rtd_optimizer_create_lbfgs_ex(eng._h, arr, len(self.fields), objective._h, po, int(lbfgs_flags), C.byref(self._h)))
+                return
             if lbfgs:
                 eng._check(lib().rtd_optimizer_create_lbfgs(eng._h, arr, len(self.fields), objective._h, po, C.byref(self._h)))
                 return
@@ -976,6 +983,14 @@ class Optimizer:
         inspection."""
         b = abi.RtdLbfgsBuffers()
         self.eng._check(lib().rtd_optimizer_lbfgs_buffers(self.eng._h, self._h, C.byref(b)))
+        return b
+
+    def lbfgs_line_buffers(self):
+        """rtd_optimizer_lbfgs_line_buffers: what the line search of an L-BFGS optimiser reads and leaves (abi.RtdLbfgsLineBuffers): the
+        device pointers of d0 and d1 and, with DVH or EUD terms, of the per-trial thresholds float[n_trials][RTD_OBJ_MAX_TERMS] and
+        {E, K, value} double[n_trials][RTD_OBJ_MAX_TERMS][3] (None without such terms)."""
+        b = abi.RtdLbfgsLineBuffers()
+        self.eng._check(lib().rtd_optimizer_lbfgs_line_buffers(self.eng._h, self._h, C.byref(b)))
         return b
 
     def set_let_objective(self, let_objective):
@@ -1270,6 +1285,12 @@ class Engine:
         objective must not have DVH or EUD terms); options: an abi.RtdLbfgsOptions (abi.default_lbfgs_options) or None. It also has
         .lbfgs_report()."""
         return Optimizer(self, fields, objective, options, lbfgs=True)
+
+    def create_lbfgs_optimizer_ex(self, fields, objective, options=None, compact=False):
+        """rtd_optimizer_create_lbfgs_ex: the L-BFGS Optimizer on an objective of any term kind (DVH and EUD terms are evaluated per trial
+        of the line search, on the float32-rounded trial volume); compact=True: its products read the fields' compact matrices
+        (Field.dose_influence_compact first; works after release_plain). It also has .lbfgs_line_buffers()."""
+        return Optimizer(self, fields, objective, options, lbfgs=True, lbfgs_flags=abi.RTD_LBFGS_COMPACT if compact else 0)
 
     def create_compact_optimizer(self, fields, objective, options=None):
         """rtd_optimizer_create_compact: the spectral optimiser of create_optimizer whose two products read the fields' compact
