@@ -1808,6 +1808,161 @@ int rtd_optimizer_create_lbfgs_ex(rtd_handle h, const rtd_field* fields, uint32_
 int rtd_optimizer_lbfgs_line_buffers(rtd_handle h, rtd_optimizer opt, rtd_lbfgs_line_buffers* b);
 
 /*
+ * ---- Hard dose constraints: an augmented Lagrangian resident on the device ----
+ *
+ * Additive to the blocks above (RTD_ABI_VERSION stays 3; no entry point, kernel or structure above changes). Everything above is a
+ * penalty with a weight. A constraint is a bound that holds at the solution: "every voxel of the cord at most 45 Gy". The method is
+ * the augmented Lagrangian around the resident spectral iteration: one multiplier per constrained voxel, a penalty rho that grows only
+ * while the violation does not shrink, and no host round trip.
+ *
+ * CONSTRAINTS. rtd_objective_add_constraint adds one to an objective: it refers to a ROI of rtd_objective_add_roi (which may carry no
+ * term), does not count towards RTD_OBJ_MAX_TERMS and lives in tables of its own. RTD_CON_MAX_DOSE: every voxel of the ROI at most
+ * dose_level; RTD_CON_MIN_DOSE: every voxel at least dose_level; RTD_CON_MAX_MEAN / RTD_CON_MIN_MEAN: the same for the ROI's mean
+ * dose. constraint_id (may be NULL) receives its number c, 0 .. RTD_CON_MAX_CONSTRAINTS - 1, in the order added.
+ * rtd_objective_eval, _eval_voxelwise, _dvh, _dose_at_volume and _eud IGNORE constraints: they answer as before.
+ * Every other creator (rtd_optimizer_create, _create_robust, _create_voxelwise, _create_4d, _create_lbfgs, _create_lbfgs_ex, the
+ * _compact ones, rtd_planset_create) refuses an objective that has a constraint with RTD_ERR_INVALID_ARG before any launch, and so
+ * does rtd_optimizer_set_let_objective for a LET objective that has one. An optimiser created BEFORE the constraint was added keeps
+ * running on the terms alone (an L-BFGS one refuses its run, as after any change of its objective).
+ *
+ * DEVICE TABLES, built synchronously on first use: the union of the constrained ROIs ascending (union_voxels); per union voxel the
+ * PER-VOXEL constraints (MAX_DOSE / MIN_DOSE) that hold it, in constraint order, as a CSR (entry_ptr[n_union + 1],
+ * entry_constraint[n_entries]). A per-voxel multiplier is one float per CSR entry: lambda[n_entries]. The mean constraints have no CSR
+ * entries: a union voxel carries a 16-bit mask of the mean constraints whose ROI holds it, and a mean constraint's multiplier is one
+ * double, mu[c] of an array double[RTD_CON_MAX_CONSTRAINTS] indexed by the constraint's number (the entries of per-voxel constraints
+ * are neither read nor written).
+ *
+ * THE ARITHMETIC. float64 throughout, no contraction, no atomics, sums by fixed trees. For constraint c on a ROI of N voxels with
+ * level L: s = +1 for a MAX kind, -1 for a MIN kind; invN = 1.0 / N (host); rho the penalty.
+ *   Per-voxel constraint, entry e at voxel v, lam = double(lambda[e]): h = s * (double(dose[v]) - L); u = lam + rho * h;
+ *   a = u > 0 ? u : 0, and a = h where h is a NaN (the value is then not finite and the optimiser's guard acts as it does today).
+ *     psi_c = (sum_e (a * a - lam * lam)) * (invN / (2 * rho)); the sum by rtd_objective_eval's tree over the union of the constrained
+ *     ROIs (one thread per union voxel, blocks of 256, wave butterfly, (w0 + w1) + (w2 + w3), block b to lane b mod 64, butterfly).
+ *     gc_e = s * (a * invN).
+ *   Mean constraint: m = (sum_v double(dose[v])) * invN over the ROI, the sum by rtd_objective_eud's chunk tree (chunks of 2048,
+ *   thread t adds the voxels t, t + 256, ... of its chunk in order, wave butterfly, (w0 + w1) + (w2 + w3); the chunk sums added the
+ *   same way). h = s * (m - L); u = mu[c] + rho * h; a as above. psi_c = (a * a - mu[c] * mu[c]) / (2 * rho); gc = s * (a * invN) at
+ *   every voxel of the ROI.
+ *   Combined gradient: g[v] = float32(double(g_terms[v]) + G), G the sum from +0.0 of the gc of the voxel's constraints in constraint
+ *   order (per-voxel and mean ones interleaved by number), g_terms[v] what rtd_objective_eval wrote (it writes every voxel of the
+ *   union of ALL ROIs, 0 where a voxel has no term, so every constrained voxel has been written).
+ *   Values: con_values[0] = the terms' values[0]; con_values[1 + c] = psi_c; values[0] = F = values[0] + psi_0 + psi_1 + ... in
+ *   constraint order; values[1 + t] stay the terms'.
+ *   Multiplier update with the same h: lambda[e] <- float32(min(max(u, 0), lambda_max)) where h is finite, otherwise lambda[e] stays;
+ *   mu[c] likewise in float64. Per constraint from the same pass: max_violation = max(0, h) over the entries (a NaN h is left out;
+ *   +inf counts), n_violating = the number of entries with h > tol (a mean constraint: 0 or 1).
+ *
+ * rtd_objective_eval_constrained   rtd_objective_eval followed by the launches above. dev_lambda float[n_entries], dev_mu
+ *                          double[RTD_CON_MAX_CONSTRAINTS], dev_values double[1 + terms], dev_con_values double[1 + n_constraints],
+ *                          dev_voxel_grad as rtd_objective_eval; all non-NULL. After the first call it only launches: no allocation,
+ *                          copy or synchronisation, so it can be captured into a graph. An evaluation uses the objective's scratch.
+ * rtd_objective_update_multipliers the update above, in place, and the violations to dev_out[n_constraints].
+ * rtd_objective_constraint_violations  the same pass without the update.
+ * rtd_objective_constraint_layout  the tables (device pointers owned by the objective, read-only, valid until the next ROI or
+ *                          constraint is added) and their sizes.
+ * RTD_ERR_INVALID_ARG: an objective without constraints (never silently forwarded) or, for eval_constrained, without terms; an unknown
+ * kind or ROI; a dose level that is not finite; a non-zero reserved word; more than RTD_CON_MAX_CONSTRAINTS; rho that is not positive
+ * and finite; lambda_max that is not positive; tol that is negative or a NaN.
+ *
+ * THE CONSTRAINED OPTIMISER. rtd_optimizer_create_constrained returns an ordinary rtd_optimizer on 1 .. RTD_OPT_MAX_FIELDS local
+ * fields with plain matrices; the objective needs at least one term and one constraint. rtd_optimizer_run, _result, _weights,
+ * _set_weights, _dose and _destroy work as on one of rtd_optimizer_create; rtd_optimizer_set_let_objective, _set_rbe, _scenario_values,
+ * _scenario_dose and _lbfgs_* refuse it with RTD_ERR_INVALID_ARG. Multipliers start at 0, rho at rho0. Iteration k, counted over all
+ * runs on the host (known at launch time; launches only, no decision on the host):
+ *   0. If k > 0 and k % inner_iterations == 0, an OUTER UPDATE runs in front of the evaluation:
+ *      (a) w = w_best if the current subproblem has a best iterate; (b) the forward product; (c) the means; (d) the multiplier update
+ *      with the current rho and lambda_max, measured with tol = feasibility_tol; (e) v = the maximum over the constraints of
+ *      max_violation. If this is not the first update and v > feasibility_tol and v > violation_shrink * v_prev then
+ *      rho = min(rho * rho_growth, rho_max). v_prev = v. {k, rho, v} is appended to the outer history (while it has room). The record's
+ *      f_best becomes +inf and its Barzilai-Borwein pair is dropped: the function has changed, and the best iterate and the pair of
+ *      the old one mean nothing for it.
+ *      On other iterations only the forward product runs.
+ *   1. rtd_objective_eval_constrained with the optimiser's lambda, mu and rho: values[0] is F.
+ *   2. The transposed product of the combined g.
+ *   3. The steps 4 to 7 of the spectral iteration AS THEY ARE: history, best iterate and guard act on F.
+ * The multiplier update is taken at the BEST iterate of each inner block, never at the current one: the spectral iteration is not
+ * monotone, an excursion would land on the update and the penalty would grow without bound.
+ * Consequences: w_best and f_best are those of the CURRENT subproblem. Run whole multiples of inner_iterations (the report carries
+ * iterations_since_update). rtd_optimizer_result's "start unusable" answer can also mean a subproblem whose first value was not
+ * finite. A captured run(n) replays the schedule it was captured with. An outer update costs one extra forward product.
+ * It notes its matrices and its objective at creation: rtd_optimizer_run refuses with RTD_ERR_NOT_READY, before its first launch,
+ * once a field's matrix has been computed again or a ROI, term or constraint has been added.
+ * rtd_optimizer_constraint_report  waits for the stream. f_objective is con_values[0] of the last evaluation; psi of the last
+ *                          evaluation; max_violation and n_violating per constraint of the last outer update. outer_history
+ *                          (may be NULL with capacity 0) receives min(capacity, outer_history_len) entries.
+ * rtd_optimizer_constraint_buffers the optimiser's own device arrays, read-only, no synchronisation.
+ * RTD_ERR_INVALID_ARG: what rtd_optimizer_create refuses; an objective without constraints; rho0 or rho_max not positive and finite or
+ * rho_max < rho0; rho_growth < 1 or not finite; violation_shrink outside (0, 1]; feasibility_tol negative or not finite; lambda_max
+ * not positive; inner_iterations 0; a non-zero reserved word.
+ *
+ * Out of scope: constraints behind L-BFGS (a monotone inner solver would suit the method better; it needs the constraint terms in the
+ * K-wide line kernels and is the natural follow-up); the robust, voxel-wise, 4D, plan-set, LET, RBE and compact-matrix optimisers; DVH
+ * and EUD constraints; upper bounds or minimum-MU rules on the weights; an on-device stopping rule; nuclear_corr, remote fields and
+ * the rtd_plan_* path.
+ */
+enum { RTD_CON_MAX_DOSE = 0, RTD_CON_MIN_DOSE = 1, RTD_CON_MAX_MEAN = 2, RTD_CON_MIN_MEAN = 3 };
+#define RTD_CON_MAX_CONSTRAINTS 16
+typedef struct rtd_dose_constraint {
+    int32_t kind;               /* RTD_CON_* */
+    int32_t roi;                /* an id of rtd_objective_add_roi */
+    double dose_level;
+    int32_t reserved[4];        /* must be 0 */
+} rtd_dose_constraint;          /* 32 bytes */
+typedef struct rtd_constraint_layout {
+    const int32_t* union_voxels;        /* [n_union], ascending */
+    const int32_t* entry_ptr;           /* [n_union + 1] */
+    const uint8_t* entry_constraint;    /* [n_entries] */
+    uint32_t n_union, n_entries, n_constraints, n_mean;
+    uint32_t reserved[4];
+} rtd_constraint_layout;        /* 56 bytes */
+typedef struct rtd_constraint_violation {
+    double max_violation;
+    uint32_t n_violating;
+    uint32_t reserved;
+} rtd_constraint_violation;     /* 16 bytes */
+typedef struct rtd_constrained_options {
+    double rho0, rho_growth, rho_max, violation_shrink, feasibility_tol, lambda_max;
+    uint32_t inner_iterations, outer_capacity;
+    int32_t reserved[4];        /* must be 0 */
+} rtd_constrained_options;      /* 72 bytes */
+typedef struct rtd_constraint_outer {
+    uint64_t iteration;         /* k of the outer update */
+    double rho;                 /* after the update's decision */
+    double max_violation;       /* v */
+} rtd_constraint_outer;         /* 24 bytes */
+typedef struct rtd_constraint_report {
+    double rho;
+    double f_objective;         /* the terms alone, of the last evaluation */
+    uint32_t outer_updates, rho_increases, iterations_since_update, n_constraints;
+    uint32_t outer_history_len; /* min(outer_updates, outer_capacity) */
+    uint32_t reserved[3];
+    double psi[RTD_CON_MAX_CONSTRAINTS];
+    double max_violation[RTD_CON_MAX_CONSTRAINTS];
+    uint32_t n_violating[RTD_CON_MAX_CONSTRAINTS];
+} rtd_constraint_report;        /* 368 bytes */
+typedef struct rtd_constraint_buffers {
+    const float* lambda;        /* [n_entries] */
+    const double* mu;           /* [RTD_CON_MAX_CONSTRAINTS] */
+    const double* rho;          /* one double */
+    const double* con_values;   /* [1 + n_constraints] */
+    const rtd_constraint_violation* violations;   /* [n_constraints], of the last outer update */
+    const rtd_constraint_outer* outer_history;    /* [outer_capacity] */
+    uint32_t n_entries, n_constraints, n_mean, outer_capacity;
+} rtd_constraint_buffers;       /* 64 bytes */
+int rtd_objective_add_constraint(rtd_handle h, rtd_objective obj, const rtd_dose_constraint* c, int32_t* constraint_id);
+int rtd_objective_constraint_layout(rtd_handle h, rtd_objective obj, rtd_constraint_layout* layout);
+int rtd_objective_eval_constrained(rtd_handle h, rtd_objective obj, const float* dev_dose, const float* dev_lambda, const double* dev_mu, double rho,
+                                   double* dev_values, double* dev_con_values, float* dev_voxel_grad);
+int rtd_objective_update_multipliers(rtd_handle h, rtd_objective obj, const float* dev_dose, double rho, double lambda_max, double tol, float* dev_lambda,
+                                     double* dev_mu, rtd_constraint_violation* dev_out);
+int rtd_objective_constraint_violations(rtd_handle h, rtd_objective obj, const float* dev_dose, double tol, rtd_constraint_violation* dev_out);
+void rtd_default_constrained_options(rtd_constrained_options* out);
+int rtd_optimizer_create_constrained(rtd_handle h, const rtd_field* fields, uint32_t n_fields, rtd_objective obj, const rtd_optimizer_options* o,
+                                     const rtd_constrained_options* c, rtd_optimizer* out);
+int rtd_optimizer_constraint_report(rtd_handle h, rtd_optimizer opt, rtd_constraint_report* r, rtd_constraint_outer* outer_history, uint32_t capacity);
+int rtd_optimizer_constraint_buffers(rtd_handle h, rtd_optimizer opt, rtd_constraint_buffers* b);
+
+/*
  * ---- Compact dose-influence matrix: fp16 values, 16-bit indices, products of its own ----
  *
  * Additive to the blocks above (RTD_ABI_VERSION stays 3; no entry point, kernel or structure above changes). The plain form of a

@@ -319,6 +319,72 @@ def default_lbfgs_options():
     return o
 
 
+RTD_CON_MAX_DOSE, RTD_CON_MIN_DOSE, RTD_CON_MAX_MEAN, RTD_CON_MIN_MEAN = 0, 1, 2, 3
+RTD_CON_MAX_CONSTRAINTS = 16
+
+
+class RtdDoseConstraint(C.Structure):
+    """rtd_dose_constraint: a hard bound on every voxel of a ROI (RTD_CON_MAX_DOSE / _MIN_DOSE) or on its mean dose (RTD_CON_MAX_MEAN /
+    _MIN_MEAN) (32 bytes)."""
+    _fields_ = [("kind", C.c_int32), ("roi", C.c_int32), ("dose_level", C.c_double), ("reserved", C.c_int32 * 4)]
+
+
+class RtdConstraintLayout(C.Structure):
+    """rtd_constraint_layout: the device tables of an objective's constraints: the union of the constrained ROIs and the CSR of the
+    per-voxel constraints, one float multiplier per entry (56 bytes)."""
+    _fields_ = [("union_voxels", C.c_void_p), ("entry_ptr", C.c_void_p), ("entry_constraint", C.c_void_p),
+                ("n_union", C.c_uint32), ("n_entries", C.c_uint32), ("n_constraints", C.c_uint32), ("n_mean", C.c_uint32),
+                ("reserved", C.c_uint32 * 4)]
+
+
+class RtdConstraintViolation(C.Structure):
+    """rtd_constraint_violation: max(0, h) over a constraint's entries and the number of entries with h > tol (16 bytes)."""
+    _fields_ = [("max_violation", C.c_double), ("n_violating", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class RtdConstrainedOptions(C.Structure):
+    """rtd_constrained_options: the penalty's start, growth and cap, the shrink the violation must show to keep the penalty, the
+    feasibility tolerance, the multiplier cap, the inner block length and the outer history's capacity (72 bytes)."""
+    _fields_ = [("rho0", C.c_double), ("rho_growth", C.c_double), ("rho_max", C.c_double), ("violation_shrink", C.c_double),
+                ("feasibility_tol", C.c_double), ("lambda_max", C.c_double), ("inner_iterations", C.c_uint32),
+                ("outer_capacity", C.c_uint32), ("reserved", C.c_int32 * 4)]
+
+
+class RtdConstraintOuter(C.Structure):
+    """rtd_constraint_outer: one outer update: its iteration, the penalty after its decision, the largest violation (24 bytes)."""
+    _fields_ = [("iteration", C.c_uint64), ("rho", C.c_double), ("max_violation", C.c_double)]
+
+
+class RtdConstraintReport(C.Structure):
+    """rtd_constraint_report: what the outer updates of a constrained optimiser did so far (368 bytes)."""
+    _fields_ = [("rho", C.c_double), ("f_objective", C.c_double), ("outer_updates", C.c_uint32), ("rho_increases", C.c_uint32),
+                ("iterations_since_update", C.c_uint32), ("n_constraints", C.c_uint32), ("outer_history_len", C.c_uint32),
+                ("reserved", C.c_uint32 * 3), ("psi", C.c_double * 16), ("max_violation", C.c_double * 16),
+                ("n_violating", C.c_uint32 * 16)]
+
+    def as_dict(self):
+        d = {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
+        for k in ("psi", "max_violation", "n_violating"):
+            d[k] = list(d[k])[:self.n_constraints]
+        return d
+
+
+class RtdConstraintBuffers(C.Structure):
+    """rtd_constraint_buffers: the device arrays of a constrained optimiser, for inspection (64 bytes)."""
+    _fields_ = [("lambda_", C.c_void_p), ("mu", C.c_void_p), ("rho", C.c_void_p), ("con_values", C.c_void_p), ("violations", C.c_void_p),
+                ("outer_history", C.c_void_p), ("n_entries", C.c_uint32), ("n_constraints", C.c_uint32), ("n_mean", C.c_uint32),
+                ("outer_capacity", C.c_uint32)]
+
+
+def default_constrained_options():
+    """rtd_default_constrained_options: rho0 1, growth 4, rho_max 1e8, shrink 0.5, tolerance 0, lambda_max 1e20, 20 inner iterations,
+    256 outer history entries."""
+    o = RtdConstrainedOptions()
+    o.rho0, o.rho_growth, o.rho_max, o.violation_shrink, o.feasibility_tol, o.lambda_max = 1.0, 4.0, 1e8, 0.5, 0.0, 1e20
+    o.inner_iterations, o.outer_capacity = 20, 256
+    return o
+
+
 class RtdDijCompactOptions(C.Structure):
     """rtd_dij_compact_options: release_plain (1: free the plain form's bulk once the compact form stands) (32 bytes)."""
     _fields_ = [("release_plain", C.c_uint32), ("reserved", C.c_int32 * 7)]

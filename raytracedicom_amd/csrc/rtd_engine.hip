@@ -43,6 +43,7 @@
 #include "rtd_optimize.hpp"
 #include "rtd_dvh.hpp"
 #include "rtd_eud.hpp"
+#include "rtd_constrain.hpp"
 #include "rtd_robust.hpp"
 #include "rtd_robust_compact.hpp"
 #include "rtd_voxelwise.hpp"
@@ -1464,6 +1465,7 @@ int rtd_compute(rtd_handle hh, const rtd_beam* beams, int n_beams, float* dose_i
 #include "rtd_dij_host.hpp"
 #include "rtd_objective_host.hpp"
 #include "rtd_optimizer_host.hpp"
+#include "rtd_constrain_host.hpp"
 #include "rtd_roi_host.hpp"
 #include "rtd_roi_ops_host.hpp"
 #include "rtd_target_host.hpp"

@@ -159,6 +159,8 @@ int rtd_optimizer_set_let_objective(rtd_handle hh, rtd_optimizer pp, rtd_objecti
     if (p->rbe) return fail(h, RTD_ERR_INVALID_ARG, "rtd_optimizer_set_let_objective: the optimiser has an RBE model (one or the other)");
     if (p->robust) return fail(h, RTD_ERR_INVALID_ARG, "rtd_optimizer_set_let_objective: not available for a robust or voxel-wise optimiser");
     if (p->lbfgs) return fail(h, RTD_ERR_INVALID_ARG, "rtd_optimizer_set_let_objective: not available for an L-BFGS optimiser");
+    if (p->constrained) return fail(h, RTD_ERR_INVALID_ARG, "rtd_optimizer_set_let_objective: not available for a constrained optimiser");
+    if (!o->cons.empty()) return fail(h, RTD_ERR_INVALID_ARG, "rtd_optimizer_set_let_objective: the LET objective has hard constraints");
     if (p->compact) return fail(h, RTD_ERR_INVALID_ARG, "rtd_optimizer_set_let_objective: not available for a compact optimiser (no compact LET values)");
     for (int a = 0; a < 3; ++a)
         if (o->dims[a] != p->obj->dims[a]) return fail(h, RTD_ERR_INVALID_ARG, "rtd_optimizer_set_let_objective: the LET objective must be on the optimiser's dose grid");

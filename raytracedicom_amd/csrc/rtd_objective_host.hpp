@@ -31,6 +31,14 @@ struct rtd_objective_impl {
     struct Eud { DevBuf<double> dPartial, dTerm; } eud;
     EudSel eudSel{};              // the selections of eval: one per EUD term, in term order, slot = the term
     int nEudSel = 0;
+    // Hard constraints (section 31; rtd_constrain_host.hpp builds and uses all of it): tables of their own, tab and built are not
+    // disturbed. The union of the constrained ROIs, the CSR of the per-voxel constraints, the mask of the mean constraints per union
+    // voxel, and the scratch of the kernels of rtd_constrain.hpp. The mean constraints read the DVH's ROI index lists.
+    std::vector<rtd_dose_constraint> cons;
+    bool conBuilt = false;
+    int nCU = 0, nCBlocks = 0, nCEntries = 0, nCChMax = 1;   // union voxels, blocks of k_con_eval, CSR entries, chunks of the largest mean-constrained ROI
+    ConTab conTab{};
+    struct Con { DevBuf<int> dUv, dPtr; DevBuf<unsigned char> dIdx; DevBuf<unsigned short> dMask; DevBuf<double> dPartial, dMeanPart, dMean, dMaxPart; DevBuf<unsigned> dCntPart; } con;
     bool hasDvhTerms() const { for (double v : vfrac) if (v > 0.0) return true; return false; }
     bool hasEudTerms() const { for (double a : expo) if (a != 0.0) return true; return false; }
 };
@@ -256,6 +264,7 @@ int rtd_objective_add_roi(rtd_handle hh, rtd_objective oo, const int32_t* voxels
     o->built = false; ++o->epoch;
     o->dvhBuilt = false;
     o->eudBuilt = false;
+    o->conBuilt = false;
     *roi_id = (int32_t)o->rois.size() - 1;
     return RTD_OK;
 }

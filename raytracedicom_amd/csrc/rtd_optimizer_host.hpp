@@ -74,6 +74,18 @@ struct rtd_optimizer_impl {
     // rtd_dij_compact_host.hpp): a plain, robust or voxel-wise optimiser whose two products are rtd_field_dose_influence_apply_compact /
     // _apply_t_compact, or their launches over the scenario axis. matEpoch: per field of sfields, what its matrix was at creation.
     bool compact = false;
+    // A constrained optimiser (section 31; rtd_optimizer_create_constrained in rtd_constrain_host.hpp allocates all of it): a plain
+    // optimiser whose iteration is constrainedRun. The multipliers (float per CSR entry, double per constraint for the mean ones), the
+    // penalty and what the outer updates decided, {terms' value, psi_c}, the last update's violations and the outer history.
+    // matEpoch / matChunks as above; conObjEpoch: the objective as it was at creation.
+    bool constrained = false;
+    rtd_constrained_options conOpt{};
+    unsigned conObjEpoch = 0;
+    DevBuf<float> dConLambda;
+    DevBuf<double> dConMu, dConValues;
+    DevBuf<ConState> dConState;
+    DevBuf<ConViolation> dConViol;
+    DevBuf<ConOuter> dConOuter;
     rtd_field_impl* const* row(int s) const { return sfields.data() + (size_t)s * fields.size(); }
     rtd_field_impl* sf(int s, size_t i) const { return row(s)[i]; }
     float* w() const { return dVec; }
@@ -121,6 +133,8 @@ int fourdSplit(rtd_handle hh, rtd_optimizer_impl* p);
 // Section 27 (rtd_lbfgs_host.hpp, included later): the iteration of an L-BFGS optimiser, and what rtd_optimizer_set_weights means to it.
 int lbfgsRun(rtd_handle hh, rtd_optimizer_impl* p, uint32_t n_iterations);
 int lbfgsWeightsSet(rtd_handle_impl* h, rtd_optimizer_impl* p);
+// Section 31 (rtd_constrain_host.hpp, included later): the iteration of a constrained optimiser.
+int constrainedRun(rtd_handle hh, rtd_optimizer_impl* p, uint32_t n_iterations);
 // Section 28 (rtd_dij_compact_host.hpp, included later): the row pointers the compact companion side reads.
 const long long* compactRowPtr(const rtd_field_impl* f);
 
@@ -273,9 +287,11 @@ int optCheckField(rtd_handle_impl* h, const std::string& who, const rtd_field_im
 // 3. Every one of the n_all fields (rows of n_fields) has a matrix; their companions and the objective are built; *offset gets the
 // spot-offset table of the first row.
 // compact: the fields' compact forms are asked for instead of their plain ones (rtd_optimizer_create_compact).
+// constrained: the caller is rtd_optimizer_create_constrained; every other creator refuses an objective with hard constraints here.
 int optPrepare(rtd_handle hh, const std::string& who, const rtd_field* fields, uint32_t n_fields, uint32_t n_all, rtd_objective_impl* o, std::vector<int>* offset,
-               bool compact = false) {
+               bool compact = false, bool constrained = false) {
     auto* h = reinterpret_cast<rtd_handle_impl*>(hh);
+    if (!constrained && !o->cons.empty()) return fail(h, RTD_ERR_INVALID_ARG, who + ": the objective has hard constraints (rtd_optimizer_create_constrained)");
     for (uint32_t i = 0; i < n_all; ++i) {
         const FieldMatrix& m = reinterpret_cast<rtd_field_impl*>(fields[i])->matrix;
         if (!m.hasMatrix()) return fail(h, RTD_ERR_NOT_READY, who + ": a field has no dose-influence matrix (call rtd_field_dose_influence first)");
@@ -472,6 +488,7 @@ int rtd_optimizer_scenario_values(rtd_handle hh, rtd_optimizer pp, double* value
     if (!h) return RTD_ERR_INVALID_ARG;
     if (!p || !values) return fail(h, RTD_ERR_INVALID_ARG, "rtd_optimizer_scenario_values: null pointer");
     if (p->lbfgs) return fail(h, RTD_ERR_INVALID_ARG, "rtd_optimizer_scenario_values: not available for an L-BFGS optimiser");
+    if (p->constrained) return fail(h, RTD_ERR_INVALID_ARG, "rtd_optimizer_scenario_values: not available for a constrained optimiser");
     RTD_HIP(h, hipSetDevice(h->device));
     if (!p->robust || p->fourd) {             // (a 4D optimiser answers as a composite: f_p = f_last, lambda 1.0, worst 0)
         OptState st{};
@@ -495,6 +512,7 @@ int rtd_optimizer_scenario_dose(rtd_handle hh, rtd_optimizer pp, uint32_t scenar
     if (!h) return RTD_ERR_INVALID_ARG;
     if (!p || !dev_dose) return fail(h, RTD_ERR_INVALID_ARG, "rtd_optimizer_scenario_dose: null pointer");
     if (p->lbfgs) return fail(h, RTD_ERR_INVALID_ARG, "rtd_optimizer_scenario_dose: not available for an L-BFGS optimiser");
+    if (p->constrained) return fail(h, RTD_ERR_INVALID_ARG, "rtd_optimizer_scenario_dose: not available for a constrained optimiser");
     if (scenario >= (uint32_t)p->nScen) return fail(h, RTD_ERR_INVALID_ARG, "rtd_optimizer_scenario_dose: scenario index out of range");
     *dev_dose = p->doseS[scenario];
     return RTD_OK;
@@ -521,6 +539,7 @@ int rtd_optimizer_run(rtd_handle hh, rtd_optimizer pp, uint32_t n_iterations) {
     if (!p) return fail(h, RTD_ERR_INVALID_ARG, "rtd_optimizer_run: null pointer");
     if (p->obj->terms.empty()) return fail(h, RTD_ERR_INVALID_ARG, "rtd_optimizer_run: the objective has no terms");
     if (p->lbfgs) return lbfgsRun(hh, p, n_iterations);
+    if (p->constrained) return constrainedRun(hh, p, n_iterations);
     if (p->letObj || p->rbe)                                          // (in front of the first launch: a refused run launches nothing)
         for (const rtd_field_impl* f : p->fields)
             if (!letReady(h, f))

@@ -228,6 +228,7 @@ int rtd_optimizer_set_rbe(rtd_handle hh, rtd_optimizer pp, rtd_rbe rr) {
     }
     if (p->robust) return fail(h, RTD_ERR_INVALID_ARG, "rtd_optimizer_set_rbe: not available for a robust or voxel-wise optimiser");
     if (p->lbfgs) return fail(h, RTD_ERR_INVALID_ARG, "rtd_optimizer_set_rbe: not available for an L-BFGS optimiser");
+    if (p->constrained) return fail(h, RTD_ERR_INVALID_ARG, "rtd_optimizer_set_rbe: not available for a constrained optimiser");
     if (p->compact) return fail(h, RTD_ERR_INVALID_ARG, "rtd_optimizer_set_rbe: not available for a compact optimiser (no compact LET values)");
     if (p->letObj) return fail(h, RTD_ERR_INVALID_ARG, "rtd_optimizer_set_rbe: the optimiser has a LET objective (one or the other)");
     for (int a = 0; a < 3; ++a)

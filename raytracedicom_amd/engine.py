@@ -179,6 +179,16 @@ def lib():
         L.rtd_optimizer_lbfgs_buffers.argtypes = [vp, vp, C.POINTER(abi.RtdLbfgsBuffers)]
         L.rtd_optimizer_create_lbfgs_ex.argtypes = [vp, vpp, C.c_uint32, vp, C.POINTER(abi.RtdLbfgsOptions), C.c_uint32, vpp]
         L.rtd_optimizer_lbfgs_line_buffers.argtypes = [vp, vp, C.POINTER(abi.RtdLbfgsLineBuffers)]
+        L.rtd_objective_add_constraint.argtypes = [vp, vp, C.POINTER(abi.RtdDoseConstraint), C.POINTER(C.c_int32)]
+        L.rtd_objective_constraint_layout.argtypes = [vp, vp, C.POINTER(abi.RtdConstraintLayout)]
+        L.rtd_objective_eval_constrained.argtypes = [vp, vp, vp, vp, vp, C.c_double, vp, vp, vp]
+        L.rtd_objective_update_multipliers.argtypes = [vp, vp, vp, C.c_double, C.c_double, C.c_double, vp, vp, vp]
+        L.rtd_objective_constraint_violations.argtypes = [vp, vp, vp, C.c_double, vp]
+        L.rtd_default_constrained_options.argtypes = [C.POINTER(abi.RtdConstrainedOptions)]
+        L.rtd_default_constrained_options.restype = None
+        L.rtd_optimizer_create_constrained.argtypes = [vp, vpp, C.c_uint32, vp, C.POINTER(abi.RtdOptimizerOptions), C.POINTER(abi.RtdConstrainedOptions), vpp]
+        L.rtd_optimizer_constraint_report.argtypes = [vp, vp, C.POINTER(abi.RtdConstraintReport), C.POINTER(abi.RtdConstraintOuter), C.c_uint32]
+        L.rtd_optimizer_constraint_buffers.argtypes = [vp, vp, C.POINTER(abi.RtdConstraintBuffers)]
         L.rtd_default_dij_compact_options.argtypes = [C.POINTER(abi.RtdDijCompactOptions)]
         L.rtd_default_dij_compact_options.restype = None
         L.rtd_field_dose_influence_compact.argtypes = [vp, vp, C.POINTER(abi.RtdDijCompactOptions)]
@@ -534,6 +544,7 @@ class Objective:
         self.dims = tuple(int(d) for d in dose_dims)
         self.n_terms = 0
         self.n_rois = 0
+        self.n_constraints = 0
         eng._check(lib().rtd_objective_create(eng._h, abi.uint3(self.dims), C.byref(self._h)))
 
     def add_roi(self, mask_or_indices):
@@ -662,6 +673,75 @@ class Objective:
             if own:
                 self.eng.device_free(buf)
         return None
+
+    def add_constraint(self, kind, roi, level):
+        """rtd_objective_add_constraint: a hard bound, abi.RTD_CON_MAX_DOSE / _MIN_DOSE on every voxel of the ROI or abi.RTD_CON_MAX_MEAN /
+        _MIN_MEAN on its mean dose -> the constraint's number. eval() and the other calls above ignore constraints; only
+        Engine.create_constrained_optimizer accepts an objective that has one."""
+        c = abi.RtdDoseConstraint(int(kind), int(roi), float(level))
+        cid = C.c_int32(-1)
+        self.eng._check(lib().rtd_objective_add_constraint(self.eng._h, self._h, C.byref(c), C.byref(cid)))
+        self.n_constraints = getattr(self, "n_constraints", 0) + 1
+        return int(cid.value)
+
+    def constraint_layout(self):
+        """rtd_objective_constraint_layout: builds the constraint tables where needed; an abi.RtdConstraintLayout (device pointers of the
+        union of the constrained ROIs and the CSR of the per-voxel constraints; n_entries floats of multipliers)."""
+        lay = abi.RtdConstraintLayout()
+        self.eng._check(lib().rtd_objective_constraint_layout(self.eng._h, self._h, C.byref(lay)))
+        return lay
+
+    def eval_constrained(self, dev_dose, dev_lambda, dev_mu, rho, dev_g, dev_values=None, dev_con_values=None):
+        """rtd_objective_eval_constrained: the augmented Lagrangian F of the dose, the multipliers dev_lambda (float32[n_entries]) and
+        dev_mu (float64[abi.RTD_CON_MAX_CONSTRAINTS]) and the penalty rho; dev_g receives the combined voxel gradient. With dev_values
+        (float64[1 + n_terms]) and dev_con_values (float64[1 + n_constraints]), both device pointers, asynchronous, returns None;
+        without, returns (values, con_values): values[0] = F, con_values[0] the terms alone, con_values[1 + c] = psi_c."""
+        own = dev_values is None or dev_con_values is None
+        nv = 8 * (1 + abi.RTD_OBJ_MAX_TERMS)
+        buf = self.eng.device_alloc(nv + 8 * (1 + abi.RTD_CON_MAX_CONSTRAINTS)) if own else None
+        dv, dc = (buf, buf + nv) if own else (dev_values, dev_con_values)
+        try:
+            self.eng._check(lib().rtd_objective_eval_constrained(self.eng._h, self._h, C.c_void_p(int(dev_dose)), C.c_void_p(int(dev_lambda)), C.c_void_p(int(dev_mu)),
+                                                                 float(rho), C.c_void_p(int(dv)), C.c_void_p(int(dc)), C.c_void_p(int(dev_g))))
+            if own:
+                vals = np.empty(1 + self.n_terms, dtype=np.float64)
+                cons = np.empty(1 + getattr(self, "n_constraints", 0), dtype=np.float64)
+                self.eng.to_host(vals, dv)
+                self.eng.to_host(cons, dc)
+                return vals, cons
+        finally:
+            if own:
+                self.eng.device_free(buf)
+        return None
+
+    def _violations(self, call, dev_out):
+        own = dev_out is None
+        do = self.eng.device_alloc(16 * abi.RTD_CON_MAX_CONSTRAINTS) if own else dev_out
+        try:
+            self.eng._check(call(C.c_void_p(int(do))))
+            if own:
+                out = (abi.RtdConstraintViolation * abi.RTD_CON_MAX_CONSTRAINTS)()
+                raw = np.empty(16 * abi.RTD_CON_MAX_CONSTRAINTS, dtype=np.uint8)
+                self.eng.to_host(raw, do)
+                C.memmove(out, raw.ctypes.data, raw.nbytes)
+                n = getattr(self, "n_constraints", 0)
+                return np.array([out[c].max_violation for c in range(n)], dtype=np.float64), np.array([out[c].n_violating for c in range(n)], dtype=np.uint32)
+        finally:
+            if own:
+                self.eng.device_free(do)
+        return None
+
+    def update_multipliers(self, dev_dose, rho, dev_lambda, dev_mu, lambda_max=1e20, tol=0.0, dev_out=None):
+        """rtd_objective_update_multipliers: lambda <- min(max(lambda + rho h, 0), lambda_max) in place (mu likewise), and per
+        constraint the largest violation and the number of entries with h > tol. With dev_out (device pointer of
+        abi.RtdConstraintViolation[n_constraints]) asynchronous, returns None; without, returns (max_violation float64[n_constraints],
+        n_violating uint32[n_constraints])."""
+        return self._violations(lambda do: lib().rtd_objective_update_multipliers(self.eng._h, self._h, C.c_void_p(int(dev_dose)), float(rho), float(lambda_max), float(tol),
+                                                                                 C.c_void_p(int(dev_lambda)), C.c_void_p(int(dev_mu)), do), dev_out)
+
+    def constraint_violations(self, dev_dose, tol=0.0, dev_out=None):
+        """rtd_objective_constraint_violations: what update_multipliers measures, without the update."""
+        return self._violations(lambda do: lib().rtd_objective_constraint_violations(self.eng._h, self._h, C.c_void_p(int(dev_dose)), float(tol), do), dev_out)
 
     def destroy(self):
         if self._h:
@@ -863,7 +943,7 @@ class Optimizer:
     dose_influence() matrix). Destroy it before its fields, its objective and its engine."""
 
     def __init__(self, eng, fields, objective, options=None, scenario_fields=None, mode=None, probabilities=None, voxelwise=False, phase_warps=None,
-                 phase_weights=None, lbfgs=False, compact=False, lbfgs_flags=None):
+                 phase_weights=None, lbfgs=False, compact=False, lbfgs_flags=None, constrained=None):
         """scenario_fields (a list of per-scenario field lists, scenario 0 the nominal one) makes it a robust optimiser
         (rtd_optimizer_create_robust) in mode abi.RTD_ROBUST_EXPECTED / _WORST_CASE, or with voxelwise=True the voxel-wise worst case
         (rtd_optimizer_create_voxelwise; mode and probabilities are then not used); `fields` is then ignored. With phase_warps (a list
@@ -873,7 +953,8 @@ class Optimizer:
         compact=True it is the spectral iteration on the fields' compact matrices (rtd_optimizer_create_compact), and with
         scenario_fields the robust or voxel-wise one on them (rtd_optimizer_create_robust_compact, _create_voxelwise_compact). With
         lbfgs=True and lbfgs_flags (an int, abi.RTD_LBFGS_COMPACT or 0) it is rtd_optimizer_create_lbfgs_ex: L-BFGS on an objective
-        of any term kind, on the compact matrices with the flag."""
+        of any term kind, on the compact matrices with the flag. With constrained (an abi.RtdConstrainedOptions, or True for the
+        defaults) it is the augmented Lagrangian of rtd_optimizer_create_constrained on an objective that has hard constraints."""
         self.eng = eng
         self.objective = objective
         self._h = C.c_void_p()
@@ -883,6 +964,10 @@ class Optimizer:
             self.fields = list(fields)
             self.scenario_fields = [self.fields]
             arr = (C.c_void_p * max(1, len(self.fields)))(*[f._h for f in self.fields])
+            if constrained is not None and constrained is not False:
+                pc = C.byref(constrained) if isinstance(constrained, abi.RtdConstrainedOptions) else None
+                eng._check(lib().rtd_optimizer_create_constrained(eng._h, arr, len(self.fields), objective._h, po, pc, C.byref(self._h)))
+                return
             if lbfgs and lbfgs_flags is not None:
                 eng._check(lib().rtd_optimizer_create_lbfgs_ex(eng._h, arr, len(self.fields), objective._h, po, int(lbfgs_flags), C.byref(self._h)))
                 return
@@ -991,6 +1076,24 @@ class Optimizer:
         {E, K, value} double[n_trials][RTD_OBJ_MAX_TERMS][3] (None without such terms)."""
         b = abi.RtdLbfgsLineBuffers()
         self.eng._check(lib().rtd_optimizer_lbfgs_line_buffers(self.eng._h, self._h, C.byref(b)))
+        return b
+
+    def constraint_report(self):
+        """rtd_optimizer_constraint_report: waits; (report dict, outer history as a list of (iteration, rho, max_violation)). Only on an
+        optimiser from Engine.create_constrained_optimizer (RtdError INVALID_ARG otherwise)."""
+        r = abi.RtdConstraintReport()
+        self.eng._check(lib().rtd_optimizer_constraint_report(self.eng._h, self._h, C.byref(r), None, 0))
+        n = int(r.outer_history_len)
+        hist = (abi.RtdConstraintOuter * max(1, n))()
+        if n:
+            self.eng._check(lib().rtd_optimizer_constraint_report(self.eng._h, self._h, C.byref(r), hist, n))
+        return r.as_dict(), [(int(hist[i].iteration), float(hist[i].rho), float(hist[i].max_violation)) for i in range(n)]
+
+    def constraint_buffers(self):
+        """rtd_optimizer_constraint_buffers: the device pointers and sizes of a constrained optimiser's own arrays
+        (abi.RtdConstraintBuffers; the multipliers are .lambda_ and .mu), for inspection."""
+        b = abi.RtdConstraintBuffers()
+        self.eng._check(lib().rtd_optimizer_constraint_buffers(self.eng._h, self._h, C.byref(b)))
         return b
 
     def set_let_objective(self, let_objective):
@@ -1291,6 +1394,12 @@ class Engine:
         of the line search, on the float32-rounded trial volume); compact=True: its products read the fields' compact matrices
         (Field.dose_influence_compact first; works after release_plain). It also has .lbfgs_line_buffers()."""
         return Optimizer(self, fields, objective, options, lbfgs=True, lbfgs_flags=abi.RTD_LBFGS_COMPACT if compact else 0)
+
+    def create_constrained_optimizer(self, fields, objective, options=None, constrained=None):
+        """rtd_optimizer_create_constrained: an Optimizer whose iteration is the augmented Lagrangian around the spectral one, on an
+        objective with at least one term and one constraint (Objective.add_constraint); constrained: an abi.RtdConstrainedOptions
+        (abi.default_constrained_options) or None. It also has .constraint_report() and .constraint_buffers()."""
+        return Optimizer(self, fields, objective, options, constrained=constrained if constrained is not None else True)
 
     def create_compact_optimizer(self, fields, objective, options=None):
         """rtd_optimizer_create_compact: the spectral optimiser of create_optimizer whose two products read the fields' compact
