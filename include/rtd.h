@@ -1963,6 +1963,78 @@ int rtd_optimizer_constraint_report(rtd_handle h, rtd_optimizer opt, rtd_constra
 int rtd_optimizer_constraint_buffers(rtd_handle h, rtd_optimizer opt, rtd_constraint_buffers* b);
 
 /*
+ * ---- Constrained L-BFGS: hard dose constraints behind the line search ----
+ *
+ * Additive to the blocks above (RTD_ABI_VERSION stays 3; no entry point, kernel or structure above changes).
+ * The follow-up the block above names now exists: the augmented Lagrangian of that block around the L-BFGS iteration of "L-BFGS with
+ * a line search on the device" instead of the spectral one. rtd_optimizer_create_constrained keeps its update at the best iterate. Here
+ * the outer update is taken at the CURRENT iterate, because the inner solver is monotone: inside a block the L-BFGS iteration accepts
+ * only trials with F_k <= f + c1 a gp and gp < 0, so the current iterate is the block's best. No weights are restored and no extra
+ * forward product runs.
+ *
+ * rtd_optimizer_create_constrained_lbfgs returns an ordinary rtd_optimizer on 1 .. RTD_OPT_MAX_FIELDS local fields. flags is 0 or
+ * RTD_LBFGS_COMPACT (the two products are then the compact ones, also after release_plain, as for rtd_optimizer_create_lbfgs_ex). The
+ * objective needs at least one term, of any kind (DVH and EUD terms included), and at least one constraint. o and c may be NULL (the
+ * defaults of rtd_default_lbfgs_options and rtd_default_constrained_options). It refuses what rtd_optimizer_create_lbfgs_ex and
+ * rtd_optimizer_create_constrained refuse: the option ranges of both, a non-zero reserved word, an objective without terms or without
+ * constraints, unknown bits in flags, remote fields (RTD_ERR_INVALID_ARG), a field without the matrix form asked for
+ * (RTD_ERR_NOT_READY). A failed allocation (RTD_ERR_OUT_OF_MEMORY) keeps nothing and leaves every object usable.
+ * rtd_optimizer_run, _result, _weights, _dose, _set_weights, _lbfgs_report, _lbfgs_buffers, _lbfgs_line_buffers, _constraint_report
+ * (iterations_since_update by the same rule) and _constraint_buffers work on it as on their own kinds; _scenario_values,
+ * _scenario_dose, _set_let_objective and _set_rbe refuse it, and so do plan sets. Every OTHER creator keeps refusing an objective that
+ * has a constraint.
+ *
+ * THE ITERATION k, counted over all runs on the host (launches only, one chain, no decision on the host, so a run can be captured
+ * into a graph; a captured run(n) replays the schedule it was captured with). F = f + sum_c psi_c is the function
+ * rtd_objective_eval_constrained evaluates with the optimiser's lambda, mu and rho.
+ *   0. If k > 0 and k % inner_iterations == 0, an OUTER UPDATE runs on the tracked dose of the current w (after the forward product
+ *      of a stale tracked dose, as in the L-BFGS iteration): the means, the multiplier update with the current rho and lambda_max,
+ *      measured with tol = feasibility_tol, and the decision (e) of the block above with its penalty rule and its outer history.
+ *      f_best becomes +inf, so the evaluation that follows makes the current w the new subproblem's best iterate. Then the L-BFGS
+ *      memory is dropped as after rtd_optimizer_set_weights (a pair w - w_prev, grad - grad_prev would mix two functions, and the ring
+ *      describes the old one): ring head, stall factor and counters stay.
+ *   1. rtd_objective_eval_constrained on the tracked dose: values[0] = F, the voxel gradient carries the constraints' share; then the
+ *      transposed products, plain or compact.
+ *   2. Steps 2 to 6 of the L-BFGS iteration unchanged, on F and its gradient.
+ *   3. THE LINE SEARCH. Every trial k < K = 1 + max_halvings is evaluated on the float32 volume
+ *      r_k[v] = k == 0 ? d1[v] : float32(double(d0[v]) + 2^-k * (double(d1[v]) - double(d0[v]))), whether or not the objective has DVH
+ *      or EUD terms: the terms as in "L-BFGS with DVH and EUD terms", the constraints with the arithmetic and the trees of the block
+ *      above (psi_{c,k} of a per-voxel constraint by rtd_objective_eval's tree over the union of the constrained ROIs, the mean
+ *      m_{c,k} by the chunk tree). F_k = the terms from +0.0 in term order, then + psi_{0,k} + psi_{1,k} + ... in constraint order:
+ *      F_k has the bits of values[0] of rtd_objective_eval_constrained(r_k). Then the decision of the L-BFGS iteration unchanged.
+ *      Inside a block the next history entry equals the accepted F_k bit for bit. Across an outer update F changes and it does not.
+ *   4. The weight and dose updates of the L-BFGS iteration unchanged.
+ * w_best and f_best are those of the current subproblem; with a monotone inner solver that is the current iterate after every
+ * accepted step. It notes its matrices and its objective at creation: rtd_optimizer_run refuses with RTD_ERR_NOT_READY, before its
+ * first launch, once a field's matrix has been computed again or a ROI, term or constraint has been added.
+ *
+ * rtd_optimizer_lbfgs_constraint_line  the device arrays the last line search left, read-only, no synchronisation:
+ *                          con_trial[k][0] = the terms' value at trial k, con_trial[k][1 + c] = psi_{c,k} (rows of
+ *                          1 + RTD_CON_MAX_CONSTRAINTS doubles), mean_trial[k][c] = m_{c,k} of a mean constraint (rows of
+ *                          RTD_CON_MAX_CONSTRAINTS doubles; +0 for a per-voxel constraint). RTD_ERR_INVALID_ARG on any other optimiser.
+ * rtd_objective_constraint_trials      the constraint half of the line search as a call of its own, on two float32 volumes and with
+ *                          the workspace of the objective (the optimiser calls the same internal function): dev_psi[k][c] = psi_{c,k}
+ *                          and dev_mean[k][c] = m_{c,k}, rows of RTD_CON_MAX_CONSTRAINTS doubles, for k < n_trials; entries past the
+ *                          objective's constraints, and dev_mean of a per-voxel constraint, are +0. dev_lambda and dev_mu as for
+ *                          rtd_objective_eval_constrained. After the first call it only launches. RTD_ERR_INVALID_ARG: n_trials
+ *                          outside 1 .. 8, rho not positive and finite, a NULL pointer, an objective without constraints.
+ *
+ * Out of scope: the robust, voxel-wise, 4D, plan-set, LET and RBE optimisers; DVH and EUD constraints;
+ * bounds or minimum-MU rules on the weights; an on-device stopping rule.
+ */
+typedef struct rtd_lbfgs_constraint_line_buffers {
+    const double* con_trial;    /* double[n_trials][1 + RTD_CON_MAX_CONSTRAINTS]: the terms' value, then psi_c */
+    const double* mean_trial;   /* double[n_trials][RTD_CON_MAX_CONSTRAINTS]: m_c of the mean constraints */
+    uint32_t n_trials, n_constraints;
+    uint32_t reserved[4];
+} rtd_lbfgs_constraint_line_buffers;   /* 40 bytes */
+int rtd_optimizer_create_constrained_lbfgs(rtd_handle h, const rtd_field* fields, uint32_t n_fields, rtd_objective obj, const rtd_lbfgs_options* o,
+                                           const rtd_constrained_options* c, uint32_t flags, rtd_optimizer* out);
+int rtd_optimizer_lbfgs_constraint_line(rtd_handle h, rtd_optimizer opt, rtd_lbfgs_constraint_line_buffers* b);
+int rtd_objective_constraint_trials(rtd_handle h, rtd_objective obj, const float* dev_d0, const float* dev_d1, uint32_t n_trials, const float* dev_lambda,
+                                    const double* dev_mu, double rho, double* dev_psi, double* dev_mean);
+
+/*
  * ---- Compact dose-influence matrix: fp16 values, 16-bit indices, products of its own ----
  *
  * Additive to the blocks above (RTD_ABI_VERSION stays 3; no entry point, kernel or structure above changes). The plain form of a

@@ -385,6 +385,14 @@ def default_constrained_options():
     return o
 
 
+class RtdLbfgsConstraintLineBuffers(C.Structure):
+    """rtd_lbfgs_constraint_line_buffers: what the last line search of a constrained L-BFGS optimiser left about the constraints:
+    con_trial double[n_trials][1 + RTD_CON_MAX_CONSTRAINTS] (the terms' value, then psi_c) and mean_trial
+    double[n_trials][RTD_CON_MAX_CONSTRAINTS] (40 bytes)."""
+    _fields_ = [("con_trial", C.c_void_p), ("mean_trial", C.c_void_p), ("n_trials", C.c_uint32), ("n_constraints", C.c_uint32),
+                ("reserved", C.c_uint32 * 4)]
+
+
 class RtdDijCompactOptions(C.Structure):
     """rtd_dij_compact_options: release_plain (1: free the plain form's bulk once the compact form stands) (32 bytes)."""
     _fields_ = [("release_plain", C.c_uint32), ("reserved", C.c_int32 * 7)]

@@ -167,6 +167,24 @@ int conCheckObjective(rtd_handle_impl* h, const std::string& who, const rtd_obje
     return RTD_OK;
 }
 
+// The ranges of rtd_constrained_options (copt may be nullptr: the defaults) -> *out.
+int conCheckOptions(rtd_handle_impl* h, const std::string& who, const rtd_constrained_options* copt, rtd_constrained_options* out) {
+    rtd_constrained_options co;
+    rtd_default_constrained_options(&co);
+    if (copt) co = *copt;
+    if (!(co.rho0 > 0.0) || !std::isfinite(co.rho0) || !(co.rho_max >= co.rho0) || !std::isfinite(co.rho_max))
+        return fail(h, RTD_ERR_INVALID_ARG, who + ": needs 0 < rho0 <= rho_max < inf");
+    if (!(co.rho_growth >= 1.0) || !std::isfinite(co.rho_growth)) return fail(h, RTD_ERR_INVALID_ARG, who + ": rho_growth must be at least 1 and finite");
+    if (!(co.violation_shrink > 0.0) || !(co.violation_shrink <= 1.0)) return fail(h, RTD_ERR_INVALID_ARG, who + ": violation_shrink must lie in (0, 1]");
+    if (!(co.feasibility_tol >= 0.0) || !std::isfinite(co.feasibility_tol)) return fail(h, RTD_ERR_INVALID_ARG, who + ": feasibility_tol must be 0 or positive and finite");
+    if (!(co.lambda_max > 0.0)) return fail(h, RTD_ERR_INVALID_ARG, who + ": lambda_max must be positive");
+    if (!co.inner_iterations) return fail(h, RTD_ERR_INVALID_ARG, who + ": inner_iterations must be at least 1");
+    for (int r : co.reserved)
+        if (r) return fail(h, RTD_ERR_INVALID_ARG, who + ": a reserved word is not zero");
+    *out = co;
+    return RTD_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -261,19 +279,10 @@ int rtd_optimizer_create_constrained(rtd_handle hh, const rtd_field* fields, uin
     if (out) *out = nullptr;
     if (!fields || !o || !out) return fail(h, RTD_ERR_INVALID_ARG, who + ": null pointer");
     rtd_constrained_options co;
-    rtd_default_constrained_options(&co);
-    if (copt) co = *copt;
-    if (!(co.rho0 > 0.0) || !std::isfinite(co.rho0) || !(co.rho_max >= co.rho0) || !std::isfinite(co.rho_max))
-        return fail(h, RTD_ERR_INVALID_ARG, who + ": needs 0 < rho0 <= rho_max < inf");
-    if (!(co.rho_growth >= 1.0) || !std::isfinite(co.rho_growth)) return fail(h, RTD_ERR_INVALID_ARG, who + ": rho_growth must be at least 1 and finite");
-    if (!(co.violation_shrink > 0.0) || !(co.violation_shrink <= 1.0)) return fail(h, RTD_ERR_INVALID_ARG, who + ": violation_shrink must lie in (0, 1]");
-    if (!(co.feasibility_tol >= 0.0) || !std::isfinite(co.feasibility_tol)) return fail(h, RTD_ERR_INVALID_ARG, who + ": feasibility_tol must be 0 or positive and finite");
-    if (!(co.lambda_max > 0.0)) return fail(h, RTD_ERR_INVALID_ARG, who + ": lambda_max must be positive");
-    if (!co.inner_iterations) return fail(h, RTD_ERR_INVALID_ARG, who + ": inner_iterations must be at least 1");
-    for (int r : co.reserved)
-        if (r) return fail(h, RTD_ERR_INVALID_ARG, who + ": a reserved word is not zero");
+    int st = conCheckOptions(h, who, copt, &co);
+    if (st != RTD_OK) return st;
     rtd_optimizer_options op;
-    int st = optCheckOptions(h, who, n_fields, opt, &op);
+    st = optCheckOptions(h, who, n_fields, opt, &op);
     if (st != RTD_OK) return st;
     for (uint32_t i = 0; i < n_fields; ++i) {
         st = optCheckField(h, who, reinterpret_cast<rtd_field_impl*>(fields[i]), o);

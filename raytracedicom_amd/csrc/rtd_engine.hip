@@ -59,6 +59,7 @@
 #include "rtd_planset.hpp"
 #include "rtd_lbfgs.hpp"
 #include "rtd_lbfgs_terms.hpp"
+#include "rtd_lbfgs_constrain.hpp"
 #include "rtd_field_memory.hpp"
 #include "rtd_field_matrix.hpp"
 #include "rtd_engine_impl.hpp"
@@ -1477,4 +1478,5 @@ int rtd_compute(rtd_handle hh, const rtd_beam* beams, int n_beams, float* dose_i
 #include "rtd_planset_host.hpp"
 #include "rtd_fourd_host.hpp"
 #include "rtd_lbfgs_host.hpp"
+#include "rtd_lbfgs_constrain_host.hpp"
 #include "rtd_dij_compact_host.hpp"

@@ -14,7 +14,7 @@
 //                   counters; k_lb_update / k_lb_update_dose carry the decision out per entry and per voxel of the fields' row boxes.
 // float64 wherever something is summed, no contraction, no atomics: every order follows from the shapes of the inputs alone. The
 // chunk tree is the optimiser's (k_opt_partials): lane t adds the entries t, t + 64, ... in order, butterfly 32 ... 1, and the chunk
-// sums are added the same way.
+// sums are added the same way. Included after rtd_constrain.hpp: lbDecide's constraint flag (section 32) reads its ConTab.
 #pragma once
 
 namespace rtd {
@@ -331,10 +331,41 @@ __global__ __launch_bounds__(256) void k_lb_line(const int* __restrict__ uv, con
 // gp from its chunk sums, then the decision. kEud: the share of an EUD term in F_k is eud[(k * kObjMaxTerms + t) * 3 + 2], the value
 // k_lb_eud_finish left for trial k (rtd_lbfgs_terms.hpp), as in objReduce<true>; without it nothing of this is compiled in, and eud is
 // not read. k_lb_decide is the kernel as it was; k_lb_decide_terms (rtd_lbfgs_terms.hpp) is the same body with kEud.
-template <bool kEud>
+// kCon (rtd_lbfgs_constrain.hpp, section 32): F_k also takes psi_{c,k} of the hard constraints, added in constraint order behind the
+// terms as k_con_reduce does; psi by k_con_reduce's tree and expressions from the block sums k_lb_con_line left. psiSh: LDS of the
+// kernel, [kConMax * kLbMaxTrials]. Without kCon nothing of this is compiled in, and con and psiSh are not read.
+struct LbCon {
+    const double* partial;        // [(c * nBlocks + block) * K + k], of k_lb_con_line
+    const double* mu;             // [kConMax]
+    const double* meanTrial;      // [k][2 kConMax]: m_{c,k}, then a_{c,k}, of k_lb_con_mean_finish
+    const double* rhoDev;
+    double* conTrial;             // [kLbMaxTrials][1 + kConMax]
+    double* meanOut;              // [kLbMaxTrials][kConMax]
+    ConTab tab;
+    int nBlocks, pad;
+};
+__device__ __forceinline__ void lbConPsi(const double* __restrict__ partial, int nBlocks, const ConTab& tab, int K, const double* __restrict__ mu,
+                                         const double* __restrict__ meanTrial, double rho, double* __restrict__ psiSh) {
+    const int lane = threadIdx.x % 64, wave = threadIdx.x / 64, nW = blockDim.x / 64;
+    for (int q = wave; q < tab.nC * K; q += nW) {                     // a wave per (constraint, trial) at a time
+        const int c = q / K, k = q % K;
+        double acc = 0.0;
+        if (!tab.mean[c]) {
+            for (int b = lane; b < nBlocks; b += 64) acc += partial[((size_t)c * nBlocks + b) * K + k];
+            acc = optWaveSum(acc);
+        }
+        if (lane == 0) {
+            double psi;
+            if (tab.mean[c]) { const double a = meanTrial[(size_t)k * 2 * kConMax + kConMax + c], m = mu[c]; psi = (a * a - m * m) / (2.0 * rho); }
+            else psi = acc * (tab.invN[c] / (2.0 * rho));
+            psiSh[q] = psi;
+        }
+    }
+}
+template <bool kEud, bool kCon = false>
 __device__ __forceinline__ void lbDecide(const double* __restrict__ partial, int nBlocks, const ObjTerm* __restrict__ terms, int nTerms,
                                          const double* __restrict__ gpPart, int nCh, OptState* __restrict__ st, LbState* __restrict__ lb, LbParams P,
-                                         const double* __restrict__ eud) {
+                                         const double* __restrict__ eud, const LbCon* con = nullptr, double* psiSh = nullptr) {
     __shared__ double sh[kObjMaxTerms * kLbMaxTrials];
     __shared__ double F[kLbMaxTrials];
     __shared__ double shGp;
@@ -356,10 +387,21 @@ __device__ __forceinline__ void lbDecide(const double* __restrict__ partial, int
         acc = optWaveSum(acc);
         if (lane == 0) shGp = acc;
     }
+    if (kCon) lbConPsi(con->partial, con->nBlocks, con->tab, K, con->mu, con->meanTrial, *con->rhoDev, psiSh);
     __syncthreads();
     if (threadIdx.x < K) {
         double f = 0.0;
         for (int t = 0; t < nTerms; ++t) f += sh[t * K + threadIdx.x];
+        if (kCon) {
+            const int k = threadIdx.x, nC = con->tab.nC;
+            con->conTrial[k * (1 + kConMax)] = f;
+            for (int c = 0; c < kConMax; ++c) {
+                const double psi = c < nC ? psiSh[c * K + k] : 0.0;
+                if (c < nC) f += psi;
+                con->conTrial[k * (1 + kConMax) + 1 + c] = psi;
+                con->meanOut[k * kConMax + c] = (c < nC && con->tab.mean[c]) ? con->meanTrial[(size_t)k * 2 * kConMax + c] : 0.0;
+            }
+        }
         F[threadIdx.x] = f;
     }
     __syncthreads();

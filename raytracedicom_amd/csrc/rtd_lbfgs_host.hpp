@@ -158,8 +158,9 @@ void rtd_default_lbfgs_options(rtd_lbfgs_options* o) {
 }
 
 // rtd_optimizer_create_lbfgs (ex == false: flags is 0, and an objective with DVH or EUD terms is refused) and _create_lbfgs_ex.
+// constrained: the caller is rtd_optimizer_create_constrained_lbfgs (rtd_lbfgs_constrain_host.hpp), whose objective has hard constraints.
 static int lbfgsCreate(rtd_handle hh, const std::string& who, bool ex, const rtd_field* fields, uint32_t n_fields, rtd_objective oo,
-                       const rtd_lbfgs_options* opt, uint32_t flags, rtd_optimizer* out) {
+                       const rtd_lbfgs_options* opt, uint32_t flags, rtd_optimizer* out, bool constrained = false) {
     auto* h = reinterpret_cast<rtd_handle_impl*>(hh);
     auto* o = reinterpret_cast<rtd_objective_impl*>(oo);
     if (!h) return RTD_ERR_INVALID_ARG;
@@ -188,7 +189,7 @@ static int lbfgsCreate(rtd_handle hh, const std::string& who, bool ex, const rtd
     if (!ex && o->hasDvhTerms()) return fail(h, RTD_ERR_INVALID_ARG, who + ": an objective with DVH terms has no K-wide line evaluation (D_v couples the voxels of a structure)");
     if (!ex && o->hasEudTerms()) return fail(h, RTD_ERR_INVALID_ARG, who + ": an objective with EUD terms has no K-wide line evaluation (E couples the voxels of a structure)");
     std::vector<int> offset;
-    st = optPrepare(hh, who, fields, n_fields, n_fields, o, &offset, compact);
+    st = optPrepare(hh, who, fields, n_fields, n_fields, o, &offset, compact, constrained);
     if (st != RTD_OK) return st;
 
     auto* p = new rtd_optimizer_impl();

@@ -38,7 +38,10 @@ struct rtd_objective_impl {
     bool conBuilt = false;
     int nCU = 0, nCBlocks = 0, nCEntries = 0, nCChMax = 1;   // union voxels, blocks of k_con_eval, CSR entries, chunks of the largest mean-constrained ROI
     ConTab conTab{};
-    struct Con { DevBuf<int> dUv, dPtr; DevBuf<unsigned char> dIdx; DevBuf<unsigned short> dMask; DevBuf<double> dPartial, dMeanPart, dMean, dMaxPart; DevBuf<unsigned> dCntPart; } con;
+    struct Con { DevBuf<int> dUv, dPtr; DevBuf<unsigned char> dIdx; DevBuf<unsigned short> dMask; DevBuf<double> dPartial, dMeanPart, dMean, dMaxPart; DevBuf<unsigned> dCntPart;
+                 // the K-wide line kernels' scratch (section 32; buildConstraintLine in rtd_lbfgs_constrain_host.hpp): the block sums
+                 // [kConMax][nCBlocks][8], the chunk sums [8][kConMax][nCChMax] and {m, a} [8][2 kConMax]
+                 DevBuf<double> dLinePart, dLineMeanPart, dLineMean; bool lineBuilt = false; } con;
     bool hasDvhTerms() const { for (double v : vfrac) if (v > 0.0) return true; return false; }
     bool hasEudTerms() const { for (double a : expo) if (a != 0.0) return true; return false; }
 };

@@ -86,6 +86,10 @@ struct rtd_optimizer_impl {
     DevBuf<ConState> dConState;
     DevBuf<ConViolation> dConViol;
     DevBuf<ConOuter> dConOuter;
+    // A constrained L-BFGS optimiser (section 32; rtd_optimizer_create_constrained_lbfgs in rtd_lbfgs_constrain_host.hpp): `lbfgs` and
+    // `constrained` both set, the buffers of both kinds, and per trial of the last line search {terms' value, psi_c} [8][1 + kConMax]
+    // and the means of the mean constraints [8][kConMax].
+    DevBuf<double> dLbConTrial, dLbConMean;
     rtd_field_impl* const* row(int s) const { return sfields.data() + (size_t)s * fields.size(); }
     rtd_field_impl* sf(int s, size_t i) const { return row(s)[i]; }
     float* w() const { return dVec; }
@@ -135,6 +139,8 @@ int lbfgsRun(rtd_handle hh, rtd_optimizer_impl* p, uint32_t n_iterations);
 int lbfgsWeightsSet(rtd_handle_impl* h, rtd_optimizer_impl* p);
 // Section 31 (rtd_constrain_host.hpp, included later): the iteration of a constrained optimiser.
 int constrainedRun(rtd_handle hh, rtd_optimizer_impl* p, uint32_t n_iterations);
+// Section 32 (rtd_lbfgs_constrain_host.hpp, included later): the iteration of a constrained L-BFGS optimiser.
+int constrainedLbfgsRun(rtd_handle hh, rtd_optimizer_impl* p, uint32_t n_iterations);
 // Section 28 (rtd_dij_compact_host.hpp, included later): the row pointers the compact companion side reads.
 const long long* compactRowPtr(const rtd_field_impl* f);
 
@@ -538,6 +544,7 @@ int rtd_optimizer_run(rtd_handle hh, rtd_optimizer pp, uint32_t n_iterations) {
     if (!h) return RTD_ERR_INVALID_ARG;
     if (!p) return fail(h, RTD_ERR_INVALID_ARG, "rtd_optimizer_run: null pointer");
     if (p->obj->terms.empty()) return fail(h, RTD_ERR_INVALID_ARG, "rtd_optimizer_run: the objective has no terms");
+    if (p->lbfgs && p->constrained) return constrainedLbfgsRun(hh, p, n_iterations);
     if (p->lbfgs) return lbfgsRun(hh, p, n_iterations);
     if (p->constrained) return constrainedRun(hh, p, n_iterations);
     if (p->letObj || p->rbe)                                          // (in front of the first launch: a refused run launches nothing)

@@ -189,6 +189,9 @@ def lib():
         L.rtd_optimizer_create_constrained.argtypes = [vp, vpp, C.c_uint32, vp, C.POINTER(abi.RtdOptimizerOptions), C.POINTER(abi.RtdConstrainedOptions), vpp]
         L.rtd_optimizer_constraint_report.argtypes = [vp, vp, C.POINTER(abi.RtdConstraintReport), C.POINTER(abi.RtdConstraintOuter), C.c_uint32]
         L.rtd_optimizer_constraint_buffers.argtypes = [vp, vp, C.POINTER(abi.RtdConstraintBuffers)]
+        L.rtd_optimizer_create_constrained_lbfgs.argtypes = [vp, vpp, C.c_uint32, vp, C.POINTER(abi.RtdLbfgsOptions), C.POINTER(abi.RtdConstrainedOptions), C.c_uint32, vpp]
+        L.rtd_optimizer_lbfgs_constraint_line.argtypes = [vp, vp, C.POINTER(abi.RtdLbfgsConstraintLineBuffers)]
+        L.rtd_objective_constraint_trials.argtypes = [vp, vp, vp, vp, C.c_uint32, vp, vp, C.c_double, vp, vp]
         L.rtd_default_dij_compact_options.argtypes = [C.POINTER(abi.RtdDijCompactOptions)]
         L.rtd_default_dij_compact_options.restype = None
         L.rtd_field_dose_influence_compact.argtypes = [vp, vp, C.POINTER(abi.RtdDijCompactOptions)]
@@ -714,6 +717,28 @@ class Objective:
                 self.eng.device_free(buf)
         return None
 
+    def constraint_trials(self, dev_d0, dev_d1, n_trials, dev_lambda, dev_mu, rho, dev_psi=None, dev_mean=None):
+        """rtd_objective_constraint_trials: the constraint half of an L-BFGS line search on the float32 trial volumes r_k formed from
+        dev_d0 and dev_d1, k < n_trials: psi[k][c] and the means mean[k][c] (rows of abi.RTD_CON_MAX_CONSTRAINTS float64). With dev_psi
+        and dev_mean (device pointers) asynchronous, returns None; without, returns (psi, mean) as float64[n_trials][16]."""
+        own = dev_psi is None or dev_mean is None
+        nb = 8 * abi.RTD_CON_MAX_CONSTRAINTS * max(1, int(n_trials))
+        buf = self.eng.device_alloc(2 * nb) if own else None
+        dp, dm = (buf, buf + nb) if own else (dev_psi, dev_mean)
+        try:
+            self.eng._check(lib().rtd_objective_constraint_trials(self.eng._h, self._h, C.c_void_p(int(dev_d0)), C.c_void_p(int(dev_d1)), int(n_trials),
+                                                                  C.c_void_p(int(dev_lambda)), C.c_void_p(int(dev_mu)), float(rho), C.c_void_p(int(dp)), C.c_void_p(int(dm))))
+            if own:
+                psi = np.empty((int(n_trials), abi.RTD_CON_MAX_CONSTRAINTS), dtype=np.float64)
+                mean = np.empty_like(psi)
+                self.eng.to_host(psi, dp)
+                self.eng.to_host(mean, dm)
+                return psi, mean
+        finally:
+            if own:
+                self.eng.device_free(buf)
+        return None
+
     def _violations(self, call, dev_out):
         own = dev_out is None
         do = self.eng.device_alloc(16 * abi.RTD_CON_MAX_CONSTRAINTS) if own else dev_out
@@ -954,7 +979,8 @@ class Optimizer:
         scenario_fields the robust or voxel-wise one on them (rtd_optimizer_create_robust_compact, _create_voxelwise_compact). With
         lbfgs=True and lbfgs_flags (an int, abi.RTD_LBFGS_COMPACT or 0) it is rtd_optimizer_create_lbfgs_ex: L-BFGS on an objective
         of any term kind, on the compact matrices with the flag. With constrained (an abi.RtdConstrainedOptions, or True for the
-        defaults) it is the augmented Lagrangian of rtd_optimizer_create_constrained on an objective that has hard constraints."""
+        defaults) it is the augmented Lagrangian of rtd_optimizer_create_constrained on an objective that has hard constraints; with
+        lbfgs=True beside it, the one of rtd_optimizer_create_constrained_lbfgs (options: an abi.RtdLbfgsOptions or None)."""
         self.eng = eng
         self.objective = objective
         self._h = C.c_void_p()
@@ -966,6 +992,10 @@ class Optimizer:
             arr = (C.c_void_p * max(1, len(self.fields)))(*[f._h for f in self.fields])
             if constrained is not None and constrained is not False:
                 pc = C.byref(constrained) if isinstance(constrained, abi.RtdConstrainedOptions) else None
+                if lbfgs:
+                    eng._check(lib().rtd_optimizer_create_constrained_lbfgs(eng._h, arr, len(self.fields), objective._h, po, pc, int(lbfgs_flags or 0),
+                                                                            C.byref(self._h)))
+                    return
                 eng._check(lib().rtd_optimizer_create_constrained(eng._h, arr, len(self.fields), objective._h, po, pc, C.byref(self._h)))
                 return
             if lbfgs and lbfgs_flags is not None:
@@ -1076,6 +1106,14 @@ class Optimizer:
         {E, K, value} double[n_trials][RTD_OBJ_MAX_TERMS][3] (None without such terms)."""
         b = abi.RtdLbfgsLineBuffers()
         self.eng._check(lib().rtd_optimizer_lbfgs_line_buffers(self.eng._h, self._h, C.byref(b)))
+        return b
+
+    def lbfgs_constraint_line(self):
+        """rtd_optimizer_lbfgs_constraint_line: the device arrays the last line search of a constrained L-BFGS optimiser left
+        (abi.RtdLbfgsConstraintLineBuffers): con_trial[k] = (the terms' value, psi_c ...) and mean_trial[k][c]. No synchronisation. Only
+        on an optimiser from Engine.create_constrained_lbfgs_optimizer (RtdError INVALID_ARG otherwise)."""
+        b = abi.RtdLbfgsConstraintLineBuffers()
+        self.eng._check(lib().rtd_optimizer_lbfgs_constraint_line(self.eng._h, self._h, C.byref(b)))
         return b
 
     def constraint_report(self):
@@ -1394,6 +1432,15 @@ class Engine:
         of the line search, on the float32-rounded trial volume); compact=True: its products read the fields' compact matrices
         (Field.dose_influence_compact first; works after release_plain). It also has .lbfgs_line_buffers()."""
         return Optimizer(self, fields, objective, options, lbfgs=True, lbfgs_flags=abi.RTD_LBFGS_COMPACT if compact else 0)
+
+    def create_constrained_lbfgs_optimizer(self, fields, objective, lbfgs_options=None, constrained_options=None, compact=False):
+        """rtd_optimizer_create_constrained_lbfgs: an Optimizer whose iteration is the augmented Lagrangian around L-BFGS, the outer
+        update at the current iterate; the objective needs a term (any kind) and a constraint. lbfgs_options: an abi.RtdLbfgsOptions or
+        None; constrained_options: an abi.RtdConstrainedOptions or None; compact=True: the products read the fields' compact matrices.
+        It has .lbfgs_report(), .lbfgs_buffers(), .lbfgs_line_buffers(), .lbfgs_constraint_line(), .constraint_report() and
+        .constraint_buffers()."""
+        return Optimizer(self, fields, objective, lbfgs_options, lbfgs=True, lbfgs_flags=abi.RTD_LBFGS_COMPACT if compact else 0,
+                         constrained=constrained_options if constrained_options is not None else True)
 
     def create_constrained_optimizer(self, fields, objective, options=None, constrained=None):
         """rtd_optimizer_create_constrained: an Optimizer whose iteration is the augmented Lagrangian around the spectral one, on an
